@@ -1,8 +1,15 @@
 #!/usr/bin/env python3
 """Headline benchmark: WordCount Map/Process/Reduce on MI355X (BASELINE.json).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
                     [--config hamlet4500|hamlet700|synth1m|synth10g]
+
+A plain run sets up, warms up, times the K steps and prints the result line: nothing else.
+``--full`` adds every side measurement to the line (the per-stage split, 700 lines, the
+untuned and radix paths, cold starts, the reference's timer semantics, the CPU pipeline,
+``synth1m``; at N > 1 the shuffle path and the ``synth1m`` strong-scaling point).
+``--dump-outputs DIR`` writes the result of the last timed step (what a caller of the job
+receives: the sorted keys, their counts and vals) as ``DIR/<name>.npy``.
 
 One "step" is one complete WordCount job: H2D of the text, Map (tokenize/emit), Process
 (compaction + radix sort), Reduce (boundary mark + head compaction + adjacent difference)
@@ -20,8 +27,8 @@ GPU of its own fails the run: a job never silently reports fewer GPUs than asked
 
 Headline (``value``): whole Hamlet, weak scaling -- every rank maps its own copy of the
 text, the ranks merge their combined (key, count) records on rank 0 (the gather strategy:
-one all-gather of device-written slots, one root merge).  The ``synth1m`` extra, at every
-N including 1, is BASELINE config 4 as strong scaling: 1M synthetic lines in total, 1/N per
+one all-gather of device-written slots, one root merge).  The ``synth1m`` extra (``--full``),
+at every N including 1, is BASELINE config 4 as strong scaling: 1M synthetic lines in total, 1/N per
 rank, range-partitioned by sample-sort splitters and exchanged over xGMI (one fixed-slot
 ``ncclAllToAll`` in steady state), every rank writing its key range into the shared host
 output over its own PCIe link, so N = 1, 2, 4, 8 form one curve.  Steps are timed between
@@ -102,11 +109,15 @@ def _nlines(text: bytes) -> int:
     return text.count(b"\n") + (0 if text.endswith(b"\n") else 1)
 
 
-def bench_single(text, steps: int, warmup: int, sort: str = "dict", graph: int = -1):
+def bench_single(text, steps: int, warmup: int, sort: str = "dict", graph: int = -1,
+                 stages: bool = True):
     """Whole-job time of `steps` back-to-back jobs, plus the median per-stage split from a
     short run with per-stage device events (graph=0).  The timed jobs carry no stage
     timestamps: small ones are lean direct launches with a polled completion word, and
-    events would cost them more than a stage takes; timed_* are their own medians."""
+    events would cost them more than a stage takes; timed_* are their own medians.
+    stages=False: the timed jobs alone (a plain run), no stage split."""
+    if not stages:
+        return _time_single(text, steps, warmup, sort, graph, stages=False)
     ms, gst, res = _time_single(text, steps, warmup, sort, graph)
     _, stages, _ = _time_single(text, min(steps, 30), min(warmup, 5), sort, 0)
     stages["timed_gpu_ms"] = gst["gpu_ms"]
@@ -177,7 +188,7 @@ def cold_first_run(text) -> dict:
             "third_job_ms": round((t[3] - t[2]) * 1e3, 4)}
 
 
-def _time_single(text, steps: int, warmup: int, sort: str, graph: int):
+def _time_single(text, steps: int, warmup: int, sort: str, graph: int, stages: bool = True):
     import locust_amd as lc
 
     size = len(text) if isinstance(text, bytes) else text.size
@@ -204,6 +215,8 @@ def _time_single(text, steps: int, warmup: int, sort: str, graph: int):
         res = run()
     t1 = time.perf_counter()
     ms = (t1 - t0) * 1e3 / steps
+    if not stages:
+        return ms, {}, res
     stage = {"map_ms": [], "process_ms": [], "reduce_ms": [], "h2d_ms": [], "d2h_ms": [],
              "gpu_ms": [], "wall_ms": []}
     for _ in range(min(steps, 50)):
@@ -212,6 +225,39 @@ def _time_single(text, steps: int, warmup: int, sort: str, graph: int):
             stage[k].append(t[k])
     med = {k: statistics.median(v) for k, v in stage.items()}
     return ms, med, res
+
+
+DUMP_MAX_ROWS = 400_000  # x (32 key bytes as float32 + count + val as float64) = 57.6 MB
+DUMP_SEED = 20240607
+
+
+def dump_outputs(res, out_dir: str) -> None:
+    """What the job's caller receives, as .npy arrays: `keys` (float32, one row of
+    kKeyBytes = 32 zero-padded bytes per entry, in result order), `counts` and `vals`
+    (float64) and `totals` (float64: tokens, distinct keys).  A result of more than
+    DUMP_MAX_ROWS entries is sampled: a fixed, seeded choice of rows (kept in order, the
+    row numbers in `rows`), so the files stay below 64 MB and two builds dump the same rows."""
+    import numpy as np
+
+    entries = res.entries()
+    n = len(entries)
+    rows = np.arange(n, dtype=np.int64)
+    if n > DUMP_MAX_ROWS:
+        rows = np.sort(np.random.default_rng(DUMP_SEED).choice(n, DUMP_MAX_ROWS, replace=False))
+    keys = np.zeros((len(rows), 32), dtype=np.float32)
+    counts = np.zeros(len(rows), dtype=np.float64)
+    vals = np.zeros(len(rows), dtype=np.float64)
+    for i, r in enumerate(rows.tolist()):
+        k, v, c = entries[r]
+        keys[i, :len(k)] = np.frombuffer(k[:32], dtype=np.uint8)
+        vals[i], counts[i] = v, c
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "keys.npy"), keys)
+    np.save(os.path.join(out_dir, "counts.npy"), counts)
+    np.save(os.path.join(out_dir, "vals.npy"), vals)
+    np.save(os.path.join(out_dir, "rows.npy"), rows.astype(np.float64))
+    np.save(os.path.join(out_dir, "totals.npy"),
+            np.array([res.num_tokens, res.num_unique], dtype=np.float64))
 
 
 def untuned(text: bytes, steps: int, warmup: int) -> dict:
@@ -664,8 +710,16 @@ def main() -> int:
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--config", default="hamlet4500",
                     choices=sorted(BASELINE_MS) + sorted(SYNTH))
+    ap.add_argument("--full", action="store_true",
+                    help="also run the side measurements (the per-stage split, 700 lines, "
+                         "untuned, radix path, cold starts, CPU pipeline, synth1m, ...); "
+                         "a plain run times the headline steps only")
     ap.add_argument("--no-extra", action="store_true",
-                    help="skip the side measurements (700 lines, radix path, synth1m, ...)")
+                    help="with --full: keep the per-stage split, skip the other side "
+                         "measurements (a plain run has none to skip)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's result as DIR/<name>.npy "
+                         "(keys, counts, vals, rows, totals)")
     ap.add_argument("--comm", default="rccl", choices=["rccl", "tcp", "tcpdev"],
                     help="communicator for N>1 (tcp: rehearsal with ranks sharing one GPU)")
     ap.add_argument("--backend", default="gpu", choices=["gpu", "cpu"],
@@ -684,6 +738,9 @@ def main() -> int:
                     help="watchdog: a run still going after this many seconds ends with one "
                          "failure line (status 'failed', every rank's last stage); 0: off")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    extras = args.full and not args.no_extra  # the side measurements beyond the stage split
     if args.backend == "cpu" and args.comm == "rccl" and args.gpus > 1:
         ap.error("--backend cpu needs --comm tcp")
 
@@ -733,14 +790,18 @@ def main() -> int:
         import locust_amd as lc
 
         res = lc._C.cpu_run(lc.make_config("cpu"), text)
+        if args.dump_outputs:
+            dump_outputs(res, args.dump_outputs)
     elif n == 1 and not args.force_dist:
         stamp("single:headline")
-        if synth and not args.no_extra:
+        if synth and extras:
             extra["cold_start"] = cold_first_run(text)  # before any warm engine exists
-        ms, stages, res = bench_single(text, args.steps, args.warmup)
+        ms, stages, res = bench_single(text, args.steps, args.warmup, stages=args.full)
         _PARTIAL["partial"] = {"ms_per_step": round(ms, 4)}
+        if args.dump_outputs:
+            dump_outputs(res, args.dump_outputs)
         stamp("single:extras")
-        if not args.no_extra and args.config == "hamlet4500":
+        if extras and args.config == "hamlet4500":
             ms700, st700, _ = bench_single(load_text("hamlet700"), args.steps, args.warmup)
             extra["hamlet700"] = {"ms_per_step": round(ms700, 4), "vs_baseline":
                                   round(ms700 / BASELINE_MS["hamlet700"], 6),
@@ -773,10 +834,12 @@ def main() -> int:
         stamp("headline")
         ms, stages, res, strategy = time_dist(dr, args.steps, args.warmup, args.strategy)
         _PARTIAL["partial"] = {"ms_per_step": round(ms, 4), "strategy": strategy}
+        if args.dump_outputs and rank == 0:
+            dump_outputs(res, args.dump_outputs)
         stamp("scale_diag")
         extra["scale_diag"] = scale_diag(dr, args, local_rank, nccl_dir)
         _PARTIAL["scale_diag"] = extra["scale_diag"]
-        if not args.no_extra and args.strategy == "auto" and strategy != "shuffle":
+        if extras and args.strategy == "auto" and strategy != "shuffle":
             # The sample-sort all-to-all shuffle on the same job (the path large inputs
             # take), so every scaling run also records the all-to-all path.
             ks, kw = (args.steps, args.warmup) if not synth else (min(args.steps, 10),
@@ -789,7 +852,7 @@ def main() -> int:
             except Exception as e:  # noqa: BLE001
                 print(f"rank {rank}: shuffle extra failed: {e}", file=sys.stderr)
                 extra["shuffle_path"] = {"error": str(e)[:300]}
-        if not args.no_extra and not synth:
+        if extras and not synth:
             stamp("extra:synth1m")
             extra["synth1m"] = synth_point(args, rank, n, dr)
     stamp("done")
@@ -846,7 +909,8 @@ def main() -> int:
         },
         "baseline_ms": round(base, 3),
         "baseline_stages_ms": baseline_stages,
-        "stages_ms_median": {k: round(v, 4) for k, v in stages.items()},
+        # N = 1 GPU: a run of its own with per-stage device events (--full); None in a plain run
+        "stages_ms_median": {k: round(v, 4) for k, v in stages.items()} if stages else None,
         "tokens": res.num_tokens,
         "unique": res.num_unique,
         # bytes the device wrote into host memory per result key (compact records: a header

@@ -34,7 +34,31 @@ def test_bench_single_gpu_line():
 
 
 def test_bench_synth_cold_start_line():
-    d = _run("--config", "synth1m", "--steps", "3", "--warmup", "1")
+    d = _run("--config", "synth1m", "--steps", "3", "--warmup", "1", "--full")
     assert d["unique"] == 202645 and d["scaling"] == "strong"
     cs = d["cold_start"]
     assert cs["first_job_ms"] > 0 and cs["third_job_ms"] > 0
+
+
+def test_bench_plain_run_is_lean_and_dumps_outputs(hamlet, tmp_path):
+    """A plain run times the headline steps only (no side measurement in the line) and
+    --dump-outputs writes the last timed step's result: the oracle's entries."""
+    import numpy as np
+
+    from locust_amd.utils import oracle
+
+    d = _run("--gpus", "1", "--steps", "7", "--warmup", "2", "--dump-outputs", str(tmp_path / "o"))
+    assert d["steps"] == 7 and d["value"] == d["ms_per_step"] > 0
+    assert d["stages_ms_median"] is None
+    for k in ("hamlet700", "untuned", "radix_path", "cold_start", "reference_semantics_ms",
+              "cpu_path", "synth1m"):
+        assert k not in d, k
+    ent, ntok, _ = oracle.wordcount(hamlet)
+    keys, counts, vals, rows, totals = (np.load(tmp_path / "o" / f"{n}.npy") for n in
+                                        ("keys", "counts", "vals", "rows", "totals"))
+    assert keys.dtype == np.float32 and keys.shape == (len(ent), 32)
+    assert counts.dtype == vals.dtype == rows.dtype == totals.dtype == np.float64
+    assert totals.tolist() == [ntok, len(ent)] and rows.tolist() == list(range(len(ent)))
+    got = [(bytes(keys[i].astype(np.uint8)).rstrip(b"\0"), int(vals[i]), int(counts[i]))
+           for i in range(len(ent))]
+    assert got == ent

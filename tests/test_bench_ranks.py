@@ -24,7 +24,7 @@ def _bench(*args, timeout=240):
 @pytest.mark.parametrize("world", [2, 3])
 def test_self_spawned_ranks_relay_one_line(hamlet, world):
     p = _bench("--gpus", str(world), "--backend", "cpu", "--comm", "tcp", "--steps", "3",
-               "--warmup", "1", "--synth-lines", "12000")
+               "--warmup", "1", "--synth-lines", "12000", "--full")
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1, p.stdout
@@ -74,3 +74,25 @@ def test_failed_rank_fails_the_run():
     d = json.loads(lines[0])
     assert d["status"] == "failed" and d["value"] is None and "rank" in d["reason"]
     assert sorted(d["progress"]) == ["0", "1"]
+
+
+def test_dump_outputs_cpu_backend(hamlet, tmp_path):
+    """--dump-outputs on the CPU rehearsal path: the .npy arrays are the oracle's entries,
+    float32 / float64, and two runs with the same arguments write the same bytes."""
+    import numpy as np
+
+    names = ("keys", "counts", "vals", "rows", "totals")
+    for sub in ("a", "b"):
+        p = _bench("--gpus", "1", "--backend", "cpu", "--steps", "2", "--warmup", "1",
+                   "--dump-outputs", str(tmp_path / sub), timeout=120)
+        assert p.returncode == 0, p.stderr[-3000:]
+    a = {n: np.load(tmp_path / "a" / f"{n}.npy") for n in names}
+    for n in names:
+        assert (tmp_path / "a" / f"{n}.npy").read_bytes() == (tmp_path / "b" / f"{n}.npy").read_bytes()
+    ent, ntok, _ = oracle.wordcount(hamlet)
+    assert a["keys"].dtype == np.float32 and a["keys"].shape == (len(ent), 32)
+    assert all(a[n].dtype == np.float64 for n in names[1:])
+    assert a["totals"].tolist() == [ntok, len(ent)]
+    got = [(bytes(a["keys"][i].astype(np.uint8)).rstrip(b"\0"), int(a["vals"][i]), int(a["counts"][i]))
+           for i in range(len(ent))]
+    assert got == ent

@@ -47,8 +47,9 @@ def _port() -> int:
 
 
 @needs_peers
-@pytest.mark.parametrize("world", sorted({2, WORLD}))
+@pytest.mark.parametrize("world", [2, "all"])  # fixed ids: the same on every machine
 def test_rccl_multiprocess_strategies(world):
+    world = WORLD if world == "all" else world
     port = _port()
     procs = []
     for r in range(world):
@@ -88,7 +89,7 @@ def test_bench_torchrun_world():
     p = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1",
                         f"--nproc-per-node={WORLD}", "--master-addr", "127.0.0.1",
                         "--master-port", str(port), "bench.py", "--gpus", str(WORLD),
-                        "--steps", "20", "--warmup", "5"],
+                        "--steps", "20", "--warmup", "5", "--full"],
                        cwd=lc.REPO_ROOT, capture_output=True, text=True, timeout=110)
     assert p.returncode == 0, p.stderr[-3000:]
     line = json.loads(p.stdout.strip().splitlines()[-1])

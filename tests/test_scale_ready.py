@@ -116,7 +116,8 @@ def _check_cli(out: bytes, rec: dict, path, gpus: int, device: bool):
 def test_bench_synth10g_cpu_ranks():
     total = 20_000_000
     d = _line(_bench("--config", "synth10g", "--synth-bytes", str(total), "--gpus", "2",
-                     "--backend", "cpu", "--comm", "tcp", "--steps", "2", "--warmup", "1"))
+                     "--backend", "cpu", "--comm", "tcp", "--steps", "2", "--warmup", "1",
+                     "--full"))
     want = _synth10g_want(total, 2)
     assert d["n_gpus"] == 2 and d["scaling"] == "strong"
     assert d["unique"] == want.num_unique and d["tokens"] == want.num_tokens
@@ -125,7 +126,7 @@ def test_bench_synth10g_cpu_ranks():
 @pytest.mark.parametrize("world", [2, 3])
 def test_bench_cpu_tcp_twin_diagnoses_itself(world, tmp_path):
     d = _line(_bench("--gpus", str(world), "--backend", "cpu", "--comm", "tcp", "--steps", "3",
-                     "--warmup", "1", "--synth-lines", "20000"))
+                     "--warmup", "1", "--synth-lines", "20000", "--full"))
     check_scale_diag(d, world, "tcp", gpu=False)
     # the report tool turns lines into the scaling table
     f = tmp_path / "scale.json"
@@ -155,7 +156,7 @@ def test_cli_cpu_ranks_synth_file(tmp_path, cli, gpus):
 @pytest.mark.gpu
 def test_bench_self_spawned_tcpdev_one_gpu():
     d = _line(_bench("--gpus", "2", "--comm", "tcpdev", "--steps", "5", "--warmup", "2",
-                     "--synth-lines", "100000"))
+                     "--synth-lines", "100000", "--full"))
     assert d["n_gpus"] == 2 and d["synth1m"]["n_gpus"] == 2
     check_scale_diag(d, 2, "tcpdev", gpu=True)
     whole = lc._C.HostText.generate(lines=100000, seed=1, first_block=0).to_bytes()
@@ -181,7 +182,7 @@ needs_peers = pytest.mark.skipif(WORLD < 2, reason="needs >= 2 GPUs (RCCL: one r
 @pytest.mark.gpu
 @needs_peers
 def test_bench_self_spawned_rccl_world():
-    d = _line(_bench("--gpus", str(WORLD), "--steps", "5", "--warmup", "2"))
+    d = _line(_bench("--gpus", str(WORLD), "--steps", "5", "--warmup", "2", "--full"))
     assert d["n_gpus"] == WORLD and d["rccl_ranks"] == WORLD
     check_scale_diag(d, WORLD, "rccl", gpu=True)
     assert d["synth1m"]["n_gpus"] == WORLD and d["synth1m"]["unique"] == SYNTH1M_UNIQUE
@@ -192,7 +193,7 @@ def test_bench_self_spawned_rccl_world():
 @needs_peers
 def test_bench_synth10g_rccl_world():
     d = _line(_bench("--config", "synth10g", "--gpus", str(WORLD), "--steps", "2", "--warmup", "1",
-                     timeout=900))
+                     "--full", timeout=900))
     assert d["n_gpus"] == WORLD and d["rccl_ranks"] == WORLD and d["value"] > 0
 
 

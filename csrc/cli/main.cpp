@@ -14,6 +14,7 @@
 //   --export-kiv FILE (results as the reference's 40-B KeyIntValuePair records)
 //   --warmup N  --iters N  --json FILE  --quiet  --check  --device N  --chunk-mb N
 //   --ref-timers (stage times taken where the reference's host timers were)
+//   --top K (the K most frequent words instead of the whole dictionary, rank order)
 // and a synthetic-text generator (BASELINE configs "1M lines" / "10 GB"):
 //   MapReduce --gen FILE (--gen-lines N | --gen-bytes N) [--seed S] [--vocab V]
 #include <sys/stat.h>
@@ -77,6 +78,7 @@ struct CliArgs {
   std::string json;
   std::string export_kiv;  // final results as KeyIntValuePair records (--export-kiv FILE)
   bool quiet = false;
+  u64 top = 0;  // --top K: the result lines are the K most frequent words (0: all)
   std::string gen_out;  // generator mode
   GenSpec gen;
 };
@@ -104,9 +106,12 @@ void help() {
       "  --output-format gpu|cpu    (result lines with val, or the CPU build's)\n"
       "  --export-kiv FILE          --json FILE|-              --quiet --check --combine\n"
       "  --warmup N --iters N       --chunk-mb N               --ref-timers\n"
+      "  --top K                    (only the K most frequent words, count descending, ties\n"
+      "                             by key; selected on the device on one GPU, K <= %u)\n"
       "  --help\n"
       "\n"
-      "Environment: LOCUST_LOG=info|debug and the LOCUST_* switches in docs/ENVIRONMENT.md.\n");
+      "Environment: LOCUST_LOG=info|debug and the LOCUST_* switches in docs/ENVIRONMENT.md.\n",
+      (unsigned)kTopKMax);
 }
 
 std::vector<std::string> split(const std::string& s, char c) {
@@ -215,6 +220,12 @@ bool parse(int argc, char** argv, CliArgs* a) {
       a->quiet = true;
     } else if (s == "--ref-timers") {
       a->cfg.ref_timers = true;
+    } else if (s == "--top") {
+      const std::string v = need("--top");
+      char* endp = nullptr;
+      const long long k = std::strtoll(v.c_str(), &endp, 10);
+      if (v.empty() || *endp || k < 1) throw Error("--top K needs an integer K >= 1");
+      a->top = (u64)k;
     } else if (s == "--chunk-mb") {
       a->cfg.chunk_bytes = (u64)std::atoll(need("--chunk-mb").c_str()) << 20;
     } else if (s == "--gen") {
@@ -247,6 +258,13 @@ bool parse(int argc, char** argv, CliArgs* a) {
   if (pos.size() > 3) {
     a->node = (int)std::strtol(pos[3].c_str(), nullptr, 10);
     if (pos.size() > 4) a->stage = (int)std::strtol(pos[4].c_str(), nullptr, 10);
+  }
+  if (a->top) {
+    if (a->stage == 1) throw Error("--top selects from a result: not with stage 1 (map only)");
+    if (!a->export_kiv.empty()) throw Error("--top and --export-kiv do not combine");
+    if (a->cfg.ref_timers) throw Error("--top and --ref-timers do not combine");
+    if (a->cfg.backend == Backend::kGpu && a->cfg.sort_path == SortPath::kRadix)
+      throw Error("--top on the GPU needs the dictionary path (--sort dict)");
   }
   if (a->byte_range) {
     if (a->stage != 1) throw Error("--byte-range is a stage-1 (map) flag");
@@ -362,6 +380,32 @@ void json_hbm(JsonOut& j, const GpuWordCount::Stats& s) {
   j.u("device_map_window", s.map_window);
 }
 
+// --top K: "top_k" in every mode's record, and where the device selected (one GPU) its
+// device time and the bytes it wrote to host memory for the result.
+const TopResult* g_top_device = nullptr;
+void json_top(JsonOut& j, const CliArgs& a) {
+  if (!a.top) return;
+  j.u("top_k", a.top);
+  if (g_top_device) {
+    j.num("select_ms", g_top_device->select_ms);
+    j.u("wire_bytes", g_top_device->wire_bytes);
+  }
+}
+
+// The statistics of a top result as a WordCountResult without entries (json, timer lines).
+WordCountResult top_stats(const TopResult& t) {
+  WordCountResult r;
+  r.num_lines = t.num_lines;
+  r.num_tokens = t.num_tokens;
+  r.num_unique = t.num_unique;
+  r.overflow_lines = t.overflow_lines;
+  r.truncated = t.truncated;
+  r.max_key_len = t.max_key_len;
+  r.chunks = t.chunks;
+  r.times = t.times;
+  return r;
+}
+
 void write_json(const CliArgs& a, const WordCountResult& r, const std::vector<double>& walls) {
   if (a.json.empty()) return;
   std::vector<double> w = walls;
@@ -380,6 +424,7 @@ void write_json(const CliArgs& a, const WordCountResult& r, const std::vector<do
   j.num("wall_ms_median", med);
   j.kv("iters", std::to_string(w.size()));
   j.u("chunks", r.chunks);
+  json_top(j, a);
   if (g_part_map) j.str("part_map", g_part_map);  // the one-shot CLI's starting map
   if (g_engine_stats_set) json_hbm(j, g_engine_stats);
   // peak resident memory of this process image (VmHWM: unlike getrusage's ru_maxrss it is
@@ -415,6 +460,7 @@ void write_json_dist(const CliArgs& a, const DistResult& root, const std::vector
                     : root.strategy == DistStrategy::kLocal   ? "local"
                                                               : "shuffle");
   j.num("wall_ms", root.total_ms);
+  json_top(j, a);
   j.str("comm", !ranks.empty() && ranks[0].rccl_clique ? "rccl" : "loopback");
   j.u("peak_rss_kb", peak_rss_kb());
   {  // page-locked host memory: every rank's engine, plus the shared output block once
@@ -513,6 +559,21 @@ void format_results(const CliArgs& a, bool cpu_default, const WordCountResult& r
   (cpu ? format_cpu_output : format_gpu_output)(r, out);
 }
 
+// --top K: the same lines for the K winners only, in rank order.
+void format_top(const CliArgs& a, bool cpu_default, const TopResult& t, std::string* out) {
+  if (a.quiet) return;
+  const bool cpu = a.out_format ? a.out_format == 2 : cpu_default;
+  format_top_output(t, cpu, out);
+}
+// ... selected on the host from a complete result (multi-rank jobs, stage 2, the CPU).
+void format_results_or_top(const CliArgs& a, bool cpu_default, const WordCountResult& r,
+                           std::string* out) {
+  if (a.top)
+    format_top(a, cpu_default, top_result(r, a.top), out);
+  else
+    format_results(a, cpu_default, r, out);
+}
+
 // The result lines to stdout, or to --result-file (a range reducer on a worker daemon,
 // whose reply carries only the tail of stdout).
 void emit_results(const CliArgs& a, const std::string& out) {
@@ -527,7 +588,9 @@ void emit_results(const CliArgs& a, const std::string& out) {
   if (std::fclose(f) != 0) throw Error("error closing " + a.result_file);
 }
 
-void print_gpu_result(const CliArgs& a, const WordCountResult& r, const std::vector<double>& walls) {
+// `top` (--top K on one GPU): the device selected; r then carries the statistics only.
+void print_gpu_result(const CliArgs& a, const WordCountResult& r, const std::vector<double>& walls,
+                      const TopResult* top = nullptr) {
   const bool rt = a.cfg.ref_timers;
   std::printf("GPU mapping %lld nanoseconds \n", ns(rt ? r.times.ref_map_ms : r.times.map_ms));
   for (u64 k = 0; k < r.overflow_lines; ++k) std::printf("WARN: Exceeded emit limit\n");
@@ -538,9 +601,13 @@ void print_gpu_result(const CliArgs& a, const WordCountResult& r, const std::vec
     LOCUST_LOG_WARN("%llu tokens longer than %d chars were truncated",
                     (unsigned long long)r.truncated, a.cfg.max_key_len);
   std::string out;
-  format_results(a, false, r, &out);
+  if (top)
+    format_top(a, false, *top, &out);
+  else
+    format_results(a, false, r, &out);
   emit_results(a, out);
   std::fflush(stdout);
+  g_top_device = top;
   write_json(a, r, walls);
   if (!a.export_kiv.empty()) write_kiv_results(a.export_kiv, r);
   std::printf("\nDone\n");
@@ -572,6 +639,7 @@ int run_direct(const CliArgs& a) {
   const u64 size = file_size(a.file);
   const u64 chunk = cfg.chunk_bytes ? cfg.chunk_bytes : kDefaultStreamChunk;
   WordCountResult r;
+  TopResult top;  // --top K: selected on the device, r keeps the statistics
   std::vector<double> walls;
   log_rss("before the engine");
   Startup& st = g_startup;
@@ -596,7 +664,12 @@ int run_direct(const CliArgs& a) {
     log_rss("with the streaming engine");
     for (int i = 0; i < a.warmup + a.iters; ++i) {
       auto src = open_file_source(a.file);
-      r = eng->run_source(*src);
+      if (a.top) {
+        top = eng->run_top_source(*src, (u32)std::min<u64>(a.top, 0xFFFFFFFFu));
+        r = top_stats(top);
+      } else {
+        r = eng->run_source(*src);
+      }
       if (i >= a.warmup) walls.push_back(r.times.wall_ms);
       if (i == 0) st.first = now_ns();
     }
@@ -617,7 +690,13 @@ int run_direct(const CliArgs& a) {
     jt.reserve((size_t)(a.warmup + a.iters));
     for (int i = 0; i < a.warmup + a.iters; ++i) {
       stamps.push_back(now_ns());
-      if (i < a.warmup) {
+      if (a.top) {
+        top = eng->run_top(in, (u32)std::min<u64>(a.top, 0xFFFFFFFFu));
+        stamps.push_back(now_ns());
+        jt.push_back(top.times);
+        r = top_stats(top);
+        if (i >= a.warmup) walls.push_back(r.times.wall_ms);
+      } else if (i < a.warmup) {
         jt.push_back(eng->run(in).times);
         stamps.push_back(now_ns());
       } else {
@@ -642,7 +721,7 @@ int run_direct(const CliArgs& a) {
   st.jobs = now_ns();
   log_rss("after the job");
   std::printf("Length: %i\n", (int)r.num_lines);
-  print_gpu_result(a, r, walls);
+  print_gpu_result(a, r, walls, a.top ? &top : nullptr);
   log_rss("after the output");
   // keep this run's tuned map for the next run on the file (after the output: not a job's)
   const u64 t_down = now_ns();
@@ -757,11 +836,12 @@ int run_reduce_stage(const CliArgs& a) {
   WordCountResult r = reduce_spills(a.cfg, files, a.reducer, a.reducers, &st);
   std::printf("%s reduce %lld nanoseconds \n", cpu ? "CPU" : "GPU", ns(st.merge_ms));
   std::string out;
-  format_results(a, cpu, r, &out);
+  format_results_or_top(a, cpu, r, &out);  // --top: of this reducer's key range
   emit_results(a, out);
   if (!a.json.empty()) {
     JsonOut j = json_head(a, "reduce_stage");
     json_counts(j, r);
+    json_top(j, a);
     j.u("input_files", st.input_files);
     j.u("indexed_files", st.indexed_files);
     j.u("records_read", st.records_read);
@@ -840,7 +920,7 @@ int run(const CliArgs& a) {
     std::printf("%s stream compaction and sorting %lld nanoseconds \n", dev, ns(dr.shuffle_ms));
     std::printf("%s reduce %lld nanoseconds \n", dev, ns(dr.reduce_ms));
     std::string out;
-    format_results(a, false, dr.result, &out);
+    format_results_or_top(a, false, dr.result, &out);
     emit_results(a, out);
     write_json_dist(a, dr, ranks);
     std::printf("\nDone\n");
@@ -849,12 +929,18 @@ int run(const CliArgs& a) {
 
   // ---------------- stage 0: full pipeline ----------------
   WordCountResult r;
+  TopResult cpu_top;  // --top K on the CPU backend
   std::vector<double> walls;
   if (cpu) {
     CpuWordCount eng(a.cfg);
     for (int i = 0; i < a.warmup; ++i) eng.run(text.input);
     for (int i = 0; i < a.iters; ++i) {
-      r = eng.run(text.input);
+      if (a.top) {
+        cpu_top = eng.run_top(text.input, a.top);
+        r = top_stats(cpu_top);
+      } else {
+        r = eng.run(text.input);
+      }
       walls.push_back(r.times.wall_ms);
     }
     std::printf("CPU mapping %lld nanoseconds \n", ns(r.times.map_ms));
@@ -862,6 +948,15 @@ int run(const CliArgs& a) {
     std::printf("CPU reducing %lld nanoseconds \n", ns(r.times.reduce_ms));
   } else {
     GpuWordCount eng(a.cfg, text.input.bytes, text.input.num_lines);
+    if (a.top) {  // the selection runs on the device: only the winners come back
+      TopResult top;
+      for (int i = 0; i < a.warmup + a.iters; ++i) {
+        top = eng.run_top(text.input, (u32)std::min<u64>(a.top, 0xFFFFFFFFu));
+        if (i >= a.warmup) walls.push_back(top.times.wall_ms);
+      }
+      print_gpu_result(a, top_stats(top), walls, &top);
+      return 0;
+    }
     for (int i = 0; i < a.warmup; ++i) eng.run(text.input);
     for (int i = 0; i < a.iters; ++i) {
       r = eng.run(text.input);
@@ -874,7 +969,10 @@ int run(const CliArgs& a) {
     LOCUST_LOG_WARN("%llu tokens longer than %d chars were truncated",
                     (unsigned long long)r.truncated, a.cfg.max_key_len);
   std::string out;
-  format_results(a, cpu, r, &out);
+  if (a.top)
+    format_top(a, cpu, cpu_top, &out);
+  else
+    format_results(a, cpu, r, &out);
   emit_results(a, out);
   write_json(a, r, walls);
   if (!a.export_kiv.empty()) write_kiv_results(a.export_kiv, r);

@@ -221,4 +221,78 @@ void validate_result(const WordCountResult& r) {
   if (r.entries.size() != r.num_unique) throw Error("LOCUST_CHECK: num_unique mismatch");
 }
 
+// ---- top-K by count: the host selection (engine.hpp) ----
+namespace {
+// rank order: count descending, then key ascending
+bool top_before(const TopEntry& a, const TopEntry& b) {
+  if (a.count != b.count) return a.count > b.count;
+  return key_compare(a.key.w, b.key.w) < 0;
+}
+}  // namespace
+
+std::vector<TopEntry> top_entries(const WordCountResult& r, u64 k) {
+  std::vector<TopEntry> all;
+  all.reserve(r.entries.size());
+  EntryVals vals(r);
+  for (const WordCountEntry e : r.entries) {  // either entry form
+    const u64 val = vals.next(e);
+    all.push_back(TopEntry{e.key, e.count, val});
+  }
+  const size_t m = (size_t)std::min<u64>(k, all.size());
+  std::partial_sort(all.begin(), all.begin() + (std::ptrdiff_t)m, all.end(), top_before);
+  all.resize(m);
+  all.shrink_to_fit();
+  return all;
+}
+
+TopResult top_result(const WordCountResult& r, u64 k) {
+  TopResult t;
+  t.entries = top_entries(r, k);
+  t.k = k;
+  t.num_lines = r.num_lines;
+  t.num_tokens = r.num_tokens;
+  t.num_unique = r.num_unique;
+  t.overflow_lines = r.overflow_lines;
+  t.truncated = r.truncated;
+  t.max_key_len = r.max_key_len;
+  t.chunks = r.chunks;
+  t.times = r.times;
+  return t;
+}
+
+void validate_top(const TopResult& t) {
+  if (t.entries.size() != std::min<u64>(t.k, t.num_unique))
+    throw Error("LOCUST_CHECK: top-k has " + std::to_string(t.entries.size()) +
+                " entries, expected min(" + std::to_string(t.k) + ", " +
+                std::to_string(t.num_unique) + ")");
+  for (size_t j = 1; j < t.entries.size(); ++j) {
+    const TopEntry &a = t.entries[j - 1], &b = t.entries[j];
+    if (b.count > a.count)
+      throw Error("LOCUST_CHECK: top-k counts increase at entry " + std::to_string(j));
+    if (b.count == a.count && key_compare(a.key.w, b.key.w) >= 0)
+      throw Error("LOCUST_CHECK: top-k tie not key-ascending at entry " + std::to_string(j));
+  }
+}
+
+void format_top_output(const TopResult& t, bool cpu_format, std::string* out) {
+  out->reserve(out->size() + t.entries.size() * 48);
+  char buf[kKeyBytes + 1];
+  for (const TopEntry& e : t.entries) {
+    const int n = unpack_key(e.key.w, buf);
+    if (n == 0) continue;
+    out->append("print key: ");
+    out->append(buf, (size_t)n);
+    if (cpu_format) {
+      out->append(" \t value: ");
+      out->append(std::to_string(e.count));
+    } else {
+      out->append(" \t val: ");
+      out->append(std::to_string(e.val));
+      out->append(" \t count: ");
+      out->append(std::to_string(e.count));
+    }
+    out->push_back('\n');
+  }
+}
+
 }  // namespace locust

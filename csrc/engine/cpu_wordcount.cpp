@@ -67,6 +67,16 @@ WordCountResult CpuWordCount::run(const TextInput& in) {
   return r;
 }
 
+TopResult CpuWordCount::run_top(const TextInput& in, u64 k) {
+  LOCUST_CHECK_ARG(k >= 1, "top-k: k must be at least 1");
+  const WordCountResult r = run(in);
+  const u64 t0 = now_ns();
+  TopResult t = top_result(r, k);
+  t.times.wall_ms += (now_ns() - t0) * 1e-6;
+  if (cfg_.check) validate_top(t);
+  return t;
+}
+
 std::vector<PackedKey> CpuWordCount::run_map_stage(const TextInput& in, WordCountResult* stats) {
   WordCountResult r;
   r.num_lines = in.num_lines;

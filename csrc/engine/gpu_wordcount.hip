@@ -30,6 +30,14 @@ WordCountResult GpuWordCount::run_source(TextSource& src) {
   LOCUST_CHECK_ARG(impl_->streaming, "run_source needs a streaming engine (chunk_bytes set)");
   return impl_->run_source(src);
 }
+TopResult GpuWordCount::run_top(const TextInput& in, u32 k) { return impl_->run_top(in, k); }
+TopResult GpuWordCount::run_top_source(TextSource& src, u32 k) {
+  LOCUST_CHECK_ARG(impl_->streaming, "run_top_source needs a streaming engine (chunk_bytes set)");
+  return impl_->run_top_source(src, k);
+}
+TopResult GpuWordCount::top_counts(const KeyCount* recs, u64 n, u32 k) {
+  return impl_->top_counts(recs, n, k);
+}
 GpuWordCount::Stats GpuWordCount::stats() const {
   Stats s;
   s.retunes = impl_->pm_retunes;

@@ -26,6 +26,7 @@ u64 DevicePipeline::pinned_bytes() const {
     if (h_ring[i]) b += ring_piece + 64;
   b += h_keys_cap * kKeyWords * sizeof(u64);
   b += h_chunk_cap * sizeof(MapCounters);
+  if (h_top) b += (kTopKMax + 1) * sizeof(TopRecord);
   b += 2 * sizeof(MapCounters) + sizeof(SortPlan) + 2 * sizeof(PartMapTables) +
        kMaxSamples * sizeof(PackedKey) + (kMaxRanks + 8) * sizeof(u64) + 64 +
        kDictParts * sizeof(u32);
@@ -255,6 +256,7 @@ u64 DevicePipeline::device_bytes() const {
   u64 b = arena.size + (radix_base ? radix_full_bytes(cap) : 0);
   if (d_text_alt) b += cap_bytes + 64;
   if (d_plan) b += plan_zero_bytes;  // (+ the plan's key arrays: small)
+  b += topk_bytes;                   // (0 until the first top job)
   return b;
 }
 
@@ -532,6 +534,10 @@ DevicePipeline::~DevicePipeline() {
     if (p) (void)hipHostFree(p);
   if (d_pmap) (void)hipFree(d_pmap);
   if (d_plan) (void)hipFree(d_plan);
+  if (d_topk) (void)hipFree(d_topk);
+  pinned_free(h_top);
+  for (auto& e : ev_top)
+    if (e) (void)hipEventDestroy(e);
 }
 
 void DevicePipeline::use_out(size_t i) {
@@ -1617,6 +1623,208 @@ WordCountResult DevicePipeline::run(const TextInput& in) {
   }
   if (cfg.check) validate_result(r);
   return r;
+}
+
+// =====================================================================================
+// Top-K by count
+// =====================================================================================
+void DevicePipeline::ensure_topk(u64 n) {
+  if (!h_top) {
+    // first top job of this engine: the mapped top records (+ the word the final kernel
+    // writes their number to) and the events
+    h_top = static_cast<TopRecord*>(pinned_alloc((kTopKMax + 1) * sizeof(TopRecord),
+                                                 hipHostMallocMapped | hipHostMallocCoherent,
+                                                 "mapped top-k records"));
+    LOCUST_HIP_CHECK(hipHostGetDevicePointer(reinterpret_cast<void**>(&d_top_mapped), h_top, 0));
+    for (auto& e : ev_top) LOCUST_HIP_CHECK(hipEventCreate(&e));
+  }
+  if (topk.cap >= std::max<u64>(n, 1)) return;
+  sync();  // nothing in flight may still use the workspace being replaced
+  if (d_topk) LOCUST_HIP_CHECK(hipFree(d_topk));
+  d_topk = nullptr;
+  topk = TopKWorkspace{};
+  // room for what this engine's passes can leave in d_out, at least for this job
+  const u64 want = std::max<u64>({n, std::min<u64>(std::max(ucap, rcap), 1ull << 20), 1});
+  const u64 bytes = topk_workspace_bytes(want);
+  size_t fr = 0, tot = 0;
+  LOCUST_HIP_CHECK(hipMemGetInfo(&fr, &tot));
+  if ((double)bytes > kHbmUsable * (double)fr)
+    throw Error("top-k selection workspace (" + std::to_string(bytes) + " B for " +
+                std::to_string(want) + " records, plus " +
+                std::to_string((kTopKMax + 1) * sizeof(TopRecord)) +
+                " B of pinned top records) does not fit the free device memory (" +
+                std::to_string(fr) + " B of " + std::to_string(tot) + " B)");
+  LOCUST_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&d_topk), bytes));
+  topk_bytes = bytes;
+  topk_workspace_carve(d_topk, want, &topk);
+}
+
+void DevicePipeline::check_top_job(u32 k) const {
+  LOCUST_CHECK_ARG(k >= 1, "top-k: k must be at least 1");
+  LOCUST_CHECK_ARG(k <= kTopKMax,
+                   "top-k: k = " + std::to_string(k) + " exceeds the device selection's limit "
+                   "kTopKMax = " + std::to_string(kTopKMax) + "; take the full result and "
+                   "select on the host (top_entries / Result.top)");
+}
+
+void DevicePipeline::enqueue_top_select(const OutRecord* recs, u64 n, u32 k) {
+  TraceRange tr("locust:top_select");
+  ensure_topk(n);
+  LOCUST_HIP_CHECK(hipEventRecord(ev_top[0], stream));
+  launch_top_select(recs, n, k, topk, d_top_mapped, reinterpret_cast<u32*>(d_top_mapped + kTopKMax),
+                    stream);
+  LOCUST_HIP_CHECK(hipEventRecord(ev_top[1], stream));
+}
+
+void DevicePipeline::collect_top(u64 n, u32 k, TopResult* t) {
+  static_assert(offsetof(TopEntry, count) == offsetof(TopRecord, count) &&
+                    offsetof(TopEntry, val) == offsetof(TopRecord, val),
+                "entry layout");
+  const u64 m = *reinterpret_cast<const u32*>(h_top + kTopKMax);
+  LOCUST_CHECK_ARG(m == std::min<u64>(k, n), "top-k selection wrote " + std::to_string(m) +
+                                                 " records, expected " +
+                                                 std::to_string(std::min<u64>(k, n)));
+  t->k = k;
+  t->entries.resize(m);
+  if (m) std::memcpy(t->entries.data(), h_top, m * sizeof(TopRecord));
+  t->select_ms = ms_between(ev_top[0], ev_top[1]);
+  t->wire_bytes = m * sizeof(TopRecord) + sizeof(u64);
+}
+
+void DevicePipeline::finish_top(u32 num_lines, u32 k, bool streamed, TopResult* t) {
+  read_counters();  // (synchronises)
+  if (streamed && (h_ctr->flags & kCtrDictOverflow))
+    throw Error("streaming dictionary overflow: more than " + std::to_string(ucap) +
+                " distinct keys; use a larger chunk size");
+  if (dict_fallback_needed()) {
+    // more distinct keys than the rank sort takes, or a full table: the radix path, which
+    // also ends in d_out
+    finish_dict_with_radix(num_lines);
+    LOCUST_HIP_CHECK(hipEventRecord(ev[4], stream));
+    read_counters();
+  }
+  const u64 n = h_ctr->num_unique;
+  LOCUST_CHECK_ARG(n <= rcap, "top-k: more distinct keys than the record buffer holds");
+  enqueue_top_select(d_out, n, k);
+  sync();
+  collect_top(n, k, t);
+  t->num_unique = n;
+}
+
+TopResult DevicePipeline::run_top(const TextInput& in, u32 k) {
+  TraceRange tr("locust:top_job");
+  LOCUST_CHECK_ARG(cfg.sort_path == SortPath::kDict,
+                   "a top-k job needs a dictionary engine (sort=dict)");
+  LOCUST_CHECK_ARG(!cfg.ref_timers, "a top-k job does not take ref_timers");
+  LOCUST_CHECK_ARG(!cfg.records_only, "a records-only engine runs no text jobs");
+  check_top_job(k);
+  sync_clean = false;  // this entry point dirties d_sync
+  const bool compat = cfg.map_path == MapPath::kCompat;
+  TopResult t;
+  t.num_lines = in.num_lines;
+  const u64 t0 = now_ns();
+  LOCUST_HIP_CHECK(hipEventRecord(ev[0], stream));
+  if (in.bytes > pass_bytes && !compat) {
+    // larger than a pass: every chunk into one dictionary, ranked and emitted once
+    LOCUST_HIP_CHECK(hipEventRecord(ev[1], stream));
+    const size_t nchunks = enqueue_stream_insert(in);
+    LOCUST_HIP_CHECK(hipEventRecord(ev[2], stream));
+    enqueue_rank();
+    LOCUST_HIP_CHECK(hipEventRecord(ev[3], stream));
+    enqueue_emit_dict(/*mapped=*/false);
+    LOCUST_HIP_CHECK(hipEventRecord(ev[4], stream));
+    finish_top(0, k, true, &t);
+    WordCountResult st;
+    stream_stats(nchunks, st);
+    t.num_tokens = st.num_tokens;
+    t.overflow_lines = st.overflow_lines;
+    t.truncated = st.truncated;
+    t.max_key_len = st.max_key_len;
+    t.chunks = st.chunks;
+  } else {
+    check_input(in);
+    enqueue_upload(in);
+    LOCUST_HIP_CHECK(hipEventRecord(ev[1], stream));
+    enqueue_map(in);
+    LOCUST_HIP_CHECK(hipEventRecord(ev[2], stream));
+    enqueue_process_dict((u32)in.num_lines, compat);
+    LOCUST_HIP_CHECK(hipEventRecord(ev[3], stream));
+    enqueue_emit_dict(/*mapped=*/false);
+    LOCUST_HIP_CHECK(hipEventRecord(ev[4], stream));
+    finish_top((u32)in.num_lines, k, false, &t);
+    WordCountResult st;
+    fill_counters(st);
+    t.num_tokens = st.num_tokens;
+    t.overflow_lines = st.overflow_lines;
+    t.truncated = st.truncated;
+    t.max_key_len = st.max_key_len;
+    t.times.h2d_ms = ms_between(ev[0], ev[1]);
+  }
+  t.times.map_ms = ms_between(ev[1], ev[2]);
+  t.times.process_ms = ms_between(ev[2], ev[3]);
+  t.times.reduce_ms = ms_between(ev[3], ev[4]);
+  t.times.gpu_ms = ms_between(ev[0], ev_top[1]);
+  t.times.wall_ms = (now_ns() - t0) * 1e-6;
+  if (cfg.check) validate_top(t);
+  return t;
+}
+
+TopResult DevicePipeline::run_top_source(TextSource& src, u32 k) {
+  TraceRange tr("locust:top_job");
+  LOCUST_CHECK_ARG(cfg.sort_path == SortPath::kDict,
+                   "a top-k job needs a dictionary engine (sort=dict)");
+  LOCUST_CHECK_ARG(!cfg.ref_timers, "a top-k job does not take ref_timers");
+  check_top_job(k);
+  sync_clean = false;
+  TopResult t;
+  const u64 t0 = now_ns();
+  LOCUST_HIP_CHECK(hipEventRecord(ev[0], stream));
+  LOCUST_HIP_CHECK(hipEventRecord(ev[1], stream));
+  const size_t nchunks = enqueue_stream_source(src);
+  LOCUST_HIP_CHECK(hipEventRecord(ev[2], stream));
+  enqueue_rank();
+  LOCUST_HIP_CHECK(hipEventRecord(ev[3], stream));
+  enqueue_emit_dict(/*mapped=*/false);
+  LOCUST_HIP_CHECK(hipEventRecord(ev[4], stream));
+  finish_top(0, k, true, &t);
+  WordCountResult st;
+  stream_stats(nchunks, st);
+  t.num_lines = src.lines();
+  t.num_tokens = st.num_tokens;
+  t.overflow_lines = st.overflow_lines;
+  t.truncated = st.truncated;
+  t.max_key_len = st.max_key_len;
+  t.chunks = st.chunks;
+  t.times.map_ms = ms_between(ev[1], ev[2]);
+  t.times.process_ms = ms_between(ev[2], ev[3]);
+  t.times.reduce_ms = ms_between(ev[3], ev[4]);
+  t.times.gpu_ms = ms_between(ev[0], ev_top[1]);
+  t.times.wall_ms = (now_ns() - t0) * 1e-6;
+  if (cfg.check) validate_top(t);
+  return t;
+}
+
+TopResult DevicePipeline::top_counts(const KeyCount* recs, u64 n, u32 k) {
+  static_assert(sizeof(KeyCount) == sizeof(OutRecord) &&
+                    offsetof(KeyCount, count) == offsetof(OutRecord, count),
+                "record layout");
+  check_top_job(k);
+  LOCUST_CHECK_ARG(n <= slot_records_cap(), "too many records for engine capacity");
+  sync_clean = false;
+  TopResult t;
+  const u64 t0 = now_ns();
+  if (n)
+    LOCUST_HIP_CHECK(hipMemcpyAsync(d_records, recs, n * sizeof(KeyCount), hipMemcpyHostToDevice,
+                                    stream));
+  enqueue_top_select(reinterpret_cast<const OutRecord*>(d_records), n, k);
+  sync();
+  collect_top(n, k, &t);
+  t.num_unique = n;
+  for (u64 i = 0; i < n; ++i) t.num_tokens += recs[i].count;
+  t.times.gpu_ms = t.select_ms;
+  t.times.wall_ms = (now_ns() - t0) * 1e-6;
+  if (cfg.check) validate_top(t);
+  return t;
 }
 
 bool DevicePipeline::host_pinned(const void* p) {

@@ -736,6 +736,31 @@ struct DevicePipeline {
 
   WordCountResult run(const TextInput& in);
 
+  // ---- top-K by count (kernels/topk.hip) ----
+  // The selection's workspace and the host-mapped top-record buffer exist from the first
+  // top job on (ensure_topk: checked against free HBM; engines that never run a top job
+  // allocate nothing for it).  d_out is the junction: every path below leaves all
+  // num_unique records there in key order, the selection reads them in place, and only
+  // the winners cross PCIe.
+  TopKWorkspace topk{};
+  char* d_topk = nullptr;
+  u64 topk_bytes = 0;
+  TopRecord* h_top = nullptr;  // kTopKMax records + the count word, host-mapped
+  TopRecord* d_top_mapped = nullptr;
+  hipEvent_t ev_top[2] = {};
+  void ensure_topk(u64 n);
+  void check_top_job(u32 k) const;
+  // The selection over recs[0 .. n) (device memory) on `stream`, timed by ev_top; the
+  // caller synchronises and collects with collect_top.
+  void enqueue_top_select(const OutRecord* recs, u64 n, u32 k);
+  void collect_top(u64 n, u32 k, TopResult* t);
+  // After a dictionary pass's insert + rank + emit into d_out: the counters, the radix
+  // fallback (as run() / finish_stream), the selection and the result.
+  void finish_top(u32 num_lines, u32 k, bool streamed, TopResult* t);
+  TopResult run_top(const TextInput& in, u32 k);
+  TopResult run_top_source(TextSource& src, u32 k);
+  TopResult top_counts(const KeyCount* recs, u64 n, u32 k);
+
   // ---------------------------------------------------------------------------------
   // Streaming: an input larger than the engine's text capacity is processed in
   // line-aligned chunks of <= cap_bytes.  Chunk k+1's H2D runs on the copy

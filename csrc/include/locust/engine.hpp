@@ -260,6 +260,53 @@ class EntryVals {
   u64 at_;
 };
 
+// ---- top-K words by count ----
+// top(K) of a WordCount result: the min(K, num_unique) entries with the largest count, in
+// rank order -- count descending, ties by key ascending (unsigned-byte order: the entry's
+// index in the key-ordered output).  The order is total, so the answer is unique.  Every
+// entry keeps the val it has in the full output (the exclusive prefix of the counts in key
+// order): the top-K lines are a reordered subset of the full output's lines.
+//
+// The device selection (kernels/topk.hip; GpuWordCount::run_top) takes K <= kTopKMax: the
+// final ordering of the winners is one workgroup's LDS sort.  The host selection
+// (top_entries) takes any K.
+constexpr u32 kTopKMax = 4096;
+constexpr u32 kTopKTile = 2048;  // records per workgroup of the selection kernels
+
+struct TopEntry {
+  PackedKey key;
+  u64 count;
+  u64 val;
+};
+static_assert(sizeof(TopEntry) == 48, "TopEntry 48 B (the device's TopRecord)");
+
+struct TopResult {
+  std::vector<TopEntry> entries;  // rank order
+  u64 k = 0;                      // the K asked for
+  // the whole job's statistics, as in WordCountResult
+  u64 num_lines = 0;
+  u64 num_tokens = 0;
+  u64 num_unique = 0;
+  u64 overflow_lines = 0;
+  u64 truncated = 0;
+  u64 max_key_len = 0;
+  u64 chunks = 1;
+  StageTimes times;
+  double select_ms = 0;  // device time of the selection (0: selected on the host)
+  u64 wire_bytes = 0;    // bytes the device wrote to host memory for the result
+};
+
+// Host selection, any k: partial sort over either entry form, val rebuilt with EntryVals.
+std::vector<TopEntry> top_entries(const WordCountResult& r, u64 k);
+// ... with the job's statistics carried over.
+TopResult top_result(const WordCountResult& r, u64 k);
+// LOCUST_CHECK invariants of a top result: min(k, num_unique) entries, counts
+// non-increasing, ties key-ascending.
+void validate_top(const TopResult& t);
+// The result lines of a top result, in rank order: the GPU build's (with val) or the CPU
+// build's (format_gpu_output / format_cpu_output, io.hpp).
+void format_top_output(const TopResult& t, bool cpu_format, std::string* out);
+
 // Text read piece by piece (a file too large to hold): whole lines go straight into the
 // engine's pinned staging, so host memory stays bounded by two chunks whatever the input.
 class TextSource {
@@ -368,6 +415,16 @@ class GpuWordCount {
   // Root merge of the gather strategy (launch_merge_sorted_runs) over host-made runs, each
   // sorted with distinct keys: the merged (key, val, count) entries.
   WordCountResult merge_runs(const std::vector<std::vector<KeyCount>>& runs);
+  // The device selection alone (kernels/topk.hip) over host-made records sorted by key
+  // with distinct keys: their top k (k <= kTopKMax, n within the engine's capacity).
+  TopResult top_counts(const KeyCount* recs, u64 n, u32 k);
+
+  // A whole job whose full records never cross PCIe: the key-ordered records stay in
+  // device memory, the selection kernels pick the top k (1 <= k <= kTopKMax) there and
+  // only those travel.  Dictionary engines (sort=dict, either map path); inputs past one
+  // pass and sources stream like run() / run_source().
+  TopResult run_top(const TextInput& in, u32 k);
+  TopResult run_top_source(TextSource& src, u32 k);
 
   const JobConfig& config() const;
   u64 token_capacity() const;
@@ -410,6 +467,7 @@ class CpuWordCount {
  public:
   explicit CpuWordCount(const JobConfig& cfg);
   WordCountResult run(const TextInput& in);
+  TopResult run_top(const TextInput& in, u64 k);  // run() + the host selection, any k
   std::vector<PackedKey> run_map_stage(const TextInput& in, WordCountResult* stats);
   WordCountResult run_reduce_stage(const PackedKey* keys, u64 n);
 

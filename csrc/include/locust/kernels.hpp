@@ -491,6 +491,58 @@ void launch_exch_pack(const KeyCount* recs, const u32* d_n, u64 cap, const ExchC
 // (acc: launch_merge_rank_slots' accumulators, summed and re-zeroed here)
 void launch_exch_report(const char* recv, u32 P, u32 slot_records, const ExchCtl* ctl,
                         u64* acc, u32 gather_records, ExchMsg3* msg3, hipStream_t s);
+// ---------------- topk.hip ----------------
+// Top-K by count over `n` output records in key order (engine.hpp "top-K words by count"):
+// the min(k, n) records with the largest count, ordered by (count descending, index
+// ascending), each with its exact u64 val (exclusive prefix of the counts in key order).
+// k <= kTopKMax (engine.hpp; the winners' final sort is one workgroup's LDS).
+//
+// A sequence of kernels on `s`; data moves between workgroups only across the kernel
+// boundaries -- no polled words, no look-back, nothing a workgroup waits for:
+//   extract     counts -> dense array, per-tile count sums, the largest count
+//   digit x 8   radix select of the k-th largest count, most significant byte first: the
+//               histogram of byte b over the counts that match the digits chosen so far
+//               (LDS histogram per workgroup, one global atomic per non-empty bin).  Every
+//               workgroup re-derives the chosen digits from the earlier passes' finished
+//               histograms, so the threshold and the remaining quota live in device memory
+//               only.  Passes above the largest count's top byte exit at once.
+//   tile count  per tile: records above the threshold T, records equal to it
+//   scan        one workgroup: exclusive scans of the tile arrays (val bases, slot bases)
+//   scatter     (count, index, val) of every record with count > T and of the first
+//               `quota` records (key order) with count == T into their candidate slots
+//   final       one workgroup sorts the <= kTopKMax candidates in LDS, gathers the keys and
+//               writes the TopRecords and their number
+struct TopRecord {
+  u64 w[kKeyWords];
+  u64 count;
+  u64 val;
+};
+static_assert(sizeof(TopRecord) == sizeof(TopEntry), "TopRecord == TopEntry (48 B)");
+constexpr int kTopKBlock = 256;
+constexpr int kTopKItems = kTopKTile / kTopKBlock;
+static_assert(kTopKTile % kTopKBlock == 0 && kTopKItems == 8, "2048-record tiles");
+static_assert((kTopKMax & (kTopKMax - 1)) == 0 && kTopKMax >= 1024 && kTopKMax <= 4096,
+              "the final sort holds kTopKMax candidates in 48 KiB of LDS");
+struct TopKWorkspace {
+  u64* counts = nullptr;      // [cap] dense counts
+  u64* tile_val = nullptr;    // [tiles] count sums, scanned in place: the tiles' val bases
+  u64* tile_ge = nullptr;     // [tiles] (#gt << 32 | #eq), scanned in place: slot bases
+  u64* sel = nullptr;         // [1 + 8 * 128]: the largest count, then 8 x 256 u32 bins
+  u64* cand_count = nullptr;  // [kTopKMax] candidates: count, record index, val
+  u32* cand_idx = nullptr;
+  u64* cand_val = nullptr;
+  u64 cap = 0;                // records the arrays hold
+};
+constexpr u64 kTopKSelWords = 1 + 8 * 256 / 2;
+u64 topk_workspace_bytes(u64 cap);
+// Carves `base` (topk_workspace_bytes(cap) bytes, 256-B aligned) into the arrays.
+void topk_workspace_carve(char* base, u64 cap, TopKWorkspace* ws);
+// Enqueues the selection over recs[0 .. n) (n <= ws.cap, n < 2^32, 1 <= k <= kTopKMax):
+// `out` (host-mapped allowed, room for min(k, n) records) and *out_n.  Zeroes every word
+// the kernels accumulate into (ws.sel) itself, on every call.
+void launch_top_select(const OutRecord* recs, u64 n, u32 k, const TopKWorkspace& ws,
+                       TopRecord* out, u32* out_n, hipStream_t s);
+
 // ---- device self-test of the string library (tests only; StringTestOut in engine.hpp) ----
 void launch_string_selftest(const char* blob, const u32* off, u32 n, const char* delims,
                             const int* ints, StringTestOut* out, hipStream_t s);
@@ -512,6 +564,10 @@ void warm_module_reduce();
 void warm_module_shuffle();
 void warm_module_signal();
 void warm_module_tokenize();
+// The selection's code object is loaded with the others (every kernel file is: a first top
+// job does no one-time loading either, tests/test_cold_path.py); its workspace and pinned
+// buffer are made by an engine's first top job only.
+void warm_module_topk();
 inline void warm_kernel_modules() {
   warm_module_dict();
   warm_module_exchange();
@@ -524,6 +580,7 @@ inline void warm_kernel_modules() {
   warm_module_shuffle();
   warm_module_signal();
   warm_module_tokenize();
+  warm_module_topk();
 }
 
 }  // namespace locust

@@ -61,6 +61,34 @@ struct PyResult {
   }
 };
 
+// A top-K result: the rank-ordered (key, val, count) entries and the job's statistics.
+struct PyTopResult {
+  TopResult t;
+  py::list entries() const {
+    py::list out;
+    for (const auto& e : t.entries)
+      out.append(py::make_tuple(py::bytes(key_to_string(e.key)), e.val, e.count));
+    return out;
+  }
+  py::dict times() const {
+    py::dict d = PyResult{WordCountResult{}}.times();
+    d["h2d_ms"] = t.times.h2d_ms;
+    d["map_ms"] = t.times.map_ms;
+    d["process_ms"] = t.times.process_ms;
+    d["reduce_ms"] = t.times.reduce_ms;
+    d["d2h_ms"] = t.times.d2h_ms;
+    d["wall_ms"] = t.times.wall_ms;
+    d["gpu_ms"] = t.times.gpu_ms;
+    d["select_ms"] = t.select_ms;
+    return d;
+  }
+  py::bytes format(bool cpu_format) const {
+    std::string s;
+    format_top_output(t, cpu_format, &s);
+    return py::bytes(s);
+  }
+};
+
 TextInput as_input(const std::string& text, u64 first_line = 0) {
   TextInput in;
   in.data = text.data();
@@ -163,6 +191,34 @@ class PyGpuEngine {
       }
     py::gil_scoped_release nogil;
     return PyResult{eng_.merge_runs(rr)};
+  }
+  // Top-K jobs: the selection runs on the device, only the winners cross PCIe.
+  PyTopResult run_top(const std::string& text, u32 k) {
+    py::gil_scoped_release nogil;
+    return PyTopResult{eng_.run_top(as_input(text), k)};
+  }
+  PyTopResult run_top_text(const HostText& t, u32 k) {
+    py::gil_scoped_release nogil;
+    return PyTopResult{eng_.run_top(t.input(), k)};
+  }
+  PyTopResult run_top_file(const std::string& path, u32 k) {
+    py::gil_scoped_release nogil;
+    auto src = open_file_source(path);
+    return PyTopResult{eng_.run_top_source(*src, k)};
+  }
+  // records: (key bytes, count), sorted by key with distinct keys -- the kernels alone.
+  PyTopResult top_counts(const std::vector<std::pair<std::string, u64>>& records, u32 k) {
+    std::vector<KeyCount> recs;
+    recs.reserve(records.size());
+    for (const auto& kc : records) {
+      KeyCount rec;
+      const PackedKey key = to_key(kc.first);
+      for (int w = 0; w < kKeyWords; ++w) rec.w[w] = key.w[w];
+      rec.count = kc.second;
+      recs.push_back(rec);
+    }
+    py::gil_scoped_release nogil;
+    return PyTopResult{eng_.top_counts(recs.data(), recs.size(), k)};
   }
   u64 capacity() const { return eng_.token_capacity(); }
   // Stage the text in the engine's pinned buffer once; run_loaded() then skips the copy.
@@ -530,7 +586,30 @@ PYBIND11_MODULE(_locust, m) {
         p.r.val_base = val_base;
         p.r.num_unique = n;
         return p;
-      }, py::arg("words"), py::arg("segments"), py::arg("val_base") = 0);
+      }, py::arg("words"), py::arg("segments"), py::arg("val_base") = 0)
+      .def("top", [](const PyResult& p, u64 k) {
+        LOCUST_CHECK_ARG(k >= 1, "top-k: k must be at least 1");
+        py::gil_scoped_release nogil;
+        return PyTopResult{top_result(p.r, k)};
+      }, py::arg("k"), "The host selection (any k): the top k entries by count, rank order.");
+
+  py::class_<PyTopResult>(m, "TopResult")
+      .def("entries", &PyTopResult::entries)
+      .def("times", &PyTopResult::times)
+      .def("format", &PyTopResult::format, py::arg("cpu_format") = false)
+      .def_property_readonly("k", [](const PyTopResult& p) { return p.t.k; })
+      .def_property_readonly("num_lines", [](const PyTopResult& p) { return p.t.num_lines; })
+      .def_property_readonly("num_tokens", [](const PyTopResult& p) { return p.t.num_tokens; })
+      .def_property_readonly("num_unique", [](const PyTopResult& p) { return p.t.num_unique; })
+      .def_property_readonly("overflow_lines", [](const PyTopResult& p) { return p.t.overflow_lines; })
+      .def_property_readonly("truncated", [](const PyTopResult& p) { return p.t.truncated; })
+      .def_property_readonly("max_key_len", [](const PyTopResult& p) { return p.t.max_key_len; })
+      .def_property_readonly("chunks", [](const PyTopResult& p) { return p.t.chunks; })
+      .def_property_readonly("select_ms", [](const PyTopResult& p) { return p.t.select_ms; })
+      .def_property_readonly("wire_bytes", [](const PyTopResult& p) { return p.t.wire_bytes; },
+                             "bytes the device wrote to host memory for the result");
+  m.attr("kTopKMax") = kTopKMax;
+  m.attr("kTopKTile") = kTopKTile;
 
   py::class_<PyGpuEngine>(m, "GpuEngine")
       .def(py::init<const JobConfig&, u64, u64>(), py::arg("cfg"), py::arg("max_bytes"),
@@ -556,12 +635,22 @@ PYBIND11_MODULE(_locust, m) {
       .def("compact_slots", &PyGpuEngine::compact_slots)
       .def("reduce_sorted", &PyGpuEngine::reduce_sorted)
       .def("merge_runs", &PyGpuEngine::merge_runs)
+      .def("run_top", &PyGpuEngine::run_top, py::arg("text"), py::arg("k"),
+           "WordCount of text, top k by count selected on the device (k <= kTopKMax).")
+      .def("run_top_text", &PyGpuEngine::run_top_text, py::arg("text"), py::arg("k"))
+      .def("run_top_file", &PyGpuEngine::run_top_file, py::arg("path"), py::arg("k"))
+      .def("top_counts", &PyGpuEngine::top_counts, py::arg("records"), py::arg("k"),
+           "The selection kernels alone over key-sorted (key, count) records.")
       .def_property_readonly("capacity", &PyGpuEngine::capacity);
 
   m.def("cpu_run", [](const JobConfig& cfg, const std::string& text) {
     CpuWordCount eng(cfg);
     return PyResult{eng.run(as_input(text))};
   });
+  m.def("cpu_run_top", [](const JobConfig& cfg, const std::string& text, u64 k) {
+    CpuWordCount eng(cfg);
+    return PyTopResult{eng.run_top(as_input(text), k)};
+  }, py::arg("cfg"), py::arg("text"), py::arg("k"));
   m.def("cpu_map_stage", [](const JobConfig& cfg, const std::string& text) {
     CpuWordCount eng(cfg);
     std::vector<py::bytes> out;

@@ -49,6 +49,8 @@ from .models.wordcount import (  # noqa: E402
     map_stage,
     reduce_stage,
     run_multi,
+    top_words_file,
+    top_words_text,
     wordcount_file,
     wordcount_text,
 )
@@ -72,6 +74,8 @@ __all__ = [
     "run_multi",
     "wordcount_file",
     "wordcount_text",
+    "top_words_file",
+    "top_words_text",
     "JobConfig",
     "DistConfig",
     "LocustError",

@@ -32,6 +32,26 @@ class Engine:
             return _C.cpu_run(self.cfg, text)
         return self._eng.run(text)
 
+    def run_top(self, text: bytes, k: int):
+        """WordCount of ``text``, then its ``k`` most frequent words (count descending,
+        ties by key ascending) as a ``TopResult``.  On the GPU the selection runs on the
+        device and only the winners cross PCIe (``k <= _C.kTopKMax``; for a larger ``k``
+        take ``run(text).top(k)``, the host selection)."""
+        if self.cpu:
+            return _C.cpu_run_top(self.cfg, text, k)
+        return self._eng.run_top(text, k)
+
+    def top_counts(self, records: list[tuple[bytes, int]], k: int):
+        """The selection alone over (key, count) records sorted by key with distinct
+        keys: a ``TopResult`` on the GPU, the plain (key, val, count) list on the CPU."""
+        if self.cpu:
+            out, pos = [], 0
+            for key, count in records:
+                out.append((key, pos, count))
+                pos += count
+            return sorted(out, key=lambda e: (-e[2], e[0]))[:k]
+        return self._eng.top_counts(records, k)
+
     def map_stage(self, text: bytes) -> list[bytes]:
         """Map + sort only (stage 1): the sorted token list of ``text``."""
         if self.cpu:
@@ -78,6 +98,22 @@ def wordcount_file(path: str, line_start: int = -1, line_end: int = -1, backend:
     cfg = cfg if cfg is not None else make_config(backend, **kw)
     text, nlines, _first, _total = _C.load_lines(path, line_start, line_end, cfg.ref_compat)
     return Engine(cfg, max(len(text), 1), max(nlines, 1)).run(text)
+
+
+def top_words_text(text: bytes, k: int, backend: str = "gpu", cfg=None, **kw):
+    """The ``k`` most frequent words of ``text`` (``TopResult``: rank-ordered
+    ``(key, val, count)`` entries, ``val`` as in the full output)."""
+    cfg = cfg if cfg is not None else make_config(backend, **kw)
+    nlines = text.count(b"\n") + (1 if text and not text.endswith(b"\n") else 0)
+    return Engine(cfg, max(len(text), 1), max(nlines, 1)).run_top(text, k)
+
+
+def top_words_file(path: str, k: int, line_start: int = -1, line_end: int = -1,
+                   backend: str = "gpu", cfg=None, **kw):
+    """The ``k`` most frequent words of a file or of its line window."""
+    cfg = cfg if cfg is not None else make_config(backend, **kw)
+    text, nlines, _first, _total = _C.load_lines(path, line_start, line_end, cfg.ref_compat)
+    return Engine(cfg, max(len(text), 1), max(nlines, 1)).run_top(text, k)
 
 
 def map_stage(path: str, spill: str, line_start: int = -1, line_end: int = -1,

@@ -55,6 +55,11 @@ def wordcount(text: bytes, delims: bytes = DEFAULT_DELIMS, emits: int = 20, max_
     return entries, pos, overflow
 
 
+def top(entries, k: int):
+    """The k entries with the largest count: count descending, ties by key ascending."""
+    return sorted(entries, key=lambda e: (-e[2], e[0]))[:k]
+
+
 def format_gpu(entries) -> bytes:
     """The reference GPU build's result lines (main.cu:132)."""
     return b"".join(b"print key: %s \t val: %d \t count: %d\n" % (k, v, c) for k, v, c in entries)

@@ -15,6 +15,7 @@
 //   --warmup N  --iters N  --json FILE  --quiet  --check  --device N  --chunk-mb N
 //   --ref-timers (stage times taken where the reference's host timers were)
 //   --top K (the K most frequent words instead of the whole dictionary, rank order)
+//   --ngram N (count the word N-grams of each line, N <= 3, instead of its words)
 // and a synthetic-text generator (BASELINE configs "1M lines" / "10 GB"):
 //   MapReduce --gen FILE (--gen-lines N | --gen-bytes N) [--seed S] [--vocab V]
 #include <sys/stat.h>
@@ -108,10 +109,14 @@ void help() {
       "  --warmup N --iters N       --chunk-mb N               --ref-timers\n"
       "  --top K                    (only the K most frequent words, count descending, ties\n"
       "                             by key; selected on the device on one GPU, K <= %u)\n"
+      "  --ngram N                  (count word N-grams, N in [1, %d]: N consecutive words of one\n"
+      "                             line joined by single spaces; never across a line end.  A\n"
+      "                             key is the first --max-key bytes of the joined words.  Not\n"
+      "                             with --map-path compat or the stage split)\n"
       "  --help\n"
       "\n"
       "Environment: LOCUST_LOG=info|debug and the LOCUST_* switches in docs/ENVIRONMENT.md.\n",
-      (unsigned)kTopKMax);
+      (unsigned)kTopKMax, kMaxNgram);
 }
 
 std::vector<std::string> split(const std::string& s, char c) {
@@ -226,6 +231,13 @@ bool parse(int argc, char** argv, CliArgs* a) {
       const long long k = std::strtoll(v.c_str(), &endp, 10);
       if (v.empty() || *endp || k < 1) throw Error("--top K needs an integer K >= 1");
       a->top = (u64)k;
+    } else if (s == "--ngram") {
+      const std::string v = need("--ngram");
+      char* endp = nullptr;
+      const long long n = std::strtoll(v.c_str(), &endp, 10);
+      if (v.empty() || *endp || n < 1 || n > kMaxNgram)
+        throw Error("--ngram N needs an integer N in [1, " + std::to_string(kMaxNgram) + "]");
+      a->cfg.ngram = (int)n;
     } else if (s == "--chunk-mb") {
       a->cfg.chunk_bytes = (u64)std::atoll(need("--chunk-mb").c_str()) << 20;
     } else if (s == "--gen") {
@@ -265,6 +277,14 @@ bool parse(int argc, char** argv, CliArgs* a) {
     if (a->cfg.ref_timers) throw Error("--top and --ref-timers do not combine");
     if (a->cfg.backend == Backend::kGpu && a->cfg.sort_path == SortPath::kRadix)
       throw Error("--top on the GPU needs the dictionary path (--sort dict)");
+  }
+  if (a->cfg.ngram > 1) {
+    // the text spill cannot carry keys with spaces, so the stage split stays a word job
+    if (a->stage != 0 || !a->inputs.empty() || a->reducers > 1)
+      throw Error("--ngram N > 1 runs whole jobs only: not with the stage split (stage 1 or 2, "
+                  "--stage, --inputs, --reducer)");
+    if (a->cfg.backend == Backend::kGpu && a->cfg.map_path == MapPath::kCompat)
+      throw Error("--ngram N > 1 needs the fast map (map_path fast), not --map-path compat");
   }
   if (a->byte_range) {
     if (a->stage != 1) throw Error("--byte-range is a stage-1 (map) flag");
@@ -345,6 +365,7 @@ JsonOut json_head(const CliArgs& a, const char* mode) {
   j.str("map_path", to_string(a.cfg.map_path));
   j.str("reduce_path", to_string(a.cfg.reduce_path));
   j.str("sort", to_string(a.cfg.sort_path));
+  j.u("ngram", (u64)a.cfg.ngram);
   return j;
 }
 

@@ -160,6 +160,12 @@ const char* to_string(ReducePath p) { return p == ReducePath::kLds ? "lds" : "gl
 const char* to_string(MapPath p) { return p == MapPath::kCompat ? "compat" : "fast"; }
 const char* to_string(SortPath p) { return p == SortPath::kRadix ? "radix" : "dict"; }
 
+void check_ngram(const JobConfig& cfg) {
+  if (cfg.ngram < 1 || cfg.ngram > kMaxNgram)
+    throw Error("ngram must be in [1, " + std::to_string(kMaxNgram) + "], got " +
+                std::to_string(cfg.ngram));
+}
+
 int tokenize_line(const char* line, u64 len, const JobConfig& cfg, std::vector<PackedKey>* out,
                   u64* truncated) {
   // The reference works on a NUL-terminated copy (main.cu:55-59); text after an embedded
@@ -167,6 +173,31 @@ int tokenize_line(const char* line, u64 len, const JobConfig& cfg, std::vector<P
   std::string buf(line, len);
   char* save = nullptr;
   char* tok = d_strtok_r(&buf[0], cfg.delimiters.c_str(), &save);
+  if (cfg.ngram > 1) {
+    // Word n-grams: every token of the line (uncapped, untruncated), then the first
+    // emits_per_line n-grams t_i ' ' ... ' ' t_(i+N-1); the key is the first max_key_len
+    // bytes of the joined words.
+    std::vector<std::pair<const char*, int>> toks;
+    for (; tok != nullptr; tok = d_strtok_r(nullptr, cfg.delimiters.c_str(), &save))
+      toks.emplace_back(tok, d_strlen(tok));
+    const size_t N = (size_t)cfg.ngram;
+    const size_t grams = toks.size() >= N ? toks.size() - N + 1 : 0;
+    const size_t emit = std::min<size_t>(grams, (size_t)std::max(cfg.emits_per_line, 0));
+    std::string joined;
+    for (size_t i = 0; i < emit; ++i) {
+      joined.assign(toks[i].first, (size_t)toks[i].second);
+      for (size_t g = 1; g < N; ++g) {
+        joined.push_back(' ');
+        joined.append(toks[i + g].first, (size_t)toks[i + g].second);
+      }
+      int n = (int)std::min<size_t>(joined.size(), (size_t)cfg.max_key_len);
+      if (joined.size() > (size_t)cfg.max_key_len && truncated) ++*truncated;
+      PackedKey k;
+      pack_key(joined.data(), n, k.w);
+      out->push_back(k);
+    }
+    return grams > emit ? 1 : 0;
+  }
   int count = 0;
   int dropped = 0;
   while (tok != nullptr) {

@@ -14,7 +14,7 @@ namespace locust {
 
 void validate_result(const WordCountResult& r);
 
-CpuWordCount::CpuWordCount(const JobConfig& cfg) : cfg_(cfg) {}
+CpuWordCount::CpuWordCount(const JobConfig& cfg) : cfg_(cfg) { check_ngram(cfg_); }
 
 namespace {
 

@@ -73,7 +73,8 @@ void DevicePipeline::enqueue_devplan(const char* host, u64 len0, const DelimMask
     if (nl) n = (u64)(static_cast<const char*>(nl) - host) + 1;
   }
   launch_map_fast(dev_text ? dev_text : d_text, n, dm, cfg.emits_per_line, cfg.max_key_len,
-                  plan_keys, nullptr, kPlanCap, d_plan_ctr, lb_map, stream);
+                  plan_keys, nullptr, kPlanCap, d_plan_ctr, lb_map, stream, nullptr, nullptr,
+                  PartMap{}, false, nullptr, nullptr, nullptr, cfg.ngram);
   launch_dict_insert(plan_keys, nullptr, &d_plan_ctr->num_records, kPlanCap, plan_dict,
                      d_plan_ctr, stream);
   launch_part_plan(plan_dict.ukeys.w[0], plan_dict.ucount, &d_plan_ctr->num_unique,
@@ -265,6 +266,9 @@ DevicePipeline::DevicePipeline(const JobConfig& c, u64 max_bytes, u64 max_lines,
   LOCUST_CHECK_ARG(cfg.emits_per_line > 0, "emits_per_line must be > 0");
   LOCUST_CHECK_ARG(cfg.max_key_len > 0 && cfg.max_key_len <= kKeyBytes - 1,
                    "max_key_len must be in [1, 31]");
+  check_ngram(cfg);
+  LOCUST_CHECK_ARG(cfg.ngram == 1 || cfg.map_path == MapPath::kFast,
+                   "ngram > 1 needs the fast map (map_path fast): the compat map emits words only");
   // construction phases, logged at LOCUST_LOG=debug (the cold CLI breakdown's engine_ms)
   u64 tc[6] = {now_ns(), 0, 0, 0, 0, 0};
   LOCUST_HIP_CHECK(hipSetDevice(cfg.device));
@@ -807,7 +811,8 @@ void DevicePipeline::enqueue_map(const TextInput& in) {
       launch_map_fast(d_text + off, len, dm, cfg.emits_per_line, cfg.max_key_len, tokens, d_parts,
                       cap, d_ctr, lb_map, stream, map_trace(),
                       part_tiles ? d_part_off + tile_off * kPartTable : nullptr, part_map(),
-                      /*large_tiles=*/true, map_combined ? d_counts : nullptr);
+                      /*large_tiles=*/true, map_combined ? d_counts : nullptr, nullptr, nullptr,
+                      cfg.ngram);
       const u64 t1 = tile_off + div_up(len, kMapTileBytesLarge);
       if (agg)
         launch_dict_partials(tokens, d_counts, d_part_off, (u32)tile_off, (u32)t1, 1, (u32)k,
@@ -838,7 +843,7 @@ void DevicePipeline::enqueue_map(const TextInput& in) {
                     cfg.emits_per_line, cfg.max_key_len, tokens, d_parts, cap, d_ctr, lb_map,
                     stream, map_trace(), part_tiles ? d_part_off : nullptr, part_map(), false,
                     map_combined ? d_counts : nullptr, plan_small() ? d_part_occ : nullptr,
-                    plan_small() && plan_trigger ? d_plan_flag : nullptr);
+                    plan_small() && plan_trigger ? d_plan_flag : nullptr, cfg.ngram);
   }
 }
 
@@ -1015,11 +1020,11 @@ void DevicePipeline::warm_first_job() {
   // small single-pass engines only: there the two-byte job launches the real job's kernels
   // (a large pass plans, pieces and aggregates differently)
   if (streaming || large_ordered || cfg.records_only || cfg.sort_path != SortPath::kDict ||
-      cfg.map_path != MapPath::kFast || cap_bytes < 2)
+      cfg.map_path != MapPath::kFast || cap_bytes < 2 * (u64)cfg.ngram)
     return;
   TextInput in;
   in.data = ensure_h_text();
-  in.bytes = 2;
+  in.bytes = 2 * (u64)cfg.ngram;  // one record: "a\n", or the n-gram "a a\n" / "a a a\n"
   in.num_lines = 1;
   if (!lean_job(in)) return;
   // one token: a byte outside the job's delimiter set
@@ -1027,8 +1032,10 @@ void DevicePipeline::warm_first_job() {
   for (const char* q = "aZ7xq"; *q && !c; ++q)
     if (cfg.delimiters.find(*q) == std::string::npos) c = *q;
   if (!c) return;
-  h_text[0] = c;
-  h_text[1] = '\n';
+  for (int g = 0; g < cfg.ngram; ++g) {
+    h_text[2 * g] = c;
+    h_text[2 * g + 1] = g + 1 < cfg.ngram && !cfg.delimiters.empty() ? cfg.delimiters[0] : '\n';
+  }
   // the engine's statistics describe the caller's jobs only
   const u64 fb = fallbacks, pp = planned_passes;
   warming = true;
@@ -1940,7 +1947,8 @@ void DevicePipeline::snapshot_window_counters() {
 void DevicePipeline::enqueue_map_window(const char* dtext, u64 len, const DelimMask& dm) {
   LOCUST_HIP_CHECK(hipMemsetAsync(d_sync, 0, sync_bytes, stream));
   launch_map_fast(dtext, len, dm, cfg.emits_per_line, cfg.max_key_len, tokens, nullptr, cap,
-                  d_ctr, lb_map, stream);
+                  d_ctr, lb_map, stream, nullptr, nullptr, PartMap{}, false, nullptr, nullptr,
+                  nullptr, cfg.ngram);
   snapshot_window_counters();
   launch_dict_insert(tokens, nullptr, &d_ctr->num_records, cap, dict, d_dctr, stream);
 }

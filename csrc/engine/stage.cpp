@@ -122,6 +122,9 @@ MapStageResult map_stage(const JobConfig& cfg_in, const std::string& file, const
   constexpr u64 kDefaultStreamChunk = 256ull << 20;
   const bool cpu = cfg_in.backend == Backend::kCpu;
   const bool lwin = !win.by_bytes && win.line_start >= 0;
+  LOCUST_CHECK_ARG(cfg_in.ngram == 1,
+                   "the stage split runs word jobs only (ngram 1): the text spill cannot carry "
+                   "keys with spaces");
   LOCUST_CHECK_ARG(!(win.by_bytes && cfg_in.ref_compat),
                    "a byte window is not a reference-compatible stage 1 (use a line window)");
   MapStageResult out;
@@ -230,6 +233,9 @@ WordCountResult reduce_spills(const JobConfig& cfg, const std::vector<std::strin
   LOCUST_CHECK_ARG(reducers >= 1 && reducer >= 0 && reducer < reducers,
                    "--reducer r/R needs 0 <= r < R");
   LOCUST_CHECK_ARG(!files.empty(), "no spill files to reduce");
+  LOCUST_CHECK_ARG(cfg.ngram == 1,
+                   "the stage split runs word jobs only (ngram 1): the text spill cannot carry "
+                   "keys with spaces");
   ReduceStageStats st;
   st.input_files = files.size();
   const u64 t0 = now_ns();

@@ -38,6 +38,9 @@ struct JobConfig {
   int emits_per_line = 20;                   // EMITS_PER_LINE (main.cu:19)
   int max_key_len = kMaxKeyLen;              // longer tokens are truncated and counted
   std::string delimiters = kDefaultDelims;   // main.cu:138
+  // Words per record: 1 = words; 2, 3 (kMaxNgram, engine.hpp) = the word n-grams of each
+  // line, joined by single spaces (fast map only).  emits_per_line caps a line's n-grams.
+  int ngram = 1;
   bool ref_compat = false;                   // reproduce B1: whole-file load drops last line
   ReducePath reduce_path = ReducePath::kLds;
   MapPath map_path = MapPath::kFast;

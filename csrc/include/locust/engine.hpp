@@ -273,6 +273,13 @@ class EntryVals {
 constexpr u32 kTopKMax = 4096;
 constexpr u32 kTopKTile = 2048;  // records per workgroup of the selection kernels
 
+// ---- word n-grams (JobConfig::ngram) ----
+// One record per n-gram of a line: N consecutive words joined by single 0x20 bytes.  N = 1
+// is the word job.  Every engine refuses a value outside [1, kMaxNgram].
+constexpr int kMaxNgram = 3;
+// Throws unless cfg.ngram is in [1, kMaxNgram] (the engine constructors' check).
+void check_ngram(const JobConfig& cfg);
+
 struct TopEntry {
   PackedKey key;
   u64 count;

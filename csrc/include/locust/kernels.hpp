@@ -119,7 +119,16 @@ void launch_map_fast(const char* text, u64 bytes, const DelimMask& dm, int emits
                      int max_key_len, KeysSoA out, u8* parts, u64 out_cap, MapCounters* ctr,
                      LookbackScratch lb, hipStream_t s, u64* trace = nullptr,
                      u32* part_off = nullptr, PartMap pm = PartMap{}, bool large_tiles = false,
-                     u64* counts = nullptr, u32* part_occ = nullptr, u32* plan_flag = nullptr);
+                     u64* counts = nullptr, u32* part_occ = nullptr, u32* plan_flag = nullptr,
+                     int ngram = 1);
+// The same map with one record per word n-gram of a line (ngram in [2, kMaxNgram]; what
+// launch_map_fast dispatches to, ngram.hip): the words joined by single 0x20 bytes, never
+// across a line end or a NUL, the key the first max_key_len bytes of the joined words.
+// Output contract and arguments as launch_map_fast.
+void launch_map_ngram(int ngram, const char* text, u64 bytes, const DelimMask& dm,
+                      int emits_per_line, int max_key_len, KeysSoA out, u8* parts, u64 out_cap,
+                      MapCounters* ctr, hipStream_t s, u64* trace, u32* part_off, PartMap pm,
+                      bool large_tiles, u64* counts, u32* part_occ, u32* plan_flag);
 
 // ---------------- radix_sort.hip ----------------
 constexpr int kSortBlock = 256;
@@ -557,6 +566,7 @@ void warm_module_dict();
 void warm_module_exchange();
 void warm_module_map();
 void warm_module_merge();
+void warm_module_ngram();
 void warm_module_partplan();
 void warm_module_psort();
 void warm_module_radix_sort();
@@ -573,6 +583,7 @@ inline void warm_kernel_modules() {
   warm_module_exchange();
   warm_module_map();
   warm_module_merge();
+  warm_module_ngram();
   warm_module_partplan();
   warm_module_psort();
   warm_module_radix_sort();

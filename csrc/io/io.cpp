@@ -1165,6 +1165,9 @@ std::string partmap_cache_path(const std::string& input, const JobConfig& cfg) {
   if (dir.empty() || !file_identity_hash(input, &h)) return "";
   const int tok[4] = {cfg.emits_per_line, cfg.max_key_len, (int)cfg.map_path, (int)cfg.sort_path};
   h = fnv1a(h, tok, sizeof(tok));
+  // a map tuned on a file's words is never applied to its n-grams (a word job's cache
+  // name stays what it was)
+  if (cfg.ngram != 1) h = fnv1a(h, &cfg.ngram, sizeof(cfg.ngram));
   h = fnv1a(h, cfg.delimiters.data(), cfg.delimiters.size());
   char name[64];
   std::snprintf(name, sizeof(name), "/partmap-%016llx.bin", (unsigned long long)h);

@@ -1,5 +1,5 @@
-// The fast map's tile (Map stage): the body of map_fast_kernel (tokenize.hip).  See
-// tokenize.hip for the algorithm.
+// The fast map's tile (Map stage): the body of map_fast_kernel (tokenize.hip) and, with
+// kGram > 1, of map_ngram_kernel (ngram.hip).  See tokenize.hip for the algorithm.
 #pragma once
 
 #include "locust/device/hash.hpp"
@@ -23,6 +23,10 @@ using dev::wave_id;
 // dependent host round trip in the middle of the map (tile timeline: masks up to 2.6 us).
 constexpr int kPre = 128;
 constexpr int kPost = 64;  // right overhang staged after the tile (>= 40 for packing)
+// The n-gram map (ngram.hip) stages a wider overhang: the later words of an n-gram that
+// starts at the end of a tile are then still LDS reads (whole Hamlet's longest bigram is 25
+// bytes); anything further goes through TileText::at to the text itself.
+constexpr int kPostGram = 128;
 
 // Delimiter set incl. '\n' and NUL (a NUL also kills the rest of its line, see
 // backward_line_ordinal), held in scalar registers.
@@ -126,6 +130,99 @@ __device__ __forceinline__ void pack_token(const unsigned char* s_text, int o, u
   }
 }
 
+// ---- word n-grams (kGram > 1, ngram.hip) ----
+// An n-gram is emitted at the start of its first word: kGram words of one line joined by
+// single 0x20 bytes, whatever delimiters stood between them.  A line end, a NUL or the end
+// of the text between two words ends the line's n-grams (bytes outside the text read as
+// '\n', see global_byte).
+
+// First set bit at position >= from of the 128-bit mask (lo, hi); 128 if there is none.
+__device__ __forceinline__ u32 first_set_from(u64 lo, u64 hi, u32 from) {
+  if (from < 64) {
+    const u64 m = lo & (~0ull << from);
+    if (m) return (u32)__ffsll((unsigned long long)m) - 1;
+    return hi ? 64u + (u32)__ffsll((unsigned long long)hi) - 1 : 128u;
+  }
+  if (from >= 128) return 128u;
+  const u64 m = hi & (~0ull << (from - 64));
+  return m ? 64u + (u32)__ffsll((unsigned long long)m) - 1 : 128u;
+}
+
+// Byte-wise walk over the n-gram whose first word starts at text position p (a live token
+// start): whether kGram words of the same line are there, and with kKey its big-endian
+// packed key (the first max_key bytes of the joined words) and its full joined length.
+// Every byte comes through TileText::at, so the walk is right wherever the words lie:
+// in the staged bytes, in the text beyond them (a delimiter run has no upper bound) or past
+// the end of the text.  The key words are built with static indices only (a dynamically
+// indexed u64[4] would live in private memory).
+template <int kGram, bool kKey, typename TT>
+__device__ __forceinline__ bool walk_gram(const TT& tt, const Delims& d, i64 p, u32 max_key,
+                                          u64* kw, u32* full_len) {
+  u64 k0 = 0, k1 = 0, k2 = 0, k3 = 0;
+  u32 k = 0;  // bytes of the joined n-gram so far
+  auto put = [&](u32 c) {
+    if (kKey && k < max_key) {
+      const u64 v = (u64)c << (56u - 8u * (k & 7u));
+      const u32 j = k >> 3;
+      k0 |= j == 0 ? v : 0ull;
+      k1 |= j == 1 ? v : 0ull;
+      k2 |= j == 2 ? v : 0ull;
+      k3 |= j == 3 ? v : 0ull;
+    }
+    ++k;
+  };
+  u32 c = tt.at(p);
+#pragma unroll
+  for (int g = 0; g < kGram; ++g) {
+    if (g) put((u32)' ');
+    do {  // the word's bytes (p is at a token start)
+      put(c);
+      c = tt.at(++p);
+    } while (!d.has(c));
+    if (g + 1 < kGram) {
+      do {  // the delimiter run up to the next word: no line end and no NUL in it
+        if (c == (u32)'\n' || c == 0u) return false;
+        c = tt.at(++p);
+      } while (d.has(c));
+    }
+  }
+  if (kKey) {
+    kw[0] = k0;
+    kw[1] = k1;
+    kw[2] = k2;
+    kw[3] = k3;
+    *full_len = k;
+  }
+  return true;
+}
+
+// Whether kGram - 1 further live token starts follow the one at this lane in its line, from
+// the step's ballot masks: dmask / brk (line end or NUL, both delimiters) of this step (d0,
+// b0) and the next 64 bytes (d1, b1).  What the 128-bit window cannot decide -- a word or a
+// delimiter run reaching past it -- is walked byte by byte.
+template <int kGram, typename TT>
+__device__ __forceinline__ bool gram_follows(const TT& tt, const Delims& d, i64 p, int lane, u64 d0,
+                                             u64 d1, u64 b0, u64 b1) {
+  u32 at = (u32)lane;
+  bool follows = true, undecided = false;
+#pragma unroll
+  for (int g = 1; g < kGram; ++g) {
+    if (follows && !undecided) {
+      const u32 e = first_set_from(d0, d1, at);  // the word's end
+      if (e == 128u) {
+        undecided = true;
+      } else {
+        const u32 nx = first_set_from(~d0, ~d1, e);  // the next word's start
+        if (first_set_from(b0, b1, e) < nx) follows = false;  // the line ends first
+        else if (nx == 128u) undecided = true;
+        at = nx;
+      }
+    }
+  }
+  if (undecided) follows = walk_gram<kGram, false>(tt, d, p, 0u, nullptr, nullptr);
+  return follows;
+}
+
 // Tokens of one partition in one 1 KiB tile from which the map asks the ordered kernel to
 // plan (split) the pass: whole Hamlet peaks at 27 under the starting map (most tiles below
 // 16), a pass whose keys crowd one partition puts ~150 there.
@@ -161,11 +258,11 @@ __device__ __forceinline__ u32 part_of_w0_skewed(const u64* s_plo, u64 w0) {
 // declared inside a device function are lowered to module scope, where every kernel of the
 // file that reaches any instantiation pays for all of them (map_fast_kernel<1, 1024> grew
 // from 4.4 to 37 KB of LDS that way).
-template <int kSteps, int kBlock>
+template <int kSteps, int kBlock, int kPostT = kPost>
 struct MapTileLds {
   static constexpr int kSeg = kSteps * 64;
   static constexpr int kTile = (kBlock / 64) * kSeg;
-  static constexpr int kStaged = kPre + kTile + kPost;
+  static constexpr int kStaged = kPre + kTile + kPostT;
   static constexpr bool kCombineTile = kSteps > 1;
   static constexpr int kListPerWave = kSteps > 1 ? kSeg / 2 : 1;
   __attribute__((aligned(16))) unsigned char text[kStaged];
@@ -186,10 +283,12 @@ struct MapTileLds {
 };
 
 // One map tile (the body of map_fast_kernel): kBlock threads, tile index `tile` (the
-// XCD-ordered block index of map_fast_kernel).
-template <int kSteps, int kBlock>
+// XCD-ordered block index of map_fast_kernel).  kGram > 1: one record per word n-gram of a
+// line (ngram.hip); which token starts emit and how a key is built differ, everything else
+// -- ordinals, slices, grouping, combining, counters -- is the word map's.
+template <int kSteps, int kBlock, int kGram = 1, int kPostT = kPost>
 __device__ __forceinline__ void map_tile(
-    MapTileLds<kSteps, kBlock>& lds, const u32 tile, const char* __restrict__ text, u64 bytes,
+    MapTileLds<kSteps, kBlock, kPostT>& lds, const u32 tile, const char* __restrict__ text, u64 bytes,
     const Delims& d, int E, int max_key, KeysSoA out, u8* __restrict__ parts, u64 out_cap,
     MapCounters* __restrict__ ctr, u64* __restrict__ trace, u32* __restrict__ part_off, PartMap pm,
     u64* __restrict__ counts, u32* __restrict__ part_occ, u32* __restrict__ plan_flag = nullptr) {
@@ -198,7 +297,7 @@ __device__ __forceinline__ void map_tile(
   const u64 t_entry = trace ? __builtin_amdgcn_s_memrealtime() : 0;
 #define MAP_STAMP(k_)                                                           \
   if (trace && threadIdx.x == 0 && tile < 4096) trace[(u64)tile * 8 + (k_)] = __builtin_amdgcn_s_memrealtime()
-  using L = MapTileLds<kSteps, kBlock>;
+  using L = MapTileLds<kSteps, kBlock, kPostT>;
   constexpr int kSeg = L::kSeg;
   constexpr int kTile = L::kTile;
   constexpr int kStaged = L::kStaged;
@@ -268,6 +367,14 @@ __device__ __forceinline__ void map_tile(
   u64 dmask[kSteps + 1];
   u32 emitted = 0, overflow = 0;
   const u64 below = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
+  // n-grams: the delimiter and line-break (line end or NUL) masks of the step and of the 64
+  // bytes after it (staged bytes outside the text are '\n')
+  u64 gd_cur = 0, gb_cur = 0;
+  if constexpr (kGram > 1) {
+    const u32 c0 = s_text[seg_lds + lane];
+    gd_cur = ballot(d.has(c0));
+    gb_cur = ballot(c0 == (u32)'\n' || c0 == 0u);
+  }
 #pragma unroll
   for (int s = 0; s < kSteps; ++s) {
     const i64 p = seg + s * 64 + lane;
@@ -295,8 +402,21 @@ __device__ __forceinline__ void map_tile(
     } else {
       ord = line_ord + __popcll(st & below);
     }
-    const bool emit = start && ord < (u32)E;
-    overflow += __popcll(ballot(start && ord == (u32)E));
+    bool emit = start && ord < (u32)E;
+    bool over = start && ord == (u32)E;
+    if constexpr (kGram > 1) {
+      const u32 cn = s_text[seg_lds + (s + 1) * 64 + lane];
+      const u64 gd_next = ballot(d.has(cn));
+      const u64 gb_next = ballot(cn == (u32)'\n' || cn == 0u);
+      if (emit || over) {
+        const bool follows = gram_follows<kGram>(tt, d, p, lane, gd_cur, gd_next, gb_cur, gb_next);
+        emit = emit && follows;
+        over = over && follows;
+      }
+      gd_cur = gd_next;
+      gb_cur = gb_next;
+    }
+    overflow += __popcll(ballot(over));
     emit_mask[s] = ballot(emit);
     emitted += __popcll(emit_mask[s]);
     if (nl) {
@@ -323,8 +443,12 @@ __device__ __forceinline__ void map_tile(
       u64 kw[kKeyWords] = {0, 0, 0, 0};
       u32 part = 0, loc = 0, len = 0;
       if (em) {
-        len = token_length(dmask[0], dmask[1], lane);
-        pack_token(s_text, seg_lds + lane, len < (u32)max_key ? len : (u32)max_key, kw);
+        if constexpr (kGram > 1) {
+          walk_gram<kGram, true>(tt, d, seg + lane, (u32)max_key, kw, &len);
+        } else {
+          len = token_length(dmask[0], dmask[1], lane);
+          pack_token(s_text, seg_lds + lane, len < (u32)max_key ? len : (u32)max_key, kw);
+        }
         part = part_of(kw[0]);
         loc = atomicAdd(&s_pcnt[part], 1u);
       }
@@ -425,7 +549,8 @@ __device__ __forceinline__ void map_tile(
       for (int s = 0; s < kSteps; ++s) {
         const u64 m = emit_mask[s];
         if ((m >> lane) & 1ull) {
-          const u32 len = token_length(dmask[s], dmask[s + 1], lane);
+          // (an n-gram's entry is its offset alone: both sweeps walk it again)
+          const u32 len = kGram > 1 ? 0u : token_length(dmask[s], dmask[s + 1], lane);
           my_list[n_w + lanes_below(m)] =
               (u32)(seg_lds + s * 64 + lane) | ((len < 255u ? len : 255u) << 16);
         }
@@ -442,9 +567,12 @@ __device__ __forceinline__ void map_tile(
         if ((u32)r * 64 >= n_w) break;  // wave-uniform
         if (i < n_w) {
           const u32 e = my_list[i];
-          const u32 len = e >> 16;
+          u32 len = e >> 16;
           u64 kw[kKeyWords];
-          pack_token(s_text, (int)(e & 0xffffu), len < (u32)max_key ? len : (u32)max_key, kw);
+          if constexpr (kGram > 1)
+            walk_gram<kGram, true>(tt, d, lo + (i64)(e & 0xffffu), (u32)max_key, kw, &len);
+          else
+            pack_token(s_text, (int)(e & 0xffffu), len < (u32)max_key ? len : (u32)max_key, kw);
           const u32 part = part_of(kw[0]);
           bool folded = false;
           if (combine && (kw[0] & 0xffull) == 0) {  // a one-word key
@@ -512,14 +640,17 @@ __device__ __forceinline__ void map_tile(
         if ((u32)r * 64 >= n_w) break;  // wave-uniform
         if (i < n_w) {
           const u32 e = my_list[i];
-          const u32 len = e >> 16;
+          u32 len = e >> 16;
+          u64 kw[kKeyWords];
+          if constexpr (kGram > 1)
+            walk_gram<kGram, true>(tt, d, lo + (i64)(e & 0xffffu), (u32)max_key, kw, &len);
           if (len > (u32)max_key) ++trunc;
           maxlen = len > maxlen ? len : maxlen;
           const u32 rank = info[r] & 0xffffu;
           if (rank == kCombined) continue;
           const u32 part = info[r] >> 16;
-          u64 kw[kKeyWords];
-          pack_token(s_text, (int)(e & 0xffffu), len < (u32)max_key ? len : (u32)max_key, kw);
+          if constexpr (kGram == 1)
+            pack_token(s_text, (int)(e & 0xffffu), len < (u32)max_key ? len : (u32)max_key, kw);
           const u64 idx = gprefix + s_pcnt[part] + (combine && s_hotc[part] ? 1u : 0u) + rank;
           if (idx < out_cap) {
 #pragma unroll
@@ -545,11 +676,16 @@ __device__ __forceinline__ void map_tile(
     const u64 m = emit_mask[s];
     if (m & (1ull << lane)) {
       const u64 idx = dst + lanes_below(m);
-      const u32 len = token_length(dmask[s], dmask[s + 1], lane);
+      u32 len;
+      u64 kw[kKeyWords];
+      if constexpr (kGram > 1) {
+        walk_gram<kGram, true>(tt, d, seg + s * 64 + lane, (u32)max_key, kw, &len);
+      } else {
+        len = token_length(dmask[s], dmask[s + 1], lane);
+        pack_token(s_text, seg_lds + s * 64 + lane, len < (u32)max_key ? len : (u32)max_key, kw);
+      }
       if (len > (u32)max_key) ++trunc;
       maxlen = len > maxlen ? len : maxlen;
-      u64 kw[kKeyWords];
-      pack_token(s_text, seg_lds + s * 64 + lane, len < (u32)max_key ? len : (u32)max_key, kw);
       if (idx < out_cap) {
 #pragma unroll
         for (int j = 0; j < kKeyWords; ++j) out.w[j][idx] = kw[j];

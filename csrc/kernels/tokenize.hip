@@ -56,8 +56,13 @@ void launch_map_fast(const char* text, u64 bytes, const DelimMask& dm, int emits
                      int max_key_len, KeysSoA out, u8* parts, u64 out_cap, MapCounters* ctr,
                      LookbackScratch lb, hipStream_t s, u64* trace, u32* part_off,
                      PartMap pm, bool large_tiles, u64* counts, u32* part_occ,
-                     u32* plan_flag) {
+                     u32* plan_flag, int ngram) {
   if (bytes == 0) return;
+  if (ngram != 1) {  // word n-grams: the same tile with its own kernels (ngram.hip)
+    launch_map_ngram(ngram, text, bytes, dm, emits_per_line, max_key_len, out, parts, out_cap, ctr,
+                     s, trace, part_off, pm, large_tiles, counts, part_occ, plan_flag);
+    return;
+  }
   const Delims d{dm.m[0] | 1ull | (1ull << '\n'), dm.m[1], dm.m[2], dm.m[3]};
   if (bytes < kMapLargeInput && !large_tiles) {
     // Small inputs: 1 KiB tiles as 16 waves x ONE 64-byte step -- the same text per

@@ -507,6 +507,7 @@ PYBIND11_MODULE(_locust, m) {
       .def_readwrite("device", &JobConfig::device)
       .def_readwrite("emits_per_line", &JobConfig::emits_per_line)
       .def_readwrite("max_key_len", &JobConfig::max_key_len)
+      .def_readwrite("ngram", &JobConfig::ngram)
       .def_readwrite("delimiters", &JobConfig::delimiters)
       .def_readwrite("ref_compat", &JobConfig::ref_compat)
       .def_readwrite("reduce_path", &JobConfig::reduce_path)
@@ -609,6 +610,7 @@ PYBIND11_MODULE(_locust, m) {
       .def_property_readonly("wire_bytes", [](const PyTopResult& p) { return p.t.wire_bytes; },
                              "bytes the device wrote to host memory for the result");
   m.attr("kTopKMax") = kTopKMax;
+  m.attr("kMaxNgram") = kMaxNgram;
   m.attr("kTopKTile") = kTopKTile;
 
   py::class_<PyGpuEngine>(m, "GpuEngine")

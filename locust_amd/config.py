@@ -36,6 +36,7 @@ def make_config(
     zero_copy_text: int | None = None,
     graph: int | None = None,
     ref_timers: bool = False,
+    ngram: int = 1,
 ):
     """Build a native ``JobConfig``.  ``None`` means: environment override or default."""
     cfg = _C.JobConfig()
@@ -67,6 +68,8 @@ def make_config(
         graph = int(os.environ.get("LOCUST_GRAPH", "-1"))
     cfg.graph = graph
     cfg.ref_timers = ref_timers
+    # 1: words; 2, 3 (_C.kMaxNgram): the word n-grams of each line (the engines refuse others)
+    cfg.ngram = ngram
     return cfg
 
 

@@ -4,6 +4,8 @@ Shares no code with the native engine: tokenization is a direct re-statement of 
 ``strtok_r`` semantics over the reference's delimiter set (main.cu:138), with the
 20-emit cap (main.cu:141) and key truncation at 29 bytes.  Sorting is Python's bytes
 order == unsigned-byte lexicographic == the reference's KIVComparator (KeyValue.h:20-33).
+Word n-grams (``ngrams``, ``wordcount(..., ngram=N)``) are stated here once; every engine
+matches them exactly.
 """
 from __future__ import annotations
 
@@ -39,19 +41,46 @@ def tokenize(line: bytes, delims: bytes = DEFAULT_DELIMS, emits: int = 20,
     return [t[:max_key] for t in out[:emits]], dropped
 
 
-def wordcount(text: bytes, delims: bytes = DEFAULT_DELIMS, emits: int = 20, max_key: int = 29):
-    """Returns (entries, num_tokens, overflow_lines): entries = [(key, val, count)] sorted."""
+def ngrams(line: bytes, n: int, delims: bytes = DEFAULT_DELIMS, emits: int = 20,
+           max_key: int = 29) -> tuple[list[bytes], bool, int]:
+    """The word n-grams of one line: (keys, overflow, truncated).
+
+    The line's tokens t0 .. t(T-1) are taken uncapped and untruncated; the n-grams are
+    g_i = t_i + b" " + ... + b" " + t_(i+n-1) for i = 0 .. T-n (none if T < n), always
+    joined by one 0x20 byte whatever stood between the tokens.  The first ``emits`` of
+    them are emitted, each as the first ``max_key`` bytes of g_i; ``overflow`` says the
+    line had more, ``truncated`` counts the emitted n-grams longer than ``max_key``.
+    n = 1 gives the tokens themselves."""
+    if not 1 <= n <= 3:
+        raise ValueError("ngram must be in [1, 3]")
+    toks, _ = tokenize(line, delims, emits=len(line) + 1, max_key=len(line) + 1)
+    grams = [b" ".join(toks[i:i + n]) for i in range(len(toks) - n + 1)]
+    emitted = grams[:emits]
+    return ([g[:max_key] for g in emitted], len(grams) > emits,
+            sum(len(g) > max_key for g in emitted))
+
+
+def wordcount(text: bytes, delims: bytes = DEFAULT_DELIMS, emits: int = 20, max_key: int = 29,
+              ngram: int = 1, stats: bool = False):
+    """Returns (entries, num_tokens, overflow_lines): entries = [(key, val, count)] sorted.
+    ``ngram`` = 2, 3: one record per word n-gram of a line (see ``ngrams``); num_tokens then
+    counts the emitted n-grams.  ``stats=True`` appends the number of truncated records:
+    (entries, num_tokens, overflow_lines, truncated)."""
     counter: Counter = Counter()
     overflow = 0
+    truncated = 0
     for line in split_lines(text):
-        toks, dropped = tokenize(line, delims, emits, max_key)
+        toks, dropped, trunc = ngrams(line, ngram, delims, emits, max_key)
         counter.update(toks)
         overflow += dropped
+        truncated += trunc
     entries = []
     pos = 0
     for key in sorted(counter):
         entries.append((key, pos, counter[key]))
         pos += counter[key]
+    if stats:
+        return entries, pos, overflow, truncated
     return entries, pos, overflow
 
 

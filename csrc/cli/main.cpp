@@ -16,6 +16,7 @@
 //   --ref-timers (stage times taken where the reference's host timers were)
 //   --top K (the K most frequent words instead of the whole dictionary, rank order)
 //   --ngram N (count the word N-grams of each line, N <= 3, instead of its words)
+//   --index (the inverted index: every word with the lines it occurs on)
 // and a synthetic-text generator (BASELINE configs "1M lines" / "10 GB"):
 //   MapReduce --gen FILE (--gen-lines N | --gen-bytes N) [--seed S] [--vocab V]
 #include <sys/stat.h>
@@ -80,6 +81,7 @@ struct CliArgs {
   std::string export_kiv;  // final results as KeyIntValuePair records (--export-kiv FILE)
   bool quiet = false;
   u64 top = 0;  // --top K: the result lines are the K most frequent words (0: all)
+  bool index = false;  // --index: the result lines carry every word's line numbers
   std::string gen_out;  // generator mode
   GenSpec gen;
 };
@@ -113,6 +115,11 @@ void help() {
       "                             line joined by single spaces; never across a line end.  A\n"
       "                             key is the first --max-key bytes of the joined words.  Not\n"
       "                             with --map-path compat or the stage split)\n"
+      "  --index                    (inverted index: after each word its count and the 0-based\n"
+      "                             numbers of the lines it occurs on, one per occurrence; whole\n"
+      "                             one-pass jobs on one GPU or --backend cpu.  Not with --top,\n"
+      "                             --ngram N > 1, the stage split, --gpus N > 1, --chunk-mb,\n"
+      "                             --sort radix or --map-path compat)\n"
       "  --help\n"
       "\n"
       "Environment: LOCUST_LOG=info|debug and the LOCUST_* switches in docs/ENVIRONMENT.md.\n",
@@ -231,6 +238,8 @@ bool parse(int argc, char** argv, CliArgs* a) {
       const long long k = std::strtoll(v.c_str(), &endp, 10);
       if (v.empty() || *endp || k < 1) throw Error("--top K needs an integer K >= 1");
       a->top = (u64)k;
+    } else if (s == "--index") {
+      a->index = true;
     } else if (s == "--ngram") {
       const std::string v = need("--ngram");
       char* endp = nullptr;
@@ -285,6 +294,26 @@ bool parse(int argc, char** argv, CliArgs* a) {
                   "--stage, --inputs, --reducer)");
     if (a->cfg.backend == Backend::kGpu && a->cfg.map_path == MapPath::kCompat)
       throw Error("--ngram N > 1 needs the fast map (map_path fast), not --map-path compat");
+  }
+  if (a->index) {
+    if (a->top) throw Error("--index and --top do not combine: an index lists every word");
+    if (a->cfg.ngram > 1)
+      throw Error("--index builds word keys only: not with --ngram N > 1");
+    if (a->stage != 0 || !a->inputs.empty() || a->reducers > 1)
+      throw Error("--index runs whole jobs only: not with the stage split (stage 1 or 2, "
+                  "--stage, --inputs, --reducer)");
+    if (a->gpus > 1)
+      throw Error("--index runs on one GPU or the CPU: not with --gpus N > 1");
+    if (a->cfg.chunk_bytes)
+      throw Error("--index takes one device pass: not with --chunk-mb (a streamed index is "
+                  "not built; use --backend cpu for larger inputs)");
+    if (!a->export_kiv.empty()) throw Error("--index and --export-kiv do not combine");
+    if (a->cfg.ref_timers) throw Error("--index and --ref-timers do not combine");
+    if (a->cfg.backend == Backend::kGpu && a->cfg.sort_path == SortPath::kRadix)
+      throw Error("--index on the GPU needs the dictionary path (--sort dict), not --sort radix");
+    if (a->cfg.backend == Backend::kGpu && a->cfg.map_path == MapPath::kCompat)
+      throw Error("--index on the GPU needs the fast map (map_path fast), not --map-path "
+                  "compat: the compat map overwrites the text the index reads again");
   }
   if (a->byte_range) {
     if (a->stage != 1) throw Error("--byte-range is a stage-1 (map) flag");
@@ -413,6 +442,19 @@ void json_top(JsonOut& j, const CliArgs& a) {
   }
 }
 
+// --index: "index": true in the record, the postings' number, and where the device built
+// it its device time and the bytes it wrote to host memory for the result.
+const IndexResult* g_index = nullptr;
+void json_index(JsonOut& j, const CliArgs& a) {
+  if (!a.index) return;
+  j.kv("index", "true");
+  if (g_index) {
+    j.num("index_ms", g_index->index_ms);
+    j.u("postings", g_index->postings.size());
+    j.u("wire_bytes", g_index->wire_bytes);
+  }
+}
+
 // The statistics of a top result as a WordCountResult without entries (json, timer lines).
 WordCountResult top_stats(const TopResult& t) {
   WordCountResult r;
@@ -446,6 +488,7 @@ void write_json(const CliArgs& a, const WordCountResult& r, const std::vector<do
   j.kv("iters", std::to_string(w.size()));
   j.u("chunks", r.chunks);
   json_top(j, a);
+  json_index(j, a);
   if (g_part_map) j.str("part_map", g_part_map);  // the one-shot CLI's starting map
   if (g_engine_stats_set) json_hbm(j, g_engine_stats);
   // peak resident memory of this process image (VmHWM: unlike getrusage's ru_maxrss it is
@@ -610,8 +653,9 @@ void emit_results(const CliArgs& a, const std::string& out) {
 }
 
 // `top` (--top K on one GPU): the device selected; r then carries the statistics only.
+// `idx` (--index): the result lines are the index's.
 void print_gpu_result(const CliArgs& a, const WordCountResult& r, const std::vector<double>& walls,
-                      const TopResult* top = nullptr) {
+                      const TopResult* top = nullptr, const IndexResult* idx = nullptr) {
   const bool rt = a.cfg.ref_timers;
   std::printf("GPU mapping %lld nanoseconds \n", ns(rt ? r.times.ref_map_ms : r.times.map_ms));
   for (u64 k = 0; k < r.overflow_lines; ++k) std::printf("WARN: Exceeded emit limit\n");
@@ -622,13 +666,17 @@ void print_gpu_result(const CliArgs& a, const WordCountResult& r, const std::vec
     LOCUST_LOG_WARN("%llu tokens longer than %d chars were truncated",
                     (unsigned long long)r.truncated, a.cfg.max_key_len);
   std::string out;
-  if (top)
+  if (idx) {
+    if (!a.quiet) format_index_output(*idx, &out);
+  } else if (top) {
     format_top(a, false, *top, &out);
-  else
+  } else {
     format_results(a, false, r, &out);
+  }
   emit_results(a, out);
   std::fflush(stdout);
   g_top_device = top;
+  g_index = idx;
   write_json(a, r, walls);
   if (!a.export_kiv.empty()) write_kiv_results(a.export_kiv, r);
   std::printf("\nDone\n");
@@ -902,7 +950,7 @@ int run(const CliArgs& a) {
   // one device pass, streamed through two pinned chunks (host memory stays bounded).
   const bool direct = !cpu && !use_window && a.stage == 0 && !a.gpus_given && a.gpus <= 1 &&
                       !a.cfg.ref_compat && a.cfg.map_path == MapPath::kFast &&
-                      a.cfg.sort_path == SortPath::kDict;
+                      a.cfg.sort_path == SortPath::kDict && !a.index;
   if (direct) return run_direct(a);
   // ---------------- multi-GPU in one process (one thread per rank) ----------------------
   // An explicit --gpus N (N >= 1) runs N ranks.  --comm auto: an ncclCommInitAll clique
@@ -910,7 +958,7 @@ int run(const CliArgs& a) {
   // (one rank, or N ranks rehearsed on fewer GPUs); --comm rccl / loopback force either.
   // A whole file is never loaded: every rank reads only its own line-aligned byte range
   // (run_single_process_file); a line window is loaded first, then sharded.
-  const bool multi = (a.gpus > 1 || (a.gpus_given && !cpu)) && a.stage == 0;
+  const bool multi = (a.gpus > 1 || (a.gpus_given && !cpu)) && a.stage == 0 && !a.index;
   // (the compat map sizes its slots per line: its ranks get the loaded text, whose line
   // count is exact, not a file range sized by bytes)
   const bool file_ranks = multi && !use_window && !a.cfg.ref_compat &&
@@ -951,12 +999,16 @@ int run(const CliArgs& a) {
   // ---------------- stage 0: full pipeline ----------------
   WordCountResult r;
   TopResult cpu_top;  // --top K on the CPU backend
+  IndexResult cpu_index;  // --index on the CPU backend
   std::vector<double> walls;
   if (cpu) {
     CpuWordCount eng(a.cfg);
     for (int i = 0; i < a.warmup; ++i) eng.run(text.input);
     for (int i = 0; i < a.iters; ++i) {
-      if (a.top) {
+      if (a.index) {
+        cpu_index = eng.run_index(text.input);
+        r = cpu_index.words;
+      } else if (a.top) {
         cpu_top = eng.run_top(text.input, a.top);
         r = top_stats(cpu_top);
       } else {
@@ -969,6 +1021,15 @@ int run(const CliArgs& a) {
     std::printf("CPU reducing %lld nanoseconds \n", ns(r.times.reduce_ms));
   } else {
     GpuWordCount eng(a.cfg, text.input.bytes, text.input.num_lines);
+    if (a.index) {  // the word job, then the index stage behind it on the device
+      IndexResult x;
+      for (int i = 0; i < a.warmup + a.iters; ++i) {
+        x = eng.run_index(text.input);
+        if (i >= a.warmup) walls.push_back(x.words.times.wall_ms);
+      }
+      print_gpu_result(a, x.words, walls, nullptr, &x);
+      return 0;
+    }
     if (a.top) {  // the selection runs on the device: only the winners come back
       TopResult top;
       for (int i = 0; i < a.warmup + a.iters; ++i) {
@@ -990,10 +1051,14 @@ int run(const CliArgs& a) {
     LOCUST_LOG_WARN("%llu tokens longer than %d chars were truncated",
                     (unsigned long long)r.truncated, a.cfg.max_key_len);
   std::string out;
-  if (a.top)
+  if (a.index) {
+    if (!a.quiet) format_index_output(cpu_index, &out);
+    g_index = &cpu_index;
+  } else if (a.top) {
     format_top(a, cpu, cpu_top, &out);
-  else
+  } else {
     format_results(a, cpu, r, &out);
+  }
   emit_results(a, out);
   write_json(a, r, walls);
   if (!a.export_kiv.empty()) write_kiv_results(a.export_kiv, r);

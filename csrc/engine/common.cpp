@@ -326,4 +326,50 @@ void format_top_output(const TopResult& t, bool cpu_format, std::string* out) {
   }
 }
 
+// ---- inverted index (engine.hpp) ----
+void validate_index(const IndexResult& r) {
+  validate_result(r.words);
+  if (r.postings.size() != r.words.num_tokens)
+    throw Error("LOCUST_CHECK: index has " + std::to_string(r.postings.size()) +
+                " postings, num_tokens=" + std::to_string(r.words.num_tokens));
+  const u64 lo = r.first_line, hi = r.first_line + r.words.num_lines;
+  u64 at = 0, j = 0;
+  for (const WordCountEntry e : r.words.entries) {
+    for (u64 k = 0; k < e.count; ++k) {
+      const u64 l = r.postings[at + k];
+      if (l < lo || l >= hi)
+        throw Error("LOCUST_CHECK: posting " + std::to_string(l) + " of entry " +
+                    std::to_string(j) + " outside the lines [" + std::to_string(lo) + ", " +
+                    std::to_string(hi) + ")");
+      if (k && l < r.postings[at + k - 1])
+        throw Error("LOCUST_CHECK: postings of entry " + std::to_string(j) +
+                    " decrease at position " + std::to_string(k));
+    }
+    at += e.count;
+    ++j;
+  }
+}
+
+void format_index_output(const IndexResult& r, std::string* out) {
+  out->reserve(out->size() + r.words.entries.size() * 40 + r.postings.size() * 6);
+  char buf[kKeyBytes + 1];
+  u64 at = 0;
+  for (const WordCountEntry e : r.words.entries) {  // either entry form
+    const int n = unpack_key(e.key.w, buf);
+    const u64 from = at;
+    at += e.count;
+    if (n == 0) continue;
+    out->append("print key: ");
+    out->append(buf, (size_t)n);
+    out->append(" \t count: ");
+    out->append(std::to_string(e.count));
+    out->append(" \t lines:");
+    for (u64 k = from; k < at && k < r.postings.size(); ++k) {
+      out->push_back(' ');
+      out->append(std::to_string(r.postings[k]));
+    }
+    out->push_back('\n');
+  }
+}
+
 }  // namespace locust

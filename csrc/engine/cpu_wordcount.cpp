@@ -77,6 +77,63 @@ TopResult CpuWordCount::run_top(const TextInput& in, u64 k) {
   return t;
 }
 
+IndexResult CpuWordCount::run_index(const TextInput& in) {
+  LOCUST_CHECK_ARG(cfg_.ngram == 1,
+                   "an index job builds word keys only (ngram 1): run it without ngram");
+  LOCUST_CHECK_ARG(in.first_line + in.num_lines <= (1ull << 32),
+                   "index: line numbers past 2^32 do not fit a u32 posting");
+  IndexResult x;
+  x.first_line = in.first_line;
+  WordCountResult& r = x.words;
+  r.num_lines = in.num_lines;
+  // map: every emitted token with its line
+  std::vector<PackedKey> toks;
+  std::vector<u32> tok_line;
+  const u64 t0 = now_ns();
+  {
+    const char* p = in.data;
+    const char* end = in.data + in.bytes;
+    u64 line = in.first_line;
+    while (p < end) {
+      const char* nl = static_cast<const char*>(memchr(p, '\n', (size_t)(end - p)));
+      const char* le = nl ? nl : end;
+      r.overflow_lines += (u64)tokenize_line(p, (u64)(le - p), cfg_, &toks, &r.truncated);
+      tok_line.resize(toks.size(), (u32)line);
+      ++line;
+      p = nl ? nl + 1 : end;
+    }
+  }
+  const u64 t1 = now_ns();
+  // process: a stable sort by key keeps each word's lines in text order = ascending
+  std::vector<u32> order(toks.size());
+  for (size_t i = 0; i < order.size(); ++i) order[i] = (u32)i;
+  std::stable_sort(order.begin(), order.end(),
+                   [&](u32 a, u32 b) { return key_less(toks[a], toks[b]); });
+  const u64 t2 = now_ns();
+  // reduce: runs of equal keys -> entries; the lines in sorted order are the postings
+  std::vector<WordCountEntry> e;
+  x.postings.resize(order.size());
+  for (size_t i = 0; i < order.size(); ++i) {
+    const PackedKey& k = toks[order[i]];
+    x.postings[i] = tok_line[order[i]];
+    if (e.empty() || key_compare(e.back().key.w, k.w) != 0)
+      e.push_back(WordCountEntry{k, 1});
+    else
+      ++e.back().count;
+  }
+  r.entries = std::move(e);
+  r.num_unique = r.entries.size();
+  r.num_tokens = toks.size();
+  const u64 t3 = now_ns();
+  r.max_key_len = max_len(toks);
+  r.times.map_ms = (t1 - t0) * 1e-6;
+  r.times.process_ms = (t2 - t1) * 1e-6;
+  r.times.reduce_ms = (t3 - t2) * 1e-6;
+  r.times.wall_ms = (t3 - t0) * 1e-6;
+  if (cfg_.check) validate_index(x);
+  return x;
+}
+
 std::vector<PackedKey> CpuWordCount::run_map_stage(const TextInput& in, WordCountResult* stats) {
   WordCountResult r;
   r.num_lines = in.num_lines;

@@ -38,6 +38,7 @@ TopResult GpuWordCount::run_top_source(TextSource& src, u32 k) {
 TopResult GpuWordCount::top_counts(const KeyCount* recs, u64 n, u32 k) {
   return impl_->top_counts(recs, n, k);
 }
+IndexResult GpuWordCount::run_index(const TextInput& in) { return impl_->run_index(in); }
 GpuWordCount::Stats GpuWordCount::stats() const {
   Stats s;
   s.retunes = impl_->pm_retunes;

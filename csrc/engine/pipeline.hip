@@ -27,6 +27,7 @@ u64 DevicePipeline::pinned_bytes() const {
   b += h_keys_cap * kKeyWords * sizeof(u64);
   b += h_chunk_cap * sizeof(MapCounters);
   if (h_top) b += (kTopKMax + 1) * sizeof(TopRecord);
+  if (h_ictr) b += h_post_cap * sizeof(u32) + sizeof(IndexCounters);
   b += 2 * sizeof(MapCounters) + sizeof(SortPlan) + 2 * sizeof(PartMapTables) +
        kMaxSamples * sizeof(PackedKey) + (kMaxRanks + 8) * sizeof(u64) + 64 +
        kDictParts * sizeof(u32);
@@ -258,6 +259,7 @@ u64 DevicePipeline::device_bytes() const {
   if (d_text_alt) b += cap_bytes + 64;
   if (d_plan) b += plan_zero_bytes;  // (+ the plan's key arrays: small)
   b += topk_bytes;                   // (0 until the first top job)
+  b += index_bytes;                  // (0 until the first index job)
   return b;
 }
 
@@ -541,6 +543,11 @@ DevicePipeline::~DevicePipeline() {
   if (d_topk) (void)hipFree(d_topk);
   pinned_free(h_top);
   for (auto& e : ev_top)
+    if (e) (void)hipEventDestroy(e);
+  if (d_index) (void)hipFree(d_index);
+  pinned_free(h_post);
+  pinned_free(h_ictr);
+  for (auto& e : ev_index)
     if (e) (void)hipEventDestroy(e);
 }
 
@@ -1832,6 +1839,156 @@ TopResult DevicePipeline::top_counts(const KeyCount* recs, u64 n, u32 k) {
   t.times.wall_ms = (now_ns() - t0) * 1e-6;
   if (cfg.check) validate_top(t);
   return t;
+}
+
+// =====================================================================================
+// Inverted index
+// =====================================================================================
+void DevicePipeline::ensure_index(u64 tokens, u64 n) {
+  if (!h_ictr) {
+    // first index job of this engine: the pinned counters and the events
+    h_ictr = static_cast<IndexCounters*>(
+        pinned_alloc(sizeof(IndexCounters), hipHostMallocDefault, "index counters"));
+    for (auto& e : ev_index) LOCUST_HIP_CHECK(hipEventCreate(&e));
+  }
+  if (h_post_cap < tokens) {
+    sync();  // (no copy into the old buffer is in flight: every job ends synchronised)
+    pinned_free(h_post);
+    h_post = nullptr;
+    h_post_cap = align_up(std::max<u64>(tokens, 1), (u64)kSortTile);
+    h_post = static_cast<u32*>(
+        pinned_alloc(h_post_cap * sizeof(u32), hipHostMallocDefault, "index postings"));
+  }
+  if (index.pair_cap >= std::max<u64>(tokens, 1) && index.rec_cap >= std::max<u64>(n, 1)) return;
+  sync();  // nothing in flight may still use the workspace being replaced
+  if (d_index) LOCUST_HIP_CHECK(hipFree(d_index));
+  d_index = nullptr;
+  index = IndexWorkspace{};
+  index_bytes = 0;
+  // sized for this job (whole sort tiles: the sort zeroes its status words for the
+  // capacity, not for the job) and for what this engine's passes can hold otherwise
+  const u64 pair_cap = align_up(std::max<u64>(tokens, 1), (u64)kSortTile);
+  const u64 rec_cap = std::max<u64>({n, std::min<u64>(std::max(ucap, rcap), 1ull << 20), 1});
+  const u64 bytes = index_workspace_bytes(pair_cap, rec_cap, cap_lines, pass_bytes);
+  size_t fr = 0, tot = 0;
+  LOCUST_HIP_CHECK(hipMemGetInfo(&fr, &tot));
+  if ((double)bytes > kHbmUsable * (double)fr)
+    throw Error("index workspace (" + std::to_string(bytes) + " B needed for " +
+                std::to_string(pair_cap) + " tokens, " + std::to_string(rec_cap) +
+                " records and " + std::to_string(cap_lines) +
+                " lines) does not fit the free device memory (" + std::to_string(fr) +
+                " B free of " + std::to_string(tot) + " B)");
+  LOCUST_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&d_index), bytes));
+  index_bytes = bytes;
+  index_workspace_carve(d_index, pair_cap, rec_cap, cap_lines, pass_bytes, &index);
+  LOCUST_HIP_CHECK(hipMemsetAsync(index.zeros, 0, pair_cap * 8, stream));
+}
+
+void DevicePipeline::check_index_job(const TextInput& in) const {
+  LOCUST_CHECK_ARG(cfg.sort_path == SortPath::kDict,
+                   "an index job needs a dictionary engine (sort=dict), not sort=radix");
+  LOCUST_CHECK_ARG(cfg.map_path != MapPath::kCompat,
+                   "an index job needs the fast map (map_path fast): the compat map "
+                   "overwrites the delimiters of the device text, which the index stage "
+                   "tokenises again");
+  LOCUST_CHECK_ARG(cfg.ngram == 1,
+                   "an index job builds word keys only (ngram 1): run it without ngram");
+  LOCUST_CHECK_ARG(!cfg.ref_timers, "an index job does not take ref_timers");
+  LOCUST_CHECK_ARG(!cfg.records_only, "a records-only engine runs no text jobs");
+  LOCUST_CHECK_ARG(!in.source && in.bytes <= pass_bytes,
+                   "an index job takes one device pass (" + std::to_string(pass_bytes) +
+                       " B here), not a streamed input of " + std::to_string(in.bytes) +
+                       " B: use --backend cpu (the CPU engine indexes any size)");
+}
+
+IndexResult DevicePipeline::run_index(const TextInput& in) {
+  TraceRange tr("locust:index_job");
+  check_index_job(in);
+  check_input(in);
+  LOCUST_CHECK_ARG(in.first_line + in.num_lines <= (1ull << 32),
+                   "index: line numbers past 2^32 do not fit a u32 posting");
+  select_out();        // the previous result may still hold the last output buffer
+  sync_clean = false;  // this entry point dirties d_sync
+  IndexResult x;
+  x.first_line = in.first_line;
+  WordCountResult& r = x.words;
+  r.num_lines = in.num_lines;
+  const u64 t0 = now_ns();
+  // the word job, its records left in d_out (as a top job)
+  LOCUST_HIP_CHECK(hipEventRecord(ev[0], stream));
+  enqueue_upload(in);
+  LOCUST_HIP_CHECK(hipEventRecord(ev[1], stream));
+  enqueue_map(in);
+  LOCUST_HIP_CHECK(hipEventRecord(ev[2], stream));
+  enqueue_process_dict((u32)in.num_lines, false);
+  LOCUST_HIP_CHECK(hipEventRecord(ev[3], stream));
+  enqueue_emit_dict(/*mapped=*/false);
+  LOCUST_HIP_CHECK(hipEventRecord(ev[4], stream));
+  read_counters();  // (synchronises)
+  if (dict_fallback_needed()) {
+    // more distinct keys than the rank sort takes, or a full table: the radix path, which
+    // also ends in d_out
+    finish_dict_with_radix((u32)in.num_lines);
+    LOCUST_HIP_CHECK(hipEventRecord(ev[4], stream));
+    read_counters();
+  }
+  fill_counters(r);
+  const u64 n = h_ctr->num_unique, T = r.num_tokens;
+  LOCUST_CHECK_ARG(n <= rcap, "index: more distinct keys than the record buffer holds");
+  LOCUST_CHECK_ARG(n < (1ull << 32) && T < (1ull << 32),
+                   "index: " + std::to_string(n) + " words / " + std::to_string(T) +
+                       " tokens do not fit the 32-bit halves of a pair word");
+  // the index stage
+  ensure_index(T, n);
+  LOCUST_HIP_CHECK(hipEventRecord(ev_index[0], stream));
+  IndexJob job;
+  job.recs = d_out;
+  job.n = n;
+  job.tokens = T;
+  job.text = map_text;
+  job.bytes = in.bytes;
+  job.num_lines = in.num_lines;
+  job.first_line = in.first_line;
+  job.dm = make_delim_mask(cfg.delimiters.c_str());
+  job.emits_per_line = cfg.emits_per_line;
+  job.max_key_len = cfg.max_key_len;
+  launch_index(job, index, h_plan, stream);
+  if (T)
+    LOCUST_HIP_CHECK(hipMemcpyAsync(h_post, index.postings, T * sizeof(u32),
+                                    hipMemcpyDeviceToHost, stream));
+  LOCUST_HIP_CHECK(hipMemcpyAsync(h_ictr, index.ctr, sizeof(IndexCounters),
+                                  hipMemcpyDeviceToHost, stream));
+  LOCUST_HIP_CHECK(hipEventRecord(ev_index[1], stream));
+  // the n records, as run()'s fallback paths deliver them
+  grow_host_out(n);
+  if (n) launch_copy_to_mapped(d_out_mapped, d_out, n * sizeof(OutRecord), stream);
+  LOCUST_HIP_CHECK(hipEventRecord(ev[5], stream));
+  sync();
+  copy_out(r.entries, n);
+  const IndexCounters ic = *h_ictr;
+  if (ic.miss)
+    throw Error("index: " + std::to_string(ic.miss) + " of " + std::to_string(T) +
+                " tokens have a key that is not among the " + std::to_string(n) +
+                " records of the word job");
+  if (ic.written != T || ic.total != T)
+    throw Error("index: " + std::to_string(ic.written) + " pairs written, the records' counts "
+                "add up to " + std::to_string(ic.total) + ", the word job emitted " +
+                std::to_string(T) + " tokens");
+  if (ic.misplaced)
+    throw Error("index: " + std::to_string(ic.misplaced) + " of " + std::to_string(T) +
+                " sorted pairs lie outside their word's range");
+  x.postings.assign(h_post, h_post + T);
+  x.index_ms = ms_between(ev_index[0], ev_index[1]);
+  x.wire_bytes = T * sizeof(u32) + n * sizeof(OutRecord) + sizeof(IndexCounters);
+  r.times.h2d_ms = ms_between(ev[0], ev[1]);
+  r.times.map_ms = ms_between(ev[1], ev[2]);
+  r.times.process_ms = ms_between(ev[2], ev[3]);
+  r.times.reduce_ms = ms_between(ev[3], ev[4]);
+  r.times.d2h_ms = ms_between(ev_index[1], ev[5]);
+  r.times.gpu_ms = ms_between(ev[0], ev[5]);
+  r.times.wall_ms = (now_ns() - t0) * 1e-6;
+  if (cfg.check) validate_index(x);
+  return x;
 }
 
 bool DevicePipeline::host_pinned(const void* p) {

@@ -761,6 +761,24 @@ struct DevicePipeline {
   TopResult run_top_source(TextSource& src, u32 k);
   TopResult top_counts(const KeyCount* recs, u64 n, u32 k);
 
+  // ---- inverted index (kernels/index.hip) ----
+  // The index stage's workspace (pair words, val, newline positions, counters, the sort's
+  // own buffers), its pinned postings buffer and its events exist from the first index
+  // job on (ensure_index: checked against free HBM); a word job allocates nothing for it.
+  // d_out is the junction, as for a top job: the word job leaves its num_unique records
+  // there in key order, the stage reads them and `map_text` in place.
+  IndexWorkspace index{};
+  char* d_index = nullptr;
+  u64 index_bytes = 0;
+  u32* h_post = nullptr;  // pinned postings (one D2H per job)
+  u64 h_post_cap = 0;
+  IndexCounters* h_ictr = nullptr;  // pinned copy of the stage's counters
+  hipEvent_t ev_index[2] = {};
+  void ensure_index(u64 tokens, u64 n);
+  // Throws unless this engine's configuration and `in` suit an index job; launches nothing.
+  void check_index_job(const TextInput& in) const;
+  IndexResult run_index(const TextInput& in);
+
   // ---------------------------------------------------------------------------------
   // Streaming: an input larger than the engine's text capacity is processed in
   // line-aligned chunks of <= cap_bytes.  Chunk k+1's H2D runs on the copy

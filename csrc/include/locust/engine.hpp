@@ -314,6 +314,31 @@ void validate_top(const TopResult& t);
 // build's (format_gpu_output / format_cpu_output, io.hpp).
 void format_top_output(const TopResult& t, bool cpu_format, std::string* out);
 
+// ---- inverted index: word -> the lines it occurs on ----
+// Every token the word job emits (its tokeniser, emit cap and key truncation, unchanged)
+// yields one pair (key, line); `line` is the global 0-based line number first_line + i.
+// The pairs are sorted by (key in unsigned-byte order, line ascending).  The result is the
+// word job's entries for the same input and configuration, and `postings`: one u32 line
+// number per emitted token in sorted pair order -- entry i's list is
+// postings[val_i .. val_i + count_i), non-decreasing, with val the reference's val (the
+// exclusive prefix of the counts: EntryVals).  A word that occurs twice on a line has that
+// line twice, so the list's length is the count and postings.size() == num_tokens.  Long
+// tokens that merge under truncation merge their lists.  Word keys only (ngram == 1).
+struct IndexResult {
+  WordCountResult words;       // the word job: entries, statistics, stage times
+  std::vector<u32> postings;   // line numbers, CSR-indexed by the entries' (val, count)
+  u64 first_line = 0;          // the input window's first line (postings start there)
+  double index_ms = 0;         // device time of the index stage (0: built on the host)
+  u64 wire_bytes = 0;          // bytes the device wrote to host memory for the result
+};
+// LOCUST_CHECK invariants of an index result: the entries' counts add up to
+// postings.size() == num_tokens, every list is non-decreasing, every posting lies in
+// [first_line, first_line + num_lines).
+void validate_index(const IndexResult& r);
+// The result lines of an index, in key order:
+//   "print key: <key> \t count: <count> \t lines: <l0> <l1> ...\n"
+void format_index_output(const IndexResult& r, std::string* out);
+
 // Text read piece by piece (a file too large to hold): whole lines go straight into the
 // engine's pinned staging, so host memory stays bounded by two chunks whatever the input.
 class TextSource {
@@ -433,6 +458,13 @@ class GpuWordCount {
   TopResult run_top(const TextInput& in, u32 k);
   TopResult run_top_source(TextSource& src, u32 k);
 
+  // The word job, then the inverted index of the same text on the device (kernels/
+  // index.hip): the records stay in device memory, the text is tokenised once more with
+  // each token's line, and the (word rank, line) pairs are sorted there.  Dictionary
+  // engines with the fast map, word keys (ngram 1), one pass (in.bytes within the engine's
+  // pass; larger inputs and sources: the CPU engine).
+  IndexResult run_index(const TextInput& in);
+
   const JobConfig& config() const;
   u64 token_capacity() const;
   u64 text_capacity() const;  // bytes per device pass (input_buffer() size)
@@ -475,6 +507,9 @@ class CpuWordCount {
   explicit CpuWordCount(const JobConfig& cfg);
   WordCountResult run(const TextInput& in);
   TopResult run_top(const TextInput& in, u64 k);  // run() + the host selection, any k
+  // The inverted index on the host, any size: (key, line) pairs, one stable sort by key.
+  // Word keys only (ngram == 1), like the GPU job.
+  IndexResult run_index(const TextInput& in);
   std::vector<PackedKey> run_map_stage(const TextInput& in, WordCountResult* stats);
   WordCountResult run_reduce_stage(const PackedKey* keys, u64 n);
 

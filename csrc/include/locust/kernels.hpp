@@ -552,6 +552,73 @@ void topk_workspace_carve(char* base, u64 cap, TopKWorkspace* ws);
 void launch_top_select(const OutRecord* recs, u64 n, u32 k, const TopKWorkspace& ws,
                        TopRecord* out, u32* out_n, hipStream_t s);
 
+// ---------------- index.hip ----------------
+// Inverted index behind a word job (engine.hpp "inverted index"): over the `n` key-ordered
+// output records of the job and the text its map read, the line number of every emitted
+// token in (key, line) order -- word i's postings are [val_i, val_i + count_i).
+//
+// A sequence of kernels on `s`; this file adds no wait between workgroups (the line index
+// and the radix sort it reuses keep their own look-back):
+//   offsets     val[0 .. n] = exclusive scan of the counts (tile sums, one-workgroup scan
+//               of the tile array, per-tile scan) and the total
+//   line index  launch_line_index over the text
+//   map         one wave per line re-tokenises it with the word job's rules, packs each
+//               emitted token's key (bit-identical to the map's), binary-searches its rank r
+//               among the records and writes the pair word r << 32 | line.  The slots come
+//               from one atomic per wave and group of up to 64 consecutive lines, whose
+//               emitted tokens the wave counts first; a key not found counts as a miss
+//   order       radix_sort() of the pair words as one-word keys
+//   emit        postings[j] = first_line + low32(sorted[j]); pairs outside their word's
+//               [val, val + count) count as misplaced
+struct IndexCounters {  // zeroed per job
+  u64 total;      // sum of the records' counts
+  u32 written;    // pair words the map wrote
+  u32 miss;       // emitted tokens whose key is not among the records
+  u32 sort_n;     // pairs handed to the sort: `written` if it is the expected number, else 0
+  u32 misplaced;  // sorted pairs outside their word's range
+};
+constexpr int kIndexBlock = 256;
+constexpr int kIndexItems = 8;
+constexpr int kIndexTile = kIndexBlock * kIndexItems;  // records per workgroup of the offsets
+struct IndexWorkspace {
+  char* zero = nullptr;  // [MapCounters | IndexCounters | line-index look-back], zeroed per job
+  u64 zero_bytes = 0;
+  MapCounters* lctr = nullptr;  // the line index's counters (num_newlines)
+  IndexCounters* ctr = nullptr;
+  LookbackScratch lb{};
+  u64* pairs = nullptr;     // [pair_cap] rank << 32 | line, in arbitrary order
+  u64* zeros = nullptr;     // [pair_cap] zero: key words 1..3 of the sort
+  u64* sorted = nullptr;    // [pair_cap] the pair words ascending
+  u64* spare = nullptr;     // [pair_cap] where the sort puts its copies of the zero words
+  u32* postings = nullptr;  // [pair_cap]
+  u64* val = nullptr;       // [rec_cap + 1]
+  u64* tile_val = nullptr;  // [tiles]
+  u64* nl_pos = nullptr;    // [line_cap + 1]
+  RadixWorkspace rx{};      // the sort's own buffers (pair_cap keys)
+  u64 pair_cap = 0, rec_cap = 0, line_cap = 0, text_cap = 0;
+};
+u64 index_zero_bytes(u64 text_cap);
+u64 index_workspace_bytes(u64 pair_cap, u64 rec_cap, u64 line_cap, u64 text_cap);
+// Carves `base` (index_workspace_bytes(...) bytes, 256-B aligned).  The caller zeroes
+// ws->zeros once.
+void index_workspace_carve(char* base, u64 pair_cap, u64 rec_cap, u64 line_cap, u64 text_cap,
+                           IndexWorkspace* ws);
+struct IndexJob {
+  const OutRecord* recs = nullptr;  // the word job's records, key order, device memory
+  u64 n = 0;                        // ... their number (num_unique)
+  u64 tokens = 0;                   // the word job's num_tokens: the pairs to expect
+  const char* text = nullptr;       // the text the map read (16-B aligned; host-mapped allowed)
+  u64 bytes = 0;
+  u64 num_lines = 0;                // its lines (sizes the grid; <= ws.line_cap)
+  u64 first_line = 0;               // global number of line 0
+  DelimMask dm{};
+  int emits_per_line = 0, max_key_len = 0;
+};
+// Enqueues the stage; ws.postings[0 .. tokens) and ws.ctr are complete when `s` has
+// drained.  With more than kSmallSortMax tokens the sort reads its plan back through
+// h_plan (pinned) and synchronises `s` once, as radix_sort does.
+void launch_index(const IndexJob& job, IndexWorkspace& ws, SortPlan* h_plan, hipStream_t s);
+
 // ---- device self-test of the string library (tests only; StringTestOut in engine.hpp) ----
 void launch_string_selftest(const char* blob, const u32* off, u32 n, const char* delims,
                             const int* ints, StringTestOut* out, hipStream_t s);
@@ -564,6 +631,7 @@ void launch_string_selftest(const char* blob, const u32* off, u32 n, const char*
 // 573 MB fat binary), +1.3 GB of host memory and ~150 ms per process.
 void warm_module_dict();
 void warm_module_exchange();
+void warm_module_index();  // (as topk below: the code object only, no buffers)
 void warm_module_map();
 void warm_module_merge();
 void warm_module_ngram();
@@ -581,6 +649,7 @@ void warm_module_topk();
 inline void warm_kernel_modules() {
   warm_module_dict();
   warm_module_exchange();
+  warm_module_index();
   warm_module_map();
   warm_module_merge();
   warm_module_ngram();

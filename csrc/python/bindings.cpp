@@ -89,6 +89,50 @@ struct PyTopResult {
   }
 };
 
+// An inverted index: the word job's entries and the CSR postings behind them.
+struct PyIndexResult {
+  IndexResult x;
+  py::list entries() const { return PyResult{x.words}.entries(); }
+  py::list postings() const {
+    py::list out;
+    for (const u32 l : x.postings) out.append(l);
+    return out;
+  }
+  // the postings as little-endian u32 words (np.frombuffer(..., dtype="<u4"))
+  py::bytes postings_bytes() const {
+    return py::bytes(reinterpret_cast<const char*>(x.postings.data()),
+                     x.postings.size() * sizeof(u32));
+  }
+  // The lines of `key` (one per occurrence; unique: each line once); empty if absent.
+  py::list lines(const std::string& key, bool unique) const {
+    py::list out;
+    if (key.size() > (size_t)kKeyBytes) return out;
+    PackedKey k;
+    pack_key(key.data(), (int)key.size(), k.w);
+    EntryVals vals(x.words);
+    for (const auto& e : x.words.entries) {
+      const u64 val = vals.next(e);
+      const int c = key_compare(e.key.w, k.w);
+      if (c < 0) continue;
+      if (c == 0)
+        for (u64 j = val; j < val + e.count && j < x.postings.size(); ++j)
+          if (!unique || j == val || x.postings[j] != x.postings[j - 1]) out.append(x.postings[j]);
+      break;
+    }
+    return out;
+  }
+  py::dict times() const {
+    py::dict d = PyResult{x.words}.times();
+    d["index_ms"] = x.index_ms;
+    return d;
+  }
+  py::bytes format() const {
+    std::string s;
+    format_index_output(x, &s);
+    return py::bytes(s);
+  }
+};
+
 TextInput as_input(const std::string& text, u64 first_line = 0) {
   TextInput in;
   in.data = text.data();
@@ -205,6 +249,15 @@ class PyGpuEngine {
     py::gil_scoped_release nogil;
     auto src = open_file_source(path);
     return PyTopResult{eng_.run_top_source(*src, k)};
+  }
+  // The word job and the inverted index behind it, on the device.
+  PyIndexResult run_index(const std::string& text, u64 first_line) {
+    py::gil_scoped_release nogil;
+    return PyIndexResult{eng_.run_index(as_input(text, first_line))};
+  }
+  PyIndexResult run_index_text(const HostText& t, u64 first_line) {
+    py::gil_scoped_release nogil;
+    return PyIndexResult{eng_.run_index(t.input(first_line))};
   }
   // records: (key bytes, count), sorted by key with distinct keys -- the kernels alone.
   PyTopResult top_counts(const std::vector<std::pair<std::string, u64>>& records, u32 k) {
@@ -609,6 +662,24 @@ PYBIND11_MODULE(_locust, m) {
       .def_property_readonly("select_ms", [](const PyTopResult& p) { return p.t.select_ms; })
       .def_property_readonly("wire_bytes", [](const PyTopResult& p) { return p.t.wire_bytes; },
                              "bytes the device wrote to host memory for the result");
+  py::class_<PyIndexResult>(m, "IndexResult")
+      .def("entries", &PyIndexResult::entries)
+      .def("postings", &PyIndexResult::postings)
+      .def("postings_bytes", &PyIndexResult::postings_bytes)
+      .def("lines", &PyIndexResult::lines, py::arg("key"), py::arg("unique") = false)
+      .def("times", &PyIndexResult::times)
+      .def("format", &PyIndexResult::format)
+      .def_property_readonly("first_line", [](const PyIndexResult& p) { return p.x.first_line; })
+      .def_property_readonly("num_lines", [](const PyIndexResult& p) { return p.x.words.num_lines; })
+      .def_property_readonly("num_tokens", [](const PyIndexResult& p) { return p.x.words.num_tokens; })
+      .def_property_readonly("num_unique", [](const PyIndexResult& p) { return p.x.words.num_unique; })
+      .def_property_readonly("overflow_lines",
+                             [](const PyIndexResult& p) { return p.x.words.overflow_lines; })
+      .def_property_readonly("truncated", [](const PyIndexResult& p) { return p.x.words.truncated; })
+      .def_property_readonly("max_key_len", [](const PyIndexResult& p) { return p.x.words.max_key_len; })
+      .def_property_readonly("index_ms", [](const PyIndexResult& p) { return p.x.index_ms; })
+      .def_property_readonly("wire_bytes", [](const PyIndexResult& p) { return p.x.wire_bytes; },
+                             "bytes the device wrote to host memory for the result");
   m.attr("kTopKMax") = kTopKMax;
   m.attr("kMaxNgram") = kMaxNgram;
   m.attr("kTopKTile") = kTopKTile;
@@ -641,6 +712,10 @@ PYBIND11_MODULE(_locust, m) {
            "WordCount of text, top k by count selected on the device (k <= kTopKMax).")
       .def("run_top_text", &PyGpuEngine::run_top_text, py::arg("text"), py::arg("k"))
       .def("run_top_file", &PyGpuEngine::run_top_file, py::arg("path"), py::arg("k"))
+      .def("run_index", &PyGpuEngine::run_index, py::arg("text"), py::arg("first_line") = 0,
+           "WordCount of text and its inverted index (word -> lines), built on the device.")
+      .def("run_index_text", &PyGpuEngine::run_index_text, py::arg("text"),
+           py::arg("first_line") = 0)
       .def("top_counts", &PyGpuEngine::top_counts, py::arg("records"), py::arg("k"),
            "The selection kernels alone over key-sorted (key, count) records.")
       .def_property_readonly("capacity", &PyGpuEngine::capacity);
@@ -653,6 +728,10 @@ PYBIND11_MODULE(_locust, m) {
     CpuWordCount eng(cfg);
     return PyTopResult{eng.run_top(as_input(text), k)};
   }, py::arg("cfg"), py::arg("text"), py::arg("k"));
+  m.def("cpu_run_index", [](const JobConfig& cfg, const std::string& text, u64 first_line) {
+    CpuWordCount eng(cfg);
+    return PyIndexResult{eng.run_index(as_input(text, first_line))};
+  }, py::arg("cfg"), py::arg("text"), py::arg("first_line") = 0);
   m.def("cpu_map_stage", [](const JobConfig& cfg, const std::string& text) {
     CpuWordCount eng(cfg);
     std::vector<py::bytes> out;

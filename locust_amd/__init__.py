@@ -46,6 +46,8 @@ from .config import make_config, make_dist_config  # noqa: E402
 from .models.wordcount import (  # noqa: E402
     Engine,
     WordCount,
+    index_file,
+    index_text,
     map_stage,
     reduce_stage,
     run_multi,
@@ -76,6 +78,8 @@ __all__ = [
     "wordcount_text",
     "top_words_file",
     "top_words_text",
+    "index_file",
+    "index_text",
     "JobConfig",
     "DistConfig",
     "LocustError",

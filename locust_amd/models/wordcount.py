@@ -41,6 +41,16 @@ class Engine:
             return _C.cpu_run_top(self.cfg, text, k)
         return self._eng.run_top(text, k)
 
+    def run_index(self, text: bytes, first_line: int = 0):
+        """WordCount of ``text`` and its inverted index (``IndexResult``): for every word
+        the lines it occurs on, one posting per occurrence, numbered from ``first_line``.
+        ``entries()`` are the word job's; entry ``(key, val, count)`` owns
+        ``postings()[val:val + count]``.  On the GPU the index is built on the device behind
+        the word job (one pass, dictionary engine, fast map, word keys)."""
+        if self.cpu:
+            return _C.cpu_run_index(self.cfg, text, first_line)
+        return self._eng.run_index(text, first_line)
+
     def top_counts(self, records: list[tuple[bytes, int]], k: int):
         """The selection alone over (key, count) records sorted by key with distinct
         keys: a ``TopResult`` on the GPU, the plain (key, val, count) list on the CPU."""
@@ -114,6 +124,23 @@ def top_words_file(path: str, k: int, line_start: int = -1, line_end: int = -1,
     cfg = cfg if cfg is not None else make_config(backend, **kw)
     text, nlines, _first, _total = _C.load_lines(path, line_start, line_end, cfg.ref_compat)
     return Engine(cfg, max(len(text), 1), max(nlines, 1)).run_top(text, k)
+
+
+def index_text(text: bytes, backend: str = "gpu", cfg=None, first_line: int = 0, **kw):
+    """The inverted index of ``text`` (``IndexResult``); lines are numbered from
+    ``first_line``."""
+    cfg = cfg if cfg is not None else make_config(backend, **kw)
+    nlines = text.count(b"\n") + (1 if text and not text.endswith(b"\n") else 0)
+    return Engine(cfg, max(len(text), 1), max(nlines, 1)).run_index(text, first_line)
+
+
+def index_file(path: str, line_start: int = -1, line_end: int = -1, backend: str = "gpu",
+               cfg=None, **kw):
+    """The inverted index of a file or of its line window, with the file's own (global)
+    line numbers."""
+    cfg = cfg if cfg is not None else make_config(backend, **kw)
+    text, nlines, first, _total = _C.load_lines(path, line_start, line_end, cfg.ref_compat)
+    return Engine(cfg, max(len(text), 1), max(nlines, 1)).run_index(text, first)
 
 
 def map_stage(path: str, spill: str, line_start: int = -1, line_end: int = -1,

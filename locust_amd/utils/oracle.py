@@ -89,6 +89,50 @@ def top(entries, k: int):
     return sorted(entries, key=lambda e: (-e[2], e[0]))[:k]
 
 
+def index(text: bytes, delims: bytes = DEFAULT_DELIMS, emits: int = 20, max_key: int = 29,
+          first_line: int = 0):
+    """The inverted index of ``text``: ``(entries, postings)``.
+
+    Every token a line emits under the word job's rules (``tokenize``: the delimiter set, a
+    NUL ends the line's tokens, the first ``emits`` tokens only, keys cut to ``max_key``
+    bytes) yields one pair (key, line), ``line`` being the global 0-based line number
+    ``first_line + i``.  The pairs are sorted by (key in unsigned-byte order, line).
+    ``entries`` are exactly ``wordcount``'s ``(key, val, count)``; ``postings`` holds one
+    line number per emitted token in sorted pair order, so word i's list is
+    ``postings[val_i : val_i + count_i]``, non-decreasing, one posting per occurrence (a
+    word twice on a line has that line twice).  Keys that merge under truncation merge
+    their lists."""
+    pairs = []
+    for i, line in enumerate(split_lines(text)):
+        toks, _dropped = tokenize(line, delims, emits, max_key)
+        pairs.extend((t, first_line + i) for t in toks)
+    pairs.sort()
+    entries = []
+    for pos, (key, _line) in enumerate(pairs):
+        if entries and entries[-1][0] == key:
+            entries[-1][2] += 1
+        else:
+            entries.append([key, pos, 1])
+    return [tuple(e) for e in entries], [line for _key, line in pairs]
+
+
+def index_lines(entries, postings, key: bytes, unique: bool = False) -> list[int]:
+    """The lines of ``key`` in an index (``unique``: each line once); [] if absent."""
+    for k, val, count in entries:
+        if k == key:
+            lines = postings[val:val + count]
+            return sorted(set(lines)) if unique else list(lines)
+    return []
+
+
+def format_index(entries, postings) -> bytes:
+    """The CLI's ``--index`` result lines, in key order."""
+    return b"".join(
+        b"print key: %s \t count: %d \t lines: %s\n"
+        % (k, c, b" ".join(b"%d" % l for l in postings[v:v + c]))
+        for k, v, c in entries)
+
+
 def format_gpu(entries) -> bytes:
     """The reference GPU build's result lines (main.cu:132)."""
     return b"".join(b"print key: %s \t val: %d \t count: %d\n" % (k, v, c) for k, v, c in entries)

@@ -109,6 +109,19 @@ def test_cpu_engine_hamlet_window_and_offset(hamlet):
     assert t.postings() == got.postings()
 
 
+def test_cpu_engine_first_line_limit():
+    """first_line + num_lines == 2^32 is the last accepted value: the last line's posting
+    is 2^32 - 1, the largest a u32 holds."""
+    text = b"alpha beta\nbeta gamma\n\nalpha\n"
+    cfg = lc.make_config("cpu", check=True)
+    first = 2**32 - 4
+    got = lc._C.cpu_run_index(cfg, text, first)
+    assert (got.entries(), got.postings()) == oracle.index(text, first_line=first)
+    assert max(got.postings()) == 2**32 - 1 and got.first_line == first
+    with pytest.raises(lc.LocustError, match=r"2\^32"):
+        lc._C.cpu_run_index(cfg, text, first + 1)
+
+
 def test_cpu_engine_refuses_ngrams():
     with pytest.raises(lc.LocustError, match="ngram"):
         cpu_index(b"a b c\n", ngram=2)

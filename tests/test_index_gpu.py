@@ -3,7 +3,11 @@
 there is exactly one right answer and no tolerance anywhere.  The shapes are the smallest
 at which each part of the stage can go wrong: the 64-byte step of the line walk, the emit
 cap, NULs, key truncation, the sort's two regimes and the binary search over thousands of
-records."""
+records.  The scale edges need their size: the second round of the one-workgroup tile scan
+and the map grid's stride (more than 524,288 records and lines), the dictionary's radix
+fallback (more than 32,768 distinct keys), the large-input path (more than 8 MiB), one line
+of thousands of bytes, pinned host text, and the last line number a u32 holds."""
+import functools
 import json
 import os
 import random
@@ -194,8 +198,8 @@ def test_search_over_thousands_of_records(eng):
     assert [c for _k, _v, c in ent].count(2) == 1 and len(got.lines(vocab[2500])) == 2
 
 
-def test_input_past_zero_copy():
-    """1.5 MiB of generated lines: the text is copied to the device, not read in place."""
+@functools.lru_cache(maxsize=None)
+def past_zero_copy_text():
     rng = random.Random(9)
     vocab = words(3000, 6)
     lines = []
@@ -203,10 +207,165 @@ def test_input_past_zero_copy():
     while size < (3 << 19):
         lines.append(b" ".join(rng.choices(vocab, k=8)))
         size += len(lines[-1]) + 1
-    text = b"\n".join(lines) + b"\n"
+    return b"\n".join(lines) + b"\n"
+
+
+def test_input_past_zero_copy():
+    """1.5 MiB of generated lines: the text is copied to the device, not read in place."""
+    text = past_zero_copy_text()
     assert len(text) > (1 << 20)
     engine = lc.Engine(gpu_cfg(), len(text), lc._C.count_lines(text))
     check(engine, text)
+
+
+# ------------------------------------------------------------------------------------
+# scale edges: each test asserts the property that makes it reach its edge
+# ------------------------------------------------------------------------------------
+INDEX_TILE = 2048      # kIndexTile: records per workgroup of the offsets kernels
+SCAN_BLOCK = 256       # kIndexBlock: tile sums the one-workgroup scan takes per round
+MAP_WAVES = 2048 * 4   # kIdxMapMaxBlocks workgroups of 4 waves
+MAP_GROUP = 64         # the most lines a wave takes per slot reservation
+RANK_SORT_MAX = 32768  # kRankSortMax: more distinct keys take the dictionary's radix fallback
+
+
+def test_second_round_of_scan_and_grid():
+    """~545,000 lines, a word of its own on almost every one: more records than one round
+    of index_tile_scan_kernel covers (the carry between rounds), more lines than one sweep
+    of index_map_kernel's full grid at group = 64 (the grid-stride step), and more distinct
+    keys than the rank sort takes (the records reach the index stage by the radix fallback)."""
+    n_lines = 545_000
+    extra = b" " + b" ".join(b"t%d" % j for j in range(25))
+    lines = []
+    for i in range(n_lines):
+        if i % 100 == 57:
+            lines.append(b"")
+            continue
+        line = b"%05x" % i
+        if i % 3 == 0:
+            line += b" shared"
+        if i % 1000 == 0:
+            line += extra  # 26 or 27 tokens: past the emit cap
+        lines.append(line)
+    text = b"\n".join(lines) + b"\n"
+    del lines
+    want_e, want_p = oracle.index(text)
+    num_lines = lc._C.count_lines(text)
+    assert num_lines == n_lines and num_lines > MAP_GROUP * MAP_WAVES
+    assert len(want_e) > SCAN_BLOCK * INDEX_TILE and len(want_e) > RANK_SORT_MAX
+    engine = lc.Engine(gpu_cfg(), len(text), num_lines)
+    got = engine.run_index(text)
+    assert got.entries() == want_e
+    assert got.postings() == want_p
+    assert got.num_tokens == len(want_p) and got.num_unique == len(want_e)
+    assert got.num_lines == n_lines and got.first_line == 0
+    assert got.overflow_lines == len(range(0, n_lines, 1000)) and got.truncated == 0
+    assert got.lines(b"shared") == [i for i in range(n_lines) if i % 3 == 0 and i % 100 != 57]
+    assert got.lines(b"%05x" % (n_lines - 1)) == [n_lines - 1]
+
+
+def test_dict_fallback_smallest():
+    """Just past 32,768 distinct words: the dictionary job is finished on the radix path and
+    the index stage reads the records from where that path leaves them.  Word jobs before
+    and after it on the same engine."""
+    vocab = words(33_000, 8)
+    order = list(vocab)
+    random.Random(12).shuffle(order)
+    order += [order[5], order[20_000], order[5], vocab[0], vocab[-1]]  # repeats, lines apart
+    lines = [b" ".join(order[i:i + 7]) for i in range(0, len(order), 7)]
+    text = b"\n".join(lines) + b"\n"
+    ent, ntok, _ = oracle.wordcount(text)
+    engine = lc.Engine(gpu_cfg(), len(text), lc._C.count_lines(text))
+    r = engine.run(text)
+    assert r.entries() == ent and r.num_tokens == ntok
+    got = check(engine, text)
+    assert got.num_unique == 33_000 and got.num_unique > RANK_SORT_MAX
+    assert got.entries() == ent
+    assert got.lines(order[5]) == [0, 33_000 // 7, 33_000 // 7]
+    assert got.lines(order[20_000]) == [20_000 // 7, 33_000 // 7]
+    r = engine.run(text)
+    assert r.entries() == ent and r.num_tokens == ntok
+
+
+def test_above_large_input():
+    """Just above 8 MiB (kMapLargeInput): large map tiles, piecewise upload, the two-kernel
+    ordered build; index and top jobs against the CPU engine (tied to the oracle by
+    test_index.py and test_topk.py).  Twice on one engine: the second round runs on the
+    retuned partition map."""
+    block = lc._C.gen_text(bytes=1 << 20, seed=5)
+    text = block * (((8 << 20) // len(block)) + 1)
+    assert (8 << 20) < len(text) < (10 << 20)
+    cpu = lc.make_config("cpu")
+    want = lc._C.cpu_run_index(cpu, text, 5)
+    want_e, want_p = want.entries(), want.postings()
+    want_top = lc._C.cpu_run_top(cpu, text, 1000).entries()
+    assert len(want_top) == 1000 and want.num_unique <= RANK_SORT_MAX  # (no radix fallback)
+    engine = lc.Engine(gpu_cfg(), len(text), lc._C.count_lines(text))
+    for _ in range(2):
+        got = engine.run_index(text, 5)
+        assert got.entries() == want_e
+        assert got.postings() == want_p
+        assert (got.num_tokens, got.num_unique) == (want.num_tokens, want.num_unique)
+        assert (got.overflow_lines, got.truncated) == (want.overflow_lines, want.truncated)
+        assert engine.run_top(text, 1000).entries() == want_top
+
+
+@pytest.mark.parametrize("which", ["hamlet_window", "past_zero_copy"])
+def test_pinned_host_text(hamlet_index, which):
+    """run_index_text on text in pinned host memory (the direct upload mode) gives what
+    run_index gives on the same bytes."""
+    text = hamlet_index["window"][0] if which == "hamlet_window" else past_zero_copy_text()
+    want = oracle.index(text, first_line=3)
+    engine = lc._C.GpuEngine(gpu_cfg(), len(text), lc._C.count_lines(text))
+    pinned = lc._C.HostText.from_bytes(text)
+    got = engine.run_index_text(pinned, first_line=3)
+    assert (got.entries(), got.postings()) == want
+    assert got.first_line == 3 and got.num_lines == lc._C.count_lines(text)
+    plain = engine.run_index(text, 3)
+    assert (plain.entries(), plain.postings()) == want
+    assert (got.num_tokens, got.overflow_lines, got.truncated) == (
+        plain.num_tokens, plain.overflow_lines, plain.truncated)
+    got = engine.run_index_text(pinned, first_line=3)  # ... and again after a pageable job
+    assert (got.entries(), got.postings()) == want
+
+
+def test_one_long_line():
+    """One line of 1,250 words of 1-6 bytes (5,000-odd bytes), no final newline: its one wave
+    walks ~90 steps of 64 bytes.  With emits_per_line = 1000 the cap falls deep inside the
+    line; a NUL at byte 3,000 ends the tokens before the cap; with emits_per_line = 5000 the
+    cap is never reached."""
+    rng = random.Random(21)
+    toks = [bytes(rng.choice(ALPHA) for _ in range(rng.randrange(1, 7))) for _ in range(1250)]
+    line = b" ".join(toks)
+    assert len(toks) > 1200 and 5000 < len(line) < 6500
+    cap_byte = len(b" ".join(toks[:1000]))
+    assert 50 * 64 < cap_byte < len(line) - 64  # the 1000th token: far in, not at the end
+    nul = line[:3000] + b"\0" + line[3001:]
+
+    def run(engine, text, emits):
+        got = check(engine, text, emits=emits)
+        want = oracle.wordcount(text, emits=emits, stats=True)
+        assert (got.num_tokens, got.overflow_lines, got.truncated) == want[1:]
+        return got
+
+    e1000 = lc.Engine(gpu_cfg(emits_per_line=1000), 1 << 16, 1 << 10)
+    got = run(e1000, line, 1000)
+    assert got.num_tokens == 1000 and got.overflow_lines == 1
+    got = run(e1000, nul, 1000)
+    assert got.num_tokens < 1000 and got.overflow_lines == 0
+    e5000 = lc.Engine(gpu_cfg(emits_per_line=5000), 1 << 16, 1 << 10)
+    got = run(e5000, line, 5000)
+    assert got.num_tokens == len(toks) and got.overflow_lines == 0
+
+
+def test_first_line_limit(eng):
+    """first_line + num_lines == 2^32 is the last accepted value."""
+    text = b"alpha beta\nbeta gamma\n\nalpha\n"
+    got = check(eng, text, first_line=2**32 - 4)
+    assert max(got.postings()) == 2**32 - 1
+    assert got.lines(b"alpha") == [2**32 - 4, 2**32 - 1]
+    with pytest.raises(lc.LocustError, match=r"2\^32"):
+        eng.run_index(text, 2**32 - 3)
+    check(eng, text, first_line=1)  # the refusal leaves the engine usable
 
 
 # ------------------------------------------------------------------------------------

@@ -105,6 +105,45 @@ def test_top_counts_wide_counts(sel_engine, kind):
     check_counts(sel_engine, counts, 700)
 
 
+def test_top_counts_second_scan_round():
+    """More than 256 tiles: topk_scan_kernel's one workgroup takes a second round and
+    carries both running totals into it.  Keys already in byte order, every count 1 except
+    60 winners in tile 0, tile 3 (one count >= 2^32: the carried prefix needs its high word),
+    the last tile of the first round, the first of the second, and the last, partial tile.
+    A winner's val is the sum of every count before it, so a winner behind tile 256 has the
+    carried sum in its val; its slot has the carried number of winners in it."""
+    n = 256 * TILE + TILE + 5
+    tiles = -(-n // TILE)
+    assert tiles > 256 and n % TILE  # a second round, a partial last tile
+    rng = random.Random(13)
+    counts = [1] * n
+    where = {0: 18, 3: 1, 255: 19, 256: 19, tiles - 1: 3}
+    assert sum(where.values()) == 60
+    for tile, m in where.items():
+        picked = rng.sample(range(tile * TILE, min((tile + 1) * TILE, n)), m)
+        for i in picked:
+            counts[i] = 2 + rng.randrange(5000)
+        if tile != 255:  # one count >= 2^32 per tile, before and behind the carry
+            counts[picked[0]] = (1 << 33) + 1000 * tile + 7
+    assert sum(c > 1 for c in counts) == 60
+    ent, pos = [], 0
+    for i, c in enumerate(counts):
+        ent.append((b"%07d" % i, pos, c))
+        pos += c
+    recs = [(key, c) for key, _v, c in ent]
+    eng = lc.Engine(lc.make_config("gpu", check=True), 2 << 20, 1 << 16)
+    assert eng.capacity >= n
+    for k in (10, 60 + TILE + 300):  # the larger: every winner, then ties cut inside tile 1
+        assert k <= KMAX
+        want = oracle.top(ent, k)
+        # among the expected: a record behind tile 256 whose val has the carried high word
+        assert any(key >= b"%07d" % (256 * TILE) and val >= 1 << 33 for key, val, _c in want)
+        got = eng.top_counts(recs, k)
+        assert got.entries() == want
+        assert got.num_unique == n and got.k == k
+    assert want[-1][2] == 1 and TILE < int(want[-1][0]) < 2 * TILE
+
+
 def test_top_counts_k_above_limit(sel_engine):
     with pytest.raises(lc.LocustError, match=str(KMAX)):
         sel_engine.top_counts([(b"a", 1), (b"b", 2)], KMAX + 1)

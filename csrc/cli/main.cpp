@@ -17,6 +17,8 @@
 //   --top K (the K most frequent words instead of the whole dictionary, rank order)
 //   --ngram N (count the word N-grams of each line, N <= 3, instead of its words)
 //   --index (the inverted index: every word with the lines it occurs on)
+//   --search "w1 w2" [--match all|any] (the lines that hold all / any of the words; repeat
+//     --search for a batch: answered from the index on the device, or by --backend cpu)
 // and a synthetic-text generator (BASELINE configs "1M lines" / "10 GB"):
 //   MapReduce --gen FILE (--gen-lines N | --gen-bytes N) [--seed S] [--vocab V]
 #include <sys/stat.h>
@@ -82,6 +84,10 @@ struct CliArgs {
   bool quiet = false;
   u64 top = 0;  // --top K: the result lines are the K most frequent words (0: all)
   bool index = false;  // --index: the result lines carry every word's line numbers
+  // --search "w1 w2" (repeatable): the result lines are the queries' answers
+  std::vector<std::string> search_args;
+  std::vector<SearchQuery> queries;
+  std::string match;  // --match all|any ("": all)
   std::string gen_out;  // generator mode
   GenSpec gen;
 };
@@ -120,6 +126,11 @@ void help() {
       "                             one-pass jobs on one GPU or --backend cpu.  Not with --top,\n"
       "                             --ngram N > 1, the stage split, --gpus N > 1, --chunk-mb,\n"
       "                             --sort radix or --map-path compat)\n"
+      "  --search \"w1 w2 ...\"       (the 0-based lines that hold the words, 1 to 8 of them, split\n"
+      "                             like the text; repeat --search for a batch.  Answered from the\n"
+      "                             index in device memory, or by --backend cpu.  Restrictions\n"
+      "                             as --index, and not with --index)\n"
+      "  --match all|any            (--search: lines with every word (default) or with any)\n"
       "  --help\n"
       "\n"
       "Environment: LOCUST_LOG=info|debug and the LOCUST_* switches in docs/ENVIRONMENT.md.\n",
@@ -240,6 +251,11 @@ bool parse(int argc, char** argv, CliArgs* a) {
       a->top = (u64)k;
     } else if (s == "--index") {
       a->index = true;
+    } else if (s == "--search") {
+      a->search_args.push_back(need("--search"));
+    } else if (s == "--match") {
+      a->match = need("--match");
+      if (a->match != "all" && a->match != "any") throw Error("--match takes all or any (how --search combines its words)");
     } else if (s == "--ngram") {
       const std::string v = need("--ngram");
       char* endp = nullptr;
@@ -295,25 +311,56 @@ bool parse(int argc, char** argv, CliArgs* a) {
     if (a->cfg.backend == Backend::kGpu && a->cfg.map_path == MapPath::kCompat)
       throw Error("--ngram N > 1 needs the fast map (map_path fast), not --map-path compat");
   }
-  if (a->index) {
-    if (a->top) throw Error("--index and --top do not combine: an index lists every word");
+  if (!a->match.empty() && a->search_args.empty())
+    throw Error("--match selects how --search combines its words: give --search too");
+  if (a->index && !a->search_args.empty())
+    throw Error("--index and --search do not combine: --index prints the whole index, "
+                "--search the lines of its queries");
+  if (a->index || !a->search_args.empty()) {
+    // a search job is the index job plus the search stage: the same restrictions
+    const std::string f = a->index ? "--index" : "--search";
+    if (a->top)
+      throw Error(f + " and --top do not combine: an index lists every word");
     if (a->cfg.ngram > 1)
-      throw Error("--index builds word keys only: not with --ngram N > 1");
+      throw Error(f + " builds word keys only: not with --ngram N > 1");
     if (a->stage != 0 || !a->inputs.empty() || a->reducers > 1)
-      throw Error("--index runs whole jobs only: not with the stage split (stage 1 or 2, "
+      throw Error(f + " runs whole jobs only: not with the stage split (stage 1 or 2, "
                   "--stage, --inputs, --reducer)");
     if (a->gpus > 1)
-      throw Error("--index runs on one GPU or the CPU: not with --gpus N > 1");
+      throw Error(f + " runs on one GPU or the CPU: not with --gpus N > 1");
     if (a->cfg.chunk_bytes)
-      throw Error("--index takes one device pass: not with --chunk-mb (a streamed index is "
+      throw Error(f + " takes one device pass: not with --chunk-mb (a streamed index is "
                   "not built; use --backend cpu for larger inputs)");
-    if (!a->export_kiv.empty()) throw Error("--index and --export-kiv do not combine");
-    if (a->cfg.ref_timers) throw Error("--index and --ref-timers do not combine");
+    if (!a->export_kiv.empty()) throw Error(f + " and --export-kiv do not combine");
+    if (a->cfg.ref_timers) throw Error(f + " and --ref-timers do not combine");
     if (a->cfg.backend == Backend::kGpu && a->cfg.sort_path == SortPath::kRadix)
-      throw Error("--index on the GPU needs the dictionary path (--sort dict), not --sort radix");
+      throw Error(f + " on the GPU needs the dictionary path (--sort dict), not --sort radix");
     if (a->cfg.backend == Backend::kGpu && a->cfg.map_path == MapPath::kCompat)
-      throw Error("--index on the GPU needs the fast map (map_path fast), not --map-path "
+      throw Error(f + " on the GPU needs the fast map (map_path fast), not --map-path "
                   "compat: the compat map overwrites the text the index reads again");
+  }
+  // the --search arguments, split with the job's own delimiter set: no term can be invalid
+  for (const std::string& arg : a->search_args) {
+    SearchQuery q;
+    q.mode = a->match == "any" ? SearchMode::kAny : SearchMode::kAll;
+    std::string cur;
+    for (const char c : arg) {
+      if (a->cfg.delimiters.find(c) != std::string::npos) {
+        if (!cur.empty()) q.terms.push_back(cur);
+        cur.clear();
+      } else {
+        cur.push_back(c);
+      }
+    }
+    if (!cur.empty()) q.terms.push_back(cur);
+    if (q.terms.empty()) throw Error("--search \"" + arg + "\" holds no word");
+    a->queries.push_back(q);
+  }
+  if (!a->queries.empty()) {
+    check_search_queries(a->queries, a->cfg);
+    if (a->cfg.backend == Backend::kGpu && a->queries.size() > (size_t)kSearchMaxQueries)
+      throw Error("--search: a device batch holds at most " + std::to_string(kSearchMaxQueries) +
+                  " queries (use --backend cpu for more)");
   }
   if (a->byte_range) {
     if (a->stage != 1) throw Error("--byte-range is a stage-1 (map) flag");
@@ -455,6 +502,35 @@ void json_index(JsonOut& j, const CliArgs& a) {
   }
 }
 
+// --search: "search": true in the record, the batch's size, its hits and the search time
+// (the device stage's, or the host evaluation's), and the bytes the device wrote to host
+// memory for the result.
+const SearchResult* g_search = nullptr;
+void json_search(JsonOut& j, const CliArgs& a) {
+  if (a.queries.empty()) return;
+  j.kv("search", "true");
+  j.u("queries", a.queries.size());
+  if (g_search) {
+    j.u("hits", g_search->lines.size());
+    j.num("index_ms", g_search->index_ms);
+    j.num("search_ms", g_search->search_ms);
+    j.u("wire_bytes", g_search->wire_bytes);
+  }
+}
+
+// The statistics of a search result as a WordCountResult without entries.
+WordCountResult search_stats(const SearchResult& t) {
+  WordCountResult r;
+  r.num_lines = t.num_lines;
+  r.num_tokens = t.num_tokens;
+  r.num_unique = t.num_unique;
+  r.overflow_lines = t.overflow_lines;
+  r.truncated = t.truncated;
+  r.max_key_len = t.max_key_len;
+  r.times = t.times;
+  return r;
+}
+
 // The statistics of a top result as a WordCountResult without entries (json, timer lines).
 WordCountResult top_stats(const TopResult& t) {
   WordCountResult r;
@@ -489,6 +565,7 @@ void write_json(const CliArgs& a, const WordCountResult& r, const std::vector<do
   j.u("chunks", r.chunks);
   json_top(j, a);
   json_index(j, a);
+  json_search(j, a);
   if (g_part_map) j.str("part_map", g_part_map);  // the one-shot CLI's starting map
   if (g_engine_stats_set) json_hbm(j, g_engine_stats);
   // peak resident memory of this process image (VmHWM: unlike getrusage's ru_maxrss it is
@@ -653,9 +730,10 @@ void emit_results(const CliArgs& a, const std::string& out) {
 }
 
 // `top` (--top K on one GPU): the device selected; r then carries the statistics only.
-// `idx` (--index): the result lines are the index's.
+// `idx` (--index): the result lines are the index's.  `srch` (--search): the queries'.
 void print_gpu_result(const CliArgs& a, const WordCountResult& r, const std::vector<double>& walls,
-                      const TopResult* top = nullptr, const IndexResult* idx = nullptr) {
+                      const TopResult* top = nullptr, const IndexResult* idx = nullptr,
+                      const SearchResult* srch = nullptr) {
   const bool rt = a.cfg.ref_timers;
   std::printf("GPU mapping %lld nanoseconds \n", ns(rt ? r.times.ref_map_ms : r.times.map_ms));
   for (u64 k = 0; k < r.overflow_lines; ++k) std::printf("WARN: Exceeded emit limit\n");
@@ -666,7 +744,9 @@ void print_gpu_result(const CliArgs& a, const WordCountResult& r, const std::vec
     LOCUST_LOG_WARN("%llu tokens longer than %d chars were truncated",
                     (unsigned long long)r.truncated, a.cfg.max_key_len);
   std::string out;
-  if (idx) {
+  if (srch) {
+    if (!a.quiet) format_search_output(*srch, &out);
+  } else if (idx) {
     if (!a.quiet) format_index_output(*idx, &out);
   } else if (top) {
     format_top(a, false, *top, &out);
@@ -677,6 +757,7 @@ void print_gpu_result(const CliArgs& a, const WordCountResult& r, const std::vec
   std::fflush(stdout);
   g_top_device = top;
   g_index = idx;
+  g_search = srch;
   write_json(a, r, walls);
   if (!a.export_kiv.empty()) write_kiv_results(a.export_kiv, r);
   std::printf("\nDone\n");
@@ -950,7 +1031,7 @@ int run(const CliArgs& a) {
   // one device pass, streamed through two pinned chunks (host memory stays bounded).
   const bool direct = !cpu && !use_window && a.stage == 0 && !a.gpus_given && a.gpus <= 1 &&
                       !a.cfg.ref_compat && a.cfg.map_path == MapPath::kFast &&
-                      a.cfg.sort_path == SortPath::kDict && !a.index;
+                      a.cfg.sort_path == SortPath::kDict && !a.index && a.queries.empty();
   if (direct) return run_direct(a);
   // ---------------- multi-GPU in one process (one thread per rank) ----------------------
   // An explicit --gpus N (N >= 1) runs N ranks.  --comm auto: an ncclCommInitAll clique
@@ -958,7 +1039,8 @@ int run(const CliArgs& a) {
   // (one rank, or N ranks rehearsed on fewer GPUs); --comm rccl / loopback force either.
   // A whole file is never loaded: every rank reads only its own line-aligned byte range
   // (run_single_process_file); a line window is loaded first, then sharded.
-  const bool multi = (a.gpus > 1 || (a.gpus_given && !cpu)) && a.stage == 0 && !a.index;
+  const bool multi = (a.gpus > 1 || (a.gpus_given && !cpu)) && a.stage == 0 && !a.index &&
+                     a.queries.empty();
   // (the compat map sizes its slots per line: its ranks get the loaded text, whose line
   // count is exact, not a file range sized by bytes)
   const bool file_ranks = multi && !use_window && !a.cfg.ref_compat &&
@@ -1000,12 +1082,16 @@ int run(const CliArgs& a) {
   WordCountResult r;
   TopResult cpu_top;  // --top K on the CPU backend
   IndexResult cpu_index;  // --index on the CPU backend
+  SearchResult cpu_search;  // --search on the CPU backend
   std::vector<double> walls;
   if (cpu) {
     CpuWordCount eng(a.cfg);
     for (int i = 0; i < a.warmup; ++i) eng.run(text.input);
     for (int i = 0; i < a.iters; ++i) {
-      if (a.index) {
+      if (!a.queries.empty()) {
+        cpu_search = eng.run_search(text.input, a.queries);
+        r = search_stats(cpu_search);
+      } else if (a.index) {
         cpu_index = eng.run_index(text.input);
         r = cpu_index.words;
       } else if (a.top) {
@@ -1021,6 +1107,15 @@ int run(const CliArgs& a) {
     std::printf("CPU reducing %lld nanoseconds \n", ns(r.times.reduce_ms));
   } else {
     GpuWordCount eng(a.cfg, text.input.bytes, text.input.num_lines);
+    if (!a.queries.empty()) {  // the word job, the index stage and the search stage
+      SearchResult sr;
+      for (int i = 0; i < a.warmup + a.iters; ++i) {
+        sr = eng.run_search(text.input, a.queries);
+        if (i >= a.warmup) walls.push_back(sr.times.wall_ms);
+      }
+      print_gpu_result(a, search_stats(sr), walls, nullptr, nullptr, &sr);
+      return 0;
+    }
     if (a.index) {  // the word job, then the index stage behind it on the device
       IndexResult x;
       for (int i = 0; i < a.warmup + a.iters; ++i) {
@@ -1051,7 +1146,10 @@ int run(const CliArgs& a) {
     LOCUST_LOG_WARN("%llu tokens longer than %d chars were truncated",
                     (unsigned long long)r.truncated, a.cfg.max_key_len);
   std::string out;
-  if (a.index) {
+  if (!a.queries.empty()) {
+    if (!a.quiet) format_search_output(cpu_search, &out);
+    g_search = &cpu_search;
+  } else if (a.index) {
     if (!a.quiet) format_index_output(cpu_index, &out);
     g_index = &cpu_index;
   } else if (a.top) {

@@ -372,4 +372,146 @@ void format_index_output(const IndexResult& r, std::string* out) {
   }
 }
 
+// ---- index search: the host evaluation (engine.hpp) ----
+PackedKey search_term_key(const std::string& term, const JobConfig& cfg) {
+  PackedKey k;
+  pack_key(term.data(), (int)std::min<size_t>(term.size(), (size_t)cfg.max_key_len), k.w);
+  return k;
+}
+
+void check_search_queries(const std::vector<SearchQuery>& queries, const JobConfig& cfg) {
+  for (size_t i = 0; i < queries.size(); ++i) {
+    const SearchQuery& q = queries[i];
+    LOCUST_CHECK_ARG(!q.terms.empty() && q.terms.size() <= (size_t)kSearchMaxTerms,
+                     "search: query " + std::to_string(i) + " has " +
+                         std::to_string(q.terms.size()) + " terms; a query takes 1 to " +
+                         std::to_string(kSearchMaxTerms));
+    for (const std::string& t : q.terms) {
+      LOCUST_CHECK_ARG(!t.empty(), "search: query " + std::to_string(i) + " has an empty term");
+      for (const char ch : t) {
+        const unsigned char c = (unsigned char)ch;
+        LOCUST_CHECK_ARG(c != 0 && c != '\n' && cfg.delimiters.find(ch) == std::string::npos,
+                         "search: a term of query " + std::to_string(i) + " holds byte " +
+                             std::to_string((unsigned)c) +
+                             " (a NUL, a newline or a delimiter), which no word can hold");
+      }
+    }
+  }
+}
+
+SearchResult search_index(const IndexResult& x, const std::vector<SearchQuery>& queries,
+                          const JobConfig& cfg) {
+  check_search_queries(queries, cfg);
+  const u64 t0 = now_ns();
+  SearchResult r;
+  r.queries = queries;
+  r.first_line = x.first_line;
+  r.num_lines = x.words.num_lines;
+  r.num_tokens = x.words.num_tokens;
+  r.num_unique = x.words.num_unique;
+  r.overflow_lines = x.words.overflow_lines;
+  r.truncated = x.words.truncated;
+  r.max_key_len = x.words.max_key_len;
+  r.times = x.words.times;
+  r.index_ms = x.index_ms;
+  r.wire_bytes = x.wire_bytes;
+  const size_t n = x.words.entries.size();
+  const WordCountEntry* ent = x.words.entries.data();
+  std::vector<u64> val(n + 1, 0);
+  for (size_t i = 0; i < n; ++i) val[i + 1] = val[i] + ent[i].count;
+  LOCUST_CHECK_ARG(val[n] == x.postings.size(), "search: the index's counts and postings disagree");
+  r.offsets.assign(1, 0);
+  r.term_counts.assign(queries.size() * kSearchMaxTerms, 0);
+  struct List {
+    const u32* p;
+    u64 len;
+  };
+  for (size_t qi = 0; qi < queries.size(); ++qi) {
+    const SearchQuery& q = queries[qi];
+    std::vector<List> lists;  // the distinct present terms
+    bool absent = false;
+    for (size_t t = 0; t < q.terms.size(); ++t) {
+      const PackedKey k = search_term_key(q.terms[t], cfg);
+      const WordCountEntry* e = std::lower_bound(
+          ent, ent + n, k,
+          [](const WordCountEntry& a, const PackedKey& b) { return key_compare(a.key.w, b.w) < 0; });
+      if (e == ent + n || key_compare(e->key.w, k.w) != 0) {
+        absent = true;
+        continue;
+      }
+      r.term_counts[qi * kSearchMaxTerms + t] = e->count;
+      const List l{x.postings.data() + val[e - ent], e->count};
+      bool dup = false;
+      for (const List& o : lists) dup |= o.p == l.p;
+      if (!dup) lists.push_back(l);
+    }
+    if (q.mode == SearchMode::kAll) {
+      if (!absent && !lists.empty()) {
+        size_t d = 0;
+        for (size_t i = 1; i < lists.size(); ++i)
+          if (lists[i].len < lists[d].len) d = i;
+        for (u64 j = 0; j < lists[d].len; ++j) {
+          const u32 line = lists[d].p[j];
+          if (j && lists[d].p[j - 1] == line) continue;
+          bool hit = true;
+          for (size_t i = 0; i < lists.size() && hit; ++i)
+            if (i != d) hit = std::binary_search(lists[i].p, lists[i].p + lists[i].len, line);
+          if (hit) r.lines.push_back(line);
+        }
+      }
+    } else {
+      const size_t from = r.lines.size();
+      for (const List& l : lists) r.lines.insert(r.lines.end(), l.p, l.p + l.len);
+      std::sort(r.lines.begin() + (std::ptrdiff_t)from, r.lines.end());
+      r.lines.erase(std::unique(r.lines.begin() + (std::ptrdiff_t)from, r.lines.end()),
+                    r.lines.end());
+    }
+    r.offsets.push_back(r.lines.size());
+  }
+  r.search_ms = (now_ns() - t0) * 1e-6;
+  r.times.wall_ms += r.search_ms;
+  if (cfg.check) validate_search(r);
+  return r;
+}
+
+void validate_search(const SearchResult& r) {
+  if (r.offsets.size() != r.queries.size() + 1 || r.offsets.front() != 0 ||
+      r.offsets.back() != r.lines.size())
+    throw Error("LOCUST_CHECK: search offsets do not span the " + std::to_string(r.lines.size()) +
+                " lines of " + std::to_string(r.queries.size()) + " queries");
+  const u64 lo = r.first_line, hi = r.first_line + r.num_lines;
+  for (size_t q = 0; q + 1 < r.offsets.size(); ++q) {
+    if (r.offsets[q + 1] < r.offsets[q] || r.offsets[q + 1] > r.lines.size())
+      throw Error("LOCUST_CHECK: search offsets decrease at query " + std::to_string(q));
+    for (u64 j = r.offsets[q]; j < r.offsets[q + 1]; ++j) {
+      const u64 l = r.lines[j];
+      if (l < lo || l >= hi)
+        throw Error("LOCUST_CHECK: line " + std::to_string(l) + " of query " + std::to_string(q) +
+                    " outside the lines [" + std::to_string(lo) + ", " + std::to_string(hi) + ")");
+      if (j > r.offsets[q] && l <= r.lines[j - 1])
+        throw Error("LOCUST_CHECK: lines of query " + std::to_string(q) +
+                    " not strictly ascending at position " + std::to_string(j - r.offsets[q]));
+    }
+  }
+}
+
+void format_search_output(const SearchResult& r, std::string* out) {
+  out->reserve(out->size() + r.queries.size() * 48 + r.lines.size() * 6);
+  for (size_t q = 0; q < r.queries.size(); ++q) {
+    out->append("print query:");
+    for (const std::string& t : r.queries[q].terms) {
+      out->push_back(' ');
+      out->append(t);
+    }
+    out->append(" \t hits: ");
+    out->append(std::to_string(r.offsets[q + 1] - r.offsets[q]));
+    out->append(" \t lines:");
+    for (u64 j = r.offsets[q]; j < r.offsets[q + 1]; ++j) {
+      out->push_back(' ');
+      out->append(std::to_string(r.lines[j]));
+    }
+    out->push_back('\n');
+  }
+}
+
 }  // namespace locust

@@ -25,20 +25,37 @@ u64 GpuWordCount::token_capacity() const { return impl_->cap; }
 char* GpuWordCount::input_buffer() { return impl_->ensure_h_text(); }
 u64 GpuWordCount::text_capacity() const { return impl_->cap_bytes; }
 
-WordCountResult GpuWordCount::run(const TextInput& in) { return impl_->run(in); }
+// (Every job but an index or a search job overwrites what the resident index reads.)
+WordCountResult GpuWordCount::run(const TextInput& in) {
+  impl_->idx_resident = false;
+  return impl_->run(in);
+}
 WordCountResult GpuWordCount::run_source(TextSource& src) {
+  impl_->idx_resident = false;
   LOCUST_CHECK_ARG(impl_->streaming, "run_source needs a streaming engine (chunk_bytes set)");
   return impl_->run_source(src);
 }
-TopResult GpuWordCount::run_top(const TextInput& in, u32 k) { return impl_->run_top(in, k); }
+TopResult GpuWordCount::run_top(const TextInput& in, u32 k) {
+  impl_->idx_resident = false;
+  return impl_->run_top(in, k);
+}
 TopResult GpuWordCount::run_top_source(TextSource& src, u32 k) {
+  impl_->idx_resident = false;
   LOCUST_CHECK_ARG(impl_->streaming, "run_top_source needs a streaming engine (chunk_bytes set)");
   return impl_->run_top_source(src, k);
 }
 TopResult GpuWordCount::top_counts(const KeyCount* recs, u64 n, u32 k) {
+  impl_->idx_resident = false;
   return impl_->top_counts(recs, n, k);
 }
 IndexResult GpuWordCount::run_index(const TextInput& in) { return impl_->run_index(in); }
+SearchResult GpuWordCount::run_search(const TextInput& in,
+                                      const std::vector<SearchQuery>& queries) {
+  return impl_->run_search(in, queries);
+}
+SearchResult GpuWordCount::search_resident(const std::vector<SearchQuery>& queries) {
+  return impl_->search_resident(queries);
+}
 GpuWordCount::Stats GpuWordCount::stats() const {
   Stats s;
   s.retunes = impl_->pm_retunes;
@@ -51,6 +68,7 @@ GpuWordCount::Stats GpuWordCount::stats() const {
   s.streaming = impl_->streaming;
   s.chunk_bytes = impl_->cap_bytes;
   s.map_window = impl_->map_window;
+  s.search_bytes = impl_->sbatch_bytes + impl_->shits_bytes;
   return s;
 }
 
@@ -81,6 +99,7 @@ bool GpuWordCount::set_partition_map(const std::vector<u64>& lo) {
 
 std::vector<PackedKey> GpuWordCount::run_map_stage(const TextInput& in, WordCountResult* stats) {
   Impl& m = *impl_;
+  m.idx_resident = false;
   m.sync_clean = false;  // this entry point dirties d_sync
   m.check_input(in);
   const u64 t0 = now_ns();
@@ -117,6 +136,7 @@ std::vector<PackedKey> GpuWordCount::run_map_stage(const TextInput& in, WordCoun
 
 WordCountResult GpuWordCount::run_reduce_stage(const PackedKey* keys, u64 n) {
   Impl& m = *impl_;
+  m.idx_resident = false;
   m.sync_clean = false;  // this entry point dirties d_sync
   WordCountResult r;
   const u64 t0 = now_ns();
@@ -142,6 +162,7 @@ WordCountResult GpuWordCount::run_reduce_stage(const PackedKey* keys, u64 n) {
 std::vector<u32> GpuWordCount::sort_keys(const PackedKey* keys, u64 n,
                                          std::vector<PackedKey>* sorted) {
   Impl& m = *impl_;
+  m.idx_resident = false;
   m.sync_clean = false;  // this entry point dirties d_sync
   m.upload_tokens(keys, n);
   m.enqueue_process(0, false, false, n);
@@ -157,6 +178,7 @@ std::vector<u32> GpuWordCount::sort_keys(const PackedKey* keys, u64 n,
 std::vector<PackedKey> GpuWordCount::compact_slots(const u32* line_counts, u32 num_lines,
                                                    const PackedKey* slot_keys) {
   Impl& m = *impl_;
+  m.idx_resident = false;
   m.sync_clean = false;  // this entry point dirties d_sync
   LOCUST_CHECK_ARG(m.cfg.map_path == MapPath::kCompat, "compact_slots needs a compat engine");
   LOCUST_CHECK_ARG(num_lines <= m.cap_lines, "too many lines for engine capacity");
@@ -185,6 +207,7 @@ std::vector<PackedKey> GpuWordCount::compact_slots(const u32* line_counts, u32 n
 
 WordCountResult GpuWordCount::reduce_sorted(const PackedKey* sorted, u64 n) {
   Impl& m = *impl_;
+  m.idx_resident = false;
   m.sync_clean = false;  // this entry point dirties d_sync
   WordCountResult r;
   m.ensure_radix_full();
@@ -198,6 +221,7 @@ WordCountResult GpuWordCount::reduce_sorted(const PackedKey* sorted, u64 n) {
 
 WordCountResult GpuWordCount::merge_runs(const std::vector<std::vector<KeyCount>>& runs) {
   Impl& m = *impl_;
+  m.idx_resident = false;
   m.sync_clean = false;  // this entry point dirties d_sync
   LOCUST_CHECK_ARG(!runs.empty() && runs.size() <= (size_t)kMaxMergeRunsHost,
                    "need 1..64 runs");

@@ -28,6 +28,9 @@ u64 DevicePipeline::pinned_bytes() const {
   b += h_chunk_cap * sizeof(MapCounters);
   if (h_top) b += (kTopKMax + 1) * sizeof(TopRecord);
   if (h_ictr) b += h_post_cap * sizeof(u32) + sizeof(IndexCounters);
+  if (h_supload)
+    b += search_upload_bytes(kSearchMaxQueries) + h_slines_cap * sizeof(u32) +
+         ((u64)kSearchMaxQueries * (kSearchMaxTerms * 4 + 8) + 72);
   b += 2 * sizeof(MapCounters) + sizeof(SortPlan) + 2 * sizeof(PartMapTables) +
        kMaxSamples * sizeof(PackedKey) + (kMaxRanks + 8) * sizeof(u64) + 64 +
        kDictParts * sizeof(u32);
@@ -260,6 +263,7 @@ u64 DevicePipeline::device_bytes() const {
   if (d_plan) b += plan_zero_bytes;  // (+ the plan's key arrays: small)
   b += topk_bytes;                   // (0 until the first top job)
   b += index_bytes;                  // (0 until the first index job)
+  b += sbatch_bytes + shits_bytes;   // (0 until the first search job)
   return b;
 }
 
@@ -548,6 +552,13 @@ DevicePipeline::~DevicePipeline() {
   pinned_free(h_post);
   pinned_free(h_ictr);
   for (auto& e : ev_index)
+    if (e) (void)hipEventDestroy(e);
+  if (d_sbatch) (void)hipFree(d_sbatch);
+  if (d_shits) (void)hipFree(d_shits);
+  pinned_free(h_supload);
+  pinned_free(h_sres);
+  pinned_free(h_slines);
+  for (auto& e : ev_search)
     if (e) (void)hipEventDestroy(e);
 }
 
@@ -1901,19 +1912,15 @@ void DevicePipeline::check_index_job(const TextInput& in) const {
                        " B: use --backend cpu (the CPU engine indexes any size)");
 }
 
-IndexResult DevicePipeline::run_index(const TextInput& in) {
-  TraceRange tr("locust:index_job");
+void DevicePipeline::enqueue_index_job(const TextInput& in, WordCountResult& r,
+                                       bool ship_postings, u64* n_out, u64* T_out) {
   check_index_job(in);
   check_input(in);
   LOCUST_CHECK_ARG(in.first_line + in.num_lines <= (1ull << 32),
                    "index: line numbers past 2^32 do not fit a u32 posting");
   select_out();        // the previous result may still hold the last output buffer
   sync_clean = false;  // this entry point dirties d_sync
-  IndexResult x;
-  x.first_line = in.first_line;
-  WordCountResult& r = x.words;
   r.num_lines = in.num_lines;
-  const u64 t0 = now_ns();
   // the word job, its records left in d_out (as a top job)
   LOCUST_HIP_CHECK(hipEventRecord(ev[0], stream));
   enqueue_upload(in);
@@ -1953,18 +1960,17 @@ IndexResult DevicePipeline::run_index(const TextInput& in) {
   job.emits_per_line = cfg.emits_per_line;
   job.max_key_len = cfg.max_key_len;
   launch_index(job, index, h_plan, stream);
-  if (T)
+  if (T && ship_postings)
     LOCUST_HIP_CHECK(hipMemcpyAsync(h_post, index.postings, T * sizeof(u32),
                                     hipMemcpyDeviceToHost, stream));
   LOCUST_HIP_CHECK(hipMemcpyAsync(h_ictr, index.ctr, sizeof(IndexCounters),
                                   hipMemcpyDeviceToHost, stream));
   LOCUST_HIP_CHECK(hipEventRecord(ev_index[1], stream));
-  // the n records, as run()'s fallback paths deliver them
-  grow_host_out(n);
-  if (n) launch_copy_to_mapped(d_out_mapped, d_out, n * sizeof(OutRecord), stream);
-  LOCUST_HIP_CHECK(hipEventRecord(ev[5], stream));
-  sync();
-  copy_out(r.entries, n);
+  *n_out = n;
+  *T_out = T;
+}
+
+void DevicePipeline::check_index_counters(u64 n, u64 T) const {
   const IndexCounters ic = *h_ictr;
   if (ic.miss)
     throw Error("index: " + std::to_string(ic.miss) + " of " + std::to_string(T) +
@@ -1977,6 +1983,42 @@ IndexResult DevicePipeline::run_index(const TextInput& in) {
   if (ic.misplaced)
     throw Error("index: " + std::to_string(ic.misplaced) + " of " + std::to_string(T) +
                 " sorted pairs lie outside their word's range");
+}
+
+void DevicePipeline::keep_index(const TextInput& in, const WordCountResult& r, u64 n, u64 T) {
+  idx_words = WordCountResult{};  // the statistics only
+  idx_words.num_lines = r.num_lines;
+  idx_words.num_tokens = r.num_tokens;
+  idx_words.num_unique = n;
+  idx_words.overflow_lines = r.overflow_lines;
+  idx_words.truncated = r.truncated;
+  idx_words.max_key_len = r.max_key_len;
+  idx_view.recs = d_out;
+  idx_view.val = index.val;
+  idx_view.postings = index.postings;
+  idx_view.n = (u32)n;
+  idx_view.first_line = (u32)in.first_line;
+  idx_num_lines = in.num_lines;
+  idx_tokens = T;
+  idx_resident = true;
+}
+
+IndexResult DevicePipeline::run_index(const TextInput& in) {
+  TraceRange tr("locust:index_job");
+  idx_resident = false;  // (until this job has left its index)
+  IndexResult x;
+  x.first_line = in.first_line;
+  WordCountResult& r = x.words;
+  const u64 t0 = now_ns();
+  u64 n = 0, T = 0;
+  enqueue_index_job(in, r, /*ship_postings=*/true, &n, &T);
+  // the n records, as run()'s fallback paths deliver them
+  grow_host_out(n);
+  if (n) launch_copy_to_mapped(d_out_mapped, d_out, n * sizeof(OutRecord), stream);
+  LOCUST_HIP_CHECK(hipEventRecord(ev[5], stream));
+  sync();
+  copy_out(r.entries, n);
+  check_index_counters(n, T);
   x.postings.assign(h_post, h_post + T);
   x.index_ms = ms_between(ev_index[0], ev_index[1]);
   x.wire_bytes = T * sizeof(u32) + n * sizeof(OutRecord) + sizeof(IndexCounters);
@@ -1987,8 +2029,198 @@ IndexResult DevicePipeline::run_index(const TextInput& in) {
   r.times.d2h_ms = ms_between(ev_index[1], ev[5]);
   r.times.gpu_ms = ms_between(ev[0], ev[5]);
   r.times.wall_ms = (now_ns() - t0) * 1e-6;
+  keep_index(in, r, n, T);
   if (cfg.check) validate_index(x);
   return x;
+}
+
+// =====================================================================================
+// Index search
+// =====================================================================================
+namespace {
+constexpr u64 kSearchQT = (u64)kSearchMaxQueries * kSearchMaxTerms;
+// the pinned result block: [SearchCounters (64 B) | t_len | offsets]
+constexpr u64 kSearchResLen = 64;
+constexpr u64 kSearchResOff = kSearchResLen + kSearchQT * sizeof(u32);
+constexpr u64 kSearchResBytes = kSearchResOff + ((u64)kSearchMaxQueries + 1) * sizeof(u64);
+}  // namespace
+
+void DevicePipeline::ensure_search() {
+  if (d_sbatch) return;
+  // first search job of this engine: the batch arrays, the pinned buffers and the events
+  const u64 bytes = search_batch_bytes();
+  LOCUST_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&d_sbatch), bytes));
+  sbatch_bytes = bytes;
+  search_batch_carve(d_sbatch, &sbatch);
+  h_supload = static_cast<char*>(pinned_alloc(search_upload_bytes(kSearchMaxQueries),
+                                              hipHostMallocDefault, "search queries"));
+  h_sres = static_cast<char*>(pinned_alloc(kSearchResBytes, hipHostMallocDefault, "search result"));
+  for (auto& e : ev_search) LOCUST_HIP_CHECK(hipEventCreate(&e));
+}
+
+void DevicePipeline::ensure_search_hits(u64 bound) {
+  if (shits.cap >= std::max<u64>(bound, 1)) return;
+  sync();  // nothing in flight may still use the workspace being replaced
+  if (d_shits) LOCUST_HIP_CHECK(hipFree(d_shits));
+  d_shits = nullptr;
+  shits = SearchHits{};
+  shits_bytes = 0;
+  // whole sort tiles: the sort zeroes its status words for the capacity, not for the batch
+  const u64 cap = align_up(std::max<u64>(bound, 1), (u64)kSortTile);
+  const u64 bytes = search_hits_bytes(cap);
+  size_t fr = 0, tot = 0;
+  LOCUST_HIP_CHECK(hipMemGetInfo(&fr, &tot));
+  if ((double)bytes > kHbmUsable * (double)fr)
+    throw Error("search workspace (" + std::to_string(bytes) + " B needed for " +
+                std::to_string(cap) + " list elements) does not fit the free device memory (" +
+                std::to_string(fr) + " B free of " + std::to_string(tot) + " B)");
+  LOCUST_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&d_shits), bytes));
+  shits_bytes = bytes;
+  search_hits_carve(d_shits, cap, &shits);
+  LOCUST_HIP_CHECK(hipMemsetAsync(shits.zeros, 0, cap * 8, stream));
+}
+
+void DevicePipeline::check_search_batch(const std::vector<SearchQuery>& queries) const {
+  LOCUST_CHECK_ARG(queries.size() <= (size_t)kSearchMaxQueries,
+                   "search: a device batch holds at most kSearchMaxQueries = " +
+                       std::to_string(kSearchMaxQueries) + " queries, not " +
+                       std::to_string(queries.size()) + "; split the batch, or evaluate on the "
+                       "host (search_index / IndexResult.search)");
+  check_search_queries(queries, cfg);
+}
+
+void DevicePipeline::search_stage(const std::vector<SearchQuery>& queries, SearchResult* r) {
+  TraceRange tr("locust:search");
+  const u32 Q = (u32)queries.size();
+  r->queries = queries;
+  r->first_line = idx_view.first_line;
+  r->num_lines = idx_words.num_lines;
+  r->num_tokens = idx_words.num_tokens;
+  r->num_unique = idx_words.num_unique;
+  r->overflow_lines = idx_words.overflow_lines;
+  r->truncated = idx_words.truncated;
+  r->max_key_len = idx_words.max_key_len;
+  r->offsets.assign((size_t)Q + 1, 0);
+  r->term_counts.assign((size_t)Q * kSearchMaxTerms, 0);
+  ensure_search();
+  LOCUST_HIP_CHECK(hipEventRecord(ev_search[0], stream));
+  if (Q == 0) {
+    LOCUST_HIP_CHECK(hipEventRecord(ev_search[1], stream));
+    sync();
+    return;
+  }
+  // the batch: q_meta | the terms' keys, packed exactly as the map packs them
+  u32* meta = reinterpret_cast<u32*>(h_supload);
+  u64* keys = reinterpret_cast<u64*>(h_supload + (u64)kSearchMaxQueries * sizeof(u32));
+  std::memset(keys, 0, (size_t)Q * kSearchMaxTerms * sizeof(PackedKey));
+  for (u32 q = 0; q < Q; ++q) {
+    const SearchQuery& sq = queries[q];
+    meta[q] = (u32)sq.terms.size() | (sq.mode == SearchMode::kAny ? kSearchAny : 0u);
+    for (size_t t = 0; t < sq.terms.size(); ++t) {
+      const PackedKey k = search_term_key(sq.terms[t], cfg);
+      std::memcpy(keys + ((u64)q * kSearchMaxTerms + t) * kKeyWords, k.w, sizeof(PackedKey));
+    }
+  }
+  LOCUST_HIP_CHECK(hipMemcpyAsync(sbatch.upload, h_supload, search_upload_bytes(Q),
+                                  hipMemcpyHostToDevice, stream));
+  // lookup: the terms' lists and the bound on the hits
+  launch_search_lookup(idx_view, sbatch, Q, stream);
+  SearchCounters* h_sc = reinterpret_cast<SearchCounters*>(h_sres);
+  u32* h_tlen = reinterpret_cast<u32*>(h_sres + kSearchResLen);
+  u64* h_off = reinterpret_cast<u64*>(h_sres + kSearchResOff);
+  LOCUST_HIP_CHECK(hipMemcpyAsync(h_sc, sbatch.ctr, sizeof(SearchCounters), hipMemcpyDeviceToHost,
+                                  stream));
+  LOCUST_HIP_CHECK(hipMemcpyAsync(h_tlen, sbatch.t_len, (u64)Q * kSearchMaxTerms * sizeof(u32),
+                                  hipMemcpyDeviceToHost, stream));
+  sync();
+  const u64 B = h_sc->bound;
+  if (B >= (1ull << 32))
+    throw Error("search: the batch's " + std::to_string(Q) + " queries walk " + std::to_string(B) +
+                " list elements, which does not fit the 32-bit slot counter (2^32): split "
+                "the batch");
+  ensure_search_hits(B);
+  // hits
+  launch_search_hits(idx_view, sbatch, Q, B, shits, stream);
+  LOCUST_HIP_CHECK(hipMemcpyAsync(h_sc, sbatch.ctr, sizeof(SearchCounters), hipMemcpyDeviceToHost,
+                                  stream));
+  sync();
+  const u64 H = h_sc->written;
+  if (H > B || h_sc->sort_n != H)
+    throw Error("search: " + std::to_string(H) + " hits written, the lists hold " +
+                std::to_string(B) + " elements");
+  if (h_slines_cap < H) {
+    pinned_free(h_slines);
+    h_slines = nullptr;
+    h_slines_cap = align_up(H, (u64)kSortTile);
+    h_slines = static_cast<u32*>(
+        pinned_alloc(h_slines_cap * sizeof(u32), hipHostMallocDefault, "search lines"));
+  }
+  // order + emit
+  launch_search_order(idx_view, sbatch, Q, H, shits, h_plan, stream);
+  LOCUST_HIP_CHECK(hipMemcpyAsync(h_off, sbatch.offsets, ((u64)Q + 1) * sizeof(u64),
+                                  hipMemcpyDeviceToHost, stream));
+  if (H)
+    LOCUST_HIP_CHECK(hipMemcpyAsync(h_slines, shits.lines, H * sizeof(u32), hipMemcpyDeviceToHost,
+                                    stream));
+  LOCUST_HIP_CHECK(hipMemcpyAsync(h_sc, sbatch.ctr, sizeof(SearchCounters), hipMemcpyDeviceToHost,
+                                  stream));
+  LOCUST_HIP_CHECK(hipEventRecord(ev_search[1], stream));
+  sync();
+  if (h_sc->misplaced)
+    throw Error("search: " + std::to_string(h_sc->misplaced) + " of " + std::to_string(H) +
+                " sorted hits lie outside their query's range");
+  if (h_off[Q] != H)
+    throw Error("search: the per-query hit counts add up to " + std::to_string(h_off[Q]) +
+                ", the hit kernel wrote " + std::to_string(H));
+  r->offsets.assign(h_off, h_off + Q + 1);
+  r->lines.assign(h_slines, h_slines + H);
+  for (u64 i = 0; i < (u64)Q * kSearchMaxTerms; ++i) r->term_counts[i] = h_tlen[i];
+  r->wire_bytes = ((u64)Q + 1) * sizeof(u64) + H * sizeof(u32) +
+                  (u64)Q * kSearchMaxTerms * sizeof(u32) + 3 * sizeof(SearchCounters);
+}
+
+SearchResult DevicePipeline::run_search(const TextInput& in,
+                                        const std::vector<SearchQuery>& queries) {
+  TraceRange tr("locust:search_job");
+  check_search_batch(queries);  // (a refused batch starts nothing)
+  idx_resident = false;         // (until this job has left its index)
+  SearchResult r;
+  WordCountResult w;
+  const u64 t0 = now_ns();
+  u64 n = 0, T = 0;
+  enqueue_index_job(in, w, /*ship_postings=*/false, &n, &T);
+  sync();
+  check_index_counters(n, T);
+  keep_index(in, w, n, T);
+  search_stage(queries, &r);
+  r.index_ms = ms_between(ev_index[0], ev_index[1]);
+  r.search_ms = ms_between(ev_search[0], ev_search[1]);
+  r.wire_bytes += sizeof(IndexCounters) + sizeof(MapCounters);
+  r.times.h2d_ms = ms_between(ev[0], ev[1]);
+  r.times.map_ms = ms_between(ev[1], ev[2]);
+  r.times.process_ms = ms_between(ev[2], ev[3]);
+  r.times.reduce_ms = ms_between(ev[3], ev[4]);
+  r.times.gpu_ms = ms_between(ev[0], ev_search[1]);
+  r.times.wall_ms = (now_ns() - t0) * 1e-6;
+  if (cfg.check) validate_search(r);
+  return r;
+}
+
+SearchResult DevicePipeline::search_resident(const std::vector<SearchQuery>& queries) {
+  TraceRange tr("locust:search_resident");
+  check_search_batch(queries);
+  if (!idx_resident)
+    throw Error("search_resident: the index on the device is stale -- this engine's last job "
+                "was not a run_index or a run_search (any other job, a refused one included, "
+                "overwrites what the index reads); run one of them first");
+  SearchResult r;
+  const u64 t0 = now_ns();
+  search_stage(queries, &r);
+  r.search_ms = ms_between(ev_search[0], ev_search[1]);
+  r.times.gpu_ms = r.search_ms;
+  r.times.wall_ms = (now_ns() - t0) * 1e-6;
+  if (cfg.check) validate_search(r);
+  return r;
 }
 
 bool DevicePipeline::host_pinned(const void* p) {

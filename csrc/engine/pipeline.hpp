@@ -778,6 +778,46 @@ struct DevicePipeline {
   // Throws unless this engine's configuration and `in` suit an index job; launches nothing.
   void check_index_job(const TextInput& in) const;
   IndexResult run_index(const TextInput& in);
+  // The word job and the index stage of an index or a search job, enqueued up to the
+  // stage's counters (ev_index[1]); ship_postings: the postings' D2H between the two, as
+  // run_index orders it.  The caller synchronises, then check_index_counters.
+  void enqueue_index_job(const TextInput& in, WordCountResult& r, bool ship_postings, u64* n_out,
+                         u64* T_out);
+  void check_index_counters(u64 n, u64 T) const;
+
+  // ---- index search (kernels/search.hip) ----
+  // The index the last run_index / run_search left on the device: d_out's records and the
+  // index workspace's val and postings.  Every other job entry point of GpuWordCount
+  // clears idx_resident (their kernels reuse d_out and the text), and so does an index or
+  // search job until it has completed.  The search stage's batch arrays, hit workspace
+  // (grown by the batch's bound; checked against free HBM), pinned buffers and events are
+  // separate allocations made by the first search job: a word, top or index job allocates
+  // nothing for search, and nothing of it overlaps the index.
+  bool idx_resident = false;
+  SearchIndex idx_view{};
+  u64 idx_num_lines = 0, idx_tokens = 0;
+  WordCountResult idx_words;  // the word job's statistics (no entries)
+  void keep_index(const TextInput& in, const WordCountResult& r, u64 n, u64 T);
+  SearchBatch sbatch{};
+  char* d_sbatch = nullptr;
+  u64 sbatch_bytes = 0;
+  SearchHits shits{};
+  char* d_shits = nullptr;
+  u64 shits_bytes = 0;
+  char* h_supload = nullptr;  // pinned [q_meta | keys]
+  char* h_sres = nullptr;     // pinned [SearchCounters | t_len | offsets]
+  u32* h_slines = nullptr;    // pinned answer lines
+  u64 h_slines_cap = 0;
+  hipEvent_t ev_search[2] = {};
+  void ensure_search();
+  void ensure_search_hits(u64 bound);
+  // Throws unless the batch fits the device stage and every term is valid; launches nothing.
+  void check_search_batch(const std::vector<SearchQuery>& queries) const;
+  // The batch over idx_view on `stream`, timed by ev_search; synchronises (the bound, the
+  // number of hits, the result) and fills r's lists, statistics and wire_bytes.
+  void search_stage(const std::vector<SearchQuery>& queries, SearchResult* r);
+  SearchResult run_search(const TextInput& in, const std::vector<SearchQuery>& queries);
+  SearchResult search_resident(const std::vector<SearchQuery>& queries);
 
   // ---------------------------------------------------------------------------------
   // Streaming: an input larger than the engine's text capacity is processed in

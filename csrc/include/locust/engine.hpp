@@ -339,6 +339,61 @@ void validate_index(const IndexResult& r);
 //   "print key: <key> \t count: <count> \t lines: <l0> <l1> ...\n"
 void format_index_output(const IndexResult& r, std::string* out);
 
+// ---- index search: all/any word queries over the inverted index ----
+// A query is 1 to kSearchMaxTerms terms and a mode.  A term is a non-empty byte string
+// without NUL, newline or a byte of the job's delimiter set; one longer than max_key_len is
+// cut to its first max_key_len bytes, as the map cuts keys, and so matches the merged list
+// of every long word with that prefix.  A term's lines are the distinct lines of its
+// postings list (none when the word is absent).  `all` answers the intersection of the
+// terms' lines (empty as soon as one term is absent), `any` their union; a term repeated
+// inside a query changes nothing.  The answer is global line numbers, ascending, each once:
+// a pure function of the index.  Each term also reports its word's count (0: absent).
+//
+// The device stage (kernels/search.hip; GpuWordCount::run_search / search_resident)
+// answers batches of up to kSearchMaxQueries queries from the index in device memory:
+// neither postings nor records cross PCIe.  The host evaluation (search_index) takes any
+// number of queries.
+constexpr u32 kSearchMaxQueries = 1024;
+constexpr u32 kSearchMaxTerms = 8;
+enum class SearchMode { kAll, kAny };
+struct SearchQuery {
+  std::vector<std::string> terms;
+  SearchMode mode = SearchMode::kAll;
+};
+struct SearchResult {
+  std::vector<SearchQuery> queries;  // as asked (terms uncut)
+  std::vector<u64> offsets;          // [queries + 1]: query i's lines are lines[offsets[i] .. offsets[i+1])
+  std::vector<u32> lines;            // global line numbers, per query strictly ascending
+  std::vector<u64> term_counts;      // [queries * kSearchMaxTerms]: term t of query i at i * 8 + t
+  u64 first_line = 0;
+  // the word job's statistics, as in TopResult
+  u64 num_lines = 0;
+  u64 num_tokens = 0;
+  u64 num_unique = 0;
+  u64 overflow_lines = 0;
+  u64 truncated = 0;
+  u64 max_key_len = 0;
+  StageTimes times;
+  double index_ms = 0;   // device time of the index stage (0: built on the host, or resident)
+  double search_ms = 0;  // device time of the search stage (host evaluation: its wall time)
+  u64 wire_bytes = 0;    // bytes the device wrote to host memory for the result
+  u64 hits() const { return lines.size(); }
+};
+// A term's key: its first min(size, cfg.max_key_len) bytes, packed as the map packs keys.
+PackedKey search_term_key(const std::string& term, const JobConfig& cfg);
+// Throws unless every query has 1..kSearchMaxTerms valid terms for cfg's delimiter set.
+void check_search_queries(const std::vector<SearchQuery>& queries, const JobConfig& cfg);
+// The host evaluation over an index result, any number of queries (cfg: the index job's
+// delimiters and max_key_len).
+SearchResult search_index(const IndexResult& x, const std::vector<SearchQuery>& queries,
+                          const JobConfig& cfg);
+// LOCUST_CHECK invariants of a search result: offsets monotone from 0 to lines.size(), every
+// query's lines strictly ascending and inside [first_line, first_line + num_lines).
+void validate_search(const SearchResult& r);
+// The result lines of a search, one per query:
+//   "print query: <terms joined by one space> \t hits: <h> \t lines: <l0> <l1> ...\n"
+void format_search_output(const SearchResult& r, std::string* out);
+
 // Text read piece by piece (a file too large to hold): whole lines go straight into the
 // engine's pinned staging, so host memory stays bounded by two chunks whatever the input.
 class TextSource {
@@ -416,6 +471,8 @@ class GpuWordCount {
     u64 device_bytes = 0, hbm_free = 0, hbm_total = 0;
     bool streaming = false;
     u64 chunk_bytes = 0, map_window = 0;
+    // device bytes of the search stage's workspace (0 until the first search job)
+    u64 search_bytes = 0;
   };
   Stats stats() const;
 
@@ -465,6 +522,15 @@ class GpuWordCount {
   // pass; larger inputs and sources: the CPU engine).
   IndexResult run_index(const TextInput& in);
 
+  // run_index's word job and index stage, then the search stage over the index in device
+  // memory (kernels/search.hip): up to kSearchMaxQueries queries; only the answers, the
+  // per-term counts and the counters cross PCIe.  run_index's refusals apply.
+  SearchResult run_search(const TextInput& in, const std::vector<SearchQuery>& queries);
+  // Another batch from the index this engine's last job left on the device.  That job must
+  // have been a run_index or a run_search: any other job (a refused one that had started
+  // to write included) marks the index stale, and this then throws.
+  SearchResult search_resident(const std::vector<SearchQuery>& queries);
+
   const JobConfig& config() const;
   u64 token_capacity() const;
   u64 text_capacity() const;  // bytes per device pass (input_buffer() size)
@@ -510,6 +576,8 @@ class CpuWordCount {
   // The inverted index on the host, any size: (key, line) pairs, one stable sort by key.
   // Word keys only (ngram == 1), like the GPU job.
   IndexResult run_index(const TextInput& in);
+  // run_index() + the host evaluation (search_index), any size and any number of queries.
+  SearchResult run_search(const TextInput& in, const std::vector<SearchQuery>& queries);
   std::vector<PackedKey> run_map_stage(const TextInput& in, WordCountResult* stats);
   WordCountResult run_reduce_stage(const PackedKey* keys, u64 n);
 

@@ -619,6 +619,94 @@ struct IndexJob {
 // h_plan (pinned) and synchronises `s` once, as radix_sort does.
 void launch_index(const IndexJob& job, IndexWorkspace& ws, SortPlan* h_plan, hipStream_t s);
 
+// ---------------- search.hip ----------------
+// All/any word queries over the inverted index launch_index left on the device (engine.hpp
+// "index search"): the key-ordered records, the CSR offsets `val` and the sorted postings.
+// A batch holds Q <= kSearchMaxQueries queries of <= kSearchMaxTerms terms each.
+//
+// A sequence of kernels on `s`; data moves between workgroups only across the kernel
+// boundaries (the radix sort it reuses keeps its own look-back), no polled word:
+//   lookup   one thread per (query, term): find_rank of the packed key, the term's val and
+//            length; per query the distinct terms, the driver (the shortest list, `all`), the
+//            dead flag (`all` with an absent term) and the bound on its hits = the elements
+//            it walks: the driver's length (`all`) or the distinct terms' lengths (`any`)
+//   scan     one workgroup: q_start[0 .. Q] = exclusive scan of the bounds, the total B
+//   (the host reads B and the term counts, and sizes the hit workspace)
+//   hits     a grid walks the flattened (query, list element) space in tiles of kSearchTile.
+//            An element counts when it is the first of its line in its list; `all`: when a
+//            binary search finds the line in every other distinct term's list; `any`: when
+//            none of the earlier distinct terms' lists holds it.  A hit is the pair word
+//            query << 32 | (line - first_line); its slot comes from one atomic per wave and
+//            step, the per-query hit counts from one atomic per wave, step and query
+//   seal     one thread: the sort's length, capped by the workspace
+//   (the host reads the number of hits H: the sort takes its regime from it)
+//   order    radix_sort() of the pair words as one-word keys
+//   offsets  one workgroup: offsets[0 .. Q] = exclusive scan of the per-query hit counts
+//   emit     lines[j] = first_line + low32(sorted[j]); a pair outside the offsets range of
+//            the query it names counts as misplaced
+struct SearchCounters {  // zeroed per batch
+  u64 bound;      // B: the elements the hit kernel walks = the upper bound on the hits
+  u32 written;    // hits the hit kernel found
+  u32 sort_n;     // pairs handed to the sort: `written` if the workspace holds them, else 0
+  u32 misplaced;  // sorted pairs outside their query's range
+  u32 pad;
+};
+constexpr int kSearchBlock = 256;
+constexpr int kSearchItems = 4;
+constexpr int kSearchTile = kSearchBlock * kSearchItems;  // elements per workgroup and step
+constexpr int kSearchMaxBlocks = 2048;                     // the hit kernel's grid cap
+constexpr u32 kSearchAny = 1u << 8;                        // q_meta: nterms | kSearchAny
+// The index a batch is answered from (all device memory, launch_index's output).
+struct SearchIndex {
+  const OutRecord* recs = nullptr;  // [n] key order
+  const u64* val = nullptr;         // [n + 1] CSR offsets
+  const u32* postings = nullptr;    // [val[n]] global line numbers
+  u32 n = 0;
+  u32 first_line = 0;
+};
+// The per-batch arrays: fixed size (kSearchMaxQueries), made by the first search job.
+struct SearchBatch {
+  char* upload = nullptr;  // [q_meta | keys]: one H2D per batch
+  u32* q_meta = nullptr;   // [kSearchMaxQueries] nterms | mode bit
+  u64* keys = nullptr;     // [Q * kSearchMaxTerms][kKeyWords] packed as kv.hpp packs
+  char* zero = nullptr;    // [SearchCounters | q_hits], zeroed per batch
+  u64 zero_bytes = 0;
+  SearchCounters* ctr = nullptr;
+  u32* q_hits = nullptr;   // [Q] hits per query
+  u64* t_val = nullptr;    // [Q * kSearchMaxTerms] the term's CSR offset
+  u32* t_len = nullptr;    // [Q * kSearchMaxTerms] its list's length = the word's count; 0: absent
+  u32* q_info = nullptr;   // [Q] driver | dead << 8 | distinct-term mask << 16
+  u32* q_bound = nullptr;  // [Q]
+  u64* q_start = nullptr;  // [Q + 1]
+  u64* offsets = nullptr;  // [Q + 1]
+};
+// The hit arrays, sized by the batch's bound B (grown on demand).
+struct SearchHits {
+  u64* pairs = nullptr;   // [cap] query << 32 | line, in arbitrary order
+  u64* zeros = nullptr;   // [cap] zero: key words 1..3 of the sort
+  u64* sorted = nullptr;  // [cap]
+  u64* spare = nullptr;   // [cap]
+  u32* lines = nullptr;   // [cap]
+  RadixWorkspace rx{};
+  u64 cap = 0;
+};
+u64 search_upload_bytes(u32 queries);  // bytes of SearchBatch::upload a batch of Q fills
+u64 search_batch_bytes();
+void search_batch_carve(char* base, SearchBatch* b);
+u64 search_hits_bytes(u64 cap);
+// Carves `base` (search_hits_bytes(cap) bytes, 256-B aligned).  The caller zeroes h->zeros once.
+void search_hits_carve(char* base, u64 cap, SearchHits* h);
+// lookup + scan: b.ctr->bound, b.t_len and b.q_start are complete when `s` has drained.
+void launch_search_lookup(const SearchIndex& ix, const SearchBatch& b, u32 queries, hipStream_t s);
+// hits + seal over the `bound` elements the lookup reported (bound <= h.cap).
+void launch_search_hits(const SearchIndex& ix, const SearchBatch& b, u32 queries, u64 bound,
+                        const SearchHits& h, hipStream_t s);
+// order + offsets + emit of the `hits` pairs the hit kernel wrote (b.ctr->sort_n == hits):
+// b.offsets[0 .. Q], h.lines[0 .. hits) and b.ctr->misplaced.  More than kSmallSortMax hits
+// read the sort's plan back through h_plan and synchronise `s` once, as radix_sort does.
+void launch_search_order(const SearchIndex& ix, const SearchBatch& b, u32 queries, u64 hits,
+                         SearchHits& h, SortPlan* h_plan, hipStream_t s);
+
 // ---- device self-test of the string library (tests only; StringTestOut in engine.hpp) ----
 void launch_string_selftest(const char* blob, const u32* off, u32 n, const char* delims,
                             const int* ints, StringTestOut* out, hipStream_t s);
@@ -639,6 +727,7 @@ void warm_module_partplan();
 void warm_module_psort();
 void warm_module_radix_sort();
 void warm_module_reduce();
+void warm_module_search();  // (as index: the code object only, no buffers)
 void warm_module_shuffle();
 void warm_module_signal();
 void warm_module_tokenize();
@@ -657,6 +746,7 @@ inline void warm_kernel_modules() {
   warm_module_psort();
   warm_module_radix_sort();
   warm_module_reduce();
+  warm_module_search();
   warm_module_shuffle();
   warm_module_signal();
   warm_module_tokenize();

@@ -28,6 +28,7 @@
 // radix sort keep their own look-back); this file adds no polled word.
 #include <algorithm>
 
+#include "locust/device/rank.hpp"
 #include "locust/device/wave.hpp"
 #include "locust/dstring.hpp"
 #include "locust/hip_check.hpp"
@@ -104,42 +105,6 @@ __global__ __launch_bounds__(kIndexBlock) void index_val_kernel(
     if (first + t < n) val[first + t] = at;
     at += c[t];
   }
-}
-
-// The rank of key (w0..w3) among the n sorted, distinct records; n when it is absent.
-__device__ __forceinline__ u32 find_rank(const OutRecord* __restrict__ recs, u32 n, u64 w0, u64 w1,
-                                         u64 w2, u64 w3) {
-  u32 lo = 0, hi = n;
-  while (lo < hi) {  // lower bound
-    const u32 mid = lo + ((hi - lo) >> 1);
-    const OutRecord* r = recs + mid;
-    bool less;  // recs[mid] < key
-    const u64 a0 = r->w[0];
-    if (a0 != w0) {
-      less = a0 < w0;
-    } else {
-      const u64 a1 = r->w[1];
-      if (a1 != w1) {
-        less = a1 < w1;
-      } else {
-        const u64 a2 = r->w[2];
-        if (a2 != w2) {
-          less = a2 < w2;
-        } else {
-          less = r->w[3] < w3;
-        }
-      }
-    }
-    if (less)
-      lo = mid + 1;
-    else
-      hi = mid;
-  }
-  if (lo < n) {
-    const OutRecord* r = recs + lo;
-    if (r->w[0] == w0 && r->w[1] == w1 && r->w[2] == w2 && r->w[3] == w3) return lo;
-  }
-  return n;
 }
 
 // The token starts of one 64-byte step of a line (c: this lane's byte, 0 past the line end;
@@ -234,7 +199,7 @@ __global__ __launch_bounds__(kIdxMapBlock) void index_map_kernel(
             w2 |= wi == 2 ? v : 0ull;
             w3 |= wi == 3 ? v : 0ull;
           }
-          const u32 rank = find_rank(recs, n, w0, w1, w2, w3);
+          const u32 rank = dev::find_rank(recs, n, w0, w1, w2, w3);
           found = rank < n;
           const u64 slot = (u64)at + (u32)__popcll(em & below);
           if (found && slot < pair_cap) pairs[slot] = ((u64)rank << 32) | (u64)(u32)line;

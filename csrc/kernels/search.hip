@@ -1,0 +1,395 @@
+// Index search: all/any word queries over the inverted index in device memory (kernels.hpp
+// "search.hip"; the semantics are engine.hpp "index search").
+//
+// launch_index has left the key-ordered records, the CSR offsets val[0 .. n] and the sorted
+// postings in device memory.  A query's answer needs rank lookups and searches in sorted
+// lists only, and is usually far smaller than the index: it is selected here and only the
+// answers cross PCIe.
+//
+// Shape (gfx950, wave64):
+//  * search_lookup_kernel: one thread per (query, term), 32 queries per workgroup.  The key
+//    was packed on the host (kv.hpp); find_rank gives the rank, val[] and the record's count
+//    the list.  The eight terms of a query meet in LDS, where the query's first thread marks
+//    the distinct terms (a repeated term has the rank of an earlier one), picks the driver
+//    and writes the bound on the query's hits = the elements the hit kernel walks for it;
+//  * search_scan_kernel: one workgroup, exclusive scan of <= kSearchMaxQueries u32 values
+//    into Q + 1 u64 words (the bounds -> q_start, later the hit counts -> offsets);
+//  * search_hit_kernel: the flattened element space [0, B) in tiles of kSearchTile, grid-
+//    stride.  A thread finds its element's query by a binary search in q_start, then the
+//    term and position, and decides the hit by binary searches confined to the other
+//    terms' CSR ranges.  Every step ends in wave-level ballots: one atomic reserves the
+//    step's slots, one atomic per distinct query of the wave adds to its hit count;
+//  * order: the device-wide radix_sort() on the one-word key, as launch_index uses it;
+//  * search_emit_kernel: lines[j] = first_line + low32(sorted[j]) and the misplaced check.
+// Data crosses between workgroups only at kernel boundaries (the radix sort keeps its own
+// look-back); this file adds no polled word.
+#include <algorithm>
+
+#include "locust/device/rank.hpp"
+#include "locust/device/wave.hpp"
+#include "locust/hip_check.hpp"
+#include "locust/kernels.hpp"
+
+namespace locust {
+namespace {
+
+constexpr int kTerms = (int)kSearchMaxTerms;
+constexpr int kLookupQueries = kSearchBlock / kTerms;  // queries per lookup workgroup
+static_assert(kTerms == 8 && kSearchBlock % kTerms == 0, "eight term threads per query");
+static_assert(kSearchMaxQueries % kSearchBlock == 0, "the scan walks whole blocks");
+
+__global__ __launch_bounds__(kSearchBlock) void search_lookup_kernel(
+    const OutRecord* __restrict__ recs, u32 n, const u64* __restrict__ val,
+    const u64* __restrict__ keys, const u32* __restrict__ q_meta, u32 Q, u64* __restrict__ t_val,
+    u32* __restrict__ t_len, u32* __restrict__ q_info, u32* __restrict__ q_bound) {
+  __shared__ u32 s_rank[kSearchBlock];
+  __shared__ u32 s_len[kSearchBlock];
+  const u32 gid = blockIdx.x * kSearchBlock + threadIdx.x;
+  const u32 q = gid / kTerms, t = gid % kTerms;
+  const u32 meta = q < Q ? q_meta[q] : 0u;
+  const u32 nterms = meta & 0xffu;
+  u32 rank = n, len = 0;
+  u64 at = 0;
+  if (t < nterms) {
+    const u64* k = keys + (u64)gid * kKeyWords;
+    rank = dev::find_rank(recs, n, k[0], k[1], k[2], k[3]);
+    if (rank < n) {
+      at = val[rank];
+      len = (u32)recs[rank].count;  // (the index holds < 2^32 postings in all)
+    }
+  }
+  if (q < Q) {
+    t_val[gid] = at;
+    t_len[gid] = len;
+  }
+  s_rank[threadIdx.x] = rank;
+  s_len[threadIdx.x] = len;
+  __syncthreads();
+  if (q < Q && t == 0) {
+    const bool any = (meta & kSearchAny) != 0;
+    const u32* rk = s_rank + threadIdx.x;
+    const u32* ln = s_len + threadIdx.x;
+    u32 mask = 0, dead = 0, driver = 0, best = ~0u;
+    u64 sum = 0;
+    for (u32 j = 0; j < nterms; ++j) {
+      if (rk[j] >= n) {  // absent
+        dead |= any ? 0u : 1u;
+        continue;
+      }
+      bool dup = false;
+      for (u32 i = 0; i < j; ++i) dup |= rk[i] == rk[j];
+      if (dup) continue;
+      mask |= 1u << j;
+      sum += ln[j];
+      if (ln[j] < best) {
+        best = ln[j];
+        driver = j;
+      }
+    }
+    // the distinct lists are disjoint ranges of < 2^32 postings: sum fits 32 bits
+    const u32 bound = any ? (u32)sum : (dead || !mask ? 0u : best);
+    q_info[q] = driver | (dead << 8) | (mask << 16);
+    q_bound[q] = bound;
+  }
+}
+
+// One workgroup: out[0 .. Q] = exclusive scan of in[0 .. Q); the total also to *total.
+__global__ __launch_bounds__(kSearchBlock) void search_scan_kernel(const u32* __restrict__ in,
+                                                                   u32 Q, u64* __restrict__ out,
+                                                                   u64* __restrict__ total) {
+  __shared__ u64 s_scan[kSearchBlock / 64 + 1];
+  u64 carry = 0;
+  for (u32 base = 0; base < Q; base += kSearchBlock) {  // (workgroup-uniform)
+    const u32 i = base + threadIdx.x;
+    const u64 v = i < Q ? in[i] : 0;
+    u64 tv;
+    const u64 ev = dev::block_exclusive_scan<u64, kSearchBlock>(v, s_scan, &tv);
+    if (i < Q) out[i] = carry + ev;
+    carry += tv;
+  }
+  if (threadIdx.x == 0) {
+    out[Q] = carry;
+    if (total) *total = carry;
+  }
+}
+
+// Is `line` among the len sorted postings at p?  (Never reads outside [p, p + len).)
+__device__ __forceinline__ bool list_has(const u32* __restrict__ p, u32 len, u32 line) {
+  u32 lo = 0, hi = len;
+  while (lo < hi) {
+    const u32 mid = lo + ((hi - lo) >> 1);
+    if (p[mid] < line)
+      lo = mid + 1;
+    else
+      hi = mid;
+  }
+  return lo < len && p[lo] == line;
+}
+
+__global__ __launch_bounds__(kSearchBlock) void search_hit_kernel(
+    const u32* __restrict__ postings, u32 first_line, const u32* __restrict__ q_meta,
+    const u32* __restrict__ q_info, const u64* __restrict__ q_start, const u64* __restrict__ t_val,
+    const u32* __restrict__ t_len, u32 Q, u64 B, u64* __restrict__ pairs, u64 pair_cap,
+    u32* __restrict__ q_hits, SearchCounters* __restrict__ ctr) {
+  const int lane = dev::lane_id();
+  for (u64 tile = blockIdx.x; tile * kSearchTile < B; tile += gridDim.x) {  // (uniform)
+#pragma unroll 1
+    for (int j = 0; j < kSearchItems; ++j) {
+      const u64 e = tile * kSearchTile + (u64)j * kSearchBlock + threadIdx.x;
+      bool hit = false;
+      u32 q = 0, line = 0;
+      if (e < B) {
+        // the query: q_start[q] <= e < q_start[q + 1] (q_start[0] = 0, q_start[Q] = B)
+        u32 lo = 0, hi = Q;
+        while (hi - lo > 1) {
+          const u32 mid = lo + ((hi - lo) >> 1);
+          if (q_start[mid] <= e)
+            lo = mid;
+          else
+            hi = mid;
+        }
+        q = lo;
+        u32 local = (u32)(e - q_start[q]);
+        const u32 info = q_info[q];
+        const bool any = (q_meta[q] & kSearchAny) != 0;
+        const u32 mask = (info >> 16) & 0xffu;
+        const u64* tv = t_val + (u64)q * kTerms;
+        const u32* tl = t_len + (u64)q * kTerms;
+        u32 term = info & 0xffu;  // `all`: the driver
+        if (any) {                // the distinct terms' lists one after the other
+          term = 0;
+          for (u32 t = 0; t < (u32)kTerms; ++t) {
+            if (!((mask >> t) & 1u)) continue;
+            term = t;
+            if (local < tl[t]) break;
+            local -= tl[t];
+          }
+        }
+        if (local < tl[term]) {  // (always, by the bound's construction)
+          const u32* list = postings + tv[term];
+          line = list[local];
+          // duplicates are adjacent: an element counts once per line
+          if (local == 0 || list[local - 1] != line) {
+            hit = true;
+            if (any) {
+              for (u32 t = 0; t < term; ++t)
+                if (((mask >> t) & 1u) && list_has(postings + tv[t], tl[t], line)) hit = false;
+            } else {
+              for (u32 t = 0; t < (u32)kTerms && hit; ++t)
+                if (((mask >> t) & 1u) && t != term) hit = list_has(postings + tv[t], tl[t], line);
+            }
+          }
+        }
+      }
+      // ---- the step's hits: the wave is converged here ----
+      const u64 hm = dev::ballot(hit);
+      if (hm == 0) continue;  // (wave-uniform)
+      const int first = __ffsll((unsigned long long)hm) - 1;
+      u32 at = 0;
+      if (lane == first) at = atomicAdd(&ctr->written, (u32)__popcll(hm));
+      at = (u32)__shfl((int)at, first, 64);
+      if (hit) {
+        const u64 slot = (u64)at + dev::lanes_below(hm);
+        if (slot < pair_cap) pairs[slot] = ((u64)q << 32) | (u64)(line - first_line);
+      }
+      // per query: one atomic for all of the wave's hits of that query
+      u64 rem = hm;
+      while (rem) {  // (wave-uniform)
+        const int leader = __ffsll((unsigned long long)rem) - 1;
+        const u32 ql = (u32)__shfl((int)q, leader, 64);
+        const u64 same = dev::ballot(hit && q == ql);
+        if (lane == leader) atomicAdd(&q_hits[ql], (u32)__popcll(same));
+        rem &= ~same;
+      }
+    }
+  }
+}
+
+// One thread, between the hits and the sort: the sort takes its length from device memory,
+// and never more than the workspace holds.
+__global__ void search_seal_kernel(SearchCounters* __restrict__ ctr, u64 cap) {
+  ctr->sort_n = ctr->written <= cap ? ctr->written : 0u;
+}
+
+// lines[j] = first_line + the pair's line; a pair outside its query's offsets range counts
+// as misplaced.
+__global__ __launch_bounds__(256) void search_emit_kernel(const u64* __restrict__ sorted, u64 H,
+                                                          const u64* __restrict__ offsets, u32 Q,
+                                                          u32 first_line, u32* __restrict__ lines,
+                                                          SearchCounters* __restrict__ ctr) {
+  if (ctr->sort_n != (u32)H) return;  // nothing was sorted (workgroup-uniform)
+  u32 bad = 0;
+  for (u64 j = (u64)blockIdx.x * 256 + threadIdx.x; j < H; j += (u64)gridDim.x * 256) {
+    const u64 w = sorted[j];
+    const u32 q = (u32)(w >> 32);
+    lines[j] = first_line + (u32)w;
+    if (q >= Q || j < offsets[q] || j >= offsets[q + 1]) ++bad;
+  }
+  const u64 bm = dev::ballot(bad != 0);
+  if (bm) {
+    bad = dev::wave_reduce_sum(bad);
+    if (dev::lane_id() == 0) atomicAdd(&ctr->misplaced, bad);
+  }
+}
+
+constexpr u64 kQ = kSearchMaxQueries;
+constexpr u64 kQT = kQ * kSearchMaxTerms;
+
+// The batch block's parts in order.
+template <class Take>
+void batch_layout(Take&& take) {
+  take(search_upload_bytes((u32)kQ));          // upload: q_meta | keys
+  take(64 + kQ * 4);                           // zero: ctr (64 B) | q_hits
+  take(kQT * 8);                               // t_val
+  take(kQT * 4);                               // t_len
+  take(kQ * 4);                                // q_info
+  take(kQ * 4);                                // q_bound
+  take((kQ + 1) * 8);                          // q_start
+  take((kQ + 1) * 8);                          // offsets
+}
+static_assert(sizeof(SearchCounters) <= 64, "zero block layout");
+
+template <class Take>
+void hits_layout(u64 cap, Take&& take) {
+  take(cap * 8);                                               // pairs
+  take(cap * 8);                                               // zeros
+  take(cap * 8);                                               // sorted
+  take(cap * 8);                                               // spare
+  take(cap * 4);                                               // lines
+  take(radix_zero_bytes(cap));                                 // rx counters + status
+  take((u64)radix_hist_blocks(cap) * kNumPositions * 256 * 4);  // rx hist_part
+  take(sizeof(SortPlan));                                      // rx plan
+  take(cap * 8);                                               // rx keys[0]
+  take(cap * 8);                                               // rx keys[1]
+  take(cap * 4);                                               // rx vals[0]
+  take(cap * 4);                                               // rx vals[1]
+}
+
+}  // namespace
+
+u64 search_upload_bytes(u32 queries) {
+  return kQ * 4 + (u64)queries * kSearchMaxTerms * kKeyWords * 8;
+}
+
+u64 search_batch_bytes() {
+  u64 b = 0;
+  batch_layout([&](u64 bytes) { b = align_up(b, 256) + bytes; });
+  return align_up(b, 256);
+}
+
+void search_batch_carve(char* base, SearchBatch* sb) {
+  char* part[8];
+  int k = 0;
+  u64 b = 0;
+  batch_layout([&](u64 bytes) {
+    b = align_up(b, 256);
+    part[k++] = base + b;
+    b += bytes;
+  });
+  sb->upload = part[0];
+  sb->q_meta = reinterpret_cast<u32*>(part[0]);
+  sb->keys = reinterpret_cast<u64*>(part[0] + kQ * 4);
+  sb->zero = part[1];
+  sb->zero_bytes = 64 + kQ * 4;
+  sb->ctr = reinterpret_cast<SearchCounters*>(part[1]);
+  sb->q_hits = reinterpret_cast<u32*>(part[1] + 64);
+  sb->t_val = reinterpret_cast<u64*>(part[2]);
+  sb->t_len = reinterpret_cast<u32*>(part[3]);
+  sb->q_info = reinterpret_cast<u32*>(part[4]);
+  sb->q_bound = reinterpret_cast<u32*>(part[5]);
+  sb->q_start = reinterpret_cast<u64*>(part[6]);
+  sb->offsets = reinterpret_cast<u64*>(part[7]);
+}
+
+u64 search_hits_bytes(u64 cap) {
+  u64 b = 0;
+  hits_layout(cap, [&](u64 bytes) { b = align_up(b, 256) + bytes; });
+  return align_up(b, 256);
+}
+
+void search_hits_carve(char* base, u64 cap, SearchHits* h) {
+  char* part[12];
+  int k = 0;
+  u64 b = 0;
+  hits_layout(cap, [&](u64 bytes) {
+    b = align_up(b, 256);
+    part[k++] = base + b;
+    b += bytes;
+  });
+  h->pairs = reinterpret_cast<u64*>(part[0]);
+  h->zeros = reinterpret_cast<u64*>(part[1]);
+  h->sorted = reinterpret_cast<u64*>(part[2]);
+  h->spare = reinterpret_cast<u64*>(part[3]);
+  h->lines = reinterpret_cast<u32*>(part[4]);
+  h->rx.tile_counters = reinterpret_cast<u32*>(part[5]);
+  h->rx.status = h->rx.tile_counters + kNumPositions;
+  h->rx.hist_part = reinterpret_cast<u32*>(part[6]);
+  h->rx.plan = reinterpret_cast<SortPlan*>(part[7]);
+  h->rx.keys[0] = reinterpret_cast<u64*>(part[8]);
+  h->rx.keys[1] = reinterpret_cast<u64*>(part[9]);
+  h->rx.vals[0] = reinterpret_cast<u32*>(part[10]);
+  h->rx.vals[1] = reinterpret_cast<u32*>(part[11]);
+  h->rx.cap = cap;
+  h->cap = cap;
+}
+
+void launch_search_lookup(const SearchIndex& ix, const SearchBatch& b, u32 queries,
+                          hipStream_t s) {
+  LOCUST_CHECK_ARG(queries >= 1 && queries <= kSearchMaxQueries,
+                   "search: a batch holds 1 to " + std::to_string(kSearchMaxQueries) +
+                       " queries, not " + std::to_string(queries));
+  LOCUST_HIP_CHECK(hipMemsetAsync(b.zero, 0, b.zero_bytes, s));
+  const u32 blocks = (u32)div_up((u64)queries, (u64)kLookupQueries);
+  search_lookup_kernel<<<dim3(blocks), dim3(kSearchBlock), 0, s>>>(
+      ix.recs, ix.n, ix.val, b.keys, b.q_meta, queries, b.t_val, b.t_len, b.q_info, b.q_bound);
+  LOCUST_HIP_LAUNCH_CHECK();
+  search_scan_kernel<<<dim3(1), dim3(kSearchBlock), 0, s>>>(b.q_bound, queries, b.q_start,
+                                                            &b.ctr->bound);
+  LOCUST_HIP_LAUNCH_CHECK();
+}
+
+void launch_search_hits(const SearchIndex& ix, const SearchBatch& b, u32 queries, u64 bound,
+                        const SearchHits& h, hipStream_t s) {
+  LOCUST_CHECK_ARG(bound < (1ull << 32) && bound <= h.cap,
+                   "search: " + std::to_string(bound) + " list elements exceed the workspace (" +
+                       std::to_string(h.cap) + ")");
+  if (bound) {
+    const u32 blocks =
+        (u32)std::min<u64>(div_up(bound, (u64)kSearchTile), (u64)kSearchMaxBlocks);
+    search_hit_kernel<<<dim3(blocks), dim3(kSearchBlock), 0, s>>>(
+        ix.postings, ix.first_line, b.q_meta, b.q_info, b.q_start, b.t_val, b.t_len, queries,
+        bound, h.pairs, h.cap, b.q_hits, b.ctr);
+    LOCUST_HIP_LAUNCH_CHECK();
+  }
+  search_seal_kernel<<<dim3(1), dim3(1), 0, s>>>(b.ctr, h.cap);
+  LOCUST_HIP_LAUNCH_CHECK();
+}
+
+void launch_search_order(const SearchIndex& ix, const SearchBatch& b, u32 queries, u64 hits,
+                         SearchHits& h, SortPlan* h_plan, hipStream_t s) {
+  LOCUST_CHECK_ARG(hits <= h.cap, "search: " + std::to_string(hits) +
+                                      " hits exceed the workspace (" + std::to_string(h.cap) + ")");
+  search_scan_kernel<<<dim3(1), dim3(kSearchBlock), 0, s>>>(b.q_hits, queries, b.offsets, nullptr);
+  LOCUST_HIP_LAUNCH_CHECK();
+  if (hits == 0) return;
+  ConstKeysSoA keys;
+  KeysSoA sorted;
+  keys.w[0] = h.pairs;
+  sorted.w[0] = h.sorted;
+  for (int j = 1; j < kKeyWords; ++j) {
+    keys.w[j] = h.zeros;
+    sorted.w[j] = h.spare;  // the gather's copies of the zero words
+  }
+  radix_sort(keys, &b.ctr->sort_n, hits, h.rx, nullptr, sorted, nullptr, nullptr, h_plan, s);
+  const u32 eblocks = (u32)std::min<u64>(div_up(hits, 256), 4096);
+  search_emit_kernel<<<dim3(eblocks), dim3(256), 0, s>>>(h.sorted, hits, b.offsets, queries,
+                                                         ix.first_line, h.lines, b.ctr);
+  LOCUST_HIP_LAUNCH_CHECK();
+}
+
+void warm_module_search() {
+  hipFuncAttributes a;
+  (void)hipFuncGetAttributes(&a, reinterpret_cast<const void*>(&search_hit_kernel));
+}
+
+}  // namespace locust

@@ -90,8 +90,12 @@ struct PyTopResult {
 };
 
 // An inverted index: the word job's entries and the CSR postings behind them.
+struct PySearchResult;
 struct PyIndexResult {
   IndexResult x;
+  JobConfig cfg;  // the job's delimiters and max_key_len: what search() validates terms by
+  PySearchResult search(const std::vector<std::vector<std::string>>& queries,
+                        const std::vector<int>& any) const;
   py::list entries() const { return PyResult{x.words}.entries(); }
   py::list postings() const {
     py::list out;
@@ -133,6 +137,69 @@ struct PyIndexResult {
   }
 };
 
+// A search result: per query the ascending global line numbers, and the terms' counts.
+struct PySearchResult {
+  SearchResult r;
+  void check(size_t i) const {
+    if (i >= r.queries.size()) throw py::index_error("query index out of range");
+  }
+  py::list lines(size_t i) const {
+    check(i);
+    py::list out;
+    for (u64 j = r.offsets[i]; j < r.offsets[i + 1]; ++j) out.append(r.lines[j]);
+    return out;
+  }
+  py::list hits() const {
+    py::list out;
+    for (size_t i = 0; i + 1 < r.offsets.size(); ++i) out.append(r.offsets[i + 1] - r.offsets[i]);
+    return out;
+  }
+  py::list term_counts(size_t i) const {
+    check(i);
+    py::list out;
+    for (size_t t = 0; t < r.queries[i].terms.size(); ++t)
+      out.append(r.term_counts[i * kSearchMaxTerms + t]);
+    return out;
+  }
+  py::dict times() const {
+    py::dict d = PyResult{WordCountResult{}}.times();
+    d["h2d_ms"] = r.times.h2d_ms;
+    d["map_ms"] = r.times.map_ms;
+    d["process_ms"] = r.times.process_ms;
+    d["reduce_ms"] = r.times.reduce_ms;
+    d["d2h_ms"] = r.times.d2h_ms;
+    d["wall_ms"] = r.times.wall_ms;
+    d["gpu_ms"] = r.times.gpu_ms;
+    d["index_ms"] = r.index_ms;
+    d["search_ms"] = r.search_ms;
+    return d;
+  }
+  py::bytes format() const {
+    std::string s;
+    format_search_output(r, &s);
+    return py::bytes(s);
+  }
+};
+
+// queries: term lists; any[i] != 0: query i in `any` mode (any.size() == queries.size()).
+std::vector<SearchQuery> to_queries(const std::vector<std::vector<std::string>>& queries,
+                                    const std::vector<int>& any) {
+  LOCUST_CHECK_ARG(any.size() == queries.size(), "search: one mode per query");
+  std::vector<SearchQuery> out(queries.size());
+  for (size_t i = 0; i < queries.size(); ++i) {
+    out[i].terms = queries[i];
+    out[i].mode = any[i] ? SearchMode::kAny : SearchMode::kAll;
+  }
+  return out;
+}
+
+PySearchResult PyIndexResult::search(const std::vector<std::vector<std::string>>& queries,
+                                     const std::vector<int>& any) const {
+  const std::vector<SearchQuery> q = to_queries(queries, any);
+  py::gil_scoped_release nogil;
+  return PySearchResult{search_index(x, q, cfg)};
+}
+
 TextInput as_input(const std::string& text, u64 first_line = 0) {
   TextInput in;
   in.data = text.data();
@@ -163,6 +230,7 @@ class PyGpuEngine {
     d["streaming"] = st.streaming;
     d["chunk_bytes"] = st.chunk_bytes;
     d["map_window"] = st.map_window;
+    d["search_bytes"] = st.search_bytes;
     return d;
   }
   PyGpuEngine(const JobConfig& cfg, u64 max_bytes, u64 max_lines)
@@ -253,11 +321,32 @@ class PyGpuEngine {
   // The word job and the inverted index behind it, on the device.
   PyIndexResult run_index(const std::string& text, u64 first_line) {
     py::gil_scoped_release nogil;
-    return PyIndexResult{eng_.run_index(as_input(text, first_line))};
+    return PyIndexResult{eng_.run_index(as_input(text, first_line)), eng_.config()};
   }
   PyIndexResult run_index_text(const HostText& t, u64 first_line) {
     py::gil_scoped_release nogil;
-    return PyIndexResult{eng_.run_index(t.input(first_line))};
+    return PyIndexResult{eng_.run_index(t.input(first_line)), eng_.config()};
+  }
+  // The word job, the index and a batch of all/any queries answered on the device.
+  PySearchResult run_search(const std::string& text,
+                            const std::vector<std::vector<std::string>>& queries,
+                            const std::vector<int>& any, u64 first_line) {
+    const std::vector<SearchQuery> q = to_queries(queries, any);
+    py::gil_scoped_release nogil;
+    return PySearchResult{eng_.run_search(as_input(text, first_line), q)};
+  }
+  PySearchResult run_search_text(const HostText& t,
+                                 const std::vector<std::vector<std::string>>& queries,
+                                 const std::vector<int>& any, u64 first_line) {
+    const std::vector<SearchQuery> q = to_queries(queries, any);
+    py::gil_scoped_release nogil;
+    return PySearchResult{eng_.run_search(t.input(first_line), q)};
+  }
+  PySearchResult search_resident(const std::vector<std::vector<std::string>>& queries,
+                                 const std::vector<int>& any) {
+    const std::vector<SearchQuery> q = to_queries(queries, any);
+    py::gil_scoped_release nogil;
+    return PySearchResult{eng_.search_resident(q)};
   }
   // records: (key bytes, count), sorted by key with distinct keys -- the kernels alone.
   PyTopResult top_counts(const std::vector<std::pair<std::string, u64>>& records, u32 k) {
@@ -667,6 +756,8 @@ PYBIND11_MODULE(_locust, m) {
       .def("postings", &PyIndexResult::postings)
       .def("postings_bytes", &PyIndexResult::postings_bytes)
       .def("lines", &PyIndexResult::lines, py::arg("key"), py::arg("unique") = false)
+      .def("_search", &PyIndexResult::search, py::arg("queries"), py::arg("any"),
+           "The host evaluation of all/any queries (any[i]: query i's mode) over this index.")
       .def("times", &PyIndexResult::times)
       .def("format", &PyIndexResult::format)
       .def_property_readonly("first_line", [](const PyIndexResult& p) { return p.x.first_line; })
@@ -680,6 +771,27 @@ PYBIND11_MODULE(_locust, m) {
       .def_property_readonly("index_ms", [](const PyIndexResult& p) { return p.x.index_ms; })
       .def_property_readonly("wire_bytes", [](const PyIndexResult& p) { return p.x.wire_bytes; },
                              "bytes the device wrote to host memory for the result");
+  py::class_<PySearchResult>(m, "SearchResult")
+      .def("lines", &PySearchResult::lines, py::arg("i"))
+      .def("hits", &PySearchResult::hits, "the number of lines of every query")
+      .def("term_counts", &PySearchResult::term_counts, py::arg("i"))
+      .def("times", &PySearchResult::times)
+      .def("format", &PySearchResult::format)
+      .def_property_readonly("queries", [](const PySearchResult& p) { return p.r.queries.size(); })
+      .def_property_readonly("first_line", [](const PySearchResult& p) { return p.r.first_line; })
+      .def_property_readonly("num_lines", [](const PySearchResult& p) { return p.r.num_lines; })
+      .def_property_readonly("num_tokens", [](const PySearchResult& p) { return p.r.num_tokens; })
+      .def_property_readonly("num_unique", [](const PySearchResult& p) { return p.r.num_unique; })
+      .def_property_readonly("overflow_lines",
+                             [](const PySearchResult& p) { return p.r.overflow_lines; })
+      .def_property_readonly("truncated", [](const PySearchResult& p) { return p.r.truncated; })
+      .def_property_readonly("max_key_len", [](const PySearchResult& p) { return p.r.max_key_len; })
+      .def_property_readonly("index_ms", [](const PySearchResult& p) { return p.r.index_ms; })
+      .def_property_readonly("search_ms", [](const PySearchResult& p) { return p.r.search_ms; })
+      .def_property_readonly("wire_bytes", [](const PySearchResult& p) { return p.r.wire_bytes; },
+                             "bytes the device wrote to host memory for the result");
+  m.attr("kSearchMaxQueries") = kSearchMaxQueries;
+  m.attr("kSearchMaxTerms") = kSearchMaxTerms;
   m.attr("kTopKMax") = kTopKMax;
   m.attr("kMaxNgram") = kMaxNgram;
   m.attr("kTopKTile") = kTopKTile;
@@ -716,6 +828,13 @@ PYBIND11_MODULE(_locust, m) {
            "WordCount of text and its inverted index (word -> lines), built on the device.")
       .def("run_index_text", &PyGpuEngine::run_index_text, py::arg("text"),
            py::arg("first_line") = 0)
+      .def("run_search", &PyGpuEngine::run_search, py::arg("text"), py::arg("queries"),
+           py::arg("any"), py::arg("first_line") = 0,
+           "WordCount of text, its index, and all/any queries answered on the device.")
+      .def("run_search_text", &PyGpuEngine::run_search_text, py::arg("text"), py::arg("queries"),
+           py::arg("any"), py::arg("first_line") = 0)
+      .def("search_resident", &PyGpuEngine::search_resident, py::arg("queries"), py::arg("any"),
+           "Another batch from the index the last run_index / run_search left on the device.")
       .def("top_counts", &PyGpuEngine::top_counts, py::arg("records"), py::arg("k"),
            "The selection kernels alone over key-sorted (key, count) records.")
       .def_property_readonly("capacity", &PyGpuEngine::capacity);
@@ -730,8 +849,15 @@ PYBIND11_MODULE(_locust, m) {
   }, py::arg("cfg"), py::arg("text"), py::arg("k"));
   m.def("cpu_run_index", [](const JobConfig& cfg, const std::string& text, u64 first_line) {
     CpuWordCount eng(cfg);
-    return PyIndexResult{eng.run_index(as_input(text, first_line))};
+    return PyIndexResult{eng.run_index(as_input(text, first_line)), cfg};
   }, py::arg("cfg"), py::arg("text"), py::arg("first_line") = 0);
+  m.def("cpu_run_search", [](const JobConfig& cfg, const std::string& text,
+                             const std::vector<std::vector<std::string>>& queries,
+                             const std::vector<int>& any, u64 first_line) {
+    CpuWordCount eng(cfg);
+    return PySearchResult{eng.run_search(as_input(text, first_line), to_queries(queries, any))};
+  }, py::arg("cfg"), py::arg("text"), py::arg("queries"), py::arg("any"),
+        py::arg("first_line") = 0);
   m.def("cpu_map_stage", [](const JobConfig& cfg, const std::string& text) {
     CpuWordCount eng(cfg);
     std::vector<py::bytes> out;

@@ -51,6 +51,8 @@ from .models.wordcount import (  # noqa: E402
     map_stage,
     reduce_stage,
     run_multi,
+    search_file,
+    search_text,
     top_words_file,
     top_words_text,
     wordcount_file,
@@ -80,6 +82,8 @@ __all__ = [
     "top_words_text",
     "index_file",
     "index_text",
+    "search_file",
+    "search_text",
     "JobConfig",
     "DistConfig",
     "LocustError",

@@ -133,6 +133,51 @@ def format_index(entries, postings) -> bytes:
         for k, v, c in entries)
 
 
+MAX_SEARCH_TERMS = 8
+
+
+def search(entries, postings, terms, mode: str = "all", delims: bytes = DEFAULT_DELIMS,
+           max_key: int = 29):
+    """One all/any word query over an index: ``(lines, counts)``.
+
+    ``entries`` and ``postings`` are ``index``'s output.  A query is 1 to 8 ``terms`` and a
+    ``mode``.  A term is a non-empty byte string without NUL, newline or a byte of
+    ``delims`` (``ValueError`` otherwise); one longer than ``max_key`` is cut to its first
+    ``max_key`` bytes, as the map cuts keys, so it matches the merged list of every long
+    word with that prefix.  A term's lines are the distinct lines of its postings list; an
+    absent word has none.  ``"all"`` is the intersection of the terms' lines (empty as soon
+    as one term is absent), ``"any"`` their union; a repeated term changes nothing.
+    ``lines`` are global line numbers, ascending, each once; ``counts[t]`` is the count of
+    term ``t``'s word, 0 when it is absent."""
+    if mode not in ("all", "any"):
+        raise ValueError("mode must be 'all' or 'any'")
+    terms = list(terms)
+    if not 1 <= len(terms) <= MAX_SEARCH_TERMS:
+        raise ValueError("a query takes 1 to %d terms" % MAX_SEARCH_TERMS)
+    bad = set(delims) | {0, 0x0A}
+    for t in terms:
+        if not t or any(c in bad for c in t):
+            raise ValueError("invalid term %r" % (t,))
+    by_key = {k: (v, c) for k, v, c in entries}
+    sets, counts = [], []
+    for t in terms:
+        v, c = by_key.get(t[:max_key], (0, 0))
+        counts.append(c)
+        sets.append(set(postings[v:v + c]))
+    hit = set.intersection(*sets) if mode == "all" else set.union(*sets)
+    return sorted(hit), counts
+
+
+def format_search(queries, answers) -> bytes:
+    """The CLI's ``--search`` result lines: one per query, ``queries[i]`` its terms and
+    ``answers[i]`` its lines (every line number after one space; none after "lines:" when
+    the query has no hit)."""
+    return b"".join(
+        b"print query: %s \t hits: %d \t lines:%s\n"
+        % (b" ".join(q), len(a), b"".join(b" %d" % l for l in a))
+        for q, a in zip(queries, answers))
+
+
 def format_gpu(entries) -> bytes:
     """The reference GPU build's result lines (main.cu:132)."""
     return b"".join(b"print key: %s \t val: %d \t count: %d\n" % (k, v, c) for k, v, c in entries)

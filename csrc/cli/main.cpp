@@ -17,8 +17,9 @@
 //   --top K (the K most frequent words instead of the whole dictionary, rank order)
 //   --ngram N (count the word N-grams of each line, N <= 3, instead of its words)
 //   --index (the inverted index: every word with the lines it occurs on)
-//   --search "w1 w2" [--match all|any] (the lines that hold all / any of the words; repeat
-//     --search for a batch: answered from the index on the device, or by --backend cpu)
+//   --search "w1 w2" [--match all|any|phrase] (the lines that hold all / any of the words,
+//     or the words as consecutive tokens in that order; repeat --search for a batch:
+//     answered from the index on the device, or by --backend cpu)
 // and a synthetic-text generator (BASELINE configs "1M lines" / "10 GB"):
 //   MapReduce --gen FILE (--gen-lines N | --gen-bytes N) [--seed S] [--vocab V]
 #include <sys/stat.h>
@@ -87,7 +88,7 @@ struct CliArgs {
   // --search "w1 w2" (repeatable): the result lines are the queries' answers
   std::vector<std::string> search_args;
   std::vector<SearchQuery> queries;
-  std::string match;  // --match all|any ("": all)
+  std::string match;  // --match all|any|phrase ("": all)
   std::string gen_out;  // generator mode
   GenSpec gen;
 };
@@ -130,7 +131,9 @@ void help() {
       "                             like the text; repeat --search for a batch.  Answered from the\n"
       "                             index in device memory, or by --backend cpu.  Restrictions\n"
       "                             as --index, and not with --index)\n"
-      "  --match all|any            (--search: lines with every word (default) or with any)\n"
+      "  --match all|any|phrase     (--search: lines with every word (default), with any, or\n"
+      "                             with the words as consecutive tokens in the order given,\n"
+      "                             whatever delimiters stand between them)\n"
       "  --help\n"
       "\n"
       "Environment: LOCUST_LOG=info|debug and the LOCUST_* switches in docs/ENVIRONMENT.md.\n",
@@ -255,7 +258,8 @@ bool parse(int argc, char** argv, CliArgs* a) {
       a->search_args.push_back(need("--search"));
     } else if (s == "--match") {
       a->match = need("--match");
-      if (a->match != "all" && a->match != "any") throw Error("--match takes all or any (how --search combines its words)");
+      if (a->match != "all" && a->match != "any" && a->match != "phrase")
+        throw Error("--match takes all, any or phrase (how --search combines its words)");
     } else if (s == "--ngram") {
       const std::string v = need("--ngram");
       char* endp = nullptr;
@@ -342,7 +346,9 @@ bool parse(int argc, char** argv, CliArgs* a) {
   // the --search arguments, split with the job's own delimiter set: no term can be invalid
   for (const std::string& arg : a->search_args) {
     SearchQuery q;
-    q.mode = a->match == "any" ? SearchMode::kAny : SearchMode::kAll;
+    q.mode = a->match == "any"      ? SearchMode::kAny
+             : a->match == "phrase" ? SearchMode::kPhrase
+                                    : SearchMode::kAll;
     std::string cur;
     for (const char c : arg) {
       if (a->cfg.delimiters.find(c) != std::string::npos) {

@@ -399,9 +399,47 @@ void check_search_queries(const std::vector<SearchQuery>& queries, const JobConf
   }
 }
 
-SearchResult search_index(const IndexResult& x, const std::vector<SearchQuery>& queries,
-                          const JobConfig& cfg) {
+namespace {
+
+// Do the first emits_per_line tokens of the line hold the keys as consecutive tokens?
+bool line_has_phrase(const char* line, u64 len, const std::vector<PackedKey>& keys,
+                     const JobConfig& cfg, std::vector<PackedKey>* toks) {
+  toks->clear();
+  tokenize_line(line, len, cfg, toks, nullptr);
+  const size_t m = keys.size();
+  for (size_t o = 0; o + m <= toks->size(); ++o) {
+    size_t j = 0;
+    while (j < m && key_compare((*toks)[o + j].w, keys[j].w) == 0) ++j;
+    if (j == m) return true;
+  }
+  return false;
+}
+
+SearchResult search_index_impl(const IndexResult& x, const TextInput* text,
+                               const std::vector<SearchQuery>& queries, const JobConfig& cfg) {
   check_search_queries(queries, cfg);
+  bool verify = false;  // a phrase of two or more terms
+  for (const SearchQuery& q : queries)
+    verify |= q.mode == SearchMode::kPhrase && q.terms.size() >= 2;
+  if (!text)
+    for (const SearchQuery& q : queries)
+      LOCUST_CHECK_ARG(q.mode != SearchMode::kPhrase,
+                       "search: a phrase query needs the text (the index holds no positions): "
+                       "use search_index(index, text, queries, cfg), or run_search on an engine");
+  std::vector<u64> line_at;  // the text's line starts, and its size behind them
+  if (verify) {
+    LOCUST_CHECK_ARG(cfg.ngram == 1, "search: a phrase is verified with word keys (ngram 1)");
+    LOCUST_CHECK_ARG(text->first_line == x.first_line && !text->source,
+                     "search: the text is not the window the index was built from");
+    for (u64 p = 0; p < text->bytes;) {
+      line_at.push_back(p);
+      const void* nl = memchr(text->data + p, '\n', (size_t)(text->bytes - p));
+      p = nl ? (u64)(static_cast<const char*>(nl) - text->data) + 1 : text->bytes;
+    }
+    // (an end without a newline: the last line ends at bytes, not one before it)
+    line_at.push_back(text->bytes && text->data[text->bytes - 1] != '\n' ? text->bytes + 1
+                                                                         : text->bytes);
+  }
   const u64 t0 = now_ns();
   SearchResult r;
   r.queries = queries;
@@ -445,7 +483,11 @@ SearchResult search_index(const IndexResult& x, const std::vector<SearchQuery>& 
       for (const List& o : lists) dup |= o.p == l.p;
       if (!dup) lists.push_back(l);
     }
-    if (q.mode == SearchMode::kAll) {
+    if (q.mode != SearchMode::kAny) {
+      const bool phrase = q.mode == SearchMode::kPhrase && q.terms.size() >= 2;
+      std::vector<PackedKey> keys, toks;
+      if (phrase)
+        for (const std::string& t : q.terms) keys.push_back(search_term_key(t, cfg));
       if (!absent && !lists.empty()) {
         size_t d = 0;
         for (size_t i = 1; i < lists.size(); ++i)
@@ -456,6 +498,13 @@ SearchResult search_index(const IndexResult& x, const std::vector<SearchQuery>& 
           bool hit = true;
           for (size_t i = 0; i < lists.size() && hit; ++i)
             if (i != d) hit = std::binary_search(lists[i].p, lists[i].p + lists[i].len, line);
+          if (hit && phrase) {  // a candidate: the line itself decides
+            const u64 l = line - x.first_line;
+            LOCUST_CHECK_ARG(l + 1 < line_at.size(),
+                             "search: the text has fewer lines than the index names");
+            hit = line_has_phrase(text->data + line_at[l], line_at[l + 1] - 1 - line_at[l], keys,
+                                  cfg, &toks);
+          }
           if (hit) r.lines.push_back(line);
         }
       }
@@ -472,6 +521,18 @@ SearchResult search_index(const IndexResult& x, const std::vector<SearchQuery>& 
   r.times.wall_ms += r.search_ms;
   if (cfg.check) validate_search(r);
   return r;
+}
+
+}  // namespace
+
+SearchResult search_index(const IndexResult& x, const std::vector<SearchQuery>& queries,
+                          const JobConfig& cfg) {
+  return search_index_impl(x, nullptr, queries, cfg);
+}
+
+SearchResult search_index(const IndexResult& x, const TextInput& text,
+                          const std::vector<SearchQuery>& queries, const JobConfig& cfg) {
+  return search_index_impl(x, &text, queries, cfg);
 }
 
 void validate_search(const SearchResult& r) {

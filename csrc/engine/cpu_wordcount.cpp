@@ -137,7 +137,7 @@ IndexResult CpuWordCount::run_index(const TextInput& in) {
 SearchResult CpuWordCount::run_search(const TextInput& in,
                                       const std::vector<SearchQuery>& queries) {
   check_search_queries(queries, cfg_);  // (before the index is built)
-  return search_index(run_index(in), queries, cfg_);
+  return search_index(run_index(in), in, queries, cfg_);
 }
 
 std::vector<PackedKey> CpuWordCount::run_map_stage(const TextInput& in, WordCountResult* stats) {

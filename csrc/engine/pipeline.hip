@@ -1948,11 +1948,20 @@ void DevicePipeline::enqueue_index_job(const TextInput& in, WordCountResult& r,
   // the index stage
   ensure_index(T, n);
   LOCUST_HIP_CHECK(hipEventRecord(ev_index[0], stream));
+  // The text stays resident for phrase queries, and the resident copy must be the engine's
+  // own: a zero-copy job's map read the pinned staging buffer, which the caller may refill
+  // between jobs.  d_text is idle in that mode; the copy (with the 16 zero bytes behind the
+  // text) runs inside the index stage's interval, so the word job's stage timers are as
+  // they were.  Every other upload mode already ended in d_text.  The stage itself then reads
+  // the copy too: three passes over device memory (line index, the map's count and pair
+  // walks) instead of three over the host's.
+  if (upload_mode == Upload::kZeroCopy)
+    LOCUST_HIP_CHECK(hipMemcpyAsync(d_text, h_text, in.bytes + 16, hipMemcpyHostToDevice, stream));
   IndexJob job;
   job.recs = d_out;
   job.n = n;
   job.tokens = T;
-  job.text = map_text;
+  job.text = d_text;
   job.bytes = in.bytes;
   job.num_lines = in.num_lines;
   job.first_line = in.first_line;
@@ -1998,6 +2007,14 @@ void DevicePipeline::keep_index(const TextInput& in, const WordCountResult& r, u
   idx_view.postings = index.postings;
   idx_view.n = (u32)n;
   idx_view.first_line = (u32)in.first_line;
+  // the text view of the phrase kernel: the device copy, never the staging buffer
+  idx_view.text = d_text;
+  idx_view.bytes = in.bytes;
+  idx_view.nl_pos = index.nl_pos;
+  idx_view.lctr = index.lctr;
+  idx_view.dm = make_delim_mask(cfg.delimiters.c_str());
+  idx_view.emits_per_line = cfg.emits_per_line;
+  idx_view.max_key_len = cfg.max_key_len;
   idx_num_lines = in.num_lines;
   idx_tokens = T;
   idx_resident = true;
@@ -2112,10 +2129,14 @@ void DevicePipeline::search_stage(const std::vector<SearchQuery>& queries, Searc
   // the batch: q_meta | the terms' keys, packed exactly as the map packs them
   u32* meta = reinterpret_cast<u32*>(h_supload);
   u64* keys = reinterpret_cast<u64*>(h_supload + (u64)kSearchMaxQueries * sizeof(u32));
+  bool verify = false;  // the batch has a phrase of two or more terms: the phrase kernel runs
   std::memset(keys, 0, (size_t)Q * kSearchMaxTerms * sizeof(PackedKey));
   for (u32 q = 0; q < Q; ++q) {
     const SearchQuery& sq = queries[q];
-    meta[q] = (u32)sq.terms.size() | (sq.mode == SearchMode::kAny ? kSearchAny : 0u);
+    meta[q] = (u32)sq.terms.size() | (sq.mode == SearchMode::kAny      ? kSearchAny
+                                      : sq.mode == SearchMode::kPhrase ? kSearchPhrase
+                                                                       : 0u);
+    verify |= sq.mode == SearchMode::kPhrase && sq.terms.size() >= 2;
     for (size_t t = 0; t < sq.terms.size(); ++t) {
       const PackedKey k = search_term_key(sq.terms[t], cfg);
       std::memcpy(keys + ((u64)q * kSearchMaxTerms + t) * kKeyWords, k.w, sizeof(PackedKey));
@@ -2139,14 +2160,18 @@ void DevicePipeline::search_stage(const std::vector<SearchQuery>& queries, Searc
                 " list elements, which does not fit the 32-bit slot counter (2^32): split "
                 "the batch");
   ensure_search_hits(B);
-  // hits
-  launch_search_hits(idx_view, sbatch, Q, B, shits, stream);
+  // hits; a phrase's candidates are verified against the resident text behind them
+  launch_search_hits(idx_view, sbatch, Q, B, verify, shits, stream);
   LOCUST_HIP_CHECK(hipMemcpyAsync(h_sc, sbatch.ctr, sizeof(SearchCounters), hipMemcpyDeviceToHost,
                                   stream));
   sync();
-  const u64 H = h_sc->written;
+  const u64 H = h_sc->written, C = h_sc->cands;
   if (H > B || h_sc->sort_n != H)
     throw Error("search: " + std::to_string(H) + " hits written, the lists hold " +
+                std::to_string(B) + " elements");
+  if (C > B || h_sc->verified != C || (C && !verify))
+    throw Error("search: " + std::to_string(C) + " phrase candidates, " +
+                std::to_string(h_sc->verified) + " of them verified, the lists hold " +
                 std::to_string(B) + " elements");
   if (h_slines_cap < H) {
     pinned_free(h_slines);

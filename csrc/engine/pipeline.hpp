@@ -766,7 +766,8 @@ struct DevicePipeline {
   // own buffers), its pinned postings buffer and its events exist from the first index
   // job on (ensure_index: checked against free HBM); a word job allocates nothing for it.
   // d_out is the junction, as for a top job: the word job leaves its num_unique records
-  // there in key order, the stage reads them and `map_text` in place.
+  // there in key order, the stage reads them in place, and the text in `d_text` (a
+  // zero-copy job copies it there first: enqueue_index_job).
   IndexWorkspace index{};
   char* d_index = nullptr;
   u64 index_bytes = 0;
@@ -786,10 +787,14 @@ struct DevicePipeline {
   void check_index_counters(u64 n, u64 T) const;
 
   // ---- index search (kernels/search.hip) ----
-  // The index the last run_index / run_search left on the device: d_out's records and the
-  // index workspace's val and postings.  Every other job entry point of GpuWordCount
-  // clears idx_resident (their kernels reuse d_out and the text), and so does an index or
-  // search job until it has completed.  The search stage's batch arrays, hit workspace
+  // The index the last run_index / run_search left on the device: d_out's records, the
+  // index workspace's val, postings and line starts (nl_pos, lctr), and the text in d_text,
+  // which phrase queries are verified against.  d_text is the engine's own copy in every
+  // upload mode (a zero-copy job copies the staging buffer there inside the index stage),
+  // so refilling the staging buffer between jobs does not touch it.  Every other job entry
+  // point of GpuWordCount clears idx_resident (their kernels reuse d_out, d_text and the
+  // index workspace), and so does an index or search job until it has completed: no job
+  // that overwrites any of them leaves the flag set.  The search stage's batch arrays, hit workspace
   // (grown by the batch's bound; checked against free HBM), pinned buffers and events are
   // separate allocations made by the first search job: a word, top or index job allocates
   // nothing for search, and nothing of it overlaps the index.

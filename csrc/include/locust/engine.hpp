@@ -339,7 +339,7 @@ void validate_index(const IndexResult& r);
 //   "print key: <key> \t count: <count> \t lines: <l0> <l1> ...\n"
 void format_index_output(const IndexResult& r, std::string* out);
 
-// ---- index search: all/any word queries over the inverted index ----
+// ---- index search: all/any/phrase word queries over the inverted index ----
 // A query is 1 to kSearchMaxTerms terms and a mode.  A term is a non-empty byte string
 // without NUL, newline or a byte of the job's delimiter set; one longer than max_key_len is
 // cut to its first max_key_len bytes, as the map cuts keys, and so matches the merged list
@@ -349,13 +349,28 @@ void format_index_output(const IndexResult& r, std::string* out);
 // inside a query changes nothing.  The answer is global line numbers, ascending, each once:
 // a pure function of the index.  Each term also reports its word's count (0: absent).
 //
+// `phrase` answers the lines on which the terms occur as consecutive tokens, in order.
+// A line's token sequence is exactly what the word job emits for it, in order: the job's
+// delimiter set, a NUL ends the line's tokens, only the first emits_per_line tokens, each
+// token cut to max_key_len bytes.  A line with tokens k_0 .. k_(n-1) matches the terms
+// t_0 .. t_(m-1), each cut to max_key_len bytes, when some o exists with k_(o+j) == t_j
+// for every j in [0, m).  Tokens past the emit cap do not exist for this purpose, a phrase
+// never crosses a line end, and what stood between two consecutive tokens does not matter:
+// any run of delimiters, of any length, counts.  Repeated terms are significant here:
+// [bye, bye] matches only a line with two consecutive bye tokens.  A one-term phrase
+// answers as `all` does, an absent term gives an empty answer, and long tokens that merge
+// under truncation match as their merged key, the rule the index uses.  The answer and the
+// per-term counts have the shape of the other modes'; repeated terms report the same count.
+//
 // The device stage (kernels/search.hip; GpuWordCount::run_search / search_resident)
 // answers batches of up to kSearchMaxQueries queries from the index in device memory:
-// neither postings nor records cross PCIe.  The host evaluation (search_index) takes any
-// number of queries.
+// neither postings nor records cross PCIe.  A phrase takes its candidate lines from the
+// `all` evaluation and verifies each against the text, which the engine keeps in device
+// memory beside the index.  The host evaluation (search_index) takes any number of
+// queries; for a phrase it needs the text too (the four-argument overload).
 constexpr u32 kSearchMaxQueries = 1024;
 constexpr u32 kSearchMaxTerms = 8;
-enum class SearchMode { kAll, kAny };
+enum class SearchMode { kAll, kAny, kPhrase };
 struct SearchQuery {
   std::vector<std::string> terms;
   SearchMode mode = SearchMode::kAll;
@@ -384,9 +399,15 @@ PackedKey search_term_key(const std::string& term, const JobConfig& cfg);
 // Throws unless every query has 1..kSearchMaxTerms valid terms for cfg's delimiter set.
 void check_search_queries(const std::vector<SearchQuery>& queries, const JobConfig& cfg);
 // The host evaluation over an index result, any number of queries (cfg: the index job's
-// delimiters and max_key_len).
+// delimiters and max_key_len).  Throws for a phrase query: the index holds no positions, so
+// a phrase needs the text -- the four-argument overload.
 SearchResult search_index(const IndexResult& x, const std::vector<SearchQuery>& queries,
                           const JobConfig& cfg);
+// The same with the text the index was built from (the same window: text.first_line ==
+// x.first_line; cfg also gives emits_per_line): a phrase's candidates come from the `all`
+// evaluation and are verified by tokenising their lines with the CPU engine's tokeniser.
+SearchResult search_index(const IndexResult& x, const TextInput& text,
+                          const std::vector<SearchQuery>& queries, const JobConfig& cfg);
 // LOCUST_CHECK invariants of a search result: offsets monotone from 0 to lines.size(), every
 // query's lines strictly ascending and inside [first_line, first_line + num_lines).
 void validate_search(const SearchResult& r);
@@ -524,7 +545,9 @@ class GpuWordCount {
 
   // run_index's word job and index stage, then the search stage over the index in device
   // memory (kernels/search.hip): up to kSearchMaxQueries queries; only the answers, the
-  // per-term counts and the counters cross PCIe.  run_index's refusals apply.
+  // per-term counts and the counters cross PCIe.  run_index's refusals apply.  The text
+  // stays in device memory beside the index (the engine's own copy, not the staging
+  // buffer): phrase queries are verified against it.
   SearchResult run_search(const TextInput& in, const std::vector<SearchQuery>& queries);
   // Another batch from the index this engine's last job left on the device.  That job must
   // have been a run_index or a run_search: any other job (a refused one that had started
@@ -576,7 +599,8 @@ class CpuWordCount {
   // The inverted index on the host, any size: (key, line) pairs, one stable sort by key.
   // Word keys only (ngram == 1), like the GPU job.
   IndexResult run_index(const TextInput& in);
-  // run_index() + the host evaluation (search_index), any size and any number of queries.
+  // run_index() + the host evaluation (search_index with the text), any size, any number
+  // of queries and every mode.
   SearchResult run_search(const TextInput& in, const std::vector<SearchQuery>& queries);
   std::vector<PackedKey> run_map_stage(const TextInput& in, WordCountResult* stats);
   WordCountResult run_reduce_stage(const PackedKey* keys, u64 n);

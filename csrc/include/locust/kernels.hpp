@@ -620,16 +620,18 @@ struct IndexJob {
 void launch_index(const IndexJob& job, IndexWorkspace& ws, SortPlan* h_plan, hipStream_t s);
 
 // ---------------- search.hip ----------------
-// All/any word queries over the inverted index launch_index left on the device (engine.hpp
-// "index search"): the key-ordered records, the CSR offsets `val` and the sorted postings.
-// A batch holds Q <= kSearchMaxQueries queries of <= kSearchMaxTerms terms each.
+// All/any/phrase word queries over the inverted index launch_index left on the device
+// (engine.hpp "index search"): the key-ordered records, the CSR offsets `val` and the sorted
+// postings; a phrase is verified against the text the index was built from, which is
+// resident too.  A batch holds Q <= kSearchMaxQueries queries of <= kSearchMaxTerms terms.
 //
 // A sequence of kernels on `s`; data moves between workgroups only across the kernel
 // boundaries (the radix sort it reuses keeps its own look-back), no polled word:
 //   lookup   one thread per (query, term): find_rank of the packed key, the term's val and
 //            length; per query the distinct terms, the driver (the shortest list, `all`), the
 //            dead flag (`all` with an absent term) and the bound on its hits = the elements
-//            it walks: the driver's length (`all`) or the distinct terms' lengths (`any`)
+//            it walks: the driver's length (`all`) or the distinct terms' lengths (`any`).
+//            A phrase is looked up as `all`: its bound covers its candidates and its hits
 //   scan     one workgroup: q_start[0 .. Q] = exclusive scan of the bounds, the total B
 //   (the host reads B and the term counts, and sizes the hit workspace)
 //   hits     a grid walks the flattened (query, list element) space in tiles of kSearchTile.
@@ -637,7 +639,19 @@ void launch_index(const IndexJob& job, IndexWorkspace& ws, SortPlan* h_plan, hip
 //            binary search finds the line in every other distinct term's list; `any`: when
 //            none of the earlier distinct terms' lists holds it.  A hit is the pair word
 //            query << 32 | (line - first_line); its slot comes from one atomic per wave and
-//            step, the per-query hit counts from one atomic per wave, step and query
+//            step, the per-query hit counts from one atomic per wave, step and query.  An
+//            element of a phrase of two or more terms that passes the `all` test is a
+//            candidate: the same pair word goes to `cands`, its slot from one atomic per wave
+//            and step on the candidate counter, and q_hits is left alone
+//   phrase   (only when the batch has a phrase of two or more terms) one wave per candidate,
+//            up to 64 consecutive candidates per wave and round.  The wave re-tokenises the
+//            candidate's line with the word job's rules (device/linetok.hpp, as index.hip's
+//            map), compares every emitted token's key with the query's packed term keys
+//            (bit j of a token's mask: it equals term j) and runs the shift-and automaton
+//            state = ((state << 1) | 1) & mask over the tokens in order; bit nterms - 1 set
+//            is a hit.  After a round lane i holds candidate i's verdict and the hits are
+//            written as the hit kernel writes them: one atomic per wave and round for the
+//            slots, one per distinct query for q_hits; one more counts the verified candidates
 //   seal     one thread: the sort's length, capped by the workspace
 //   (the host reads the number of hits H: the sort takes its regime from it)
 //   order    radix_sort() of the pair words as one-word keys
@@ -649,13 +663,17 @@ struct SearchCounters {  // zeroed per batch
   u32 written;    // hits the hit kernel found
   u32 sort_n;     // pairs handed to the sort: `written` if the workspace holds them, else 0
   u32 misplaced;  // sorted pairs outside their query's range
+  u32 cands;      // phrase candidates the hit kernel wrote
+  u32 verified;   // phrase candidates the phrase kernel has decided
   u32 pad;
 };
+static_assert(sizeof(SearchCounters) <= 64, "the counters share one 64-byte block");
 constexpr int kSearchBlock = 256;
 constexpr int kSearchItems = 4;
 constexpr int kSearchTile = kSearchBlock * kSearchItems;  // elements per workgroup and step
 constexpr int kSearchMaxBlocks = 2048;                     // the hit kernel's grid cap
-constexpr u32 kSearchAny = 1u << 8;                        // q_meta: nterms | kSearchAny
+constexpr u32 kSearchAny = 1u << 8;                        // q_meta: nterms | mode bit
+constexpr u32 kSearchPhrase = 1u << 9;                     // (neither bit: `all`)
 // The index a batch is answered from (all device memory, launch_index's output).
 struct SearchIndex {
   const OutRecord* recs = nullptr;  // [n] key order
@@ -663,6 +681,14 @@ struct SearchIndex {
   const u32* postings = nullptr;    // [val[n]] global line numbers
   u32 n = 0;
   u32 first_line = 0;
+  // what the phrase kernel reads: the text the index was built from (the engine's own
+  // device copy), its line starts as launch_index left them, and the job's token rules
+  const char* text = nullptr;
+  u64 bytes = 0;
+  const u64* nl_pos = nullptr;         // [num_newlines] IndexWorkspace::nl_pos
+  const MapCounters* lctr = nullptr;   // num_newlines
+  DelimMask dm{};
+  int emits_per_line = 0, max_key_len = 0;
 };
 // The per-batch arrays: fixed size (kSearchMaxQueries), made by the first search job.
 struct SearchBatch {
@@ -683,6 +709,7 @@ struct SearchBatch {
 // The hit arrays, sized by the batch's bound B (grown on demand).
 struct SearchHits {
   u64* pairs = nullptr;   // [cap] query << 32 | line, in arbitrary order
+  u64* cands = nullptr;   // [cap] phrase candidates: the same pair words, not yet verified
   u64* zeros = nullptr;   // [cap] zero: key words 1..3 of the sort
   u64* sorted = nullptr;  // [cap]
   u64* spare = nullptr;   // [cap]
@@ -698,9 +725,10 @@ u64 search_hits_bytes(u64 cap);
 void search_hits_carve(char* base, u64 cap, SearchHits* h);
 // lookup + scan: b.ctr->bound, b.t_len and b.q_start are complete when `s` has drained.
 void launch_search_lookup(const SearchIndex& ix, const SearchBatch& b, u32 queries, hipStream_t s);
-// hits + seal over the `bound` elements the lookup reported (bound <= h.cap).
+// hits (+ phrase, when `verify`: the batch has a phrase of two or more terms) + seal over
+// the `bound` elements the lookup reported (bound <= h.cap).
 void launch_search_hits(const SearchIndex& ix, const SearchBatch& b, u32 queries, u64 bound,
-                        const SearchHits& h, hipStream_t s);
+                        bool verify, const SearchHits& h, hipStream_t s);
 // order + offsets + emit of the `hits` pairs the hit kernel wrote (b.ctr->sort_n == hits):
 // b.offsets[0 .. Q], h.lines[0 .. hits) and b.ctr->misplaced.  More than kSmallSortMax hits
 // read the sort's plan back through h_plan and synchronise `s` once, as radix_sort does.

@@ -28,6 +28,7 @@
 // radix sort keep their own look-back); this file adds no polled word.
 #include <algorithm>
 
+#include "locust/device/linetok.hpp"
 #include "locust/device/rank.hpp"
 #include "locust/device/wave.hpp"
 #include "locust/dstring.hpp"
@@ -40,8 +41,7 @@ namespace {
 constexpr int kIdxMapBlock = 256;
 constexpr int kIdxMapWaves = kIdxMapBlock / 64;
 constexpr int kIdxMapMaxBlocks = 2048;  // 8 workgroups per CU
-constexpr int kIdxRow = 64 + 32;  // a step's bytes + the 32 behind them (keys <= 31 bytes)
-static_assert(kKeyBytes <= 32, "a key that starts in lane 63 ends inside the staged row");
+constexpr int kIdxRow = dev::kLineRow;  // a step's bytes + the 32 behind them
 
 // tile_val[tile] = the tile's count sum.
 __global__ __launch_bounds__(kIndexBlock) void index_tile_sum_kernel(
@@ -107,21 +107,6 @@ __global__ __launch_bounds__(kIndexBlock) void index_val_kernel(
   }
 }
 
-// The token starts of one 64-byte step of a line (c: this lane's byte, 0 past the line end;
-// carry: the previous step's last byte belonged to a token).  *last: a NUL, or the line
-// end, lies inside the step.
-__device__ __forceinline__ u64 step_starts(unsigned c, const DelimMask& dm, u64* carry,
-                                           bool* last) {
-  // bytes past the line end were loaded as 0: they end the tokens like a NUL
-  const u64 z = dev::ballot(c == 0u);
-  u64 m = dev::ballot(c != 0u && !mask_is_delim(dm, c));
-  if (z) m &= (z & (~z + 1)) - 1;  // nothing at or behind the first NUL (or the end)
-  const u64 starts = m & ~((m << 1) | *carry);
-  *carry = m >> 63;
-  *last = z != 0;
-  return starts;
-}
-
 // One wave per line; a wave takes `group` consecutive lines at a time, grid-stride over the
 // groups.  It first counts the group's emitted tokens (ballots only), reserves their slots
 // with ONE atomic -- every wave of the grid adds to the same word, and such atomics
@@ -157,7 +142,7 @@ __global__ __launch_bounds__(kIdxMapBlock) void index_map_kernel(
         const u64 p = pos + lane;
         const unsigned c = p < end ? (unsigned char)text[p] : 0u;
         bool last;
-        seen += (u32)__popcll(step_starts(c, dm, &carry, &last));
+        seen += (u32)__popcll(dev::step_starts(c, dm, &carry, &last));
         if (last) break;
       }
       total += seen < E ? seen : E;
@@ -182,23 +167,14 @@ __global__ __launch_bounds__(kIdxMapBlock) void index_map_kernel(
         if (lane < 32) row[64 + lane] = (unsigned char)c2;
         __builtin_amdgcn_wave_barrier();
         bool last;
-        const u64 starts = step_starts(c, dm, &carry, &last);
+        const u64 starts = dev::step_starts(c, dm, &carry, &last);
         const u32 ord = seen + (u32)__popcll(starts & below);
         const bool emit = ((starts >> lane) & 1ull) && ord < E;
         const u64 em = dev::ballot(emit);
         bool found = false;
         if (emit) {
-          u64 w0 = 0, w1 = 0, w2 = 0, w3 = 0;
-          for (int len = 0; len < max_key_len; ++len) {
-            const unsigned ch = row[lane + len];
-            if (ch == 0u || mask_is_delim(dm, ch)) break;
-            const u64 v = (u64)ch << (56 - 8 * (len & 7));
-            const int wi = len >> 3;
-            w0 |= wi == 0 ? v : 0ull;
-            w1 |= wi == 1 ? v : 0ull;
-            w2 |= wi == 2 ? v : 0ull;
-            w3 |= wi == 3 ? v : 0ull;
-          }
+          u64 w0, w1, w2, w3;
+          dev::pack_row_key(row, lane, dm, max_key_len, &w0, &w1, &w2, &w3);
           const u32 rank = dev::find_rank(recs, n, w0, w1, w2, w3);
           found = rank < n;
           const u64 slot = (u64)at + (u32)__popcll(em & below);

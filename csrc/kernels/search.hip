@@ -1,5 +1,5 @@
-// Index search: all/any word queries over the inverted index in device memory (kernels.hpp
-// "search.hip"; the semantics are engine.hpp "index search").
+// Index search: all/any/phrase word queries over the inverted index in device memory
+// (kernels.hpp "search.hip"; the semantics are engine.hpp "index search").
 //
 // launch_index has left the key-ordered records, the CSR offsets val[0 .. n] and the sorted
 // postings in device memory.  A query's answer needs rank lookups and searches in sorted
@@ -18,13 +18,21 @@
 //    stride.  A thread finds its element's query by a binary search in q_start, then the
 //    term and position, and decides the hit by binary searches confined to the other
 //    terms' CSR ranges.  Every step ends in wave-level ballots: one atomic reserves the
-//    step's slots, one atomic per distinct query of the wave adds to its hit count;
+//    step's slots, one atomic per distinct query of the wave adds to its hit count
+//    (commit_hits).  A phrase of two or more terms is looked up and walked as `all`, but
+//    what passes is a candidate: its pair word goes to `cands`;
+//  * search_phrase_kernel: one wave per candidate line, up to 64 consecutive candidates per
+//    wave and round.  The wave walks the line 64 bytes per step with index.hip's tokeniser
+//    (device/linetok.hpp), compares each emitted token's key with the query's term keys
+//    (staged in LDS) and runs a shift-and automaton over the tokens.  Lane i keeps candidate
+//    i's verdict, and the round ends in commit_hits;
 //  * order: the device-wide radix_sort() on the one-word key, as launch_index uses it;
 //  * search_emit_kernel: lines[j] = first_line + low32(sorted[j]) and the misplaced check.
 // Data crosses between workgroups only at kernel boundaries (the radix sort keeps its own
 // look-back); this file adds no polled word.
 #include <algorithm>
 
+#include "locust/device/linetok.hpp"
 #include "locust/device/rank.hpp"
 #include "locust/device/wave.hpp"
 #include "locust/hip_check.hpp"
@@ -37,6 +45,9 @@ constexpr int kTerms = (int)kSearchMaxTerms;
 constexpr int kLookupQueries = kSearchBlock / kTerms;  // queries per lookup workgroup
 static_assert(kTerms == 8 && kSearchBlock % kTerms == 0, "eight term threads per query");
 static_assert(kSearchMaxQueries % kSearchBlock == 0, "the scan walks whole blocks");
+constexpr int kPhraseBlock = 256;
+constexpr int kPhraseWaves = kPhraseBlock / 64;
+constexpr int kPhraseMaxBlocks = 2048;  // 8 workgroups per CU
 
 __global__ __launch_bounds__(kSearchBlock) void search_lookup_kernel(
     const OutRecord* __restrict__ recs, u32 n, const u64* __restrict__ val,
@@ -66,7 +77,7 @@ __global__ __launch_bounds__(kSearchBlock) void search_lookup_kernel(
   s_len[threadIdx.x] = len;
   __syncthreads();
   if (q < Q && t == 0) {
-    const bool any = (meta & kSearchAny) != 0;
+    const bool any = (meta & kSearchAny) != 0;  // (a phrase is looked up as `all`)
     const u32* rk = s_rank + threadIdx.x;
     const u32* ln = s_len + threadIdx.x;
     u32 mask = 0, dead = 0, driver = 0, best = ~0u;
@@ -126,18 +137,47 @@ __device__ __forceinline__ bool list_has(const u32* __restrict__ p, u32 len, u32
   return lo < len && p[lo] == line;
 }
 
+// The hits of one converged wave step (hit: this lane has one, of query q on local line
+// rel_line): one atomic reserves the step's slots in `pairs`, one atomic per distinct query
+// of the wave adds to its hit count.
+__device__ __forceinline__ void commit_hits(bool hit, u32 q, u32 rel_line, u64* __restrict__ pairs,
+                                            u64 pair_cap, u32* __restrict__ q_hits,
+                                            SearchCounters* __restrict__ ctr) {
+  const int lane = dev::lane_id();
+  const u64 hm = dev::ballot(hit);
+  if (hm == 0) return;  // (wave-uniform)
+  const int first = __ffsll((unsigned long long)hm) - 1;
+  u32 at = 0;
+  if (lane == first) at = atomicAdd(&ctr->written, (u32)__popcll(hm));
+  at = (u32)__shfl((int)at, first, 64);
+  if (hit) {
+    const u64 slot = (u64)at + dev::lanes_below(hm);
+    if (slot < pair_cap) pairs[slot] = ((u64)q << 32) | (u64)rel_line;
+  }
+  // per query: one atomic for all of the wave's hits of that query
+  u64 rem = hm;
+  while (rem) {  // (wave-uniform)
+    const int leader = __ffsll((unsigned long long)rem) - 1;
+    const u32 ql = (u32)__shfl((int)q, leader, 64);
+    const u64 same = dev::ballot(hit && q == ql);
+    if (lane == leader) atomicAdd(&q_hits[ql], (u32)__popcll(same));
+    rem &= ~same;
+  }
+}
+
 __global__ __launch_bounds__(kSearchBlock) void search_hit_kernel(
     const u32* __restrict__ postings, u32 first_line, const u32* __restrict__ q_meta,
     const u32* __restrict__ q_info, const u64* __restrict__ q_start, const u64* __restrict__ t_val,
-    const u32* __restrict__ t_len, u32 Q, u64 B, u64* __restrict__ pairs, u64 pair_cap,
-    u32* __restrict__ q_hits, SearchCounters* __restrict__ ctr) {
+    const u32* __restrict__ t_len, u32 Q, u64 B, u64* __restrict__ pairs,
+    u64* __restrict__ cands, u64 pair_cap, u32* __restrict__ q_hits,
+    SearchCounters* __restrict__ ctr) {
   const int lane = dev::lane_id();
   for (u64 tile = blockIdx.x; tile * kSearchTile < B; tile += gridDim.x) {  // (uniform)
 #pragma unroll 1
     for (int j = 0; j < kSearchItems; ++j) {
       const u64 e = tile * kSearchTile + (u64)j * kSearchBlock + threadIdx.x;
-      bool hit = false;
-      u32 q = 0, line = 0;
+      bool hit = false, cand = false;
+      u32 q = 0, line = first_line;
       if (e < B) {
         // the query: q_start[q] <= e < q_start[q + 1] (q_start[0] = 0, q_start[Q] = B)
         u32 lo = 0, hi = Q;
@@ -151,7 +191,10 @@ __global__ __launch_bounds__(kSearchBlock) void search_hit_kernel(
         q = lo;
         u32 local = (u32)(e - q_start[q]);
         const u32 info = q_info[q];
-        const bool any = (q_meta[q] & kSearchAny) != 0;
+        const u32 meta = q_meta[q];
+        const bool any = (meta & kSearchAny) != 0;
+        // a phrase of two or more terms: what passes the `all` test is only a candidate
+        const bool verify = (meta & kSearchPhrase) != 0 && (meta & 0xffu) >= 2u;
         const u32 mask = (info >> 16) & 0xffu;
         const u64* tv = t_val + (u64)q * kTerms;
         const u32* tl = t_len + (u64)q * kTerms;
@@ -178,30 +221,121 @@ __global__ __launch_bounds__(kSearchBlock) void search_hit_kernel(
               for (u32 t = 0; t < (u32)kTerms && hit; ++t)
                 if (((mask >> t) & 1u) && t != term) hit = list_has(postings + tv[t], tl[t], line);
             }
+            cand = hit && verify;
+            hit = hit && !verify;
           }
         }
       }
-      // ---- the step's hits: the wave is converged here ----
-      const u64 hm = dev::ballot(hit);
-      if (hm == 0) continue;  // (wave-uniform)
-      const int first = __ffsll((unsigned long long)hm) - 1;
-      u32 at = 0;
-      if (lane == first) at = atomicAdd(&ctr->written, (u32)__popcll(hm));
-      at = (u32)__shfl((int)at, first, 64);
-      if (hit) {
-        const u64 slot = (u64)at + dev::lanes_below(hm);
-        if (slot < pair_cap) pairs[slot] = ((u64)q << 32) | (u64)(line - first_line);
+      // ---- the step's candidates and hits: the wave is converged here ----
+      const u64 cm = dev::ballot(cand);
+      if (cm) {  // (wave-uniform)
+        const int first = __ffsll((unsigned long long)cm) - 1;
+        u32 at = 0;
+        if (lane == first) at = atomicAdd(&ctr->cands, (u32)__popcll(cm));
+        at = (u32)__shfl((int)at, first, 64);
+        if (cand) {
+          const u64 slot = (u64)at + dev::lanes_below(cm);
+          if (slot < pair_cap) cands[slot] = ((u64)q << 32) | (u64)(line - first_line);
+        }
       }
-      // per query: one atomic for all of the wave's hits of that query
-      u64 rem = hm;
-      while (rem) {  // (wave-uniform)
-        const int leader = __ffsll((unsigned long long)rem) - 1;
-        const u32 ql = (u32)__shfl((int)q, leader, 64);
-        const u64 same = dev::ballot(hit && q == ql);
-        if (lane == leader) atomicAdd(&q_hits[ql], (u32)__popcll(same));
-        rem &= ~same;
-      }
+      commit_hits(hit, q, line - first_line, pairs, pair_cap, q_hits, ctr);
     }
+  }
+}
+
+// One wave per candidate; a wave takes `group` (<= 64) consecutive candidates per round,
+// grid-stride over the rounds.  The candidates' number comes from device memory (the hit
+// kernel's counter): no host round trip between the two kernels.  Lane i keeps candidate
+// i's verdict, so a round ends like a step of the hit kernel: ONE atomic for its slots and
+// one per distinct query -- one atomic per verified line would serialise on ctr->written as
+// index_map_kernel's comment (index.hip) records for 10^6 lines.
+__global__ __launch_bounds__(kPhraseBlock) void search_phrase_kernel(
+    const char* __restrict__ text, u64 bytes, const u64* __restrict__ nl_pos,
+    const MapCounters* __restrict__ lctr, DelimMask dm, int emits_per_line, int max_key_len,
+    u32 group, const u32* __restrict__ q_meta, const u64* __restrict__ keys, u32 Q,
+    const u64* __restrict__ cands, u64* __restrict__ pairs, u64 pair_cap,
+    u32* __restrict__ q_hits, SearchCounters* __restrict__ ctr) {
+  __shared__ unsigned char s_row[kPhraseWaves][dev::kLineRow];
+  __shared__ u64 s_keys[kPhraseWaves][kTerms * kKeyWords];
+  const int lane = dev::lane_id();
+  unsigned char* row = s_row[dev::wave_id()];
+  u64* qk = s_keys[dev::wave_id()];
+  const u64 num_nl = lctr->num_newlines;
+  const u64 num_lines = bytes ? num_nl + 1 : 0;
+  const u64 C = ctr->cands <= pair_cap ? ctr->cands : 0;  // (an overflow: the host throws)
+  const u64 wave = (u64)blockIdx.x * kPhraseWaves + dev::wave_id();
+  const u64 nwaves = (u64)gridDim.x * kPhraseWaves;
+  const u64 below = lane ? (~0ull >> (64 - lane)) : 0ull;  // the lanes below this one
+  const u32 E = (u32)emits_per_line;
+  for (u64 g0 = wave * group; g0 < C; g0 += nwaves * group) {  // (wave-uniform)
+    const u32 cnt = (u32)(g0 + group < C ? group : C - g0);
+    const u64 mine = (u32)lane < cnt ? cands[g0 + lane] : 0ull;  // lane i: candidate i
+    bool hit = false;
+    u32 q_loaded = ~0u;  // the query whose term keys the wave's LDS row holds
+    for (u32 i = 0; i < cnt; ++i) {
+      const u32 q = (u32)__shfl((int)(u32)(mine >> 32), (int)i, 64);
+      const u64 line = (u32)__shfl((int)(u32)mine, (int)i, 64);
+      if (q >= Q || line >= num_lines) continue;  // (wave-uniform; never: the hit kernel's words)
+      const u32 m = q_meta[q] & 0xffu;
+      if (m == 0 || m > (u32)kTerms) continue;    // (never: the host checked the batch)
+      if (q != q_loaded) {  // (wave-uniform) neighbours mostly share their query
+        __builtin_amdgcn_wave_barrier();  // the previous candidate's key reads are done
+        if (lane < kTerms * kKeyWords) qk[lane] = keys[(u64)q * kTerms * kKeyWords + lane];
+        __builtin_amdgcn_wave_barrier();
+        q_loaded = q;
+      }
+      const u64 start = line ? nl_pos[line - 1] + 1 : 0;
+      const u64 end = line < num_nl ? nl_pos[line] : bytes;
+      const u32 accept = 1u << (m - 1);
+      u32 seen = 0;   // token starts of this line before the current step
+      u32 state = 0;  // bit j: the last j + 1 tokens equal terms 0 .. j
+      u64 carry = 0;
+      bool match = false;
+      for (u64 pos = start; pos < end && seen < E && !match; pos += 64) {
+        const u64 p = pos + lane;
+        const unsigned c = p < end ? (unsigned char)text[p] : 0u;
+        const u64 p2 = pos + 64 + lane;
+        const unsigned c2 = (lane < 32 && p2 < end) ? (unsigned char)text[p2] : 0u;
+        __builtin_amdgcn_wave_barrier();  // the previous step's key reads are done
+        row[lane] = (unsigned char)c;
+        if (lane < 32) row[64 + lane] = (unsigned char)c2;
+        __builtin_amdgcn_wave_barrier();
+        bool last;
+        const u64 starts = dev::step_starts(c, dm, &carry, &last);
+        const u32 ord = seen + (u32)__popcll(starts & below);
+        const bool emit = ((starts >> lane) & 1ull) && ord < E;
+        u32 eq = 0;  // bit j: this lane's token equals term j
+        if (emit) {
+          u64 w0, w1, w2, w3;
+          dev::pack_row_key(row, lane, dm, max_key_len, &w0, &w1, &w2, &w3);
+          for (u32 j = 0; j < m; ++j) {
+            const u64* k = qk + j * kKeyWords;
+            eq |= (u32)(k[0] == w0 && k[1] == w1 && k[2] == w2 && k[3] == w3) << j;
+          }
+        }
+        // the automaton over the step's emitted tokens in order (all wave-uniform)
+        u64 em = dev::ballot(emit);
+        if (dev::ballot(eq != 0u) == 0) {
+          if (em) state = 0;  // no token of this step equals any term
+        } else {
+          while (em) {
+            const int tl = __ffsll((unsigned long long)em) - 1;
+            const u32 e = (u32)__shfl((int)eq, tl, 64);
+            state = ((state << 1) | 1u) & e;
+            if (state & accept) {
+              match = true;
+              break;
+            }
+            em &= em - 1;
+          }
+        }
+        seen += (u32)__popcll(starts);
+        if (last) break;  // a NUL, or the line end, inside this step
+      }
+      if ((u32)lane == i) hit = match;
+    }
+    if (lane == 0) atomicAdd(&ctr->verified, cnt);
+    commit_hits(hit, (u32)(mine >> 32), (u32)mine, pairs, pair_cap, q_hits, ctr);
   }
 }
 
@@ -252,6 +386,7 @@ static_assert(sizeof(SearchCounters) <= 64, "zero block layout");
 template <class Take>
 void hits_layout(u64 cap, Take&& take) {
   take(cap * 8);                                               // pairs
+  take(cap * 8);                                               // cands
   take(cap * 8);                                               // zeros
   take(cap * 8);                                               // sorted
   take(cap * 8);                                               // spare
@@ -308,7 +443,7 @@ u64 search_hits_bytes(u64 cap) {
 }
 
 void search_hits_carve(char* base, u64 cap, SearchHits* h) {
-  char* part[12];
+  char* part[13];
   int k = 0;
   u64 b = 0;
   hits_layout(cap, [&](u64 bytes) {
@@ -317,18 +452,19 @@ void search_hits_carve(char* base, u64 cap, SearchHits* h) {
     b += bytes;
   });
   h->pairs = reinterpret_cast<u64*>(part[0]);
-  h->zeros = reinterpret_cast<u64*>(part[1]);
-  h->sorted = reinterpret_cast<u64*>(part[2]);
-  h->spare = reinterpret_cast<u64*>(part[3]);
-  h->lines = reinterpret_cast<u32*>(part[4]);
-  h->rx.tile_counters = reinterpret_cast<u32*>(part[5]);
+  h->cands = reinterpret_cast<u64*>(part[1]);
+  h->zeros = reinterpret_cast<u64*>(part[2]);
+  h->sorted = reinterpret_cast<u64*>(part[3]);
+  h->spare = reinterpret_cast<u64*>(part[4]);
+  h->lines = reinterpret_cast<u32*>(part[5]);
+  h->rx.tile_counters = reinterpret_cast<u32*>(part[6]);
   h->rx.status = h->rx.tile_counters + kNumPositions;
-  h->rx.hist_part = reinterpret_cast<u32*>(part[6]);
-  h->rx.plan = reinterpret_cast<SortPlan*>(part[7]);
-  h->rx.keys[0] = reinterpret_cast<u64*>(part[8]);
-  h->rx.keys[1] = reinterpret_cast<u64*>(part[9]);
-  h->rx.vals[0] = reinterpret_cast<u32*>(part[10]);
-  h->rx.vals[1] = reinterpret_cast<u32*>(part[11]);
+  h->rx.hist_part = reinterpret_cast<u32*>(part[7]);
+  h->rx.plan = reinterpret_cast<SortPlan*>(part[8]);
+  h->rx.keys[0] = reinterpret_cast<u64*>(part[9]);
+  h->rx.keys[1] = reinterpret_cast<u64*>(part[10]);
+  h->rx.vals[0] = reinterpret_cast<u32*>(part[11]);
+  h->rx.vals[1] = reinterpret_cast<u32*>(part[12]);
   h->rx.cap = cap;
   h->cap = cap;
 }
@@ -349,7 +485,7 @@ void launch_search_lookup(const SearchIndex& ix, const SearchBatch& b, u32 queri
 }
 
 void launch_search_hits(const SearchIndex& ix, const SearchBatch& b, u32 queries, u64 bound,
-                        const SearchHits& h, hipStream_t s) {
+                        bool verify, const SearchHits& h, hipStream_t s) {
   LOCUST_CHECK_ARG(bound < (1ull << 32) && bound <= h.cap,
                    "search: " + std::to_string(bound) + " list elements exceed the workspace (" +
                        std::to_string(h.cap) + ")");
@@ -358,7 +494,21 @@ void launch_search_hits(const SearchIndex& ix, const SearchBatch& b, u32 queries
         (u32)std::min<u64>(div_up(bound, (u64)kSearchTile), (u64)kSearchMaxBlocks);
     search_hit_kernel<<<dim3(blocks), dim3(kSearchBlock), 0, s>>>(
         ix.postings, ix.first_line, b.q_meta, b.q_info, b.q_start, b.t_val, b.t_len, queries,
-        bound, h.pairs, h.cap, b.q_hits, b.ctr);
+        bound, h.pairs, h.cands, h.cap, b.q_hits, b.ctr);
+    LOCUST_HIP_LAUNCH_CHECK();
+  }
+  if (bound && verify && ix.bytes) {
+    LOCUST_CHECK_ARG(ix.text && ix.nl_pos && ix.lctr && ix.emits_per_line > 0 &&
+                         ix.max_key_len > 0 && ix.max_key_len <= kKeyBytes,
+                     "search: a phrase needs the index's text view");
+    // at most `bound` candidates: one per wave while they are few, up to 64 per wave and
+    // round when every wave of a full grid has many to walk anyway (as launch_index)
+    const u32 group = (u32)std::min<u64>(div_up(bound, (u64)kPhraseMaxBlocks), 64);
+    const u32 blocks = (u32)std::min<u64>(div_up(div_up(bound, (u64)group), (u64)kPhraseWaves),
+                                          (u64)kPhraseMaxBlocks);
+    search_phrase_kernel<<<dim3(blocks), dim3(kPhraseBlock), 0, s>>>(
+        ix.text, ix.bytes, ix.nl_pos, ix.lctr, ix.dm, ix.emits_per_line, ix.max_key_len, group,
+        b.q_meta, b.keys, queries, h.cands, h.pairs, h.cap, b.q_hits, b.ctr);
     LOCUST_HIP_LAUNCH_CHECK();
   }
   search_seal_kernel<<<dim3(1), dim3(1), 0, s>>>(b.ctr, h.cap);

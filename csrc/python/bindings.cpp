@@ -181,14 +181,17 @@ struct PySearchResult {
   }
 };
 
-// queries: term lists; any[i] != 0: query i in `any` mode (any.size() == queries.size()).
+// queries: term lists; any[i]: query i's mode -- 0 `all`, 2 `phrase`, every other value `any`
+// (any.size() == queries.size()).
 std::vector<SearchQuery> to_queries(const std::vector<std::vector<std::string>>& queries,
                                     const std::vector<int>& any) {
   LOCUST_CHECK_ARG(any.size() == queries.size(), "search: one mode per query");
   std::vector<SearchQuery> out(queries.size());
   for (size_t i = 0; i < queries.size(); ++i) {
     out[i].terms = queries[i];
-    out[i].mode = any[i] ? SearchMode::kAny : SearchMode::kAll;
+    out[i].mode = any[i] == 0   ? SearchMode::kAll
+                  : any[i] == 2 ? SearchMode::kPhrase
+                                : SearchMode::kAny;
   }
   return out;
 }

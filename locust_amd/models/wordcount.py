@@ -15,21 +15,27 @@ from ..config import make_config, make_dist_config
 _C = load()
 
 
+_SEARCH_MODES = {"all": 0, "any": 1, "phrase": 2}
+
+
 def _search_args(queries, mode):
-    """(term lists, one any-flag per query) for the native search entry points."""
+    """(term lists, one mode flag per query: 0 all, 1 any, 2 phrase) for the native search
+    entry points."""
     queries = [list(q) for q in queries]
     modes = [mode] * len(queries) if isinstance(mode, str) else list(mode)
     if len(modes) != len(queries):
         raise ValueError("search: one mode per query")
     for m in modes:
-        if m not in ("all", "any"):
-            raise ValueError("search: mode must be 'all' or 'any', not %r" % (m,))
-    return queries, [int(m == "any") for m in modes]
+        if m not in _SEARCH_MODES:
+            raise ValueError("search: mode must be 'all', 'any' or 'phrase', not %r" % (m,))
+    return queries, [_SEARCH_MODES[m] for m in modes]
 
 
 def _index_search(self, queries, mode="all"):
     """All/any word queries over this index, evaluated on the host (``SearchResult``):
-    ``queries`` and ``mode`` as ``Engine.run_search`` takes them, any number of queries."""
+    ``queries`` and ``mode`` as ``Engine.run_search`` takes them, any number of queries.
+    A ``"phrase"`` query is refused: the index holds no positions, so a phrase needs the
+    text (``Engine.run_search``, ``search_text``)."""
     queries, flags = _search_args(queries, mode)
     return self._search(queries, flags)
 
@@ -76,12 +82,15 @@ class Engine:
     def run_search(self, text: bytes, queries, mode="all", first_line: int = 0):
         """WordCount of ``text``, its inverted index, and a batch of word queries answered
         from it (``SearchResult``).  ``queries`` is a list of term lists (1 to 8 byte-string
-        terms each); ``mode`` is ``"all"`` (lines that hold every term) or ``"any"`` (lines
-        that hold at least one), or a list with one mode per query.  ``lines(i)`` are query
+        terms each); ``mode`` is ``"all"`` (lines that hold every term), ``"any"`` (lines
+        that hold at least one) or ``"phrase"`` (lines on which the terms are consecutive
+        tokens, in order: ``oracle.phrase`` states the rules), or a list with one mode per
+        query.  ``lines(i)`` are query
         ``i``'s global line numbers, ascending, each once.  On the GPU the index stays in
         device memory and only the answers cross PCIe (at most ``_C.kSearchMaxQueries``
-        queries per batch; ``run_index(text).search(...)`` evaluates any number on the
-        host)."""
+        queries per batch; ``run_index(text).search(...)`` evaluates any number of all/any
+        queries on the host).  A phrase is verified on the device against the engine's own
+        copy of the text; the CPU engine answers phrases of any size."""
         queries, flags = _search_args(queries, mode)
         if self.cpu:
             return _C.cpu_run_search(self.cfg, text, queries, flags, first_line)
@@ -89,7 +98,8 @@ class Engine:
 
     def search_resident(self, queries, mode="all"):
         """Another batch from the index this engine's last job left on the device; that
-        job must have been a ``run_index`` or a ``run_search`` (GPU engines only)."""
+        job must have been a ``run_index`` or a ``run_search`` (GPU engines only).  Every
+        mode of ``run_search``: the job's text is resident too, so phrases are answered."""
         if self.cpu:
             raise _C.LocustError("search_resident needs a GPU engine: the CPU engine keeps "
                                  "no index (use run_index(text).search(...))")
@@ -190,7 +200,8 @@ def index_file(path: str, line_start: int = -1, line_end: int = -1, backend: str
 
 def search_text(text: bytes, queries, mode="all", backend: str = "gpu", cfg=None,
                 first_line: int = 0, **kw):
-    """All/any word queries over ``text`` (``SearchResult``); see ``Engine.run_search``."""
+    """All/any/phrase word queries over ``text`` (``SearchResult``); see
+    ``Engine.run_search``."""
     cfg = cfg if cfg is not None else make_config(backend, **kw)
     nlines = text.count(b"\n") + (1 if text and not text.endswith(b"\n") else 0)
     return Engine(cfg, max(len(text), 1), max(nlines, 1)).run_search(text, queries, mode,
@@ -199,8 +210,8 @@ def search_text(text: bytes, queries, mode="all", backend: str = "gpu", cfg=None
 
 def search_file(path: str, queries, mode="all", line_start: int = -1, line_end: int = -1,
                 backend: str = "gpu", cfg=None, **kw):
-    """All/any word queries over a file or its line window, answered with the file's own
-    (global) line numbers."""
+    """All/any/phrase word queries over a file or its line window, answered with the file's
+    own (global) line numbers."""
     cfg = cfg if cfg is not None else make_config(backend, **kw)
     text, nlines, first, _total = _C.load_lines(path, line_start, line_end, cfg.ref_compat)
     return Engine(cfg, max(len(text), 1), max(nlines, 1)).run_search(text, queries, mode, first)

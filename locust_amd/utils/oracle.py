@@ -168,6 +168,45 @@ def search(entries, postings, terms, mode: str = "all", delims: bytes = DEFAULT_
     return sorted(hit), counts
 
 
+def phrase(text: bytes, terms, delims: bytes = DEFAULT_DELIMS, emits: int = 20,
+           max_key: int = 29, first_line: int = 0):
+    """One phrase query over ``text``: ``(lines, counts)``, as ``search`` answers.
+
+    `phrase` answers the lines on which the terms occur as consecutive tokens, in order.
+    A line's token sequence is exactly what the word job emits for it, in order: the job's
+    delimiter set, a NUL ends the line's tokens, only the first emits_per_line tokens, each
+    token cut to max_key_len bytes.  A line with tokens k_0 .. k_(n-1) matches the terms
+    t_0 .. t_(m-1), each cut to max_key_len bytes, when some o exists with k_(o+j) == t_j
+    for every j in [0, m).  Tokens past the emit cap do not exist for this purpose, a phrase
+    never crosses a line end, and what stood between two consecutive tokens does not matter:
+    any run of delimiters, of any length, counts.  Repeated terms are significant here:
+    [bye, bye] matches only a line with two consecutive bye tokens.  A one-term phrase
+    answers as `all` does, an absent term gives an empty answer, and long tokens that merge
+    under truncation match as their merged key, the rule the index uses.  The answer and the
+    per-term counts have the shape of the other modes'; repeated terms report the same count.
+
+    Terms are validated as ``search`` validates them (``ValueError``).  Written straight from
+    the paragraph above: every line is tokenised and every window compared; no index."""
+    terms = list(terms)
+    if not 1 <= len(terms) <= MAX_SEARCH_TERMS:
+        raise ValueError("a query takes 1 to %d terms" % MAX_SEARCH_TERMS)
+    bad = set(delims) | {0, 0x0A}
+    for t in terms:
+        if not t or any(c in bad for c in t):
+            raise ValueError("invalid term %r" % (t,))
+    want = [t[:max_key] for t in terms]
+    m = len(want)
+    lines = []
+    counts = [0] * m
+    for i, line in enumerate(split_lines(text)):
+        toks, _dropped = tokenize(line, delims, emits, max_key)
+        for j, t in enumerate(want):
+            counts[j] += toks.count(t)
+        if any(toks[o:o + m] == want for o in range(len(toks) - m + 1)):
+            lines.append(first_line + i)
+    return lines, counts
+
+
 def format_search(queries, answers) -> bytes:
     """The CLI's ``--search`` result lines: one per query, ``queries[i]`` its terms and
     ``answers[i]`` its lines (every line number after one space; none after "lines:" when

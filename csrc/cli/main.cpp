@@ -20,6 +20,7 @@
 //   --search "w1 w2" [--match all|any|phrase] (the lines that hold all / any of the words,
 //     or the words as consecutive tokens in that order; repeat --search for a batch:
 //     answered from the index on the device, or by --backend cpu)
+//   --rank K (with --search: each query's K best lines with their scores, best first)
 // and a synthetic-text generator (BASELINE configs "1M lines" / "10 GB"):
 //   MapReduce --gen FILE (--gen-lines N | --gen-bytes N) [--seed S] [--vocab V]
 #include <sys/stat.h>
@@ -89,6 +90,8 @@ struct CliArgs {
   std::vector<std::string> search_args;
   std::vector<SearchQuery> queries;
   std::string match;  // --match all|any|phrase ("": all)
+  bool rank_given = false;
+  u64 rank = 0;  // --rank K: every query answers its K best lines, scored (0: all its lines)
   std::string gen_out;  // generator mode
   GenSpec gen;
 };
@@ -134,6 +137,11 @@ void help() {
       "  --match all|any|phrase     (--search: lines with every word (default), with any, or\n"
       "                             with the words as consecutive tokens in the order given,\n"
       "                             whatever delimiters stand between them)\n"
+      "  --rank K                   (--search: only each query's K best lines, best first, as\n"
+      "                             line:score; a line's score adds, per distinct word of the\n"
+      "                             query, its occurrences on the line times a weight that grows\n"
+      "                             with the word's rarity.  Scored and selected on the device on\n"
+      "                             one GPU, or by --backend cpu; K >= 1)\n"
       "  --help\n"
       "\n"
       "Environment: LOCUST_LOG=info|debug and the LOCUST_* switches in docs/ENVIRONMENT.md.\n",
@@ -260,6 +268,15 @@ bool parse(int argc, char** argv, CliArgs* a) {
       a->match = need("--match");
       if (a->match != "all" && a->match != "any" && a->match != "phrase")
         throw Error("--match takes all, any or phrase (how --search combines its words)");
+    } else if (s == "--rank") {
+      const std::string v = need("--rank");
+      char* endp = nullptr;
+      const long long k = std::strtoll(v.c_str(), &endp, 10);
+      if (v.empty() || *endp || k < 1 || k > 0xffffffffll)
+        throw Error("--rank K (the best K lines of every --search query) needs an integer K "
+                    "with 1 <= K < 2^32");
+      a->rank = (u64)k;
+      a->rank_given = true;
     } else if (s == "--ngram") {
       const std::string v = need("--ngram");
       char* endp = nullptr;
@@ -317,6 +334,8 @@ bool parse(int argc, char** argv, CliArgs* a) {
   }
   if (!a->match.empty() && a->search_args.empty())
     throw Error("--match selects how --search combines its words: give --search too");
+  if (a->rank_given && a->search_args.empty())
+    throw Error("--rank K selects the best lines of a --search query: give --search too");
   if (a->index && !a->search_args.empty())
     throw Error("--index and --search do not combine: --index prints the whole index, "
                 "--search the lines of its queries");
@@ -364,6 +383,10 @@ bool parse(int argc, char** argv, CliArgs* a) {
   }
   if (!a->queries.empty()) {
     check_search_queries(a->queries, a->cfg);
+    if (a->rank && (u64)a->cfg.emits_per_line > kRankMaxEmits)
+      throw Error("--rank K takes --emits-per-line <= " + std::to_string(kRankMaxEmits) +
+                  " (emits_per_line <= kRankMaxEmits: its scores fit 22 bits)");
+    check_search_rank(a->rank, a->cfg);
     if (a->cfg.backend == Backend::kGpu && a->queries.size() > (size_t)kSearchMaxQueries)
       throw Error("--search: a device batch holds at most " + std::to_string(kSearchMaxQueries) +
                   " queries (use --backend cpu for more)");
@@ -518,6 +541,10 @@ void json_search(JsonOut& j, const CliArgs& a) {
   j.u("queries", a.queries.size());
   if (g_search) {
     j.u("hits", g_search->lines.size());
+    u64 matches = 0;
+    for (const u64 m : g_search->matches) matches += m;
+    j.u("rank_k", g_search->rank_k);
+    j.u("matches", matches);
     j.num("index_ms", g_search->index_ms);
     j.num("search_ms", g_search->search_ms);
     j.u("wire_bytes", g_search->wire_bytes);
@@ -1095,7 +1122,7 @@ int run(const CliArgs& a) {
     for (int i = 0; i < a.warmup; ++i) eng.run(text.input);
     for (int i = 0; i < a.iters; ++i) {
       if (!a.queries.empty()) {
-        cpu_search = eng.run_search(text.input, a.queries);
+        cpu_search = eng.run_search(text.input, a.queries, a.rank);
         r = search_stats(cpu_search);
       } else if (a.index) {
         cpu_index = eng.run_index(text.input);
@@ -1116,7 +1143,7 @@ int run(const CliArgs& a) {
     if (!a.queries.empty()) {  // the word job, the index stage and the search stage
       SearchResult sr;
       for (int i = 0; i < a.warmup + a.iters; ++i) {
-        sr = eng.run_search(text.input, a.queries);
+        sr = eng.run_search(text.input, a.queries, a.rank);
         if (i >= a.warmup) walls.push_back(sr.times.wall_ms);
       }
       print_gpu_result(a, search_stats(sr), walls, nullptr, nullptr, &sr);

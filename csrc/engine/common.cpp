@@ -399,6 +399,16 @@ void check_search_queries(const std::vector<SearchQuery>& queries, const JobConf
   }
 }
 
+void check_search_rank(u64 rank_k, const JobConfig& cfg) {
+  if (rank_k == 0) return;
+  LOCUST_CHECK_ARG(rank_k <= 0xffffffffull,
+                   "search: rank takes 1 <= K < 2^32, not " + std::to_string(rank_k));
+  LOCUST_CHECK_ARG((u64)cfg.emits_per_line <= kRankMaxEmits,
+                   "search: a ranked search takes emits_per_line <= kRankMaxEmits = " +
+                       std::to_string(kRankMaxEmits) + " (its scores fit 22 bits), not " +
+                       std::to_string(cfg.emits_per_line));
+}
+
 namespace {
 
 // Do the first emits_per_line tokens of the line hold the keys as consecutive tokens?
@@ -416,8 +426,10 @@ bool line_has_phrase(const char* line, u64 len, const std::vector<PackedKey>& ke
 }
 
 SearchResult search_index_impl(const IndexResult& x, const TextInput* text,
-                               const std::vector<SearchQuery>& queries, const JobConfig& cfg) {
+                               const std::vector<SearchQuery>& queries, const JobConfig& cfg,
+                               u64 rank_k) {
   check_search_queries(queries, cfg);
+  check_search_rank(rank_k, cfg);
   bool verify = false;  // a phrase of two or more terms
   for (const SearchQuery& q : queries)
     verify |= q.mode == SearchMode::kPhrase && q.terms.size() >= 2;
@@ -453,6 +465,8 @@ SearchResult search_index_impl(const IndexResult& x, const TextInput* text,
   r.times = x.words.times;
   r.index_ms = x.index_ms;
   r.wire_bytes = x.wire_bytes;
+  r.rank_k = rank_k;
+  r.emits_per_line = (u64)cfg.emits_per_line;
   const size_t n = x.words.entries.size();
   const WordCountEntry* ent = x.words.entries.data();
   std::vector<u64> val(n + 1, 0);
@@ -464,8 +478,10 @@ SearchResult search_index_impl(const IndexResult& x, const TextInput* text,
     const u32* p;
     u64 len;
   };
+  std::vector<std::pair<u32, u32>> ranked;  // (score, line) of one query's matching lines
   for (size_t qi = 0; qi < queries.size(); ++qi) {
     const SearchQuery& q = queries[qi];
+    const size_t from = r.lines.size();
     std::vector<List> lists;  // the distinct present terms
     bool absent = false;
     for (size_t t = 0; t < q.terms.size(); ++t) {
@@ -509,11 +525,37 @@ SearchResult search_index_impl(const IndexResult& x, const TextInput* text,
         }
       }
     } else {
-      const size_t from = r.lines.size();
       for (const List& l : lists) r.lines.insert(r.lines.end(), l.p, l.p + l.len);
       std::sort(r.lines.begin() + (std::ptrdiff_t)from, r.lines.end());
       r.lines.erase(std::unique(r.lines.begin() + (std::ptrdiff_t)from, r.lines.end()),
                     r.lines.end());
+    }
+    r.matches.push_back(r.lines.size() - from);
+    if (rank_k) {  // the matching lines' scores, the order and the cut
+      const u64 N = x.postings.size();
+      ranked.clear();
+      for (size_t j = from; j < r.lines.size(); ++j) {
+        const u32 line = r.lines[j];
+        u64 score = 0;
+        for (const List& l : lists) {
+          const auto eq = std::equal_range(l.p, l.p + l.len, line);
+          const u64 w = N / l.len;  // (>= 1: a list is part of the postings)
+          score += (u64)(64 - __builtin_clzll(w)) * (u64)(eq.second - eq.first);
+        }
+        if (score == 0 || score > 32 * (u64)cfg.emits_per_line)
+          throw Error("search: line " + std::to_string(line) + " of query " + std::to_string(qi) +
+                      " scores " + std::to_string(score) + ", outside [1, 32 * emits_per_line]");
+        ranked.emplace_back((u32)score, line);
+      }
+      std::sort(ranked.begin(), ranked.end(), [](const auto& a, const auto& b) {
+        return a.first != b.first ? a.first > b.first : a.second < b.second;
+      });
+      if (ranked.size() > rank_k) ranked.resize((size_t)rank_k);
+      r.lines.resize(from);
+      for (const auto& sl : ranked) {
+        r.lines.push_back(sl.second);
+        r.scores.push_back(sl.first);
+      }
     }
     r.offsets.push_back(r.lines.size());
   }
@@ -526,13 +568,14 @@ SearchResult search_index_impl(const IndexResult& x, const TextInput* text,
 }  // namespace
 
 SearchResult search_index(const IndexResult& x, const std::vector<SearchQuery>& queries,
-                          const JobConfig& cfg) {
-  return search_index_impl(x, nullptr, queries, cfg);
+                          const JobConfig& cfg, u64 rank_k) {
+  return search_index_impl(x, nullptr, queries, cfg, rank_k);
 }
 
 SearchResult search_index(const IndexResult& x, const TextInput& text,
-                          const std::vector<SearchQuery>& queries, const JobConfig& cfg) {
-  return search_index_impl(x, &text, queries, cfg);
+                          const std::vector<SearchQuery>& queries, const JobConfig& cfg,
+                          u64 rank_k) {
+  return search_index_impl(x, &text, queries, cfg, rank_k);
 }
 
 void validate_search(const SearchResult& r) {
@@ -540,15 +583,37 @@ void validate_search(const SearchResult& r) {
       r.offsets.back() != r.lines.size())
     throw Error("LOCUST_CHECK: search offsets do not span the " + std::to_string(r.lines.size()) +
                 " lines of " + std::to_string(r.queries.size()) + " queries");
+  if (r.matches.size() != r.queries.size() ||
+      r.scores.size() != (r.rank_k ? r.lines.size() : (size_t)0))
+    throw Error("LOCUST_CHECK: search result with " + std::to_string(r.matches.size()) +
+                " match counts and " + std::to_string(r.scores.size()) + " scores for " +
+                std::to_string(r.queries.size()) + " queries and " +
+                std::to_string(r.lines.size()) + " lines");
   const u64 lo = r.first_line, hi = r.first_line + r.num_lines;
   for (size_t q = 0; q + 1 < r.offsets.size(); ++q) {
     if (r.offsets[q + 1] < r.offsets[q] || r.offsets[q + 1] > r.lines.size())
       throw Error("LOCUST_CHECK: search offsets decrease at query " + std::to_string(q));
+    const u64 returned = r.offsets[q + 1] - r.offsets[q];
+    if (r.rank_k ? returned > std::min<u64>(r.rank_k, r.matches[q]) : returned != r.matches[q])
+      throw Error("LOCUST_CHECK: query " + std::to_string(q) + " returns " +
+                  std::to_string(returned) + " lines of " + std::to_string(r.matches[q]) +
+                  " matches");
     for (u64 j = r.offsets[q]; j < r.offsets[q + 1]; ++j) {
       const u64 l = r.lines[j];
       if (l < lo || l >= hi)
         throw Error("LOCUST_CHECK: line " + std::to_string(l) + " of query " + std::to_string(q) +
                     " outside the lines [" + std::to_string(lo) + ", " + std::to_string(hi) + ")");
+      if (r.rank_k) {
+        const u64 sc = r.scores[j];
+        if (sc < 1 || sc > 32 * r.emits_per_line)
+          throw Error("LOCUST_CHECK: score " + std::to_string(sc) + " of query " +
+                      std::to_string(q) + " outside [1, 32 * emits_per_line]");
+        if (j > r.offsets[q] &&
+            (sc > r.scores[j - 1] || (sc == r.scores[j - 1] && l <= r.lines[j - 1])))
+          throw Error("LOCUST_CHECK: lines of query " + std::to_string(q) +
+                      " not in rank order at position " + std::to_string(j - r.offsets[q]));
+        continue;
+      }
       if (j > r.offsets[q] && l <= r.lines[j - 1])
         throw Error("LOCUST_CHECK: lines of query " + std::to_string(q) +
                     " not strictly ascending at position " + std::to_string(j - r.offsets[q]));
@@ -565,11 +630,15 @@ void format_search_output(const SearchResult& r, std::string* out) {
       out->append(t);
     }
     out->append(" \t hits: ");
-    out->append(std::to_string(r.offsets[q + 1] - r.offsets[q]));
-    out->append(" \t lines:");
+    out->append(std::to_string(r.rank_k ? r.matches[q] : r.offsets[q + 1] - r.offsets[q]));
+    out->append(r.rank_k ? " \t top:" : " \t lines:");
     for (u64 j = r.offsets[q]; j < r.offsets[q + 1]; ++j) {
       out->push_back(' ');
       out->append(std::to_string(r.lines[j]));
+      if (r.rank_k) {
+        out->push_back(':');
+        out->append(std::to_string(r.scores[j]));
+      }
     }
     out->push_back('\n');
   }

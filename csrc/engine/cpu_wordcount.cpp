@@ -135,9 +135,10 @@ IndexResult CpuWordCount::run_index(const TextInput& in) {
 }
 
 SearchResult CpuWordCount::run_search(const TextInput& in,
-                                      const std::vector<SearchQuery>& queries) {
+                                      const std::vector<SearchQuery>& queries, u64 rank_k) {
   check_search_queries(queries, cfg_);  // (before the index is built)
-  return search_index(run_index(in), in, queries, cfg_);
+  check_search_rank(rank_k, cfg_);
+  return search_index(run_index(in), in, queries, cfg_, rank_k);
 }
 
 std::vector<PackedKey> CpuWordCount::run_map_stage(const TextInput& in, WordCountResult* stats) {

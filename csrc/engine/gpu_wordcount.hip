@@ -50,11 +50,11 @@ TopResult GpuWordCount::top_counts(const KeyCount* recs, u64 n, u32 k) {
 }
 IndexResult GpuWordCount::run_index(const TextInput& in) { return impl_->run_index(in); }
 SearchResult GpuWordCount::run_search(const TextInput& in,
-                                      const std::vector<SearchQuery>& queries) {
-  return impl_->run_search(in, queries);
+                                      const std::vector<SearchQuery>& queries, u64 rank_k) {
+  return impl_->run_search(in, queries, rank_k);
 }
-SearchResult GpuWordCount::search_resident(const std::vector<SearchQuery>& queries) {
-  return impl_->search_resident(queries);
+SearchResult GpuWordCount::search_resident(const std::vector<SearchQuery>& queries, u64 rank_k) {
+  return impl_->search_resident(queries, rank_k);
 }
 GpuWordCount::Stats GpuWordCount::stats() const {
   Stats s;

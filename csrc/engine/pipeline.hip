@@ -30,7 +30,7 @@ u64 DevicePipeline::pinned_bytes() const {
   if (h_ictr) b += h_post_cap * sizeof(u32) + sizeof(IndexCounters);
   if (h_supload)
     b += search_upload_bytes(kSearchMaxQueries) + h_slines_cap * sizeof(u32) +
-         ((u64)kSearchMaxQueries * (kSearchMaxTerms * 4 + 8) + 72);
+         ((u64)kSearchMaxQueries * (kSearchMaxTerms * 4 + 8 + 4) + 72);
   b += 2 * sizeof(MapCounters) + sizeof(SortPlan) + 2 * sizeof(PartMapTables) +
        kMaxSamples * sizeof(PackedKey) + (kMaxRanks + 8) * sizeof(u64) + 64 +
        kDictParts * sizeof(u32);
@@ -2056,10 +2056,11 @@ IndexResult DevicePipeline::run_index(const TextInput& in) {
 // =====================================================================================
 namespace {
 constexpr u64 kSearchQT = (u64)kSearchMaxQueries * kSearchMaxTerms;
-// the pinned result block: [SearchCounters (64 B) | t_len | offsets]
+// the pinned result block: [SearchCounters (64 B) | t_len | offsets | q_hits (ranked)]
 constexpr u64 kSearchResLen = 64;
 constexpr u64 kSearchResOff = kSearchResLen + kSearchQT * sizeof(u32);
-constexpr u64 kSearchResBytes = kSearchResOff + ((u64)kSearchMaxQueries + 1) * sizeof(u64);
+constexpr u64 kSearchResHits = kSearchResOff + ((u64)kSearchMaxQueries + 1) * sizeof(u64);
+constexpr u64 kSearchResBytes = kSearchResHits + (u64)kSearchMaxQueries * sizeof(u32);
 }  // namespace
 
 void DevicePipeline::ensure_search() {
@@ -2097,16 +2098,19 @@ void DevicePipeline::ensure_search_hits(u64 bound) {
   LOCUST_HIP_CHECK(hipMemsetAsync(shits.zeros, 0, cap * 8, stream));
 }
 
-void DevicePipeline::check_search_batch(const std::vector<SearchQuery>& queries) const {
+void DevicePipeline::check_search_batch(const std::vector<SearchQuery>& queries,
+                                        u64 rank_k) const {
   LOCUST_CHECK_ARG(queries.size() <= (size_t)kSearchMaxQueries,
                    "search: a device batch holds at most kSearchMaxQueries = " +
                        std::to_string(kSearchMaxQueries) + " queries, not " +
                        std::to_string(queries.size()) + "; split the batch, or evaluate on the "
                        "host (search_index / IndexResult.search)");
   check_search_queries(queries, cfg);
+  check_search_rank(rank_k, cfg);
 }
 
-void DevicePipeline::search_stage(const std::vector<SearchQuery>& queries, SearchResult* r) {
+void DevicePipeline::search_stage(const std::vector<SearchQuery>& queries, u64 rank_k,
+                                  SearchResult* r) {
   TraceRange tr("locust:search");
   const u32 Q = (u32)queries.size();
   r->queries = queries;
@@ -2117,7 +2121,10 @@ void DevicePipeline::search_stage(const std::vector<SearchQuery>& queries, Searc
   r->overflow_lines = idx_words.overflow_lines;
   r->truncated = idx_words.truncated;
   r->max_key_len = idx_words.max_key_len;
+  r->rank_k = rank_k;
+  r->emits_per_line = (u64)cfg.emits_per_line;
   r->offsets.assign((size_t)Q + 1, 0);
+  r->matches.assign((size_t)Q, 0);
   r->term_counts.assign((size_t)Q * kSearchMaxTerms, 0);
   ensure_search();
   LOCUST_HIP_CHECK(hipEventRecord(ev_search[0], stream));
@@ -2164,6 +2171,10 @@ void DevicePipeline::search_stage(const std::vector<SearchQuery>& queries, Searc
   launch_search_hits(idx_view, sbatch, Q, B, verify, shits, stream);
   LOCUST_HIP_CHECK(hipMemcpyAsync(h_sc, sbatch.ctr, sizeof(SearchCounters), hipMemcpyDeviceToHost,
                                   stream));
+  u32* h_hits = reinterpret_cast<u32*>(h_sres + kSearchResHits);
+  if (rank_k)  // the matches: they size what comes back
+    LOCUST_HIP_CHECK(hipMemcpyAsync(h_hits, sbatch.q_hits, (u64)Q * sizeof(u32),
+                                    hipMemcpyDeviceToHost, stream));
   sync();
   const u64 H = h_sc->written, C = h_sc->cands;
   if (H > B || h_sc->sort_n != H)
@@ -2173,12 +2184,56 @@ void DevicePipeline::search_stage(const std::vector<SearchQuery>& queries, Searc
     throw Error("search: " + std::to_string(C) + " phrase candidates, " +
                 std::to_string(h_sc->verified) + " of them verified, the lists hold " +
                 std::to_string(B) + " elements");
-  if (h_slines_cap < H) {
+  // ranked: R lines and R scores come back, R = the sum of min(matches, K)
+  u64 R = 0, M = 0;
+  if (rank_k)
+    for (u32 q = 0; q < Q; ++q) {
+      R += std::min<u64>(h_hits[q], rank_k);
+      M += h_hits[q];
+    }
+  if (rank_k && M != H)
+    throw Error("search: the per-query hit counts add up to " + std::to_string(M) +
+                ", the hit kernel wrote " + std::to_string(H));
+  const u64 need = rank_k ? 2 * R : H;
+  if (h_slines_cap < need) {
     pinned_free(h_slines);
     h_slines = nullptr;
-    h_slines_cap = align_up(H, (u64)kSortTile);
+    h_slines_cap = align_up(need, (u64)kSortTile);
     h_slines = static_cast<u32*>(
         pinned_alloc(h_slines_cap * sizeof(u32), hipHostMallocDefault, "search lines"));
+  }
+  if (rank_k) {
+    // offsets + score + order + top: only the winners and their scores cross
+    launch_search_rank(idx_view, sbatch, Q, H, (u32)rank_k, shits, h_plan, stream);
+    LOCUST_HIP_CHECK(hipMemcpyAsync(h_off, sbatch.out_off, ((u64)Q + 1) * sizeof(u64),
+                                    hipMemcpyDeviceToHost, stream));
+    if (R) {
+      LOCUST_HIP_CHECK(hipMemcpyAsync(h_slines, shits.lines, R * sizeof(u32),
+                                      hipMemcpyDeviceToHost, stream));
+      LOCUST_HIP_CHECK(hipMemcpyAsync(h_slines + R, search_rank_scores(shits), R * sizeof(u32),
+                                      hipMemcpyDeviceToHost, stream));
+    }
+    LOCUST_HIP_CHECK(hipMemcpyAsync(h_sc, sbatch.ctr, sizeof(SearchCounters),
+                                    hipMemcpyDeviceToHost, stream));
+    LOCUST_HIP_CHECK(hipEventRecord(ev_search[1], stream));
+    sync();
+    if (h_sc->misplaced)
+      throw Error("search: " + std::to_string(h_sc->misplaced) + " of " + std::to_string(H) +
+                  " sorted hits lie outside their query's range");
+    if (h_sc->unscored)
+      throw Error("search: " + std::to_string(h_sc->unscored) + " of " + std::to_string(H) +
+                  " hits score 0 or more than 32 * emits_per_line");
+    if (h_off[Q] != R)
+      throw Error("search: the output offsets end at " + std::to_string(h_off[Q]) +
+                  ", the hit counts and K give " + std::to_string(R));
+    r->offsets.assign(h_off, h_off + Q + 1);
+    r->matches.assign(h_hits, h_hits + Q);
+    r->lines.assign(h_slines, h_slines + R);
+    r->scores.assign(h_slines + R, h_slines + 2 * R);
+    for (u64 i = 0; i < (u64)Q * kSearchMaxTerms; ++i) r->term_counts[i] = h_tlen[i];
+    r->wire_bytes = ((u64)Q + 1) * sizeof(u64) + (u64)Q * sizeof(u32) + 2 * R * sizeof(u32) +
+                    (u64)Q * kSearchMaxTerms * sizeof(u32) + 3 * sizeof(SearchCounters);
+    return;
   }
   // order + emit
   launch_search_order(idx_view, sbatch, Q, H, shits, h_plan, stream);
@@ -2198,6 +2253,7 @@ void DevicePipeline::search_stage(const std::vector<SearchQuery>& queries, Searc
     throw Error("search: the per-query hit counts add up to " + std::to_string(h_off[Q]) +
                 ", the hit kernel wrote " + std::to_string(H));
   r->offsets.assign(h_off, h_off + Q + 1);
+  for (u32 q = 0; q < Q; ++q) r->matches[q] = h_off[q + 1] - h_off[q];
   r->lines.assign(h_slines, h_slines + H);
   for (u64 i = 0; i < (u64)Q * kSearchMaxTerms; ++i) r->term_counts[i] = h_tlen[i];
   r->wire_bytes = ((u64)Q + 1) * sizeof(u64) + H * sizeof(u32) +
@@ -2205,9 +2261,9 @@ void DevicePipeline::search_stage(const std::vector<SearchQuery>& queries, Searc
 }
 
 SearchResult DevicePipeline::run_search(const TextInput& in,
-                                        const std::vector<SearchQuery>& queries) {
+                                        const std::vector<SearchQuery>& queries, u64 rank_k) {
   TraceRange tr("locust:search_job");
-  check_search_batch(queries);  // (a refused batch starts nothing)
+  check_search_batch(queries, rank_k);  // (a refused batch starts nothing)
   idx_resident = false;         // (until this job has left its index)
   SearchResult r;
   WordCountResult w;
@@ -2217,7 +2273,7 @@ SearchResult DevicePipeline::run_search(const TextInput& in,
   sync();
   check_index_counters(n, T);
   keep_index(in, w, n, T);
-  search_stage(queries, &r);
+  search_stage(queries, rank_k, &r);
   r.index_ms = ms_between(ev_index[0], ev_index[1]);
   r.search_ms = ms_between(ev_search[0], ev_search[1]);
   r.wire_bytes += sizeof(IndexCounters) + sizeof(MapCounters);
@@ -2231,16 +2287,17 @@ SearchResult DevicePipeline::run_search(const TextInput& in,
   return r;
 }
 
-SearchResult DevicePipeline::search_resident(const std::vector<SearchQuery>& queries) {
+SearchResult DevicePipeline::search_resident(const std::vector<SearchQuery>& queries,
+                                             u64 rank_k) {
   TraceRange tr("locust:search_resident");
-  check_search_batch(queries);
+  check_search_batch(queries, rank_k);
   if (!idx_resident)
     throw Error("search_resident: the index on the device is stale -- this engine's last job "
                 "was not a run_index or a run_search (any other job, a refused one included, "
                 "overwrites what the index reads); run one of them first");
   SearchResult r;
   const u64 t0 = now_ns();
-  search_stage(queries, &r);
+  search_stage(queries, rank_k, &r);
   r.search_ms = ms_between(ev_search[0], ev_search[1]);
   r.times.gpu_ms = r.search_ms;
   r.times.wall_ms = (now_ns() - t0) * 1e-6;

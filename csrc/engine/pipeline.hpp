@@ -810,19 +810,22 @@ struct DevicePipeline {
   char* d_shits = nullptr;
   u64 shits_bytes = 0;
   char* h_supload = nullptr;  // pinned [q_meta | keys]
-  char* h_sres = nullptr;     // pinned [SearchCounters | t_len | offsets]
-  u32* h_slines = nullptr;    // pinned answer lines
+  char* h_sres = nullptr;     // pinned [SearchCounters | t_len | offsets | q_hits (ranked)]
+  u32* h_slines = nullptr;    // pinned answer lines (ranked: the scores behind them)
   u64 h_slines_cap = 0;
   hipEvent_t ev_search[2] = {};
   void ensure_search();
   void ensure_search_hits(u64 bound);
-  // Throws unless the batch fits the device stage and every term is valid; launches nothing.
-  void check_search_batch(const std::vector<SearchQuery>& queries) const;
+  // Throws unless the batch fits the device stage, every term is valid and rank_k is 0
+  // (unranked) or an accepted K (check_search_rank); launches nothing.
+  void check_search_batch(const std::vector<SearchQuery>& queries, u64 rank_k) const;
   // The batch over idx_view on `stream`, timed by ev_search; synchronises (the bound, the
   // number of hits, the result) and fills r's lists, statistics and wire_bytes.
-  void search_stage(const std::vector<SearchQuery>& queries, SearchResult* r);
-  SearchResult run_search(const TextInput& in, const std::vector<SearchQuery>& queries);
-  SearchResult search_resident(const std::vector<SearchQuery>& queries);
+  // rank_k != 0: the ranked answer (engine.hpp "ranked search").
+  void search_stage(const std::vector<SearchQuery>& queries, u64 rank_k, SearchResult* r);
+  SearchResult run_search(const TextInput& in, const std::vector<SearchQuery>& queries,
+                          u64 rank_k);
+  SearchResult search_resident(const std::vector<SearchQuery>& queries, u64 rank_k);
 
   // ---------------------------------------------------------------------------------
   // Streaming: an input larger than the engine's text capacity is processed in

@@ -368,8 +368,35 @@ void format_index_output(const IndexResult& r, std::string* out);
 // `all` evaluation and verifies each against the text, which the engine keeps in device
 // memory beside the index.  The host evaluation (search_index) takes any number of
 // queries; for a phrase it needs the text too (the four-argument overload).
+//
+// ---- ranked search: the best K lines of every query, best first ----
+// The matching set of a query is exactly what `all` / `any` / `phrase` answer.  Ranking
+// never changes which lines match, only their order and how many are returned.
+//   N            the index's postings.size() (= num_tokens, and val[n] on the device).
+//   distinct present terms
+//                the query's terms, each cut to max_key_len bytes; a term whose cut key
+//                repeats an earlier one counts once (in `phrase` mode too, where repetition
+//                matters for matching only); a term whose word is absent contributes nothing.
+//   c_t          the term's word count (> 0 for a present term).
+//   weight(t)    bit_length(N / c_t) = 32 - clz(N / c_t), integer division: in [1, 32]
+//                because 1 <= c_t <= N < 2^32.  A rarer word weighs more.
+//   tf(t, line)  how often `line` occurs in t's postings list (one posting per occurrence;
+//                long tokens merged under truncation count together, as in the index).
+//   score(query, line)
+//                the sum over the distinct present terms of weight(t) * tf(t, line), a u32.
+// Every matching line holds at least one present term in every mode, so it scores at least 1
+// (a score of 0 for a hit is an internal error: the device counts it and the host throws).
+// A line's tf values sum to at most emits_per_line, so score <= 32 * emits_per_line; a ranked
+// search is refused when emits_per_line > kRankMaxEmits, so every accepted score is at most
+// kRankScoreMax = 2^21 and fits a 22-bit field.  An unranked search knows no such limit.
+// The answer of a query: `matches`, the number of matching lines (the unranked hit count),
+// and the first min(K, matches) matching lines in the order (score descending, line
+// ascending), each with its score.  The order is total, so the answer is unique.  K is one
+// u32 >= 1 per batch; rank_k == 0 means the unranked answer.
 constexpr u32 kSearchMaxQueries = 1024;
 constexpr u32 kSearchMaxTerms = 8;
+constexpr u64 kRankMaxEmits = 65536;
+constexpr u32 kRankScoreMax = 32u * (u32)kRankMaxEmits;  // 2^21
 enum class SearchMode { kAll, kAny, kPhrase };
 struct SearchQuery {
   std::vector<std::string> terms;
@@ -379,7 +406,12 @@ struct SearchResult {
   std::vector<SearchQuery> queries;  // as asked (terms uncut)
   std::vector<u64> offsets;          // [queries + 1]: query i's lines are lines[offsets[i] .. offsets[i+1])
   std::vector<u32> lines;            // global line numbers, per query strictly ascending
+                                     // (ranked: per query in rank order)
   std::vector<u64> term_counts;      // [queries * kSearchMaxTerms]: term t of query i at i * 8 + t
+  u64 rank_k = 0;                    // 0: unranked
+  std::vector<u32> scores;           // ranked: parallel to lines; unranked: empty
+  std::vector<u64> matches;          // [queries] matching lines (unranked: the hit counts)
+  u64 emits_per_line = 0;            // the job's (a ranked score is at most 32 * this)
   u64 first_line = 0;
   // the word job's statistics, as in TopResult
   u64 num_lines = 0;
@@ -398,21 +430,30 @@ struct SearchResult {
 PackedKey search_term_key(const std::string& term, const JobConfig& cfg);
 // Throws unless every query has 1..kSearchMaxTerms valid terms for cfg's delimiter set.
 void check_search_queries(const std::vector<SearchQuery>& queries, const JobConfig& cfg);
+// Throws unless rank_k is 0 (unranked) or a u32 >= 1 with cfg.emits_per_line <= kRankMaxEmits.
+void check_search_rank(u64 rank_k, const JobConfig& cfg);
 // The host evaluation over an index result, any number of queries (cfg: the index job's
 // delimiters and max_key_len).  Throws for a phrase query: the index holds no positions, so
 // a phrase needs the text -- the four-argument overload.
+// rank_k != 0 ranks every query (scores come from the postings alone).
 SearchResult search_index(const IndexResult& x, const std::vector<SearchQuery>& queries,
-                          const JobConfig& cfg);
+                          const JobConfig& cfg, u64 rank_k = 0);
 // The same with the text the index was built from (the same window: text.first_line ==
 // x.first_line; cfg also gives emits_per_line): a phrase's candidates come from the `all`
 // evaluation and are verified by tokenising their lines with the CPU engine's tokeniser.
 SearchResult search_index(const IndexResult& x, const TextInput& text,
-                          const std::vector<SearchQuery>& queries, const JobConfig& cfg);
+                          const std::vector<SearchQuery>& queries, const JobConfig& cfg,
+                          u64 rank_k = 0);
 // LOCUST_CHECK invariants of a search result: offsets monotone from 0 to lines.size(), every
-// query's lines strictly ascending and inside [first_line, first_line + num_lines).
+// line inside [first_line, first_line + num_lines), one `matches` per query.  Unranked: every
+// query's lines strictly ascending, matches == the hit counts, no scores.  Ranked: one score
+// per line, each in [1, 32 * emits_per_line], per query non-increasing with equal scores on
+// ascending lines, and at most min(rank_k, matches) lines per query.
 void validate_search(const SearchResult& r);
 // The result lines of a search, one per query:
 //   "print query: <terms joined by one space> \t hits: <h> \t lines: <l0> <l1> ...\n"
+// ranked (hits: the matches; nothing after "top:" when nothing matched):
+//   "print query: <terms> \t hits: <matches> \t top: <l0>:<s0> <l1>:<s1> ...\n"
 void format_search_output(const SearchResult& r, std::string* out);
 
 // Text read piece by piece (a file too large to hold): whole lines go straight into the
@@ -548,11 +589,12 @@ class GpuWordCount {
   // per-term counts and the counters cross PCIe.  run_index's refusals apply.  The text
   // stays in device memory beside the index (the engine's own copy, not the staging
   // buffer): phrase queries are verified against it.
-  SearchResult run_search(const TextInput& in, const std::vector<SearchQuery>& queries);
+  SearchResult run_search(const TextInput& in, const std::vector<SearchQuery>& queries,
+                          u64 rank_k = 0);
   // Another batch from the index this engine's last job left on the device.  That job must
   // have been a run_index or a run_search: any other job (a refused one that had started
   // to write included) marks the index stale, and this then throws.
-  SearchResult search_resident(const std::vector<SearchQuery>& queries);
+  SearchResult search_resident(const std::vector<SearchQuery>& queries, u64 rank_k = 0);
 
   const JobConfig& config() const;
   u64 token_capacity() const;
@@ -601,7 +643,8 @@ class CpuWordCount {
   IndexResult run_index(const TextInput& in);
   // run_index() + the host evaluation (search_index with the text), any size, any number
   // of queries and every mode.
-  SearchResult run_search(const TextInput& in, const std::vector<SearchQuery>& queries);
+  SearchResult run_search(const TextInput& in, const std::vector<SearchQuery>& queries,
+                          u64 rank_k = 0);
   std::vector<PackedKey> run_map_stage(const TextInput& in, WordCountResult* stats);
   WordCountResult run_reduce_stage(const PackedKey* keys, u64 n);
 

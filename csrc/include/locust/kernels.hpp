@@ -658,6 +658,22 @@ void launch_index(const IndexJob& job, IndexWorkspace& ws, SortPlan* h_plan, hip
 //   offsets  one workgroup: offsets[0 .. Q] = exclusive scan of the per-query hit counts
 //   emit     lines[j] = first_line + low32(sorted[j]); a pair outside the offsets range of
 //            the query it names counts as misplaced
+// A ranked batch (engine.hpp "ranked search"; launch_search_rank in place of
+// launch_search_order) goes on from the seal with the unsorted pairs:
+//   offsets  the same scan of the per-query hit counts (the matches, and the segments of the
+//            sorted keys), and once more over min(hits, K): out_off[0 .. Q], where each
+//            query's returned lines go.  All in u64: K = 2^32 - 1 overflows nothing
+//   score    one thread per pair: per distinct present term tf = upper bound - lower bound
+//            of the line in the term's CSR range (never outside it), weight =
+//            32 - clz(N / t_len) with N = val[n]; the pair becomes the rank key
+//            query << 54 | (kRankScoreMax - score) << 32 | rel_line in `cands`, which the
+//            phrase kernel has left.  A score of 0 or above 32 * emits_per_line counts in
+//            `unscored`
+//   order    radix_sort() of the rank keys as one-word keys: (query, score descending, line
+//            ascending); the keys are distinct
+//   top      one thread per sorted key at j: pos = j - offsets[q], the misplaced check as
+//            emit's, and when pos < K lines[out_off[q] + pos] = first_line + rel_line and
+//            scores[out_off[q] + pos] = score.  No atomics: every position is determined
 struct SearchCounters {  // zeroed per batch
   u64 bound;      // B: the elements the hit kernel walks = the upper bound on the hits
   u32 written;    // hits the hit kernel found
@@ -665,7 +681,7 @@ struct SearchCounters {  // zeroed per batch
   u32 misplaced;  // sorted pairs outside their query's range
   u32 cands;      // phrase candidates the hit kernel wrote
   u32 verified;   // phrase candidates the phrase kernel has decided
-  u32 pad;
+  u32 unscored;   // ranked: hits whose score is 0 or above 32 * emits_per_line
 };
 static_assert(sizeof(SearchCounters) <= 64, "the counters share one 64-byte block");
 constexpr int kSearchBlock = 256;
@@ -705,6 +721,8 @@ struct SearchBatch {
   u32* q_bound = nullptr;  // [Q]
   u64* q_start = nullptr;  // [Q + 1]
   u64* offsets = nullptr;  // [Q + 1]
+  u64* out_off = nullptr;  // [Q + 1] ranked: scan of min(hits, K).  The same words as q_start,
+                           // which nothing reads behind the hit kernel
 };
 // The hit arrays, sized by the batch's bound B (grown on demand).
 struct SearchHits {
@@ -717,6 +735,9 @@ struct SearchHits {
   RadixWorkspace rx{};
   u64 cap = 0;
 };
+// Ranked: the returned lines' scores [cap], parallel to h.lines, in the words of h.pairs (the
+// score kernel has turned every pair into its rank key by then).
+inline u32* search_rank_scores(const SearchHits& h) { return reinterpret_cast<u32*>(h.pairs); }
 u64 search_upload_bytes(u32 queries);  // bytes of SearchBatch::upload a batch of Q fills
 u64 search_batch_bytes();
 void search_batch_carve(char* base, SearchBatch* b);
@@ -734,6 +755,12 @@ void launch_search_hits(const SearchIndex& ix, const SearchBatch& b, u32 queries
 // read the sort's plan back through h_plan and synchronise `s` once, as radix_sort does.
 void launch_search_order(const SearchIndex& ix, const SearchBatch& b, u32 queries, u64 hits,
                          SearchHits& h, SortPlan* h_plan, hipStream_t s);
+// The ranked way from the same point (b.ctr->sort_n == hits): offsets + score + order + top.
+// b.offsets[0 .. Q] (the matches), b.out_off[0 .. Q], h.lines and search_rank_scores(h)
+// [0 .. out_off[Q]), b.ctr->misplaced and b.ctr->unscored.  1 <= k; ix.emits_per_line <=
+// kRankMaxEmits.  Synchronises as launch_search_order does.
+void launch_search_rank(const SearchIndex& ix, const SearchBatch& b, u32 queries, u64 hits,
+                        u32 k, SearchHits& h, SortPlan* h_plan, hipStream_t s);
 
 // ---- device self-test of the string library (tests only; StringTestOut in engine.hpp) ----
 void launch_string_selftest(const char* blob, const u32* off, u32 n, const char* delims,

@@ -28,6 +28,15 @@
 //    i's verdict, and the round ends in commit_hits;
 //  * order: the device-wide radix_sort() on the one-word key, as launch_index uses it;
 //  * search_emit_kernel: lines[j] = first_line + low32(sorted[j]) and the misplaced check.
+// A ranked batch (engine.hpp "ranked search") takes another way behind the seal:
+//  * search_score_kernel: one thread per hit pair, tiles of kSearchTile, grid-stride.  The
+//    line's tf in every distinct term's list is upper bound - lower bound, both confined to
+//    the list's CSR range; the weight comes from the list's length and N = val[n].  The pair
+//    becomes the rank key query << 54 | (kRankScoreMax - score) << 32 | rel_line, so the
+//    same ascending one-word sort yields (query, score descending, line ascending);
+//  * search_top_kernel: one thread per sorted key; position pos inside its query's segment
+//    (the misplaced check as the emit kernel's), and when pos < K the line and its score go
+//    to out_off[q] + pos: every output position is determined, no atomics, no compaction.
 // Data crosses between workgroups only at kernel boundaries (the radix sort keeps its own
 // look-back); this file adds no polled word.
 #include <algorithm>
@@ -104,15 +113,17 @@ __global__ __launch_bounds__(kSearchBlock) void search_lookup_kernel(
   }
 }
 
-// One workgroup: out[0 .. Q] = exclusive scan of in[0 .. Q); the total also to *total.
+// One workgroup: out[0 .. Q] = exclusive scan of min(in[0 .. Q), clip); the total also to
+// *total.
 __global__ __launch_bounds__(kSearchBlock) void search_scan_kernel(const u32* __restrict__ in,
-                                                                   u32 Q, u64* __restrict__ out,
+                                                                   u32 Q, u32 clip,
+                                                                   u64* __restrict__ out,
                                                                    u64* __restrict__ total) {
   __shared__ u64 s_scan[kSearchBlock / 64 + 1];
   u64 carry = 0;
   for (u32 base = 0; base < Q; base += kSearchBlock) {  // (workgroup-uniform)
     const u32 i = base + threadIdx.x;
-    const u64 v = i < Q ? in[i] : 0;
+    const u64 v = i < Q ? (in[i] < clip ? in[i] : clip) : 0;
     u64 tv;
     const u64 ev = dev::block_exclusive_scan<u64, kSearchBlock>(v, s_scan, &tv);
     if (i < Q) out[i] = carry + ev;
@@ -135,6 +146,38 @@ __device__ __forceinline__ bool list_has(const u32* __restrict__ p, u32 len, u32
       hi = mid;
   }
   return lo < len && p[lo] == line;
+}
+
+// How often does `line` occur among the len sorted postings at p?  (Never reads outside
+// [p, p + len).)
+__device__ __forceinline__ u32 list_tf(const u32* __restrict__ p, u32 len, u32 line) {
+  u32 lo = 0, hi = len;
+  while (lo < hi) {  // lower bound
+    const u32 mid = lo + ((hi - lo) >> 1);
+    if (p[mid] < line)
+      lo = mid + 1;
+    else
+      hi = mid;
+  }
+  const u32 first = lo;
+  if (lo == len || p[lo] != line) return 0;  // (most terms of an `any` query, on most lines)
+  // the upper bound: tf is small on most lines, so gallop from the lower bound (p[at] == line
+  // throughout), then bisect the last stride
+  u32 at = lo, step = 1;
+  while (step < len - at && p[at + step] == line) {
+    at += step;
+    if (step < (1u << 31)) step <<= 1;
+  }
+  lo = at + 1;
+  hi = step < len - at ? at + step : len;  // p[hi] > line, or the list's end
+  while (lo < hi) {
+    const u32 mid = lo + ((hi - lo) >> 1);
+    if (p[mid] <= line)
+      lo = mid + 1;
+    else
+      hi = mid;
+  }
+  return lo - first;
 }
 
 // The hits of one converged wave step (hit: this lane has one, of query q on local line
@@ -366,6 +409,86 @@ __global__ __launch_bounds__(256) void search_emit_kernel(const u64* __restrict_
   }
 }
 
+// ---- ranked search ----
+constexpr int kRankLineBits = 32, kRankScoreBits = 22;
+constexpr int kRankQueryShift = kRankLineBits + kRankScoreBits;
+constexpr u64 kRankScoreMask = (1ull << kRankScoreBits) - 1;
+static_assert(kRankScoreMax <= kRankScoreMask, "kRankScoreMax - score fits the score field");
+static_assert(kSearchMaxQueries == 1u << (64 - kRankQueryShift),
+              "the query fills the bits above the score field");
+
+// keys[e] = the rank key of pairs[e], e < H.  A hit whose score is 0 or above max_score (or
+// whose query is none of the batch) counts in ctr->unscored: the host throws.
+__global__ __launch_bounds__(kSearchBlock) void search_score_kernel(
+    const u32* __restrict__ postings, const u64* __restrict__ val, u32 n, u32 first_line,
+    const u32* __restrict__ q_info, const u64* __restrict__ t_val, const u32* __restrict__ t_len,
+    u32 Q, u32 max_score, const u64* __restrict__ pairs, u64 H, u64* __restrict__ keys,
+    SearchCounters* __restrict__ ctr) {
+  if (ctr->sort_n != (u32)H) return;  // the pairs are not all there (workgroup-uniform)
+  const u32 N = (u32)val[n];          // (the index holds < 2^32 postings in all)
+  u32 bad = 0;
+  for (u64 tile = blockIdx.x; tile * kSearchTile < H; tile += gridDim.x) {  // (uniform)
+#pragma unroll 1
+    for (int j = 0; j < kSearchItems; ++j) {
+      const u64 e = tile * kSearchTile + (u64)j * kSearchBlock + threadIdx.x;
+      if (e >= H) continue;
+      const u64 w = pairs[e];
+      const u32 q = (u32)(w >> 32), rel = (u32)w;
+      u64 score = 0;
+      if (q < Q) {
+        const u32 mask = (q_info[q] >> 16) & 0xffu;
+        const u64* tv = t_val + (u64)q * kTerms;
+        const u32* tl = t_len + (u64)q * kTerms;
+        for (u32 t = 0; t < (u32)kTerms; ++t) {
+          if (!((mask >> t) & 1u) || tl[t] == 0) continue;
+          const u32 weight = 32u - (u32)__clz((int)(N / tl[t]));  // bit_length(N / c_t)
+          score += (u64)weight * list_tf(postings + tv[t], tl[t], first_line + rel);
+        }
+      }
+      if (score < 1 || score > max_score) {
+        ++bad;
+        score = score < 1 ? 0 : kRankScoreMax;  // (any key: the host throws)
+      }
+      keys[e] = ((u64)(q & (kSearchMaxQueries - 1)) << kRankQueryShift) |
+                ((u64)(kRankScoreMax - (u32)score) << kRankLineBits) | (u64)rel;
+    }
+  }
+  const u64 bm = dev::ballot(bad != 0);
+  if (bm) {
+    bad = dev::wave_reduce_sum(bad);
+    if (dev::lane_id() == 0) atomicAdd(&ctr->unscored, bad);
+  }
+}
+
+// Sorted key j lies at position pos = j - offsets[q] of its query's segment (outside it:
+// misplaced, as the emit kernel counts); the first K of a segment go to out_off[q] + pos.
+__global__ __launch_bounds__(256) void search_top_kernel(
+    const u64* __restrict__ sorted, u64 H, const u64* __restrict__ offsets,
+    const u64* __restrict__ out_off, u32 Q, u32 K, u32 first_line, u32* __restrict__ lines,
+    u32* __restrict__ scores, SearchCounters* __restrict__ ctr) {
+  if (ctr->sort_n != (u32)H) return;  // nothing was sorted (workgroup-uniform)
+  u32 bad = 0;
+  for (u64 j = (u64)blockIdx.x * 256 + threadIdx.x; j < H; j += (u64)gridDim.x * 256) {
+    const u64 w = sorted[j];
+    const u32 q = (u32)(w >> kRankQueryShift);
+    if (q >= Q || j < offsets[q] || j >= offsets[q + 1]) {
+      ++bad;
+      continue;
+    }
+    const u64 pos = j - offsets[q];
+    if (pos < (u64)K) {  // (pos < min(hits of q, K): inside out_off[q .. q + 1])
+      const u64 o = out_off[q] + pos;
+      lines[o] = first_line + (u32)w;
+      scores[o] = kRankScoreMax - (u32)((w >> kRankLineBits) & kRankScoreMask);
+    }
+  }
+  const u64 bm = dev::ballot(bad != 0);
+  if (bm) {
+    bad = dev::wave_reduce_sum(bad);
+    if (dev::lane_id() == 0) atomicAdd(&ctr->misplaced, bad);
+  }
+}
+
 constexpr u64 kQ = kSearchMaxQueries;
 constexpr u64 kQT = kQ * kSearchMaxTerms;
 
@@ -433,6 +556,7 @@ void search_batch_carve(char* base, SearchBatch* sb) {
   sb->q_info = reinterpret_cast<u32*>(part[4]);
   sb->q_bound = reinterpret_cast<u32*>(part[5]);
   sb->q_start = reinterpret_cast<u64*>(part[6]);
+  sb->out_off = sb->q_start;  // (ranked: the hit kernel has read q_start by then)
   sb->offsets = reinterpret_cast<u64*>(part[7]);
 }
 
@@ -479,7 +603,7 @@ void launch_search_lookup(const SearchIndex& ix, const SearchBatch& b, u32 queri
   search_lookup_kernel<<<dim3(blocks), dim3(kSearchBlock), 0, s>>>(
       ix.recs, ix.n, ix.val, b.keys, b.q_meta, queries, b.t_val, b.t_len, b.q_info, b.q_bound);
   LOCUST_HIP_LAUNCH_CHECK();
-  search_scan_kernel<<<dim3(1), dim3(kSearchBlock), 0, s>>>(b.q_bound, queries, b.q_start,
+  search_scan_kernel<<<dim3(1), dim3(kSearchBlock), 0, s>>>(b.q_bound, queries, ~0u, b.q_start,
                                                             &b.ctr->bound);
   LOCUST_HIP_LAUNCH_CHECK();
 }
@@ -519,7 +643,8 @@ void launch_search_order(const SearchIndex& ix, const SearchBatch& b, u32 querie
                          SearchHits& h, SortPlan* h_plan, hipStream_t s) {
   LOCUST_CHECK_ARG(hits <= h.cap, "search: " + std::to_string(hits) +
                                       " hits exceed the workspace (" + std::to_string(h.cap) + ")");
-  search_scan_kernel<<<dim3(1), dim3(kSearchBlock), 0, s>>>(b.q_hits, queries, b.offsets, nullptr);
+  search_scan_kernel<<<dim3(1), dim3(kSearchBlock), 0, s>>>(b.q_hits, queries, ~0u, b.offsets,
+                                                            nullptr);
   LOCUST_HIP_LAUNCH_CHECK();
   if (hits == 0) return;
   ConstKeysSoA keys;
@@ -534,6 +659,42 @@ void launch_search_order(const SearchIndex& ix, const SearchBatch& b, u32 querie
   const u32 eblocks = (u32)std::min<u64>(div_up(hits, 256), 4096);
   search_emit_kernel<<<dim3(eblocks), dim3(256), 0, s>>>(h.sorted, hits, b.offsets, queries,
                                                          ix.first_line, h.lines, b.ctr);
+  LOCUST_HIP_LAUNCH_CHECK();
+}
+
+void launch_search_rank(const SearchIndex& ix, const SearchBatch& b, u32 queries, u64 hits,
+                        u32 k, SearchHits& h, SortPlan* h_plan, hipStream_t s) {
+  LOCUST_CHECK_ARG(hits <= h.cap, "search: " + std::to_string(hits) +
+                                      " hits exceed the workspace (" + std::to_string(h.cap) + ")");
+  LOCUST_CHECK_ARG(k >= 1 && ix.emits_per_line > 0 && (u64)ix.emits_per_line <= kRankMaxEmits,
+                   "search: a ranked batch takes K >= 1 and emits_per_line <= kRankMaxEmits");
+  // the segments of the sorted keys, and where each query's first min(hits, K) go
+  search_scan_kernel<<<dim3(1), dim3(kSearchBlock), 0, s>>>(b.q_hits, queries, ~0u, b.offsets,
+                                                            nullptr);
+  LOCUST_HIP_LAUNCH_CHECK();
+  search_scan_kernel<<<dim3(1), dim3(kSearchBlock), 0, s>>>(b.q_hits, queries, k, b.out_off,
+                                                            nullptr);
+  LOCUST_HIP_LAUNCH_CHECK();
+  if (hits == 0) return;
+  // the phrase kernel is done with `cands`: the rank keys go there
+  const u32 sblocks = (u32)std::min<u64>(div_up(hits, (u64)kSearchTile), (u64)kSearchMaxBlocks);
+  search_score_kernel<<<dim3(sblocks), dim3(kSearchBlock), 0, s>>>(
+      ix.postings, ix.val, ix.n, ix.first_line, b.q_info, b.t_val, b.t_len, queries,
+      32u * (u32)ix.emits_per_line, h.pairs, hits, h.cands, b.ctr);
+  LOCUST_HIP_LAUNCH_CHECK();
+  ConstKeysSoA keys;
+  KeysSoA sorted;
+  keys.w[0] = h.cands;
+  sorted.w[0] = h.sorted;
+  for (int j = 1; j < kKeyWords; ++j) {
+    keys.w[j] = h.zeros;
+    sorted.w[j] = h.spare;  // the gather's copies of the zero words
+  }
+  radix_sort(keys, &b.ctr->sort_n, hits, h.rx, nullptr, sorted, nullptr, nullptr, h_plan, s);
+  const u32 tblocks = (u32)std::min<u64>(div_up(hits, 256), 4096);
+  search_top_kernel<<<dim3(tblocks), dim3(256), 0, s>>>(h.sorted, hits, b.offsets, b.out_off,
+                                                        queries, k, ix.first_line, h.lines,
+                                                        search_rank_scores(h), b.ctr);
   LOCUST_HIP_LAUNCH_CHECK();
 }
 

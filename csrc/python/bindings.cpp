@@ -95,7 +95,7 @@ struct PyIndexResult {
   IndexResult x;
   JobConfig cfg;  // the job's delimiters and max_key_len: what search() validates terms by
   PySearchResult search(const std::vector<std::vector<std::string>>& queries,
-                        const std::vector<int>& any) const;
+                        const std::vector<int>& any, const py::object& rank) const;
   py::list entries() const { return PyResult{x.words}.entries(); }
   py::list postings() const {
     py::list out;
@@ -137,7 +137,8 @@ struct PyIndexResult {
   }
 };
 
-// A search result: per query the ascending global line numbers, and the terms' counts.
+// A search result: per query the ascending global line numbers, and the terms' counts
+// (ranked: the best lines first, and their scores).
 struct PySearchResult {
   SearchResult r;
   void check(size_t i) const {
@@ -152,6 +153,18 @@ struct PySearchResult {
   py::list hits() const {
     py::list out;
     for (size_t i = 0; i + 1 < r.offsets.size(); ++i) out.append(r.offsets[i + 1] - r.offsets[i]);
+    return out;
+  }
+  py::list scores(size_t i) const {
+    check(i);
+    py::list out;
+    if (r.rank_k)
+      for (u64 j = r.offsets[i]; j < r.offsets[i + 1]; ++j) out.append(r.scores[j]);
+    return out;
+  }
+  py::list matches() const {
+    py::list out;
+    for (const u64 m : r.matches) out.append(m);
     return out;
   }
   py::list term_counts(size_t i) const {
@@ -196,11 +209,26 @@ std::vector<SearchQuery> to_queries(const std::vector<std::vector<std::string>>&
   return out;
 }
 
+// rank: None (the unranked answer) or K >= 1 -> the engines' rank_k (0: unranked).
+u64 to_rank(const py::object& rank) {
+  if (rank.is_none()) return 0;
+  long long k = 0;
+  try {
+    k = rank.cast<long long>();
+  } catch (const py::cast_error&) {  // (not an integer, or one past 64 bits)
+  }
+  LOCUST_CHECK_ARG(k >= 1 && k < (1ll << 32),
+                   "search: rank takes None or 1 <= K < 2^32, not " +
+                       py::str(rank).cast<std::string>());
+  return (u64)k;
+}
+
 PySearchResult PyIndexResult::search(const std::vector<std::vector<std::string>>& queries,
-                                     const std::vector<int>& any) const {
+                                     const std::vector<int>& any, const py::object& rank) const {
   const std::vector<SearchQuery> q = to_queries(queries, any);
+  const u64 k = to_rank(rank);
   py::gil_scoped_release nogil;
-  return PySearchResult{search_index(x, q, cfg)};
+  return PySearchResult{search_index(x, q, cfg, k)};
 }
 
 TextInput as_input(const std::string& text, u64 first_line = 0) {
@@ -333,23 +361,28 @@ class PyGpuEngine {
   // The word job, the index and a batch of all/any queries answered on the device.
   PySearchResult run_search(const std::string& text,
                             const std::vector<std::vector<std::string>>& queries,
-                            const std::vector<int>& any, u64 first_line) {
+                            const std::vector<int>& any, u64 first_line,
+                            const py::object& rank) {
     const std::vector<SearchQuery> q = to_queries(queries, any);
+    const u64 k = to_rank(rank);
     py::gil_scoped_release nogil;
-    return PySearchResult{eng_.run_search(as_input(text, first_line), q)};
+    return PySearchResult{eng_.run_search(as_input(text, first_line), q, k)};
   }
   PySearchResult run_search_text(const HostText& t,
                                  const std::vector<std::vector<std::string>>& queries,
-                                 const std::vector<int>& any, u64 first_line) {
+                                 const std::vector<int>& any, u64 first_line,
+                                 const py::object& rank) {
     const std::vector<SearchQuery> q = to_queries(queries, any);
+    const u64 k = to_rank(rank);
     py::gil_scoped_release nogil;
-    return PySearchResult{eng_.run_search(t.input(first_line), q)};
+    return PySearchResult{eng_.run_search(t.input(first_line), q, k)};
   }
   PySearchResult search_resident(const std::vector<std::vector<std::string>>& queries,
-                                 const std::vector<int>& any) {
+                                 const std::vector<int>& any, const py::object& rank) {
     const std::vector<SearchQuery> q = to_queries(queries, any);
+    const u64 k = to_rank(rank);
     py::gil_scoped_release nogil;
-    return PySearchResult{eng_.search_resident(q)};
+    return PySearchResult{eng_.search_resident(q, k)};
   }
   // records: (key bytes, count), sorted by key with distinct keys -- the kernels alone.
   PyTopResult top_counts(const std::vector<std::pair<std::string, u64>>& records, u32 k) {
@@ -760,6 +793,7 @@ PYBIND11_MODULE(_locust, m) {
       .def("postings_bytes", &PyIndexResult::postings_bytes)
       .def("lines", &PyIndexResult::lines, py::arg("key"), py::arg("unique") = false)
       .def("_search", &PyIndexResult::search, py::arg("queries"), py::arg("any"),
+           py::arg("rank") = py::none(),
            "The host evaluation of all/any queries (any[i]: query i's mode) over this index.")
       .def("times", &PyIndexResult::times)
       .def("format", &PyIndexResult::format)
@@ -778,6 +812,12 @@ PYBIND11_MODULE(_locust, m) {
       .def("lines", &PySearchResult::lines, py::arg("i"))
       .def("hits", &PySearchResult::hits, "the number of lines of every query")
       .def("term_counts", &PySearchResult::term_counts, py::arg("i"))
+      .def("scores", &PySearchResult::scores, py::arg("i"),
+           "ranked: the scores of lines(i), in the same order; unranked: empty")
+      .def("matches", &PySearchResult::matches,
+           "the number of matching lines of every query (unranked: hits())")
+      .def_property_readonly("rank_k", [](const PySearchResult& p) { return p.r.rank_k; },
+                             "the batch's K; 0: unranked")
       .def("times", &PySearchResult::times)
       .def("format", &PySearchResult::format)
       .def_property_readonly("queries", [](const PySearchResult& p) { return p.r.queries.size(); })
@@ -795,6 +835,7 @@ PYBIND11_MODULE(_locust, m) {
                              "bytes the device wrote to host memory for the result");
   m.attr("kSearchMaxQueries") = kSearchMaxQueries;
   m.attr("kSearchMaxTerms") = kSearchMaxTerms;
+  m.attr("kRankMaxEmits") = kRankMaxEmits;
   m.attr("kTopKMax") = kTopKMax;
   m.attr("kMaxNgram") = kMaxNgram;
   m.attr("kTopKTile") = kTopKTile;
@@ -832,11 +873,12 @@ PYBIND11_MODULE(_locust, m) {
       .def("run_index_text", &PyGpuEngine::run_index_text, py::arg("text"),
            py::arg("first_line") = 0)
       .def("run_search", &PyGpuEngine::run_search, py::arg("text"), py::arg("queries"),
-           py::arg("any"), py::arg("first_line") = 0,
+           py::arg("any"), py::arg("first_line") = 0, py::arg("rank") = py::none(),
            "WordCount of text, its index, and all/any queries answered on the device.")
       .def("run_search_text", &PyGpuEngine::run_search_text, py::arg("text"), py::arg("queries"),
-           py::arg("any"), py::arg("first_line") = 0)
+           py::arg("any"), py::arg("first_line") = 0, py::arg("rank") = py::none())
       .def("search_resident", &PyGpuEngine::search_resident, py::arg("queries"), py::arg("any"),
+           py::arg("rank") = py::none(),
            "Another batch from the index the last run_index / run_search left on the device.")
       .def("top_counts", &PyGpuEngine::top_counts, py::arg("records"), py::arg("k"),
            "The selection kernels alone over key-sorted (key, count) records.")
@@ -856,11 +898,13 @@ PYBIND11_MODULE(_locust, m) {
   }, py::arg("cfg"), py::arg("text"), py::arg("first_line") = 0);
   m.def("cpu_run_search", [](const JobConfig& cfg, const std::string& text,
                              const std::vector<std::vector<std::string>>& queries,
-                             const std::vector<int>& any, u64 first_line) {
+                             const std::vector<int>& any, u64 first_line,
+                             const py::object& rank) {
     CpuWordCount eng(cfg);
-    return PySearchResult{eng.run_search(as_input(text, first_line), to_queries(queries, any))};
+    return PySearchResult{
+        eng.run_search(as_input(text, first_line), to_queries(queries, any), to_rank(rank))};
   }, py::arg("cfg"), py::arg("text"), py::arg("queries"), py::arg("any"),
-        py::arg("first_line") = 0);
+        py::arg("first_line") = 0, py::arg("rank") = py::none());
   m.def("cpu_map_stage", [](const JobConfig& cfg, const std::string& text) {
     CpuWordCount eng(cfg);
     std::vector<py::bytes> out;

@@ -31,13 +31,13 @@ def _search_args(queries, mode):
     return queries, [_SEARCH_MODES[m] for m in modes]
 
 
-def _index_search(self, queries, mode="all"):
+def _index_search(self, queries, mode="all", rank=None):
     """All/any word queries over this index, evaluated on the host (``SearchResult``):
-    ``queries`` and ``mode`` as ``Engine.run_search`` takes them, any number of queries.
-    A ``"phrase"`` query is refused: the index holds no positions, so a phrase needs the
-    text (``Engine.run_search``, ``search_text``)."""
+    ``queries``, ``mode`` and ``rank`` as ``Engine.run_search`` takes them, any number of
+    queries.  A ``"phrase"`` query is refused: the index holds no positions, so a phrase
+    needs the text (``Engine.run_search``, ``search_text``)."""
     queries, flags = _search_args(queries, mode)
-    return self._search(queries, flags)
+    return self._search(queries, flags, rank)
 
 
 _C.IndexResult.search = _index_search
@@ -79,7 +79,7 @@ class Engine:
             return _C.cpu_run_index(self.cfg, text, first_line)
         return self._eng.run_index(text, first_line)
 
-    def run_search(self, text: bytes, queries, mode="all", first_line: int = 0):
+    def run_search(self, text: bytes, queries, mode="all", first_line: int = 0, rank=None):
         """WordCount of ``text``, its inverted index, and a batch of word queries answered
         from it (``SearchResult``).  ``queries`` is a list of term lists (1 to 8 byte-string
         terms each); ``mode`` is ``"all"`` (lines that hold every term), ``"any"`` (lines
@@ -90,21 +90,29 @@ class Engine:
         device memory and only the answers cross PCIe (at most ``_C.kSearchMaxQueries``
         queries per batch; ``run_index(text).search(...)`` evaluates any number of all/any
         queries on the host).  A phrase is verified on the device against the engine's own
-        copy of the text; the CPU engine answers phrases of any size."""
+        copy of the text; the CPU engine answers phrases of any size.
+
+        ``rank=K`` (``K >= 1``, one per batch) answers every query's best ``K`` lines, best
+        first (``oracle.rank`` states the score): ``lines(i)`` are in the order (score
+        descending, line ascending), ``scores(i)`` are their scores and ``matches()`` counts
+        every query's matching lines, of which ``min(K, matches)`` are returned.  On the GPU
+        the lines are scored and selected on the device and only the winners cross PCIe.
+        ``rank=None`` is the unranked answer (``scores(i)`` empty, ``matches() == hits()``)."""
         queries, flags = _search_args(queries, mode)
         if self.cpu:
-            return _C.cpu_run_search(self.cfg, text, queries, flags, first_line)
-        return self._eng.run_search(text, queries, flags, first_line)
+            return _C.cpu_run_search(self.cfg, text, queries, flags, first_line, rank)
+        return self._eng.run_search(text, queries, flags, first_line, rank)
 
-    def search_resident(self, queries, mode="all"):
+    def search_resident(self, queries, mode="all", rank=None):
         """Another batch from the index this engine's last job left on the device; that
         job must have been a ``run_index`` or a ``run_search`` (GPU engines only).  Every
-        mode of ``run_search``: the job's text is resident too, so phrases are answered."""
+        mode of ``run_search``: the job's text is resident too, so phrases are answered.
+        ``rank`` as ``run_search`` takes it."""
         if self.cpu:
             raise _C.LocustError("search_resident needs a GPU engine: the CPU engine keeps "
                                  "no index (use run_index(text).search(...))")
         queries, flags = _search_args(queries, mode)
-        return self._eng.search_resident(queries, flags)
+        return self._eng.search_resident(queries, flags, rank)
 
     def top_counts(self, records: list[tuple[bytes, int]], k: int):
         """The selection alone over (key, count) records sorted by key with distinct
@@ -199,22 +207,23 @@ def index_file(path: str, line_start: int = -1, line_end: int = -1, backend: str
 
 
 def search_text(text: bytes, queries, mode="all", backend: str = "gpu", cfg=None,
-                first_line: int = 0, **kw):
+                first_line: int = 0, rank=None, **kw):
     """All/any/phrase word queries over ``text`` (``SearchResult``); see
     ``Engine.run_search``."""
     cfg = cfg if cfg is not None else make_config(backend, **kw)
     nlines = text.count(b"\n") + (1 if text and not text.endswith(b"\n") else 0)
     return Engine(cfg, max(len(text), 1), max(nlines, 1)).run_search(text, queries, mode,
-                                                                      first_line)
+                                                                      first_line, rank)
 
 
 def search_file(path: str, queries, mode="all", line_start: int = -1, line_end: int = -1,
-                backend: str = "gpu", cfg=None, **kw):
+                backend: str = "gpu", cfg=None, rank=None, **kw):
     """All/any/phrase word queries over a file or its line window, answered with the file's
     own (global) line numbers."""
     cfg = cfg if cfg is not None else make_config(backend, **kw)
     text, nlines, first, _total = _C.load_lines(path, line_start, line_end, cfg.ref_compat)
-    return Engine(cfg, max(len(text), 1), max(nlines, 1)).run_search(text, queries, mode, first)
+    return Engine(cfg, max(len(text), 1), max(nlines, 1)).run_search(text, queries, mode, first,
+                                                                      rank)
 
 
 def map_stage(path: str, spill: str, line_start: int = -1, line_end: int = -1,

@@ -217,6 +217,49 @@ def format_search(queries, answers) -> bytes:
         for q, a in zip(queries, answers))
 
 
+RANK_MAX_EMITS = 65536
+
+
+def rank(entries, postings, lines, terms, k: int, max_key: int = 29):
+    """The ranked answer of one query: ``(top, matches)``.
+
+    ``lines`` is the query's matching set, as ``search`` or ``phrase`` answered it; ranking
+    never changes which lines match, only their order and how many are returned.  N is
+    ``len(postings)``.  The distinct present terms are the ``terms``, each cut to
+    ``max_key`` bytes, a repeated cut key counted once and an absent word left out.  A
+    term's weight is ``bit_length(N // c)`` with ``c`` its word's count (a rarer word weighs
+    more); ``tf`` is how often the line occurs in the term's postings list; a line's score
+    is the sum of ``weight * tf`` over the distinct present terms.  ``top`` is the first
+    ``min(k, matches)`` matching lines in the order (score descending, line ascending) as
+    ``(line, score)`` pairs, ``matches`` is ``len(lines)``.  ``k >= 1``."""
+    if k < 1:
+        raise ValueError("rank takes k >= 1")
+    n = len(postings)
+    by_key = {key: (v, c) for key, v, c in entries}
+    lists = []
+    seen = set()
+    for t in terms:
+        key = t[:max_key]
+        if key in seen or key not in by_key:
+            continue
+        seen.add(key)
+        v, c = by_key[key]
+        lists.append(((n // c).bit_length(), list(postings[v:v + c])))
+    scored = [(sum(w * l.count(line) for w, l in lists), line) for line in lines]
+    scored.sort(key=lambda sl: (-sl[0], sl[1]))
+    return [(line, score) for score, line in scored[:k]], len(lines)
+
+
+def format_ranked(queries, tops, matches) -> bytes:
+    """The CLI's ``--search ... --rank K`` result lines: one per query, ``queries[i]`` its
+    terms, ``tops[i]`` its ``(line, score)`` pairs and ``matches[i]`` its number of matching
+    lines (nothing after "top:" when nothing matched)."""
+    return b"".join(
+        b"print query: %s \t hits: %d \t top:%s\n"
+        % (b" ".join(q), m, b"".join(b" %d:%d" % (l, s) for l, s in t))
+        for q, t, m in zip(queries, tops, matches))
+
+
 def format_gpu(entries) -> bytes:
     """The reference GPU build's result lines (main.cu:132)."""
     return b"".join(b"print key: %s \t val: %d \t count: %d\n" % (k, v, c) for k, v, c in entries)

@@ -21,6 +21,7 @@
 //     or the words as consecutive tokens in that order; repeat --search for a batch:
 //     answered from the index on the device, or by --backend cpu)
 //   --rank K (with --search: each query's K best lines with their scores, best first)
+//   --wildcard (with --search: a word that ends in * is a prefix term, "ham*")
 // and a synthetic-text generator (BASELINE configs "1M lines" / "10 GB"):
 //   MapReduce --gen FILE (--gen-lines N | --gen-bytes N) [--seed S] [--vocab V]
 #include <sys/stat.h>
@@ -92,6 +93,7 @@ struct CliArgs {
   std::string match;  // --match all|any|phrase ("": all)
   bool rank_given = false;
   u64 rank = 0;  // --rank K: every query answers its K best lines, scored (0: all its lines)
+  bool wildcard = false;  // --wildcard: a --search word that ends in * is a prefix term
   std::string gen_out;  // generator mode
   GenSpec gen;
 };
@@ -142,6 +144,10 @@ void help() {
       "                             query, its occurrences on the line times a weight that grows\n"
       "                             with the word's rarity.  Scored and selected on the device on\n"
       "                             one GPU, or by --backend cpu; K >= 1)\n"
+      "  --wildcard                 (--search: a word that ends in * stands for every word that\n"
+      "                             starts with what precedes the star, \"ham*\": it counts as\n"
+      "                             one word whose lines are all of theirs.  A lone * is refused,\n"
+      "                             a * anywhere else is literal.  With every --match and --rank)\n"
       "  --help\n"
       "\n"
       "Environment: LOCUST_LOG=info|debug and the LOCUST_* switches in docs/ENVIRONMENT.md.\n",
@@ -268,6 +274,8 @@ bool parse(int argc, char** argv, CliArgs* a) {
       a->match = need("--match");
       if (a->match != "all" && a->match != "any" && a->match != "phrase")
         throw Error("--match takes all, any or phrase (how --search combines its words)");
+    } else if (s == "--wildcard") {
+      a->wildcard = true;
     } else if (s == "--rank") {
       const std::string v = need("--rank");
       char* endp = nullptr;
@@ -336,6 +344,8 @@ bool parse(int argc, char** argv, CliArgs* a) {
     throw Error("--match selects how --search combines its words: give --search too");
   if (a->rank_given && a->search_args.empty())
     throw Error("--rank K selects the best lines of a --search query: give --search too");
+  if (a->wildcard && a->search_args.empty())
+    throw Error("--wildcard selects how --search reads a word that ends in *: give --search too");
   if (a->index && !a->search_args.empty())
     throw Error("--index and --search do not combine: --index prints the whole index, "
                 "--search the lines of its queries");
@@ -364,22 +374,22 @@ bool parse(int argc, char** argv, CliArgs* a) {
   }
   // the --search arguments, split with the job's own delimiter set: no term can be invalid
   for (const std::string& arg : a->search_args) {
-    SearchQuery q;
-    q.mode = a->match == "any"      ? SearchMode::kAny
-             : a->match == "phrase" ? SearchMode::kPhrase
-                                    : SearchMode::kAll;
+    std::vector<std::string> terms;
+    const SearchMode mode = a->match == "any"      ? SearchMode::kAny
+                            : a->match == "phrase" ? SearchMode::kPhrase
+                                                   : SearchMode::kAll;
     std::string cur;
     for (const char c : arg) {
       if (a->cfg.delimiters.find(c) != std::string::npos) {
-        if (!cur.empty()) q.terms.push_back(cur);
+        if (!cur.empty()) terms.push_back(cur);
         cur.clear();
       } else {
         cur.push_back(c);
       }
     }
-    if (!cur.empty()) q.terms.push_back(cur);
-    if (q.terms.empty()) throw Error("--search \"" + arg + "\" holds no word");
-    a->queries.push_back(q);
+    if (!cur.empty()) terms.push_back(cur);
+    if (terms.empty()) throw Error("--search \"" + arg + "\" holds no word");
+    a->queries.push_back(make_search_query(terms, mode, a->wildcard));
   }
   if (!a->queries.empty()) {
     check_search_queries(a->queries, a->cfg);

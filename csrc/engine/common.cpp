@@ -379,6 +379,28 @@ PackedKey search_term_key(const std::string& term, const JobConfig& cfg) {
   return k;
 }
 
+SearchQuery make_search_query(const std::vector<std::string>& terms, SearchMode mode,
+                              bool wildcard) {
+  SearchQuery q;
+  q.terms = terms;
+  q.mode = mode;
+  if (!wildcard) return q;
+  bool any = false;
+  std::vector<u8> prefix(terms.size(), 0);
+  for (size_t t = 0; t < terms.size(); ++t) {
+    std::string& s = q.terms[t];
+    LOCUST_CHECK_ARG(s != "*", "search: a lone * is no prefix term: give the prefix before "
+                               "the star (ham*)");
+    if (s.size() > 1 && s.back() == '*') {
+      s.pop_back();
+      prefix[t] = 1;
+      any = true;
+    }
+  }
+  if (any) q.prefix = std::move(prefix);
+  return q;
+}
+
 void check_search_queries(const std::vector<SearchQuery>& queries, const JobConfig& cfg) {
   for (size_t i = 0; i < queries.size(); ++i) {
     const SearchQuery& q = queries[i];
@@ -386,6 +408,10 @@ void check_search_queries(const std::vector<SearchQuery>& queries, const JobConf
                      "search: query " + std::to_string(i) + " has " +
                          std::to_string(q.terms.size()) + " terms; a query takes 1 to " +
                          std::to_string(kSearchMaxTerms));
+    LOCUST_CHECK_ARG(q.prefix.empty() || q.prefix.size() == q.terms.size(),
+                     "search: query " + std::to_string(i) + " has " +
+                         std::to_string(q.prefix.size()) + " prefix flags for " +
+                         std::to_string(q.terms.size()) + " terms; give none or one per term");
     for (const std::string& t : q.terms) {
       LOCUST_CHECK_ARG(!t.empty(), "search: query " + std::to_string(i) + " has an empty term");
       for (const char ch : t) {
@@ -397,6 +423,14 @@ void check_search_queries(const std::vector<SearchQuery>& queries, const JobConf
       }
     }
   }
+}
+
+void check_search_merge(u64 queries, u64 elements) {
+  if (elements >= (1ull << 32))
+    throw Error("search: the prefix terms of the batch's " + std::to_string(queries) +
+                " queries merge " + std::to_string(elements) +
+                " list elements, which does not fit the 32-bit sort counter (2^32): split "
+                "the batch");
 }
 
 void check_search_rank(u64 rank_k, const JobConfig& cfg) {
@@ -412,14 +446,23 @@ void check_search_rank(u64 rank_k, const JobConfig& cfg) {
 namespace {
 
 // Do the first emits_per_line tokens of the line hold the keys as consecutive tokens?
+// masks: empty, or per key and word the bytes a token must share with it (a prefix term:
+// key_word_mask of its words; a plain term: every byte).
 bool line_has_phrase(const char* line, u64 len, const std::vector<PackedKey>& keys,
-                     const JobConfig& cfg, std::vector<PackedKey>* toks) {
+                     const std::vector<PackedKey>& masks, const JobConfig& cfg,
+                     std::vector<PackedKey>* toks) {
   toks->clear();
   tokenize_line(line, len, cfg, toks, nullptr);
   const size_t m = keys.size();
+  const auto eq = [&](const PackedKey& tok, size_t j) {
+    if (masks.empty()) return key_compare(tok.w, keys[j].w) == 0;
+    bool same = true;
+    for (int i = 0; i < kKeyWords; ++i) same &= (tok.w[i] & masks[j].w[i]) == keys[j].w[i];
+    return same;
+  };
   for (size_t o = 0; o + m <= toks->size(); ++o) {
     size_t j = 0;
-    while (j < m && key_compare((*toks)[o + j].w, keys[j].w) == 0) ++j;
+    while (j < m && eq((*toks)[o + j], j)) ++j;
     if (j == m) return true;
   }
   return false;
@@ -477,33 +520,70 @@ SearchResult search_index_impl(const IndexResult& x, const TextInput* text,
   struct List {
     const u32* p;
     u64 len;
+    size_t lo, hi;  // the key range [lo, hi) of its words
   };
   std::vector<std::pair<u32, u32>> ranked;  // (score, line) of one query's matching lines
   for (size_t qi = 0; qi < queries.size(); ++qi) {
     const SearchQuery& q = queries[qi];
     const size_t from = r.lines.size();
-    std::vector<List> lists;  // the distinct present terms
-    bool absent = false;
+    std::vector<List> lists;  // the present terms of distinct key ranges
+    std::vector<std::vector<u32>> own;  // the merged lists of this query's prefix terms
+    bool absent = false, wild = false;
     for (size_t t = 0; t < q.terms.size(); ++t) {
       const PackedKey k = search_term_key(q.terms[t], cfg);
-      const WordCountEntry* e = std::lower_bound(
-          ent, ent + n, k,
-          [](const WordCountEntry& a, const PackedKey& b) { return key_compare(a.key.w, b.w) < 0; });
-      if (e == ent + n || key_compare(e->key.w, k.w) != 0) {
+      const auto less = [](const WordCountEntry& a, const PackedKey& b) {
+        return key_compare(a.key.w, b.w) < 0;
+      };
+      const size_t lo = (size_t)(std::lower_bound(ent, ent + n, k, less) - ent);
+      size_t hi = lo;
+      if (search_term_prefix(q, t, cfg)) {  // the keys from p padded with 0x00 to p with 0xff
+        wild = true;
+        PackedKey top;
+        for (int j = 0; j < kKeyWords; ++j) top.w[j] = k.w[j] | ~key_word_mask(k.w[j]);
+        hi = (size_t)(std::upper_bound(ent, ent + n, top,
+                                       [](const PackedKey& b, const WordCountEntry& a) {
+                                         return key_compare(b.w, a.key.w) < 0;
+                                       }) -
+                      ent);
+      } else if (lo < n && key_compare(ent[lo].key.w, k.w) == 0) {
+        hi = lo + 1;
+      }
+      if (hi <= lo) {
         absent = true;
         continue;
       }
-      r.term_counts[qi * kSearchMaxTerms + t] = e->count;
-      const List l{x.postings.data() + val[e - ent], e->count};
+      r.term_counts[qi * kSearchMaxTerms + t] = val[hi] - val[lo];
       bool dup = false;
-      for (const List& o : lists) dup |= o.p == l.p;
-      if (!dup) lists.push_back(l);
+      for (const List& o : lists) dup |= o.lo == lo && o.hi == hi;
+      if (dup) continue;
+      List l{x.postings.data() + val[lo], val[hi] - val[lo], lo, hi};
+      if (hi - lo >= 2) {  // a concatenation of sorted lists: merge
+        own.emplace_back(l.p, l.p + l.len);
+        std::sort(own.back().begin(), own.back().end());
+        l.p = own.back().data();
+      }
+      lists.push_back(l);
+    }
+    // the score's terms: none whose key range lies inside another's (equal ranges are one
+    // list here already)
+    std::vector<List> scored;
+    for (const List& l : lists) {
+      bool inside = false;
+      for (const List& o : lists) inside |= &o != &l && o.lo <= l.lo && l.hi <= o.hi;
+      if (!inside) scored.push_back(l);
     }
     if (q.mode != SearchMode::kAny) {
       const bool phrase = q.mode == SearchMode::kPhrase && q.terms.size() >= 2;
-      std::vector<PackedKey> keys, toks;
+      std::vector<PackedKey> keys, masks, toks;
       if (phrase)
-        for (const std::string& t : q.terms) keys.push_back(search_term_key(t, cfg));
+        for (size_t t = 0; t < q.terms.size(); ++t) {
+          keys.push_back(search_term_key(q.terms[t], cfg));
+          if (!wild) continue;
+          PackedKey m;
+          for (int j = 0; j < kKeyWords; ++j)
+            m.w[j] = search_term_prefix(q, t, cfg) ? key_word_mask(keys.back().w[j]) : ~0ull;
+          masks.push_back(m);
+        }
       if (!absent && !lists.empty()) {
         size_t d = 0;
         for (size_t i = 1; i < lists.size(); ++i)
@@ -519,7 +599,7 @@ SearchResult search_index_impl(const IndexResult& x, const TextInput* text,
             LOCUST_CHECK_ARG(l + 1 < line_at.size(),
                              "search: the text has fewer lines than the index names");
             hit = line_has_phrase(text->data + line_at[l], line_at[l + 1] - 1 - line_at[l], keys,
-                                  cfg, &toks);
+                                  masks, cfg, &toks);
           }
           if (hit) r.lines.push_back(line);
         }
@@ -537,7 +617,7 @@ SearchResult search_index_impl(const IndexResult& x, const TextInput* text,
       for (size_t j = from; j < r.lines.size(); ++j) {
         const u32 line = r.lines[j];
         u64 score = 0;
-        for (const List& l : lists) {
+        for (const List& l : scored) {
           const auto eq = std::equal_range(l.p, l.p + l.len, line);
           const u64 w = N / l.len;  // (>= 1: a list is part of the postings)
           score += (u64)(64 - __builtin_clzll(w)) * (u64)(eq.second - eq.first);
@@ -625,9 +705,10 @@ void format_search_output(const SearchResult& r, std::string* out) {
   out->reserve(out->size() + r.queries.size() * 48 + r.lines.size() * 6);
   for (size_t q = 0; q < r.queries.size(); ++q) {
     out->append("print query:");
-    for (const std::string& t : r.queries[q].terms) {
+    for (size_t t = 0; t < r.queries[q].terms.size(); ++t) {
       out->push_back(' ');
-      out->append(t);
+      out->append(r.queries[q].terms[t]);
+      if (r.queries[q].is_prefix(t)) out->push_back('*');
     }
     out->append(" \t hits: ");
     out->append(std::to_string(r.rank_k ? r.matches[q] : r.offsets[q + 1] - r.offsets[q]));

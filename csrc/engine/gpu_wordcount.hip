@@ -68,7 +68,8 @@ GpuWordCount::Stats GpuWordCount::stats() const {
   s.streaming = impl_->streaming;
   s.chunk_bytes = impl_->cap_bytes;
   s.map_window = impl_->map_window;
-  s.search_bytes = impl_->sbatch_bytes + impl_->shits_bytes;
+  s.search_bytes = impl_->sbatch_bytes + impl_->shits_bytes +
+                   impl_->sbatch.merged_cap * sizeof(u32);
   return s;
 }
 

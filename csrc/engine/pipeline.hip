@@ -264,6 +264,7 @@ u64 DevicePipeline::device_bytes() const {
   b += topk_bytes;                   // (0 until the first top job)
   b += index_bytes;                  // (0 until the first index job)
   b += sbatch_bytes + shits_bytes;   // (0 until the first search job)
+  b += sbatch.merged_cap * sizeof(u32);  // (0 until a batch merges a prefix term's lists)
   return b;
 }
 
@@ -555,6 +556,7 @@ DevicePipeline::~DevicePipeline() {
     if (e) (void)hipEventDestroy(e);
   if (d_sbatch) (void)hipFree(d_sbatch);
   if (d_shits) (void)hipFree(d_shits);
+  if (d_smerged) (void)hipFree(d_smerged);
   pinned_free(h_supload);
   pinned_free(h_sres);
   pinned_free(h_slines);
@@ -2098,6 +2100,27 @@ void DevicePipeline::ensure_search_hits(u64 bound) {
   LOCUST_HIP_CHECK(hipMemsetAsync(shits.zeros, 0, cap * 8, stream));
 }
 
+void DevicePipeline::ensure_search_merged(u64 elements) {
+  if (sbatch.merged_cap >= elements) return;
+  sync();  // nothing in flight may still read the lists being replaced
+  if (d_smerged) LOCUST_HIP_CHECK(hipFree(d_smerged));
+  d_smerged = nullptr;
+  sbatch.merged = nullptr;
+  sbatch.merged_cap = 0;
+  const u64 cap = align_up(elements, (u64)kSortTile);
+  const u64 bytes = cap * sizeof(u32);
+  size_t fr = 0, tot = 0;
+  LOCUST_HIP_CHECK(hipMemGetInfo(&fr, &tot));
+  if ((double)bytes > kHbmUsable * (double)fr)
+    throw Error("search workspace (" + std::to_string(bytes) + " B needed for the " +
+                std::to_string(elements) + " list elements the batch's prefix terms merge) "
+                "does not fit the free device memory (" + std::to_string(fr) + " B free of " +
+                std::to_string(tot) + " B): split the batch");
+  LOCUST_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&d_smerged), bytes));
+  sbatch.merged = d_smerged;
+  sbatch.merged_cap = cap;
+}
+
 void DevicePipeline::check_search_batch(const std::vector<SearchQuery>& queries,
                                         u64 rank_k) const {
   LOCUST_CHECK_ARG(queries.size() <= (size_t)kSearchMaxQueries,
@@ -2145,6 +2168,8 @@ void DevicePipeline::search_stage(const std::vector<SearchQuery>& queries, u64 r
                                                                        : 0u);
     verify |= sq.mode == SearchMode::kPhrase && sq.terms.size() >= 2;
     for (size_t t = 0; t < sq.terms.size(); ++t) {
+      // a prefix term's flag; its length needs no word: the key's non-zero bytes are it
+      if (search_term_prefix(sq, t, cfg)) meta[q] |= 1u << (kSearchPrefixShift + (int)t);
       const PackedKey k = search_term_key(sq.terms[t], cfg);
       std::memcpy(keys + ((u64)q * kSearchMaxTerms + t) * kKeyWords, k.w, sizeof(PackedKey));
     }
@@ -2166,7 +2191,17 @@ void DevicePipeline::search_stage(const std::vector<SearchQuery>& queries, u64 r
     throw Error("search: the batch's " + std::to_string(Q) + " queries walk " + std::to_string(B) +
                 " list elements, which does not fit the 32-bit slot counter (2^32): split "
                 "the batch");
-  ensure_search_hits(B);
+  // X: the list elements of the prefix terms that cover two or more words (0: no such term,
+  // and nothing below differs from a batch without prefix terms)
+  const u64 X = h_sc->merge;
+  check_search_merge(Q, X);
+  ensure_search_hits(std::max(B, X));  // (the expand stage's scratch: idle until the hits)
+  if (X) {
+    // expand: the merged lists, which the hit, phrase and score kernels read as any list
+    ensure_search_merged(X);
+    launch_search_expand(idx_view, sbatch, Q, X, shits, h_plan, stream);
+  }
+  r->merged = X;
   // hits; a phrase's candidates are verified against the resident text behind them
   launch_search_hits(idx_view, sbatch, Q, B, verify, shits, stream);
   LOCUST_HIP_CHECK(hipMemcpyAsync(h_sc, sbatch.ctr, sizeof(SearchCounters), hipMemcpyDeviceToHost,
@@ -2177,6 +2212,10 @@ void DevicePipeline::search_stage(const std::vector<SearchQuery>& queries, u64 r
                                     hipMemcpyDeviceToHost, stream));
   sync();
   const u64 H = h_sc->written, C = h_sc->cands;
+  if (h_sc->merge_n != (u32)X || h_sc->unmerged)
+    throw Error("search: " + std::to_string(h_sc->merge_n) + " of " + std::to_string(X) +
+                " list elements of prefix terms merged, " + std::to_string(h_sc->unmerged) +
+                " of them outside their term's range");
   if (H > B || h_sc->sort_n != H)
     throw Error("search: " + std::to_string(H) + " hits written, the lists hold " +
                 std::to_string(B) + " elements");

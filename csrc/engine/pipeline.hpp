@@ -816,6 +816,10 @@ struct DevicePipeline {
   hipEvent_t ev_search[2] = {};
   void ensure_search();
   void ensure_search_hits(u64 bound);
+  // The merged lists of a batch's prefix terms (sbatch.merged, sbatch.merged_cap): made by
+  // the first batch that merges any, grown on demand.
+  u32* d_smerged = nullptr;
+  void ensure_search_merged(u64 elements);
   // Throws unless the batch fits the device stage, every term is valid and rank_k is 0
   // (unranked) or an accepted K (check_search_rank); launches nothing.
   void check_search_batch(const std::vector<SearchQuery>& queries, u64 rank_k) const;

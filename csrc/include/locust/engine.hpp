@@ -393,6 +393,34 @@ void format_index_output(const IndexResult& r, std::string* out);
 // and the first min(K, matches) matching lines in the order (score descending, line
 // ascending), each with its score.  The order is total, so the answer is unique.  K is one
 // u32 >= 1 per batch; rank_k == 0 means the unranked answer.
+//
+// ---- prefix terms: `ham*` ----
+// A term of a query may be a prefix term with prefix p (SearchQuery::prefix[t] != 0, terms[t]
+// holding p without the star).  p is non-empty, validated exactly as a term is and cut to
+// max_key_len bytes as a term is.  Its words are the index keys k with k[:len(p)] == p, a
+// word equal to p among them: the keys are in unsigned-byte order, so they are one
+// contiguous rank range [lo, hi), and their postings one contiguous range of the CSR.  Its
+// list is the multiset union of those words' postings, non-decreasing; its count, as
+// reported in term_counts, is the sum of their counts.  If no word matches, the term is
+// absent.  If len(p) == max_key_len (after the cut), it is exactly the plain term p.
+// In `all`, `any` and the candidate stage of `phrase`, a prefix term behaves as a word with
+// that list.  In `phrase` verification a token matches a prefix term when the token's key
+// (cut to max_key_len) starts with p; a token shorter than p does not match.
+// Ranked: a prefix term's c_t is its merged count (the weight still bit_length(N / c_t), in
+// [1, 32]) and its tf the line's multiplicity in the merged list.  Prefix ranges and single
+// words form a laminar family: two terms' key ranges are nested or disjoint.  A present
+// term whose key range lies inside the range of another present term of the same query
+// contributes nothing to the score; of equal ranges the first occurrence counts (for plain
+// terms this is "a repeated key counts once").  The remaining terms have disjoint ranges,
+// so a line's tf values still sum to at most emits_per_line and every bound above holds
+// unchanged.  Matching is not affected by this rule.
+// The device merges the list of a prefix term that covers two or more words (one radix sort
+// of all such lists of the batch, kernels.hpp "search.hip"); SearchResult::merged is the
+// number of list elements it merged: over the batch's prefix terms that cover two or more
+// words, a term whose range repeats an earlier term's of its query left out, the sum of
+// their counts.  A term covering one word uses that word's list in place.
+// `*` is no delimiter: `ham*` is a legal literal token, and stays one unless the caller
+// asks for wildcards (make_search_query).
 constexpr u32 kSearchMaxQueries = 1024;
 constexpr u32 kSearchMaxTerms = 8;
 constexpr u64 kRankMaxEmits = 65536;
@@ -401,6 +429,8 @@ enum class SearchMode { kAll, kAny, kPhrase };
 struct SearchQuery {
   std::vector<std::string> terms;
   SearchMode mode = SearchMode::kAll;
+  std::vector<u8> prefix;  // empty: no prefix term; else parallel to terms, != 0: a prefix term
+  bool is_prefix(size_t t) const { return t < prefix.size() && prefix[t] != 0; }
 };
 struct SearchResult {
   std::vector<SearchQuery> queries;  // as asked (terms uncut)
@@ -412,6 +442,8 @@ struct SearchResult {
   std::vector<u32> scores;           // ranked: parallel to lines; unranked: empty
   std::vector<u64> matches;          // [queries] matching lines (unranked: the hit counts)
   u64 emits_per_line = 0;            // the job's (a ranked score is at most 32 * this)
+  u64 merged = 0;                    // list elements the device merged for prefix terms (0:
+                                     // none, or the host evaluation)
   u64 first_line = 0;
   // the word job's statistics, as in TopResult
   u64 num_lines = 0;
@@ -428,8 +460,22 @@ struct SearchResult {
 };
 // A term's key: its first min(size, cfg.max_key_len) bytes, packed as the map packs keys.
 PackedKey search_term_key(const std::string& term, const JobConfig& cfg);
-// Throws unless every query has 1..kSearchMaxTerms valid terms for cfg's delimiter set.
+// Is term t of q a prefix term after the cut?  (A prefix of max_key_len bytes or more is
+// exactly the plain term.)
+inline bool search_term_prefix(const SearchQuery& q, size_t t, const JobConfig& cfg) {
+  return q.is_prefix(t) && q.terms[t].size() < (size_t)cfg.max_key_len;
+}
+// The query of user terms.  wildcard: a term that ends in `*` and is longer than one byte
+// becomes a prefix term of what precedes the star; a lone `*` is an error; a `*` anywhere
+// else is literal.  Without wildcard every term is literal.
+SearchQuery make_search_query(const std::vector<std::string>& terms, SearchMode mode,
+                              bool wildcard);
+// Throws unless every query has 1..kSearchMaxTerms valid terms for cfg's delimiter set (and
+// `prefix` empty or as long as `terms`).
 void check_search_queries(const std::vector<SearchQuery>& queries, const JobConfig& cfg);
+// Throws when the `elements` list elements a device batch's prefix terms merge
+// (SearchResult::merged) do not fit the merge's 32-bit element counter.
+void check_search_merge(u64 queries, u64 elements);
 // Throws unless rank_k is 0 (unranked) or a u32 >= 1 with cfg.emits_per_line <= kRankMaxEmits.
 void check_search_rank(u64 rank_k, const JobConfig& cfg);
 // The host evaluation over an index result, any number of queries (cfg: the index job's
@@ -452,6 +498,7 @@ SearchResult search_index(const IndexResult& x, const TextInput& text,
 void validate_search(const SearchResult& r);
 // The result lines of a search, one per query:
 //   "print query: <terms joined by one space> \t hits: <h> \t lines: <l0> <l1> ...\n"
+// (a prefix term as it was asked: with its star)
 // ranked (hits: the matches; nothing after "top:" when nothing matched):
 //   "print query: <terms> \t hits: <matches> \t top: <l0>:<s0> <l1>:<s1> ...\n"
 void format_search_output(const SearchResult& r, std::string* out);

@@ -631,9 +631,34 @@ void launch_index(const IndexJob& job, IndexWorkspace& ws, SortPlan* h_plan, hip
 //            length; per query the distinct terms, the driver (the shortest list, `all`), the
 //            dead flag (`all` with an absent term) and the bound on its hits = the elements
 //            it walks: the driver's length (`all`) or the distinct terms' lengths (`any`).
-//            A phrase is looked up as `all`: its bound covers its candidates and its hits
+//            A phrase is looked up as `all`: its bound covers its candidates and its hits.
+//            A prefix term (engine.hpp "prefix terms"; q_meta bit 16 + t, the key's non-zero
+//            bytes are the prefix) finds its words' rank range [lo, hi) with
+//            dev::find_prefix_range: the lower bound of p padded with 0x00, the upper bound
+//            of p padded with 0xff.  Its list is postings[val[lo] .. val[hi]), its length
+//            val[hi] - val[lo].  Terms are distinct when their ranges differ; the score mask
+//            (q_info bits 24..31) leaves out a term whose range lies inside another's, and
+//            `any` walks only the score mask's terms (a list inside another adds no line).
+//            x_len = the length of a list of two or more words that repeats no earlier
+//            term's of its query: it has to be merged; the lengths add up in ctr->merge (one
+//            atomic per wave that has any)
 //   scan     one workgroup: q_start[0 .. Q] = exclusive scan of the bounds, the total B
-//   (the host reads B and the term counts, and sizes the hit workspace)
+//   (the host reads B, the merge total X and the term counts in one readback, and sizes the
+//   hit workspace for max(B, X))
+//   expand   (only when X > 0: the batch has a prefix term that covers two or more words;
+//            every other batch runs the launches, copies and synchronisations it ran before
+//            prefix terms existed)
+//            scan     x_start[0 .. Q * 8] = exclusive scan of x_len over the slots
+//            gather   the flattened [0, X) in tiles of kSearchTile, grid-stride: a binary
+//                     search in x_start finds the element's slot, the key is
+//                     slot << 32 | (line - first_line), written to the hit workspace's
+//                     `pairs` (idle until the hit stage); its first thread sets merge_n = X
+//            order    radix_sort() of the keys as one-word keys: (slot, line)
+//            strip    merged[e] = first_line + low32(sorted[e]); a key outside its slot's
+//                     x_start range counts in `unmerged` (the host throws); the merged
+//                     slots' t_val become kSearchMerged | x_start[slot]
+//            The hit, phrase-candidate and score stages read such a term's list from
+//            merged + x_start[slot], t_len elements, as they read any list
 //   hits     a grid walks the flattened (query, list element) space in tiles of kSearchTile.
 //            An element counts when it is the first of its line in its list; `all`: when a
 //            binary search finds the line in every other distinct term's list; `any`: when
@@ -647,7 +672,9 @@ void launch_index(const IndexJob& job, IndexWorkspace& ws, SortPlan* h_plan, hip
 //            up to 64 consecutive candidates per wave and round.  The wave re-tokenises the
 //            candidate's line with the word job's rules (device/linetok.hpp, as index.hip's
 //            map), compares every emitted token's key with the query's packed term keys
-//            (bit j of a token's mask: it equals term j) and runs the shift-and automaton
+//            (bit j of a token's mask: it equals term j; for a prefix term: it starts with
+//            the term's bytes, (w_i & key_word_mask(k_i)) == k_i for the four key words, the
+//            masks computed in registers) and runs the shift-and automaton
 //            state = ((state << 1) | 1) & mask over the tokens in order; bit nterms - 1 set
 //            is a hit.  After a round lane i holds candidate i's verdict and the hits are
 //            written as the hit kernel writes them: one atomic per wave and round for the
@@ -663,8 +690,8 @@ void launch_index(const IndexJob& job, IndexWorkspace& ws, SortPlan* h_plan, hip
 //   offsets  the same scan of the per-query hit counts (the matches, and the segments of the
 //            sorted keys), and once more over min(hits, K): out_off[0 .. Q], where each
 //            query's returned lines go.  All in u64: K = 2^32 - 1 overflows nothing
-//   score    one thread per pair: per distinct present term tf = upper bound - lower bound
-//            of the line in the term's CSR range (never outside it), weight =
+//   score    one thread per pair: per term of the score mask tf = upper bound - lower bound
+//            of the line in the term's list (never outside it), weight =
 //            32 - clz(N / t_len) with N = val[n]; the pair becomes the rank key
 //            query << 54 | (kRankScoreMax - score) << 32 | rel_line in `cands`, which the
 //            phrase kernel has left.  A score of 0 or above 32 * emits_per_line counts in
@@ -682,6 +709,9 @@ struct SearchCounters {  // zeroed per batch
   u32 cands;      // phrase candidates the hit kernel wrote
   u32 verified;   // phrase candidates the phrase kernel has decided
   u32 unscored;   // ranked: hits whose score is 0 or above 32 * emits_per_line
+  u64 merge;      // X: the list elements of the prefix terms to merge (the lookup's sum)
+  u32 merge_n;    // keys handed to the merge's sort: X if the workspace holds them, else 0
+  u32 unmerged;   // sorted merge keys outside their slot's x_start range
 };
 static_assert(sizeof(SearchCounters) <= 64, "the counters share one 64-byte block");
 constexpr int kSearchBlock = 256;
@@ -690,6 +720,9 @@ constexpr int kSearchTile = kSearchBlock * kSearchItems;  // elements per workgr
 constexpr int kSearchMaxBlocks = 2048;                     // the hit kernel's grid cap
 constexpr u32 kSearchAny = 1u << 8;                        // q_meta: nterms | mode bit
 constexpr u32 kSearchPhrase = 1u << 9;                     // (neither bit: `all`)
+constexpr int kSearchPrefixShift = 16;  // q_meta bit 16 + t: term t is a prefix term
+constexpr u64 kSearchMerged = 1ull << 63;  // t_val: the list lies in `merged`, not in postings
+constexpr u32 kSearchSlots = kSearchMaxQueries * kSearchMaxTerms;  // (query, term) slots
 // The index a batch is answered from (all device memory, launch_index's output).
 struct SearchIndex {
   const OutRecord* recs = nullptr;  // [n] key order
@@ -715,9 +748,18 @@ struct SearchBatch {
   u64 zero_bytes = 0;
   SearchCounters* ctr = nullptr;
   u32* q_hits = nullptr;   // [Q] hits per query
-  u64* t_val = nullptr;    // [Q * kSearchMaxTerms] the term's CSR offset
-  u32* t_len = nullptr;    // [Q * kSearchMaxTerms] its list's length = the word's count; 0: absent
-  u32* q_info = nullptr;   // [Q] driver | dead << 8 | distinct-term mask << 16
+  u64* t_val = nullptr;    // [Q * kSearchMaxTerms] the term's CSR offset; behind the expand
+                           // stage kSearchMerged | its offset in `merged` for a merged list
+  u32* t_len = nullptr;    // [Q * kSearchMaxTerms] its list's length = the count of its word
+                           // (prefix term: of its words); 0: absent
+  u32* q_info = nullptr;   // [Q] driver | dead << 8 | distinct-term mask << 16 | score mask
+                           // << 24 (the terms whose key range lies inside no other's)
+  u32* x_len = nullptr;    // [Q * kSearchMaxTerms] the slot's merged length: t_len of a prefix
+                           // term that covers two or more words and repeats no earlier term
+                           // of its query, else 0
+  u64* x_start = nullptr;  // [kSearchSlots + 1] expand: exclusive scan of x_len
+  u32* merged = nullptr;   // [merged_cap] expand: the merged lists, slot after slot (an
+  u64 merged_cap = 0;      // allocation of its own, grown on demand: the engine sets both)
   u32* q_bound = nullptr;  // [Q]
   u64* q_start = nullptr;  // [Q + 1]
   u64* offsets = nullptr;  // [Q + 1]
@@ -744,8 +786,17 @@ void search_batch_carve(char* base, SearchBatch* b);
 u64 search_hits_bytes(u64 cap);
 // Carves `base` (search_hits_bytes(cap) bytes, 256-B aligned).  The caller zeroes h->zeros once.
 void search_hits_carve(char* base, u64 cap, SearchHits* h);
-// lookup + scan: b.ctr->bound, b.t_len and b.q_start are complete when `s` has drained.
+// lookup + scan: b.ctr->bound, b.ctr->merge, b.t_len and b.q_start are complete when `s` has
+// drained.
 void launch_search_lookup(const SearchIndex& ix, const SearchBatch& b, u32 queries, hipStream_t s);
+// expand (only when the lookup reported merge = X > 0): scan + gather + order + strip.
+// b.merged[0 .. X) holds the merged lists and b.t_val names them when `s` has drained; the
+// gather's keys and the sort use h (X <= h.cap, X <= b.merged_cap), which the hit stage may
+// overwrite behind it.  b.ctr->unmerged counts sorted keys outside their slot's range.  More
+// than kSmallSortMax elements read the sort's plan back and synchronise `s` once, as
+// launch_search_order does.
+void launch_search_expand(const SearchIndex& ix, const SearchBatch& b, u32 queries, u64 x,
+                          SearchHits& h, SortPlan* h_plan, hipStream_t s);
 // hits (+ phrase, when `verify`: the batch has a phrase of two or more terms) + seal over
 // the `bound` elements the lookup reported (bound <= h.cap).
 void launch_search_hits(const SearchIndex& ix, const SearchBatch& b, u32 queries, u64 bound,

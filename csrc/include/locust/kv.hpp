@@ -163,6 +163,14 @@ LOCUST_HD inline int key_compare(const uint64_t* a, const uint64_t* b) {
   return 0;
 }
 
+// The bytes of a packed key word down to its last non-zero one, as a mask (0 for a zero
+// word).  A key holds no NUL before its padding, so over a prefix p's packed words this is
+// the mask of p's bytes: a key k starts with p when (k[j] & mask(p[j])) == p[j] for every
+// word, p | ~mask is p padded with 0xff, and p itself is p padded with 0x00.
+LOCUST_HD inline uint64_t key_word_mask(uint64_t k) {
+  return k ? ~0ull << (__builtin_ctzll(k) & ~7) : 0ull;
+}
+
 LOCUST_HD inline bool key_less(const PackedKey& a, const PackedKey& b) {
   return key_compare(a.w, b.w) < 0;
 }

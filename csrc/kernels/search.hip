@@ -9,11 +9,22 @@
 // Shape (gfx950, wave64):
 //  * search_lookup_kernel: one thread per (query, term), 32 queries per workgroup.  The key
 //    was packed on the host (kv.hpp); find_rank gives the rank, val[] and the record's count
-//    the list.  The eight terms of a query meet in LDS, where the query's first thread marks
-//    the distinct terms (a repeated term has the rank of an earlier one), picks the driver
-//    and writes the bound on the query's hits = the elements the hit kernel walks for it;
-//  * search_scan_kernel: one workgroup, exclusive scan of <= kSearchMaxQueries u32 values
-//    into Q + 1 u64 words (the bounds -> q_start, later the hit counts -> offsets);
+//    the list.  The eight terms of a query meet in LDS: every term thread compares its rank
+//    range with the others' (a repeated term has the range of an earlier one), and the
+//    query's first thread combines the flags into the distinct terms and the score mask,
+//    picks the driver and writes the bound on the query's hits = the elements the hit kernel
+//    walks for it.
+//    A prefix term (`ham*`, engine.hpp "prefix terms") finds the rank range of its words
+//    instead (find_prefix_range): terms are told apart by their ranges, and the lengths of
+//    the lists that cover two or more words add up to the batch's merge total X;
+//  * search_scan_kernel: one workgroup, exclusive scan of u32 values into count + 1 u64
+//    words (the bounds -> q_start, later the hit counts -> offsets, the merged lengths of
+//    the Q * 8 slots -> x_start);
+//  * expand, only when X > 0: search_gather_kernel writes the key slot << 32 | line of
+//    every element of the lists to merge (tiles of kSearchTile over [0, X), the slot by a
+//    binary search in x_start), radix_sort() orders them, search_strip_kernel writes
+//    merged[e] and points the slots' t_val there.  From then on such a list is read like
+//    any other (term_list);
 //  * search_hit_kernel: the flattened element space [0, B) in tiles of kSearchTile, grid-
 //    stride.  A thread finds its element's query by a binary search in q_start, then the
 //    term and position, and decides the hit by binary searches confined to the other
@@ -61,44 +72,88 @@ constexpr int kPhraseMaxBlocks = 2048;  // 8 workgroups per CU
 __global__ __launch_bounds__(kSearchBlock) void search_lookup_kernel(
     const OutRecord* __restrict__ recs, u32 n, const u64* __restrict__ val,
     const u64* __restrict__ keys, const u32* __restrict__ q_meta, u32 Q, u64* __restrict__ t_val,
-    u32* __restrict__ t_len, u32* __restrict__ q_info, u32* __restrict__ q_bound) {
-  __shared__ u32 s_rank[kSearchBlock];
+    u32* __restrict__ t_len, u32* __restrict__ q_info, u32* __restrict__ q_bound,
+    u32* __restrict__ x_len, SearchCounters* __restrict__ ctr) {
+  // a term's words: the rank range [lo, hi) -- one word, or a prefix term's; absent: n, n
+  __shared__ u32 s_lo[kSearchBlock];
+  __shared__ u32 s_hi[kSearchBlock];
   __shared__ u32 s_len[kSearchBlock];
+  __shared__ u32 s_flag[kSearchBlock];  // 1: present | 2: dup | 4: inside (below)
   const u32 gid = blockIdx.x * kSearchBlock + threadIdx.x;
   const u32 q = gid / kTerms, t = gid % kTerms;
   const u32 meta = q < Q ? q_meta[q] : 0u;
-  const u32 nterms = meta & 0xffu;
-  u32 rank = n, len = 0;
+  const u32 nterms = min(meta & 0xffu, (u32)kTerms);  // (the host checked: at most eight)
+  u32 lo = n, hi = n, len = 0;
   u64 at = 0;
   if (t < nterms) {
     const u64* k = keys + (u64)gid * kKeyWords;
-    rank = dev::find_rank(recs, n, k[0], k[1], k[2], k[3]);
-    if (rank < n) {
-      at = val[rank];
-      len = (u32)recs[rank].count;  // (the index holds < 2^32 postings in all)
+    if ((meta >> (kSearchPrefixShift + t)) & 1u) {
+      dev::find_prefix_range(recs, n, k[0], k[1], k[2], k[3], &lo, &hi);
+      if (lo < hi) {
+        at = val[lo];
+        len = (u32)(val[hi] - at);  // (the index holds < 2^32 postings in all)
+      } else {
+        lo = hi = n;
+      }
+    } else {
+      const u32 rank = dev::find_rank(recs, n, k[0], k[1], k[2], k[3]);
+      if (rank < n) {
+        lo = rank;
+        hi = rank + 1;
+        at = val[rank];
+        len = (u32)recs[rank].count;  // (the index holds < 2^32 postings in all)
+      }
     }
   }
   if (q < Q) {
     t_val[gid] = at;
     t_len[gid] = len;
   }
-  s_rank[threadIdx.x] = rank;
+  s_lo[threadIdx.x] = lo;
+  s_hi[threadIdx.x] = hi;
   s_len[threadIdx.x] = len;
+  __syncthreads();
+  // Ranges are nested or disjoint.  Every term thread looks at the query's other terms: dup,
+  // an earlier term has the same words; inside, another present term's range holds this
+  // one's (of equal ranges the first counts).  The eight threads of a query do this side by
+  // side, so its first thread only has to combine eight flag words below.
+  bool dup = false, inside = false;
+  if (lo < hi) {
+    const u32 base = threadIdx.x - t;
+    for (u32 i = 0; i < nterms; ++i) {
+      const u32 ilo = s_lo[base + i], ihi = s_hi[base + i];
+      if (i == t || ilo >= ihi) continue;
+      const bool same = ilo == lo && ihi == hi;
+      dup |= same && i < t;
+      inside |= same ? i < t : (ilo <= lo && hi <= ihi);
+    }
+  }
+  s_flag[threadIdx.x] = (lo < hi ? 1u : 0u) | (dup ? 2u : 0u) | (inside ? 4u : 0u);
+  // a list of two or more words is merged (the expand stage), unless an earlier term of the
+  // query has the same words.  Only a prefix term covers two words.
+  const bool wide = hi - lo >= 2u && !dup;
+  if (q < Q) x_len[gid] = wide ? len : 0u;
+  if (dev::ballot(wide)) {  // (wave-uniform; no batch without prefix terms gets here)
+    const u64 x = dev::wave_reduce_sum<u64>(wide ? (u64)len : 0ull);
+    if (dev::lane_id() == 0) atomicAdd((unsigned long long*)&ctr->merge, (unsigned long long)x);
+  }
   __syncthreads();
   if (q < Q && t == 0) {
     const bool any = (meta & kSearchAny) != 0;  // (a phrase is looked up as `all`)
-    const u32* rk = s_rank + threadIdx.x;
+    const u32* fl = s_flag + threadIdx.x;
     const u32* ln = s_len + threadIdx.x;
-    u32 mask = 0, dead = 0, driver = 0, best = ~0u;
+    u32 mask = 0, smask = 0, dead = 0, driver = 0, best = ~0u;
     u64 sum = 0;
     for (u32 j = 0; j < nterms; ++j) {
-      if (rk[j] >= n) {  // absent
+      const u32 f = fl[j];
+      if (!(f & 1u)) {  // absent
         dead |= any ? 0u : 1u;
         continue;
       }
-      bool dup = false;
-      for (u32 i = 0; i < j; ++i) dup |= rk[i] == rk[j];
-      if (dup) continue;
+      if (!(f & 4u)) smask |= 1u << j;
+      // `any`: a list inside another adds no line to the union, and the lists left are
+      // disjoint ranges of < 2^32 postings, so sum fits 32 bits
+      if (f & (any ? 4u : 2u)) continue;
       mask |= 1u << j;
       sum += ln[j];
       if (ln[j] < best) {
@@ -106,9 +161,8 @@ __global__ __launch_bounds__(kSearchBlock) void search_lookup_kernel(
         driver = j;
       }
     }
-    // the distinct lists are disjoint ranges of < 2^32 postings: sum fits 32 bits
     const u32 bound = any ? (u32)sum : (dead || !mask ? 0u : best);
-    q_info[q] = driver | (dead << 8) | (mask << 16);
+    q_info[q] = driver | (dead << 8) | (mask << 16) | (smask << 24);
     q_bound[q] = bound;
   }
 }
@@ -132,6 +186,62 @@ __global__ __launch_bounds__(kSearchBlock) void search_scan_kernel(const u32* __
   if (threadIdx.x == 0) {
     out[Q] = carry;
     if (total) *total = carry;
+  }
+}
+
+// ---- expand: the merged lists of the prefix terms that cover two or more words ----
+// Such a term's postings are one CSR range, but a concatenation of per-word sorted lists.
+// x_start (the scan of x_len over the S = Q * 8 slots) lays the lists out one after the
+// other in [0, X); element e becomes the key slot << 32 | (line - first_line), the one-word
+// radix_sort() orders the keys by (slot, line), and what is left is to strip the slot.
+__global__ __launch_bounds__(kSearchBlock) void search_gather_kernel(
+    const u32* __restrict__ postings, u32 first_line, const u64* __restrict__ x_start,
+    const u64* __restrict__ t_val, u32 S, u64 X, u64 cap, u64* __restrict__ keys,
+    SearchCounters* __restrict__ ctr) {
+  if (x_start[S] != X || X > cap) return;  // (uniform; never: the host throws on merge_n)
+  if (blockIdx.x == 0 && threadIdx.x == 0) ctr->merge_n = (u32)X;  // the sort's length
+  for (u64 tile = blockIdx.x; tile * kSearchTile < X; tile += gridDim.x) {  // (uniform)
+#pragma unroll 1
+    for (int j = 0; j < kSearchItems; ++j) {
+      const u64 e = tile * kSearchTile + (u64)j * kSearchBlock + threadIdx.x;
+      if (e >= X) continue;
+      // the slot: x_start[slot] <= e < x_start[slot + 1] (x_start[0] = 0, x_start[S] = X)
+      u32 lo = 0, hi = S;
+      while (hi - lo > 1) {
+        const u32 mid = lo + ((hi - lo) >> 1);
+        if (x_start[mid] <= e)
+          lo = mid;
+        else
+          hi = mid;
+      }
+      // (e - x_start[lo] < x_len[lo] = the slot's t_len: inside its CSR range)
+      const u32 line = postings[t_val[lo] + (e - x_start[lo])];
+      keys[e] = ((u64)lo << 32) | (u64)(line - first_line);
+    }
+  }
+}
+
+// merged[e] = first_line + the key's line; a key outside its slot's x_start range counts as
+// unmerged.  The merged slots' t_val now name their lists in `merged`.
+__global__ __launch_bounds__(256) void search_strip_kernel(
+    const u64* __restrict__ sorted, u64 X, const u64* __restrict__ x_start,
+    const u32* __restrict__ x_len, u32 S, u32 first_line, u32* __restrict__ merged,
+    u64* __restrict__ t_val, SearchCounters* __restrict__ ctr) {
+  if (ctr->merge_n != (u32)X) return;  // nothing was sorted (workgroup-uniform)
+  const u64 gid = (u64)blockIdx.x * 256 + threadIdx.x, stride = (u64)gridDim.x * 256;
+  u32 bad = 0;
+  for (u64 e = gid; e < X; e += stride) {
+    const u64 w = sorted[e];
+    const u32 slot = (u32)(w >> 32);
+    merged[e] = first_line + (u32)w;
+    if (slot >= S || e < x_start[slot] || e >= x_start[slot + 1]) ++bad;
+  }
+  for (u64 slot = gid; slot < S; slot += stride)
+    if (x_len[slot]) t_val[slot] = kSearchMerged | x_start[slot];
+  const u64 bm = dev::ballot(bad != 0);
+  if (bm) {
+    bad = dev::wave_reduce_sum(bad);
+    if (dev::lane_id() == 0) atomicAdd(&ctr->unmerged, bad);
   }
 }
 
@@ -180,6 +290,14 @@ __device__ __forceinline__ u32 list_tf(const u32* __restrict__ p, u32 len, u32 l
   return lo - first;
 }
 
+// A term's list: at its CSR offset in the postings, or (kSearchMerged, a prefix term of two
+// or more words behind the expand stage) at its offset in `merged`.  Either way t_len
+// elements, and list_has / list_tf stay inside them.
+__device__ __forceinline__ const u32* term_list(const u32* __restrict__ postings,
+                                                const u32* __restrict__ merged, u64 tv) {
+  return ((tv & kSearchMerged) ? merged : postings) + (tv & ~kSearchMerged);
+}
+
 // The hits of one converged wave step (hit: this lane has one, of query q on local line
 // rel_line): one atomic reserves the step's slots in `pairs`, one atomic per distinct query
 // of the wave adds to its hit count.
@@ -209,7 +327,8 @@ __device__ __forceinline__ void commit_hits(bool hit, u32 q, u32 rel_line, u64* 
 }
 
 __global__ __launch_bounds__(kSearchBlock) void search_hit_kernel(
-    const u32* __restrict__ postings, u32 first_line, const u32* __restrict__ q_meta,
+    const u32* __restrict__ postings, const u32* __restrict__ merged, u32 first_line,
+    const u32* __restrict__ q_meta,
     const u32* __restrict__ q_info, const u64* __restrict__ q_start, const u64* __restrict__ t_val,
     const u32* __restrict__ t_len, u32 Q, u64 B, u64* __restrict__ pairs,
     u64* __restrict__ cands, u64 pair_cap, u32* __restrict__ q_hits,
@@ -252,17 +371,20 @@ __global__ __launch_bounds__(kSearchBlock) void search_hit_kernel(
           }
         }
         if (local < tl[term]) {  // (always, by the bound's construction)
-          const u32* list = postings + tv[term];
+          const u32* list = term_list(postings, merged, tv[term]);
           line = list[local];
           // duplicates are adjacent: an element counts once per line
           if (local == 0 || list[local - 1] != line) {
             hit = true;
             if (any) {
               for (u32 t = 0; t < term; ++t)
-                if (((mask >> t) & 1u) && list_has(postings + tv[t], tl[t], line)) hit = false;
+                if (((mask >> t) & 1u) &&
+                    list_has(term_list(postings, merged, tv[t]), tl[t], line))
+                  hit = false;
             } else {
               for (u32 t = 0; t < (u32)kTerms && hit; ++t)
-                if (((mask >> t) & 1u) && t != term) hit = list_has(postings + tv[t], tl[t], line);
+                if (((mask >> t) & 1u) && t != term)
+                  hit = list_has(term_list(postings, merged, tv[t]), tl[t], line);
             }
             cand = hit && verify;
             hit = hit && !verify;
@@ -319,8 +441,10 @@ __global__ __launch_bounds__(kPhraseBlock) void search_phrase_kernel(
       const u32 q = (u32)__shfl((int)(u32)(mine >> 32), (int)i, 64);
       const u64 line = (u32)__shfl((int)(u32)mine, (int)i, 64);
       if (q >= Q || line >= num_lines) continue;  // (wave-uniform; never: the hit kernel's words)
-      const u32 m = q_meta[q] & 0xffu;
+      const u32 meta = q_meta[q];
+      const u32 m = meta & 0xffu;
       if (m == 0 || m > (u32)kTerms) continue;    // (never: the host checked the batch)
+      const u32 pre = (meta >> kSearchPrefixShift) & 0xffu;  // bit j: term j is a prefix term
       if (q != q_loaded) {  // (wave-uniform) neighbours mostly share their query
         __builtin_amdgcn_wave_barrier();  // the previous candidate's key reads are done
         if (lane < kTerms * kKeyWords) qk[lane] = keys[(u64)q * kTerms * kKeyWords + lane];
@@ -353,6 +477,12 @@ __global__ __launch_bounds__(kPhraseBlock) void search_phrase_kernel(
           dev::pack_row_key(row, lane, dm, max_key_len, &w0, &w1, &w2, &w3);
           for (u32 j = 0; j < m; ++j) {
             const u64* k = qk + j * kKeyWords;
+            if ((pre >> j) & 1u) {  // (wave-uniform) the token starts with the term's bytes
+              eq |= (u32)(k[0] == (w0 & key_word_mask(k[0])) && k[1] == (w1 & key_word_mask(k[1])) &&
+                          k[2] == (w2 & key_word_mask(k[2])) && k[3] == (w3 & key_word_mask(k[3])))
+                    << j;
+              continue;
+            }
             eq |= (u32)(k[0] == w0 && k[1] == w1 && k[2] == w2 && k[3] == w3) << j;
           }
         }
@@ -420,7 +550,8 @@ static_assert(kSearchMaxQueries == 1u << (64 - kRankQueryShift),
 // keys[e] = the rank key of pairs[e], e < H.  A hit whose score is 0 or above max_score (or
 // whose query is none of the batch) counts in ctr->unscored: the host throws.
 __global__ __launch_bounds__(kSearchBlock) void search_score_kernel(
-    const u32* __restrict__ postings, const u64* __restrict__ val, u32 n, u32 first_line,
+    const u32* __restrict__ postings, const u32* __restrict__ merged,
+    const u64* __restrict__ val, u32 n, u32 first_line,
     const u32* __restrict__ q_info, const u64* __restrict__ t_val, const u32* __restrict__ t_len,
     u32 Q, u32 max_score, const u64* __restrict__ pairs, u64 H, u64* __restrict__ keys,
     SearchCounters* __restrict__ ctr) {
@@ -436,13 +567,14 @@ __global__ __launch_bounds__(kSearchBlock) void search_score_kernel(
       const u32 q = (u32)(w >> 32), rel = (u32)w;
       u64 score = 0;
       if (q < Q) {
-        const u32 mask = (q_info[q] >> 16) & 0xffu;
+        const u32 mask = q_info[q] >> 24;  // the score mask: nested ranges count once
         const u64* tv = t_val + (u64)q * kTerms;
         const u32* tl = t_len + (u64)q * kTerms;
         for (u32 t = 0; t < (u32)kTerms; ++t) {
           if (!((mask >> t) & 1u) || tl[t] == 0) continue;
           const u32 weight = 32u - (u32)__clz((int)(N / tl[t]));  // bit_length(N / c_t)
-          score += (u64)weight * list_tf(postings + tv[t], tl[t], first_line + rel);
+          score += (u64)weight *
+                   list_tf(term_list(postings, merged, tv[t]), tl[t], first_line + rel);
         }
       }
       if (score < 1 || score > max_score) {
@@ -503,6 +635,8 @@ void batch_layout(Take&& take) {
   take(kQ * 4);                                // q_bound
   take((kQ + 1) * 8);                          // q_start
   take((kQ + 1) * 8);                          // offsets
+  take(kQT * 4);                               // x_len
+  take((kQT + 1) * 8);                         // x_start
 }
 static_assert(sizeof(SearchCounters) <= 64, "zero block layout");
 
@@ -536,7 +670,7 @@ u64 search_batch_bytes() {
 }
 
 void search_batch_carve(char* base, SearchBatch* sb) {
-  char* part[8];
+  char* part[10];
   int k = 0;
   u64 b = 0;
   batch_layout([&](u64 bytes) {
@@ -558,6 +692,8 @@ void search_batch_carve(char* base, SearchBatch* sb) {
   sb->q_start = reinterpret_cast<u64*>(part[6]);
   sb->out_off = sb->q_start;  // (ranked: the hit kernel has read q_start by then)
   sb->offsets = reinterpret_cast<u64*>(part[7]);
+  sb->x_len = reinterpret_cast<u32*>(part[8]);
+  sb->x_start = reinterpret_cast<u64*>(part[9]);
 }
 
 u64 search_hits_bytes(u64 cap) {
@@ -601,10 +737,41 @@ void launch_search_lookup(const SearchIndex& ix, const SearchBatch& b, u32 queri
   LOCUST_HIP_CHECK(hipMemsetAsync(b.zero, 0, b.zero_bytes, s));
   const u32 blocks = (u32)div_up((u64)queries, (u64)kLookupQueries);
   search_lookup_kernel<<<dim3(blocks), dim3(kSearchBlock), 0, s>>>(
-      ix.recs, ix.n, ix.val, b.keys, b.q_meta, queries, b.t_val, b.t_len, b.q_info, b.q_bound);
+      ix.recs, ix.n, ix.val, b.keys, b.q_meta, queries, b.t_val, b.t_len, b.q_info, b.q_bound,
+      b.x_len, b.ctr);
   LOCUST_HIP_LAUNCH_CHECK();
   search_scan_kernel<<<dim3(1), dim3(kSearchBlock), 0, s>>>(b.q_bound, queries, ~0u, b.q_start,
                                                             &b.ctr->bound);
+  LOCUST_HIP_LAUNCH_CHECK();
+}
+
+void launch_search_expand(const SearchIndex& ix, const SearchBatch& b, u32 queries, u64 x,
+                          SearchHits& h, SortPlan* h_plan, hipStream_t s) {
+  LOCUST_CHECK_ARG(queries >= 1 && queries <= kSearchMaxQueries && x >= 1 && x < (1ull << 32) &&
+                       x <= h.cap && b.merged && x <= b.merged_cap,
+                   "search: " + std::to_string(x) + " list elements to merge exceed the "
+                   "workspace (" + std::to_string(h.cap) + ", " + std::to_string(b.merged_cap) +
+                       ")");
+  const u32 slots = queries * kSearchMaxTerms;
+  search_scan_kernel<<<dim3(1), dim3(kSearchBlock), 0, s>>>(b.x_len, slots, ~0u, b.x_start,
+                                                            nullptr);
+  LOCUST_HIP_LAUNCH_CHECK();
+  const u32 gblocks = (u32)std::min<u64>(div_up(x, (u64)kSearchTile), (u64)kSearchMaxBlocks);
+  search_gather_kernel<<<dim3(gblocks), dim3(kSearchBlock), 0, s>>>(
+      ix.postings, ix.first_line, b.x_start, b.t_val, slots, x, h.cap, h.pairs, b.ctr);
+  LOCUST_HIP_LAUNCH_CHECK();
+  ConstKeysSoA keys;
+  KeysSoA sorted;
+  keys.w[0] = h.pairs;
+  sorted.w[0] = h.sorted;
+  for (int j = 1; j < kKeyWords; ++j) {
+    keys.w[j] = h.zeros;
+    sorted.w[j] = h.spare;  // the gather's copies of the zero words
+  }
+  radix_sort(keys, &b.ctr->merge_n, x, h.rx, nullptr, sorted, nullptr, nullptr, h_plan, s);
+  const u32 sblocks = (u32)std::min<u64>(div_up(std::max<u64>(x, slots), 256), 4096);
+  search_strip_kernel<<<dim3(sblocks), dim3(256), 0, s>>>(h.sorted, x, b.x_start, b.x_len, slots,
+                                                          ix.first_line, b.merged, b.t_val, b.ctr);
   LOCUST_HIP_LAUNCH_CHECK();
 }
 
@@ -617,8 +784,8 @@ void launch_search_hits(const SearchIndex& ix, const SearchBatch& b, u32 queries
     const u32 blocks =
         (u32)std::min<u64>(div_up(bound, (u64)kSearchTile), (u64)kSearchMaxBlocks);
     search_hit_kernel<<<dim3(blocks), dim3(kSearchBlock), 0, s>>>(
-        ix.postings, ix.first_line, b.q_meta, b.q_info, b.q_start, b.t_val, b.t_len, queries,
-        bound, h.pairs, h.cands, h.cap, b.q_hits, b.ctr);
+        ix.postings, b.merged, ix.first_line, b.q_meta, b.q_info, b.q_start, b.t_val, b.t_len,
+        queries, bound, h.pairs, h.cands, h.cap, b.q_hits, b.ctr);
     LOCUST_HIP_LAUNCH_CHECK();
   }
   if (bound && verify && ix.bytes) {
@@ -679,7 +846,7 @@ void launch_search_rank(const SearchIndex& ix, const SearchBatch& b, u32 queries
   // the phrase kernel is done with `cands`: the rank keys go there
   const u32 sblocks = (u32)std::min<u64>(div_up(hits, (u64)kSearchTile), (u64)kSearchMaxBlocks);
   search_score_kernel<<<dim3(sblocks), dim3(kSearchBlock), 0, s>>>(
-      ix.postings, ix.val, ix.n, ix.first_line, b.q_info, b.t_val, b.t_len, queries,
+      ix.postings, b.merged, ix.val, ix.n, ix.first_line, b.q_info, b.t_val, b.t_len, queries,
       32u * (u32)ix.emits_per_line, h.pairs, hits, h.cands, b.ctr);
   LOCUST_HIP_LAUNCH_CHECK();
   ConstKeysSoA keys;

@@ -95,7 +95,7 @@ struct PyIndexResult {
   IndexResult x;
   JobConfig cfg;  // the job's delimiters and max_key_len: what search() validates terms by
   PySearchResult search(const std::vector<std::vector<std::string>>& queries,
-                        const std::vector<int>& any, const py::object& rank) const;
+                        const std::vector<int>& any, const py::object& rank, bool wildcard) const;
   py::list entries() const { return PyResult{x.words}.entries(); }
   py::list postings() const {
     py::list out;
@@ -195,17 +195,17 @@ struct PySearchResult {
 };
 
 // queries: term lists; any[i]: query i's mode -- 0 `all`, 2 `phrase`, every other value `any`
-// (any.size() == queries.size()).
+// (any.size() == queries.size()).  wildcard: make_search_query's rule for a trailing `*`.
 std::vector<SearchQuery> to_queries(const std::vector<std::vector<std::string>>& queries,
-                                    const std::vector<int>& any) {
+                                    const std::vector<int>& any, bool wildcard) {
   LOCUST_CHECK_ARG(any.size() == queries.size(), "search: one mode per query");
   std::vector<SearchQuery> out(queries.size());
-  for (size_t i = 0; i < queries.size(); ++i) {
-    out[i].terms = queries[i];
-    out[i].mode = any[i] == 0   ? SearchMode::kAll
-                  : any[i] == 2 ? SearchMode::kPhrase
-                                : SearchMode::kAny;
-  }
+  for (size_t i = 0; i < queries.size(); ++i)
+    out[i] = make_search_query(queries[i],
+                               any[i] == 0   ? SearchMode::kAll
+                               : any[i] == 2 ? SearchMode::kPhrase
+                                             : SearchMode::kAny,
+                               wildcard);
   return out;
 }
 
@@ -224,8 +224,9 @@ u64 to_rank(const py::object& rank) {
 }
 
 PySearchResult PyIndexResult::search(const std::vector<std::vector<std::string>>& queries,
-                                     const std::vector<int>& any, const py::object& rank) const {
-  const std::vector<SearchQuery> q = to_queries(queries, any);
+                                     const std::vector<int>& any, const py::object& rank,
+                                     bool wildcard) const {
+  const std::vector<SearchQuery> q = to_queries(queries, any, wildcard);
   const u64 k = to_rank(rank);
   py::gil_scoped_release nogil;
   return PySearchResult{search_index(x, q, cfg, k)};
@@ -362,8 +363,8 @@ class PyGpuEngine {
   PySearchResult run_search(const std::string& text,
                             const std::vector<std::vector<std::string>>& queries,
                             const std::vector<int>& any, u64 first_line,
-                            const py::object& rank) {
-    const std::vector<SearchQuery> q = to_queries(queries, any);
+                            const py::object& rank, bool wildcard) {
+    const std::vector<SearchQuery> q = to_queries(queries, any, wildcard);
     const u64 k = to_rank(rank);
     py::gil_scoped_release nogil;
     return PySearchResult{eng_.run_search(as_input(text, first_line), q, k)};
@@ -371,15 +372,16 @@ class PyGpuEngine {
   PySearchResult run_search_text(const HostText& t,
                                  const std::vector<std::vector<std::string>>& queries,
                                  const std::vector<int>& any, u64 first_line,
-                                 const py::object& rank) {
-    const std::vector<SearchQuery> q = to_queries(queries, any);
+                                 const py::object& rank, bool wildcard) {
+    const std::vector<SearchQuery> q = to_queries(queries, any, wildcard);
     const u64 k = to_rank(rank);
     py::gil_scoped_release nogil;
     return PySearchResult{eng_.run_search(t.input(first_line), q, k)};
   }
   PySearchResult search_resident(const std::vector<std::vector<std::string>>& queries,
-                                 const std::vector<int>& any, const py::object& rank) {
-    const std::vector<SearchQuery> q = to_queries(queries, any);
+                                 const std::vector<int>& any, const py::object& rank,
+                                 bool wildcard) {
+    const std::vector<SearchQuery> q = to_queries(queries, any, wildcard);
     const u64 k = to_rank(rank);
     py::gil_scoped_release nogil;
     return PySearchResult{eng_.search_resident(q, k)};
@@ -793,7 +795,7 @@ PYBIND11_MODULE(_locust, m) {
       .def("postings_bytes", &PyIndexResult::postings_bytes)
       .def("lines", &PyIndexResult::lines, py::arg("key"), py::arg("unique") = false)
       .def("_search", &PyIndexResult::search, py::arg("queries"), py::arg("any"),
-           py::arg("rank") = py::none(),
+           py::arg("rank") = py::none(), py::arg("wildcard") = false,
            "The host evaluation of all/any queries (any[i]: query i's mode) over this index.")
       .def("times", &PyIndexResult::times)
       .def("format", &PyIndexResult::format)
@@ -831,6 +833,8 @@ PYBIND11_MODULE(_locust, m) {
       .def_property_readonly("max_key_len", [](const PySearchResult& p) { return p.r.max_key_len; })
       .def_property_readonly("index_ms", [](const PySearchResult& p) { return p.r.index_ms; })
       .def_property_readonly("search_ms", [](const PySearchResult& p) { return p.r.search_ms; })
+      .def_property_readonly("merged", [](const PySearchResult& p) { return p.r.merged; },
+                             "list elements the device merged for prefix terms")
       .def_property_readonly("wire_bytes", [](const PySearchResult& p) { return p.r.wire_bytes; },
                              "bytes the device wrote to host memory for the result");
   m.attr("kSearchMaxQueries") = kSearchMaxQueries;
@@ -874,11 +878,13 @@ PYBIND11_MODULE(_locust, m) {
            py::arg("first_line") = 0)
       .def("run_search", &PyGpuEngine::run_search, py::arg("text"), py::arg("queries"),
            py::arg("any"), py::arg("first_line") = 0, py::arg("rank") = py::none(),
+           py::arg("wildcard") = false,
            "WordCount of text, its index, and all/any queries answered on the device.")
       .def("run_search_text", &PyGpuEngine::run_search_text, py::arg("text"), py::arg("queries"),
-           py::arg("any"), py::arg("first_line") = 0, py::arg("rank") = py::none())
+           py::arg("any"), py::arg("first_line") = 0, py::arg("rank") = py::none(),
+           py::arg("wildcard") = false)
       .def("search_resident", &PyGpuEngine::search_resident, py::arg("queries"), py::arg("any"),
-           py::arg("rank") = py::none(),
+           py::arg("rank") = py::none(), py::arg("wildcard") = false,
            "Another batch from the index the last run_index / run_search left on the device.")
       .def("top_counts", &PyGpuEngine::top_counts, py::arg("records"), py::arg("k"),
            "The selection kernels alone over key-sorted (key, count) records.")
@@ -899,12 +905,14 @@ PYBIND11_MODULE(_locust, m) {
   m.def("cpu_run_search", [](const JobConfig& cfg, const std::string& text,
                              const std::vector<std::vector<std::string>>& queries,
                              const std::vector<int>& any, u64 first_line,
-                             const py::object& rank) {
+                             const py::object& rank, bool wildcard) {
     CpuWordCount eng(cfg);
-    return PySearchResult{
-        eng.run_search(as_input(text, first_line), to_queries(queries, any), to_rank(rank))};
+    return PySearchResult{eng.run_search(as_input(text, first_line),
+                                         to_queries(queries, any, wildcard), to_rank(rank))};
   }, py::arg("cfg"), py::arg("text"), py::arg("queries"), py::arg("any"),
-        py::arg("first_line") = 0, py::arg("rank") = py::none());
+        py::arg("first_line") = 0, py::arg("rank") = py::none(), py::arg("wildcard") = false);
+  m.def("check_search_merge", &check_search_merge, py::arg("queries"), py::arg("elements"),
+        "Throws when a device batch's prefix terms would merge 2^32 list elements or more.");
   m.def("cpu_map_stage", [](const JobConfig& cfg, const std::string& text) {
     CpuWordCount eng(cfg);
     std::vector<py::bytes> out;

@@ -31,13 +31,13 @@ def _search_args(queries, mode):
     return queries, [_SEARCH_MODES[m] for m in modes]
 
 
-def _index_search(self, queries, mode="all", rank=None):
+def _index_search(self, queries, mode="all", rank=None, wildcard=False):
     """All/any word queries over this index, evaluated on the host (``SearchResult``):
     ``queries``, ``mode`` and ``rank`` as ``Engine.run_search`` takes them, any number of
     queries.  A ``"phrase"`` query is refused: the index holds no positions, so a phrase
     needs the text (``Engine.run_search``, ``search_text``)."""
     queries, flags = _search_args(queries, mode)
-    return self._search(queries, flags, rank)
+    return self._search(queries, flags, rank, bool(wildcard))
 
 
 _C.IndexResult.search = _index_search
@@ -79,7 +79,8 @@ class Engine:
             return _C.cpu_run_index(self.cfg, text, first_line)
         return self._eng.run_index(text, first_line)
 
-    def run_search(self, text: bytes, queries, mode="all", first_line: int = 0, rank=None):
+    def run_search(self, text: bytes, queries, mode="all", first_line: int = 0, rank=None,
+                   wildcard=False):
         """WordCount of ``text``, its inverted index, and a batch of word queries answered
         from it (``SearchResult``).  ``queries`` is a list of term lists (1 to 8 byte-string
         terms each); ``mode`` is ``"all"`` (lines that hold every term), ``"any"`` (lines
@@ -97,13 +98,21 @@ class Engine:
         descending, line ascending), ``scores(i)`` are their scores and ``matches()`` counts
         every query's matching lines, of which ``min(K, matches)`` are returned.  On the GPU
         the lines are scored and selected on the device and only the winners cross PCIe.
-        ``rank=None`` is the unranked answer (``scores(i)`` empty, ``matches() == hits()``)."""
+        ``rank=None`` is the unranked answer (``scores(i)`` empty, ``matches() == hits()``).
+
+        ``wildcard=True`` reads a term that ends in ``*`` (and is longer than one byte) as a
+        prefix term: ``ham*`` stands for every word that starts with ``ham``, and behaves as
+        one word whose list is the merged lists of them all (``oracle.search`` with
+        ``wildcard=True`` states the rules).  A lone ``*`` is refused and a ``*`` anywhere
+        else is literal; without ``wildcard`` every ``*`` is.  On the GPU the lists are merged
+        on the device; ``merged`` is the number of list elements the batch merged."""
         queries, flags = _search_args(queries, mode)
         if self.cpu:
-            return _C.cpu_run_search(self.cfg, text, queries, flags, first_line, rank)
-        return self._eng.run_search(text, queries, flags, first_line, rank)
+            return _C.cpu_run_search(self.cfg, text, queries, flags, first_line, rank,
+                                     bool(wildcard))
+        return self._eng.run_search(text, queries, flags, first_line, rank, bool(wildcard))
 
-    def search_resident(self, queries, mode="all", rank=None):
+    def search_resident(self, queries, mode="all", rank=None, wildcard=False):
         """Another batch from the index this engine's last job left on the device; that
         job must have been a ``run_index`` or a ``run_search`` (GPU engines only).  Every
         mode of ``run_search``: the job's text is resident too, so phrases are answered.
@@ -112,7 +121,7 @@ class Engine:
             raise _C.LocustError("search_resident needs a GPU engine: the CPU engine keeps "
                                  "no index (use run_index(text).search(...))")
         queries, flags = _search_args(queries, mode)
-        return self._eng.search_resident(queries, flags, rank)
+        return self._eng.search_resident(queries, flags, rank, bool(wildcard))
 
     def top_counts(self, records: list[tuple[bytes, int]], k: int):
         """The selection alone over (key, count) records sorted by key with distinct
@@ -207,23 +216,23 @@ def index_file(path: str, line_start: int = -1, line_end: int = -1, backend: str
 
 
 def search_text(text: bytes, queries, mode="all", backend: str = "gpu", cfg=None,
-                first_line: int = 0, rank=None, **kw):
+                first_line: int = 0, rank=None, wildcard=False, **kw):
     """All/any/phrase word queries over ``text`` (``SearchResult``); see
     ``Engine.run_search``."""
     cfg = cfg if cfg is not None else make_config(backend, **kw)
     nlines = text.count(b"\n") + (1 if text and not text.endswith(b"\n") else 0)
     return Engine(cfg, max(len(text), 1), max(nlines, 1)).run_search(text, queries, mode,
-                                                                      first_line, rank)
+                                                                      first_line, rank, wildcard)
 
 
 def search_file(path: str, queries, mode="all", line_start: int = -1, line_end: int = -1,
-                backend: str = "gpu", cfg=None, rank=None, **kw):
+                backend: str = "gpu", cfg=None, rank=None, wildcard=False, **kw):
     """All/any/phrase word queries over a file or its line window, answered with the file's
     own (global) line numbers."""
     cfg = cfg if cfg is not None else make_config(backend, **kw)
     text, nlines, first, _total = _C.load_lines(path, line_start, line_end, cfg.ref_compat)
     return Engine(cfg, max(len(text), 1), max(nlines, 1)).run_search(text, queries, mode, first,
-                                                                      rank)
+                                                                      rank, wildcard)
 
 
 def map_stage(path: str, spill: str, line_start: int = -1, line_end: int = -1,

@@ -136,8 +136,59 @@ def format_index(entries, postings) -> bytes:
 MAX_SEARCH_TERMS = 8
 
 
+def prefix_terms(terms, wildcard: bool, delims: bytes = DEFAULT_DELIMS, max_key: int = 29):
+    """The terms of a query as ``(p, is_prefix)`` pairs, validated and cut.
+
+    Without ``wildcard`` every term is literal.  With it, a term that ends in ``*`` and is
+    longer than one byte is a prefix term of what precedes the star, a lone ``*`` is an
+    error and a ``*`` anywhere else is literal.  ``p`` is non-empty and validated exactly
+    as a term is (no NUL, newline or byte of ``delims``: ``ValueError``), and cut to
+    ``max_key`` bytes as a term is.  A prefix of ``max_key`` bytes (after the cut) is
+    exactly the plain term ``p``: it comes back with ``is_prefix`` False."""
+    bad = set(delims) | {0, 0x0A}
+    out = []
+    for t in terms:
+        if wildcard and t == b"*":
+            raise ValueError("a lone * is no prefix term")
+        pre = bool(wildcard) and len(t) > 1 and t.endswith(b"*")
+        p = t[:-1] if pre else t
+        if not p or any(c in bad for c in p):
+            raise ValueError("invalid term %r" % (t,))
+        p = p[:max_key]
+        out.append((p, pre and len(p) < max_key))
+    return out
+
+
+def _term_words(entries, p: bytes, pre: bool):
+    """The indices of a term's words among ``entries``: the keys that start with ``p``
+    (a word equal to ``p`` among them) for a prefix term, the key ``p`` for a plain one."""
+    return [i for i, (k, _v, _c) in enumerate(entries)
+            if (k[:len(p)] == p if pre else k == p)]
+
+
+def _term_list(entries, postings, words):
+    """The merged list of the words: the multiset union of their postings, non-decreasing."""
+    return sorted(l for i in words for l in postings[entries[i][1]:entries[i][1] + entries[i][2]])
+
+
+def merged_elements(entries, queries, delims: bytes = DEFAULT_DELIMS, max_key: int = 29) -> int:
+    """``SearchResult.merged`` of a device batch of wildcard ``queries`` (term lists): over
+    the batch's prefix terms that cover two or more words, a term whose words repeat an
+    earlier term's of its query left out, the sum of their counts.  (A term that covers one
+    word uses that word's list in place: nothing is merged.)"""
+    total = 0
+    for terms in queries:
+        seen = []
+        for p, pre in prefix_terms(terms, True, delims, max_key):
+            words = _term_words(entries, p, pre)
+            if len(words) >= 2 and words not in seen:
+                total += sum(entries[i][2] for i in words)
+            seen.append(words)
+    return total
+
+
 def search(entries, postings, terms, mode: str = "all", delims: bytes = DEFAULT_DELIMS,
-           max_key: int = 29):
+           max_key: int = 29, *, wildcard: bool = False):
     """One all/any word query over an index: ``(lines, counts)``.
 
     ``entries`` and ``postings`` are ``index``'s output.  A query is 1 to 8 ``terms`` and a
@@ -148,12 +199,26 @@ def search(entries, postings, terms, mode: str = "all", delims: bytes = DEFAULT_
     absent word has none.  ``"all"`` is the intersection of the terms' lines (empty as soon
     as one term is absent), ``"any"`` their union; a repeated term changes nothing.
     ``lines`` are global line numbers, ascending, each once; ``counts[t]`` is the count of
-    term ``t``'s word, 0 when it is absent."""
+    term ``t``'s word, 0 when it is absent.
+
+    ``wildcard=True``: a term may be a prefix term (``prefix_terms``).  Its words are the
+    index keys ``k`` with ``k[:len(p)] == p``, a word equal to ``p`` among them; its list is
+    the multiset union of those words' postings, non-decreasing; its count is the sum of
+    their counts; if no word matches, the term is absent.  In ``"all"`` and ``"any"`` it
+    behaves as a word with that list."""
     if mode not in ("all", "any"):
         raise ValueError("mode must be 'all' or 'any'")
     terms = list(terms)
     if not 1 <= len(terms) <= MAX_SEARCH_TERMS:
         raise ValueError("a query takes 1 to %d terms" % MAX_SEARCH_TERMS)
+    if wildcard:
+        sets, counts = [], []
+        for p, pre in prefix_terms(terms, True, delims, max_key):
+            lines = _term_list(entries, postings, _term_words(entries, p, pre))
+            counts.append(len(lines))
+            sets.append(set(lines))
+        hit = set.intersection(*sets) if mode == "all" else set.union(*sets)
+        return sorted(hit), counts
     bad = set(delims) | {0, 0x0A}
     for t in terms:
         if not t or any(c in bad for c in t):
@@ -169,7 +234,7 @@ def search(entries, postings, terms, mode: str = "all", delims: bytes = DEFAULT_
 
 
 def phrase(text: bytes, terms, delims: bytes = DEFAULT_DELIMS, emits: int = 20,
-           max_key: int = 29, first_line: int = 0):
+           max_key: int = 29, first_line: int = 0, *, wildcard: bool = False):
     """One phrase query over ``text``: ``(lines, counts)``, as ``search`` answers.
 
     `phrase` answers the lines on which the terms occur as consecutive tokens, in order.
@@ -186,10 +251,33 @@ def phrase(text: bytes, terms, delims: bytes = DEFAULT_DELIMS, emits: int = 20,
     per-term counts have the shape of the other modes'; repeated terms report the same count.
 
     Terms are validated as ``search`` validates them (``ValueError``).  Written straight from
-    the paragraph above: every line is tokenised and every window compared; no index."""
+    the paragraph above: every line is tokenised and every window compared; no index.
+
+    ``wildcard=True``: a term may be a prefix term (``prefix_terms``).  A token matches a
+    prefix term when the token's key (cut to ``max_key``) starts with ``p``; a token shorter
+    than ``p`` does not match.  Its count is the number of emitted tokens that match it.  A
+    one-term phrase answers the lines that hold a matching token, as `all` does."""
     terms = list(terms)
     if not 1 <= len(terms) <= MAX_SEARCH_TERMS:
         raise ValueError("a query takes 1 to %d terms" % MAX_SEARCH_TERMS)
+    if wildcard:
+        want = prefix_terms(terms, True, delims, max_key)
+        m = len(want)
+
+        def fits(tok, term):
+            p, pre = term
+            return tok[:len(p)] == p if pre else tok == p
+
+        lines = []
+        counts = [0] * m
+        for i, line in enumerate(split_lines(text)):
+            toks, _dropped = tokenize(line, delims, emits, max_key)
+            for j, term in enumerate(want):
+                counts[j] += sum(fits(tok, term) for tok in toks)
+            if any(all(fits(toks[o + j], want[j]) for j in range(m))
+                   for o in range(len(toks) - m + 1)):
+                lines.append(first_line + i)
+        return lines, counts
     bad = set(delims) | {0, 0x0A}
     for t in terms:
         if not t or any(c in bad for c in t):
@@ -220,7 +308,8 @@ def format_search(queries, answers) -> bytes:
 RANK_MAX_EMITS = 65536
 
 
-def rank(entries, postings, lines, terms, k: int, max_key: int = 29):
+def rank(entries, postings, lines, terms, k: int, max_key: int = 29, *,
+         wildcard: bool = False, delims: bytes = DEFAULT_DELIMS):
     """The ranked answer of one query: ``(top, matches)``.
 
     ``lines`` is the query's matching set, as ``search`` or ``phrase`` answered it; ranking
@@ -231,9 +320,36 @@ def rank(entries, postings, lines, terms, k: int, max_key: int = 29):
     more); ``tf`` is how often the line occurs in the term's postings list; a line's score
     is the sum of ``weight * tf`` over the distinct present terms.  ``top`` is the first
     ``min(k, matches)`` matching lines in the order (score descending, line ascending) as
-    ``(line, score)`` pairs, ``matches`` is ``len(lines)``.  ``k >= 1``."""
+    ``(line, score)`` pairs, ``matches`` is ``len(lines)``.  ``k >= 1``.
+
+    ``wildcard=True``: a term may be a prefix term (``prefix_terms``).  Its ``c`` is its
+    merged count (the sum of its words' counts; the weight is still ``bit_length(N // c)``)
+    and its ``tf`` the line's multiplicity in its merged list.  Every present term has a
+    key range, the set of its words; prefix ranges and single words form a laminar family:
+    two ranges are nested or disjoint.  A present term whose range lies inside the range of
+    another present term of the query contributes nothing to the score; of equal ranges the
+    first occurrence counts (for plain terms: a repeated key counts once)."""
     if k < 1:
         raise ValueError("rank takes k >= 1")
+    if wildcard:
+        n = len(postings)
+        ranges = [set(_term_words(entries, p, pre))
+                  for p, pre in prefix_terms(terms, True, delims, max_key)]
+        lists = []
+        for j, rj in enumerate(ranges):
+            if not rj:  # absent
+                continue
+            if any(ri and i != j and rj <= ri and (rj != ri or i < j)
+                   for i, ri in enumerate(ranges)):
+                continue
+            merged = _term_list(entries, postings, sorted(rj))
+            tf = {}
+            for line in merged:
+                tf[line] = tf.get(line, 0) + 1
+            lists.append(((n // len(merged)).bit_length(), tf))
+        scored = [(sum(w * tf.get(line, 0) for w, tf in lists), line) for line in lines]
+        scored.sort(key=lambda sl: (-sl[0], sl[1]))
+        return [(line, score) for score, line in scored[:k]], len(lines)
     n = len(postings)
     by_key = {key: (v, c) for key, v, c in entries}
     lists = []

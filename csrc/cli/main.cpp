@@ -17,9 +17,11 @@
 //   --top K (the K most frequent words instead of the whole dictionary, rank order)
 //   --ngram N (count the word N-grams of each line, N <= 3, instead of its words)
 //   --index (the inverted index: every word with the lines it occurs on)
-//   --search "w1 w2" [--match all|any|phrase] (the lines that hold all / any of the words,
-//     or the words as consecutive tokens in that order; repeat --search for a batch:
-//     answered from the index on the device, or by --backend cpu)
+//   --search "w1 w2" [--match all|any|phrase|near] (the lines that hold all / any of the
+//     words, the words as consecutive tokens in that order, or the words within --within W
+//     tokens of one another; repeat --search for a batch: answered from the index on the
+//     device, or by --backend cpu)
+//   --within W (with --match near: the window in tokens, W >= 1)
 //   --rank K (with --search: each query's K best lines with their scores, best first)
 //   --wildcard (with --search: a word that ends in * is a prefix term, "ham*")
 // and a synthetic-text generator (BASELINE configs "1M lines" / "10 GB"):
@@ -90,7 +92,9 @@ struct CliArgs {
   // --search "w1 w2" (repeatable): the result lines are the queries' answers
   std::vector<std::string> search_args;
   std::vector<SearchQuery> queries;
-  std::string match;  // --match all|any|phrase ("": all)
+  std::string match;  // --match all|any|phrase|near ("": all)
+  bool within_given = false;
+  u64 within = 0;  // --within W: the window of --match near, in tokens
   bool rank_given = false;
   u64 rank = 0;  // --rank K: every query answers its K best lines, scored (0: all its lines)
   bool wildcard = false;  // --wildcard: a --search word that ends in * is a prefix term
@@ -136,9 +140,13 @@ void help() {
       "                             like the text; repeat --search for a batch.  Answered from the\n"
       "                             index in device memory, or by --backend cpu.  Restrictions\n"
       "                             as --index, and not with --index)\n"
-      "  --match all|any|phrase     (--search: lines with every word (default), with any, or\n"
-      "                             with the words as consecutive tokens in the order given,\n"
-      "                             whatever delimiters stand between them)\n"
+      "  --match all|any|phrase|near\n"
+      "                             (--search: lines with every word (default), with any, with\n"
+      "                             the words as consecutive tokens in the order given, whatever\n"
+      "                             delimiters stand between them, or with every word inside some\n"
+      "                             --within W consecutive tokens of the line, in any order)\n"
+      "  --within W                 (--match near, which needs it: the window in tokens,\n"
+      "                             1 <= W < 2^32; with W = 2 two words must be neighbours)\n"
       "  --rank K                   (--search: only each query's K best lines, best first, as\n"
       "                             line:score; a line's score adds, per distinct word of the\n"
       "                             query, its occurrences on the line times a weight that grows\n"
@@ -272,8 +280,17 @@ bool parse(int argc, char** argv, CliArgs* a) {
       a->search_args.push_back(need("--search"));
     } else if (s == "--match") {
       a->match = need("--match");
-      if (a->match != "all" && a->match != "any" && a->match != "phrase")
-        throw Error("--match takes all, any or phrase (how --search combines its words)");
+      if (a->match != "all" && a->match != "any" && a->match != "phrase" && a->match != "near")
+        throw Error("--match takes all, any, phrase or near (how --search combines its words)");
+    } else if (s == "--within") {
+      const std::string v = need("--within");
+      char* endp = nullptr;
+      const long long w = std::strtoll(v.c_str(), &endp, 10);
+      if (v.empty() || *endp || w < 1 || w > (long long)kSearchMaxWithin)
+        throw Error("--within W (the window of --match near, in tokens) needs an integer W "
+                    "with 1 <= W < 2^32");
+      a->within = (u64)w;
+      a->within_given = true;
     } else if (s == "--wildcard") {
       a->wildcard = true;
     } else if (s == "--rank") {
@@ -342,6 +359,10 @@ bool parse(int argc, char** argv, CliArgs* a) {
   }
   if (!a->match.empty() && a->search_args.empty())
     throw Error("--match selects how --search combines its words: give --search too");
+  if (a->within_given && a->match != "near")
+    throw Error("--within W is the window of --match near: give --match near too");
+  if (a->match == "near" && !a->within_given)
+    throw Error("--match near needs its window: give --within W too (W tokens, W >= 1)");
   if (a->rank_given && a->search_args.empty())
     throw Error("--rank K selects the best lines of a --search query: give --search too");
   if (a->wildcard && a->search_args.empty())
@@ -377,6 +398,7 @@ bool parse(int argc, char** argv, CliArgs* a) {
     std::vector<std::string> terms;
     const SearchMode mode = a->match == "any"      ? SearchMode::kAny
                             : a->match == "phrase" ? SearchMode::kPhrase
+                            : a->match == "near"   ? SearchMode::kNear
                                                    : SearchMode::kAll;
     std::string cur;
     for (const char c : arg) {
@@ -389,7 +411,7 @@ bool parse(int argc, char** argv, CliArgs* a) {
     }
     if (!cur.empty()) terms.push_back(cur);
     if (terms.empty()) throw Error("--search \"" + arg + "\" holds no word");
-    a->queries.push_back(make_search_query(terms, mode, a->wildcard));
+    a->queries.push_back(make_search_query(terms, mode, a->wildcard, a->within));
   }
   if (!a->queries.empty()) {
     check_search_queries(a->queries, a->cfg);

@@ -380,10 +380,11 @@ PackedKey search_term_key(const std::string& term, const JobConfig& cfg) {
 }
 
 SearchQuery make_search_query(const std::vector<std::string>& terms, SearchMode mode,
-                              bool wildcard) {
+                              bool wildcard, u64 within) {
   SearchQuery q;
   q.terms = terms;
   q.mode = mode;
+  q.within = within;
   if (!wildcard) return q;
   bool any = false;
   std::vector<u8> prefix(terms.size(), 0);
@@ -412,6 +413,14 @@ void check_search_queries(const std::vector<SearchQuery>& queries, const JobConf
                      "search: query " + std::to_string(i) + " has " +
                          std::to_string(q.prefix.size()) + " prefix flags for " +
                          std::to_string(q.terms.size()) + " terms; give none or one per term");
+    if (q.mode == SearchMode::kNear)
+      LOCUST_CHECK_ARG(q.within >= 1 && q.within <= kSearchMaxWithin,
+                       "search: query " + std::to_string(i) + " is a near query: it takes a "
+                       "window 1 <= W < 2^32 (within), not " + std::to_string(q.within));
+    else
+      LOCUST_CHECK_ARG(q.within == 0,
+                       "search: query " + std::to_string(i) + " has a window (within " +
+                           std::to_string(q.within) + ") but is no near query");
     for (const std::string& t : q.terms) {
       LOCUST_CHECK_ARG(!t.empty(), "search: query " + std::to_string(i) + " has an empty term");
       for (const char ch : t) {
@@ -445,25 +454,56 @@ void check_search_rank(u64 rank_k, const JobConfig& cfg) {
 
 namespace {
 
+// Does the token match key j?  masks: empty, or per key and word the bytes a token must
+// share with it (a prefix term: key_word_mask of its words; a plain term: every byte).
+bool token_matches(const PackedKey& tok, size_t j, const std::vector<PackedKey>& keys,
+                   const std::vector<PackedKey>& masks) {
+  if (masks.empty()) return key_compare(tok.w, keys[j].w) == 0;
+  bool same = true;
+  for (int i = 0; i < kKeyWords; ++i) same &= (tok.w[i] & masks[j].w[i]) == keys[j].w[i];
+  return same;
+}
+
 // Do the first emits_per_line tokens of the line hold the keys as consecutive tokens?
-// masks: empty, or per key and word the bytes a token must share with it (a prefix term:
-// key_word_mask of its words; a plain term: every byte).
 bool line_has_phrase(const char* line, u64 len, const std::vector<PackedKey>& keys,
                      const std::vector<PackedKey>& masks, const JobConfig& cfg,
                      std::vector<PackedKey>* toks) {
   toks->clear();
   tokenize_line(line, len, cfg, toks, nullptr);
   const size_t m = keys.size();
-  const auto eq = [&](const PackedKey& tok, size_t j) {
-    if (masks.empty()) return key_compare(tok.w, keys[j].w) == 0;
-    bool same = true;
-    for (int i = 0; i < kKeyWords; ++i) same &= (tok.w[i] & masks[j].w[i]) == keys[j].w[i];
-    return same;
-  };
   for (size_t o = 0; o + m <= toks->size(); ++o) {
     size_t j = 0;
-    while (j < m && eq((*toks)[o + j], j)) ++j;
+    while (j < m && token_matches((*toks)[o + j], j, keys, masks)) ++j;
     if (j == m) return true;
+  }
+  return false;
+}
+
+// Do `within` consecutive tokens among the first emits_per_line of the line match every key?
+// Per key the position of its last matching token: the shortest window that ends at token o
+// and covers every key starts at the smallest of them.
+bool line_has_near(const char* line, u64 len, const std::vector<PackedKey>& keys,
+                   const std::vector<PackedKey>& masks, u64 within, const JobConfig& cfg,
+                   std::vector<PackedKey>* toks) {
+  toks->clear();
+  tokenize_line(line, len, cfg, toks, nullptr);
+  const size_t m = keys.size();
+  std::vector<size_t> last(m, (size_t)-1);
+  for (size_t o = 0; o < toks->size(); ++o) {
+    bool any = false;
+    for (size_t j = 0; j < m; ++j)
+      if (token_matches((*toks)[o], j, keys, masks)) {
+        last[j] = o;
+        any = true;
+      }
+    if (!any) continue;
+    size_t first = o;
+    bool all = true;
+    for (size_t j = 0; j < m && all; ++j) {
+      all = last[j] != (size_t)-1;
+      first = std::min(first, last[j]);
+    }
+    if (all && (u64)(o - first) < within) return true;
   }
   return false;
 }
@@ -473,17 +513,24 @@ SearchResult search_index_impl(const IndexResult& x, const TextInput* text,
                                u64 rank_k) {
   check_search_queries(queries, cfg);
   check_search_rank(rank_k, cfg);
-  bool verify = false;  // a phrase of two or more terms
+  bool verify = false;  // a phrase, or a near query, of two or more terms
   for (const SearchQuery& q : queries)
-    verify |= q.mode == SearchMode::kPhrase && q.terms.size() >= 2;
+    verify |= (q.mode == SearchMode::kPhrase || q.mode == SearchMode::kNear) &&
+              q.terms.size() >= 2;
   if (!text)
-    for (const SearchQuery& q : queries)
+    for (const SearchQuery& q : queries) {
       LOCUST_CHECK_ARG(q.mode != SearchMode::kPhrase,
                        "search: a phrase query needs the text (the index holds no positions): "
                        "use search_index(index, text, queries, cfg), or run_search on an engine");
+      LOCUST_CHECK_ARG(q.mode != SearchMode::kNear || q.terms.size() < 2,
+                       "search: a near query of two or more terms needs the text (the index "
+                       "holds no positions): use search_index(index, text, queries, cfg), or "
+                       "run_search on an engine");
+    }
   std::vector<u64> line_at;  // the text's line starts, and its size behind them
   if (verify) {
-    LOCUST_CHECK_ARG(cfg.ngram == 1, "search: a phrase is verified with word keys (ngram 1)");
+    LOCUST_CHECK_ARG(cfg.ngram == 1,
+                     "search: a phrase or near query is verified with word keys (ngram 1)");
     LOCUST_CHECK_ARG(text->first_line == x.first_line && !text->source,
                      "search: the text is not the window the index was built from");
     for (u64 p = 0; p < text->bytes;) {
@@ -574,8 +621,11 @@ SearchResult search_index_impl(const IndexResult& x, const TextInput* text,
     }
     if (q.mode != SearchMode::kAny) {
       const bool phrase = q.mode == SearchMode::kPhrase && q.terms.size() >= 2;
+      // (W >= emits_per_line: no line has more tokens, the `all` answer stands)
+      const bool near = q.mode == SearchMode::kNear && q.terms.size() >= 2 &&
+                        q.within < (u64)cfg.emits_per_line;
       std::vector<PackedKey> keys, masks, toks;
-      if (phrase)
+      if (phrase || near)
         for (size_t t = 0; t < q.terms.size(); ++t) {
           keys.push_back(search_term_key(q.terms[t], cfg));
           if (!wild) continue;
@@ -594,12 +644,14 @@ SearchResult search_index_impl(const IndexResult& x, const TextInput* text,
           bool hit = true;
           for (size_t i = 0; i < lists.size() && hit; ++i)
             if (i != d) hit = std::binary_search(lists[i].p, lists[i].p + lists[i].len, line);
-          if (hit && phrase) {  // a candidate: the line itself decides
+          if (hit && (phrase || near)) {  // a candidate: the line itself decides
             const u64 l = line - x.first_line;
             LOCUST_CHECK_ARG(l + 1 < line_at.size(),
                              "search: the text has fewer lines than the index names");
-            hit = line_has_phrase(text->data + line_at[l], line_at[l + 1] - 1 - line_at[l], keys,
-                                  masks, cfg, &toks);
+            const char* at = text->data + line_at[l];
+            const u64 len = line_at[l + 1] - 1 - line_at[l];
+            hit = phrase ? line_has_phrase(at, len, keys, masks, cfg, &toks)
+                         : line_has_near(at, len, keys, masks, q.within, cfg, &toks);
           }
           if (hit) r.lines.push_back(line);
         }

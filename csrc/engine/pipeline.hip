@@ -29,7 +29,7 @@ u64 DevicePipeline::pinned_bytes() const {
   if (h_top) b += (kTopKMax + 1) * sizeof(TopRecord);
   if (h_ictr) b += h_post_cap * sizeof(u32) + sizeof(IndexCounters);
   if (h_supload)
-    b += search_upload_bytes(kSearchMaxQueries) + h_slines_cap * sizeof(u32) +
+    b += search_upload_bytes(kSearchMaxQueries, true) + h_slines_cap * sizeof(u32) +
          ((u64)kSearchMaxQueries * (kSearchMaxTerms * 4 + 8 + 4) + 72);
   b += 2 * sizeof(MapCounters) + sizeof(SortPlan) + 2 * sizeof(PartMapTables) +
        kMaxSamples * sizeof(PackedKey) + (kMaxRanks + 8) * sizeof(u64) + 64 +
@@ -2072,7 +2072,7 @@ void DevicePipeline::ensure_search() {
   LOCUST_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&d_sbatch), bytes));
   sbatch_bytes = bytes;
   search_batch_carve(d_sbatch, &sbatch);
-  h_supload = static_cast<char*>(pinned_alloc(search_upload_bytes(kSearchMaxQueries),
+  h_supload = static_cast<char*>(pinned_alloc(search_upload_bytes(kSearchMaxQueries, true),
                                               hipHostMallocDefault, "search queries"));
   h_sres = static_cast<char*>(pinned_alloc(kSearchResBytes, hipHostMallocDefault, "search result"));
   for (auto& e : ev_search) LOCUST_HIP_CHECK(hipEventCreate(&e));
@@ -2156,17 +2156,26 @@ void DevicePipeline::search_stage(const std::vector<SearchQuery>& queries, u64 r
     sync();
     return;
   }
-  // the batch: q_meta | the terms' keys, packed exactly as the map packs them
+  // the batch: q_meta | the terms' keys, packed exactly as the map packs them | the windows,
+  // only when a near query needs them
   u32* meta = reinterpret_cast<u32*>(h_supload);
   u64* keys = reinterpret_cast<u64*>(h_supload + (u64)kSearchMaxQueries * sizeof(u32));
+  u32* within = search_within(keys, Q);
   bool verify = false;  // the batch has a phrase of two or more terms: the phrase kernel runs
+  bool near = false;    // ... a near query of two or more terms and W < emits_per_line: the
+                        // near kernel runs (a wider window holds every line: answered as `all`)
   std::memset(keys, 0, (size_t)Q * kSearchMaxTerms * sizeof(PackedKey));
   for (u32 q = 0; q < Q; ++q) {
     const SearchQuery& sq = queries[q];
+    const bool qnear = sq.mode == SearchMode::kNear && sq.terms.size() >= 2 &&
+                       sq.within < (u64)cfg.emits_per_line;
     meta[q] = (u32)sq.terms.size() | (sq.mode == SearchMode::kAny      ? kSearchAny
                                       : sq.mode == SearchMode::kPhrase ? kSearchPhrase
+                                      : qnear                          ? kSearchNear
                                                                        : 0u);
+    within[q] = qnear ? (u32)sq.within : 0u;
     verify |= sq.mode == SearchMode::kPhrase && sq.terms.size() >= 2;
+    near |= qnear;
     for (size_t t = 0; t < sq.terms.size(); ++t) {
       // a prefix term's flag; its length needs no word: the key's non-zero bytes are it
       if (search_term_prefix(sq, t, cfg)) meta[q] |= 1u << (kSearchPrefixShift + (int)t);
@@ -2174,7 +2183,7 @@ void DevicePipeline::search_stage(const std::vector<SearchQuery>& queries, u64 r
       std::memcpy(keys + ((u64)q * kSearchMaxTerms + t) * kKeyWords, k.w, sizeof(PackedKey));
     }
   }
-  LOCUST_HIP_CHECK(hipMemcpyAsync(sbatch.upload, h_supload, search_upload_bytes(Q),
+  LOCUST_HIP_CHECK(hipMemcpyAsync(sbatch.upload, h_supload, search_upload_bytes(Q, near),
                                   hipMemcpyHostToDevice, stream));
   // lookup: the terms' lists and the bound on the hits
   launch_search_lookup(idx_view, sbatch, Q, stream);
@@ -2202,8 +2211,9 @@ void DevicePipeline::search_stage(const std::vector<SearchQuery>& queries, u64 r
     launch_search_expand(idx_view, sbatch, Q, X, shits, h_plan, stream);
   }
   r->merged = X;
-  // hits; a phrase's candidates are verified against the resident text behind them
-  launch_search_hits(idx_view, sbatch, Q, B, verify, shits, stream);
+  // hits; a phrase's and a near query's candidates are verified against the resident text
+  // behind them
+  launch_search_hits(idx_view, sbatch, Q, B, verify, near, shits, stream);
   LOCUST_HIP_CHECK(hipMemcpyAsync(h_sc, sbatch.ctr, sizeof(SearchCounters), hipMemcpyDeviceToHost,
                                   stream));
   u32* h_hits = reinterpret_cast<u32*>(h_sres + kSearchResHits);
@@ -2211,7 +2221,7 @@ void DevicePipeline::search_stage(const std::vector<SearchQuery>& queries, u64 r
     LOCUST_HIP_CHECK(hipMemcpyAsync(h_hits, sbatch.q_hits, (u64)Q * sizeof(u32),
                                     hipMemcpyDeviceToHost, stream));
   sync();
-  const u64 H = h_sc->written, C = h_sc->cands;
+  const u64 H = h_sc->written, C = h_sc->cands, NC = h_sc->ncands;
   if (h_sc->merge_n != (u32)X || h_sc->unmerged)
     throw Error("search: " + std::to_string(h_sc->merge_n) + " of " + std::to_string(X) +
                 " list elements of prefix terms merged, " + std::to_string(h_sc->unmerged) +
@@ -2222,6 +2232,10 @@ void DevicePipeline::search_stage(const std::vector<SearchQuery>& queries, u64 r
   if (C > B || h_sc->verified != C || (C && !verify))
     throw Error("search: " + std::to_string(C) + " phrase candidates, " +
                 std::to_string(h_sc->verified) + " of them verified, the lists hold " +
+                std::to_string(B) + " elements");
+  if (C + NC > B || h_sc->nverified != NC || (NC && !near))
+    throw Error("search: " + std::to_string(NC) + " near candidates, " +
+                std::to_string(h_sc->nverified) + " of them verified, the lists hold " +
                 std::to_string(B) + " elements");
   // ranked: R lines and R scores come back, R = the sum of min(matches, K)
   u64 R = 0, M = 0;

@@ -339,7 +339,7 @@ void validate_index(const IndexResult& r);
 //   "print key: <key> \t count: <count> \t lines: <l0> <l1> ...\n"
 void format_index_output(const IndexResult& r, std::string* out);
 
-// ---- index search: all/any/phrase word queries over the inverted index ----
+// ---- index search: all/any/phrase/near word queries over the inverted index ----
 // A query is 1 to kSearchMaxTerms terms and a mode.  A term is a non-empty byte string
 // without NUL, newline or a byte of the job's delimiter set; one longer than max_key_len is
 // cut to its first max_key_len bytes, as the map cuts keys, and so matches the merged list
@@ -362,15 +362,33 @@ void format_index_output(const IndexResult& r, std::string* out);
 // under truncation match as their merged key, the rule the index uses.  The answer and the
 // per-term counts have the shape of the other modes'; repeated terms report the same count.
 //
+// `near` answers the lines on which the terms occur within W tokens of one another, in any
+// order.  The window W (SearchQuery::within) is a u32 >= 1 given per query; W = 0, a `near`
+// query without a window and a window on a query of another mode are refused.  A line's
+// token sequence is exactly the phrase mode's: the job's delimiter set, a NUL ends the
+// line's tokens, only the first emits_per_line tokens exist, each token cut to max_key_len
+// bytes.  A line with tokens k_0 .. k_(n-1) matches when positions a <= b exist with
+// b - a + 1 <= W such that every term is matched by at least one token k_i, a <= i <= b.
+// Token matching is the phrase verification's: a plain term matches a token by equality of
+// cut keys, a prefix term p when the token's cut key starts with p.  Order does not matter
+// ([be, to] answers as [to, be]); a repeated term changes nothing (set semantics, as in
+// `all`: [bye, bye] needs one bye); one token may satisfy several terms, which happens only
+// with prefix terms ([Ham*, Hamlet] with W = 1 matches every line with the token Hamlet).
+// A window never crosses a line end, an absent term gives an empty answer, a one-term query
+// answers as `all` does, and so does every W >= emits_per_line (no line has more tokens):
+// the engines take that shortcut and verify nothing.  term_counts, `merged` and the ranked
+// score (tf over the whole line, from the postings -- not over the window) are `all`'s.
+//
 // The device stage (kernels/search.hip; GpuWordCount::run_search / search_resident)
 // answers batches of up to kSearchMaxQueries queries from the index in device memory:
-// neither postings nor records cross PCIe.  A phrase takes its candidate lines from the
-// `all` evaluation and verifies each against the text, which the engine keeps in device
-// memory beside the index.  The host evaluation (search_index) takes any number of
-// queries; for a phrase it needs the text too (the four-argument overload).
+// neither postings nor records cross PCIe.  A phrase or a `near` query takes its candidate
+// lines from the `all` evaluation and verifies each against the text, which the engine
+// keeps in device memory beside the index.  The host evaluation (search_index) takes any
+// number of queries; for a phrase, or a `near` query of two or more terms, it needs the
+// text too (the four-argument overload).
 //
 // ---- ranked search: the best K lines of every query, best first ----
-// The matching set of a query is exactly what `all` / `any` / `phrase` answer.  Ranking
+// The matching set of a query is exactly what `all` / `any` / `phrase` / `near` answer.  Ranking
 // never changes which lines match, only their order and how many are returned.
 //   N            the index's postings.size() (= num_tokens, and val[n] on the device).
 //   distinct present terms
@@ -403,9 +421,9 @@ void format_index_output(const IndexResult& r, std::string* out);
 // list is the multiset union of those words' postings, non-decreasing; its count, as
 // reported in term_counts, is the sum of their counts.  If no word matches, the term is
 // absent.  If len(p) == max_key_len (after the cut), it is exactly the plain term p.
-// In `all`, `any` and the candidate stage of `phrase`, a prefix term behaves as a word with
-// that list.  In `phrase` verification a token matches a prefix term when the token's key
-// (cut to max_key_len) starts with p; a token shorter than p does not match.
+// In `all`, `any` and the candidate stage of `phrase` and `near`, a prefix term behaves as a
+// word with that list.  In `phrase` and `near` verification a token matches a prefix term
+// when the token's key (cut to max_key_len) starts with p; a token shorter than p does not.
 // Ranked: a prefix term's c_t is its merged count (the weight still bit_length(N / c_t), in
 // [1, 32]) and its tf the line's multiplicity in the merged list.  Prefix ranges and single
 // words form a laminar family: two terms' key ranges are nested or disjoint.  A present
@@ -425,10 +443,12 @@ constexpr u32 kSearchMaxQueries = 1024;
 constexpr u32 kSearchMaxTerms = 8;
 constexpr u64 kRankMaxEmits = 65536;
 constexpr u32 kRankScoreMax = 32u * (u32)kRankMaxEmits;  // 2^21
-enum class SearchMode { kAll, kAny, kPhrase };
+constexpr u64 kSearchMaxWithin = 0xffffffffull;  // a `near` window: 1 <= W <= 2^32 - 1
+enum class SearchMode { kAll, kAny, kPhrase, kNear };
 struct SearchQuery {
   std::vector<std::string> terms;
   SearchMode mode = SearchMode::kAll;
+  u64 within = 0;  // kNear: the window W in tokens, 1 .. kSearchMaxWithin; other modes: 0
   std::vector<u8> prefix;  // empty: no prefix term; else parallel to terms, != 0: a prefix term
   bool is_prefix(size_t t) const { return t < prefix.size() && prefix[t] != 0; }
 };
@@ -468,10 +488,12 @@ inline bool search_term_prefix(const SearchQuery& q, size_t t, const JobConfig& 
 // The query of user terms.  wildcard: a term that ends in `*` and is longer than one byte
 // becomes a prefix term of what precedes the star; a lone `*` is an error; a `*` anywhere
 // else is literal.  Without wildcard every term is literal.
+// within: the window of a `near` query (0: none).
 SearchQuery make_search_query(const std::vector<std::string>& terms, SearchMode mode,
-                              bool wildcard);
+                              bool wildcard, u64 within = 0);
 // Throws unless every query has 1..kSearchMaxTerms valid terms for cfg's delimiter set (and
-// `prefix` empty or as long as `terms`).
+// `prefix` empty or as long as `terms`), a `near` query a window in [1, kSearchMaxWithin]
+// and every other query none (within == 0).
 void check_search_queries(const std::vector<SearchQuery>& queries, const JobConfig& cfg);
 // Throws when the `elements` list elements a device batch's prefix terms merge
 // (SearchResult::merged) do not fit the merge's 32-bit element counter.
@@ -479,14 +501,16 @@ void check_search_merge(u64 queries, u64 elements);
 // Throws unless rank_k is 0 (unranked) or a u32 >= 1 with cfg.emits_per_line <= kRankMaxEmits.
 void check_search_rank(u64 rank_k, const JobConfig& cfg);
 // The host evaluation over an index result, any number of queries (cfg: the index job's
-// delimiters and max_key_len).  Throws for a phrase query: the index holds no positions, so
-// a phrase needs the text -- the four-argument overload.
+// delimiters and max_key_len).  Throws for a phrase query and for a `near` query of two or
+// more terms: the index holds no positions, so they need the text -- the four-argument
+// overload.
 // rank_k != 0 ranks every query (scores come from the postings alone).
 SearchResult search_index(const IndexResult& x, const std::vector<SearchQuery>& queries,
                           const JobConfig& cfg, u64 rank_k = 0);
 // The same with the text the index was built from (the same window: text.first_line ==
-// x.first_line; cfg also gives emits_per_line): a phrase's candidates come from the `all`
-// evaluation and are verified by tokenising their lines with the CPU engine's tokeniser.
+// x.first_line; cfg also gives emits_per_line): a phrase's or a `near` query's candidates
+// come from the `all` evaluation and are verified by tokenising their lines with the CPU
+// engine's tokeniser.
 SearchResult search_index(const IndexResult& x, const TextInput& text,
                           const std::vector<SearchQuery>& queries, const JobConfig& cfg,
                           u64 rank_k = 0);

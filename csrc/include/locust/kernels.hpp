@@ -620,10 +620,11 @@ struct IndexJob {
 void launch_index(const IndexJob& job, IndexWorkspace& ws, SortPlan* h_plan, hipStream_t s);
 
 // ---------------- search.hip ----------------
-// All/any/phrase word queries over the inverted index launch_index left on the device
+// All/any/phrase/near word queries over the inverted index launch_index left on the device
 // (engine.hpp "index search"): the key-ordered records, the CSR offsets `val` and the sorted
-// postings; a phrase is verified against the text the index was built from, which is
-// resident too.  A batch holds Q <= kSearchMaxQueries queries of <= kSearchMaxTerms terms.
+// postings; a phrase or a `near` query is verified against the text the index was built
+// from, which is resident too.  A batch holds Q <= kSearchMaxQueries queries of
+// <= kSearchMaxTerms terms.
 //
 // A sequence of kernels on `s`; data moves between workgroups only across the kernel
 // boundaries (the radix sort it reuses keeps its own look-back), no polled word:
@@ -631,7 +632,8 @@ void launch_index(const IndexJob& job, IndexWorkspace& ws, SortPlan* h_plan, hip
 //            length; per query the distinct terms, the driver (the shortest list, `all`), the
 //            dead flag (`all` with an absent term) and the bound on its hits = the elements
 //            it walks: the driver's length (`all`) or the distinct terms' lengths (`any`).
-//            A phrase is looked up as `all`: its bound covers its candidates and its hits.
+//            A phrase or a `near` query is looked up as `all`: its bound covers its
+//            candidates and its hits.
 //            A prefix term (engine.hpp "prefix terms"; q_meta bit 16 + t, the key's non-zero
 //            bytes are the prefix) finds its words' rank range [lo, hi) with
 //            dev::find_prefix_range: the lower bound of p padded with 0x00, the upper bound
@@ -667,7 +669,11 @@ void launch_index(const IndexJob& job, IndexWorkspace& ws, SortPlan* h_plan, hip
 //            step, the per-query hit counts from one atomic per wave, step and query.  An
 //            element of a phrase of two or more terms that passes the `all` test is a
 //            candidate: the same pair word goes to `cands`, its slot from one atomic per wave
-//            and step on the candidate counter, and q_hits is left alone
+//            and step on the candidate counter, and q_hits is left alone.  The same holds
+//            for a `near` query that needs verification (kSearchNear) and has two or more
+//            distinct terms; its candidates have a counter of their own (ncands) and fill
+//            `cands` from its last word downwards, so neither verify kernel sees the
+//            other's (cands + ncands <= B <= cap: the two ends never meet)
 //   phrase   (only when the batch has a phrase of two or more terms) one wave per candidate,
 //            up to 64 consecutive candidates per wave and round.  The wave re-tokenises the
 //            candidate's line with the word job's rules (device/linetok.hpp, as index.hip's
@@ -679,6 +685,17 @@ void launch_index(const IndexJob& job, IndexWorkspace& ws, SortPlan* h_plan, hip
 //            is a hit.  After a round lane i holds candidate i's verdict and the hits are
 //            written as the hit kernel writes them: one atomic per wave and round for the
 //            slots, one per distinct query for q_hits; one more counts the verified candidates
+//   near     (only when the batch has a `near` query that needs verification: two or more
+//            terms and W < emits_per_line) the phrase kernel's skeleton and token masks over
+//            the `near` candidates.  In place of the automaton the wave keeps, per term, 1 +
+//            the ordinal of the last token that matched it (0: none yet): lane j < 8 holds
+//            term min(j, nterms - 1)'s in one register, updated by a select.  It walks only
+//            the step's tokens whose mask is non-zero, in order; behind each, the minimum
+//            over lanes 0 .. 7 (three DPP row shifts) is non-zero when every term has been
+//            seen, and the line matches if ord + 1 - min < W (a minimal covering window
+//            ends at a matching token).  The state carries across the 64-byte steps;
+//            ordinals and W are full u32.  Commits as the phrase kernel does; `nverified`
+//            counts the decided candidates
 //   seal     one thread: the sort's length, capped by the workspace
 //   (the host reads the number of hits H: the sort takes its regime from it)
 //   order    radix_sort() of the pair words as one-word keys
@@ -712,6 +729,8 @@ struct SearchCounters {  // zeroed per batch
   u64 merge;      // X: the list elements of the prefix terms to merge (the lookup's sum)
   u32 merge_n;    // keys handed to the merge's sort: X if the workspace holds them, else 0
   u32 unmerged;   // sorted merge keys outside their slot's x_start range
+  u32 ncands;     // `near` candidates the hit kernel wrote (from the end of `cands` down)
+  u32 nverified;  // `near` candidates the near kernel has decided
 };
 static_assert(sizeof(SearchCounters) <= 64, "the counters share one 64-byte block");
 constexpr int kSearchBlock = 256;
@@ -720,6 +739,8 @@ constexpr int kSearchTile = kSearchBlock * kSearchItems;  // elements per workgr
 constexpr int kSearchMaxBlocks = 2048;                     // the hit kernel's grid cap
 constexpr u32 kSearchAny = 1u << 8;                        // q_meta: nterms | mode bit
 constexpr u32 kSearchPhrase = 1u << 9;                     // (neither bit: `all`)
+constexpr u32 kSearchNear = 1u << 10;  // a `near` query to verify (W < emits_per_line, two or
+                                       // more terms); every other `near` query goes as `all`
 constexpr int kSearchPrefixShift = 16;  // q_meta bit 16 + t: term t is a prefix term
 constexpr u64 kSearchMerged = 1ull << 63;  // t_val: the list lies in `merged`, not in postings
 constexpr u32 kSearchSlots = kSearchMaxQueries * kSearchMaxTerms;  // (query, term) slots
@@ -730,7 +751,7 @@ struct SearchIndex {
   const u32* postings = nullptr;    // [val[n]] global line numbers
   u32 n = 0;
   u32 first_line = 0;
-  // what the phrase kernel reads: the text the index was built from (the engine's own
+  // what the phrase and near kernels read: the text the index was built from (the engine's own
   // device copy), its line starts as launch_index left them, and the job's token rules
   const char* text = nullptr;
   u64 bytes = 0;
@@ -741,9 +762,11 @@ struct SearchIndex {
 };
 // The per-batch arrays: fixed size (kSearchMaxQueries), made by the first search job.
 struct SearchBatch {
-  char* upload = nullptr;  // [q_meta | keys]: one H2D per batch
+  char* upload = nullptr;  // [q_meta | keys | within]: one H2D per batch
   u32* q_meta = nullptr;   // [kSearchMaxQueries] nterms | mode bit
   u64* keys = nullptr;     // [Q * kSearchMaxTerms][kKeyWords] packed as kv.hpp packs
+                           // (behind them, only in a batch that verifies a `near` query, the
+                           // Q windows: search_within)
   char* zero = nullptr;    // [SearchCounters | q_hits], zeroed per batch
   u64 zero_bytes = 0;
   SearchCounters* ctr = nullptr;
@@ -769,7 +792,8 @@ struct SearchBatch {
 // The hit arrays, sized by the batch's bound B (grown on demand).
 struct SearchHits {
   u64* pairs = nullptr;   // [cap] query << 32 | line, in arbitrary order
-  u64* cands = nullptr;   // [cap] phrase candidates: the same pair words, not yet verified
+  u64* cands = nullptr;   // [cap] phrase candidates: the same pair words, not yet verified;
+                          // `near` candidates from cands[cap - 1] downwards
   u64* zeros = nullptr;   // [cap] zero: key words 1..3 of the sort
   u64* sorted = nullptr;  // [cap]
   u64* spare = nullptr;   // [cap]
@@ -780,7 +804,12 @@ struct SearchHits {
 // Ranked: the returned lines' scores [cap], parallel to h.lines, in the words of h.pairs (the
 // score kernel has turned every pair into its rank key by then).
 inline u32* search_rank_scores(const SearchHits& h) { return reinterpret_cast<u32*>(h.pairs); }
-u64 search_upload_bytes(u32 queries);  // bytes of SearchBatch::upload a batch of Q fills
+// bytes of SearchBatch::upload a batch of Q fills (within: with one window per query)
+u64 search_upload_bytes(u32 queries, bool within = false);
+// The windows of a batch of `queries` that verifies a `near` query: [queries] u32 behind keys.
+inline u32* search_within(u64* keys, u32 queries) {
+  return reinterpret_cast<u32*>(keys + (u64)queries * kSearchMaxTerms * kKeyWords);
+}
 u64 search_batch_bytes();
 void search_batch_carve(char* base, SearchBatch* b);
 u64 search_hits_bytes(u64 cap);
@@ -797,10 +826,11 @@ void launch_search_lookup(const SearchIndex& ix, const SearchBatch& b, u32 queri
 // launch_search_order does.
 void launch_search_expand(const SearchIndex& ix, const SearchBatch& b, u32 queries, u64 x,
                           SearchHits& h, SortPlan* h_plan, hipStream_t s);
-// hits (+ phrase, when `verify`: the batch has a phrase of two or more terms) + seal over
-// the `bound` elements the lookup reported (bound <= h.cap).
+// hits (+ phrase, when `verify`: the batch has a phrase of two or more terms; + near, when
+// `near`: the batch has a kSearchNear query and its windows) + seal over the `bound`
+// elements the lookup reported (bound <= h.cap).
 void launch_search_hits(const SearchIndex& ix, const SearchBatch& b, u32 queries, u64 bound,
-                        bool verify, const SearchHits& h, hipStream_t s);
+                        bool verify, bool near, const SearchHits& h, hipStream_t s);
 // order + offsets + emit of the `hits` pairs the hit kernel wrote (b.ctr->sort_n == hits):
 // b.offsets[0 .. Q], h.lines[0 .. hits) and b.ctr->misplaced.  More than kSmallSortMax hits
 // read the sort's plan back through h_plan and synchronise `s` once, as radix_sort does.

@@ -1,4 +1,4 @@
-// Index search: all/any/phrase word queries over the inverted index in device memory
+// Index search: all/any/phrase/near word queries over the inverted index in device memory
 // (kernels.hpp "search.hip"; the semantics are engine.hpp "index search").
 //
 // launch_index has left the key-ordered records, the CSR offsets val[0 .. n] and the sorted
@@ -37,6 +37,11 @@
 //    (device/linetok.hpp), compares each emitted token's key with the query's term keys
 //    (staged in LDS) and runs a shift-and automaton over the tokens.  Lane i keeps candidate
 //    i's verdict, and the round ends in commit_hits;
+//  * search_near_kernel: the phrase kernel's skeleton and token masks (token_term_mask) over
+//    the candidates of the `near` queries, which the hit kernel keeps apart (they fill
+//    `cands` from its end).  Its state is, per term, the ordinal of the last matching token
+//    (lane j < 8 keeps term j's); only tokens with a non-zero mask are walked, and behind
+//    each a minimum over those lanes decides;
 //  * order: the device-wide radix_sort() on the one-word key, as launch_index uses it;
 //  * search_emit_kernel: lines[j] = first_line + low32(sorted[j]) and the misplaced check.
 // A ranked batch (engine.hpp "ranked search") takes another way behind the seal:
@@ -338,7 +343,7 @@ __global__ __launch_bounds__(kSearchBlock) void search_hit_kernel(
 #pragma unroll 1
     for (int j = 0; j < kSearchItems; ++j) {
       const u64 e = tile * kSearchTile + (u64)j * kSearchBlock + threadIdx.x;
-      bool hit = false, cand = false;
+      bool hit = false, cand = false, near = false;
       u32 q = 0, line = first_line;
       if (e < B) {
         // the query: q_start[q] <= e < q_start[q + 1] (q_start[0] = 0, q_start[Q] = B)
@@ -358,6 +363,8 @@ __global__ __launch_bounds__(kSearchBlock) void search_hit_kernel(
         // a phrase of two or more terms: what passes the `all` test is only a candidate
         const bool verify = (meta & kSearchPhrase) != 0 && (meta & 0xffu) >= 2u;
         const u32 mask = (info >> 16) & 0xffu;
+        // so does a `near` query to verify, of two or more distinct terms (one: `all`)
+        near = (meta & kSearchNear) != 0 && (mask & (mask - 1u)) != 0u;
         const u64* tv = t_val + (u64)q * kTerms;
         const u32* tl = t_len + (u64)q * kTerms;
         u32 term = info & 0xffu;  // `all`: the driver
@@ -386,26 +393,62 @@ __global__ __launch_bounds__(kSearchBlock) void search_hit_kernel(
                 if (((mask >> t) & 1u) && t != term)
                   hit = list_has(term_list(postings, merged, tv[t]), tl[t], line);
             }
-            cand = hit && verify;
-            hit = hit && !verify;
+            cand = hit && (verify || near);
+            hit = hit && !cand;
           }
         }
       }
       // ---- the step's candidates and hits: the wave is converged here ----
-      const u64 cm = dev::ballot(cand);
-      if (cm) {  // (wave-uniform)
-        const int first = __ffsll((unsigned long long)cm) - 1;
-        u32 at = 0;
-        if (lane == first) at = atomicAdd(&ctr->cands, (u32)__popcll(cm));
-        at = (u32)__shfl((int)at, first, 64);
-        if (cand) {
-          const u64 slot = (u64)at + dev::lanes_below(cm);
-          if (slot < pair_cap) cands[slot] = ((u64)q << 32) | (u64)(line - first_line);
+      if (dev::ballot(cand)) {  // (wave-uniform)
+        // a phrase's from cands[0] upwards, a near query's from cands[pair_cap - 1] downwards
+        const u64 nm = dev::ballot(cand && near);
+        const u64 cm = dev::ballot(cand && !near);
+        if (cm) {  // (wave-uniform)
+          const int first = __ffsll((unsigned long long)cm) - 1;
+          u32 at = 0;
+          if (lane == first) at = atomicAdd(&ctr->cands, (u32)__popcll(cm));
+          at = (u32)__shfl((int)at, first, 64);
+          if (cand && !near) {
+            const u64 slot = (u64)at + dev::lanes_below(cm);
+            if (slot < pair_cap) cands[slot] = ((u64)q << 32) | (u64)(line - first_line);
+          }
+        }
+        if (nm) {  // (wave-uniform)
+          const int first = __ffsll((unsigned long long)nm) - 1;
+          u32 at = 0;
+          if (lane == first) at = atomicAdd(&ctr->ncands, (u32)__popcll(nm));
+          at = (u32)__shfl((int)at, first, 64);
+          if (cand && near) {
+            const u64 slot = (u64)at + dev::lanes_below(nm);
+            if (slot < pair_cap)
+              cands[pair_cap - 1 - slot] = ((u64)q << 32) | (u64)(line - first_line);
+          }
         }
       }
       commit_hits(hit, q, line - first_line, pairs, pair_cap, q_hits, ctr);
     }
   }
+}
+
+// Bit j: the token that starts at row[at] matches term j of the m keys at qk -- it equals
+// the key, or (pre bit j: a prefix term) starts with the key's bytes.
+__device__ __forceinline__ u32 token_term_mask(const unsigned char* row, int at,
+                                               const DelimMask& dm, int max_key_len,
+                                               const u64* qk, u32 m, u32 pre) {
+  u64 w0, w1, w2, w3;
+  dev::pack_row_key(row, at, dm, max_key_len, &w0, &w1, &w2, &w3);
+  u32 eq = 0;
+  for (u32 j = 0; j < m; ++j) {
+    const u64* k = qk + j * kKeyWords;
+    if ((pre >> j) & 1u) {  // (wave-uniform) the token starts with the term's bytes
+      eq |= (u32)(k[0] == (w0 & key_word_mask(k[0])) && k[1] == (w1 & key_word_mask(k[1])) &&
+                  k[2] == (w2 & key_word_mask(k[2])) && k[3] == (w3 & key_word_mask(k[3])))
+            << j;
+      continue;
+    }
+    eq |= (u32)(k[0] == w0 && k[1] == w1 && k[2] == w2 && k[3] == w3) << j;
+  }
+  return eq;
 }
 
 // One wave per candidate; a wave takes `group` (<= 64) consecutive candidates per round,
@@ -472,20 +515,7 @@ __global__ __launch_bounds__(kPhraseBlock) void search_phrase_kernel(
         const u32 ord = seen + (u32)__popcll(starts & below);
         const bool emit = ((starts >> lane) & 1ull) && ord < E;
         u32 eq = 0;  // bit j: this lane's token equals term j
-        if (emit) {
-          u64 w0, w1, w2, w3;
-          dev::pack_row_key(row, lane, dm, max_key_len, &w0, &w1, &w2, &w3);
-          for (u32 j = 0; j < m; ++j) {
-            const u64* k = qk + j * kKeyWords;
-            if ((pre >> j) & 1u) {  // (wave-uniform) the token starts with the term's bytes
-              eq |= (u32)(k[0] == (w0 & key_word_mask(k[0])) && k[1] == (w1 & key_word_mask(k[1])) &&
-                          k[2] == (w2 & key_word_mask(k[2])) && k[3] == (w3 & key_word_mask(k[3])))
-                    << j;
-              continue;
-            }
-            eq |= (u32)(k[0] == w0 && k[1] == w1 && k[2] == w2 && k[3] == w3) << j;
-          }
-        }
+        if (emit) eq = token_term_mask(row, lane, dm, max_key_len, qk, m, pre);
         // the automaton over the step's emitted tokens in order (all wave-uniform)
         u64 em = dev::ballot(emit);
         if (dev::ballot(eq != 0u) == 0) {
@@ -508,6 +538,112 @@ __global__ __launch_bounds__(kPhraseBlock) void search_phrase_kernel(
       if ((u32)lane == i) hit = match;
     }
     if (lane == 0) atomicAdd(&ctr->verified, cnt);
+    commit_hits(hit, (u32)(mine >> 32), (u32)mine, pairs, pair_cap, q_hits, ctr);
+  }
+}
+
+// The phrase kernel's sibling for `near` queries (engine.hpp "index search"): the same rounds
+// over the near candidates, which the hit kernel wrote from cands[pair_cap - 1] downwards,
+// the same walk and the same token masks.  In place of the automaton: per term the ordinal
+// of the last token that matched it.  Lane j < 8 keeps term j's in one register (updated by
+// a select: no indexing, no scratch; 0: not seen yet); eight scalars and a set of seen terms
+// instead cost 104 SGPRs and a wave of occupancy.  Only the step's tokens whose mask is
+// non-zero are walked, in order; behind each, the minimum over lanes 0 .. 7 (three DPP
+// steps) tells whether every term has been seen and where the shortest covering window that
+// ends there starts: the line matches when ord - min < W.  (A minimal covering window always
+// ends at a matching token.)  The state carries across the 64-byte steps; ordinals and W
+// are full u32.
+__global__ __launch_bounds__(kPhraseBlock) void search_near_kernel(
+    const char* __restrict__ text, u64 bytes, const u64* __restrict__ nl_pos,
+    const MapCounters* __restrict__ lctr, DelimMask dm, int emits_per_line, int max_key_len,
+    u32 group, const u32* __restrict__ q_meta, const u64* __restrict__ keys, u32 Q,
+    const u64* __restrict__ cands, u64* __restrict__ pairs, u64 pair_cap,
+    u32* __restrict__ q_hits, SearchCounters* __restrict__ ctr) {
+  __shared__ unsigned char s_row[kPhraseWaves][dev::kLineRow];
+  __shared__ u64 s_keys[kPhraseWaves][kTerms * kKeyWords];
+  const int lane = dev::lane_id();
+  unsigned char* row = s_row[dev::wave_id()];
+  u64* qk = s_keys[dev::wave_id()];
+  const u64 num_nl = lctr->num_newlines;  // (bytes > 0, the launch's check: num_nl + 1 lines)
+  const u32 C = ctr->ncands <= pair_cap ? ctr->ncands : 0u;  // (an overflow: the host throws)
+  const u32 wave = blockIdx.x * kPhraseWaves + dev::wave_id();
+  // a round of all waves: at most kPhraseMaxBlocks * kPhraseWaves * 64 = 2^19 candidates
+  const u32 stride = gridDim.x * kPhraseWaves * group;
+  const u64 below = lane ? (~0ull >> (64 - lane)) : 0ull;  // the lanes below this one
+  const u32 E = (u32)emits_per_line;
+  for (u64 g0 = (u64)wave * group; g0 < C; g0 += stride) {  // (wave-uniform)
+    const u32 cnt = (u32)(g0 + group < C ? group : C - g0);
+    // lane i: candidate i (g0 + lane < C <= pair_cap: inside cands)
+    const u64 mine = (u32)lane < cnt ? cands[pair_cap - 1 - (g0 + lane)] : 0ull;
+    bool hit = false;
+    u32 q_loaded = ~0u;  // the query whose term keys the wave's LDS row holds
+    for (u32 i = 0; i < cnt; ++i) {
+      const u32 q = (u32)__shfl((int)(u32)(mine >> 32), (int)i, 64);
+      const u64 line = (u32)__shfl((int)(u32)mine, (int)i, 64);
+      if (q >= Q || line > num_nl) continue;  // (wave-uniform; never: the hit kernel's words)
+      const u32 meta = q_meta[q];
+      const u32 m = meta & 0xffu;
+      if (m == 0 || m > (u32)kTerms) continue;    // (never: the host checked the batch)
+      const u32 pre = (meta >> kSearchPrefixShift) & 0xffu;  // bit j: term j is a prefix term
+      // the batch's windows stand behind its keys (search_within)
+      const u32 W = reinterpret_cast<const u32*>(keys + (u64)Q * kTerms * kKeyWords)[q];
+      if (q != q_loaded) {  // (wave-uniform) neighbours mostly share their query
+        __builtin_amdgcn_wave_barrier();  // the previous candidate's key reads are done
+        if (lane < kTerms * kKeyWords) qk[lane] = keys[(u64)q * kTerms * kKeyWords + lane];
+        __builtin_amdgcn_wave_barrier();
+        q_loaded = q;
+      }
+      const u64 start = line ? nl_pos[line - 1] + 1 : 0;
+      const u64 end = line < num_nl ? nl_pos[line] : bytes;
+      u32 seen = 0;  // token starts of this line before the current step
+      // lane j < 8: 1 + the ordinal of the last token that matched term min(j, m - 1) (the
+      // lanes behind the query's terms repeat its last one), 0: none yet
+      const u32 term = min((u32)(lane & 7), m - 1u);
+      u32 lastv = 0;
+      u64 carry = 0;
+      bool match = false;
+      for (u64 pos = start; pos < end && seen < E && !match; pos += 64) {
+        const u64 p = pos + lane;
+        const unsigned c = p < end ? (unsigned char)text[p] : 0u;
+        const u64 p2 = pos + 64 + lane;
+        const unsigned c2 = (lane < 32 && p2 < end) ? (unsigned char)text[p2] : 0u;
+        __builtin_amdgcn_wave_barrier();  // the previous step's key reads are done
+        row[lane] = (unsigned char)c;
+        if (lane < 32) row[64 + lane] = (unsigned char)c2;
+        __builtin_amdgcn_wave_barrier();
+        bool last;
+        const u64 starts = dev::step_starts(c, dm, &carry, &last);
+        const u32 ord = seen + (u32)__popcll(starts & below);
+        const bool emit = ((starts >> lane) & 1ull) && ord < E;
+        u32 eq = 0;  // bit j: this lane's token matches term j
+        if (emit) eq = token_term_mask(row, lane, dm, max_key_len, qk, m, pre);
+        // the step's matching tokens in order (all wave-uniform)
+        u64 mm = dev::ballot(eq != 0u);
+        while (mm) {
+          const int tl = __ffsll((unsigned long long)mm) - 1;
+          const u32 e = (u32)__builtin_amdgcn_readlane((int)eq, tl);
+          const u32 o = (u32)__builtin_amdgcn_readlane((int)ord, tl);  // its ordinal
+          lastv = ((e >> term) & 1u) ? o + 1u : lastv;  // (lanes >= 8: never read)
+          // lane 7: the minimum over lanes 0 .. 7 (row_shr 1, 2, 4; a lane without a source
+          // reads 0, which never reaches lane 7)
+          u32 x = lastv;
+          x = min(x, dev::dpp_mov<0x111, 0xf>(x));
+          x = min(x, dev::dpp_mov<0x112, 0xf>(x));
+          x = min(x, dev::dpp_mov<0x114, 0xf>(x));
+          const u32 first = (u32)__builtin_amdgcn_readlane((int)x, 7);
+          // every term seen, and the tokens first - 1 .. o are at most W
+          if (first != 0u && o + 1u - first < W) {
+            match = true;
+            break;
+          }
+          mm &= mm - 1;
+        }
+        seen += (u32)__popcll(starts);
+        if (last) break;  // a NUL, or the line end, inside this step
+      }
+      if ((u32)lane == i) hit = match;
+    }
+    if (lane == 0) atomicAdd(&ctr->nverified, cnt);
     commit_hits(hit, (u32)(mine >> 32), (u32)mine, pairs, pair_cap, q_hits, ctr);
   }
 }
@@ -627,7 +763,7 @@ constexpr u64 kQT = kQ * kSearchMaxTerms;
 // The batch block's parts in order.
 template <class Take>
 void batch_layout(Take&& take) {
-  take(search_upload_bytes((u32)kQ));          // upload: q_meta | keys
+  take(search_upload_bytes((u32)kQ, true));    // upload: q_meta | keys | within
   take(64 + kQ * 4);                           // zero: ctr (64 B) | q_hits
   take(kQT * 8);                               // t_val
   take(kQT * 4);                               // t_len
@@ -659,8 +795,8 @@ void hits_layout(u64 cap, Take&& take) {
 
 }  // namespace
 
-u64 search_upload_bytes(u32 queries) {
-  return kQ * 4 + (u64)queries * kSearchMaxTerms * kKeyWords * 8;
+u64 search_upload_bytes(u32 queries, bool within) {
+  return kQ * 4 + (u64)queries * kSearchMaxTerms * kKeyWords * 8 + (within ? (u64)queries * 4 : 0);
 }
 
 u64 search_batch_bytes() {
@@ -776,7 +912,7 @@ void launch_search_expand(const SearchIndex& ix, const SearchBatch& b, u32 queri
 }
 
 void launch_search_hits(const SearchIndex& ix, const SearchBatch& b, u32 queries, u64 bound,
-                        bool verify, const SearchHits& h, hipStream_t s) {
+                        bool verify, bool near, const SearchHits& h, hipStream_t s) {
   LOCUST_CHECK_ARG(bound < (1ull << 32) && bound <= h.cap,
                    "search: " + std::to_string(bound) + " list elements exceed the workspace (" +
                        std::to_string(h.cap) + ")");
@@ -798,6 +934,19 @@ void launch_search_hits(const SearchIndex& ix, const SearchBatch& b, u32 queries
     const u32 blocks = (u32)std::min<u64>(div_up(div_up(bound, (u64)group), (u64)kPhraseWaves),
                                           (u64)kPhraseMaxBlocks);
     search_phrase_kernel<<<dim3(blocks), dim3(kPhraseBlock), 0, s>>>(
+        ix.text, ix.bytes, ix.nl_pos, ix.lctr, ix.dm, ix.emits_per_line, ix.max_key_len, group,
+        b.q_meta, b.keys, queries, h.cands, h.pairs, h.cap, b.q_hits, b.ctr);
+    LOCUST_HIP_LAUNCH_CHECK();
+  }
+  if (bound && near && ix.bytes) {
+    LOCUST_CHECK_ARG(ix.text && ix.nl_pos && ix.lctr && ix.emits_per_line > 0 &&
+                         ix.max_key_len > 0 && ix.max_key_len <= kKeyBytes,
+                     "search: a near query needs the index's text view");
+    // the phrase kernel's grid: at most `bound` candidates
+    const u32 group = (u32)std::min<u64>(div_up(bound, (u64)kPhraseMaxBlocks), 64);
+    const u32 blocks = (u32)std::min<u64>(div_up(div_up(bound, (u64)group), (u64)kPhraseWaves),
+                                          (u64)kPhraseMaxBlocks);
+    search_near_kernel<<<dim3(blocks), dim3(kPhraseBlock), 0, s>>>(
         ix.text, ix.bytes, ix.nl_pos, ix.lctr, ix.dm, ix.emits_per_line, ix.max_key_len, group,
         b.q_meta, b.keys, queries, h.cands, h.pairs, h.cap, b.q_hits, b.ctr);
     LOCUST_HIP_LAUNCH_CHECK();
@@ -843,7 +992,7 @@ void launch_search_rank(const SearchIndex& ix, const SearchBatch& b, u32 queries
                                                             nullptr);
   LOCUST_HIP_LAUNCH_CHECK();
   if (hits == 0) return;
-  // the phrase kernel is done with `cands`: the rank keys go there
+  // the phrase and near kernels are done with `cands`: the rank keys go there
   const u32 sblocks = (u32)std::min<u64>(div_up(hits, (u64)kSearchTile), (u64)kSearchMaxBlocks);
   search_score_kernel<<<dim3(sblocks), dim3(kSearchBlock), 0, s>>>(
       ix.postings, b.merged, ix.val, ix.n, ix.first_line, b.q_info, b.t_val, b.t_len, queries,

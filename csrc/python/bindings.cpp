@@ -95,7 +95,8 @@ struct PyIndexResult {
   IndexResult x;
   JobConfig cfg;  // the job's delimiters and max_key_len: what search() validates terms by
   PySearchResult search(const std::vector<std::vector<std::string>>& queries,
-                        const std::vector<int>& any, const py::object& rank, bool wildcard) const;
+                        const std::vector<int>& any, const py::object& rank, bool wildcard,
+                        const std::vector<u64>& within) const;
   py::list entries() const { return PyResult{x.words}.entries(); }
   py::list postings() const {
     py::list out;
@@ -194,18 +195,24 @@ struct PySearchResult {
   }
 };
 
-// queries: term lists; any[i]: query i's mode -- 0 `all`, 2 `phrase`, every other value `any`
-// (any.size() == queries.size()).  wildcard: make_search_query's rule for a trailing `*`.
+// queries: term lists; any[i]: query i's mode -- 0 `all`, 2 `phrase`, 3 `near`, every other
+// value `any` (any.size() == queries.size()).  wildcard: make_search_query's rule for a
+// trailing `*`.  within: empty, or one window per query (0: none; check_search_queries holds
+// it against the mode).
 std::vector<SearchQuery> to_queries(const std::vector<std::vector<std::string>>& queries,
-                                    const std::vector<int>& any, bool wildcard) {
+                                    const std::vector<int>& any, bool wildcard,
+                                    const std::vector<u64>& within) {
   LOCUST_CHECK_ARG(any.size() == queries.size(), "search: one mode per query");
+  LOCUST_CHECK_ARG(within.empty() || within.size() == queries.size(),
+                   "search: one window (within) per query, or none");
   std::vector<SearchQuery> out(queries.size());
   for (size_t i = 0; i < queries.size(); ++i)
     out[i] = make_search_query(queries[i],
                                any[i] == 0   ? SearchMode::kAll
                                : any[i] == 2 ? SearchMode::kPhrase
+                               : any[i] == 3 ? SearchMode::kNear
                                              : SearchMode::kAny,
-                               wildcard);
+                               wildcard, within.empty() ? 0 : within[i]);
   return out;
 }
 
@@ -225,8 +232,8 @@ u64 to_rank(const py::object& rank) {
 
 PySearchResult PyIndexResult::search(const std::vector<std::vector<std::string>>& queries,
                                      const std::vector<int>& any, const py::object& rank,
-                                     bool wildcard) const {
-  const std::vector<SearchQuery> q = to_queries(queries, any, wildcard);
+                                     bool wildcard, const std::vector<u64>& within) const {
+  const std::vector<SearchQuery> q = to_queries(queries, any, wildcard, within);
   const u64 k = to_rank(rank);
   py::gil_scoped_release nogil;
   return PySearchResult{search_index(x, q, cfg, k)};
@@ -363,8 +370,9 @@ class PyGpuEngine {
   PySearchResult run_search(const std::string& text,
                             const std::vector<std::vector<std::string>>& queries,
                             const std::vector<int>& any, u64 first_line,
-                            const py::object& rank, bool wildcard) {
-    const std::vector<SearchQuery> q = to_queries(queries, any, wildcard);
+                            const py::object& rank, bool wildcard,
+                            const std::vector<u64>& within) {
+    const std::vector<SearchQuery> q = to_queries(queries, any, wildcard, within);
     const u64 k = to_rank(rank);
     py::gil_scoped_release nogil;
     return PySearchResult{eng_.run_search(as_input(text, first_line), q, k)};
@@ -372,16 +380,17 @@ class PyGpuEngine {
   PySearchResult run_search_text(const HostText& t,
                                  const std::vector<std::vector<std::string>>& queries,
                                  const std::vector<int>& any, u64 first_line,
-                                 const py::object& rank, bool wildcard) {
-    const std::vector<SearchQuery> q = to_queries(queries, any, wildcard);
+                                 const py::object& rank, bool wildcard,
+                            const std::vector<u64>& within) {
+    const std::vector<SearchQuery> q = to_queries(queries, any, wildcard, within);
     const u64 k = to_rank(rank);
     py::gil_scoped_release nogil;
     return PySearchResult{eng_.run_search(t.input(first_line), q, k)};
   }
   PySearchResult search_resident(const std::vector<std::vector<std::string>>& queries,
                                  const std::vector<int>& any, const py::object& rank,
-                                 bool wildcard) {
-    const std::vector<SearchQuery> q = to_queries(queries, any, wildcard);
+                                 bool wildcard, const std::vector<u64>& within) {
+    const std::vector<SearchQuery> q = to_queries(queries, any, wildcard, within);
     const u64 k = to_rank(rank);
     py::gil_scoped_release nogil;
     return PySearchResult{eng_.search_resident(q, k)};
@@ -796,6 +805,7 @@ PYBIND11_MODULE(_locust, m) {
       .def("lines", &PyIndexResult::lines, py::arg("key"), py::arg("unique") = false)
       .def("_search", &PyIndexResult::search, py::arg("queries"), py::arg("any"),
            py::arg("rank") = py::none(), py::arg("wildcard") = false,
+           py::arg("within") = std::vector<u64>(),
            "The host evaluation of all/any queries (any[i]: query i's mode) over this index.")
       .def("times", &PyIndexResult::times)
       .def("format", &PyIndexResult::format)
@@ -878,13 +888,14 @@ PYBIND11_MODULE(_locust, m) {
            py::arg("first_line") = 0)
       .def("run_search", &PyGpuEngine::run_search, py::arg("text"), py::arg("queries"),
            py::arg("any"), py::arg("first_line") = 0, py::arg("rank") = py::none(),
-           py::arg("wildcard") = false,
+           py::arg("wildcard") = false, py::arg("within") = std::vector<u64>(),
            "WordCount of text, its index, and all/any queries answered on the device.")
       .def("run_search_text", &PyGpuEngine::run_search_text, py::arg("text"), py::arg("queries"),
            py::arg("any"), py::arg("first_line") = 0, py::arg("rank") = py::none(),
-           py::arg("wildcard") = false)
+           py::arg("wildcard") = false, py::arg("within") = std::vector<u64>())
       .def("search_resident", &PyGpuEngine::search_resident, py::arg("queries"), py::arg("any"),
            py::arg("rank") = py::none(), py::arg("wildcard") = false,
+           py::arg("within") = std::vector<u64>(),
            "Another batch from the index the last run_index / run_search left on the device.")
       .def("top_counts", &PyGpuEngine::top_counts, py::arg("records"), py::arg("k"),
            "The selection kernels alone over key-sorted (key, count) records.")
@@ -905,12 +916,15 @@ PYBIND11_MODULE(_locust, m) {
   m.def("cpu_run_search", [](const JobConfig& cfg, const std::string& text,
                              const std::vector<std::vector<std::string>>& queries,
                              const std::vector<int>& any, u64 first_line,
-                             const py::object& rank, bool wildcard) {
+                             const py::object& rank, bool wildcard,
+                             const std::vector<u64>& within) {
     CpuWordCount eng(cfg);
     return PySearchResult{eng.run_search(as_input(text, first_line),
-                                         to_queries(queries, any, wildcard), to_rank(rank))};
+                                         to_queries(queries, any, wildcard, within),
+                                         to_rank(rank))};
   }, py::arg("cfg"), py::arg("text"), py::arg("queries"), py::arg("any"),
-        py::arg("first_line") = 0, py::arg("rank") = py::none(), py::arg("wildcard") = false);
+        py::arg("first_line") = 0, py::arg("rank") = py::none(), py::arg("wildcard") = false,
+        py::arg("within") = std::vector<u64>());
   m.def("check_search_merge", &check_search_merge, py::arg("queries"), py::arg("elements"),
         "Throws when a device batch's prefix terms would merge 2^32 list elements or more.");
   m.def("cpu_map_stage", [](const JobConfig& cfg, const std::string& text) {

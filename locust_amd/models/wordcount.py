@@ -15,29 +15,49 @@ from ..config import make_config, make_dist_config
 _C = load()
 
 
-_SEARCH_MODES = {"all": 0, "any": 1, "phrase": 2}
+_SEARCH_MODES = {"all": 0, "any": 1, "phrase": 2, "near": 3}
 
 
-def _search_args(queries, mode):
-    """(term lists, one mode flag per query: 0 all, 1 any, 2 phrase) for the native search
-    entry points."""
+def _search_args(queries, mode, within=None):
+    """(term lists, one mode flag per query: 0 all, 1 any, 2 phrase, 3 near, one window per
+    query: 0 none) for the native search entry points."""
     queries = [list(q) for q in queries]
     modes = [mode] * len(queries) if isinstance(mode, str) else list(mode)
     if len(modes) != len(queries):
         raise ValueError("search: one mode per query")
     for m in modes:
         if m not in _SEARCH_MODES:
-            raise ValueError("search: mode must be 'all', 'any' or 'phrase', not %r" % (m,))
-    return queries, [_SEARCH_MODES[m] for m in modes]
+            raise ValueError("search: mode must be 'all', 'any', 'phrase' or 'near', not %r"
+                             % (m,))
+    if not isinstance(within, (list, tuple)):  # one window for the batch's near queries
+        windows = [within if m == "near" else None for m in modes]
+        if within is not None and "near" not in modes:
+            raise ValueError("search: within is the window of a 'near' query; no query of "
+                             "this batch is one")
+    else:
+        windows = list(within)
+        if len(windows) != len(queries):
+            raise ValueError("search: one window (within) per query, None for a query that "
+                             "is not 'near'")
+    for m, w in zip(modes, windows):
+        if m != "near":
+            if w is not None:
+                raise ValueError("search: within=%r on a %r query; only a 'near' query takes "
+                                 "a window" % (w, m))
+        elif isinstance(w, bool) or not isinstance(w, int) or not 1 <= w < 1 << 32:
+            raise ValueError("search: a 'near' query takes within=W, an integer with "
+                             "1 <= W < 2^32, not %r" % (w,))
+    return queries, [_SEARCH_MODES[m] for m in modes], [w or 0 for w in windows]
 
 
-def _index_search(self, queries, mode="all", rank=None, wildcard=False):
+def _index_search(self, queries, mode="all", rank=None, wildcard=False, within=None):
     """All/any word queries over this index, evaluated on the host (``SearchResult``):
-    ``queries``, ``mode`` and ``rank`` as ``Engine.run_search`` takes them, any number of
-    queries.  A ``"phrase"`` query is refused: the index holds no positions, so a phrase
-    needs the text (``Engine.run_search``, ``search_text``)."""
-    queries, flags = _search_args(queries, mode)
-    return self._search(queries, flags, rank, bool(wildcard))
+    ``queries``, ``mode``, ``rank`` and ``within`` as ``Engine.run_search`` takes them, any
+    number of queries.  A ``"phrase"`` query, and a ``"near"`` query of two or more terms, is
+    refused: the index holds no positions, so they need the text (``Engine.run_search``,
+    ``search_text``)."""
+    queries, flags, windows = _search_args(queries, mode, within)
+    return self._search(queries, flags, rank, bool(wildcard), windows)
 
 
 _C.IndexResult.search = _index_search
@@ -80,18 +100,22 @@ class Engine:
         return self._eng.run_index(text, first_line)
 
     def run_search(self, text: bytes, queries, mode="all", first_line: int = 0, rank=None,
-                   wildcard=False):
+                   wildcard=False, within=None):
         """WordCount of ``text``, its inverted index, and a batch of word queries answered
         from it (``SearchResult``).  ``queries`` is a list of term lists (1 to 8 byte-string
         terms each); ``mode`` is ``"all"`` (lines that hold every term), ``"any"`` (lines
-        that hold at least one) or ``"phrase"`` (lines on which the terms are consecutive
-        tokens, in order: ``oracle.phrase`` states the rules), or a list with one mode per
-        query.  ``lines(i)`` are query
+        that hold at least one), ``"phrase"`` (lines on which the terms are consecutive
+        tokens, in order: ``oracle.phrase`` states the rules) or ``"near"`` (lines on which
+        some ``within`` consecutive tokens match every term, in any order: ``oracle.near``
+        states the rules), or a list with one mode per query.  ``within`` is the window of
+        the ``"near"`` queries, which need one: an int ``W`` with ``1 <= W < 2**32`` for all
+        of them, or a list with one entry per query, ``None`` for a query that is not
+        ``"near"``.  ``lines(i)`` are query
         ``i``'s global line numbers, ascending, each once.  On the GPU the index stays in
         device memory and only the answers cross PCIe (at most ``_C.kSearchMaxQueries``
         queries per batch; ``run_index(text).search(...)`` evaluates any number of all/any
-        queries on the host).  A phrase is verified on the device against the engine's own
-        copy of the text; the CPU engine answers phrases of any size.
+        queries on the host).  A phrase or a near query is verified on the device against
+        the engine's own copy of the text; the CPU engine answers them at any size.
 
         ``rank=K`` (``K >= 1``, one per batch) answers every query's best ``K`` lines, best
         first (``oracle.rank`` states the score): ``lines(i)`` are in the order (score
@@ -106,22 +130,23 @@ class Engine:
         ``wildcard=True`` states the rules).  A lone ``*`` is refused and a ``*`` anywhere
         else is literal; without ``wildcard`` every ``*`` is.  On the GPU the lists are merged
         on the device; ``merged`` is the number of list elements the batch merged."""
-        queries, flags = _search_args(queries, mode)
+        queries, flags, windows = _search_args(queries, mode, within)
         if self.cpu:
             return _C.cpu_run_search(self.cfg, text, queries, flags, first_line, rank,
-                                     bool(wildcard))
-        return self._eng.run_search(text, queries, flags, first_line, rank, bool(wildcard))
+                                     bool(wildcard), windows)
+        return self._eng.run_search(text, queries, flags, first_line, rank, bool(wildcard),
+                                    windows)
 
-    def search_resident(self, queries, mode="all", rank=None, wildcard=False):
+    def search_resident(self, queries, mode="all", rank=None, wildcard=False, within=None):
         """Another batch from the index this engine's last job left on the device; that
         job must have been a ``run_index`` or a ``run_search`` (GPU engines only).  Every
-        mode of ``run_search``: the job's text is resident too, so phrases are answered.
-        ``rank`` as ``run_search`` takes it."""
+        mode of ``run_search``: the job's text is resident too, so phrases and near queries
+        are answered.  ``rank`` and ``within`` as ``run_search`` takes them."""
         if self.cpu:
             raise _C.LocustError("search_resident needs a GPU engine: the CPU engine keeps "
                                  "no index (use run_index(text).search(...))")
-        queries, flags = _search_args(queries, mode)
-        return self._eng.search_resident(queries, flags, rank, bool(wildcard))
+        queries, flags, windows = _search_args(queries, mode, within)
+        return self._eng.search_resident(queries, flags, rank, bool(wildcard), windows)
 
     def top_counts(self, records: list[tuple[bytes, int]], k: int):
         """The selection alone over (key, count) records sorted by key with distinct
@@ -216,23 +241,23 @@ def index_file(path: str, line_start: int = -1, line_end: int = -1, backend: str
 
 
 def search_text(text: bytes, queries, mode="all", backend: str = "gpu", cfg=None,
-                first_line: int = 0, rank=None, wildcard=False, **kw):
-    """All/any/phrase word queries over ``text`` (``SearchResult``); see
+                first_line: int = 0, rank=None, wildcard=False, within=None, **kw):
+    """All/any/phrase/near word queries over ``text`` (``SearchResult``); see
     ``Engine.run_search``."""
     cfg = cfg if cfg is not None else make_config(backend, **kw)
     nlines = text.count(b"\n") + (1 if text and not text.endswith(b"\n") else 0)
-    return Engine(cfg, max(len(text), 1), max(nlines, 1)).run_search(text, queries, mode,
-                                                                      first_line, rank, wildcard)
+    return Engine(cfg, max(len(text), 1), max(nlines, 1)).run_search(
+        text, queries, mode, first_line, rank, wildcard, within)
 
 
 def search_file(path: str, queries, mode="all", line_start: int = -1, line_end: int = -1,
-                backend: str = "gpu", cfg=None, rank=None, wildcard=False, **kw):
-    """All/any/phrase word queries over a file or its line window, answered with the file's
+                backend: str = "gpu", cfg=None, rank=None, wildcard=False, within=None, **kw):
+    """All/any/phrase/near word queries over a file or its line window, answered with the file's
     own (global) line numbers."""
     cfg = cfg if cfg is not None else make_config(backend, **kw)
     text, nlines, first, _total = _C.load_lines(path, line_start, line_end, cfg.ref_compat)
-    return Engine(cfg, max(len(text), 1), max(nlines, 1)).run_search(text, queries, mode, first,
-                                                                      rank, wildcard)
+    return Engine(cfg, max(len(text), 1), max(nlines, 1)).run_search(
+        text, queries, mode, first, rank, wildcard, within)
 
 
 def map_stage(path: str, spill: str, line_start: int = -1, line_end: int = -1,

@@ -295,6 +295,57 @@ def phrase(text: bytes, terms, delims: bytes = DEFAULT_DELIMS, emits: int = 20,
     return lines, counts
 
 
+MAX_SEARCH_WITHIN = (1 << 32) - 1
+
+
+def near(text: bytes, terms, within: int, delims: bytes = DEFAULT_DELIMS, emits: int = 20,
+         max_key: int = 29, first_line: int = 0, *, wildcard: bool = False):
+    """One proximity query over ``text``: ``(lines, counts)``, as ``search`` answers.
+
+    `near` answers the lines on which the terms occur within ``within`` = W tokens of one
+    another, in any order; W is an integer with 1 <= W <= 2^32 - 1 (``ValueError``
+    otherwise).  A line's token sequence is exactly the phrase mode's: the job's delimiter
+    set, a NUL ends the line's tokens, only the first emits_per_line tokens exist, each
+    token cut to max_key_len bytes.  A line with tokens k_0 .. k_(n-1) matches when
+    positions a <= b exist with b - a + 1 <= W such that every term is matched by at least
+    one token k_i, a <= i <= b.  A plain term, cut to max_key_len bytes, matches a token by
+    equality; with ``wildcard=True`` a prefix term (``prefix_terms``) matches a token whose
+    key starts with ``p``.  Order does not matter, a repeated term changes nothing (set
+    semantics, as in `all`), one token may satisfy several terms, a window never crosses a
+    line end, and an absent term gives an empty answer.  A one-term query and every
+    W >= emits_per_line answer as `all` does.  ``counts[t]`` is the number of emitted tokens
+    that match term ``t``, as `all` reports it.
+
+    Terms are validated as ``search`` validates them (``ValueError``).  Written straight from
+    the paragraph above: every line is tokenised and every window of W consecutive tokens
+    tested; no index."""
+    terms = list(terms)
+    if not 1 <= len(terms) <= MAX_SEARCH_TERMS:
+        raise ValueError("a query takes 1 to %d terms" % MAX_SEARCH_TERMS)
+    if isinstance(within, bool) or not isinstance(within, int) or \
+            not 1 <= within <= MAX_SEARCH_WITHIN:
+        raise ValueError("a near query takes a window 1 <= W < 2^32, not %r" % (within,))
+    want = prefix_terms(terms, wildcard, delims, max_key)
+
+    def fits(tok, term):
+        p, pre = term
+        return tok[:len(p)] == p if pre else tok == p
+
+    lines = []
+    counts = [0] * len(want)
+    for i, line in enumerate(split_lines(text)):
+        toks, _dropped = tokenize(line, delims, emits, max_key)
+        for j, term in enumerate(want):
+            counts[j] += sum(fits(tok, term) for tok in toks)
+        # the windows of W consecutive tokens (a shorter line: the one window it has)
+        for a in range(max(len(toks) - within, 0) + 1):
+            win = toks[a:a + within]
+            if all(any(fits(tok, term) for tok in win) for term in want):
+                lines.append(first_line + i)
+                break
+    return lines, counts
+
+
 def format_search(queries, answers) -> bytes:
     """The CLI's ``--search`` result lines: one per query, ``queries[i]`` its terms and
     ``answers[i]`` its lines (every line number after one space; none after "lines:" when

@@ -22,6 +22,7 @@
 //     tokens of one another; repeat --search for a batch: answered from the index on the
 //     device, or by --backend cpu)
 //   --within W (with --match near: the window in tokens, W >= 1)
+//   --not "w1 w2" (after a --search: lines that hold one of these words are no answer of it)
 //   --rank K (with --search: each query's K best lines with their scores, best first)
 //   --wildcard (with --search: a word that ends in * is a prefix term, "ham*")
 // and a synthetic-text generator (BASELINE configs "1M lines" / "10 GB"):
@@ -91,6 +92,7 @@ struct CliArgs {
   bool index = false;  // --index: the result lines carry every word's line numbers
   // --search "w1 w2" (repeatable): the result lines are the queries' answers
   std::vector<std::string> search_args;
+  std::vector<std::string> not_args;  // parallel: the --not words of each --search, joined by ' '
   std::vector<SearchQuery> queries;
   std::string match;  // --match all|any|phrase|near ("": all)
   bool within_given = false;
@@ -147,6 +149,13 @@ void help() {
       "                             --within W consecutive tokens of the line, in any order)\n"
       "  --within W                 (--match near, which needs it: the window in tokens,\n"
       "                             1 <= W < 2^32; with W = 2 two words must be neighbours)\n"
+      "  --not \"w1 w2 ...\"          (exclusion words of the nearest --search before it, split\n"
+      "                             like the text: a line that holds one of them is no answer of\n"
+      "                             that query, whatever --match says.  Repeatable: the words add\n"
+      "                             up; a query takes 8 words in all.  A word found nowhere takes\n"
+      "                             nothing away.  With every --match, --within, --rank, --wildcard\n"
+      "                             and --backend cpu; taken away on the device before a phrase is\n"
+      "                             verified or a line is scored)\n"
       "  --rank K                   (--search: only each query's K best lines, best first, as\n"
       "                             line:score; a line's score adds, per distinct word of the\n"
       "                             query, its occurrences on the line times a weight that grows\n"
@@ -278,6 +287,13 @@ bool parse(int argc, char** argv, CliArgs* a) {
       a->index = true;
     } else if (s == "--search") {
       a->search_args.push_back(need("--search"));
+      a->not_args.emplace_back();
+    } else if (s == "--not") {
+      const std::string v = need("--not");
+      if (a->search_args.empty())
+        throw Error("--not \"" + v + "\" names words that the --search before it must not "
+                    "find on a line: give --search first");
+      a->not_args.back() += " " + v;
     } else if (s == "--match") {
       a->match = need("--match");
       if (a->match != "all" && a->match != "any" && a->match != "phrase" && a->match != "near")
@@ -394,12 +410,8 @@ bool parse(int argc, char** argv, CliArgs* a) {
                   "compat: the compat map overwrites the text the index reads again");
   }
   // the --search arguments, split with the job's own delimiter set: no term can be invalid
-  for (const std::string& arg : a->search_args) {
+  const auto words = [&](const std::string& arg) {
     std::vector<std::string> terms;
-    const SearchMode mode = a->match == "any"      ? SearchMode::kAny
-                            : a->match == "phrase" ? SearchMode::kPhrase
-                            : a->match == "near"   ? SearchMode::kNear
-                                                   : SearchMode::kAll;
     std::string cur;
     for (const char c : arg) {
       if (a->cfg.delimiters.find(c) != std::string::npos) {
@@ -410,8 +422,19 @@ bool parse(int argc, char** argv, CliArgs* a) {
       }
     }
     if (!cur.empty()) terms.push_back(cur);
+    return terms;
+  };
+  for (size_t i = 0; i < a->search_args.size(); ++i) {
+    const std::string& arg = a->search_args[i];
+    const SearchMode mode = a->match == "any"      ? SearchMode::kAny
+                            : a->match == "phrase" ? SearchMode::kPhrase
+                            : a->match == "near"   ? SearchMode::kNear
+                                                   : SearchMode::kAll;
+    const std::vector<std::string> terms = words(arg);
     if (terms.empty()) throw Error("--search \"" + arg + "\" holds no word");
-    a->queries.push_back(make_search_query(terms, mode, a->wildcard, a->within));
+    // (a --not that holds no word excludes nothing)
+    const std::vector<std::string> exclude = words(a->not_args[i]);
+    a->queries.push_back(make_search_query(terms, mode, a->wildcard, a->within, exclude));
   }
   if (!a->queries.empty()) {
     check_search_queries(a->queries, a->cfg);

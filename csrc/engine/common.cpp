@@ -380,15 +380,17 @@ PackedKey search_term_key(const std::string& term, const JobConfig& cfg) {
 }
 
 SearchQuery make_search_query(const std::vector<std::string>& terms, SearchMode mode,
-                              bool wildcard, u64 within) {
+                              bool wildcard, u64 within, const std::vector<std::string>& exclude) {
   SearchQuery q;
   q.terms = terms;
+  q.terms.insert(q.terms.end(), exclude.begin(), exclude.end());
+  q.excluded = (u32)exclude.size();
   q.mode = mode;
   q.within = within;
   if (!wildcard) return q;
   bool any = false;
-  std::vector<u8> prefix(terms.size(), 0);
-  for (size_t t = 0; t < terms.size(); ++t) {
+  std::vector<u8> prefix(q.terms.size(), 0);
+  for (size_t t = 0; t < q.terms.size(); ++t) {
     std::string& s = q.terms[t];
     LOCUST_CHECK_ARG(s != "*", "search: a lone * is no prefix term: give the prefix before "
                                "the star (ham*)");
@@ -408,7 +410,13 @@ void check_search_queries(const std::vector<SearchQuery>& queries, const JobConf
     LOCUST_CHECK_ARG(!q.terms.empty() && q.terms.size() <= (size_t)kSearchMaxTerms,
                      "search: query " + std::to_string(i) + " has " +
                          std::to_string(q.terms.size()) + " terms; a query takes 1 to " +
-                         std::to_string(kSearchMaxTerms));
+                         std::to_string(kSearchMaxTerms) +
+                         (q.excluded ? ", positive and exclusion terms together" : ""));
+    LOCUST_CHECK_ARG((size_t)q.excluded < q.terms.size(),
+                     "search: query " + std::to_string(i) + " has no positive term (" +
+                         std::to_string(q.excluded) + " exclusion terms of " +
+                         std::to_string(q.terms.size()) + "); exclusion terms take lines away "
+                         "from what at least one positive term answers");
     LOCUST_CHECK_ARG(q.prefix.empty() || q.prefix.size() == q.terms.size(),
                      "search: query " + std::to_string(i) + " has " +
                          std::to_string(q.prefix.size()) + " prefix flags for " +
@@ -513,16 +521,16 @@ SearchResult search_index_impl(const IndexResult& x, const TextInput* text,
                                u64 rank_k) {
   check_search_queries(queries, cfg);
   check_search_rank(rank_k, cfg);
-  bool verify = false;  // a phrase, or a near query, of two or more terms
+  bool verify = false;  // a phrase, or a near query, of two or more positive terms
   for (const SearchQuery& q : queries)
     verify |= (q.mode == SearchMode::kPhrase || q.mode == SearchMode::kNear) &&
-              q.terms.size() >= 2;
+              q.positives() >= 2;
   if (!text)
     for (const SearchQuery& q : queries) {
       LOCUST_CHECK_ARG(q.mode != SearchMode::kPhrase,
                        "search: a phrase query needs the text (the index holds no positions): "
                        "use search_index(index, text, queries, cfg), or run_search on an engine");
-      LOCUST_CHECK_ARG(q.mode != SearchMode::kNear || q.terms.size() < 2,
+      LOCUST_CHECK_ARG(q.mode != SearchMode::kNear || q.positives() < 2,
                        "search: a near query of two or more terms needs the text (the index "
                        "holds no positions): use search_index(index, text, queries, cfg), or "
                        "run_search on an engine");
@@ -573,10 +581,13 @@ SearchResult search_index_impl(const IndexResult& x, const TextInput* text,
   for (size_t qi = 0; qi < queries.size(); ++qi) {
     const SearchQuery& q = queries[qi];
     const size_t from = r.lines.size();
-    std::vector<List> lists;  // the present terms of distinct key ranges
+    std::vector<List> lists;  // the present positive terms of distinct key ranges
+    std::vector<List> not_lists;  // the present exclusion terms of distinct key ranges
     std::vector<std::vector<u32>> own;  // the merged lists of this query's prefix terms
+    const size_t npos = q.positives();
     bool absent = false, wild = false;
     for (size_t t = 0; t < q.terms.size(); ++t) {
+      const bool pos = t < npos;
       const PackedKey k = search_term_key(q.terms[t], cfg);
       const auto less = [](const WordCountEntry& a, const PackedKey& b) {
         return key_compare(a.key.w, b.w) < 0;
@@ -584,7 +595,7 @@ SearchResult search_index_impl(const IndexResult& x, const TextInput* text,
       const size_t lo = (size_t)(std::lower_bound(ent, ent + n, k, less) - ent);
       size_t hi = lo;
       if (search_term_prefix(q, t, cfg)) {  // the keys from p padded with 0x00 to p with 0xff
-        wild = true;
+        wild |= pos;
         PackedKey top;
         for (int j = 0; j < kKeyWords; ++j) top.w[j] = k.w[j] | ~key_word_mask(k.w[j]);
         hi = (size_t)(std::upper_bound(ent, ent + n, top,
@@ -596,12 +607,13 @@ SearchResult search_index_impl(const IndexResult& x, const TextInput* text,
         hi = lo + 1;
       }
       if (hi <= lo) {
-        absent = true;
+        absent |= pos;  // (an absent exclusion term excludes nothing)
         continue;
       }
       r.term_counts[qi * kSearchMaxTerms + t] = val[hi] - val[lo];
+      std::vector<List>& into = pos ? lists : not_lists;
       bool dup = false;
-      for (const List& o : lists) dup |= o.lo == lo && o.hi == hi;
+      for (const List& o : into) dup |= o.lo == lo && o.hi == hi;
       if (dup) continue;
       List l{x.postings.data() + val[lo], val[hi] - val[lo], lo, hi};
       if (hi - lo >= 2) {  // a concatenation of sorted lists: merge
@@ -609,8 +621,14 @@ SearchResult search_index_impl(const IndexResult& x, const TextInput* text,
         std::sort(own.back().begin(), own.back().end());
         l.p = own.back().data();
       }
-      lists.push_back(l);
+      into.push_back(l);
     }
+    // is the line one of the query's excluded lines?
+    const auto excluded = [&](u32 line) {
+      for (const List& l : not_lists)
+        if (std::binary_search(l.p, l.p + l.len, line)) return true;
+      return false;
+    };
     // the score's terms: none whose key range lies inside another's (equal ranges are one
     // list here already)
     std::vector<List> scored;
@@ -620,13 +638,13 @@ SearchResult search_index_impl(const IndexResult& x, const TextInput* text,
       if (!inside) scored.push_back(l);
     }
     if (q.mode != SearchMode::kAny) {
-      const bool phrase = q.mode == SearchMode::kPhrase && q.terms.size() >= 2;
+      const bool phrase = q.mode == SearchMode::kPhrase && npos >= 2;
       // (W >= emits_per_line: no line has more tokens, the `all` answer stands)
-      const bool near = q.mode == SearchMode::kNear && q.terms.size() >= 2 &&
+      const bool near = q.mode == SearchMode::kNear && npos >= 2 &&
                         q.within < (u64)cfg.emits_per_line;
       std::vector<PackedKey> keys, masks, toks;
-      if (phrase || near)
-        for (size_t t = 0; t < q.terms.size(); ++t) {
+      if (phrase || near)  // the positive terms only
+        for (size_t t = 0; t < npos; ++t) {
           keys.push_back(search_term_key(q.terms[t], cfg));
           if (!wild) continue;
           PackedKey m;
@@ -644,6 +662,7 @@ SearchResult search_index_impl(const IndexResult& x, const TextInput* text,
           bool hit = true;
           for (size_t i = 0; i < lists.size() && hit; ++i)
             if (i != d) hit = std::binary_search(lists[i].p, lists[i].p + lists[i].len, line);
+          hit = hit && !excluded(line);  // (before the line is read: the index decides)
           if (hit && (phrase || near)) {  // a candidate: the line itself decides
             const u64 l = line - x.first_line;
             LOCUST_CHECK_ARG(l + 1 < line_at.size(),
@@ -661,6 +680,9 @@ SearchResult search_index_impl(const IndexResult& x, const TextInput* text,
       std::sort(r.lines.begin() + (std::ptrdiff_t)from, r.lines.end());
       r.lines.erase(std::unique(r.lines.begin() + (std::ptrdiff_t)from, r.lines.end()),
                     r.lines.end());
+      if (!not_lists.empty())
+        r.lines.erase(std::remove_if(r.lines.begin() + (std::ptrdiff_t)from, r.lines.end(), excluded),
+                      r.lines.end());
     }
     r.matches.push_back(r.lines.size() - from);
     if (rank_k) {  // the matching lines' scores, the order and the cut
@@ -757,7 +779,9 @@ void format_search_output(const SearchResult& r, std::string* out) {
   out->reserve(out->size() + r.queries.size() * 48 + r.lines.size() * 6);
   for (size_t q = 0; q < r.queries.size(); ++q) {
     out->append("print query:");
+    const size_t npos = r.queries[q].positives();
     for (size_t t = 0; t < r.queries[q].terms.size(); ++t) {
+      if (t == npos) out->append(" \t not:");
       out->push_back(' ');
       out->append(r.queries[q].terms[t]);
       if (r.queries[q].is_prefix(t)) out->push_back('*');

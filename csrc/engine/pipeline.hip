@@ -2167,16 +2167,19 @@ void DevicePipeline::search_stage(const std::vector<SearchQuery>& queries, u64 r
   std::memset(keys, 0, (size_t)Q * kSearchMaxTerms * sizeof(PackedKey));
   for (u32 q = 0; q < Q; ++q) {
     const SearchQuery& sq = queries[q];
-    const bool qnear = sq.mode == SearchMode::kNear && sq.terms.size() >= 2 &&
+    // (the modes see the positive terms only; the exclusion terms stand behind them)
+    const size_t npos = sq.positives();
+    const bool qnear = sq.mode == SearchMode::kNear && npos >= 2 &&
                        sq.within < (u64)cfg.emits_per_line;
     meta[q] = (u32)sq.terms.size() | (sq.mode == SearchMode::kAny      ? kSearchAny
                                       : sq.mode == SearchMode::kPhrase ? kSearchPhrase
                                       : qnear                          ? kSearchNear
                                                                        : 0u);
     within[q] = qnear ? (u32)sq.within : 0u;
-    verify |= sq.mode == SearchMode::kPhrase && sq.terms.size() >= 2;
+    verify |= sq.mode == SearchMode::kPhrase && npos >= 2;
     near |= qnear;
     for (size_t t = 0; t < sq.terms.size(); ++t) {
+      if (t >= npos) meta[q] |= 1u << (kSearchExcludeShift + (int)t);
       // a prefix term's flag; its length needs no word: the key's non-zero bytes are it
       if (search_term_prefix(sq, t, cfg)) meta[q] |= 1u << (kSearchPrefixShift + (int)t);
       const PackedKey k = search_term_key(sq.terms[t], cfg);

@@ -379,6 +379,41 @@ void format_index_output(const IndexResult& r, std::string* out);
 // the engines take that shortcut and verify nothing.  term_counts, `merged` and the ranked
 // score (tf over the whole line, from the postings -- not over the window) are `all`'s.
 //
+// Exclusion terms.  A query has 1 or more positive terms and 0 or more exclusion terms
+// (SearchQuery::excluded: the last `excluded` entries of `terms`); together they number at
+// most kSearchMaxTerms.  An exclusion term is validated, cut to max_key_len and, with
+// wildcards, read as a prefix term exactly as a positive term is.
+//   Excluded lines.  A term's lines are the distinct lines of its postings list, as for
+//     `all`; a prefix term's list is its merged list.  A query's excluded lines are the union
+//     of its exclusion terms' lines.  An absent exclusion term excludes nothing: it does not
+//     empty the answer, unlike an absent positive term in `all`.
+//   Matching set.  The matching set is what the mode answers for the positive terms alone,
+//     minus the excluded lines.  The mode, the `near` window, the repetition rules and the
+//     one-term shortcuts apply to the positive terms only: the `near` shortcut "W >=
+//     emits_per_line answers as `all`" and the shortcut "one distinct term answers as `all`"
+//     count distinct positive terms, and phrase and `near` verification sees only the positive
+//     terms.  [alpha beta] not gamma as a phrase matches the line `alpha beta delta` and does
+//     not match `alpha beta gamma`: the second line is excluded because it holds gamma
+//     anywhere among its emitted tokens.
+//   Pure function of the index.  Exclusion depends only on the index, so a token past the
+//     emit cap excludes nothing: the rule every other mode follows.
+//   Overlap with a positive term.  An exclusion term whose words equal or contain a positive
+//     term's words empties `all`, `phrase` and `near`; in `any` it removes that term's lines
+//     from the union.  This is legal, not an error.
+//   Ranked.  `matches` counts the matching set after exclusion.  Exclusion terms take no part
+//     in the score, in the "distinct present terms" or in the nesting rule: in Ham* not
+//     Hamlet, Ham* still scores with its full merged count.  The bound score <= 32 *
+//     emits_per_line is unchanged.
+//   term_counts report every term, positive terms first and then the exclusion terms in the
+//     order given; an exclusion term reports its word's count, or its merged count.
+//   `merged`: the rule is unchanged and runs over all of the query's terms: the sum of the
+//     counts over the query's terms that cover two or more words, a term whose words repeat
+//     an earlier term's left out.  An exclusion prefix term covering two or more words is
+//     therefore merged by the expand stage and counted; one covering a single word uses that
+//     word's list in place.
+//   Refused with a clear error: a query with no positive term, more than kSearchMaxTerms
+//     terms in total, an invalid exclusion term, a lone `*` with wildcards.
+//
 // The device stage (kernels/search.hip; GpuWordCount::run_search / search_resident)
 // answers batches of up to kSearchMaxQueries queries from the index in device memory:
 // neither postings nor records cross PCIe.  A phrase or a `near` query takes its candidate
@@ -450,7 +485,10 @@ struct SearchQuery {
   SearchMode mode = SearchMode::kAll;
   u64 within = 0;  // kNear: the window W in tokens, 1 .. kSearchMaxWithin; other modes: 0
   std::vector<u8> prefix;  // empty: no prefix term; else parallel to terms, != 0: a prefix term
+  u32 excluded = 0;  // the last `excluded` entries of terms are exclusion terms ("not")
   bool is_prefix(size_t t) const { return t < prefix.size() && prefix[t] != 0; }
+  // the positive terms: terms[0 .. positives())
+  size_t positives() const { return excluded < terms.size() ? terms.size() - excluded : 0; }
 };
 struct SearchResult {
   std::vector<SearchQuery> queries;  // as asked (terms uncut)
@@ -488,12 +526,14 @@ inline bool search_term_prefix(const SearchQuery& q, size_t t, const JobConfig& 
 // The query of user terms.  wildcard: a term that ends in `*` and is longer than one byte
 // becomes a prefix term of what precedes the star; a lone `*` is an error; a `*` anywhere
 // else is literal.  Without wildcard every term is literal.
-// within: the window of a `near` query (0: none).
+// within: the window of a `near` query (0: none).  exclude: the query's exclusion terms, read
+// as `terms` are and appended behind them.
 SearchQuery make_search_query(const std::vector<std::string>& terms, SearchMode mode,
-                              bool wildcard, u64 within = 0);
-// Throws unless every query has 1..kSearchMaxTerms valid terms for cfg's delimiter set (and
-// `prefix` empty or as long as `terms`), a `near` query a window in [1, kSearchMaxWithin]
-// and every other query none (within == 0).
+                              bool wildcard, u64 within = 0,
+                              const std::vector<std::string>& exclude = {});
+// Throws unless every query has 1..kSearchMaxTerms valid terms for cfg's delimiter set, at
+// least one of them positive (and `prefix` empty or as long as `terms`), a `near` query a
+// window in [1, kSearchMaxWithin] and every other query none (within == 0).
 void check_search_queries(const std::vector<SearchQuery>& queries, const JobConfig& cfg);
 // Throws when the `elements` list elements a device batch's prefix terms merge
 // (SearchResult::merged) do not fit the merge's 32-bit element counter.
@@ -503,7 +543,7 @@ void check_search_rank(u64 rank_k, const JobConfig& cfg);
 // The host evaluation over an index result, any number of queries (cfg: the index job's
 // delimiters and max_key_len).  Throws for a phrase query and for a `near` query of two or
 // more terms: the index holds no positions, so they need the text -- the four-argument
-// overload.
+// overload (what counts are the positive terms).
 // rank_k != 0 ranks every query (scores come from the postings alone).
 SearchResult search_index(const IndexResult& x, const std::vector<SearchQuery>& queries,
                           const JobConfig& cfg, u64 rank_k = 0);
@@ -522,7 +562,8 @@ SearchResult search_index(const IndexResult& x, const TextInput& text,
 void validate_search(const SearchResult& r);
 // The result lines of a search, one per query:
 //   "print query: <terms joined by one space> \t hits: <h> \t lines: <l0> <l1> ...\n"
-// (a prefix term as it was asked: with its star)
+// (a prefix term as it was asked: with its star; <terms> are the positive terms, and a query
+// with exclusion terms prints " \t not: <those joined by one space>" before " \t hits:")
 // ranked (hits: the matches; nothing after "top:" when nothing matched):
 //   "print query: <terms> \t hits: <matches> \t top: <l0>:<s0> <l1>:<s1> ...\n"
 void format_search_output(const SearchResult& r, std::string* out);

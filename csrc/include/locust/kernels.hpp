@@ -644,6 +644,15 @@ void launch_index(const IndexJob& job, IndexWorkspace& ws, SortPlan* h_plan, hip
 //            x_len = the length of a list of two or more words that repeats no earlier
 //            term's of its query: it has to be merged; the lengths add up in ctr->merge (one
 //            atomic per wave that has any)
+//            Exclusion terms (engine.hpp "exclusion terms"; q_meta bit 24 + t: term t is
+//            one, and the host packs them behind the positive terms) are resolved like any
+//            term into t_val, t_len, x_len and the merge total, and left out of the driver
+//            choice, the bound, the dead flag, the distinct-term mask and the score mask,
+//            which all see the positive terms as if they were the whole query.  The present
+//            ones go to the hit kernel as q_info bits 8..15: bit i is set when an exclusion
+//            term's words are those of term i, the query's first term with them (itself, an
+//            earlier exclusion term or a positive term), so every exclusion list is read once
+//            and a merged list through the slot that owns it
 //   scan     one workgroup: q_start[0 .. Q] = exclusive scan of the bounds, the total B
 //   (the host reads B, the merge total X and the term counts in one readback, and sizes the
 //   hit workspace for max(B, X))
@@ -673,7 +682,11 @@ void launch_index(const IndexJob& job, IndexWorkspace& ws, SortPlan* h_plan, hip
 //            for a `near` query that needs verification (kSearchNear) and has two or more
 //            distinct terms; its candidates have a counter of their own (ncands) and fill
 //            `cands` from its last word downwards, so neither verify kernel sees the
-//            other's (cands + ncands <= B <= cap: the two ends never meet)
+//            other's (cands + ncands <= B <= cap: the two ends never meet).
+//            Before the hit / candidate split, an element of a query with exclusion lists is
+//            dropped when a binary search finds its line in one of them (term_list: merged
+//            lists too): excluded lines reach neither `cands` nor `pairs` nor q_hits.  A
+//            batch without exclusion terms only tests the empty mask
 //   phrase   (only when the batch has a phrase of two or more terms) one wave per candidate,
 //            up to 64 consecutive candidates per wave and round.  The wave re-tokenises the
 //            candidate's line with the word job's rules (device/linetok.hpp, as index.hip's
@@ -681,15 +694,16 @@ void launch_index(const IndexJob& job, IndexWorkspace& ws, SortPlan* h_plan, hip
 //            (bit j of a token's mask: it equals term j; for a prefix term: it starts with
 //            the term's bytes, (w_i & key_word_mask(k_i)) == k_i for the four key words, the
 //            masks computed in registers) and runs the shift-and automaton
-//            state = ((state << 1) | 1) & mask over the tokens in order; bit nterms - 1 set
-//            is a hit.  After a round lane i holds candidate i's verdict and the hits are
+//            state = ((state << 1) | 1) & mask over the tokens in order; bit m - 1 set
+//            is a hit (m: the positive terms, nterms - the exclusion terms; only their keys
+//            are compared).  After a round lane i holds candidate i's verdict and the hits are
 //            written as the hit kernel writes them: one atomic per wave and round for the
 //            slots, one per distinct query for q_hits; one more counts the verified candidates
 //   near     (only when the batch has a `near` query that needs verification: two or more
 //            terms and W < emits_per_line) the phrase kernel's skeleton and token masks over
 //            the `near` candidates.  In place of the automaton the wave keeps, per term, 1 +
 //            the ordinal of the last token that matched it (0: none yet): lane j < 8 holds
-//            term min(j, nterms - 1)'s in one register, updated by a select.  It walks only
+//            term min(j, m - 1)'s (m as the phrase kernel's) in one register, updated by a select.  It walks only
 //            the step's tokens whose mask is non-zero, in order; behind each, the minimum
 //            over lanes 0 .. 7 (three DPP row shifts) is non-zero when every term has been
 //            seen, and the line matches if ord + 1 - min < W (a minimal covering window
@@ -742,6 +756,8 @@ constexpr u32 kSearchPhrase = 1u << 9;                     // (neither bit: `all
 constexpr u32 kSearchNear = 1u << 10;  // a `near` query to verify (W < emits_per_line, two or
                                        // more terms); every other `near` query goes as `all`
 constexpr int kSearchPrefixShift = 16;  // q_meta bit 16 + t: term t is a prefix term
+constexpr int kSearchExcludeShift = 24;  // q_meta bit 24 + t: term t is an exclusion term (the
+                                         // last terms of the query: positive terms stand first)
 constexpr u64 kSearchMerged = 1ull << 63;  // t_val: the list lies in `merged`, not in postings
 constexpr u32 kSearchSlots = kSearchMaxQueries * kSearchMaxTerms;  // (query, term) slots
 // The index a batch is answered from (all device memory, launch_index's output).
@@ -763,7 +779,7 @@ struct SearchIndex {
 // The per-batch arrays: fixed size (kSearchMaxQueries), made by the first search job.
 struct SearchBatch {
   char* upload = nullptr;  // [q_meta | keys | within]: one H2D per batch
-  u32* q_meta = nullptr;   // [kSearchMaxQueries] nterms | mode bit
+  u32* q_meta = nullptr;   // [kSearchMaxQueries] nterms | mode bit | prefix bits | exclusion bits
   u64* keys = nullptr;     // [Q * kSearchMaxTerms][kKeyWords] packed as kv.hpp packs
                            // (behind them, only in a batch that verifies a `near` query, the
                            // Q windows: search_within)
@@ -775,8 +791,9 @@ struct SearchBatch {
                            // stage kSearchMerged | its offset in `merged` for a merged list
   u32* t_len = nullptr;    // [Q * kSearchMaxTerms] its list's length = the count of its word
                            // (prefix term: of its words); 0: absent
-  u32* q_info = nullptr;   // [Q] driver | dead << 8 | distinct-term mask << 16 | score mask
-                           // << 24 (the terms whose key range lies inside no other's)
+  u32* q_info = nullptr;   // [Q] driver | dead << 3 | exclusion lists << 8 | distinct-term
+                           // mask << 16 | score mask << 24 (the terms whose key range lies
+                           // inside no other's); both masks: positive terms only
   u32* x_len = nullptr;    // [Q * kSearchMaxTerms] the slot's merged length: t_len of a prefix
                            // term that covers two or more words and repeats no earlier term
                            // of its query, else 0

@@ -16,7 +16,10 @@
 //    walks for it.
 //    A prefix term (`ham*`, engine.hpp "prefix terms") finds the rank range of its words
 //    instead (find_prefix_range): terms are told apart by their ranges, and the lengths of
-//    the lists that cover two or more words add up to the batch's merge total X;
+//    the lists that cover two or more words add up to the batch's merge total X.
+//    An exclusion term (engine.hpp "exclusion terms"; the host packs them behind the positive
+//    terms) is resolved like any term, but stays out of the driver choice, the bound, the dead
+//    flag and both masks: the present ones' lists go to the hit kernel as a mask of their own;
 //  * search_scan_kernel: one workgroup, exclusive scan of u32 values into count + 1 u64
 //    words (the bounds -> q_start, later the hit counts -> offsets, the merged lengths of
 //    the Q * 8 slots -> x_start);
@@ -31,7 +34,8 @@
 //    terms' CSR ranges.  Every step ends in wave-level ballots: one atomic reserves the
 //    step's slots, one atomic per distinct query of the wave adds to its hit count
 //    (commit_hits).  A phrase of two or more terms is looked up and walked as `all`, but
-//    what passes is a candidate: its pair word goes to `cands`;
+//    what passes is a candidate: its pair word goes to `cands`.  Before that split, a line
+//    found in one of the query's exclusion lists is dropped: it is no hit and no candidate;
 //  * search_phrase_kernel: one wave per candidate line, up to 64 consecutive candidates per
 //    wave and round.  The wave walks the line 64 bytes per step with index.hip's tokeniser
 //    (device/linetok.hpp), compares each emitted token's key with the query's term keys
@@ -83,11 +87,13 @@ __global__ __launch_bounds__(kSearchBlock) void search_lookup_kernel(
   __shared__ u32 s_lo[kSearchBlock];
   __shared__ u32 s_hi[kSearchBlock];
   __shared__ u32 s_len[kSearchBlock];
-  __shared__ u32 s_flag[kSearchBlock];  // 1: present | 2: dup | 4: inside (below)
+  __shared__ u32 s_flag[kSearchBlock];  // 1: present | 2: dup | 4: inside | first << 4 (below)
   const u32 gid = blockIdx.x * kSearchBlock + threadIdx.x;
   const u32 q = gid / kTerms, t = gid % kTerms;
   const u32 meta = q < Q ? q_meta[q] : 0u;
   const u32 nterms = min(meta & 0xffu, (u32)kTerms);  // (the host checked: at most eight)
+  // the positive terms stand first; terms npos .. nterms - 1 are exclusion terms
+  const u32 npos = nterms - min((u32)__popc(meta >> kSearchExcludeShift), nterms);
   u32 lo = n, hi = n, len = 0;
   u64 at = 0;
   if (t < nterms) {
@@ -122,7 +128,10 @@ __global__ __launch_bounds__(kSearchBlock) void search_lookup_kernel(
   // an earlier term has the same words; inside, another present term's range holds this
   // one's (of equal ranges the first counts).  The eight threads of a query do this side by
   // side, so its first thread only has to combine eight flag words below.
+  // `inside` is the positive terms' rule among themselves (an exclusion term's is not read);
+  // first: the query's first term with this one's words, whose list stands for them all.
   bool dup = false, inside = false;
+  u32 first = t;
   if (lo < hi) {
     const u32 base = threadIdx.x - t;
     for (u32 i = 0; i < nterms; ++i) {
@@ -130,10 +139,12 @@ __global__ __launch_bounds__(kSearchBlock) void search_lookup_kernel(
       if (i == t || ilo >= ihi) continue;
       const bool same = ilo == lo && ihi == hi;
       dup |= same && i < t;
-      inside |= same ? i < t : (ilo <= lo && hi <= ihi);
+      first = same && i < first ? i : first;
+      if (i < npos) inside |= same ? i < t : (ilo <= lo && hi <= ihi);
     }
   }
-  s_flag[threadIdx.x] = (lo < hi ? 1u : 0u) | (dup ? 2u : 0u) | (inside ? 4u : 0u);
+  s_flag[threadIdx.x] =
+      (lo < hi ? 1u : 0u) | (dup ? 2u : 0u) | (inside ? 4u : 0u) | (first << 4);
   // a list of two or more words is merged (the expand stage), unless an earlier term of the
   // query has the same words.  Only a prefix term covers two words.
   const bool wide = hi - lo >= 2u && !dup;
@@ -147,9 +158,9 @@ __global__ __launch_bounds__(kSearchBlock) void search_lookup_kernel(
     const bool any = (meta & kSearchAny) != 0;  // (a phrase is looked up as `all`)
     const u32* fl = s_flag + threadIdx.x;
     const u32* ln = s_len + threadIdx.x;
-    u32 mask = 0, smask = 0, dead = 0, driver = 0, best = ~0u;
+    u32 mask = 0, smask = 0, xmask = 0, dead = 0, driver = 0, best = ~0u;
     u64 sum = 0;
-    for (u32 j = 0; j < nterms; ++j) {
+    for (u32 j = 0; j < npos; ++j) {
       const u32 f = fl[j];
       if (!(f & 1u)) {  // absent
         dead |= any ? 0u : 1u;
@@ -166,8 +177,13 @@ __global__ __launch_bounds__(kSearchBlock) void search_lookup_kernel(
         driver = j;
       }
     }
+    // the present exclusion terms' lists, each once: an absent one excludes nothing, and one
+    // with an earlier term's words (a positive term's too) is that term's list -- the merged
+    // one, when the words are two or more
+    for (u32 j = npos; j < nterms; ++j)
+      if (fl[j] & 1u) xmask |= 1u << (fl[j] >> 4);
     const u32 bound = any ? (u32)sum : (dead || !mask ? 0u : best);
-    q_info[q] = driver | (dead << 8) | (mask << 16) | (smask << 24);
+    q_info[q] = driver | (dead << 3) | (xmask << 8) | (mask << 16) | (smask << 24);
     q_bound[q] = bound;
   }
 }
@@ -361,13 +377,16 @@ __global__ __launch_bounds__(kSearchBlock) void search_hit_kernel(
         const u32 meta = q_meta[q];
         const bool any = (meta & kSearchAny) != 0;
         // a phrase of two or more terms: what passes the `all` test is only a candidate
-        const bool verify = (meta & kSearchPhrase) != 0 && (meta & 0xffu) >= 2u;
+        // (of two or more positive terms: exclusion terms are not part of the phrase)
+        const bool verify = (meta & kSearchPhrase) != 0 &&
+                            (meta & 0xffu) >= 2u + (u32)__popc(meta >> kSearchExcludeShift);
         const u32 mask = (info >> 16) & 0xffu;
+        const u32 xmask = (info >> 8) & 0xffu;  // the exclusion lists (0: none, most batches)
         // so does a `near` query to verify, of two or more distinct terms (one: `all`)
         near = (meta & kSearchNear) != 0 && (mask & (mask - 1u)) != 0u;
         const u64* tv = t_val + (u64)q * kTerms;
         const u32* tl = t_len + (u64)q * kTerms;
-        u32 term = info & 0xffu;  // `all`: the driver
+        u32 term = info & 7u;  // `all`: the driver
         if (any) {                // the distinct terms' lists one after the other
           term = 0;
           for (u32 t = 0; t < (u32)kTerms; ++t) {
@@ -392,6 +411,12 @@ __global__ __launch_bounds__(kSearchBlock) void search_hit_kernel(
               for (u32 t = 0; t < (u32)kTerms && hit; ++t)
                 if (((mask >> t) & 1u) && t != term)
                   hit = list_has(term_list(postings, merged, tv[t]), tl[t], line);
+            }
+            // an excluded line is neither hit nor candidate
+            if (hit && xmask) {
+              for (u32 t = 0; t < (u32)kTerms && hit; ++t)
+                if ((xmask >> t) & 1u)
+                  hit = !list_has(term_list(postings, merged, tv[t]), tl[t], line);
             }
             cand = hit && (verify || near);
             hit = hit && !cand;
@@ -485,7 +510,8 @@ __global__ __launch_bounds__(kPhraseBlock) void search_phrase_kernel(
       const u64 line = (u32)__shfl((int)(u32)mine, (int)i, 64);
       if (q >= Q || line >= num_lines) continue;  // (wave-uniform; never: the hit kernel's words)
       const u32 meta = q_meta[q];
-      const u32 m = meta & 0xffu;
+      // the positive terms, which stand first: exclusion terms are no part of the match
+      const u32 m = (meta & 0xffu) - (u32)__popc(meta >> kSearchExcludeShift);
       if (m == 0 || m > (u32)kTerms) continue;    // (never: the host checked the batch)
       const u32 pre = (meta >> kSearchPrefixShift) & 0xffu;  // bit j: term j is a prefix term
       if (q != q_loaded) {  // (wave-uniform) neighbours mostly share their query
@@ -582,7 +608,8 @@ __global__ __launch_bounds__(kPhraseBlock) void search_near_kernel(
       const u64 line = (u32)__shfl((int)(u32)mine, (int)i, 64);
       if (q >= Q || line > num_nl) continue;  // (wave-uniform; never: the hit kernel's words)
       const u32 meta = q_meta[q];
-      const u32 m = meta & 0xffu;
+      // the positive terms, which stand first: exclusion terms are no part of the match
+      const u32 m = (meta & 0xffu) - (u32)__popc(meta >> kSearchExcludeShift);
       if (m == 0 || m > (u32)kTerms) continue;    // (never: the host checked the batch)
       const u32 pre = (meta >> kSearchPrefixShift) & 0xffu;  // bit j: term j is a prefix term
       // the batch's windows stand behind its keys (search_within)

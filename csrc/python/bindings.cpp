@@ -96,7 +96,8 @@ struct PyIndexResult {
   JobConfig cfg;  // the job's delimiters and max_key_len: what search() validates terms by
   PySearchResult search(const std::vector<std::vector<std::string>>& queries,
                         const std::vector<int>& any, const py::object& rank, bool wildcard,
-                        const std::vector<u64>& within) const;
+                        const std::vector<u64>& within,
+                        const std::vector<std::vector<std::string>>& exclude) const;
   py::list entries() const { return PyResult{x.words}.entries(); }
   py::list postings() const {
     py::list out;
@@ -198,13 +199,17 @@ struct PySearchResult {
 // queries: term lists; any[i]: query i's mode -- 0 `all`, 2 `phrase`, 3 `near`, every other
 // value `any` (any.size() == queries.size()).  wildcard: make_search_query's rule for a
 // trailing `*`.  within: empty, or one window per query (0: none; check_search_queries holds
-// it against the mode).
+// it against the mode).  exclude: empty, or one list of exclusion terms per query (an empty
+// list: none).
 std::vector<SearchQuery> to_queries(const std::vector<std::vector<std::string>>& queries,
                                     const std::vector<int>& any, bool wildcard,
-                                    const std::vector<u64>& within) {
+                                    const std::vector<u64>& within,
+                                    const std::vector<std::vector<std::string>>& exclude) {
   LOCUST_CHECK_ARG(any.size() == queries.size(), "search: one mode per query");
   LOCUST_CHECK_ARG(within.empty() || within.size() == queries.size(),
                    "search: one window (within) per query, or none");
+  LOCUST_CHECK_ARG(exclude.empty() || exclude.size() == queries.size(),
+                   "search: one list of exclusion terms (exclude) per query, or none");
   std::vector<SearchQuery> out(queries.size());
   for (size_t i = 0; i < queries.size(); ++i)
     out[i] = make_search_query(queries[i],
@@ -212,7 +217,8 @@ std::vector<SearchQuery> to_queries(const std::vector<std::vector<std::string>>&
                                : any[i] == 2 ? SearchMode::kPhrase
                                : any[i] == 3 ? SearchMode::kNear
                                              : SearchMode::kAny,
-                               wildcard, within.empty() ? 0 : within[i]);
+                               wildcard, within.empty() ? 0 : within[i],
+                               exclude.empty() ? std::vector<std::string>() : exclude[i]);
   return out;
 }
 
@@ -232,8 +238,9 @@ u64 to_rank(const py::object& rank) {
 
 PySearchResult PyIndexResult::search(const std::vector<std::vector<std::string>>& queries,
                                      const std::vector<int>& any, const py::object& rank,
-                                     bool wildcard, const std::vector<u64>& within) const {
-  const std::vector<SearchQuery> q = to_queries(queries, any, wildcard, within);
+                                     bool wildcard, const std::vector<u64>& within,
+                                     const std::vector<std::vector<std::string>>& exclude) const {
+  const std::vector<SearchQuery> q = to_queries(queries, any, wildcard, within, exclude);
   const u64 k = to_rank(rank);
   py::gil_scoped_release nogil;
   return PySearchResult{search_index(x, q, cfg, k)};
@@ -371,8 +378,9 @@ class PyGpuEngine {
                             const std::vector<std::vector<std::string>>& queries,
                             const std::vector<int>& any, u64 first_line,
                             const py::object& rank, bool wildcard,
-                            const std::vector<u64>& within) {
-    const std::vector<SearchQuery> q = to_queries(queries, any, wildcard, within);
+                            const std::vector<u64>& within,
+                            const std::vector<std::vector<std::string>>& exclude) {
+    const std::vector<SearchQuery> q = to_queries(queries, any, wildcard, within, exclude);
     const u64 k = to_rank(rank);
     py::gil_scoped_release nogil;
     return PySearchResult{eng_.run_search(as_input(text, first_line), q, k)};
@@ -381,16 +389,18 @@ class PyGpuEngine {
                                  const std::vector<std::vector<std::string>>& queries,
                                  const std::vector<int>& any, u64 first_line,
                                  const py::object& rank, bool wildcard,
-                            const std::vector<u64>& within) {
-    const std::vector<SearchQuery> q = to_queries(queries, any, wildcard, within);
+                            const std::vector<u64>& within,
+                            const std::vector<std::vector<std::string>>& exclude) {
+    const std::vector<SearchQuery> q = to_queries(queries, any, wildcard, within, exclude);
     const u64 k = to_rank(rank);
     py::gil_scoped_release nogil;
     return PySearchResult{eng_.run_search(t.input(first_line), q, k)};
   }
   PySearchResult search_resident(const std::vector<std::vector<std::string>>& queries,
                                  const std::vector<int>& any, const py::object& rank,
-                                 bool wildcard, const std::vector<u64>& within) {
-    const std::vector<SearchQuery> q = to_queries(queries, any, wildcard, within);
+                                 bool wildcard, const std::vector<u64>& within,
+                                 const std::vector<std::vector<std::string>>& exclude) {
+    const std::vector<SearchQuery> q = to_queries(queries, any, wildcard, within, exclude);
     const u64 k = to_rank(rank);
     py::gil_scoped_release nogil;
     return PySearchResult{eng_.search_resident(q, k)};
@@ -806,6 +816,7 @@ PYBIND11_MODULE(_locust, m) {
       .def("_search", &PyIndexResult::search, py::arg("queries"), py::arg("any"),
            py::arg("rank") = py::none(), py::arg("wildcard") = false,
            py::arg("within") = std::vector<u64>(),
+           py::arg("exclude") = std::vector<std::vector<std::string>>(),
            "The host evaluation of all/any queries (any[i]: query i's mode) over this index.")
       .def("times", &PyIndexResult::times)
       .def("format", &PyIndexResult::format)
@@ -889,13 +900,16 @@ PYBIND11_MODULE(_locust, m) {
       .def("run_search", &PyGpuEngine::run_search, py::arg("text"), py::arg("queries"),
            py::arg("any"), py::arg("first_line") = 0, py::arg("rank") = py::none(),
            py::arg("wildcard") = false, py::arg("within") = std::vector<u64>(),
+           py::arg("exclude") = std::vector<std::vector<std::string>>(),
            "WordCount of text, its index, and all/any queries answered on the device.")
       .def("run_search_text", &PyGpuEngine::run_search_text, py::arg("text"), py::arg("queries"),
            py::arg("any"), py::arg("first_line") = 0, py::arg("rank") = py::none(),
-           py::arg("wildcard") = false, py::arg("within") = std::vector<u64>())
+           py::arg("wildcard") = false, py::arg("within") = std::vector<u64>(),
+           py::arg("exclude") = std::vector<std::vector<std::string>>())
       .def("search_resident", &PyGpuEngine::search_resident, py::arg("queries"), py::arg("any"),
            py::arg("rank") = py::none(), py::arg("wildcard") = false,
            py::arg("within") = std::vector<u64>(),
+           py::arg("exclude") = std::vector<std::vector<std::string>>(),
            "Another batch from the index the last run_index / run_search left on the device.")
       .def("top_counts", &PyGpuEngine::top_counts, py::arg("records"), py::arg("k"),
            "The selection kernels alone over key-sorted (key, count) records.")
@@ -917,14 +931,16 @@ PYBIND11_MODULE(_locust, m) {
                              const std::vector<std::vector<std::string>>& queries,
                              const std::vector<int>& any, u64 first_line,
                              const py::object& rank, bool wildcard,
-                             const std::vector<u64>& within) {
+                             const std::vector<u64>& within,
+                             const std::vector<std::vector<std::string>>& exclude) {
     CpuWordCount eng(cfg);
     return PySearchResult{eng.run_search(as_input(text, first_line),
-                                         to_queries(queries, any, wildcard, within),
+                                         to_queries(queries, any, wildcard, within, exclude),
                                          to_rank(rank))};
   }, py::arg("cfg"), py::arg("text"), py::arg("queries"), py::arg("any"),
         py::arg("first_line") = 0, py::arg("rank") = py::none(), py::arg("wildcard") = false,
-        py::arg("within") = std::vector<u64>());
+        py::arg("within") = std::vector<u64>(),
+           py::arg("exclude") = std::vector<std::vector<std::string>>());
   m.def("check_search_merge", &check_search_merge, py::arg("queries"), py::arg("elements"),
         "Throws when a device batch's prefix terms would merge 2^32 list elements or more.");
   m.def("cpu_map_stage", [](const JobConfig& cfg, const std::string& text) {

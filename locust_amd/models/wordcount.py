@@ -18,10 +18,29 @@ _C = load()
 _SEARCH_MODES = {"all": 0, "any": 1, "phrase": 2, "near": 3}
 
 
-def _search_args(queries, mode, within=None):
+def _search_exclude(exclude, n):
+    """One list of exclusion terms per query (``[]``: none) from ``exclude``: ``None``, or a
+    list with one entry per query, each ``None`` or a list of byte-string terms."""
+    if exclude is None:
+        return []
+    if isinstance(exclude, (bytes, str)) or len(exclude) != n:
+        raise ValueError("search: exclude takes one entry per query, each None or a list of "
+                         "terms")
+    out = []
+    for x in exclude:
+        if isinstance(x, (bytes, str)):
+            raise ValueError("search: an entry of exclude is None or a list of terms, not the "
+                             "term %r itself" % (x,))
+        out.append([] if x is None else list(x))
+    return out
+
+
+def _search_args(queries, mode, within=None, exclude=None):
     """(term lists, one mode flag per query: 0 all, 1 any, 2 phrase, 3 near, one window per
-    query: 0 none) for the native search entry points."""
+    query: 0 none, one list of exclusion terms per query or none at all) for the native search
+    entry points."""
     queries = [list(q) for q in queries]
+    exclude = _search_exclude(exclude, len(queries))
     modes = [mode] * len(queries) if isinstance(mode, str) else list(mode)
     if len(modes) != len(queries):
         raise ValueError("search: one mode per query")
@@ -47,17 +66,18 @@ def _search_args(queries, mode, within=None):
         elif isinstance(w, bool) or not isinstance(w, int) or not 1 <= w < 1 << 32:
             raise ValueError("search: a 'near' query takes within=W, an integer with "
                              "1 <= W < 2^32, not %r" % (w,))
-    return queries, [_SEARCH_MODES[m] for m in modes], [w or 0 for w in windows]
+    return queries, [_SEARCH_MODES[m] for m in modes], [w or 0 for w in windows], exclude
 
 
-def _index_search(self, queries, mode="all", rank=None, wildcard=False, within=None):
+def _index_search(self, queries, mode="all", rank=None, wildcard=False, within=None,
+                  exclude=None):
     """All/any word queries over this index, evaluated on the host (``SearchResult``):
-    ``queries``, ``mode``, ``rank`` and ``within`` as ``Engine.run_search`` takes them, any
-    number of queries.  A ``"phrase"`` query, and a ``"near"`` query of two or more terms, is
-    refused: the index holds no positions, so they need the text (``Engine.run_search``,
-    ``search_text``)."""
-    queries, flags, windows = _search_args(queries, mode, within)
-    return self._search(queries, flags, rank, bool(wildcard), windows)
+    ``queries``, ``mode``, ``rank``, ``within`` and ``exclude`` as ``Engine.run_search`` takes
+    them, any number of queries.  A ``"phrase"`` query, and a ``"near"`` query of two or more
+    positive terms, is refused: the index holds no positions, so they need the text
+    (``Engine.run_search``, ``search_text``)."""
+    queries, flags, windows, exclude = _search_args(queries, mode, within, exclude)
+    return self._search(queries, flags, rank, bool(wildcard), windows, exclude)
 
 
 _C.IndexResult.search = _index_search
@@ -100,7 +120,7 @@ class Engine:
         return self._eng.run_index(text, first_line)
 
     def run_search(self, text: bytes, queries, mode="all", first_line: int = 0, rank=None,
-                   wildcard=False, within=None):
+                   wildcard=False, within=None, exclude=None):
         """WordCount of ``text``, its inverted index, and a batch of word queries answered
         from it (``SearchResult``).  ``queries`` is a list of term lists (1 to 8 byte-string
         terms each); ``mode`` is ``"all"`` (lines that hold every term), ``"any"`` (lines
@@ -129,24 +149,34 @@ class Engine:
         one word whose list is the merged lists of them all (``oracle.search`` with
         ``wildcard=True`` states the rules).  A lone ``*`` is refused and a ``*`` anywhere
         else is literal; without ``wildcard`` every ``*`` is.  On the GPU the lists are merged
-        on the device; ``merged`` is the number of list elements the batch merged."""
-        queries, flags, windows = _search_args(queries, mode, within)
+        on the device; ``merged`` is the number of list elements the batch merged.
+
+        ``exclude`` gives exclusion terms: a list with one entry per query, each ``None`` or
+        a list of byte-string terms (``oracle.search(..., exclude=)`` states the rules).  A
+        query answers what its mode answers for its own terms, minus every line that holds an
+        exclusion term; an absent exclusion term takes nothing away.  Own and exclusion terms
+        together number at most 8, ``wildcard`` applies to both, ``term_counts(i)`` lists the
+        own terms first and then the exclusion terms, and a ranked query scores by its own
+        terms only.  On the GPU the lines are dropped on the device, before verification,
+        scoring and the sort."""
+        queries, flags, windows, exclude = _search_args(queries, mode, within, exclude)
         if self.cpu:
             return _C.cpu_run_search(self.cfg, text, queries, flags, first_line, rank,
-                                     bool(wildcard), windows)
+                                     bool(wildcard), windows, exclude)
         return self._eng.run_search(text, queries, flags, first_line, rank, bool(wildcard),
-                                    windows)
+                                    windows, exclude)
 
-    def search_resident(self, queries, mode="all", rank=None, wildcard=False, within=None):
+    def search_resident(self, queries, mode="all", rank=None, wildcard=False, within=None,
+                        exclude=None):
         """Another batch from the index this engine's last job left on the device; that
         job must have been a ``run_index`` or a ``run_search`` (GPU engines only).  Every
         mode of ``run_search``: the job's text is resident too, so phrases and near queries
-        are answered.  ``rank`` and ``within`` as ``run_search`` takes them."""
+        are answered.  ``rank``, ``within`` and ``exclude`` as ``run_search`` takes them."""
         if self.cpu:
             raise _C.LocustError("search_resident needs a GPU engine: the CPU engine keeps "
                                  "no index (use run_index(text).search(...))")
-        queries, flags, windows = _search_args(queries, mode, within)
-        return self._eng.search_resident(queries, flags, rank, bool(wildcard), windows)
+        queries, flags, windows, exclude = _search_args(queries, mode, within, exclude)
+        return self._eng.search_resident(queries, flags, rank, bool(wildcard), windows, exclude)
 
     def top_counts(self, records: list[tuple[bytes, int]], k: int):
         """The selection alone over (key, count) records sorted by key with distinct
@@ -241,23 +271,25 @@ def index_file(path: str, line_start: int = -1, line_end: int = -1, backend: str
 
 
 def search_text(text: bytes, queries, mode="all", backend: str = "gpu", cfg=None,
-                first_line: int = 0, rank=None, wildcard=False, within=None, **kw):
+                first_line: int = 0, rank=None, wildcard=False, within=None, exclude=None,
+                **kw):
     """All/any/phrase/near word queries over ``text`` (``SearchResult``); see
     ``Engine.run_search``."""
     cfg = cfg if cfg is not None else make_config(backend, **kw)
     nlines = text.count(b"\n") + (1 if text and not text.endswith(b"\n") else 0)
     return Engine(cfg, max(len(text), 1), max(nlines, 1)).run_search(
-        text, queries, mode, first_line, rank, wildcard, within)
+        text, queries, mode, first_line, rank, wildcard, within, exclude)
 
 
 def search_file(path: str, queries, mode="all", line_start: int = -1, line_end: int = -1,
-                backend: str = "gpu", cfg=None, rank=None, wildcard=False, within=None, **kw):
+                backend: str = "gpu", cfg=None, rank=None, wildcard=False, within=None,
+                exclude=None, **kw):
     """All/any/phrase/near word queries over a file or its line window, answered with the file's
     own (global) line numbers."""
     cfg = cfg if cfg is not None else make_config(backend, **kw)
     text, nlines, first, _total = _C.load_lines(path, line_start, line_end, cfg.ref_compat)
     return Engine(cfg, max(len(text), 1), max(nlines, 1)).run_search(
-        text, queries, mode, first, rank, wildcard, within)
+        text, queries, mode, first, rank, wildcard, within, exclude)
 
 
 def map_stage(path: str, spill: str, line_start: int = -1, line_end: int = -1,

@@ -171,12 +171,97 @@ def _term_list(entries, postings, words):
     return sorted(l for i in words for l in postings[entries[i][1]:entries[i][1] + entries[i][2]])
 
 
-def merged_elements(entries, queries, delims: bytes = DEFAULT_DELIMS, max_key: int = 29) -> int:
+EXCLUDE_RULES = """
+    Exclusion terms.  A query has 1 or more positive terms and 0 or more exclusion terms
+    (``exclude``); together they number at most 8.  An exclusion term is validated, cut to
+    max_key_len and, with wildcards, read as a prefix term exactly as a positive term is.
+
+    - Excluded lines.  A term's lines are the distinct lines of its postings list, as for
+      `all`; a prefix term's list is its merged list.  A query's excluded lines are the union
+      of its exclusion terms' lines.  An absent exclusion term excludes nothing: it does not
+      empty the answer, unlike an absent positive term in `all`.
+    - Matching set.  The matching set is what the mode answers for the positive terms alone,
+      minus the excluded lines.  The mode, the `near` window, the repetition rules and the
+      one-term shortcuts apply to the positive terms only: the `near` shortcut "W >=
+      emits_per_line answers as `all`" and the shortcut "one distinct term answers as `all`"
+      count distinct positive terms, and phrase and `near` verification sees only the
+      positive terms.  [alpha beta] not gamma as a phrase matches the line `alpha beta delta`
+      and does not match `alpha beta gamma`: the second line is excluded because it holds
+      gamma anywhere among its emitted tokens.
+    - Pure function of the index.  Exclusion depends only on the index, so a token past the
+      emit cap excludes nothing: the rule every other mode follows.
+    - Overlap with a positive term.  An exclusion term whose words equal or contain a
+      positive term's words empties `all`, `phrase` and `near`; in `any` it removes that
+      term's lines from the union.  This is legal, not an error.
+    - Ranked.  `matches` counts the matching set after exclusion.  Exclusion terms take no
+      part in the score, in the "distinct present terms" or in the nesting rule: in Ham* not
+      Hamlet, Ham* still scores with its full merged count.  The bound score <= 32 *
+      emits_per_line is unchanged.
+    - term_counts report every term, positive terms first and then the exclusion terms in
+      the order given; an exclusion term reports its word's count, or its merged count.
+    - `merged`: the rule is unchanged and runs over all of the query's terms: the sum of the
+      counts over the query's terms that cover two or more words, a term whose words repeat
+      an earlier term's left out.  An exclusion prefix term covering two or more words is
+      therefore merged and counted; one covering a single word uses that word's list in
+      place.
+    - Refused (``ValueError``): a query with no positive term, more than 8 terms in total,
+      an invalid exclusion term, a lone `*` with wildcards.
+"""
+
+
+def _check_exclude(terms, exclude):
+    """The exclusion terms as a list (``None``: none), the term budget checked."""
+    exclude = [] if exclude is None else list(exclude)
+    if isinstance(terms, (bytes, str)) or any(not isinstance(t, bytes) for t in exclude):
+        raise ValueError("exclusion terms are byte strings")
+    if len(terms) < 1:
+        raise ValueError("a query takes at least one positive term")
+    if len(terms) + len(exclude) > MAX_SEARCH_TERMS:
+        raise ValueError("a query takes at most %d terms, positive and exclusion terms "
+                         "together" % MAX_SEARCH_TERMS)
+    return exclude
+
+
+def _excluded_by_index(entries, postings, exclude, wildcard, delims, max_key):
+    """``(lines, counts)`` of exclusion terms over an index: the union of the terms' lines as
+    a set, and every term's count (its word's, or its merged count; 0: absent)."""
+    out, counts = set(), []
+    for p, pre in prefix_terms(exclude, wildcard, delims, max_key):
+        lines = _term_list(entries, postings, _term_words(entries, p, pre))
+        counts.append(len(lines))
+        out.update(lines)
+    return out, counts
+
+
+def _excluded_by_text(text, exclude, wildcard, delims, emits, max_key, first_line):
+    """The same from the text: a line is excluded when one of its emitted tokens (the index
+    holds no other) matches an exclusion term; a term's count is its matching tokens."""
+    want = prefix_terms(exclude, wildcard, delims, max_key)
+    out, counts = set(), [0] * len(want)
+    for i, line in enumerate(split_lines(text)):
+        toks, _dropped = tokenize(line, delims, emits, max_key)
+        for j, (p, pre) in enumerate(want):
+            n = sum((tok[:len(p)] == p) if pre else (tok == p) for tok in toks)
+            counts[j] += n
+            if n:
+                out.add(first_line + i)
+    return out, counts
+
+
+def merged_elements(entries, queries, delims: bytes = DEFAULT_DELIMS, max_key: int = 29, *,
+                    exclude=None) -> int:
     """``SearchResult.merged`` of a device batch of wildcard ``queries`` (term lists): over
     the batch's prefix terms that cover two or more words, a term whose words repeat an
     earlier term's of its query left out, the sum of their counts.  (A term that covers one
-    word uses that word's list in place: nothing is merged.)"""
+    word uses that word's list in place: nothing is merged.)
+
+    ``exclude``: one entry per query, ``None`` or its exclusion terms, which stand behind the
+    query's own terms (``EXCLUDE_RULES``: the rule runs over all of the query's terms)."""
     total = 0
+    if exclude is not None:
+        if len(exclude) != len(queries):
+            raise ValueError("exclude takes one entry per query")
+        queries = [list(q) + _check_exclude(list(q), x) for q, x in zip(queries, exclude)]
     for terms in queries:
         seen = []
         for p, pre in prefix_terms(terms, True, delims, max_key):
@@ -188,7 +273,7 @@ def merged_elements(entries, queries, delims: bytes = DEFAULT_DELIMS, max_key: i
 
 
 def search(entries, postings, terms, mode: str = "all", delims: bytes = DEFAULT_DELIMS,
-           max_key: int = 29, *, wildcard: bool = False):
+           max_key: int = 29, *, wildcard: bool = False, exclude=None):
     """One all/any word query over an index: ``(lines, counts)``.
 
     ``entries`` and ``postings`` are ``index``'s output.  A query is 1 to 8 ``terms`` and a
@@ -205,10 +290,21 @@ def search(entries, postings, terms, mode: str = "all", delims: bytes = DEFAULT_
     index keys ``k`` with ``k[:len(p)] == p``, a word equal to ``p`` among them; its list is
     the multiset union of those words' postings, non-decreasing; its count is the sum of
     their counts; if no word matches, the term is absent.  In ``"all"`` and ``"any"`` it
-    behaves as a word with that list."""
+    behaves as a word with that list.
+
+    ``exclude``: the query's exclusion terms (``EXCLUDE_RULES``).  The answer is the one
+    above for ``terms`` alone minus the excluded lines, and ``counts`` lists the terms'
+    counts first and then the exclusion terms'."""
     if mode not in ("all", "any"):
         raise ValueError("mode must be 'all' or 'any'")
     terms = list(terms)
+    if exclude is not None:
+        exclude = _check_exclude(terms, exclude)
+        lines, counts = search(entries, postings, terms, mode, delims, max_key,
+                               wildcard=wildcard)
+        gone, xcounts = _excluded_by_index(entries, postings, exclude, wildcard, delims,
+                                           max_key)
+        return [l for l in lines if l not in gone], counts + xcounts
     if not 1 <= len(terms) <= MAX_SEARCH_TERMS:
         raise ValueError("a query takes 1 to %d terms" % MAX_SEARCH_TERMS)
     if wildcard:
@@ -234,7 +330,7 @@ def search(entries, postings, terms, mode: str = "all", delims: bytes = DEFAULT_
 
 
 def phrase(text: bytes, terms, delims: bytes = DEFAULT_DELIMS, emits: int = 20,
-           max_key: int = 29, first_line: int = 0, *, wildcard: bool = False):
+           max_key: int = 29, first_line: int = 0, *, wildcard: bool = False, exclude=None):
     """One phrase query over ``text``: ``(lines, counts)``, as ``search`` answers.
 
     `phrase` answers the lines on which the terms occur as consecutive tokens, in order.
@@ -256,8 +352,19 @@ def phrase(text: bytes, terms, delims: bytes = DEFAULT_DELIMS, emits: int = 20,
     ``wildcard=True``: a term may be a prefix term (``prefix_terms``).  A token matches a
     prefix term when the token's key (cut to ``max_key``) starts with ``p``; a token shorter
     than ``p`` does not match.  Its count is the number of emitted tokens that match it.  A
-    one-term phrase answers the lines that hold a matching token, as `all` does."""
+    one-term phrase answers the lines that hold a matching token, as `all` does.
+
+    ``exclude``: the query's exclusion terms (``EXCLUDE_RULES``).  The answer is the one
+    above for ``terms`` alone minus the lines with an emitted token that matches an exclusion
+    term, and ``counts`` lists the terms' counts first and then the exclusion terms'."""
     terms = list(terms)
+    if exclude is not None:
+        exclude = _check_exclude(terms, exclude)
+        lines, counts = phrase(text, terms, delims, emits, max_key, first_line,
+                               wildcard=wildcard)
+        gone, xcounts = _excluded_by_text(text, exclude, wildcard, delims, emits, max_key,
+                                          first_line)
+        return [l for l in lines if l not in gone], counts + xcounts
     if not 1 <= len(terms) <= MAX_SEARCH_TERMS:
         raise ValueError("a query takes 1 to %d terms" % MAX_SEARCH_TERMS)
     if wildcard:
@@ -299,7 +406,7 @@ MAX_SEARCH_WITHIN = (1 << 32) - 1
 
 
 def near(text: bytes, terms, within: int, delims: bytes = DEFAULT_DELIMS, emits: int = 20,
-         max_key: int = 29, first_line: int = 0, *, wildcard: bool = False):
+         max_key: int = 29, first_line: int = 0, *, wildcard: bool = False, exclude=None):
     """One proximity query over ``text``: ``(lines, counts)``, as ``search`` answers.
 
     `near` answers the lines on which the terms occur within ``within`` = W tokens of one
@@ -318,8 +425,19 @@ def near(text: bytes, terms, within: int, delims: bytes = DEFAULT_DELIMS, emits:
 
     Terms are validated as ``search`` validates them (``ValueError``).  Written straight from
     the paragraph above: every line is tokenised and every window of W consecutive tokens
-    tested; no index."""
+    tested; no index.
+
+    ``exclude``: the query's exclusion terms (``EXCLUDE_RULES``).  The answer is the one
+    above for ``terms`` alone minus the lines with an emitted token that matches an exclusion
+    term, and ``counts`` lists the terms' counts first and then the exclusion terms'."""
     terms = list(terms)
+    if exclude is not None:
+        exclude = _check_exclude(terms, exclude)
+        lines, counts = near(text, terms, within, delims, emits, max_key, first_line,
+                             wildcard=wildcard)
+        gone, xcounts = _excluded_by_text(text, exclude, wildcard, delims, emits, max_key,
+                                          first_line)
+        return [l for l in lines if l not in gone], counts + xcounts
     if not 1 <= len(terms) <= MAX_SEARCH_TERMS:
         raise ValueError("a query takes 1 to %d terms" % MAX_SEARCH_TERMS)
     if isinstance(within, bool) or not isinstance(within, int) or \
@@ -346,21 +464,36 @@ def near(text: bytes, terms, within: int, delims: bytes = DEFAULT_DELIMS, emits:
     return lines, counts
 
 
-def format_search(queries, answers) -> bytes:
+def _query_text(queries, exclude):
+    """Each query's text in a result line: its terms joined by one space and, when it has
+    exclusion terms, `` \t not: `` and those joined by one space."""
+    if exclude is None:
+        exclude = [None] * len(queries)
+    if len(exclude) != len(queries):
+        raise ValueError("exclude takes one entry per query")
+    return [b" ".join(q) + (b" \t not: " + b" ".join(x) if x else b"")
+            for q, x in zip(queries, exclude)]
+
+
+def format_search(queries, answers, *, exclude=None) -> bytes:
     """The CLI's ``--search`` result lines: one per query, ``queries[i]`` its terms and
     ``answers[i]`` its lines (every line number after one space; none after "lines:" when
-    the query has no hit)."""
+    the query has no hit).
+
+    ``exclude``: one entry per query, ``None`` or its exclusion terms; a query with exclusion
+    terms prints `` \t not: <terms joined by one space>`` between its text and ``hits:``
+    (terms as they were asked: a prefix term with its star)."""
     return b"".join(
         b"print query: %s \t hits: %d \t lines:%s\n"
-        % (b" ".join(q), len(a), b"".join(b" %d" % l for l in a))
-        for q, a in zip(queries, answers))
+        % (q, len(a), b"".join(b" %d" % l for l in a))
+        for q, a in zip(_query_text(queries, exclude), answers))
 
 
 RANK_MAX_EMITS = 65536
 
 
 def rank(entries, postings, lines, terms, k: int, max_key: int = 29, *,
-         wildcard: bool = False, delims: bytes = DEFAULT_DELIMS):
+         wildcard: bool = False, delims: bytes = DEFAULT_DELIMS, exclude=None):
     """The ranked answer of one query: ``(top, matches)``.
 
     ``lines`` is the query's matching set, as ``search`` or ``phrase`` answered it; ranking
@@ -379,9 +512,20 @@ def rank(entries, postings, lines, terms, k: int, max_key: int = 29, *,
     key range, the set of its words; prefix ranges and single words form a laminar family:
     two ranges are nested or disjoint.  A present term whose range lies inside the range of
     another present term of the query contributes nothing to the score; of equal ranges the
-    first occurrence counts (for plain terms: a repeated key counts once)."""
+    first occurrence counts (for plain terms: a repeated key counts once).
+
+    ``exclude``: the query's exclusion terms (``EXCLUDE_RULES``).  The matching set is
+    ``lines`` minus the excluded lines (``lines`` may be the answer before or after the
+    exclusion) and ``matches`` counts it; the exclusion terms take no part in the score, in
+    the distinct present terms or in the nesting rule."""
     if k < 1:
         raise ValueError("rank takes k >= 1")
+    if exclude is not None:
+        exclude = _check_exclude(list(terms), exclude)
+        gone, _counts = _excluded_by_index(entries, postings, exclude, wildcard, delims,
+                                           max_key)
+        return rank(entries, postings, [l for l in lines if l not in gone], terms, k,
+                    max_key, wildcard=wildcard, delims=delims)
     if wildcard:
         n = len(postings)
         ranges = [set(_term_words(entries, p, pre))
@@ -417,14 +561,15 @@ def rank(entries, postings, lines, terms, k: int, max_key: int = 29, *,
     return [(line, score) for score, line in scored[:k]], len(lines)
 
 
-def format_ranked(queries, tops, matches) -> bytes:
+def format_ranked(queries, tops, matches, *, exclude=None) -> bytes:
     """The CLI's ``--search ... --rank K`` result lines: one per query, ``queries[i]`` its
     terms, ``tops[i]`` its ``(line, score)`` pairs and ``matches[i]`` its number of matching
-    lines (nothing after "top:" when nothing matched)."""
+    lines (nothing after "top:" when nothing matched).  ``exclude`` as ``format_search``
+    takes it."""
     return b"".join(
         b"print query: %s \t hits: %d \t top:%s\n"
-        % (b" ".join(q), m, b"".join(b" %d:%d" % (l, s) for l, s in t))
-        for q, t, m in zip(queries, tops, matches))
+        % (q, m, b"".join(b" %d:%d" % (l, s) for l, s in t))
+        for q, t, m in zip(_query_text(queries, exclude), tops, matches))
 
 
 def format_gpu(entries) -> bytes:

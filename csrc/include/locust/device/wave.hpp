@@ -114,6 +114,12 @@ __device__ __forceinline__ uint32_t ld_agent(const uint32_t* p) {
 __device__ __forceinline__ void st_agent(uint32_t* p, uint32_t v) {
   __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
+// Waits for every store (and load) this wave has issued.  Two places in a hand-off: every
+// storing wave before the barrier in front of its workgroup's release fence, and the
+// releasing lane between the fence and the flag store or counter add -- the compiler may
+// drop the fence's own wait when it believes nothing is outstanding, and the signal then
+// overtakes the write-back.  Inline asm: the compiler neither drops nor moves it.
+__device__ __forceinline__ void drain_vmem() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
 
 }  // namespace dev
 }  // namespace locust

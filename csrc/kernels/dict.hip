@@ -1710,9 +1710,15 @@ __device__ __forceinline__ void ordered_partition(
   }
   // ---- the run's counters: the last partition's look-back prefix ----
   auto publish_totals = [&](u32 u, u64 total, u64 ovf_total) {
-    ctr->num_unique = u;
-    ctr->total_count = total;
-    if (ovf_total) ctr->flags |= kCtrDictOverflow;
+    // ctr is read by other workgroups (the last one's overflow check) and re-zeroed by the
+    // last one: agent-scope atomics, not plain stores -- a plain store's dirty line (the
+    // whole struct is one) could be written back later, over that re-zeroing
+    const u32 flags_out = ctr->flags | (ovf_total ? kCtrDictOverflow : 0u);  // (the map's bits)
+    dev::st_agent(&ctr->num_unique, u);
+    dev::st_agent(&ctr->total_count, total);
+    if (ovf_total)
+      (void)__hip_atomic_fetch_or(&ctr->flags, kCtrDictOverflow, __ATOMIC_RELAXED,
+                                  __HIP_MEMORY_SCOPE_AGENT);
     if (ctr_out) {
       ctr_out->num_records = ctr->num_records;
       ctr_out->map_tokens = ctr->map_tokens;
@@ -1722,7 +1728,7 @@ __device__ __forceinline__ void ordered_partition(
       ctr_out->num_newlines = ctr->num_newlines;
       ctr_out->max_key_len = ctr->max_key_len;
       ctr_out->total_count = total;
-      ctr_out->flags = ctr->flags | (ovf_total ? kCtrDictOverflow : 0u);
+      ctr_out->flags = flags_out;
     }
     if (ex.hdr) {  // the gather slot's header: this rank's records are complete
       // field by field from the template: a whole-struct copy went through private memory
@@ -1750,15 +1756,23 @@ __device__ __forceinline__ void ordered_partition(
     // first while earlier ones still read look-back words) re-zeroes the counters and
     // every look-back word, unless a partition overflowed (the host then redoes the
     // Process stage from these counters and resets everything itself).
+    // The hand-off, in the order it needs: every wave waits for its own stores, the
+    // workgroup meets, thread 0 releases (the L2 write-back), waits for the write-back, and
+    // only then counts the workgroup done.
+    dev::drain_vmem();
     __syncthreads();
     if (threadIdx.x == 0) {
-      // release this workgroup's counter / status writes (and, when the host is told of the
-      // end, its host-mapped records: system scope); release only -- the last workgroup
-      // acquires (an acq_rel fence here also invalidated this XCD's caches, every time)
+      // release this workgroup's records, headers and totals (system scope when the host
+      // is told of the end: they are host-mapped); release only -- the last workgroup
+      // acquires (an acq_rel fence here also invalidated this XCD's caches, every time).
+      // The write-back is needed for the host-mapped words too: plain stores to them stay
+      // in this XCD's L2 until it (measured: without the fence the host read a header
+      // table that was not out yet -- docs/PERFORMANCE.md, "Write-through tail").
       if (ex.host_done)
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "");
       else
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+      dev::drain_vmem();  // the count stays behind the write-back (see drain_vmem)
       s_count = atomicAdd(ex.done_counter, 1u) == (u32)kDictParts - 1 ? 1u : 0u;
       if (trace) trace[(u64)v * 32 + 25] = __builtin_amdgcn_s_memrealtime();
     }
@@ -1769,6 +1783,10 @@ __device__ __forceinline__ void ordered_partition(
       // writes waited for) before counting itself done, and this one saw all 256 counts.
       // So the store is relaxed: a release here wrote the L2 back again and waited for the
       // acquire's load below, two more memory round trips before the host could see it.
+      // (This rests on the hardware, not on a formal happens-before edge: each workgroup's
+      // write-back is waited for -- drain_vmem -- before its count, and this store issues
+      // only after the last count has returned.  tests/test_signal_stress.py and
+      // tests/test_writethrough_tail.py guard it; docs/ARCHITECTURE.md, visibility.)
       // The re-zeroing below touches device scratch only, which the next job's kernels --
       // behind this one on the stream -- see complete; the host's turnaround overlaps it.
       if (ex.host_done && threadIdx.x == 0)

@@ -320,11 +320,13 @@ __global__ __launch_bounds__(kMergeBlock) void merge_emit_compact_kernel(
     u64* out = dst + s_base + before;
     for (u32 q = threadIdx.x; q < (u32)tile_words; q += kMergeBlock) out[q] = s_out[q];
   }
+  dev::drain_vmem();  // every wave: its own stores, before the barrier
   __syncthreads();
   if (threadIdx.x == 0) {
     // this workgroup's records (host memory): one system-scope release, not an acq_rel
-    // fence in every thread
+    // fence in every thread; the count stays behind the write-back (see drain_vmem)
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "");
+    dev::drain_vmem();
     const u32 prev = atomicAdd(done, 1u);
     if (prev == gridDim.x - 1) {
       __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");  // every workgroup's records

@@ -48,14 +48,19 @@ __device__ __forceinline__ void reduce_tail(u32 p, u32 U, u64 pfx, MapCounters* 
                                             u32& s_last, bool looked_back = false) {
   if (!looked_back) pfx = dev::block_lookback(ra.status, p, U, &s_prefix);
   if (p == (u32)kDictParts - 1 && threadIdx.x == 0) {
-    ctr->num_unique = (u32)(pfx + U);
-    ctr->total_count = ctr->num_records;
+    // agent-scope atomics (as dict.hip): no dirty line of ctr is left to be written back
+    // over the last workgroup's re-zeroing
+    const u32 n = ctr->num_records;  // (the map's: complete before this kernel)
+    dev::st_agent(&ctr->num_unique, (u32)(pfx + U));
+    dev::st_agent(&ctr->total_count, (u64)n);
   }
+  dev::drain_vmem();  // every wave: its own stores, before the barrier
   __syncthreads();
   if (threadIdx.x == 0) {
     // this workgroup's records (host-mapped) and counter writes; release only (the last
-    // workgroup acquires)
+    // workgroup acquires); the count stays behind the write-back (see drain_vmem)
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "");
+    dev::drain_vmem();
     s_last = atomicAdd(ra.done_counter, 1u) == (u32)kDictParts - 1 ? 1u : 0u;
   }
   __syncthreads();

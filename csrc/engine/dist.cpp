@@ -64,27 +64,33 @@ bool exch_enabled() {
   return !(v && v[0] == '0');
 }
 
-// Weighted quantile splitters from every rank's evenly spaced samples.
+}  // namespace
+
+// Weighted quantile splitters from every rank's evenly spaced samples (dist.hpp).  Integer
+// arithmetic, each sample weighing its rank's record count -- the device planner's rule
+// (exch_plan_kernel) word for word.  Weights of count / s in double agreed with it only
+// while s was a power of two: at s = 3, 10 or 63 the rounded prefix sums missed the ties
+// with total * p / parts and picked a neighbouring sample (tests/test_exchange_ref.py).
 std::vector<PackedKey> choose_splitters(const std::vector<PackedKey>& samples, u32 s,
                                         const std::vector<u64>& counts, int parts) {
+  using u128 = unsigned __int128;
   struct W {
     PackedKey k;
-    double w;
+    u64 w;
   };
   std::vector<W> all;
-  double total = 0;
+  u128 total = 0;
   for (size_t r = 0; r < counts.size(); ++r) {
-    if (!counts[r]) continue;
-    const double w = (double)counts[r] / (double)s;
-    for (u32 i = 0; i < s; ++i) all.push_back({samples[r * s + i], w});
-    total += (double)counts[r];
+    if (!counts[r]) continue;  // (a weightless sample is never the first past a target)
+    for (u32 i = 0; i < s; ++i) all.push_back({samples[r * s + i], counts[r]});
+    total += (u128)counts[r] * s;
   }
   std::sort(all.begin(), all.end(), [](const W& a, const W& b) { return key_less(a.k, b.k); });
   std::vector<PackedKey> sp;
-  double run = 0;
+  u128 run = 0;
   size_t i = 0;
   for (int p = 1; p < parts; ++p) {
-    const double target = total * p / parts;
+    const u128 target = total * (u128)p / (u128)parts;
     while (i < all.size() && run + all[i].w <= target) run += all[i++].w;
     PackedKey k;
     if (i < all.size()) {
@@ -96,8 +102,6 @@ std::vector<PackedKey> choose_splitters(const std::vector<PackedKey>& samples, u
   }
   return sp;
 }
-
-}  // namespace
 
 // Control-plane messages: every allgather carries the status word of the stage before it,
 // so failure agreement costs no extra collective.  Msg1 also carries the map statistics,

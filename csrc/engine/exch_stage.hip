@@ -1,0 +1,316 @@
+// Stage-level entry points of the device-resident shuffle (locust/exch_stage.hpp): one
+// launch_* of exchange.hip / shuffle.hip per call, on plain device buffers of its own.
+// Every size a kernel indexes by is checked here first, so no launch can leave its buffers.
+#include "locust/exch_stage.hpp"
+
+#include <algorithm>
+#include <cstring>
+
+#include "locust/hip_check.hpp"
+#include "locust/kernels.hpp"
+
+namespace locust {
+namespace {
+
+constexpr u64 kStageMaxBytes = 1ull << 30;  // largest single buffer of a stage call
+
+template <class T>
+struct DevBuf {  // a plain device allocation of max(n, 1) elements
+  T* p = nullptr;
+  u64 n;
+  explicit DevBuf(u64 count) : n(std::max<u64>(count, 1)) {
+    LOCUST_CHECK_ARG(n * sizeof(T) <= kStageMaxBytes, "exchange stage: buffer too large");
+    LOCUST_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&p), n * sizeof(T)));
+  }
+  ~DevBuf() { (void)hipFree(p); }
+  DevBuf(const DevBuf&) = delete;
+  DevBuf& operator=(const DevBuf&) = delete;
+  void upload(const T* src, u64 count) {
+    if (count) LOCUST_HIP_CHECK(hipMemcpy(p, src, count * sizeof(T), hipMemcpyHostToDevice));
+  }
+  void download(T* dst, u64 count) const {
+    if (count) LOCUST_HIP_CHECK(hipMemcpy(dst, p, count * sizeof(T), hipMemcpyDeviceToHost));
+  }
+  void fill(unsigned char byte) { LOCUST_HIP_CHECK(hipMemset(p, byte, n * sizeof(T))); }
+};
+
+struct DevKeys {  // packed keys, structure-of-arrays
+  DevBuf<u64> w0, w1, w2, w3;
+  explicit DevKeys(u64 n) : w0(n), w1(n), w2(n), w3(n) {}
+  u64* word(int j) { return j == 0 ? w0.p : j == 1 ? w1.p : j == 2 ? w2.p : w3.p; }
+  KeysSoA soa() {
+    KeysSoA k;
+    for (int j = 0; j < kKeyWords; ++j) k.w[j] = word(j);
+    return k;
+  }
+  template <class Rec>  // PackedKey or KeyCount: anything with w[kKeyWords]
+  void upload(const Rec* recs, u64 n) {
+    std::vector<u64> col(n);
+    for (int j = 0; j < kKeyWords; ++j) {
+      for (u64 i = 0; i < n; ++i) col[i] = recs[i].w[j];
+      if (n) LOCUST_HIP_CHECK(hipMemcpy(word(j), col.data(), n * sizeof(u64), hipMemcpyHostToDevice));
+    }
+  }
+  void download(PackedKey* out, u64 n) {
+    std::vector<u64> col(n);
+    for (int j = 0; j < kKeyWords; ++j) {
+      if (n) LOCUST_HIP_CHECK(hipMemcpy(col.data(), word(j), n * sizeof(u64), hipMemcpyDeviceToHost));
+      for (u64 i = 0; i < n; ++i) out[i].w[j] = col[i];
+    }
+  }
+};
+static_assert(kKeyWords == 4, "DevKeys holds four word arrays");
+
+void sync() { LOCUST_HIP_CHECK(hipStreamSynchronize(nullptr)); }
+
+bool all_pattern(const char* p, u64 bytes) {
+  for (u64 i = 0; i < bytes; ++i)
+    if ((unsigned char)p[i] != kExchStagePattern) return false;
+  return true;
+}
+
+// launch_exch_pack behind the ExchCtl in d_ctl, then the send buffer taken apart.
+void pack_and_read(const ExchCtl* d_ctl, u32 P, const std::vector<KeyCount>& records,
+                   u32 slot_records, u64 pack_cap, ExchStagePlan* out) {
+  const u64 sb = exch_slot_bytes(slot_records);
+  LOCUST_CHECK_ARG((u64)P * sb <= kStageMaxBytes, "exchange stage: send buffer too large");
+  const u32 n = (u32)records.size();
+  DevBuf<KeyCount> d_recs(n);
+  d_recs.upload(records.data(), n);
+  DevBuf<u32> d_n(1);
+  d_n.upload(&n, 1);
+  DevBuf<char> d_send((u64)P * sb);
+  d_send.fill(kExchStagePattern);
+  launch_exch_pack(d_recs.p, d_n.p, pack_cap ? pack_cap : n, d_ctl, P, slot_records, d_send.p,
+                   nullptr);
+  sync();
+  std::vector<char> send((u64)P * sb);
+  d_send.download(send.data(), send.size());
+  out->slots.resize(P);
+  for (u32 d = 0; d < P; ++d) {
+    ExchStageSlot& sl = out->slots[d];
+    const char* base = send.data() + (u64)d * sb;
+    std::memcpy(&sl.header, base, sizeof(SlotHeader));
+    const char* area = base + sizeof(SlotHeader);
+    const u64 held = std::min<u64>(sl.header.n, slot_records);
+    sl.records.resize(held);
+    if (held) std::memcpy(sl.records.data(), area, held * sizeof(KeyCount));
+    sl.tail_intact = all_pattern(area + held * sizeof(KeyCount), (slot_records - held) * sizeof(KeyCount));
+    sl.dirty_records = 0;
+    for (u64 r = slot_records; r > 0; --r)
+      if (!all_pattern(area + (r - 1) * sizeof(KeyCount), sizeof(KeyCount))) {
+        sl.dirty_records = r;
+        break;
+      }
+  }
+}
+
+}  // namespace
+
+ExchStagePlan exch_stage_plan_pack(u32 P, u32 S, const std::vector<i32>& status,
+                                   const std::vector<u64>& n_local,
+                                   const std::vector<PackedKey>& samples,
+                                   const std::vector<KeyCount>& records, u32 slot_records,
+                                   u64 pack_cap) {
+  // (the same shape check as ShardEngine's exchange: the kernels' tables hold 64 ranks)
+  LOCUST_CHECK_ARG(P >= 1 && P <= kExchMaxRanks, "exchange: bad shape");
+  LOCUST_CHECK_ARG(S >= 1 && S <= 4096, "exchange stage: 1..4096 samples per rank");
+  LOCUST_CHECK_ARG(status.size() == P && n_local.size() == P && samples.size() == (u64)P * S,
+                   "exchange stage: need P statuses, P counts and P x S samples");
+  LOCUST_CHECK_ARG(records.size() < (1ull << 32), "exchange stage: too many records");
+  const u64 mb = exch_msg1_bytes(S);
+  std::vector<char> msgs((u64)P * mb);
+  for (u32 r = 0; r < P; ++r) {
+    ExchMsg1 h{};
+    h.status = status[r];
+    h.n_local = n_local[r];
+    std::memcpy(msgs.data() + (u64)r * mb, &h, sizeof h);
+    std::memcpy(msgs.data() + (u64)r * mb + sizeof h, samples.data() + (u64)r * S,
+                (u64)S * sizeof(PackedKey));
+  }
+  const u32 n = (u32)records.size();
+  DevBuf<char> d_msgs(msgs.size());
+  d_msgs.upload(msgs.data(), msgs.size());
+  DevKeys d_keys(n);
+  d_keys.upload(records.data(), n);
+  DevBuf<u32> d_n(1);
+  d_n.upload(&n, 1);
+  DevBuf<ExchCtl> d_ctl(1);
+  d_ctl.fill(kExchStagePattern);
+  launch_exch_plan(d_msgs.p, P, S, d_keys.soa(), d_n.p, slot_records, d_ctl.p, nullptr);
+  sync();
+  ExchStagePlan out;
+  d_ctl.download(&out.ctl, 1);
+  // the pack kernel indexes the records by these offsets: they must describe them
+  for (u32 p = 0; p < P; ++p)
+    if (out.ctl.off[p] > out.ctl.off[p + 1] || out.ctl.off[p + 1] > n)
+      throw Error("exchange stage: the plan's offsets leave the records");
+  if (out.ctl.off[0] != 0 || out.ctl.off[P] != n)
+    throw Error("exchange stage: the plan's offsets do not cover the records");
+  pack_and_read(d_ctl.p, P, records, slot_records, pack_cap, &out);
+  return out;
+}
+
+ExchStagePlan exch_stage_pack(const ExchCtl& ctl, u32 P, const std::vector<KeyCount>& records,
+                              u32 slot_records, u64 pack_cap) {
+  LOCUST_CHECK_ARG(P >= 1 && P <= kExchMaxRanks, "exchange: bad shape");
+  LOCUST_CHECK_ARG(records.size() < (1ull << 32), "exchange stage: too many records");
+  LOCUST_CHECK_ARG(ctl.off[0] == 0 && ctl.off[P] == records.size(),
+                   "exchange stage: offsets must cover the records");
+  for (u32 p = 0; p < P; ++p)
+    LOCUST_CHECK_ARG(ctl.off[p] <= ctl.off[p + 1], "exchange stage: offsets must ascend");
+  DevBuf<ExchCtl> d_ctl(1);
+  d_ctl.upload(&ctl, 1);
+  ExchStagePlan out;
+  out.ctl = ctl;
+  pack_and_read(d_ctl.p, P, records, slot_records, pack_cap, &out);
+  return out;
+}
+
+std::vector<PackedKey> exch_stage_sample(const std::vector<PackedKey>& sorted, u32 S) {
+  LOCUST_CHECK_ARG(S >= 1 && S <= (1u << 20), "exchange stage: 1..2^20 samples");
+  LOCUST_CHECK_ARG(sorted.size() < (1ull << 32), "exchange stage: too many keys");
+  const u32 n = (u32)sorted.size();
+  DevKeys d_keys(n);
+  d_keys.upload(sorted.data(), n);
+  DevBuf<u32> d_n(1);
+  d_n.upload(&n, 1);
+  DevBuf<PackedKey> d_out(S);
+  d_out.fill(kExchStagePattern);
+  launch_sample_keys(d_keys.soa(), d_n.p, S, d_out.p, nullptr);
+  sync();
+  std::vector<PackedKey> out(S);
+  d_out.download(out.data(), S);
+  return out;
+}
+
+u32 exch_stage_dict_overflow_flag() { return kCtrDictOverflow; }
+
+ExchStageHeader exch_stage_header(const ExchStageCounters& c, const ExchMsg1& tmpl,
+                                  bool combined, const std::vector<PackedKey>& sorted, u32 S,
+                                  u32 guard) {
+  LOCUST_CHECK_ARG(S <= (1u << 20) && guard <= 1024, "exchange stage: too many samples");
+  LOCUST_CHECK_ARG(sorted.size() < (1ull << 32), "exchange stage: too many keys");
+  MapCounters ctr{};
+  ctr.flags = c.flags;
+  ctr.num_unique = c.num_unique;
+  ctr.num_records = c.num_records;
+  ctr.map_tokens = c.map_tokens;
+  ctr.overflow_lines = c.overflow_lines;
+  ctr.truncated = c.truncated;
+  ctr.max_key_len = c.max_key_len;
+  const u32 n = (u32)sorted.size();
+  DevBuf<MapCounters> d_ctr(1);
+  d_ctr.upload(&ctr, 1);
+  DevKeys d_keys(n);
+  d_keys.upload(sorted.data(), n);
+  DevBuf<u32> d_n(1);
+  d_n.upload(&n, 1);
+  const u64 bytes = exch_msg1_bytes(S + guard);
+  DevBuf<char> d_out(bytes);
+  d_out.fill(kExchStagePattern);
+  launch_exch_header(d_ctr.p, tmpl, combined, reinterpret_cast<ExchMsg1*>(d_out.p), nullptr,
+                     d_keys.soa(), d_n.p, S);
+  sync();
+  std::vector<char> raw(bytes);
+  d_out.download(raw.data(), bytes);
+  ExchStageHeader out;
+  std::memcpy(&out.msg, raw.data(), sizeof(ExchMsg1));
+  out.samples.resize(S);
+  if (S) std::memcpy(out.samples.data(), raw.data() + sizeof(ExchMsg1), (u64)S * sizeof(PackedKey));
+  out.tail_intact = all_pattern(raw.data() + exch_msg1_bytes(S), (u64)guard * sizeof(PackedKey));
+  return out;
+}
+
+std::vector<u64> exch_stage_offsets(const std::vector<PackedKey>& sorted,
+                                    const std::vector<PackedKey>& splitters, u32 P) {
+  LOCUST_CHECK_ARG(P >= 1 && P <= (1u << 16) && splitters.size() == (u64)P - 1,
+                   "exchange stage: P buckets need P - 1 splitters");
+  LOCUST_CHECK_ARG(sorted.size() < (1ull << 32), "exchange stage: too many keys");
+  const u32 n = (u32)sorted.size();
+  DevKeys d_keys(n);
+  d_keys.upload(sorted.data(), n);
+  DevBuf<u32> d_n(1);
+  d_n.upload(&n, 1);
+  DevBuf<PackedKey> d_sp(P - 1);
+  d_sp.upload(splitters.data(), P - 1);
+  DevBuf<u64> d_off((u64)P + 1);
+  d_off.fill(kExchStagePattern);
+  launch_bucket_offsets(d_keys.soa(), d_n.p, d_sp.p, P, d_off.p, nullptr);
+  sync();
+  std::vector<u64> out((u64)P + 1);
+  d_off.download(out.data(), out.size());
+  return out;
+}
+
+ExchStageRoundTrip exch_stage_roundtrip(const std::vector<PackedKey>& keys,
+                                        const std::vector<u64>* counts,
+                                        const std::vector<u64>& lo) {
+  LOCUST_CHECK_ARG(keys.size() < (1ull << 32), "exchange stage: too many keys");
+  LOCUST_CHECK_ARG(!counts || counts->size() == keys.size(), "exchange stage: one count per key");
+  LOCUST_CHECK_ARG(lo.empty() || lo.size() == (size_t)kDictParts + 1,
+                   "lo needs kDictParts + 1 entries");
+  const u32 n = (u32)keys.size();
+  DevKeys d_keys(n), d_back(n);
+  d_keys.upload(keys.data(), n);
+  DevBuf<u64> d_counts(n), d_counts_back(n);
+  if (counts) d_counts.upload(counts->data(), n);
+  DevBuf<u32> d_n(1);
+  d_n.upload(&n, 1);
+  DevBuf<KeyCount> d_recs(n);
+  d_recs.fill(kExchStagePattern);
+  DevBuf<u8> d_parts(n);
+  DevBuf<u64> d_lo(kDictParts + 1);
+  PartMap pm;
+  if (!lo.empty()) {
+    d_lo.upload(lo.data(), lo.size());
+    pm.lo = d_lo.p;
+  }
+  for (int j = 0; j < kKeyWords; ++j)
+    LOCUST_HIP_CHECK(hipMemset(d_back.word(j), kExchStagePattern, (u64)std::max(n, 1u) * sizeof(u64)));
+  d_counts_back.fill(kExchStagePattern);
+  d_parts.fill(kExchStagePattern);
+  launch_pack_records(d_keys.soa(), counts ? d_counts.p : nullptr, d_n.p, n, d_recs.p, nullptr);
+  launch_unpack_records(d_recs.p, n, d_back.soa(), d_counts_back.p, d_parts.p, nullptr, pm);
+  sync();
+  ExchStageRoundTrip out;
+  out.packed.resize(n);
+  out.keys.resize(n);
+  out.counts.resize(n);
+  out.parts.resize(n);
+  d_recs.download(out.packed.data(), n);
+  d_back.download(out.keys.data(), n);
+  d_counts_back.download(out.counts.data(), n);
+  d_parts.download(out.parts.data(), n);
+  return out;
+}
+
+ExchStageReport exch_stage_report(const std::vector<SlotHeader>& headers, u32 slot_records,
+                                  const ExchCtl& ctl, const std::vector<u64>& acc,
+                                  u32 gather_records) {
+  const u32 P = (u32)headers.size();
+  LOCUST_CHECK_ARG(headers.size() >= 1 && headers.size() <= kExchMaxRanks, "exchange: bad shape");
+  LOCUST_CHECK_ARG(acc.size() == 3u * kMergeAccSpread, "exchange stage: 64 accumulator triples");
+  const u64 sb = exch_slot_bytes(slot_records);
+  LOCUST_CHECK_ARG((u64)P * sb <= kStageMaxBytes, "exchange stage: receive buffer too large");
+  std::vector<char> recv((u64)P * sb, (char)kExchStagePattern);
+  for (u32 q = 0; q < P; ++q) std::memcpy(recv.data() + (u64)q * sb, &headers[q], sizeof(SlotHeader));
+  DevBuf<char> d_recv(recv.size());
+  d_recv.upload(recv.data(), recv.size());
+  DevBuf<ExchCtl> d_ctl(1);
+  d_ctl.upload(&ctl, 1);
+  DevBuf<u64> d_acc(acc.size());
+  d_acc.upload(acc.data(), acc.size());
+  DevBuf<ExchMsg3> d_msg(1);
+  d_msg.fill(kExchStagePattern);
+  launch_exch_report(d_recv.p, P, slot_records, d_ctl.p, d_acc.p, gather_records, d_msg.p,
+                     nullptr);
+  sync();
+  ExchStageReport out;
+  d_msg.download(&out.msg, 1);
+  out.acc.resize(acc.size());
+  d_acc.download(out.acc.data(), out.acc.size());
+  return out;
+}
+
+}  // namespace locust

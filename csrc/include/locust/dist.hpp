@@ -395,6 +395,14 @@ void copy_device(void* dst, const void* src, u64 bytes, bool to_host, void* stre
 // Split a line-aligned text into `parts` line-aligned shards of ~equal bytes.
 std::vector<TextInput> shard_text(const TextInput& in, int parts);
 
+// Weighted-quantile splitters of the host-staged shuffle, from every rank's `s` evenly
+// spaced samples (samples[r * s + i]) and record counts: splitter p (p = 1..parts-1) is
+// the first sample, in key order, whose inclusive weight exceeds total * p / parts, each
+// sample of rank r weighing counts[r]; the all-ones key if there is none.  The same rule as
+// the device planner's (exch_plan_kernel, exchange.hip).
+std::vector<PackedKey> choose_splitters(const std::vector<PackedKey>& samples, u32 s,
+                                        const std::vector<u64>& counts, int parts);
+
 // One process drives `cfg.world` ranks (threads) over the visible GPUs (round robin);
 // rank 0's result is returned.  With Backend::kCpu the ranks use the CPU shard engine.
 // comm: kAuto = kLoopback (device-to-device copies between the ranks' buffers); kRccl =

@@ -14,6 +14,7 @@
 #include "locust/dist.hpp"
 #include "locust/dstring.hpp"
 #include "locust/engine.hpp"
+#include "locust/exch_stage.hpp"
 #include "locust/gen.hpp"
 #include "locust/io.hpp"
 #include "locust/stage.hpp"
@@ -688,6 +689,61 @@ class PyDistRank {
   TextInput loaded_in_;
 };
 
+// ---- stage entry points of the device shuffle (locust/exch_stage.hpp) ----
+// Keys cross as blobs of 32-byte packed keys: each key its bytes, NUL padded -- the
+// big-endian form of its four words, so bytes compare like the packed keys do.
+std::vector<PackedKey> keys_from_blob(const std::string& b) {
+  LOCUST_CHECK_ARG(b.size() % kKeyBytes == 0, "a key blob holds 32 bytes per key");
+  std::vector<PackedKey> out(b.size() / kKeyBytes);
+  for (size_t i = 0; i < out.size(); ++i) pack_key(b.data() + i * kKeyBytes, kKeyBytes, out[i].w);
+  return out;
+}
+template <class Rec>  // PackedKey or KeyCount
+py::bytes blob_from_keys(const Rec* k, size_t n) {
+  std::string b(n * kKeyBytes, '\0');
+  for (size_t i = 0; i < n; ++i)
+    for (int j = 0; j < kKeyBytes; ++j)
+      b[i * kKeyBytes + j] = (char)(k[i].w[j >> 3] >> (56 - 8 * (j & 7)));
+  return py::bytes(b);
+}
+std::vector<KeyCount> records_from(const std::string& keys, const std::vector<u64>& counts) {
+  const std::vector<PackedKey> k = keys_from_blob(keys);
+  LOCUST_CHECK_ARG(k.size() == counts.size(), "one count per key");
+  std::vector<KeyCount> r(k.size());
+  for (size_t i = 0; i < k.size(); ++i) {
+    for (int w = 0; w < kKeyWords; ++w) r[i].w[w] = k[i].w[w];
+    r[i].count = counts[i];
+  }
+  return r;
+}
+py::dict exch_plan_dict(const ExchStagePlan& p, u32 P) {
+  py::dict d;
+  d["off"] = std::vector<u64>(p.ctl.off, p.ctl.off + P + 1);
+  d["flags"] = p.ctl.flags;
+  d["max_bucket"] = p.ctl.max_bucket;
+  py::list slots;
+  for (const ExchStageSlot& s : p.slots) {
+    py::dict e;
+    e["status"] = s.header.status;
+    e["record_flags"] = s.header.record_flags;
+    e["n"] = s.header.n;
+    e["slot_cap"] = s.header.slot_cap;
+    // the header's other fields (map statistics of the gather strategy, padding)
+    e["rest"] = std::vector<u64>{s.header.lines, s.header.tokens, s.header.overflow_lines,
+                                 s.header.truncated, s.header.max_key_len, s.header.pad[0],
+                                 s.header.pad[1]};
+    e["keys"] = blob_from_keys(s.records.data(), s.records.size());
+    std::vector<u64> counts(s.records.size());
+    for (size_t i = 0; i < counts.size(); ++i) counts[i] = s.records[i].count;
+    e["counts"] = counts;
+    e["dirty_records"] = s.dirty_records;
+    e["tail_intact"] = s.tail_intact;
+    slots.append(e);
+  }
+  d["slots"] = slots;
+  return d;
+}
+
 }  // namespace
 
 PYBIND11_MODULE(_locust, m) {
@@ -1216,6 +1272,177 @@ PYBIND11_MODULE(_locust, m) {
     PackedKey k = to_key(s);
     return std::vector<u64>(k.w, k.w + kKeyWords);
   });
+  // ---- the device shuffle's stages, each alone (locust/exch_stage.hpp; tests) ----
+  m.attr("EXCH_SEND_OVERFLOW") = kExchSendOverflow;
+  m.attr("EXCH_RECV_TRUNCATED") = kExchRecvTruncated;
+  m.attr("EXCH_ABORT") = kExchAbort;
+  m.attr("EXCH_TOO_MANY_SAMPLES") = kExchTooManySamples;
+  m.attr("EXCH_GATHER_OVERFLOW") = kExchGatherOverflow;
+  m.attr("EXCH_MAP_REDO") = kExchMapRedo;
+  m.attr("EXCH_MAX_RANKS") = kExchMaxRanks;
+  m.attr("EXCH_MAX_PLAN_SAMPLES") = kExchMaxPlanSamples;
+  m.attr("SLOT_OK") = kSlotOk;
+  m.attr("SLOT_FAILED") = kSlotFailed;
+  m.attr("SLOT_REDO") = kSlotRedo;
+  m.attr("EXCH_STAGE_PATTERN") = (u32)kExchStagePattern;
+  m.def("ctr_dict_overflow_flag", &exch_stage_dict_overflow_flag);
+  m.def("choose_splitters", [](const std::string& samples, u32 s, const std::vector<u64>& counts,
+                               int parts) {
+    const std::vector<PackedKey> smp = keys_from_blob(samples);
+    LOCUST_CHECK_ARG(s >= 1 && parts >= 1 && smp.size() == counts.size() * (u64)s,
+                     "need s samples per rank");
+    const std::vector<PackedKey> sp = choose_splitters(smp, s, counts, parts);
+    return blob_from_keys(sp.data(), sp.size());
+  }, py::arg("samples"), py::arg("s"), py::arg("counts"), py::arg("parts"),
+        "The host-staged shuffle's weighted-quantile splitters (dist.cpp; no GPU).");
+  m.def("exch_plan_pack", [](u32 P, u32 S, const std::vector<i32>& status,
+                             const std::vector<u64>& n_local, const std::string& samples,
+                             const std::string& keys, const std::vector<u64>& counts,
+                             u32 slot_records, u64 pack_cap) {
+    const std::vector<PackedKey> smp = keys_from_blob(samples);
+    const std::vector<KeyCount> recs = records_from(keys, counts);
+    ExchStagePlan p;
+    {
+      py::gil_scoped_release nogil;
+      p = exch_stage_plan_pack(P, S, status, n_local, smp, recs, slot_records, pack_cap);
+    }
+    return exch_plan_dict(p, P);
+  }, py::arg("P"), py::arg("S"), py::arg("status"), py::arg("n_local"), py::arg("samples"),
+        py::arg("keys"), py::arg("counts"), py::arg("slot_records"), py::arg("pack_cap") = 0,
+        "launch_exch_plan + launch_exch_pack on free-standing messages and sorted records.");
+  m.def("exch_pack", [](const std::vector<u64>& off, u32 flags, const std::string& keys,
+                        const std::vector<u64>& counts, u32 slot_records, u64 pack_cap) {
+    LOCUST_CHECK_ARG(off.size() >= 2 && off.size() <= (size_t)kExchMaxRanks + 1,
+                     "exchange: bad shape");
+    const u32 P = (u32)off.size() - 1;
+    ExchCtl ctl{};
+    for (size_t i = 0; i < off.size(); ++i) ctl.off[i] = off[i];
+    ctl.flags = flags;
+    for (u32 p = 0; p < P; ++p)
+      if (off[p + 1] >= off[p]) ctl.max_bucket = std::max(ctl.max_bucket, off[p + 1] - off[p]);
+    const std::vector<KeyCount> recs = records_from(keys, counts);
+    ExchStagePlan p;
+    {
+      py::gil_scoped_release nogil;
+      p = exch_stage_pack(ctl, P, recs, slot_records, pack_cap);
+    }
+    return exch_plan_dict(p, P);
+  }, py::arg("off"), py::arg("flags"), py::arg("keys"), py::arg("counts"),
+        py::arg("slot_records"), py::arg("pack_cap") = 0,
+        "launch_exch_pack alone behind given bucket offsets (P + 1) and plan flags.");
+  m.def("exch_sample", [](const std::string& keys, u32 S) {
+    const std::vector<PackedKey> k = keys_from_blob(keys);
+    std::vector<PackedKey> out;
+    {
+      py::gil_scoped_release nogil;
+      out = exch_stage_sample(k, S);
+    }
+    return blob_from_keys(out.data(), out.size());
+  }, py::arg("keys"), py::arg("S"), "launch_sample_keys of sorted keys -> S keys.");
+  m.def("exch_header", [](const py::dict& ctr, const py::dict& tmpl, bool combined,
+                          const std::string& keys, u32 S) {
+    auto get = [](const py::dict& d, const char* k) -> u64 {
+      return d.contains(k) ? d[k].cast<u64>() : 0;
+    };
+    ExchStageCounters c;
+    c.flags = (u32)get(ctr, "flags");
+    c.num_unique = (u32)get(ctr, "num_unique");
+    c.num_records = (u32)get(ctr, "num_records");
+    c.map_tokens = (u32)get(ctr, "map_tokens");
+    c.overflow_lines = (u32)get(ctr, "overflow_lines");
+    c.truncated = (u32)get(ctr, "truncated");
+    c.max_key_len = (u32)get(ctr, "max_key_len");
+    ExchMsg1 t{};
+    t.status = tmpl.contains("status") ? tmpl["status"].cast<i32>() : 0;
+    t.record_flags = (u32)get(tmpl, "record_flags");
+    t.n_local = get(tmpl, "n_local");
+    t.lines = get(tmpl, "lines");
+    t.tokens = get(tmpl, "tokens");
+    t.overflow_lines = get(tmpl, "overflow_lines");
+    t.truncated = get(tmpl, "truncated");
+    t.max_key_len = get(tmpl, "max_key_len");
+    t.out_region = get(tmpl, "out_region");
+    const std::vector<PackedKey> k = keys_from_blob(keys);
+    ExchStageHeader h;
+    {
+      py::gil_scoped_release nogil;
+      h = exch_stage_header(c, t, combined, k, S);
+    }
+    py::dict d;
+    d["status"] = h.msg.status;
+    d["record_flags"] = h.msg.record_flags;
+    d["n_local"] = h.msg.n_local;
+    d["lines"] = h.msg.lines;
+    d["tokens"] = h.msg.tokens;
+    d["overflow_lines"] = h.msg.overflow_lines;
+    d["truncated"] = h.msg.truncated;
+    d["max_key_len"] = h.msg.max_key_len;
+    d["out_region"] = h.msg.out_region;
+    d["samples"] = blob_from_keys(h.samples.data(), h.samples.size());
+    d["tail_intact"] = h.tail_intact;
+    return d;
+  }, py::arg("ctr"), py::arg("tmpl"), py::arg("combined"), py::arg("keys"), py::arg("S"),
+        "launch_exch_header: the written ExchMsg1, its S samples, and whether the bytes "
+        "behind them are untouched.");
+  m.def("exch_offsets", [](const std::string& keys, const std::string& splitters, u32 P) {
+    const std::vector<PackedKey> k = keys_from_blob(keys), sp = keys_from_blob(splitters);
+    py::gil_scoped_release nogil;
+    return exch_stage_offsets(k, sp, P);
+  }, py::arg("keys"), py::arg("splitters"), py::arg("P"),
+        "launch_bucket_offsets of P - 1 splitters in sorted keys -> P + 1 offsets.");
+  m.def("exch_roundtrip", [](const std::string& keys, const py::object& counts,
+                             const std::vector<u64>& lo) {
+    const std::vector<PackedKey> k = keys_from_blob(keys);
+    std::vector<u64> c;
+    if (!counts.is_none()) c = counts.cast<std::vector<u64>>();
+    ExchStageRoundTrip r;
+    {
+      py::gil_scoped_release nogil;
+      r = exch_stage_roundtrip(k, counts.is_none() ? nullptr : &c, lo);
+    }
+    py::dict d;
+    d["packed_keys"] = blob_from_keys(r.packed.data(), r.packed.size());
+    std::vector<u64> pc(r.packed.size());
+    for (size_t i = 0; i < pc.size(); ++i) pc[i] = r.packed[i].count;
+    d["packed_counts"] = pc;
+    d["keys"] = blob_from_keys(r.keys.data(), r.keys.size());
+    d["counts"] = r.counts;
+    d["parts"] = py::bytes(reinterpret_cast<const char*>(r.parts.data()), r.parts.size());
+    return d;
+  }, py::arg("keys"), py::arg("counts"), py::arg("lo") = std::vector<u64>{},
+        "launch_pack_records, then launch_unpack_records with the partition map `lo`.");
+  m.def("exch_report", [](const std::vector<std::pair<i32, u64>>& headers, u32 slot_records,
+                          u32 flags, u64 max_bucket, const std::vector<u64>& acc,
+                          u32 gather_records) {
+    std::vector<SlotHeader> hs(headers.size());
+    for (size_t q = 0; q < hs.size(); ++q) {
+      hs[q] = SlotHeader{};
+      hs[q].status = headers[q].first;
+      hs[q].record_flags = 3u;
+      hs[q].n = headers[q].second;
+      hs[q].slot_cap = slot_records;
+    }
+    ExchCtl ctl{};
+    ctl.flags = flags;
+    ctl.max_bucket = max_bucket;
+    ExchStageReport r;
+    {
+      py::gil_scoped_release nogil;
+      r = exch_stage_report(hs, slot_records, ctl, acc, gather_records);
+    }
+    py::dict d;
+    d["status"] = r.msg.status;
+    d["flags"] = r.msg.flags;
+    d["max_bucket"] = r.msg.max_bucket;
+    d["n_out"] = r.msg.n_out;
+    d["total"] = r.msg.total;
+    d["out_words"] = r.msg.out_words;
+    d["pad"] = std::vector<u64>(r.msg.pad, r.msg.pad + 3);
+    d["acc"] = r.acc;
+    return d;
+  }, py::arg("headers"), py::arg("slot_records"), py::arg("flags"), py::arg("max_bucket"),
+        py::arg("acc"), py::arg("gather_records"),
+        "launch_exch_report over P received (status, n) slot headers.");
   m.def("write_spill",
         [](const std::string& path, const std::vector<std::pair<std::string, u64>>& recs,
            const std::string& fmt) {

@@ -272,6 +272,26 @@ def test_gpu_device_exchange_loopback(hamlet, world):
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("text,world", [
+    (b"to be or not to be\nthat is the question\nwhether tis nobler\n", 8),  # five empty ranks
+    (b"word\n" * 2000, 4),  # one distinct key: every sample of every rank ties
+], ids=["three_lines_world8", "one_word_world4"])
+def test_gpu_device_exchange_loopback_degenerate(text, world):
+    """The loopback exchange where the planner's edge cases are the whole job: ranks with
+    no records (their samples are the all-ones key, their weight 0), and sample lists that
+    are one key repeated on every rank."""
+    job = lc.make_config("gpu", combine=True, check=True)
+    cfgs = [lc.make_dist_config(world, job, strategy="shuffle") for _ in range(4)]
+    ent, ntok, _ = oracle.wordcount(text)
+    out = lc._C.run_multi_schedule(text, cfgs, "loopback")
+    assert [i["host_syncs"] for _, i in out][:2] == [2, 1]
+    for j, (res, info) in enumerate(out):
+        assert info["strategy"] == "shuffle"
+        assert info["device_exchange"], (j, info)
+        assert res.entries() == ent and res.num_tokens == ntok
+
+
+@pytest.mark.gpu
 def test_gpu_device_exchange_many_keys():
     text = _distinct_text(30000) + b"w000001 w000007 w029999\n" * 3
     ent = oracle.wordcount(text)[0]

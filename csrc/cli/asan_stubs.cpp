@@ -21,10 +21,13 @@ TopResult GpuWordCount::run_top(const TextInput&, u32) { no_gpu(); }
 TopResult GpuWordCount::run_top_source(TextSource&, u32) { no_gpu(); }
 TopResult GpuWordCount::top_counts(const KeyCount*, u64, u32) { no_gpu(); }
 IndexResult GpuWordCount::run_index(const TextInput&) { no_gpu(); }
-SearchResult GpuWordCount::run_search(const TextInput&, const std::vector<SearchQuery>&, u64) {
+SearchResult GpuWordCount::run_search(const TextInput&, const std::vector<SearchQuery>&, u64,
+                                      bool) {
   no_gpu();
 }
-SearchResult GpuWordCount::search_resident(const std::vector<SearchQuery>&, u64) { no_gpu(); }
+SearchResult GpuWordCount::search_resident(const std::vector<SearchQuery>&, u64, bool) {
+  no_gpu();
+}
 char* GpuWordCount::input_buffer() { no_gpu(); }
 GpuWordCount::Stats GpuWordCount::stats() const { no_gpu(); }
 bool GpuWordCount::partition_map(std::vector<u64>*) { no_gpu(); }

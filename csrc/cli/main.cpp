@@ -25,6 +25,8 @@
 //   --not "w1 w2" (after a --search: lines that hold one of these words are no answer of it)
 //   --rank K (with --search: each query's K best lines with their scores, best first)
 //   --wildcard (with --search: a word that ends in * is a prefix term, "ham*")
+//   --glob (with --search: * and ? anywhere in a word, "*ing", "h?mlet"; a superset of --wildcard)
+//   --ignore-case (with --search: the ASCII letters of every word match either case)
 // and a synthetic-text generator (BASELINE configs "1M lines" / "10 GB"):
 //   MapReduce --gen FILE (--gen-lines N | --gen-bytes N) [--seed S] [--vocab V]
 #include <sys/stat.h>
@@ -100,6 +102,8 @@ struct CliArgs {
   bool rank_given = false;
   u64 rank = 0;  // --rank K: every query answers its K best lines, scored (0: all its lines)
   bool wildcard = false;  // --wildcard: a --search word that ends in * is a prefix term
+  bool glob = false;      // --glob: * and ? anywhere in a --search word (pattern terms)
+  bool ignore_case = false;  // --ignore-case: the batch's ASCII letters match either case
   std::string gen_out;  // generator mode
   GenSpec gen;
 };
@@ -165,6 +169,20 @@ void help() {
       "                             starts with what precedes the star, \"ham*\": it counts as\n"
       "                             one word whose lines are all of theirs.  A lone * is refused,\n"
       "                             a * anywhere else is literal.  With every --match and --rank)\n"
+      "  --glob                     (--search: * stands for any run of bytes, the empty one too,\n"
+      "                             and ? for exactly one byte, anywhere in a word: \"*ing\",\n"
+      "                             \"h?mlet\", \"*aml*\".  Such a word counts as one word whose\n"
+      "                             lines are those of every word the whole pattern matches; the\n"
+      "                             device scans the dictionary for them.  \"ham*\" stays the\n"
+      "                             prefix word of --wildcard, which --glob includes.  A pattern\n"
+      "                             is never cut: one longer than the key length is refused, and so\n"
+      "                             is one of stars alone.  With every --match, --rank, --not,\n"
+      "                             --within and --backend cpu; --rank then takes\n"
+      "                             --emits-per-line <= 8192)\n"
+      "  --ignore-case              (--search: the ASCII letters of every word of every query,\n"
+      "                             --not words too, match either case: \"to be\" finds \"To be\".\n"
+      "                             Other bytes match only themselves.  With --glob, --wildcard and\n"
+      "                             everything --glob goes with)\n"
       "  --help\n"
       "\n"
       "Environment: LOCUST_LOG=info|debug and the LOCUST_* switches in docs/ENVIRONMENT.md.\n",
@@ -309,6 +327,10 @@ bool parse(int argc, char** argv, CliArgs* a) {
       a->within_given = true;
     } else if (s == "--wildcard") {
       a->wildcard = true;
+    } else if (s == "--glob") {
+      a->glob = true;
+    } else if (s == "--ignore-case") {
+      a->ignore_case = true;
     } else if (s == "--rank") {
       const std::string v = need("--rank");
       char* endp = nullptr;
@@ -383,6 +405,10 @@ bool parse(int argc, char** argv, CliArgs* a) {
     throw Error("--rank K selects the best lines of a --search query: give --search too");
   if (a->wildcard && a->search_args.empty())
     throw Error("--wildcard selects how --search reads a word that ends in *: give --search too");
+  if (a->glob && a->search_args.empty())
+    throw Error("--glob selects how --search reads * and ? in a word: give --search too");
+  if (a->ignore_case && a->search_args.empty())
+    throw Error("--ignore-case selects how --search compares letters: give --search too");
   if (a->index && !a->search_args.empty())
     throw Error("--index and --search do not combine: --index prints the whole index, "
                 "--search the lines of its queries");
@@ -414,7 +440,9 @@ bool parse(int argc, char** argv, CliArgs* a) {
     std::vector<std::string> terms;
     std::string cur;
     for (const char c : arg) {
-      if (a->cfg.delimiters.find(c) != std::string::npos) {
+      // (--glob: a metacharacter is part of its word even when the job splits text at it)
+      const bool meta = a->glob && (c == '*' || c == '?');
+      if (!meta && a->cfg.delimiters.find(c) != std::string::npos) {
         if (!cur.empty()) terms.push_back(cur);
         cur.clear();
       } else {
@@ -434,14 +462,14 @@ bool parse(int argc, char** argv, CliArgs* a) {
     if (terms.empty()) throw Error("--search \"" + arg + "\" holds no word");
     // (a --not that holds no word excludes nothing)
     const std::vector<std::string> exclude = words(a->not_args[i]);
-    a->queries.push_back(make_search_query(terms, mode, a->wildcard, a->within, exclude));
+    a->queries.push_back(make_search_query(terms, mode, a->wildcard, a->within, exclude, a->glob));
   }
   if (!a->queries.empty()) {
     check_search_queries(a->queries, a->cfg);
     if (a->rank && (u64)a->cfg.emits_per_line > kRankMaxEmits)
       throw Error("--rank K takes --emits-per-line <= " + std::to_string(kRankMaxEmits) +
                   " (emits_per_line <= kRankMaxEmits: its scores fit 22 bits)");
-    check_search_rank(a->rank, a->cfg);
+    check_search_rank(a->rank, a->cfg, search_has_patterns(a->queries, a->ignore_case));
     if (a->cfg.backend == Backend::kGpu && a->queries.size() > (size_t)kSearchMaxQueries)
       throw Error("--search: a device batch holds at most " + std::to_string(kSearchMaxQueries) +
                   " queries (use --backend cpu for more)");
@@ -1177,7 +1205,7 @@ int run(const CliArgs& a) {
     for (int i = 0; i < a.warmup; ++i) eng.run(text.input);
     for (int i = 0; i < a.iters; ++i) {
       if (!a.queries.empty()) {
-        cpu_search = eng.run_search(text.input, a.queries, a.rank);
+        cpu_search = eng.run_search(text.input, a.queries, a.rank, a.ignore_case);
         r = search_stats(cpu_search);
       } else if (a.index) {
         cpu_index = eng.run_index(text.input);
@@ -1198,7 +1226,7 @@ int run(const CliArgs& a) {
     if (!a.queries.empty()) {  // the word job, the index stage and the search stage
       SearchResult sr;
       for (int i = 0; i < a.warmup + a.iters; ++i) {
-        sr = eng.run_search(text.input, a.queries, a.rank);
+        sr = eng.run_search(text.input, a.queries, a.rank, a.ignore_case);
         if (i >= a.warmup) walls.push_back(sr.times.wall_ms);
       }
       print_gpu_result(a, search_stats(sr), walls, nullptr, nullptr, &sr);

@@ -11,6 +11,7 @@
 #include <thread>
 
 #include "locust/config.hpp"
+#include "locust/device/glob.hpp"
 #include "locust/dstring.hpp"
 #include "locust/engine.hpp"
 
@@ -380,13 +381,40 @@ PackedKey search_term_key(const std::string& term, const JobConfig& cfg) {
 }
 
 SearchQuery make_search_query(const std::vector<std::string>& terms, SearchMode mode,
-                              bool wildcard, u64 within, const std::vector<std::string>& exclude) {
+                              bool wildcard, u64 within, const std::vector<std::string>& exclude,
+                              bool glob) {
   SearchQuery q;
   q.terms = terms;
   q.terms.insert(q.terms.end(), exclude.begin(), exclude.end());
   q.excluded = (u32)exclude.size();
   q.mode = mode;
   q.within = within;
+  if (glob) {
+    bool any_prefix = false, any_pattern = false;
+    std::vector<u8> prefix(q.terms.size(), 0), pattern(q.terms.size(), 0);
+    for (size_t t = 0; t < q.terms.size(); ++t) {
+      std::string& s = q.terms[t];
+      std::string c;  // runs of stars collapsed
+      for (const char ch : s)
+        if (ch != '*' || c.empty() || c.back() != '*') c.push_back(ch);
+      LOCUST_CHECK_ARG(c != "*", "search: a pattern of stars alone is no term: give at least "
+                                 "one other byte (ham*, *ing, h?mlet)");
+      const size_t meta = c.find_first_of("*?");
+      if (meta == std::string::npos) continue;  // a plain term (s == c: it holds no star)
+      s = c;
+      if (meta == s.size() - 1 && s.back() == '*') {  // p*: the prefix term
+        s.pop_back();
+        prefix[t] = 1;
+        any_prefix = true;
+      } else {
+        pattern[t] = 1;
+        any_pattern = true;
+      }
+    }
+    if (any_prefix) q.prefix = std::move(prefix);
+    if (any_pattern) q.pattern = std::move(pattern);
+    return q;
+  }
   if (!wildcard) return q;
   bool any = false;
   std::vector<u8> prefix(q.terms.size(), 0);
@@ -429,9 +457,29 @@ void check_search_queries(const std::vector<SearchQuery>& queries, const JobConf
       LOCUST_CHECK_ARG(q.within == 0,
                        "search: query " + std::to_string(i) + " has a window (within " +
                            std::to_string(q.within) + ") but is no near query");
-    for (const std::string& t : q.terms) {
+    LOCUST_CHECK_ARG(q.pattern.empty() || q.pattern.size() == q.terms.size(),
+                     "search: query " + std::to_string(i) + " has " +
+                         std::to_string(q.pattern.size()) + " pattern flags for " +
+                         std::to_string(q.terms.size()) + " terms; give none or one per term");
+    for (size_t ti = 0; ti < q.terms.size(); ++ti) {
+      const std::string& t = q.terms[ti];
       LOCUST_CHECK_ARG(!t.empty(), "search: query " + std::to_string(i) + " has an empty term");
+      const bool pat = q.is_pattern(ti);
+      if (pat) {
+        LOCUST_CHECK_ARG(!q.is_prefix(ti), "search: term " + std::to_string(ti) + " of query " +
+                                               std::to_string(i) +
+                                               " is flagged as a prefix term and as a pattern "
+                                               "term; it is one or the other");
+        LOCUST_CHECK_ARG(t.size() <= (size_t)cfg.max_key_len,
+                         "search: the pattern " + t + " of query " + std::to_string(i) + " has " +
+                             std::to_string(t.size()) + " bytes; a pattern is never cut and "
+                             "takes at most max_key_len = " + std::to_string(cfg.max_key_len));
+        LOCUST_CHECK_ARG(t.find_first_not_of('*') != std::string::npos,
+                         "search: a pattern of stars alone (query " + std::to_string(i) +
+                             ") is no term: give at least one other byte (ham*, *ing, h?mlet)");
+      }
       for (const char ch : t) {
+        if (pat && (ch == '*' || ch == '?')) continue;  // a metacharacter, not a word's byte
         const unsigned char c = (unsigned char)ch;
         LOCUST_CHECK_ARG(c != 0 && c != '\n' && cfg.delimiters.find(ch) == std::string::npos,
                          "search: a term of query " + std::to_string(i) + " holds byte " +
@@ -450,10 +498,57 @@ void check_search_merge(u64 queries, u64 elements) {
                 "the batch");
 }
 
-void check_search_rank(u64 rank_k, const JobConfig& cfg) {
+bool search_term_pattern(const SearchQuery& q, size_t t, const JobConfig& cfg, bool ignore_case,
+                         SearchPattern* out) {
+  const bool pat = q.is_pattern(t);
+  if (!pat && !ignore_case) return false;
+  if (!out) return true;
+  const std::string& s = q.terms[t];
+  char bytes[kKeyBytes];
+  u32 meta = 0;
+  int n = 0;
+  if (pat) {  // as asked: never cut (check_search_queries), star runs collapsed
+    for (const char ch : s) {
+      if (n == kKeyBytes) break;
+      const bool m = ch == '*' || ch == '?';
+      if (ch == '*' && n && bytes[n - 1] == '*' && ((meta >> (n - 1)) & 1u)) continue;
+      if (m) meta |= 1u << n;
+      bytes[n++] = ch;
+    }
+  } else {  // the cut term, every byte literal; a prefix term (after the cut) and its star
+    const int len = (int)std::min<size_t>(s.size(), (size_t)cfg.max_key_len);
+    for (; n < len && n < kKeyBytes; ++n) bytes[n] = s[(size_t)n];
+    if (search_term_prefix(q, t, cfg) && n < kKeyBytes) {
+      meta |= 1u << n;
+      bytes[n++] = '*';
+    }
+  }
+  if (ignore_case)
+    for (int i = 0; i < n; ++i)
+      if (!((meta >> i) & 1u) && bytes[i] >= 'A' && bytes[i] <= 'Z') bytes[i] = (char)(bytes[i] | 0x20);
+  pack_key(bytes, n, out->p.w);
+  out->meta = meta;
+  return true;
+}
+
+bool search_has_patterns(const std::vector<SearchQuery>& queries, bool ignore_case) {
+  if (ignore_case) return !queries.empty();
+  for (const SearchQuery& q : queries)
+    for (const u8 f : q.pattern)
+      if (f) return true;
+  return false;
+}
+
+void check_search_rank(u64 rank_k, const JobConfig& cfg, bool patterns) {
   if (rank_k == 0) return;
   LOCUST_CHECK_ARG(rank_k <= 0xffffffffull,
                    "search: rank takes 1 <= K < 2^32, not " + std::to_string(rank_k));
+  LOCUST_CHECK_ARG(!patterns || (u64)cfg.emits_per_line <= kRankMaxEmits / kSearchMaxTerms,
+                   "search: a ranked search with a pattern term (glob, ignore_case) takes "
+                   "emits_per_line <= kRankMaxEmits / " + std::to_string(kSearchMaxTerms) + " = " +
+                       std::to_string(kRankMaxEmits / kSearchMaxTerms) +
+                       " (pattern terms' lists may overlap: a score reaches 32 * emits_per_line "
+                       "* 8 and must fit 22 bits), not " + std::to_string(cfg.emits_per_line));
   LOCUST_CHECK_ARG((u64)cfg.emits_per_line <= kRankMaxEmits,
                    "search: a ranked search takes emits_per_line <= kRankMaxEmits = " +
                        std::to_string(kRankMaxEmits) + " (its scores fit 22 bits), not " +
@@ -462,26 +557,37 @@ void check_search_rank(u64 rank_k, const JobConfig& cfg) {
 
 namespace {
 
-// Does the token match key j?  masks: empty, or per key and word the bytes a token must
-// share with it (a prefix term: key_word_mask of its words; a plain term: every byte).
-bool token_matches(const PackedKey& tok, size_t j, const std::vector<PackedKey>& keys,
-                   const std::vector<PackedKey>& masks) {
-  if (masks.empty()) return key_compare(tok.w, keys[j].w) == 0;
+// The positive terms a line's tokens are matched against.  masks: empty, or per key and word
+// the bytes a token must share with it (a prefix term: key_word_mask of its words; a plain
+// term: every byte).  pats: empty, or per key whether it is evaluated as a pattern term
+// (is_pat) and then its pattern.
+struct TokenTerms {
+  std::vector<PackedKey> keys, masks;
+  std::vector<SearchPattern> pats;
+  std::vector<u8> is_pat;
+  bool fold = false;
+  size_t size() const { return keys.size(); }
+};
+
+// Does the token match term j?
+bool token_matches(const PackedKey& tok, size_t j, const TokenTerms& tt) {
+  if (!tt.pats.empty() && tt.is_pat[j])
+    return glob_match(tt.pats[j].p.w, tt.pats[j].meta, tok.w, tt.fold);
+  if (tt.masks.empty()) return key_compare(tok.w, tt.keys[j].w) == 0;
   bool same = true;
-  for (int i = 0; i < kKeyWords; ++i) same &= (tok.w[i] & masks[j].w[i]) == keys[j].w[i];
+  for (int i = 0; i < kKeyWords; ++i) same &= (tok.w[i] & tt.masks[j].w[i]) == tt.keys[j].w[i];
   return same;
 }
 
 // Do the first emits_per_line tokens of the line hold the keys as consecutive tokens?
-bool line_has_phrase(const char* line, u64 len, const std::vector<PackedKey>& keys,
-                     const std::vector<PackedKey>& masks, const JobConfig& cfg,
+bool line_has_phrase(const char* line, u64 len, const TokenTerms& keys, const JobConfig& cfg,
                      std::vector<PackedKey>* toks) {
   toks->clear();
   tokenize_line(line, len, cfg, toks, nullptr);
   const size_t m = keys.size();
   for (size_t o = 0; o + m <= toks->size(); ++o) {
     size_t j = 0;
-    while (j < m && token_matches((*toks)[o + j], j, keys, masks)) ++j;
+    while (j < m && token_matches((*toks)[o + j], j, keys)) ++j;
     if (j == m) return true;
   }
   return false;
@@ -490,9 +596,8 @@ bool line_has_phrase(const char* line, u64 len, const std::vector<PackedKey>& ke
 // Do `within` consecutive tokens among the first emits_per_line of the line match every key?
 // Per key the position of its last matching token: the shortest window that ends at token o
 // and covers every key starts at the smallest of them.
-bool line_has_near(const char* line, u64 len, const std::vector<PackedKey>& keys,
-                   const std::vector<PackedKey>& masks, u64 within, const JobConfig& cfg,
-                   std::vector<PackedKey>* toks) {
+bool line_has_near(const char* line, u64 len, const TokenTerms& keys, u64 within,
+                   const JobConfig& cfg, std::vector<PackedKey>* toks) {
   toks->clear();
   tokenize_line(line, len, cfg, toks, nullptr);
   const size_t m = keys.size();
@@ -500,7 +605,7 @@ bool line_has_near(const char* line, u64 len, const std::vector<PackedKey>& keys
   for (size_t o = 0; o < toks->size(); ++o) {
     bool any = false;
     for (size_t j = 0; j < m; ++j)
-      if (token_matches((*toks)[o], j, keys, masks)) {
+      if (token_matches((*toks)[o], j, keys)) {
         last[j] = o;
         any = true;
       }
@@ -518,9 +623,10 @@ bool line_has_near(const char* line, u64 len, const std::vector<PackedKey>& keys
 
 SearchResult search_index_impl(const IndexResult& x, const TextInput* text,
                                const std::vector<SearchQuery>& queries, const JobConfig& cfg,
-                               u64 rank_k) {
+                               u64 rank_k, bool ignore_case) {
   check_search_queries(queries, cfg);
-  check_search_rank(rank_k, cfg);
+  const bool patterns = search_has_patterns(queries, ignore_case);
+  check_search_rank(rank_k, cfg, patterns);
   bool verify = false;  // a phrase, or a near query, of two or more positive terms
   for (const SearchQuery& q : queries)
     verify |= (q.mode == SearchMode::kPhrase || q.mode == SearchMode::kNear) &&
@@ -564,6 +670,7 @@ SearchResult search_index_impl(const IndexResult& x, const TextInput* text,
   r.index_ms = x.index_ms;
   r.wire_bytes = x.wire_bytes;
   r.rank_k = rank_k;
+  r.ignore_case = ignore_case;
   r.emits_per_line = (u64)cfg.emits_per_line;
   const size_t n = x.words.entries.size();
   const WordCountEntry* ent = x.words.entries.data();
@@ -575,7 +682,9 @@ SearchResult search_index_impl(const IndexResult& x, const TextInput* text,
   struct List {
     const u32* p;
     u64 len;
-    size_t lo, hi;  // the key range [lo, hi) of its words
+    size_t lo, hi;  // the key range [lo, hi) of its words (a pattern term: lo == hi)
+    bool is_pat;        // a pattern term, and its pattern
+    SearchPattern pat;
   };
   std::vector<std::pair<u32, u32>> ranked;  // (score, line) of one query's matching lines
   for (size_t qi = 0; qi < queries.size(); ++qi) {
@@ -588,6 +697,43 @@ SearchResult search_index_impl(const IndexResult& x, const TextInput* text,
     bool absent = false, wild = false;
     for (size_t t = 0; t < q.terms.size(); ++t) {
       const bool pos = t < npos;
+      SearchPattern sp;
+      if (search_term_pattern(q, t, cfg, ignore_case, &sp)) {
+        // a pattern term: its words are scattered ranks, found by a scan with the matcher
+        std::vector<List>& into = pos ? lists : not_lists;
+        const List* same = nullptr;
+        for (const List& o : into)
+          if (o.is_pat && o.pat.meta == sp.meta && key_compare(o.pat.p.w, sp.p.w) == 0) same = &o;
+        if (same) {  // repeats an earlier term: the same count, no second list
+          r.term_counts[qi * kSearchMaxTerms + t] = same->len;
+          continue;
+        }
+        std::vector<size_t> words;
+        u64 len = 0;
+        for (size_t i = 0; i < n; ++i)
+          if (glob_match(sp.p.w, sp.meta, ent[i].key.w, ignore_case)) {
+            words.push_back(i);
+            len += ent[i].count;
+          }
+        if (words.empty()) {
+          // (an absent term is no list, so a later repetition scans again: absent again)
+          absent |= pos;
+          continue;
+        }
+        r.term_counts[qi * kSearchMaxTerms + t] = len;
+        List l{x.postings.data() + val[words[0]], len, 0, 0, true, sp};
+        if (words.size() >= 2) {
+          own.emplace_back();
+          own.back().reserve((size_t)len);
+          for (const size_t w : words)
+            own.back().insert(own.back().end(), x.postings.data() + val[w],
+                              x.postings.data() + val[w + 1]);
+          std::sort(own.back().begin(), own.back().end());
+          l.p = own.back().data();
+        }
+        into.push_back(l);
+        continue;
+      }
       const PackedKey k = search_term_key(q.terms[t], cfg);
       const auto less = [](const WordCountEntry& a, const PackedKey& b) {
         return key_compare(a.key.w, b.w) < 0;
@@ -615,7 +761,7 @@ SearchResult search_index_impl(const IndexResult& x, const TextInput* text,
       bool dup = false;
       for (const List& o : into) dup |= o.lo == lo && o.hi == hi;
       if (dup) continue;
-      List l{x.postings.data() + val[lo], val[hi] - val[lo], lo, hi};
+      List l{x.postings.data() + val[lo], val[hi] - val[lo], lo, hi, false, SearchPattern{}};
       if (hi - lo >= 2) {  // a concatenation of sorted lists: merge
         own.emplace_back(l.p, l.p + l.len);
         std::sort(own.back().begin(), own.back().end());
@@ -634,7 +780,8 @@ SearchResult search_index_impl(const IndexResult& x, const TextInput* text,
     std::vector<List> scored;
     for (const List& l : lists) {
       bool inside = false;
-      for (const List& o : lists) inside |= &o != &l && o.lo <= l.lo && l.hi <= o.hi;
+      for (const List& o : lists)  // (pattern terms: inside nothing, and nothing inside them)
+        inside |= &o != &l && !o.is_pat && !l.is_pat && o.lo <= l.lo && l.hi <= o.hi;
       if (!inside) scored.push_back(l);
     }
     if (q.mode != SearchMode::kAny) {
@@ -642,15 +789,22 @@ SearchResult search_index_impl(const IndexResult& x, const TextInput* text,
       // (W >= emits_per_line: no line has more tokens, the `all` answer stands)
       const bool near = q.mode == SearchMode::kNear && npos >= 2 &&
                         q.within < (u64)cfg.emits_per_line;
-      std::vector<PackedKey> keys, masks, toks;
+      TokenTerms keys;
+      std::vector<PackedKey> toks;
+      keys.fold = ignore_case;
       if (phrase || near)  // the positive terms only
         for (size_t t = 0; t < npos; ++t) {
-          keys.push_back(search_term_key(q.terms[t], cfg));
+          keys.keys.push_back(search_term_key(q.terms[t], cfg));
+          if (patterns) {
+            SearchPattern sp;
+            keys.is_pat.push_back(search_term_pattern(q, t, cfg, ignore_case, &sp) ? 1 : 0);
+            keys.pats.push_back(sp);
+          }
           if (!wild) continue;
           PackedKey m;
           for (int j = 0; j < kKeyWords; ++j)
-            m.w[j] = search_term_prefix(q, t, cfg) ? key_word_mask(keys.back().w[j]) : ~0ull;
-          masks.push_back(m);
+            m.w[j] = search_term_prefix(q, t, cfg) ? key_word_mask(keys.keys.back().w[j]) : ~0ull;
+          keys.masks.push_back(m);
         }
       if (!absent && !lists.empty()) {
         size_t d = 0;
@@ -669,8 +823,8 @@ SearchResult search_index_impl(const IndexResult& x, const TextInput* text,
                              "search: the text has fewer lines than the index names");
             const char* at = text->data + line_at[l];
             const u64 len = line_at[l + 1] - 1 - line_at[l];
-            hit = phrase ? line_has_phrase(at, len, keys, masks, cfg, &toks)
-                         : line_has_near(at, len, keys, masks, q.within, cfg, &toks);
+            hit = phrase ? line_has_phrase(at, len, keys, cfg, &toks)
+                         : line_has_near(at, len, keys, q.within, cfg, &toks);
           }
           if (hit) r.lines.push_back(line);
         }
@@ -696,9 +850,10 @@ SearchResult search_index_impl(const IndexResult& x, const TextInput* text,
           const u64 w = N / l.len;  // (>= 1: a list is part of the postings)
           score += (u64)(64 - __builtin_clzll(w)) * (u64)(eq.second - eq.first);
         }
-        if (score == 0 || score > 32 * (u64)cfg.emits_per_line)
+        if (score == 0 || score > 32 * (u64)cfg.emits_per_line * (patterns ? kSearchMaxTerms : 1))
           throw Error("search: line " + std::to_string(line) + " of query " + std::to_string(qi) +
-                      " scores " + std::to_string(score) + ", outside [1, 32 * emits_per_line]");
+                      " scores " + std::to_string(score) + ", outside [1, 32 * emits_per_line" +
+                      (patterns ? " * 8]" : "]"));
         ranked.emplace_back((u32)score, line);
       }
       std::sort(ranked.begin(), ranked.end(), [](const auto& a, const auto& b) {
@@ -722,14 +877,14 @@ SearchResult search_index_impl(const IndexResult& x, const TextInput* text,
 }  // namespace
 
 SearchResult search_index(const IndexResult& x, const std::vector<SearchQuery>& queries,
-                          const JobConfig& cfg, u64 rank_k) {
-  return search_index_impl(x, nullptr, queries, cfg, rank_k);
+                          const JobConfig& cfg, u64 rank_k, bool ignore_case) {
+  return search_index_impl(x, nullptr, queries, cfg, rank_k, ignore_case);
 }
 
 SearchResult search_index(const IndexResult& x, const TextInput& text,
                           const std::vector<SearchQuery>& queries, const JobConfig& cfg,
-                          u64 rank_k) {
-  return search_index_impl(x, &text, queries, cfg, rank_k);
+                          u64 rank_k, bool ignore_case) {
+  return search_index_impl(x, &text, queries, cfg, rank_k, ignore_case);
 }
 
 void validate_search(const SearchResult& r) {
@@ -744,6 +899,9 @@ void validate_search(const SearchResult& r) {
                 std::to_string(r.queries.size()) + " queries and " +
                 std::to_string(r.lines.size()) + " lines");
   const u64 lo = r.first_line, hi = r.first_line + r.num_lines;
+  // (pattern terms' lists may overlap: one token may count for every term of a query)
+  const u64 score_max = 32 * r.emits_per_line *
+                        (search_has_patterns(r.queries, r.ignore_case) ? kSearchMaxTerms : 1);
   for (size_t q = 0; q + 1 < r.offsets.size(); ++q) {
     if (r.offsets[q + 1] < r.offsets[q] || r.offsets[q + 1] > r.lines.size())
       throw Error("LOCUST_CHECK: search offsets decrease at query " + std::to_string(q));
@@ -759,9 +917,9 @@ void validate_search(const SearchResult& r) {
                     " outside the lines [" + std::to_string(lo) + ", " + std::to_string(hi) + ")");
       if (r.rank_k) {
         const u64 sc = r.scores[j];
-        if (sc < 1 || sc > 32 * r.emits_per_line)
+        if (sc < 1 || sc > score_max)
           throw Error("LOCUST_CHECK: score " + std::to_string(sc) + " of query " +
-                      std::to_string(q) + " outside [1, 32 * emits_per_line]");
+                      std::to_string(q) + " outside [1, " + std::to_string(score_max) + "]");
         if (j > r.offsets[q] &&
             (sc > r.scores[j - 1] || (sc == r.scores[j - 1] && l <= r.lines[j - 1])))
           throw Error("LOCUST_CHECK: lines of query " + std::to_string(q) +

@@ -50,11 +50,13 @@ TopResult GpuWordCount::top_counts(const KeyCount* recs, u64 n, u32 k) {
 }
 IndexResult GpuWordCount::run_index(const TextInput& in) { return impl_->run_index(in); }
 SearchResult GpuWordCount::run_search(const TextInput& in,
-                                      const std::vector<SearchQuery>& queries, u64 rank_k) {
-  return impl_->run_search(in, queries, rank_k);
+                                      const std::vector<SearchQuery>& queries, u64 rank_k,
+                                      bool ignore_case) {
+  return impl_->run_search(in, queries, rank_k, ignore_case);
 }
-SearchResult GpuWordCount::search_resident(const std::vector<SearchQuery>& queries, u64 rank_k) {
-  return impl_->search_resident(queries, rank_k);
+SearchResult GpuWordCount::search_resident(const std::vector<SearchQuery>& queries, u64 rank_k,
+                                           bool ignore_case) {
+  return impl_->search_resident(queries, rank_k, ignore_case);
 }
 GpuWordCount::Stats GpuWordCount::stats() const {
   Stats s;
@@ -69,7 +71,8 @@ GpuWordCount::Stats GpuWordCount::stats() const {
   s.chunk_bytes = impl_->cap_bytes;
   s.map_window = impl_->map_window;
   s.search_bytes = impl_->sbatch_bytes + impl_->shits_bytes +
-                   impl_->sbatch.merged_cap * sizeof(u32);
+                   impl_->sbatch.merged_cap * sizeof(u32) +
+                   (impl_->d_spat ? search_pattern_bytes() : 0);
   return s;
 }
 

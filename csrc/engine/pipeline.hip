@@ -557,6 +557,8 @@ DevicePipeline::~DevicePipeline() {
   if (d_sbatch) (void)hipFree(d_sbatch);
   if (d_shits) (void)hipFree(d_shits);
   if (d_smerged) (void)hipFree(d_smerged);
+  if (d_spat) (void)hipFree(d_spat);
+  pinned_free(h_spat);
   pinned_free(h_supload);
   pinned_free(h_sres);
   pinned_free(h_slines);
@@ -2121,19 +2123,28 @@ void DevicePipeline::ensure_search_merged(u64 elements) {
   sbatch.merged_cap = cap;
 }
 
-void DevicePipeline::check_search_batch(const std::vector<SearchQuery>& queries,
-                                        u64 rank_k) const {
+void DevicePipeline::ensure_search_patterns() {
+  if (d_spat) return;
+  // first batch of this engine with a pattern term: the per-slot pattern arrays and the pinned
+  // half that is uploaded (engines that never see a pattern keep their footprint)
+  LOCUST_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&d_spat), search_pattern_bytes()));
+  h_spat = static_cast<u32*>(
+      pinned_alloc(search_pattern_upload_bytes(), hipHostMallocDefault, "search patterns"));
+}
+
+void DevicePipeline::check_search_batch(const std::vector<SearchQuery>& queries, u64 rank_k,
+                                        bool ignore_case) const {
   LOCUST_CHECK_ARG(queries.size() <= (size_t)kSearchMaxQueries,
                    "search: a device batch holds at most kSearchMaxQueries = " +
                        std::to_string(kSearchMaxQueries) + " queries, not " +
                        std::to_string(queries.size()) + "; split the batch, or evaluate on the "
                        "host (search_index / IndexResult.search)");
   check_search_queries(queries, cfg);
-  check_search_rank(rank_k, cfg);
+  check_search_rank(rank_k, cfg, search_has_patterns(queries, ignore_case));
 }
 
 void DevicePipeline::search_stage(const std::vector<SearchQuery>& queries, u64 rank_k,
-                                  SearchResult* r) {
+                                  bool ignore_case, SearchResult* r) {
   TraceRange tr("locust:search");
   const u32 Q = (u32)queries.size();
   r->queries = queries;
@@ -2145,11 +2156,17 @@ void DevicePipeline::search_stage(const std::vector<SearchQuery>& queries, u64 r
   r->truncated = idx_words.truncated;
   r->max_key_len = idx_words.max_key_len;
   r->rank_k = rank_k;
+  r->ignore_case = ignore_case;
   r->emits_per_line = (u64)cfg.emits_per_line;
   r->offsets.assign((size_t)Q + 1, 0);
   r->matches.assign((size_t)Q, 0);
   r->term_counts.assign((size_t)Q * kSearchMaxTerms, 0);
   ensure_search();
+  // a batch with a pattern term (engine.hpp "pattern terms") drives the pattern stages; every
+  // other batch runs what it ran before they existed
+  const bool patterns = Q != 0 && search_has_patterns(queries, ignore_case);
+  if (patterns) ensure_search_patterns();
+  sbatch.pat = patterns ? d_spat : nullptr;
   LOCUST_HIP_CHECK(hipEventRecord(ev_search[0], stream));
   if (Q == 0) {
     LOCUST_HIP_CHECK(hipEventRecord(ev_search[1], stream));
@@ -2165,6 +2182,7 @@ void DevicePipeline::search_stage(const std::vector<SearchQuery>& queries, u64 r
   bool near = false;    // ... a near query of two or more terms and W < emits_per_line: the
                         // near kernel runs (a wider window holds every line: answered as `all`)
   std::memset(keys, 0, (size_t)Q * kSearchMaxTerms * sizeof(PackedKey));
+  if (patterns) std::memset(h_spat, 0, search_pattern_upload_bytes());
   for (u32 q = 0; q < Q; ++q) {
     const SearchQuery& sq = queries[q];
     // (the modes see the positive terms only; the exclusion terms stand behind them)
@@ -2181,6 +2199,16 @@ void DevicePipeline::search_stage(const std::vector<SearchQuery>& queries, u64 r
     for (size_t t = 0; t < sq.terms.size(); ++t) {
       if (t >= npos) meta[q] |= 1u << (kSearchExcludeShift + (int)t);
       // a prefix term's flag; its length needs no word: the key's non-zero bytes are it
+      SearchPattern sp;
+      if (search_term_pattern(sq, t, cfg, ignore_case, &sp)) {
+        // a pattern slot: the flag and the map in the pattern upload, the pattern's bytes in
+        // the slot's key words (q_meta's prefix bit stays clear: a prefix term under
+        // ignore_case is the pattern p*)
+        h_spat[q] |= (1u << t) | (ignore_case ? kSearchFold : 0u);
+        h_spat[kSearchPatMeta + (u64)q * kSearchMaxTerms + t] = sp.meta;
+        std::memcpy(keys + ((u64)q * kSearchMaxTerms + t) * kKeyWords, sp.p.w, sizeof(PackedKey));
+        continue;
+      }
       if (search_term_prefix(sq, t, cfg)) meta[q] |= 1u << (kSearchPrefixShift + (int)t);
       const PackedKey k = search_term_key(sq.terms[t], cfg);
       std::memcpy(keys + ((u64)q * kSearchMaxTerms + t) * kKeyWords, k.w, sizeof(PackedKey));
@@ -2188,7 +2216,11 @@ void DevicePipeline::search_stage(const std::vector<SearchQuery>& queries, u64 r
   }
   LOCUST_HIP_CHECK(hipMemcpyAsync(sbatch.upload, h_supload, search_upload_bytes(Q, near),
                                   hipMemcpyHostToDevice, stream));
-  // lookup: the terms' lists and the bound on the hits
+  if (patterns)
+    LOCUST_HIP_CHECK(hipMemcpyAsync(d_spat, h_spat, search_pattern_upload_bytes(),
+                                    hipMemcpyHostToDevice, stream));
+  // lookup (behind the match stage, in a pattern batch): the terms' lists and the bound on the
+  // hits
   launch_search_lookup(idx_view, sbatch, Q, stream);
   SearchCounters* h_sc = reinterpret_cast<SearchCounters*>(h_sres);
   u32* h_tlen = reinterpret_cast<u32*>(h_sres + kSearchResLen);
@@ -2199,6 +2231,10 @@ void DevicePipeline::search_stage(const std::vector<SearchQuery>& queries, u64 r
                                   hipMemcpyDeviceToHost, stream));
   sync();
   const u64 B = h_sc->bound;
+  if (h_sc->anyover)
+    throw Error("search: " + std::to_string(h_sc->anyover) + " `any` queries of the batch walk "
+                "2^32 list elements or more each (their pattern terms' lists overlap): split "
+                "the queries");
   if (B >= (1ull << 32))
     throw Error("search: the batch's " + std::to_string(Q) + " queries walk " + std::to_string(B) +
                 " list elements, which does not fit the 32-bit slot counter (2^32): split "
@@ -2278,7 +2314,7 @@ void DevicePipeline::search_stage(const std::vector<SearchQuery>& queries, u64 r
                   " sorted hits lie outside their query's range");
     if (h_sc->unscored)
       throw Error("search: " + std::to_string(h_sc->unscored) + " of " + std::to_string(H) +
-                  " hits score 0 or more than 32 * emits_per_line");
+                  " hits score 0 or more than 32 * emits_per_line" + (patterns ? " * 8" : ""));
     if (h_off[Q] != R)
       throw Error("search: the output offsets end at " + std::to_string(h_off[Q]) +
                   ", the hit counts and K give " + std::to_string(R));
@@ -2317,9 +2353,10 @@ void DevicePipeline::search_stage(const std::vector<SearchQuery>& queries, u64 r
 }
 
 SearchResult DevicePipeline::run_search(const TextInput& in,
-                                        const std::vector<SearchQuery>& queries, u64 rank_k) {
+                                        const std::vector<SearchQuery>& queries, u64 rank_k,
+                                        bool ignore_case) {
   TraceRange tr("locust:search_job");
-  check_search_batch(queries, rank_k);  // (a refused batch starts nothing)
+  check_search_batch(queries, rank_k, ignore_case);  // (a refused batch starts nothing)
   idx_resident = false;         // (until this job has left its index)
   SearchResult r;
   WordCountResult w;
@@ -2329,7 +2366,7 @@ SearchResult DevicePipeline::run_search(const TextInput& in,
   sync();
   check_index_counters(n, T);
   keep_index(in, w, n, T);
-  search_stage(queries, rank_k, &r);
+  search_stage(queries, rank_k, ignore_case, &r);
   r.index_ms = ms_between(ev_index[0], ev_index[1]);
   r.search_ms = ms_between(ev_search[0], ev_search[1]);
   r.wire_bytes += sizeof(IndexCounters) + sizeof(MapCounters);
@@ -2344,16 +2381,16 @@ SearchResult DevicePipeline::run_search(const TextInput& in,
 }
 
 SearchResult DevicePipeline::search_resident(const std::vector<SearchQuery>& queries,
-                                             u64 rank_k) {
+                                             u64 rank_k, bool ignore_case) {
   TraceRange tr("locust:search_resident");
-  check_search_batch(queries, rank_k);
+  check_search_batch(queries, rank_k, ignore_case);
   if (!idx_resident)
     throw Error("search_resident: the index on the device is stale -- this engine's last job "
                 "was not a run_index or a run_search (any other job, a refused one included, "
                 "overwrites what the index reads); run one of them first");
   SearchResult r;
   const u64 t0 = now_ns();
-  search_stage(queries, rank_k, &r);
+  search_stage(queries, rank_k, ignore_case, &r);
   r.search_ms = ms_between(ev_search[0], ev_search[1]);
   r.times.gpu_ms = r.search_ms;
   r.times.wall_ms = (now_ns() - t0) * 1e-6;

@@ -822,14 +822,22 @@ struct DevicePipeline {
   void ensure_search_merged(u64 elements);
   // Throws unless the batch fits the device stage, every term is valid and rank_k is 0
   // (unranked) or an accepted K (check_search_rank); launches nothing.
-  void check_search_batch(const std::vector<SearchQuery>& queries, u64 rank_k) const;
+  void check_search_batch(const std::vector<SearchQuery>& queries, u64 rank_k,
+                          bool ignore_case) const;
+  // The pattern arrays (kernels.hpp search_pattern_*): device words and their pinned upload
+  // half, made by the engine's first batch with a pattern term.
+  u32* d_spat = nullptr;
+  u32* h_spat = nullptr;
+  void ensure_search_patterns();
   // The batch over idx_view on `stream`, timed by ev_search; synchronises (the bound, the
   // number of hits, the result) and fills r's lists, statistics and wire_bytes.
   // rank_k != 0: the ranked answer (engine.hpp "ranked search").
-  void search_stage(const std::vector<SearchQuery>& queries, u64 rank_k, SearchResult* r);
+  void search_stage(const std::vector<SearchQuery>& queries, u64 rank_k, bool ignore_case,
+                    SearchResult* r);
   SearchResult run_search(const TextInput& in, const std::vector<SearchQuery>& queries,
-                          u64 rank_k);
-  SearchResult search_resident(const std::vector<SearchQuery>& queries, u64 rank_k);
+                          u64 rank_k, bool ignore_case);
+  SearchResult search_resident(const std::vector<SearchQuery>& queries, u64 rank_k,
+                               bool ignore_case);
 
   // ---------------------------------------------------------------------------------
   // Streaming: an input larger than the engine's text capacity is processed in

@@ -474,6 +474,54 @@ void format_index_output(const IndexResult& r, std::string* out);
 // their counts.  A term covering one word uses that word's list in place.
 // `*` is no delimiter: `ham*` is a legal literal token, and stays one unless the caller
 // asks for wildcards (make_search_query).
+//
+// ---- pattern terms: `*ing`, `h?mlet`, and ignore_case ----
+// A term may be a pattern term (SearchQuery::pattern[t] != 0, terms[t] holding the pattern as
+// asked, runs of `*` collapsed to one).  make_search_query's `glob` makes them: after the
+// collapse a term without `*` or `?` is a plain term, `p*` with p non-empty and free of
+// metacharacters is the prefix term of the section above (its cut rule included: glob is a
+// superset of wildcard, and both together are glob), and anything else that holds a `*` or a
+// `?` is a pattern term.  There is no escape character.  A pattern's bytes other than `*` and
+// `?` are validated as a term's are; a pattern longer than max_key_len bytes (a pattern is
+// never cut) and one with no byte other than `*` are refused.  `???` is legal.
+//   Words.  A pattern term's words are the index keys k, as the index holds them (cut to
+//     max_key_len, their length the bytes before the NUL padding), that the pattern matches
+//     as a whole: `*` matches any run of bytes, the empty run included; `?` exactly one byte
+//     and never the padding (`ab?` does not match the key `ab`); every other byte itself
+//     (device/glob.hpp: the one matcher both engines use).  The words are a scattered set of
+//     ranks, not a range.  The term's list is the multiset union of its words' postings, non-
+//     decreasing; its count the sum of their counts; without a word it is absent.
+//   ignore_case is a property of a whole batch.  Every term of the batch -- positive or
+//     exclusion; plain, prefix or pattern -- is cut exactly as without it and then evaluated as
+//     a pattern term whose bytes A-Z and a-z match either case: plain `hamlet` is the pattern
+//     `hamlet` (a `*` or `?` in it stays literal), prefix `ham*` the pattern `ham*`.  Only
+//     ASCII letters fold: `@`, `[`, `` ` ``, `{` and every byte of 0x80 or above match only
+//     themselves.
+//   Modes.  In `all`, `any`, exclusion and the candidate stage of `phrase` and `near` a pattern
+//     term is a word with its list.  In `phrase` and `near` verification a token matches a
+//     pattern term when its cut key matches the pattern under the same rule and the same fold.
+//     Absent-term rules, one-term shortcuts, the emit cap and the `near` window are unchanged.
+//   Identity.  Two pattern terms of a query are the same term when their pattern bytes (and
+//     which of them are metacharacters) are equal -- under ignore_case: equal after lower-casing
+//     ASCII.  The later one repeats the earlier one: it reports the same count, is not merged
+//     again and scores once.  A pattern term is never the same as a plain or prefix term, even
+//     when their word sets coincide; it is never inside another term's range and no term is
+//     inside it: the laminar-family rule applies to plain and prefix terms among themselves.
+//   Ranked.  weight and tf are a prefix term's: c_t is the term's count, tf the line's
+//     multiplicity in its list.  Lists of pattern terms may overlap, so one token may count for
+//     up to eight terms: a score is at most 32 * emits_per_line * 8.  A ranked batch that holds
+//     a pattern term (every batch under ignore_case) is refused when emits_per_line >
+//     kRankMaxEmits / 8, so the 22-bit score field still suffices; the device's `unscored`
+//     bound and validate_search's upper bound are 32 * emits_per_line * 8 for such a batch and
+//     unchanged for every other.
+//   `merged` adds the count of every pattern term that covers two or more words and repeats no
+//     earlier term of its query; one with exactly one word uses that word's list in place.
+//   `any` bound.  Overlapping lists can push a query's `any` bound past 2^32: the lookup sums
+//     in u64, counts the overflow and the host throws.
+//   term_counts keep their order, and format_search_output prints a pattern term as asked.
+// The device finds a pattern term's words by a scan of the dictionary (kernels.hpp
+// "search.hip": match, scatter): (pattern slots) x (dictionary words) matcher calls per batch,
+// twice for the slots that cover two or more words.
 constexpr u32 kSearchMaxQueries = 1024;
 constexpr u32 kSearchMaxTerms = 8;
 constexpr u64 kRankMaxEmits = 65536;
@@ -486,7 +534,9 @@ struct SearchQuery {
   u64 within = 0;  // kNear: the window W in tokens, 1 .. kSearchMaxWithin; other modes: 0
   std::vector<u8> prefix;  // empty: no prefix term; else parallel to terms, != 0: a prefix term
   u32 excluded = 0;  // the last `excluded` entries of terms are exclusion terms ("not")
+  std::vector<u8> pattern;  // empty: no pattern term; else parallel to terms, != 0: a pattern term
   bool is_prefix(size_t t) const { return t < prefix.size() && prefix[t] != 0; }
+  bool is_pattern(size_t t) const { return t < pattern.size() && pattern[t] != 0; }
   // the positive terms: terms[0 .. positives())
   size_t positives() const { return excluded < terms.size() ? terms.size() - excluded : 0; }
 };
@@ -502,6 +552,7 @@ struct SearchResult {
   u64 emits_per_line = 0;            // the job's (a ranked score is at most 32 * this)
   u64 merged = 0;                    // list elements the device merged for prefix terms (0:
                                      // none, or the host evaluation)
+  bool ignore_case = false;          // the batch was evaluated with ignore_case
   u64 first_line = 0;
   // the word job's statistics, as in TopResult
   u64 num_lines = 0;
@@ -527,10 +578,26 @@ inline bool search_term_prefix(const SearchQuery& q, size_t t, const JobConfig& 
 // becomes a prefix term of what precedes the star; a lone `*` is an error; a `*` anywhere
 // else is literal.  Without wildcard every term is literal.
 // within: the window of a `near` query (0: none).  exclude: the query's exclusion terms, read
-// as `terms` are and appended behind them.
+// as `terms` are and appended behind them.  glob: "pattern terms" above (runs of `*` collapse;
+// a lone star, or a run of them, is an error); with glob, wildcard changes nothing.
 SearchQuery make_search_query(const std::vector<std::string>& terms, SearchMode mode,
                               bool wildcard, u64 within = 0,
-                              const std::vector<std::string>& exclude = {});
+                              const std::vector<std::string>& exclude = {}, bool glob = false);
+// A term as the pattern it is evaluated as: the packed bytes (kv.hpp) and the map of its
+// metacharacters (device/glob.hpp).
+struct SearchPattern {
+  PackedKey p;
+  u32 meta = 0;
+};
+// Is term t of q evaluated as a pattern term -- a pattern term, or any term under
+// ignore_case?  If so *out (when given) is its pattern: a pattern term's bytes as asked, a
+// prefix term's cut prefix and a star, a plain term's cut bytes, all literal; under ignore_case
+// with the ASCII letters lower-cased (two terms are the same term when their patterns are
+// equal).
+bool search_term_pattern(const SearchQuery& q, size_t t, const JobConfig& cfg, bool ignore_case,
+                         SearchPattern* out = nullptr);
+// Does a batch of these queries hold a term that is evaluated as a pattern term?
+bool search_has_patterns(const std::vector<SearchQuery>& queries, bool ignore_case);
 // Throws unless every query has 1..kSearchMaxTerms valid terms for cfg's delimiter set, at
 // least one of them positive (and `prefix` empty or as long as `terms`), a `near` query a
 // window in [1, kSearchMaxWithin] and every other query none (within == 0).
@@ -538,31 +605,36 @@ void check_search_queries(const std::vector<SearchQuery>& queries, const JobConf
 // Throws when the `elements` list elements a device batch's prefix terms merge
 // (SearchResult::merged) do not fit the merge's 32-bit element counter.
 void check_search_merge(u64 queries, u64 elements);
-// Throws unless rank_k is 0 (unranked) or a u32 >= 1 with cfg.emits_per_line <= kRankMaxEmits.
-void check_search_rank(u64 rank_k, const JobConfig& cfg);
+// Throws unless rank_k is 0 (unranked) or a u32 >= 1 with cfg.emits_per_line <= kRankMaxEmits
+// (patterns: the batch holds a pattern term -- kRankMaxEmits / kSearchMaxTerms).
+void check_search_rank(u64 rank_k, const JobConfig& cfg, bool patterns = false);
 // The host evaluation over an index result, any number of queries (cfg: the index job's
 // delimiters and max_key_len).  Throws for a phrase query and for a `near` query of two or
 // more terms: the index holds no positions, so they need the text -- the four-argument
 // overload (what counts are the positive terms).
 // rank_k != 0 ranks every query (scores come from the postings alone).
+// ignore_case: "pattern terms" above.  Pattern terms' words come from a scan of the entries
+// with the shared matcher.
 SearchResult search_index(const IndexResult& x, const std::vector<SearchQuery>& queries,
-                          const JobConfig& cfg, u64 rank_k = 0);
+                          const JobConfig& cfg, u64 rank_k = 0, bool ignore_case = false);
 // The same with the text the index was built from (the same window: text.first_line ==
 // x.first_line; cfg also gives emits_per_line): a phrase's or a `near` query's candidates
 // come from the `all` evaluation and are verified by tokenising their lines with the CPU
 // engine's tokeniser.
 SearchResult search_index(const IndexResult& x, const TextInput& text,
                           const std::vector<SearchQuery>& queries, const JobConfig& cfg,
-                          u64 rank_k = 0);
+                          u64 rank_k = 0, bool ignore_case = false);
 // LOCUST_CHECK invariants of a search result: offsets monotone from 0 to lines.size(), every
 // line inside [first_line, first_line + num_lines), one `matches` per query.  Unranked: every
 // query's lines strictly ascending, matches == the hit counts, no scores.  Ranked: one score
-// per line, each in [1, 32 * emits_per_line], per query non-increasing with equal scores on
-// ascending lines, and at most min(rank_k, matches) lines per query.
+// per line, each in [1, 32 * emits_per_line] (a batch with a pattern term: times 8), per query
+// non-increasing with equal scores on ascending lines, and at most min(rank_k, matches) lines
+// per query.
 void validate_search(const SearchResult& r);
 // The result lines of a search, one per query:
 //   "print query: <terms joined by one space> \t hits: <h> \t lines: <l0> <l1> ...\n"
-// (a prefix term as it was asked: with its star; <terms> are the positive terms, and a query
+// (a prefix term as it was asked: with its star; a pattern term as it was asked, too;
+// <terms> are the positive terms, and a query
 // with exclusion terms prints " \t not: <those joined by one space>" before " \t hits:")
 // ranked (hits: the matches; nothing after "top:" when nothing matched):
 //   "print query: <terms> \t hits: <matches> \t top: <l0>:<s0> <l1>:<s1> ...\n"
@@ -702,11 +774,12 @@ class GpuWordCount {
   // stays in device memory beside the index (the engine's own copy, not the staging
   // buffer): phrase queries are verified against it.
   SearchResult run_search(const TextInput& in, const std::vector<SearchQuery>& queries,
-                          u64 rank_k = 0);
+                          u64 rank_k = 0, bool ignore_case = false);
   // Another batch from the index this engine's last job left on the device.  That job must
   // have been a run_index or a run_search: any other job (a refused one that had started
   // to write included) marks the index stale, and this then throws.
-  SearchResult search_resident(const std::vector<SearchQuery>& queries, u64 rank_k = 0);
+  SearchResult search_resident(const std::vector<SearchQuery>& queries, u64 rank_k = 0,
+                               bool ignore_case = false);
 
   const JobConfig& config() const;
   u64 token_capacity() const;
@@ -756,7 +829,7 @@ class CpuWordCount {
   // run_index() + the host evaluation (search_index with the text), any size, any number
   // of queries and every mode.
   SearchResult run_search(const TextInput& in, const std::vector<SearchQuery>& queries,
-                          u64 rank_k = 0);
+                          u64 rank_k = 0, bool ignore_case = false);
   std::vector<PackedKey> run_map_stage(const TextInput& in, WordCountResult* stats);
   WordCountResult run_reduce_stage(const PackedKey* keys, u64 n);
 

@@ -628,6 +628,14 @@ void launch_index(const IndexJob& job, IndexWorkspace& ws, SortPlan* h_plan, hip
 //
 // A sequence of kernels on `s`; data moves between workgroups only across the kernel
 // boundaries (the radix sort it reuses keeps its own look-back), no polled word:
+//   match    (only in a batch that has a pattern term, b.pat != null; engine.hpp "pattern
+//            terms") a grid walks the records in tiles of kSearchBlock, one record per thread,
+//            the key in registers, and loops over the batch's pattern slots (grid y: a share
+//            of the queries).  A pattern is wave-uniform: its words and its metacharacter map
+//            come by scalar loads.  One ballot per wave and pattern; a wave with a match adds,
+//            by one lane, its matching words and their summed counts to the slot's `words`
+//            and `len` and leaves one matching rank.  (pattern slots) x (dictionary words)
+//            matcher calls (device/glob.hpp)
 //   lookup   one thread per (query, term): find_rank of the packed key, the term's val and
 //            length; per query the distinct terms, the driver (the shortest list, `all`), the
 //            dead flag (`all` with an absent term) and the bound on its hits = the elements
@@ -653,6 +661,14 @@ void launch_index(const IndexJob& job, IndexWorkspace& ws, SortPlan* h_plan, hip
 //            term's words are those of term i, the query's first term with them (itself, an
 //            earlier exclusion term or a positive term), so every exclusion list is read once
 //            and a merged list through the slot that owns it
+//            A pattern slot takes its length and its words from the match stage, not from a
+//            range search: one word, t_val = val[rank] and the list stays in place; two or
+//            more and no dup, it is wide and adds its length to x_len and ctr->merge exactly as
+//            a wide prefix slot does.  It is dup when an earlier pattern term of its query has
+//            equal pattern words and metacharacter map (the host lower-cases a folding
+//            batch's patterns); it takes no part in the range rules: never the same as a plain
+//            or prefix term, never inside one, none inside it.  An `any` query's bound is
+//            summed in u64; one past 32 bits counts in ctr->anyover
 //   scan     one workgroup: q_start[0 .. Q] = exclusive scan of the bounds, the total B
 //   (the host reads B, the merge total X and the term counts in one readback, and sizes the
 //   hit workspace for max(B, X))
@@ -663,10 +679,20 @@ void launch_index(const IndexJob& job, IndexWorkspace& ws, SortPlan* h_plan, hip
 //            gather   the flattened [0, X) in tiles of kSearchTile, grid-stride: a binary
 //                     search in x_start finds the element's slot, the key is
 //                     slot << 32 | (line - first_line), written to the hit workspace's
-//                     `pairs` (idle until the hit stage); its first thread sets merge_n = X
+//                     `pairs` (idle until the hit stage); its first thread sets merge_n = X.
+//                     It skips the elements of pattern slots
+//            scatter  (pattern batches) the match stage's walk and match once more, over the
+//                     wide pattern slots only.  Per wave and pattern: a wave prefix sum of the
+//                     matching words' counts, one atomic on the slot's cursor reserves the
+//                     room, then the whole wave copies each matching word's postings in turn,
+//                     coalesced (never one thread per word: `the` has thousands), as keys
+//                     slot << 32 | (line - first_line) at x_start[slot] + the reserved offset,
+//                     never outside the slot's part of [0, X).  The order of the words does
+//                     not matter: the sort decides
 //            order    radix_sort() of the keys as one-word keys: (slot, line)
 //            strip    merged[e] = first_line + low32(sorted[e]); a key outside its slot's
-//                     x_start range counts in `unmerged` (the host throws); the merged
+//                     x_start range counts in `unmerged` (the host throws), and so does a
+//                     pattern slot whose cursor does not end at its x_len; the merged
 //                     slots' t_val become kSearchMerged | x_start[slot]
 //            The hit, phrase-candidate and score stages read such a term's list from
 //            merged + x_start[slot], t_len elements, as they read any list
@@ -710,7 +736,12 @@ void launch_index(const IndexJob& job, IndexWorkspace& ws, SortPlan* h_plan, hip
 //            ends at a matching token).  The state carries across the 64-byte steps;
 //            ordinals and W are full u32.  Commits as the phrase kernel does; `nverified`
 //            counts the decided candidates
-//   seal     one thread: the sort's length, capped by the workspace
+//            A batch that has a pattern term runs the two kernels' siblings instead
+//            (search_globphrase_kernel, search_globnear_kernel: the same bodies, compiled with
+//            the matcher): a token matches a pattern term when glob_match says so of its cut
+//            key, with the batch's fold; plain and prefix terms of such a batch match as ever.
+//            Every other batch runs the kernels it ran before, at their resources
+//   seal    one thread: the sort's length, capped by the workspace
 //   (the host reads the number of hits H: the sort takes its regime from it)
 //   order    radix_sort() of the pair words as one-word keys
 //   offsets  one workgroup: offsets[0 .. Q] = exclusive scan of the per-query hit counts
@@ -725,8 +756,8 @@ void launch_index(const IndexJob& job, IndexWorkspace& ws, SortPlan* h_plan, hip
 //            of the line in the term's list (never outside it), weight =
 //            32 - clz(N / t_len) with N = val[n]; the pair becomes the rank key
 //            query << 54 | (kRankScoreMax - score) << 32 | rel_line in `cands`, which the
-//            phrase kernel has left.  A score of 0 or above 32 * emits_per_line counts in
-//            `unscored`
+//            phrase kernel has left.  A score of 0 or above 32 * emits_per_line (a batch that
+//            has a pattern term: times 8, its lists may overlap) counts in `unscored`
 //   order    radix_sort() of the rank keys as one-word keys: (query, score descending, line
 //            ascending); the keys are distinct
 //   top      one thread per sorted key at j: pos = j - offsets[q], the misplaced check as
@@ -745,6 +776,9 @@ struct SearchCounters {  // zeroed per batch
   u32 unmerged;   // sorted merge keys outside their slot's x_start range
   u32 ncands;     // `near` candidates the hit kernel wrote (from the end of `cands` down)
   u32 nverified;  // `near` candidates the near kernel has decided
+  u32 anyover;    // `any` queries whose bound (the sum of their lists' lengths; pattern terms'
+                  // lists may overlap) does not fit 32 bits: the host throws
+  u32 pad;
 };
 static_assert(sizeof(SearchCounters) <= 64, "the counters share one 64-byte block");
 constexpr int kSearchBlock = 256;
@@ -760,6 +794,26 @@ constexpr int kSearchExcludeShift = 24;  // q_meta bit 24 + t: term t is an excl
                                          // last terms of the query: positive terms stand first)
 constexpr u64 kSearchMerged = 1ull << 63;  // t_val: the list lies in `merged`, not in postings
 constexpr u32 kSearchSlots = kSearchMaxQueries * kSearchMaxTerms;  // (query, term) slots
+// The pattern arrays (engine.hpp "pattern terms"): one allocation of u32 words, made by an
+// engine's first batch that has a pattern term.  The first two parts are uploaded per pattern
+// batch, the other four zeroed per pattern batch:
+//   flags  [kSearchMaxQueries] bit t: term t is evaluated as a pattern term, its pattern's
+//          bytes in the slot's `keys` words; kSearchFold: ASCII letters match either case
+//   meta   [kSearchSlots] the pattern's metacharacter map (device/glob.hpp)
+//   words  [kSearchSlots] the index keys the pattern matches (the match kernel's count)
+//   len    [kSearchSlots] the sum of their counts: the list's length (< 2^32: the words are
+//          distinct, and the index holds fewer postings than that)
+//   rank   [kSearchSlots] the rank of one matching word (the word, when there is just one)
+//   cursor [kSearchSlots] the scatter kernel's fill of the slot's part of [0, X)
+constexpr u32 kSearchFold = 1u << 8;
+constexpr u64 kSearchPatMeta = kSearchMaxQueries;
+constexpr u64 kSearchPatWords = kSearchPatMeta + kSearchSlots;
+constexpr u64 kSearchPatLen = kSearchPatWords + kSearchSlots;
+constexpr u64 kSearchPatRank = kSearchPatLen + kSearchSlots;
+constexpr u64 kSearchPatCursor = kSearchPatRank + kSearchSlots;
+constexpr u64 kSearchPatEnd = kSearchPatCursor + kSearchSlots;
+inline u64 search_pattern_bytes() { return kSearchPatEnd * sizeof(u32); }
+inline u64 search_pattern_upload_bytes() { return kSearchPatWords * sizeof(u32); }
 // The index a batch is answered from (all device memory, launch_index's output).
 struct SearchIndex {
   const OutRecord* recs = nullptr;  // [n] key order
@@ -800,6 +854,9 @@ struct SearchBatch {
   u64* x_start = nullptr;  // [kSearchSlots + 1] expand: exclusive scan of x_len
   u32* merged = nullptr;   // [merged_cap] expand: the merged lists, slot after slot (an
   u64 merged_cap = 0;      // allocation of its own, grown on demand: the engine sets both)
+  u32* pat = nullptr;      // the pattern arrays (above) of a batch that has a pattern term; null
+                           // in every other batch (the engine sets it per batch), and then no
+                           // pattern stage runs
   u32* q_bound = nullptr;  // [Q]
   u64* q_start = nullptr;  // [Q + 1]
   u64* offsets = nullptr;  // [Q + 1]

@@ -20,6 +20,16 @@
 //    An exclusion term (engine.hpp "exclusion terms"; the host packs them behind the positive
 //    terms) is resolved like any term, but stays out of the driver choice, the bound, the dead
 //    flag and both masks: the present ones' lists go to the hit kernel as a mask of their own;
+//  * search_match_kernel, only in a batch that has a pattern term (engine.hpp "pattern terms"):
+//    a pattern term's words are a scattered set of ranks, so a grid walks the dictionary, one
+//    record per thread with the key in registers, and tries every pattern slot of the batch on
+//    it with the shared matcher (device/glob.hpp).  A pattern is wave-uniform (scalar loads);
+//    one ballot per wave and pattern, and one lane of a wave with a match adds the matching
+//    words and their summed counts to the slot's arrays.  The lookup then reads a pattern
+//    slot's length and word count from there instead of searching a range; a slot of two or
+//    more words is merged by the expand stage, where search_scatter_kernel -- the same walk
+//    and match -- copies each matching word's postings, the whole wave per word, to a place a
+//    wave prefix sum and one atomic on the slot's cursor reserve;
 //  * search_scan_kernel: one workgroup, exclusive scan of u32 values into count + 1 u64
 //    words (the bounds -> q_start, later the hit counts -> offsets, the merged lengths of
 //    the Q * 8 slots -> x_start);
@@ -61,6 +71,7 @@
 // look-back); this file adds no polled word.
 #include <algorithm>
 
+#include "locust/device/glob.hpp"
 #include "locust/device/linetok.hpp"
 #include "locust/device/rank.hpp"
 #include "locust/device/wave.hpp"
@@ -78,11 +89,57 @@ constexpr int kPhraseBlock = 256;
 constexpr int kPhraseWaves = kPhraseBlock / 64;
 constexpr int kPhraseMaxBlocks = 2048;  // 8 workgroups per CU
 
+// ---- pattern terms: the dictionary scan ----
+// The walk the match and the scatter kernel share: grid x strides over the records in tiles
+// of kSearchBlock, one record per thread; grid y takes every gridDim.y-th query.  A tile's
+// waves are whole (the tail's dead lanes match nothing), so every ballot below is converged.
+constexpr u32 kMatchMaxBlocks = 1024;  // the grid: x * y workgroups at most
+
+// words[slot] += the records the slot's pattern matches, len[slot] += their counts, rank[slot]
+// = one of them (pw: words | len | rank, zeroed per batch).
+__global__ __launch_bounds__(kSearchBlock) void search_match_kernel(
+    const OutRecord* __restrict__ recs, u32 n, const u64* __restrict__ keys,
+    const u32* __restrict__ pq, u32 Q, u32* __restrict__ pw) {
+  const int lane = dev::lane_id();
+  for (u32 base = blockIdx.x * kSearchBlock; base < n; base += gridDim.x * kSearchBlock) {
+    const u32 rank = base + threadIdx.x;
+    const bool live = rank < n;
+    u64 k0 = 0, k1 = 0, k2 = 0, k3 = 0;
+    u32 cnt = 0;
+    if (live) {
+      k0 = recs[rank].w[0];
+      k1 = recs[rank].w[1];
+      k2 = recs[rank].w[2];
+      k3 = recs[rank].w[3];
+      cnt = (u32)recs[rank].count;  // (the index holds < 2^32 postings in all)
+    }
+    for (u32 q = blockIdx.y; q < Q; q += gridDim.y) {  // (uniform)
+      const u32 fl = pq[q];
+      const bool fold = (fl & kSearchFold) != 0;
+      for (u32 pm = fl & 0xffu; pm; pm &= pm - 1u) {  // (uniform) the query's pattern terms
+        const u32 slot = q * kTerms + (u32)__ffs((int)pm) - 1u;
+        const u64* p = keys + (u64)slot * kKeyWords;
+        const bool m = live && glob_match(p[0], p[1], p[2], p[3], pq[kSearchPatMeta + slot], k0,
+                                          k1, k2, k3, fold);
+        const u64 bm = dev::ballot(m);
+        if (bm == 0) continue;  // (wave-uniform)
+        const u32 sum = dev::wave_reduce_sum(m ? cnt : 0u);
+        if (lane == __ffsll((unsigned long long)bm) - 1) {
+          atomicAdd(&pw[slot], (u32)__popcll(bm));
+          atomicAdd(&pw[kSearchSlots + slot], sum);
+          pw[2 * kSearchSlots + slot] = rank;
+        }
+      }
+    }
+  }
+}
+
 __global__ __launch_bounds__(kSearchBlock) void search_lookup_kernel(
     const OutRecord* __restrict__ recs, u32 n, const u64* __restrict__ val,
     const u64* __restrict__ keys, const u32* __restrict__ q_meta, u32 Q, u64* __restrict__ t_val,
     u32* __restrict__ t_len, u32* __restrict__ q_info, u32* __restrict__ q_bound,
-    u32* __restrict__ x_len, SearchCounters* __restrict__ ctr) {
+    u32* __restrict__ x_len, SearchCounters* __restrict__ ctr, const u32* __restrict__ pq,
+    const u32* __restrict__ pw) {
   // a term's words: the rank range [lo, hi) -- one word, or a prefix term's; absent: n, n
   __shared__ u32 s_lo[kSearchBlock];
   __shared__ u32 s_hi[kSearchBlock];
@@ -96,7 +153,22 @@ __global__ __launch_bounds__(kSearchBlock) void search_lookup_kernel(
   const u32 npos = nterms - min((u32)__popc(meta >> kSearchExcludeShift), nterms);
   u32 lo = n, hi = n, len = 0;
   u64 at = 0;
-  if (t < nterms) {
+  // a pattern slot (pq: the batch's pattern flags and maps, null in a batch without pattern
+  // terms; pw: the match kernel's words | len | rank): its words are no range, so lo = hi = n
+  // keeps it out of the range rules below, and pwords stands for hi - lo
+  const u32 pfl = pq && q < Q ? pq[q] : 0u;
+  const bool ispat = t < nterms && ((pfl >> t) & 1u);
+  u32 pwords = 0;
+  if (ispat) {
+    pwords = pw[gid];
+    const u32 rank = pw[2 * kSearchSlots + gid];
+    if (pwords && rank < n) {
+      len = pw[kSearchSlots + gid];
+      if (pwords == 1) at = val[rank];  // the word's list in place
+    } else {
+      pwords = 0;
+    }
+  } else if (t < nterms) {
     const u64* k = keys + (u64)gid * kKeyWords;
     if ((meta >> (kSearchPrefixShift + t)) & 1u) {
       dev::find_prefix_range(recs, n, k[0], k[1], k[2], k[3], &lo, &hi);
@@ -143,11 +215,27 @@ __global__ __launch_bounds__(kSearchBlock) void search_lookup_kernel(
       if (i < npos) inside |= same ? i < t : (ilo <= lo && hi <= ihi);
     }
   }
-  s_flag[threadIdx.x] =
-      (lo < hi ? 1u : 0u) | (dup ? 2u : 0u) | (inside ? 4u : 0u) | (first << 4);
+  if (pwords) {
+    // pattern terms are the same term when their pattern words and maps are equal; the later
+    // one repeats the earlier one (and counts as inside it: it scores once)
+    const u64* k = keys + (u64)gid * kKeyWords;
+    const u32 km = pq[kSearchPatMeta + gid];
+    for (u32 i = 0; i < t; ++i) {
+      if (!((pfl >> i) & 1u)) continue;
+      const u64* o = keys + (u64)(gid - t + i) * kKeyWords;
+      if (o[0] != k[0] || o[1] != k[1] || o[2] != k[2] || o[3] != k[3] ||
+          pq[kSearchPatMeta + gid - t + i] != km)
+        continue;
+      dup = true;
+      first = i < first ? i : first;
+      inside |= i < npos;
+    }
+  }
+  s_flag[threadIdx.x] = (lo < hi || pwords ? 1u : 0u) | (dup ? 2u : 0u) | (inside ? 4u : 0u) |
+                        (first << 4);
   // a list of two or more words is merged (the expand stage), unless an earlier term of the
-  // query has the same words.  Only a prefix term covers two words.
-  const bool wide = hi - lo >= 2u && !dup;
+  // query has the same words.  Only a prefix term or a pattern term covers two words.
+  const bool wide = (hi - lo >= 2u || pwords >= 2u) && !dup;
   if (q < Q) x_len[gid] = wide ? len : 0u;
   if (dev::ballot(wide)) {  // (wave-uniform; no batch without prefix terms gets here)
     const u64 x = dev::wave_reduce_sum<u64>(wide ? (u64)len : 0ull);
@@ -168,7 +256,8 @@ __global__ __launch_bounds__(kSearchBlock) void search_lookup_kernel(
       }
       if (!(f & 4u)) smask |= 1u << j;
       // `any`: a list inside another adds no line to the union, and the lists left are
-      // disjoint ranges of < 2^32 postings, so sum fits 32 bits
+      // disjoint ranges of < 2^32 postings, so sum fits 32 bits -- but for pattern terms'
+      // lists, which may overlap: anyover below
       if (f & (any ? 4u : 2u)) continue;
       mask |= 1u << j;
       sum += ln[j];
@@ -182,6 +271,7 @@ __global__ __launch_bounds__(kSearchBlock) void search_lookup_kernel(
     // one, when the words are two or more
     for (u32 j = npos; j < nterms; ++j)
       if (fl[j] & 1u) xmask |= 1u << (fl[j] >> 4);
+    if (any && (sum >> 32)) atomicAdd(&ctr->anyover, 1u);  // (the host throws)
     const u32 bound = any ? (u32)sum : (dead || !mask ? 0u : best);
     q_info[q] = driver | (dead << 3) | (xmask << 8) | (mask << 16) | (smask << 24);
     q_bound[q] = bound;
@@ -218,7 +308,7 @@ __global__ __launch_bounds__(kSearchBlock) void search_scan_kernel(const u32* __
 __global__ __launch_bounds__(kSearchBlock) void search_gather_kernel(
     const u32* __restrict__ postings, u32 first_line, const u64* __restrict__ x_start,
     const u64* __restrict__ t_val, u32 S, u64 X, u64 cap, u64* __restrict__ keys,
-    SearchCounters* __restrict__ ctr) {
+    SearchCounters* __restrict__ ctr, const u32* __restrict__ pq) {
   if (x_start[S] != X || X > cap) return;  // (uniform; never: the host throws on merge_n)
   if (blockIdx.x == 0 && threadIdx.x == 0) ctr->merge_n = (u32)X;  // the sort's length
   for (u64 tile = blockIdx.x; tile * kSearchTile < X; tile += gridDim.x) {  // (uniform)
@@ -235,9 +325,70 @@ __global__ __launch_bounds__(kSearchBlock) void search_gather_kernel(
         else
           hi = mid;
       }
+      // a pattern slot's words are no CSR range: the scatter kernel fills its part
+      if (pq && ((pq[lo / kTerms] >> (lo % kTerms)) & 1u)) continue;
       // (e - x_start[lo] < x_len[lo] = the slot's t_len: inside its CSR range)
       const u32 line = postings[t_val[lo] + (e - x_start[lo])];
       keys[e] = ((u64)lo << 32) | (u64)(line - first_line);
+    }
+  }
+}
+
+// The wide pattern slots' part of the keys (x_len != 0 and a pattern slot): the match kernel's
+// walk and match; the matching words of a wave and pattern take consecutive room in the slot's
+// part of [0, X) -- a wave prefix sum of their counts behind one atomic on the slot's cursor --
+// and the wave copies their postings word by word, 64 elements per step.  Reads stay inside
+// the CSR (a word's val range), writes inside [x_start[slot], x_start[slot + 1]), whatever
+// the cursor says: a slot that does not fill exactly counts as unmerged in the strip.
+__global__ __launch_bounds__(kSearchBlock) void search_scatter_kernel(
+    const OutRecord* __restrict__ recs, u32 n, const u64* __restrict__ val,
+    const u32* __restrict__ postings, u32 first_line, const u64* __restrict__ pkeys,
+    const u32* __restrict__ pq, u32 Q, const u32* __restrict__ x_len,
+    const u64* __restrict__ x_start, u64 X, u64 cap, u32* __restrict__ cursor,
+    u64* __restrict__ keys) {
+  if (x_start[Q * kTerms] != X || X > cap) return;  // (uniform; as the gather kernel)
+  const int lane = dev::lane_id();
+  for (u32 base = blockIdx.x * kSearchBlock; base < n; base += gridDim.x * kSearchBlock) {
+    const u32 rank = base + threadIdx.x;
+    const bool live = rank < n;
+    u64 k0 = 0, k1 = 0, k2 = 0, k3 = 0;
+    u32 src = 0, cnt = 0;
+    if (live) {
+      k0 = recs[rank].w[0];
+      k1 = recs[rank].w[1];
+      k2 = recs[rank].w[2];
+      k3 = recs[rank].w[3];
+      src = (u32)val[rank];  // (the index holds < 2^32 postings in all)
+      cnt = (u32)(val[rank + 1] - val[rank]);
+    }
+    for (u32 q = blockIdx.y; q < Q; q += gridDim.y) {  // (uniform)
+      const u32 fl = pq[q];
+      const bool fold = (fl & kSearchFold) != 0;
+      for (u32 pm = fl & 0xffu; pm; pm &= pm - 1u) {  // (uniform) the query's pattern terms
+        const u32 slot = q * kTerms + (u32)__ffs((int)pm) - 1u;
+        if (x_len[slot] == 0u) continue;  // (uniform) not wide: nothing to merge
+        const u64* p = pkeys + (u64)slot * kKeyWords;
+        const bool m = live && glob_match(p[0], p[1], p[2], p[3], pq[kSearchPatMeta + slot], k0,
+                                          k1, k2, k3, fold);
+        u64 bm = dev::ballot(m);
+        if (bm == 0) continue;  // (wave-uniform)
+        const u32 mine = m ? cnt : 0u;
+        const u32 incl = dev::wave_inclusive_scan(mine);
+        const u32 total = (u32)__shfl((int)incl, 63, 64);
+        u32 at = 0;
+        if (lane == 0) at = atomicAdd(&cursor[slot], total);
+        at = (u32)__shfl((int)at, 0, 64) + incl - mine;  // this lane's word, inside the slot
+        const u64 lo = x_start[slot], hi = x_start[slot + 1];
+        for (; bm; bm &= bm - 1) {  // (wave-uniform) word by word, the whole wave copying
+          const int l = __ffsll((unsigned long long)bm) - 1;
+          const u32 wsrc = (u32)__shfl((int)src, l, 64);
+          const u32 wcnt = (u32)__shfl((int)cnt, l, 64);
+          const u64 dst = lo + (u32)__shfl((int)at, l, 64);
+          for (u32 i = (u32)lane; i < wcnt; i += 64u)
+            if (dst + i < hi)
+              keys[dst + i] = ((u64)slot << 32) | (u64)(postings[wsrc + i] - first_line);
+        }
+      }
     }
   }
 }
@@ -247,7 +398,8 @@ __global__ __launch_bounds__(kSearchBlock) void search_gather_kernel(
 __global__ __launch_bounds__(256) void search_strip_kernel(
     const u64* __restrict__ sorted, u64 X, const u64* __restrict__ x_start,
     const u32* __restrict__ x_len, u32 S, u32 first_line, u32* __restrict__ merged,
-    u64* __restrict__ t_val, SearchCounters* __restrict__ ctr) {
+    u64* __restrict__ t_val, SearchCounters* __restrict__ ctr, const u32* __restrict__ pq,
+    const u32* __restrict__ cursor) {
   if (ctr->merge_n != (u32)X) return;  // nothing was sorted (workgroup-uniform)
   const u64 gid = (u64)blockIdx.x * 256 + threadIdx.x, stride = (u64)gridDim.x * 256;
   u32 bad = 0;
@@ -258,7 +410,11 @@ __global__ __launch_bounds__(256) void search_strip_kernel(
     if (slot >= S || e < x_start[slot] || e >= x_start[slot + 1]) ++bad;
   }
   for (u64 slot = gid; slot < S; slot += stride)
-    if (x_len[slot]) t_val[slot] = kSearchMerged | x_start[slot];
+    if (x_len[slot]) {
+      t_val[slot] = kSearchMerged | x_start[slot];
+      // a pattern slot the scatter kernel did not fill exactly
+      if (pq && ((pq[slot / kTerms] >> (slot % kTerms)) & 1u) && cursor[slot] != x_len[slot]) ++bad;
+    }
   const u64 bm = dev::ballot(bad != 0);
   if (bm) {
     bad = dev::wave_reduce_sum(bad);
@@ -455,16 +611,36 @@ __global__ __launch_bounds__(kSearchBlock) void search_hit_kernel(
   }
 }
 
+// A pointer kept in vector registers from here on.  The verify kernels' walk keeps 97 scalar
+// registers live, and the matcher's divergent loop needs about twenty more for its masks: their
+// glob siblings move the pointers they rarely use out of the scalar file instead of spilling.
+template <class T>
+__device__ __forceinline__ T* in_vgprs(T* p) {
+  u64 v = reinterpret_cast<u64>(p);
+  asm volatile("" : "+v"(v));
+  return reinterpret_cast<T*>(v);
+}
+
 // Bit j: the token that starts at row[at] matches term j of the m keys at qk -- it equals
-// the key, or (pre bit j: a prefix term) starts with the key's bytes.
+// the key, or (pre bit j: a prefix term) starts with the key's bytes.  kGlob (a batch with
+// pattern terms): or (pt bit j: a pattern term) the key is a pattern that matches the token's
+// cut key, qm[j] its metacharacter map and pt's kSearchFold the batch's fold.
+template <bool kGlob>
 __device__ __forceinline__ u32 token_term_mask(const unsigned char* row, int at,
                                                const DelimMask& dm, int max_key_len,
-                                               const u64* qk, u32 m, u32 pre) {
+                                               const u64* qk, u32 m, u32 pre, u32 pt,
+                                               const u32* qm) {
   u64 w0, w1, w2, w3;
   dev::pack_row_key(row, at, dm, max_key_len, &w0, &w1, &w2, &w3);
   u32 eq = 0;
   for (u32 j = 0; j < m; ++j) {
     const u64* k = qk + j * kKeyWords;
+    if (kGlob && ((pt >> j) & 1u)) {  // (wave-uniform)
+      eq |= (u32)glob_match(k[0], k[1], k[2], k[3], qm[j], w0, w1, w2, w3,
+                            (pt & kSearchFold) != 0)
+            << j;
+      continue;
+    }
     if ((pre >> j) & 1u) {  // (wave-uniform) the token starts with the term's bytes
       eq |= (u32)(k[0] == (w0 & key_word_mask(k[0])) && k[1] == (w1 & key_word_mask(k[1])) &&
                   k[2] == (w2 & key_word_mask(k[2])) && k[3] == (w3 & key_word_mask(k[3])))
@@ -482,17 +658,28 @@ __device__ __forceinline__ u32 token_term_mask(const unsigned char* row, int at,
 // i's verdict, so a round ends like a step of the hit kernel: ONE atomic for its slots and
 // one per distinct query -- one atomic per verified line would serialise on ctr->written as
 // index_map_kernel's comment (index.hip) records for 10^6 lines.
-__global__ __launch_bounds__(kPhraseBlock) void search_phrase_kernel(
+template <bool kGlob>
+__device__ __forceinline__ void search_phrase_body(
+    unsigned char* row, u64* qk, u32* qm, const u32* __restrict__ pq,
     const char* __restrict__ text, u64 bytes, const u64* __restrict__ nl_pos,
-    const MapCounters* __restrict__ lctr, DelimMask dm, int emits_per_line, int max_key_len,
-    u32 group, const u32* __restrict__ q_meta, const u64* __restrict__ keys, u32 Q,
-    const u64* __restrict__ cands, u64* __restrict__ pairs, u64 pair_cap,
+    const MapCounters* __restrict__ lctr, const DelimMask& dm, int emits_per_line,
+    int max_key_len, u32 group, const u32* __restrict__ q_meta, const u64* __restrict__ keys,
+    u32 Q, const u64* __restrict__ cands, u64* __restrict__ pairs, u64 pair_cap,
     u32* __restrict__ q_hits, SearchCounters* __restrict__ ctr) {
-  __shared__ unsigned char s_row[kPhraseWaves][dev::kLineRow];
-  __shared__ u64 s_keys[kPhraseWaves][kTerms * kKeyWords];
+  // row, qk, qm: this wave's LDS -- the line step, the query's term keys and (kGlob) its
+  // pattern terms' metacharacter maps; pq: the batch's pattern flags and maps (kGlob)
+  if (kGlob) {  // (in_vgprs: room in the scalar file for the matcher)
+    pq = in_vgprs(pq);
+    nl_pos = in_vgprs(nl_pos);
+    q_meta = in_vgprs(q_meta);
+    keys = in_vgprs(keys);
+    cands = in_vgprs(cands);
+    pairs = in_vgprs(pairs);
+    q_hits = in_vgprs(q_hits);
+    ctr = in_vgprs(ctr);
+    lctr = in_vgprs(lctr);
+  }
   const int lane = dev::lane_id();
-  unsigned char* row = s_row[dev::wave_id()];
-  u64* qk = s_keys[dev::wave_id()];
   const u64 num_nl = lctr->num_newlines;
   const u64 num_lines = bytes ? num_nl + 1 : 0;
   const u64 C = ctr->cands <= pair_cap ? ctr->cands : 0;  // (an overflow: the host throws)
@@ -514,9 +701,11 @@ __global__ __launch_bounds__(kPhraseBlock) void search_phrase_kernel(
       const u32 m = (meta & 0xffu) - (u32)__popc(meta >> kSearchExcludeShift);
       if (m == 0 || m > (u32)kTerms) continue;    // (never: the host checked the batch)
       const u32 pre = (meta >> kSearchPrefixShift) & 0xffu;  // bit j: term j is a prefix term
+      const u32 pt = kGlob ? pq[q] : 0u;  // bit j: term j is a pattern term | kSearchFold
       if (q != q_loaded) {  // (wave-uniform) neighbours mostly share their query
         __builtin_amdgcn_wave_barrier();  // the previous candidate's key reads are done
         if (lane < kTerms * kKeyWords) qk[lane] = keys[(u64)q * kTerms * kKeyWords + lane];
+        if (kGlob && lane < kTerms) qm[lane] = pq[kSearchPatMeta + (u64)q * kTerms + lane];
         __builtin_amdgcn_wave_barrier();
         q_loaded = q;
       }
@@ -541,7 +730,7 @@ __global__ __launch_bounds__(kPhraseBlock) void search_phrase_kernel(
         const u32 ord = seen + (u32)__popcll(starts & below);
         const bool emit = ((starts >> lane) & 1ull) && ord < E;
         u32 eq = 0;  // bit j: this lane's token equals term j
-        if (emit) eq = token_term_mask(row, lane, dm, max_key_len, qk, m, pre);
+        if (emit) eq = token_term_mask<kGlob>(row, lane, dm, max_key_len, qk, m, pre, pt, qm);
         // the automaton over the step's emitted tokens in order (all wave-uniform)
         u64 em = dev::ballot(emit);
         if (dev::ballot(eq != 0u) == 0) {
@@ -579,17 +768,28 @@ __global__ __launch_bounds__(kPhraseBlock) void search_phrase_kernel(
 // ends there starts: the line matches when ord - min < W.  (A minimal covering window always
 // ends at a matching token.)  The state carries across the 64-byte steps; ordinals and W
 // are full u32.
-__global__ __launch_bounds__(kPhraseBlock) void search_near_kernel(
+template <bool kGlob>
+__device__ __forceinline__ void search_near_body(
+    unsigned char* row, u64* qk, u32* qm, const u32* __restrict__ pq,
     const char* __restrict__ text, u64 bytes, const u64* __restrict__ nl_pos,
-    const MapCounters* __restrict__ lctr, DelimMask dm, int emits_per_line, int max_key_len,
-    u32 group, const u32* __restrict__ q_meta, const u64* __restrict__ keys, u32 Q,
-    const u64* __restrict__ cands, u64* __restrict__ pairs, u64 pair_cap,
+    const MapCounters* __restrict__ lctr, const DelimMask& dm, int emits_per_line,
+    int max_key_len, u32 group, const u32* __restrict__ q_meta, const u64* __restrict__ keys,
+    u32 Q, const u64* __restrict__ cands, u64* __restrict__ pairs, u64 pair_cap,
     u32* __restrict__ q_hits, SearchCounters* __restrict__ ctr) {
-  __shared__ unsigned char s_row[kPhraseWaves][dev::kLineRow];
-  __shared__ u64 s_keys[kPhraseWaves][kTerms * kKeyWords];
+  // row, qk, qm: this wave's LDS -- the line step, the query's term keys and (kGlob) its
+  // pattern terms' metacharacter maps; pq: the batch's pattern flags and maps (kGlob)
+  if (kGlob) {  // (in_vgprs: room in the scalar file for the matcher)
+    pq = in_vgprs(pq);
+    nl_pos = in_vgprs(nl_pos);
+    q_meta = in_vgprs(q_meta);
+    keys = in_vgprs(keys);
+    cands = in_vgprs(cands);
+    pairs = in_vgprs(pairs);
+    q_hits = in_vgprs(q_hits);
+    ctr = in_vgprs(ctr);
+    lctr = in_vgprs(lctr);
+  }
   const int lane = dev::lane_id();
-  unsigned char* row = s_row[dev::wave_id()];
-  u64* qk = s_keys[dev::wave_id()];
   const u64 num_nl = lctr->num_newlines;  // (bytes > 0, the launch's check: num_nl + 1 lines)
   const u32 C = ctr->ncands <= pair_cap ? ctr->ncands : 0u;  // (an overflow: the host throws)
   const u32 wave = blockIdx.x * kPhraseWaves + dev::wave_id();
@@ -612,11 +812,13 @@ __global__ __launch_bounds__(kPhraseBlock) void search_near_kernel(
       const u32 m = (meta & 0xffu) - (u32)__popc(meta >> kSearchExcludeShift);
       if (m == 0 || m > (u32)kTerms) continue;    // (never: the host checked the batch)
       const u32 pre = (meta >> kSearchPrefixShift) & 0xffu;  // bit j: term j is a prefix term
+      const u32 pt = kGlob ? pq[q] : 0u;  // bit j: term j is a pattern term | kSearchFold
       // the batch's windows stand behind its keys (search_within)
       const u32 W = reinterpret_cast<const u32*>(keys + (u64)Q * kTerms * kKeyWords)[q];
       if (q != q_loaded) {  // (wave-uniform) neighbours mostly share their query
         __builtin_amdgcn_wave_barrier();  // the previous candidate's key reads are done
         if (lane < kTerms * kKeyWords) qk[lane] = keys[(u64)q * kTerms * kKeyWords + lane];
+        if (kGlob && lane < kTerms) qm[lane] = pq[kSearchPatMeta + (u64)q * kTerms + lane];
         __builtin_amdgcn_wave_barrier();
         q_loaded = q;
       }
@@ -643,7 +845,7 @@ __global__ __launch_bounds__(kPhraseBlock) void search_near_kernel(
         const u32 ord = seen + (u32)__popcll(starts & below);
         const bool emit = ((starts >> lane) & 1ull) && ord < E;
         u32 eq = 0;  // bit j: this lane's token matches term j
-        if (emit) eq = token_term_mask(row, lane, dm, max_key_len, qk, m, pre);
+        if (emit) eq = token_term_mask<kGlob>(row, lane, dm, max_key_len, qk, m, pre, pt, qm);
         // the step's matching tokens in order (all wave-uniform)
         u64 mm = dev::ballot(eq != 0u);
         while (mm) {
@@ -673,6 +875,63 @@ __global__ __launch_bounds__(kPhraseBlock) void search_near_kernel(
     if (lane == 0) atomicAdd(&ctr->nverified, cnt);
     commit_hits(hit, (u32)(mine >> 32), (u32)mine, pairs, pair_cap, q_hits, ctr);
   }
+}
+
+// The verify kernels: the two bodies above, without and with the pattern matcher.
+__global__ __launch_bounds__(kPhraseBlock) void search_phrase_kernel(
+    const char* __restrict__ text, u64 bytes, const u64* __restrict__ nl_pos,
+    const MapCounters* __restrict__ lctr, DelimMask dm, int emits_per_line, int max_key_len,
+    u32 group, const u32* __restrict__ q_meta, const u64* __restrict__ keys, u32 Q,
+    const u64* __restrict__ cands, u64* __restrict__ pairs, u64 pair_cap,
+    u32* __restrict__ q_hits, SearchCounters* __restrict__ ctr) {
+  __shared__ unsigned char s_row[kPhraseWaves][dev::kLineRow];
+  __shared__ u64 s_keys[kPhraseWaves][kTerms * kKeyWords];
+  search_phrase_body<false>(s_row[dev::wave_id()], s_keys[dev::wave_id()], nullptr, nullptr, text,
+                        bytes, nl_pos, lctr, dm, emits_per_line, max_key_len, group, q_meta, keys,
+                        Q, cands, pairs, pair_cap, q_hits, ctr);
+}
+
+// ... of a batch that has a pattern term (pq: its pattern flags and maps).
+__global__ __launch_bounds__(kPhraseBlock) void search_globphrase_kernel(
+    const char* __restrict__ text, u64 bytes, const u64* __restrict__ nl_pos,
+    const MapCounters* __restrict__ lctr, DelimMask dm, int emits_per_line, int max_key_len,
+    u32 group, const u32* __restrict__ q_meta, const u64* __restrict__ keys, u32 Q,
+    const u64* __restrict__ cands, u64* __restrict__ pairs, u64 pair_cap,
+    u32* __restrict__ q_hits, SearchCounters* __restrict__ ctr, const u32* __restrict__ pq) {
+  __shared__ unsigned char s_row[kPhraseWaves][dev::kLineRow];
+  __shared__ u64 s_keys[kPhraseWaves][kTerms * kKeyWords];
+  __shared__ u32 s_meta[kPhraseWaves][kTerms];
+  search_phrase_body<true>(s_row[dev::wave_id()], s_keys[dev::wave_id()], s_meta[dev::wave_id()], pq,
+                       text, bytes, nl_pos, lctr, dm, emits_per_line, max_key_len, group, q_meta,
+                       keys, Q, cands, pairs, pair_cap, q_hits, ctr);
+}
+
+__global__ __launch_bounds__(kPhraseBlock) void search_near_kernel(
+    const char* __restrict__ text, u64 bytes, const u64* __restrict__ nl_pos,
+    const MapCounters* __restrict__ lctr, DelimMask dm, int emits_per_line, int max_key_len,
+    u32 group, const u32* __restrict__ q_meta, const u64* __restrict__ keys, u32 Q,
+    const u64* __restrict__ cands, u64* __restrict__ pairs, u64 pair_cap,
+    u32* __restrict__ q_hits, SearchCounters* __restrict__ ctr) {
+  __shared__ unsigned char s_row[kPhraseWaves][dev::kLineRow];
+  __shared__ u64 s_keys[kPhraseWaves][kTerms * kKeyWords];
+  search_near_body<false>(s_row[dev::wave_id()], s_keys[dev::wave_id()], nullptr, nullptr, text,
+                        bytes, nl_pos, lctr, dm, emits_per_line, max_key_len, group, q_meta, keys,
+                        Q, cands, pairs, pair_cap, q_hits, ctr);
+}
+
+// ... of a batch that has a pattern term (pq: its pattern flags and maps).
+__global__ __launch_bounds__(kPhraseBlock) void search_globnear_kernel(
+    const char* __restrict__ text, u64 bytes, const u64* __restrict__ nl_pos,
+    const MapCounters* __restrict__ lctr, DelimMask dm, int emits_per_line, int max_key_len,
+    u32 group, const u32* __restrict__ q_meta, const u64* __restrict__ keys, u32 Q,
+    const u64* __restrict__ cands, u64* __restrict__ pairs, u64 pair_cap,
+    u32* __restrict__ q_hits, SearchCounters* __restrict__ ctr, const u32* __restrict__ pq) {
+  __shared__ unsigned char s_row[kPhraseWaves][dev::kLineRow];
+  __shared__ u64 s_keys[kPhraseWaves][kTerms * kKeyWords];
+  __shared__ u32 s_meta[kPhraseWaves][kTerms];
+  search_near_body<true>(s_row[dev::wave_id()], s_keys[dev::wave_id()], s_meta[dev::wave_id()], pq,
+                       text, bytes, nl_pos, lctr, dm, emits_per_line, max_key_len, group, q_meta,
+                       keys, Q, cands, pairs, pair_cap, q_hits, ctr);
 }
 
 // One thread, between the hits and the sort: the sort takes its length from device memory,
@@ -892,16 +1151,35 @@ void search_hits_carve(char* base, u64 cap, SearchHits* h) {
   h->cap = cap;
 }
 
+namespace {
+// The dictionary scan's grid: x over the record tiles, y over the queries while there are few
+// tiles (a small dictionary would otherwise leave most of the device idle).
+dim3 match_grid(u32 n, u32 queries) {
+  const u32 x = (u32)std::min<u64>(div_up((u64)std::max(n, 1u), (u64)kSearchBlock), kMatchMaxBlocks);
+  const u32 y = std::min(queries, std::max(1u, kMatchMaxBlocks / x));
+  return dim3(x, y);
+}
+}  // namespace
+
 void launch_search_lookup(const SearchIndex& ix, const SearchBatch& b, u32 queries,
                           hipStream_t s) {
   LOCUST_CHECK_ARG(queries >= 1 && queries <= kSearchMaxQueries,
                    "search: a batch holds 1 to " + std::to_string(kSearchMaxQueries) +
                        " queries, not " + std::to_string(queries));
   LOCUST_HIP_CHECK(hipMemsetAsync(b.zero, 0, b.zero_bytes, s));
+  if (b.pat) {  // match: the pattern slots' words, lengths and cursors start from zero
+    LOCUST_HIP_CHECK(hipMemsetAsync(b.pat + kSearchPatWords, 0,
+                                    (kSearchPatEnd - kSearchPatWords) * sizeof(u32), s));
+    if (ix.n) {
+      search_match_kernel<<<match_grid(ix.n, queries), dim3(kSearchBlock), 0, s>>>(
+          ix.recs, ix.n, b.keys, b.pat, queries, b.pat + kSearchPatWords);
+      LOCUST_HIP_LAUNCH_CHECK();
+    }
+  }
   const u32 blocks = (u32)div_up((u64)queries, (u64)kLookupQueries);
   search_lookup_kernel<<<dim3(blocks), dim3(kSearchBlock), 0, s>>>(
       ix.recs, ix.n, ix.val, b.keys, b.q_meta, queries, b.t_val, b.t_len, b.q_info, b.q_bound,
-      b.x_len, b.ctr);
+      b.x_len, b.ctr, b.pat, b.pat ? b.pat + kSearchPatWords : nullptr);
   LOCUST_HIP_LAUNCH_CHECK();
   search_scan_kernel<<<dim3(1), dim3(kSearchBlock), 0, s>>>(b.q_bound, queries, ~0u, b.q_start,
                                                             &b.ctr->bound);
@@ -921,8 +1199,14 @@ void launch_search_expand(const SearchIndex& ix, const SearchBatch& b, u32 queri
   LOCUST_HIP_LAUNCH_CHECK();
   const u32 gblocks = (u32)std::min<u64>(div_up(x, (u64)kSearchTile), (u64)kSearchMaxBlocks);
   search_gather_kernel<<<dim3(gblocks), dim3(kSearchBlock), 0, s>>>(
-      ix.postings, ix.first_line, b.x_start, b.t_val, slots, x, h.cap, h.pairs, b.ctr);
+      ix.postings, ix.first_line, b.x_start, b.t_val, slots, x, h.cap, h.pairs, b.ctr, b.pat);
   LOCUST_HIP_LAUNCH_CHECK();
+  if (b.pat && ix.n) {  // the wide pattern slots' part of the keys
+    search_scatter_kernel<<<match_grid(ix.n, queries), dim3(kSearchBlock), 0, s>>>(
+        ix.recs, ix.n, ix.val, ix.postings, ix.first_line, b.keys, b.pat, queries, b.x_len,
+        b.x_start, x, h.cap, b.pat + kSearchPatCursor, h.pairs);
+    LOCUST_HIP_LAUNCH_CHECK();
+  }
   ConstKeysSoA keys;
   KeysSoA sorted;
   keys.w[0] = h.pairs;
@@ -934,7 +1218,9 @@ void launch_search_expand(const SearchIndex& ix, const SearchBatch& b, u32 queri
   radix_sort(keys, &b.ctr->merge_n, x, h.rx, nullptr, sorted, nullptr, nullptr, h_plan, s);
   const u32 sblocks = (u32)std::min<u64>(div_up(std::max<u64>(x, slots), 256), 4096);
   search_strip_kernel<<<dim3(sblocks), dim3(256), 0, s>>>(h.sorted, x, b.x_start, b.x_len, slots,
-                                                          ix.first_line, b.merged, b.t_val, b.ctr);
+                                                          ix.first_line, b.merged, b.t_val, b.ctr,
+                                                          b.pat,
+                                                          b.pat ? b.pat + kSearchPatCursor : nullptr);
   LOCUST_HIP_LAUNCH_CHECK();
 }
 
@@ -960,9 +1246,14 @@ void launch_search_hits(const SearchIndex& ix, const SearchBatch& b, u32 queries
     const u32 group = (u32)std::min<u64>(div_up(bound, (u64)kPhraseMaxBlocks), 64);
     const u32 blocks = (u32)std::min<u64>(div_up(div_up(bound, (u64)group), (u64)kPhraseWaves),
                                           (u64)kPhraseMaxBlocks);
-    search_phrase_kernel<<<dim3(blocks), dim3(kPhraseBlock), 0, s>>>(
-        ix.text, ix.bytes, ix.nl_pos, ix.lctr, ix.dm, ix.emits_per_line, ix.max_key_len, group,
-        b.q_meta, b.keys, queries, h.cands, h.pairs, h.cap, b.q_hits, b.ctr);
+    if (b.pat)  // (a batch that has a pattern term: the sibling with the matcher)
+      search_globphrase_kernel<<<dim3(blocks), dim3(kPhraseBlock), 0, s>>>(
+          ix.text, ix.bytes, ix.nl_pos, ix.lctr, ix.dm, ix.emits_per_line, ix.max_key_len, group,
+          b.q_meta, b.keys, queries, h.cands, h.pairs, h.cap, b.q_hits, b.ctr, b.pat);
+    else
+      search_phrase_kernel<<<dim3(blocks), dim3(kPhraseBlock), 0, s>>>(
+          ix.text, ix.bytes, ix.nl_pos, ix.lctr, ix.dm, ix.emits_per_line, ix.max_key_len, group,
+          b.q_meta, b.keys, queries, h.cands, h.pairs, h.cap, b.q_hits, b.ctr);
     LOCUST_HIP_LAUNCH_CHECK();
   }
   if (bound && near && ix.bytes) {
@@ -973,9 +1264,14 @@ void launch_search_hits(const SearchIndex& ix, const SearchBatch& b, u32 queries
     const u32 group = (u32)std::min<u64>(div_up(bound, (u64)kPhraseMaxBlocks), 64);
     const u32 blocks = (u32)std::min<u64>(div_up(div_up(bound, (u64)group), (u64)kPhraseWaves),
                                           (u64)kPhraseMaxBlocks);
-    search_near_kernel<<<dim3(blocks), dim3(kPhraseBlock), 0, s>>>(
-        ix.text, ix.bytes, ix.nl_pos, ix.lctr, ix.dm, ix.emits_per_line, ix.max_key_len, group,
-        b.q_meta, b.keys, queries, h.cands, h.pairs, h.cap, b.q_hits, b.ctr);
+    if (b.pat)
+      search_globnear_kernel<<<dim3(blocks), dim3(kPhraseBlock), 0, s>>>(
+          ix.text, ix.bytes, ix.nl_pos, ix.lctr, ix.dm, ix.emits_per_line, ix.max_key_len, group,
+          b.q_meta, b.keys, queries, h.cands, h.pairs, h.cap, b.q_hits, b.ctr, b.pat);
+    else
+      search_near_kernel<<<dim3(blocks), dim3(kPhraseBlock), 0, s>>>(
+          ix.text, ix.bytes, ix.nl_pos, ix.lctr, ix.dm, ix.emits_per_line, ix.max_key_len, group,
+          b.q_meta, b.keys, queries, h.cands, h.pairs, h.cap, b.q_hits, b.ctr);
     LOCUST_HIP_LAUNCH_CHECK();
   }
   search_seal_kernel<<<dim3(1), dim3(1), 0, s>>>(b.ctr, h.cap);
@@ -1009,8 +1305,12 @@ void launch_search_rank(const SearchIndex& ix, const SearchBatch& b, u32 queries
                         u32 k, SearchHits& h, SortPlan* h_plan, hipStream_t s) {
   LOCUST_CHECK_ARG(hits <= h.cap, "search: " + std::to_string(hits) +
                                       " hits exceed the workspace (" + std::to_string(h.cap) + ")");
-  LOCUST_CHECK_ARG(k >= 1 && ix.emits_per_line > 0 && (u64)ix.emits_per_line <= kRankMaxEmits,
-                   "search: a ranked batch takes K >= 1 and emits_per_line <= kRankMaxEmits");
+  // (pattern terms' lists may overlap: a token may count for each of a query's eight terms)
+  const u32 per_token = b.pat ? 32u * kSearchMaxTerms : 32u;
+  LOCUST_CHECK_ARG(k >= 1 && ix.emits_per_line > 0 &&
+                       (u64)ix.emits_per_line * per_token <= (u64)kRankScoreMax,
+                   "search: a ranked batch takes K >= 1 and emits_per_line <= kRankMaxEmits (a "
+                   "batch with a pattern term: an eighth of it)");
   // the segments of the sorted keys, and where each query's first min(hits, K) go
   search_scan_kernel<<<dim3(1), dim3(kSearchBlock), 0, s>>>(b.q_hits, queries, ~0u, b.offsets,
                                                             nullptr);
@@ -1023,7 +1323,7 @@ void launch_search_rank(const SearchIndex& ix, const SearchBatch& b, u32 queries
   const u32 sblocks = (u32)std::min<u64>(div_up(hits, (u64)kSearchTile), (u64)kSearchMaxBlocks);
   search_score_kernel<<<dim3(sblocks), dim3(kSearchBlock), 0, s>>>(
       ix.postings, b.merged, ix.val, ix.n, ix.first_line, b.q_info, b.t_val, b.t_len, queries,
-      32u * (u32)ix.emits_per_line, h.pairs, hits, h.cands, b.ctr);
+      per_token * (u32)ix.emits_per_line, h.pairs, hits, h.cands, b.ctr);
   LOCUST_HIP_LAUNCH_CHECK();
   ConstKeysSoA keys;
   KeysSoA sorted;

@@ -98,7 +98,8 @@ struct PyIndexResult {
   PySearchResult search(const std::vector<std::vector<std::string>>& queries,
                         const std::vector<int>& any, const py::object& rank, bool wildcard,
                         const std::vector<u64>& within,
-                        const std::vector<std::vector<std::string>>& exclude) const;
+                        const std::vector<std::vector<std::string>>& exclude, bool glob,
+                        bool ignore_case) const;
   py::list entries() const { return PyResult{x.words}.entries(); }
   py::list postings() const {
     py::list out;
@@ -201,11 +202,12 @@ struct PySearchResult {
 // value `any` (any.size() == queries.size()).  wildcard: make_search_query's rule for a
 // trailing `*`.  within: empty, or one window per query (0: none; check_search_queries holds
 // it against the mode).  exclude: empty, or one list of exclusion terms per query (an empty
-// list: none).
+// list: none).  glob: make_search_query's rule for `*` and `?` anywhere in a term.
 std::vector<SearchQuery> to_queries(const std::vector<std::vector<std::string>>& queries,
                                     const std::vector<int>& any, bool wildcard,
                                     const std::vector<u64>& within,
-                                    const std::vector<std::vector<std::string>>& exclude) {
+                                    const std::vector<std::vector<std::string>>& exclude,
+                                    bool glob) {
   LOCUST_CHECK_ARG(any.size() == queries.size(), "search: one mode per query");
   LOCUST_CHECK_ARG(within.empty() || within.size() == queries.size(),
                    "search: one window (within) per query, or none");
@@ -219,7 +221,7 @@ std::vector<SearchQuery> to_queries(const std::vector<std::vector<std::string>>&
                                : any[i] == 3 ? SearchMode::kNear
                                              : SearchMode::kAny,
                                wildcard, within.empty() ? 0 : within[i],
-                               exclude.empty() ? std::vector<std::string>() : exclude[i]);
+                               exclude.empty() ? std::vector<std::string>() : exclude[i], glob);
   return out;
 }
 
@@ -240,11 +242,12 @@ u64 to_rank(const py::object& rank) {
 PySearchResult PyIndexResult::search(const std::vector<std::vector<std::string>>& queries,
                                      const std::vector<int>& any, const py::object& rank,
                                      bool wildcard, const std::vector<u64>& within,
-                                     const std::vector<std::vector<std::string>>& exclude) const {
-  const std::vector<SearchQuery> q = to_queries(queries, any, wildcard, within, exclude);
+                                     const std::vector<std::vector<std::string>>& exclude, bool glob,
+                        bool ignore_case) const {
+  const std::vector<SearchQuery> q = to_queries(queries, any, wildcard, within, exclude, glob);
   const u64 k = to_rank(rank);
   py::gil_scoped_release nogil;
-  return PySearchResult{search_index(x, q, cfg, k)};
+  return PySearchResult{search_index(x, q, cfg, k, ignore_case)};
 }
 
 TextInput as_input(const std::string& text, u64 first_line = 0) {
@@ -380,31 +383,34 @@ class PyGpuEngine {
                             const std::vector<int>& any, u64 first_line,
                             const py::object& rank, bool wildcard,
                             const std::vector<u64>& within,
-                            const std::vector<std::vector<std::string>>& exclude) {
-    const std::vector<SearchQuery> q = to_queries(queries, any, wildcard, within, exclude);
+                            const std::vector<std::vector<std::string>>& exclude, bool glob,
+                        bool ignore_case) {
+    const std::vector<SearchQuery> q = to_queries(queries, any, wildcard, within, exclude, glob);
     const u64 k = to_rank(rank);
     py::gil_scoped_release nogil;
-    return PySearchResult{eng_.run_search(as_input(text, first_line), q, k)};
+    return PySearchResult{eng_.run_search(as_input(text, first_line), q, k, ignore_case)};
   }
   PySearchResult run_search_text(const HostText& t,
                                  const std::vector<std::vector<std::string>>& queries,
                                  const std::vector<int>& any, u64 first_line,
                                  const py::object& rank, bool wildcard,
                             const std::vector<u64>& within,
-                            const std::vector<std::vector<std::string>>& exclude) {
-    const std::vector<SearchQuery> q = to_queries(queries, any, wildcard, within, exclude);
+                            const std::vector<std::vector<std::string>>& exclude, bool glob,
+                        bool ignore_case) {
+    const std::vector<SearchQuery> q = to_queries(queries, any, wildcard, within, exclude, glob);
     const u64 k = to_rank(rank);
     py::gil_scoped_release nogil;
-    return PySearchResult{eng_.run_search(t.input(first_line), q, k)};
+    return PySearchResult{eng_.run_search(t.input(first_line), q, k, ignore_case)};
   }
   PySearchResult search_resident(const std::vector<std::vector<std::string>>& queries,
                                  const std::vector<int>& any, const py::object& rank,
                                  bool wildcard, const std::vector<u64>& within,
-                                 const std::vector<std::vector<std::string>>& exclude) {
-    const std::vector<SearchQuery> q = to_queries(queries, any, wildcard, within, exclude);
+                                 const std::vector<std::vector<std::string>>& exclude, bool glob,
+                        bool ignore_case) {
+    const std::vector<SearchQuery> q = to_queries(queries, any, wildcard, within, exclude, glob);
     const u64 k = to_rank(rank);
     py::gil_scoped_release nogil;
-    return PySearchResult{eng_.search_resident(q, k)};
+    return PySearchResult{eng_.search_resident(q, k, ignore_case)};
   }
   // records: (key bytes, count), sorted by key with distinct keys -- the kernels alone.
   PyTopResult top_counts(const std::vector<std::pair<std::string, u64>>& records, u32 k) {
@@ -873,6 +879,7 @@ PYBIND11_MODULE(_locust, m) {
            py::arg("rank") = py::none(), py::arg("wildcard") = false,
            py::arg("within") = std::vector<u64>(),
            py::arg("exclude") = std::vector<std::vector<std::string>>(),
+           py::arg("glob") = false, py::arg("ignore_case") = false,
            "The host evaluation of all/any queries (any[i]: query i's mode) over this index.")
       .def("times", &PyIndexResult::times)
       .def("format", &PyIndexResult::format)
@@ -957,15 +964,18 @@ PYBIND11_MODULE(_locust, m) {
            py::arg("any"), py::arg("first_line") = 0, py::arg("rank") = py::none(),
            py::arg("wildcard") = false, py::arg("within") = std::vector<u64>(),
            py::arg("exclude") = std::vector<std::vector<std::string>>(),
+           py::arg("glob") = false, py::arg("ignore_case") = false,
            "WordCount of text, its index, and all/any queries answered on the device.")
       .def("run_search_text", &PyGpuEngine::run_search_text, py::arg("text"), py::arg("queries"),
            py::arg("any"), py::arg("first_line") = 0, py::arg("rank") = py::none(),
            py::arg("wildcard") = false, py::arg("within") = std::vector<u64>(),
-           py::arg("exclude") = std::vector<std::vector<std::string>>())
+           py::arg("exclude") = std::vector<std::vector<std::string>>(),
+           py::arg("glob") = false, py::arg("ignore_case") = false)
       .def("search_resident", &PyGpuEngine::search_resident, py::arg("queries"), py::arg("any"),
            py::arg("rank") = py::none(), py::arg("wildcard") = false,
            py::arg("within") = std::vector<u64>(),
            py::arg("exclude") = std::vector<std::vector<std::string>>(),
+           py::arg("glob") = false, py::arg("ignore_case") = false,
            "Another batch from the index the last run_index / run_search left on the device.")
       .def("top_counts", &PyGpuEngine::top_counts, py::arg("records"), py::arg("k"),
            "The selection kernels alone over key-sorted (key, count) records.")
@@ -988,15 +998,17 @@ PYBIND11_MODULE(_locust, m) {
                              const std::vector<int>& any, u64 first_line,
                              const py::object& rank, bool wildcard,
                              const std::vector<u64>& within,
-                             const std::vector<std::vector<std::string>>& exclude) {
+                             const std::vector<std::vector<std::string>>& exclude, bool glob,
+                        bool ignore_case) {
     CpuWordCount eng(cfg);
     return PySearchResult{eng.run_search(as_input(text, first_line),
-                                         to_queries(queries, any, wildcard, within, exclude),
-                                         to_rank(rank))};
+                                         to_queries(queries, any, wildcard, within, exclude, glob),
+                                         to_rank(rank), ignore_case)};
   }, py::arg("cfg"), py::arg("text"), py::arg("queries"), py::arg("any"),
         py::arg("first_line") = 0, py::arg("rank") = py::none(), py::arg("wildcard") = false,
         py::arg("within") = std::vector<u64>(),
-           py::arg("exclude") = std::vector<std::vector<std::string>>());
+           py::arg("exclude") = std::vector<std::vector<std::string>>(),
+           py::arg("glob") = false, py::arg("ignore_case") = false);
   m.def("check_search_merge", &check_search_merge, py::arg("queries"), py::arg("elements"),
         "Throws when a device batch's prefix terms would merge 2^32 list elements or more.");
   m.def("cpu_map_stage", [](const JobConfig& cfg, const std::string& text) {

@@ -9,6 +9,8 @@ matches them exactly.
 """
 from __future__ import annotations
 
+import re
+
 from collections import Counter
 
 DEFAULT_DELIMS = b" ,.-;:'()\"\t"
@@ -159,6 +161,105 @@ def prefix_terms(terms, wildcard: bool, delims: bytes = DEFAULT_DELIMS, max_key:
     return out
 
 
+PATTERN_RULES = """
+    Pattern terms (``glob=True``) and ``ignore_case=True``.
+
+    - With ``glob``, runs of ``*`` in a term collapse to one ``*`` first.  A term without ``*``
+      or ``?`` is then a plain term; ``p*`` with ``p`` non-empty and free of metacharacters is
+      the prefix term of ``wildcard`` (its cut rule included: ``glob`` is a superset of
+      ``wildcard``, and both together are ``glob``); anything else that holds a ``*`` or ``?``
+      is a pattern term.  There is no escape character.
+    - A pattern's bytes other than ``*`` and ``?`` are validated as a term's are.  Refused
+      (``ValueError``): a pattern longer than ``max_key`` bytes after the collapse (a pattern
+      is never cut), and one with no byte other than ``*``.  ``???`` is legal.
+    - A pattern term's words are the index keys (cut to ``max_key`` as the index holds them)
+      that the whole pattern matches: ``*`` any run of bytes, the empty run included; ``?``
+      exactly one byte; every other byte itself.  Its list is the multiset union of its words'
+      postings, its count the sum of their counts; without a word it is absent.  In phrase and
+      near verification a token matches when its cut key matches the pattern.
+    - ``ignore_case`` holds for all terms of a query, positive and exclusion: each is cut
+      exactly as without it and then evaluated as a pattern whose bytes A-Z and a-z match
+      either case -- plain ``hamlet`` as the pattern ``hamlet`` (a ``*`` or ``?`` in it stays
+      literal), prefix ``ham*`` as ``ham*``.  Only ASCII letters fold.
+    - Identity: two pattern terms are the same term when their collapsed pattern bytes are
+      equal (under ``ignore_case``: after lower-casing ASCII).  The later one repeats the
+      earlier one: same count, not merged again, scores once.  A pattern term is never the
+      same as a plain or prefix term, never inside another term's range, and no term is
+      inside it; the nesting rule applies to plain and prefix terms among themselves.
+    - Ranked: weight and tf as for a prefix term.  Lists of pattern terms may overlap, so a
+      score is at most 32 * emits_per_line * 8; a ranked query with a pattern term is refused
+      when emits_per_line > RANK_MAX_EMITS / 8.
+    - ``merged`` adds the count of every pattern term that covers two or more words and
+      repeats no earlier term of its query.
+
+    The matching here is independent of the engines' matcher: the pattern is translated to a
+    bytes regular expression (``re.escape``, ``*`` -> ``.*``, ``?`` -> ``.``, DOTALL,
+    ``fullmatch``), a folding letter to a two-byte class.
+"""
+
+
+class QueryTerm:
+    """One term as it is evaluated: ``kind`` is ``"plain"``, ``"prefix"`` or ``"pattern"``;
+    ``p`` the cut bytes of a plain or prefix term; ``rx`` a pattern's compiled expression and
+    ``ident`` what makes two pattern terms the same term."""
+
+    def __init__(self, kind, p=b"", rx=None, ident=None):
+        self.kind, self.p, self.rx, self.ident = kind, p, rx, ident
+
+    def fits(self, tok: bytes) -> bool:
+        if self.kind == "pattern":
+            return self.rx.fullmatch(tok) is not None
+        return tok[:len(self.p)] == self.p if self.kind == "prefix" else tok == self.p
+
+
+def _pattern_term(cells, fold: bool) -> QueryTerm:
+    """The pattern term of ``cells``: (byte, is_meta) pairs."""
+    out = []
+    for c, meta in cells:
+        if meta:
+            out.append(b".*" if c == 0x2A else b".")
+        elif fold and (0x41 <= c <= 0x5A or 0x61 <= c <= 0x7A):
+            out.append(b"[" + bytes([c & ~0x20]) + bytes([c | 0x20]) + b"]")
+        else:
+            out.append(re.escape(bytes([c])))
+    ident = tuple((c | 0x20 if fold and not meta and 0x41 <= c <= 0x5A else c, meta)
+                  for c, meta in cells)
+    return QueryTerm("pattern", rx=re.compile(b"".join(out), re.DOTALL), ident=ident)
+
+
+def query_terms(terms, wildcard: bool = False, glob: bool = False, ignore_case: bool = False,
+                delims: bytes = DEFAULT_DELIMS, max_key: int = 29):
+    """The terms of a query as ``QueryTerm`` objects, validated and cut: ``prefix_terms``'
+    sibling for ``glob`` and ``ignore_case`` (``PATTERN_RULES``)."""
+    bad = set(delims) | {0, 0x0A}
+    out = []
+    for t in terms:
+        cells = None  # a pattern term's (byte, is_meta) pairs
+        if glob:
+            t = re.sub(rb"\*+", b"*", t)
+            if t == b"*":
+                raise ValueError("a pattern of stars alone is no term")
+            metas = [i for i, c in enumerate(t) if c in b"*?"]
+            if metas and not (metas == [len(t) - 1] and t.endswith(b"*")):
+                if len(t) > max_key:
+                    raise ValueError("the pattern %r is longer than max_key" % (t,))
+                cells = [(c, c in b"*?") for c in t]
+                if any(c in bad for c, meta in cells if not meta):
+                    raise ValueError("invalid term %r" % (t,))
+        if cells is None:
+            (p, pre), = prefix_terms([t], wildcard or glob, delims, max_key)
+            if not ignore_case:
+                out.append(QueryTerm("prefix" if pre else "plain", p))
+                continue
+            cells = [(c, False) for c in p] + ([(0x2A, True)] if pre else [])
+        out.append(_pattern_term(cells, ignore_case))
+    return out
+
+
+def _qt_words(entries, term: QueryTerm):
+    return [i for i, (k, _v, _c) in enumerate(entries) if term.fits(k)]
+
+
 def _term_words(entries, p: bytes, pre: bool):
     """The indices of a term's words among ``entries``: the keys that start with ``p``
     (a word equal to ``p`` among them) for a prefix term, the key ``p`` for a plain one."""
@@ -222,26 +323,28 @@ def _check_exclude(terms, exclude):
     return exclude
 
 
-def _excluded_by_index(entries, postings, exclude, wildcard, delims, max_key):
+def _excluded_by_index(entries, postings, exclude, wildcard, delims, max_key, glob=False,
+                       ignore_case=False):
     """``(lines, counts)`` of exclusion terms over an index: the union of the terms' lines as
     a set, and every term's count (its word's, or its merged count; 0: absent)."""
     out, counts = set(), []
-    for p, pre in prefix_terms(exclude, wildcard, delims, max_key):
-        lines = _term_list(entries, postings, _term_words(entries, p, pre))
+    for term in query_terms(exclude, wildcard, glob, ignore_case, delims, max_key):
+        lines = _term_list(entries, postings, _qt_words(entries, term))
         counts.append(len(lines))
         out.update(lines)
     return out, counts
 
 
-def _excluded_by_text(text, exclude, wildcard, delims, emits, max_key, first_line):
+def _excluded_by_text(text, exclude, wildcard, delims, emits, max_key, first_line, glob=False,
+                      ignore_case=False):
     """The same from the text: a line is excluded when one of its emitted tokens (the index
     holds no other) matches an exclusion term; a term's count is its matching tokens."""
-    want = prefix_terms(exclude, wildcard, delims, max_key)
+    want = query_terms(exclude, wildcard, glob, ignore_case, delims, max_key)
     out, counts = set(), [0] * len(want)
     for i, line in enumerate(split_lines(text)):
         toks, _dropped = tokenize(line, delims, emits, max_key)
-        for j, (p, pre) in enumerate(want):
-            n = sum((tok[:len(p)] == p) if pre else (tok == p) for tok in toks)
+        for j, term in enumerate(want):
+            n = sum(term.fits(tok) for tok in toks)
             counts[j] += n
             if n:
                 out.add(first_line + i)
@@ -249,14 +352,20 @@ def _excluded_by_text(text, exclude, wildcard, delims, emits, max_key, first_lin
 
 
 def merged_elements(entries, queries, delims: bytes = DEFAULT_DELIMS, max_key: int = 29, *,
-                    exclude=None) -> int:
+                    exclude=None, glob: bool = False, ignore_case: bool = False,
+                    wildcard: bool = True) -> int:
     """``SearchResult.merged`` of a device batch of wildcard ``queries`` (term lists): over
     the batch's prefix terms that cover two or more words, a term whose words repeat an
     earlier term's of its query left out, the sum of their counts.  (A term that covers one
     word uses that word's list in place: nothing is merged.)
 
     ``exclude``: one entry per query, ``None`` or its exclusion terms, which stand behind the
-    query's own terms (``EXCLUDE_RULES``: the rule runs over all of the query's terms)."""
+    query's own terms (``EXCLUDE_RULES``: the rule runs over all of the query's terms).
+
+    ``glob`` / ``ignore_case`` (``PATTERN_RULES``): a pattern term that covers two or more
+    words and repeats no earlier pattern term of its query adds its count.  ``wildcard=False``
+    with them: the batch was asked without wildcards (a trailing ``*`` is literal unless
+    ``glob`` reads it)."""
     total = 0
     if exclude is not None:
         if len(exclude) != len(queries):
@@ -264,16 +373,19 @@ def merged_elements(entries, queries, delims: bytes = DEFAULT_DELIMS, max_key: i
         queries = [list(q) + _check_exclude(list(q), x) for q, x in zip(queries, exclude)]
     for terms in queries:
         seen = []
-        for p, pre in prefix_terms(terms, True, delims, max_key):
-            words = _term_words(entries, p, pre)
-            if len(words) >= 2 and words not in seen:
+        for term in query_terms(terms, wildcard, glob, ignore_case, delims, max_key):
+            words = _qt_words(entries, term)
+            # what a later term must repeat: a pattern term's pattern, another term's words
+            same = term.ident if term.kind == "pattern" else words
+            if len(words) >= 2 and same not in seen:
                 total += sum(entries[i][2] for i in words)
-            seen.append(words)
+            seen.append(same)
     return total
 
 
 def search(entries, postings, terms, mode: str = "all", delims: bytes = DEFAULT_DELIMS,
-           max_key: int = 29, *, wildcard: bool = False, exclude=None):
+           max_key: int = 29, *, wildcard: bool = False, exclude=None, glob: bool = False,
+           ignore_case: bool = False):
     """One all/any word query over an index: ``(lines, counts)``.
 
     ``entries`` and ``postings`` are ``index``'s output.  A query is 1 to 8 ``terms`` and a
@@ -301,16 +413,16 @@ def search(entries, postings, terms, mode: str = "all", delims: bytes = DEFAULT_
     if exclude is not None:
         exclude = _check_exclude(terms, exclude)
         lines, counts = search(entries, postings, terms, mode, delims, max_key,
-                               wildcard=wildcard)
+                               wildcard=wildcard, glob=glob, ignore_case=ignore_case)
         gone, xcounts = _excluded_by_index(entries, postings, exclude, wildcard, delims,
-                                           max_key)
+                                           max_key, glob, ignore_case)
         return [l for l in lines if l not in gone], counts + xcounts
     if not 1 <= len(terms) <= MAX_SEARCH_TERMS:
         raise ValueError("a query takes 1 to %d terms" % MAX_SEARCH_TERMS)
-    if wildcard:
+    if wildcard or glob or ignore_case:  # (``glob`` / ``ignore_case``: PATTERN_RULES)
         sets, counts = [], []
-        for p, pre in prefix_terms(terms, True, delims, max_key):
-            lines = _term_list(entries, postings, _term_words(entries, p, pre))
+        for term in query_terms(terms, wildcard, glob, ignore_case, delims, max_key):
+            lines = _term_list(entries, postings, _qt_words(entries, term))
             counts.append(len(lines))
             sets.append(set(lines))
         hit = set.intersection(*sets) if mode == "all" else set.union(*sets)
@@ -330,7 +442,8 @@ def search(entries, postings, terms, mode: str = "all", delims: bytes = DEFAULT_
 
 
 def phrase(text: bytes, terms, delims: bytes = DEFAULT_DELIMS, emits: int = 20,
-           max_key: int = 29, first_line: int = 0, *, wildcard: bool = False, exclude=None):
+           max_key: int = 29, first_line: int = 0, *, wildcard: bool = False, exclude=None,
+           glob: bool = False, ignore_case: bool = False):
     """One phrase query over ``text``: ``(lines, counts)``, as ``search`` answers.
 
     `phrase` answers the lines on which the terms occur as consecutive tokens, in order.
@@ -361,19 +474,18 @@ def phrase(text: bytes, terms, delims: bytes = DEFAULT_DELIMS, emits: int = 20,
     if exclude is not None:
         exclude = _check_exclude(terms, exclude)
         lines, counts = phrase(text, terms, delims, emits, max_key, first_line,
-                               wildcard=wildcard)
+                               wildcard=wildcard, glob=glob, ignore_case=ignore_case)
         gone, xcounts = _excluded_by_text(text, exclude, wildcard, delims, emits, max_key,
-                                          first_line)
+                                          first_line, glob, ignore_case)
         return [l for l in lines if l not in gone], counts + xcounts
     if not 1 <= len(terms) <= MAX_SEARCH_TERMS:
         raise ValueError("a query takes 1 to %d terms" % MAX_SEARCH_TERMS)
-    if wildcard:
-        want = prefix_terms(terms, True, delims, max_key)
+    if wildcard or glob or ignore_case:  # (``glob`` / ``ignore_case``: PATTERN_RULES)
+        want = query_terms(terms, wildcard, glob, ignore_case, delims, max_key)
         m = len(want)
 
         def fits(tok, term):
-            p, pre = term
-            return tok[:len(p)] == p if pre else tok == p
+            return term.fits(tok)
 
         lines = []
         counts = [0] * m
@@ -406,7 +518,8 @@ MAX_SEARCH_WITHIN = (1 << 32) - 1
 
 
 def near(text: bytes, terms, within: int, delims: bytes = DEFAULT_DELIMS, emits: int = 20,
-         max_key: int = 29, first_line: int = 0, *, wildcard: bool = False, exclude=None):
+         max_key: int = 29, first_line: int = 0, *, wildcard: bool = False, exclude=None,
+         glob: bool = False, ignore_case: bool = False):
     """One proximity query over ``text``: ``(lines, counts)``, as ``search`` answers.
 
     `near` answers the lines on which the terms occur within ``within`` = W tokens of one
@@ -434,20 +547,20 @@ def near(text: bytes, terms, within: int, delims: bytes = DEFAULT_DELIMS, emits:
     if exclude is not None:
         exclude = _check_exclude(terms, exclude)
         lines, counts = near(text, terms, within, delims, emits, max_key, first_line,
-                             wildcard=wildcard)
+                             wildcard=wildcard, glob=glob, ignore_case=ignore_case)
         gone, xcounts = _excluded_by_text(text, exclude, wildcard, delims, emits, max_key,
-                                          first_line)
+                                          first_line, glob, ignore_case)
         return [l for l in lines if l not in gone], counts + xcounts
     if not 1 <= len(terms) <= MAX_SEARCH_TERMS:
         raise ValueError("a query takes 1 to %d terms" % MAX_SEARCH_TERMS)
     if isinstance(within, bool) or not isinstance(within, int) or \
             not 1 <= within <= MAX_SEARCH_WITHIN:
         raise ValueError("a near query takes a window 1 <= W < 2^32, not %r" % (within,))
-    want = prefix_terms(terms, wildcard, delims, max_key)
+    # (``glob`` / ``ignore_case``: PATTERN_RULES)
+    want = query_terms(terms, wildcard, glob, ignore_case, delims, max_key)
 
     def fits(tok, term):
-        p, pre = term
-        return tok[:len(p)] == p if pre else tok == p
+        return term.fits(tok)
 
     lines = []
     counts = [0] * len(want)
@@ -493,7 +606,8 @@ RANK_MAX_EMITS = 65536
 
 
 def rank(entries, postings, lines, terms, k: int, max_key: int = 29, *,
-         wildcard: bool = False, delims: bytes = DEFAULT_DELIMS, exclude=None):
+         wildcard: bool = False, delims: bytes = DEFAULT_DELIMS, exclude=None,
+         glob: bool = False, ignore_case: bool = False, emits=None):
     """The ranked answer of one query: ``(top, matches)``.
 
     ``lines`` is the query's matching set, as ``search`` or ``phrase`` answered it; ranking
@@ -517,25 +631,41 @@ def rank(entries, postings, lines, terms, k: int, max_key: int = 29, *,
     ``exclude``: the query's exclusion terms (``EXCLUDE_RULES``).  The matching set is
     ``lines`` minus the excluded lines (``lines`` may be the answer before or after the
     exclusion) and ``matches`` counts it; the exclusion terms take no part in the score, in
-    the distinct present terms or in the nesting rule."""
+    the distinct present terms or in the nesting rule.
+
+    ``glob`` / ``ignore_case`` (``PATTERN_RULES``): a pattern term scores as a prefix term
+    does, once per distinct pattern, outside the nesting rule.  ``emits`` (the job's
+    emits_per_line), when given, is held against the limit of a ranked search: RANK_MAX_EMITS,
+    or an eighth of it for a query with a pattern term (``ValueError``)."""
     if k < 1:
         raise ValueError("rank takes k >= 1")
+    if emits is not None:
+        pat = any(t.kind == "pattern" for t in query_terms(
+            list(terms) + list(exclude or []), wildcard, glob, ignore_case, delims, max_key))
+        if emits > (RANK_MAX_EMITS // MAX_SEARCH_TERMS if pat else RANK_MAX_EMITS):
+            raise ValueError("a ranked search takes emits_per_line <= %d"
+                             % (RANK_MAX_EMITS // MAX_SEARCH_TERMS if pat else RANK_MAX_EMITS))
     if exclude is not None:
         exclude = _check_exclude(list(terms), exclude)
         gone, _counts = _excluded_by_index(entries, postings, exclude, wildcard, delims,
-                                           max_key)
+                                           max_key, glob, ignore_case)
         return rank(entries, postings, [l for l in lines if l not in gone], terms, k,
-                    max_key, wildcard=wildcard, delims=delims)
-    if wildcard:
+                    max_key, wildcard=wildcard, delims=delims, glob=glob,
+                    ignore_case=ignore_case)
+    if wildcard or glob or ignore_case:
         n = len(postings)
-        ranges = [set(_term_words(entries, p, pre))
-                  for p, pre in prefix_terms(terms, True, delims, max_key)]
+        want = query_terms(terms, wildcard, glob, ignore_case, delims, max_key)
+        ranges = [set(_qt_words(entries, t)) for t in want]
         lists = []
         for j, rj in enumerate(ranges):
             if not rj:  # absent
                 continue
-            if any(ri and i != j and rj <= ri and (rj != ri or i < j)
-                   for i, ri in enumerate(ranges)):
+            if want[j].kind == "pattern":  # once per distinct pattern; no nesting rule
+                if any(want[i].kind == "pattern" and want[i].ident == want[j].ident
+                       for i in range(j)):
+                    continue
+            elif any(ri and i != j and want[i].kind != "pattern" and rj <= ri and
+                     (rj != ri or i < j) for i, ri in enumerate(ranges)):
                 continue
             merged = _term_list(entries, postings, sorted(rj))
             tf = {}

@@ -27,6 +27,8 @@
 //   --wildcard (with --search: a word that ends in * is a prefix term, "ham*")
 //   --glob (with --search: * and ? anywhere in a word, "*ing", "h?mlet"; a superset of --wildcard)
 //   --ignore-case (with --search: the ASCII letters of every word match either case)
+//   --show N (with --search: under each query's line, every returned line's first N bytes)
+//   --mark (with --show: the matching tokens of a shown line stand between >> and <<)
 // and a synthetic-text generator (BASELINE configs "1M lines" / "10 GB"):
 //   MapReduce --gen FILE (--gen-lines N | --gen-bytes N) [--seed S] [--vocab V]
 #include <sys/stat.h>
@@ -104,6 +106,8 @@ struct CliArgs {
   bool wildcard = false;  // --wildcard: a --search word that ends in * is a prefix term
   bool glob = false;      // --glob: * and ? anywhere in a --search word (pattern terms)
   bool ignore_case = false;  // --ignore-case: the batch's ASCII letters match either case
+  u64 show = 0;       // --show N: the returned lines' first N bytes (0: line numbers only)
+  bool mark = false;  // --mark: the shown lines' matching tokens between >> and <<
   std::string gen_out;  // generator mode
   GenSpec gen;
 };
@@ -179,6 +183,14 @@ void help() {
       "                             is one of stars alone.  With every --match, --rank, --not,\n"
       "                             --within and --backend cpu; --rank then takes\n"
       "                             --emits-per-line <= 8192)\n"
+      "  --show N                   (--search: under each query's result line, one line per\n"
+      "                             returned line: two spaces, its number, \": \" and its first N\n"
+      "                             bytes, 1 <= N <= 65536; the lines are gathered on the device.\n"
+      "                             With every --match, --rank (the winners, in rank order),\n"
+      "                             --not, --wildcard, --glob and --ignore-case)\n"
+      "  --mark                     (--show: every token of a shown line that matches one of the\n"
+      "                             query's words -- not its --not words -- stands between >>\n"
+      "                             and <<, as far as it lies inside the N bytes)\n"
       "  --ignore-case              (--search: the ASCII letters of every word of every query,\n"
       "                             --not words too, match either case: \"to be\" finds \"To be\".\n"
       "                             Other bytes match only themselves.  With --glob, --wildcard and\n"
@@ -331,6 +343,16 @@ bool parse(int argc, char** argv, CliArgs* a) {
       a->glob = true;
     } else if (s == "--ignore-case") {
       a->ignore_case = true;
+    } else if (s == "--show") {
+      const std::string v = need("--show");
+      char* endp = nullptr;
+      const long long n = std::strtoll(v.c_str(), &endp, 10);
+      if (v.empty() || *endp || n < 1 || n > (long long)kShowMaxBytes)
+        throw Error("--show N (the first N bytes of every line a --search query returns) needs "
+                    "an integer N with 1 <= N <= " + std::to_string(kShowMaxBytes));
+      a->show = (u64)n;
+    } else if (s == "--mark") {
+      a->mark = true;
     } else if (s == "--rank") {
       const std::string v = need("--rank");
       char* endp = nullptr;
@@ -409,6 +431,10 @@ bool parse(int argc, char** argv, CliArgs* a) {
     throw Error("--glob selects how --search reads * and ? in a word: give --search too");
   if (a->ignore_case && a->search_args.empty())
     throw Error("--ignore-case selects how --search compares letters: give --search too");
+  if (a->show && a->search_args.empty())
+    throw Error("--show N prints the lines a --search query returns: give --search too");
+  if (a->mark && !a->show)
+    throw Error("--mark marks the matching tokens of the lines --show prints: give --show too");
   if (a->index && !a->search_args.empty())
     throw Error("--index and --search do not combine: --index prints the whole index, "
                 "--search the lines of its queries");
@@ -630,6 +656,10 @@ void json_search(JsonOut& j, const CliArgs& a) {
     j.u("matches", matches);
     j.num("index_ms", g_search->index_ms);
     j.num("search_ms", g_search->search_ms);
+    j.u("show_bytes", g_search->show_bytes);
+    j.num("show_ms", g_search->show_ms);
+    j.u("cut_lines", g_search->cut_lines);
+    j.u("spans", g_search->spans.size() / 3);
     j.u("wire_bytes", g_search->wire_bytes);
   }
 }
@@ -861,7 +891,7 @@ void print_gpu_result(const CliArgs& a, const WordCountResult& r, const std::vec
                     (unsigned long long)r.truncated, a.cfg.max_key_len);
   std::string out;
   if (srch) {
-    if (!a.quiet) format_search_output(*srch, &out);
+    if (!a.quiet) format_search_output(*srch, &out, a.mark);
   } else if (idx) {
     if (!a.quiet) format_index_output(*idx, &out);
   } else if (top) {
@@ -1205,7 +1235,7 @@ int run(const CliArgs& a) {
     for (int i = 0; i < a.warmup; ++i) eng.run(text.input);
     for (int i = 0; i < a.iters; ++i) {
       if (!a.queries.empty()) {
-        cpu_search = eng.run_search(text.input, a.queries, a.rank, a.ignore_case);
+        cpu_search = eng.run_search(text.input, a.queries, a.rank, a.ignore_case, a.show);
         r = search_stats(cpu_search);
       } else if (a.index) {
         cpu_index = eng.run_index(text.input);
@@ -1226,7 +1256,7 @@ int run(const CliArgs& a) {
     if (!a.queries.empty()) {  // the word job, the index stage and the search stage
       SearchResult sr;
       for (int i = 0; i < a.warmup + a.iters; ++i) {
-        sr = eng.run_search(text.input, a.queries, a.rank, a.ignore_case);
+        sr = eng.run_search(text.input, a.queries, a.rank, a.ignore_case, a.show);
         if (i >= a.warmup) walls.push_back(sr.times.wall_ms);
       }
       print_gpu_result(a, search_stats(sr), walls, nullptr, nullptr, &sr);
@@ -1263,7 +1293,7 @@ int run(const CliArgs& a) {
                     (unsigned long long)r.truncated, a.cfg.max_key_len);
   std::string out;
   if (!a.queries.empty()) {
-    if (!a.quiet) format_search_output(cpu_search, &out);
+    if (!a.quiet) format_search_output(cpu_search, &out, a.mark);
     g_search = &cpu_search;
   } else if (a.index) {
     if (!a.quiet) format_index_output(cpu_index, &out);

@@ -168,7 +168,7 @@ void check_ngram(const JobConfig& cfg) {
 }
 
 int tokenize_line(const char* line, u64 len, const JobConfig& cfg, std::vector<PackedKey>* out,
-                  u64* truncated) {
+                  u64* truncated, std::vector<std::pair<u32, u32>>* at) {
   // The reference works on a NUL-terminated copy (main.cu:55-59); text after an embedded
   // NUL is invisible to strtok_r, exactly as here.
   std::string buf(line, len);
@@ -207,6 +207,7 @@ int tokenize_line(const char* line, u64 len, const JobConfig& cfg, std::vector<P
       break;
     }
     int n = d_strlen(tok);
+    if (at) at->emplace_back((u32)(tok - buf.data()), (u32)n);
     if (n > cfg.max_key_len) {
       if (truncated) ++*truncated;
       n = cfg.max_key_len;
@@ -555,6 +556,16 @@ void check_search_rank(u64 rank_k, const JobConfig& cfg, bool patterns) {
                        std::to_string(cfg.emits_per_line));
 }
 
+void check_search_show(u64 show, u64 text_bytes) {
+  if (show == 0) return;
+  LOCUST_CHECK_ARG(show <= kShowMaxBytes,
+                   "search: show takes 1 <= N <= " + std::to_string(kShowMaxBytes) +
+                       " bytes per line, not " + std::to_string(show));
+  LOCUST_CHECK_ARG(text_bytes < (1ull << 32),
+                   "search: show takes a text window of less than 2^32 bytes (a span's start is "
+                   "a u32), not " + std::to_string(text_bytes) + ": search a line window");
+}
+
 namespace {
 
 // The positive terms a line's tokens are matched against.  masks: empty, or per key and word
@@ -621,12 +632,82 @@ bool line_has_near(const char* line, u64 len, const TokenTerms& keys, u64 within
   return false;
 }
 
+// The positive terms of q as a line's tokens are matched against them.
+TokenTerms positive_terms(const SearchQuery& q, const JobConfig& cfg, bool patterns,
+                          bool ignore_case) {
+  TokenTerms keys;
+  keys.fold = ignore_case;
+  bool wild = false;
+  const size_t npos = q.positives();
+  for (size_t t = 0; t < npos; ++t) wild |= search_term_prefix(q, t, cfg);
+  for (size_t t = 0; t < npos; ++t) {
+    keys.keys.push_back(search_term_key(q.terms[t], cfg));
+    if (patterns) {
+      SearchPattern sp;
+      keys.is_pat.push_back(search_term_pattern(q, t, cfg, ignore_case, &sp) ? 1 : 0);
+      keys.pats.push_back(sp);
+    }
+    if (!wild) continue;
+    PackedKey m;
+    for (int j = 0; j < kKeyWords; ++j)
+      m.w[j] = search_term_prefix(q, t, cfg) ? key_word_mask(keys.keys.back().w[j]) : ~0ull;
+    keys.masks.push_back(m);
+  }
+  return keys;
+}
+
+// engine.hpp "show": the shown bytes and the spans of every entry of r, from the text.
+void show_lines(const TextInput& text, const std::vector<u64>& line_at, const JobConfig& cfg,
+                bool patterns, u32 show, SearchResult* r) {
+  const u64 t0 = now_ns();
+  r->show_bytes = show;
+  r->text_off.assign(1, 0);
+  r->span_off.assign(1, 0);
+  std::vector<PackedKey> toks;
+  std::vector<std::pair<u32, u32>> at;
+  for (size_t qi = 0; qi < r->queries.size(); ++qi) {
+    const TokenTerms keys = positive_terms(r->queries[qi], cfg, patterns, r->ignore_case);
+    for (u64 e = r->offsets[qi]; e < r->offsets[qi + 1]; ++e) {
+      const u64 l = r->lines[e] - r->first_line;
+      LOCUST_CHECK_ARG(l + 1 < line_at.size(),
+                       "search: the text has fewer lines than the index names");
+      const char* p = text.data + line_at[l];
+      u64 len = line_at[l + 1] - 1 - line_at[l];
+      toks.clear();
+      at.clear();
+      tokenize_line(p, len, cfg, &toks, nullptr, &at);
+      // (the text ends where the tokeniser stops: at a NUL, too)
+      if (const void* nul = memchr(p, 0, (size_t)len))
+        len = (u64)(static_cast<const char*>(nul) - p);
+      r->cut_lines += len > show ? 1 : 0;
+      r->text.append(p, (size_t)std::min<u64>(len, show));
+      r->text_off.push_back(r->text.size());
+      for (size_t o = 0; o < toks.size(); ++o) {
+        u32 mask = 0;
+        for (size_t j = 0; j < keys.size(); ++j) mask |= (u32)token_matches(toks[o], j, keys) << j;
+        if (!mask) continue;
+        r->spans.push_back(at[o].first);
+        r->spans.push_back(at[o].second);
+        r->spans.push_back(mask);
+      }
+      r->span_off.push_back(r->spans.size() / 3);
+    }
+  }
+  r->show_ms = (now_ns() - t0) * 1e-6;
+  r->times.wall_ms += r->show_ms;
+}
+
 SearchResult search_index_impl(const IndexResult& x, const TextInput* text,
                                const std::vector<SearchQuery>& queries, const JobConfig& cfg,
-                               u64 rank_k, bool ignore_case) {
+                               u64 rank_k, bool ignore_case, u64 show) {
   check_search_queries(queries, cfg);
   const bool patterns = search_has_patterns(queries, ignore_case);
   check_search_rank(rank_k, cfg, patterns);
+  LOCUST_CHECK_ARG(show == 0 || text,
+                   "search: show needs the text (the index holds no bytes): use "
+                   "search_index(index, text, queries, cfg, ...), the four-argument overload, or "
+                   "run_search on an engine");
+  check_search_show(show, text ? text->bytes : 0);
   bool verify = false;  // a phrase, or a near query, of two or more positive terms
   for (const SearchQuery& q : queries)
     verify |= (q.mode == SearchMode::kPhrase || q.mode == SearchMode::kNear) &&
@@ -642,9 +723,10 @@ SearchResult search_index_impl(const IndexResult& x, const TextInput* text,
                        "run_search on an engine");
     }
   std::vector<u64> line_at;  // the text's line starts, and its size behind them
-  if (verify) {
+  if (verify || show) {
     LOCUST_CHECK_ARG(cfg.ngram == 1,
-                     "search: a phrase or near query is verified with word keys (ngram 1)");
+                     "search: a phrase or near query is verified, and a line shown, with word "
+                     "keys (ngram 1)");
     LOCUST_CHECK_ARG(text->first_line == x.first_line && !text->source,
                      "search: the text is not the window the index was built from");
     for (u64 p = 0; p < text->bytes;) {
@@ -694,7 +776,7 @@ SearchResult search_index_impl(const IndexResult& x, const TextInput* text,
     std::vector<List> not_lists;  // the present exclusion terms of distinct key ranges
     std::vector<std::vector<u32>> own;  // the merged lists of this query's prefix terms
     const size_t npos = q.positives();
-    bool absent = false, wild = false;
+    bool absent = false;
     for (size_t t = 0; t < q.terms.size(); ++t) {
       const bool pos = t < npos;
       SearchPattern sp;
@@ -741,7 +823,6 @@ SearchResult search_index_impl(const IndexResult& x, const TextInput* text,
       const size_t lo = (size_t)(std::lower_bound(ent, ent + n, k, less) - ent);
       size_t hi = lo;
       if (search_term_prefix(q, t, cfg)) {  // the keys from p padded with 0x00 to p with 0xff
-        wild |= pos;
         PackedKey top;
         for (int j = 0; j < kKeyWords; ++j) top.w[j] = k.w[j] | ~key_word_mask(k.w[j]);
         hi = (size_t)(std::upper_bound(ent, ent + n, top,
@@ -791,21 +872,8 @@ SearchResult search_index_impl(const IndexResult& x, const TextInput* text,
                         q.within < (u64)cfg.emits_per_line;
       TokenTerms keys;
       std::vector<PackedKey> toks;
-      keys.fold = ignore_case;
       if (phrase || near)  // the positive terms only
-        for (size_t t = 0; t < npos; ++t) {
-          keys.keys.push_back(search_term_key(q.terms[t], cfg));
-          if (patterns) {
-            SearchPattern sp;
-            keys.is_pat.push_back(search_term_pattern(q, t, cfg, ignore_case, &sp) ? 1 : 0);
-            keys.pats.push_back(sp);
-          }
-          if (!wild) continue;
-          PackedKey m;
-          for (int j = 0; j < kKeyWords; ++j)
-            m.w[j] = search_term_prefix(q, t, cfg) ? key_word_mask(keys.keys.back().w[j]) : ~0ull;
-          keys.masks.push_back(m);
-        }
+        keys = positive_terms(q, cfg, patterns, ignore_case);
       if (!absent && !lists.empty()) {
         size_t d = 0;
         for (size_t i = 1; i < lists.size(); ++i)
@@ -870,6 +938,7 @@ SearchResult search_index_impl(const IndexResult& x, const TextInput* text,
   }
   r.search_ms = (now_ns() - t0) * 1e-6;
   r.times.wall_ms += r.search_ms;
+  if (show) show_lines(*text, line_at, cfg, patterns, (u32)show, &r);
   if (cfg.check) validate_search(r);
   return r;
 }
@@ -877,14 +946,14 @@ SearchResult search_index_impl(const IndexResult& x, const TextInput* text,
 }  // namespace
 
 SearchResult search_index(const IndexResult& x, const std::vector<SearchQuery>& queries,
-                          const JobConfig& cfg, u64 rank_k, bool ignore_case) {
-  return search_index_impl(x, nullptr, queries, cfg, rank_k, ignore_case);
+                          const JobConfig& cfg, u64 rank_k, bool ignore_case, u64 show) {
+  return search_index_impl(x, nullptr, queries, cfg, rank_k, ignore_case, show);
 }
 
 SearchResult search_index(const IndexResult& x, const TextInput& text,
                           const std::vector<SearchQuery>& queries, const JobConfig& cfg,
-                          u64 rank_k, bool ignore_case) {
-  return search_index_impl(x, &text, queries, cfg, rank_k, ignore_case);
+                          u64 rank_k, bool ignore_case, u64 show) {
+  return search_index_impl(x, &text, queries, cfg, rank_k, ignore_case, show);
 }
 
 void validate_search(const SearchResult& r) {
@@ -931,10 +1000,57 @@ void validate_search(const SearchResult& r) {
                     " not strictly ascending at position " + std::to_string(j - r.offsets[q]));
     }
   }
+  if (r.show_bytes == 0) {
+    if (!r.text.empty() || !r.text_off.empty() || !r.spans.empty() || !r.span_off.empty() ||
+        r.cut_lines)
+      throw Error("LOCUST_CHECK: search result without show holds shown lines");
+    return;
+  }
+  const size_t E = r.lines.size();
+  if (r.text_off.size() != E + 1 || r.text_off.front() != 0 || r.text_off.back() != r.text.size())
+    throw Error("LOCUST_CHECK: show text offsets do not span the " + std::to_string(r.text.size()) +
+                " bytes of " + std::to_string(E) + " entries");
+  if (r.span_off.size() != E + 1 || r.span_off.front() != 0 || r.spans.size() % 3 != 0 ||
+      r.span_off.back() != r.spans.size() / 3)
+    throw Error("LOCUST_CHECK: show span offsets do not span the " +
+                std::to_string(r.spans.size() / 3) + " spans of " + std::to_string(E) + " entries");
+  if (r.cut_lines > E)
+    throw Error("LOCUST_CHECK: " + std::to_string(r.cut_lines) + " cut lines of " +
+                std::to_string(E) + " entries");
+  for (size_t q = 0; q + 1 < r.offsets.size(); ++q) {
+    const u32 npos = (u32)r.queries[q].positives();
+    for (u64 e = r.offsets[q]; e < r.offsets[q + 1]; ++e) {
+      if (r.text_off[e + 1] < r.text_off[e] || r.text_off[e + 1] - r.text_off[e] > r.show_bytes ||
+          r.text_off[e + 1] > r.text.size())
+        throw Error("LOCUST_CHECK: entry " + std::to_string(e) + " shows " +
+                    std::to_string(r.text_off[e + 1] - r.text_off[e]) + " bytes, N = " +
+                    std::to_string(r.show_bytes));
+      if (r.span_off[e + 1] < r.span_off[e] || r.span_off[e + 1] > r.spans.size() / 3)
+        throw Error("LOCUST_CHECK: show span offsets decrease at entry " + std::to_string(e));
+      // a line shorter than N is shown whole: its spans lie inside the shown bytes
+      const u64 tl = r.text_off[e + 1] - r.text_off[e];
+      const u64 line_max = tl < r.show_bytes ? tl : (1ull << 32);
+      u64 from = 0;  // the end of the span before
+      for (u64 s = r.span_off[e]; s < r.span_off[e + 1]; ++s) {
+        const u64 st = r.spans[3 * s], ln = r.spans[3 * s + 1];
+        const u32 mask = r.spans[3 * s + 2];
+        if (ln == 0 || st < from || (s > r.span_off[e] && st == from) || st + ln > line_max)
+          throw Error("LOCUST_CHECK: span " + std::to_string(s - r.span_off[e]) + " of entry " +
+                      std::to_string(e) + " (" + std::to_string(st) + ", " + std::to_string(ln) +
+                      ") overlaps the span before it or leaves the line");
+        if (mask == 0 || (npos < 32 && (mask >> npos) != 0))
+          throw Error("LOCUST_CHECK: span " + std::to_string(s - r.span_off[e]) + " of entry " +
+                      std::to_string(e) + " has mask " + std::to_string(mask) + " for " +
+                      std::to_string(npos) + " positive terms");
+        from = st + ln;
+      }
+    }
+  }
 }
 
-void format_search_output(const SearchResult& r, std::string* out) {
-  out->reserve(out->size() + r.queries.size() * 48 + r.lines.size() * 6);
+void format_search_output(const SearchResult& r, std::string* out, bool mark) {
+  out->reserve(out->size() + r.queries.size() * 48 + r.lines.size() * 6 + r.text.size() +
+               r.lines.size() * 16);
   for (size_t q = 0; q < r.queries.size(); ++q) {
     out->append("print query:");
     const size_t npos = r.queries[q].positives();
@@ -956,6 +1072,27 @@ void format_search_output(const SearchResult& r, std::string* out) {
       }
     }
     out->push_back('\n');
+    if (!r.show_bytes) continue;
+    for (u64 e = r.offsets[q]; e < r.offsets[q + 1]; ++e) {
+      out->append("  ");
+      out->append(std::to_string(r.lines[e]));
+      out->append(": ");
+      const char* t = r.text.data() + r.text_off[e];
+      const u64 tl = r.text_off[e + 1] - r.text_off[e];
+      u64 done = 0;
+      if (mark)
+        for (u64 s = r.span_off[e]; s < r.span_off[e + 1]; ++s) {
+          const u64 st = r.spans[3 * s], en = std::min<u64>(st + r.spans[3 * s + 1], tl);
+          if (st >= tl) break;  // (ascending: the spans behind it lie outside the shown bytes too)
+          out->append(t + done, (size_t)(st - done));
+          out->append(">>");
+          out->append(t + st, (size_t)(en - st));
+          out->append("<<");
+          done = en;
+        }
+      out->append(t + done, (size_t)(tl - done));
+      out->push_back('\n');
+    }
   }
 }
 

@@ -51,12 +51,12 @@ TopResult GpuWordCount::top_counts(const KeyCount* recs, u64 n, u32 k) {
 IndexResult GpuWordCount::run_index(const TextInput& in) { return impl_->run_index(in); }
 SearchResult GpuWordCount::run_search(const TextInput& in,
                                       const std::vector<SearchQuery>& queries, u64 rank_k,
-                                      bool ignore_case) {
-  return impl_->run_search(in, queries, rank_k, ignore_case);
+                                      bool ignore_case, u64 show) {
+  return impl_->run_search(in, queries, rank_k, ignore_case, show);
 }
 SearchResult GpuWordCount::search_resident(const std::vector<SearchQuery>& queries, u64 rank_k,
-                                           bool ignore_case) {
-  return impl_->search_resident(queries, rank_k, ignore_case);
+                                           bool ignore_case, u64 show) {
+  return impl_->search_resident(queries, rank_k, ignore_case, show);
 }
 GpuWordCount::Stats GpuWordCount::stats() const {
   Stats s;
@@ -72,7 +72,8 @@ GpuWordCount::Stats GpuWordCount::stats() const {
   s.map_window = impl_->map_window;
   s.search_bytes = impl_->sbatch_bytes + impl_->shits_bytes +
                    impl_->sbatch.merged_cap * sizeof(u32) +
-                   (impl_->d_spat ? search_pattern_bytes() : 0);
+                   (impl_->d_spat ? search_pattern_bytes() : 0) + impl_->show_entry_cap_bytes +
+                   impl_->sshow.cap_text + impl_->sshow.cap_spans * 3 * sizeof(u32);
   return s;
 }
 

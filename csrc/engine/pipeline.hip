@@ -564,6 +564,12 @@ DevicePipeline::~DevicePipeline() {
   pinned_free(h_slines);
   for (auto& e : ev_search)
     if (e) (void)hipEventDestroy(e);
+  if (d_show_entries) (void)hipFree(d_show_entries);
+  if (d_show_text) (void)hipFree(d_show_text);
+  if (d_show_spans) (void)hipFree(d_show_spans);
+  pinned_free(h_show);
+  for (auto& e : ev_show)
+    if (e) (void)hipEventDestroy(e);
 }
 
 void DevicePipeline::use_out(size_t i) {
@@ -2143,8 +2149,136 @@ void DevicePipeline::check_search_batch(const std::vector<SearchQuery>& queries,
   check_search_rank(rank_k, cfg, search_has_patterns(queries, ignore_case));
 }
 
+void DevicePipeline::show_stage(u32 Q, const u64* offsets, u64 E, u32 N, SearchResult* r) {
+  TraceRange tr("locust:show");
+  r->show_bytes = N;
+  r->text_off.assign(1, 0);
+  r->span_off.assign(1, 0);
+  if (E == 0) return;  // nothing returned: nothing to show, nothing launched
+  if (!ev_show[0])
+    for (auto& e : ev_show) LOCUST_HIP_CHECK(hipEventCreate(&e));
+  size_t fr = 0, tot = 0;
+  if (sshow.cap_entries < E) {
+    // (the stream is drained: search_stage has synchronised)
+    if (d_show_entries) LOCUST_HIP_CHECK(hipFree(d_show_entries));
+    d_show_entries = nullptr;
+    sshow.cap_entries = 0;
+    show_entry_cap_bytes = 0;
+    const u64 cap = align_up(E, (u64)4096);
+    const u64 bytes = show_entry_bytes(cap);
+    LOCUST_HIP_CHECK(hipMemGetInfo(&fr, &tot));
+    if ((double)bytes > kHbmUsable * (double)fr)
+      throw Error("show: the stage's per-entry arrays (" + std::to_string(bytes) + " B for " +
+                  std::to_string(E) + " returned lines) do not fit the free device memory (" +
+                  std::to_string(fr) + " B free of " + std::to_string(tot) +
+                  " B): use --rank K to return fewer lines");
+    LOCUST_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&d_show_entries), bytes));
+    show_entry_cap_bytes = bytes;
+    show_entry_carve(d_show_entries, cap, &sshow);
+  }
+  LOCUST_HIP_CHECK(hipEventRecord(ev_show[0], stream));
+  launch_show_measure(idx_view, sbatch, Q, shits.lines, offsets, E, N, sshow, stream);
+  // the stage's one readback: the totals size, or refuse, the payload
+  if (h_show_cap < sizeof(ShowCounters)) {
+    h_show_cap = 1u << 20;
+    h_show = static_cast<char*>(pinned_alloc(h_show_cap, hipHostMallocDefault, "show payload"));
+  }
+  ShowCounters* h_ctr = reinterpret_cast<ShowCounters*>(h_show);
+  LOCUST_HIP_CHECK(hipMemcpyAsync(h_ctr, sshow.ctr, sizeof(ShowCounters), hipMemcpyDeviceToHost,
+                                  stream));
+  sync();
+  const u64 T = h_ctr->text, S = h_ctr->spans, cut = h_ctr->cut;
+  if (T > E * (u64)N || cut > E)
+    throw Error("show: the measure pass reports " + std::to_string(T) + " text bytes and " +
+                std::to_string(cut) + " cut lines for " + std::to_string(E) + " entries of at "
+                "most " + std::to_string(N) + " bytes");
+  const u64 off_bytes = (E + 1) * sizeof(u64);
+  const u64 payload = T + S * 3 * sizeof(u32) + 2 * off_bytes;
+  const u64 need = align_up(sizeof(ShowCounters), 256) + align_up(2 * off_bytes, 256) +
+                   align_up(S * 3 * sizeof(u32), 256) + T;
+  if (payload > kShowMaxPayload)
+    throw Error("show: the batch's payload (" + std::to_string(payload) + " B: " +
+                std::to_string(T) + " text bytes and " + std::to_string(S) + " spans of " +
+                std::to_string(E) + " returned lines) exceeds the pinned buffer's limit (" +
+                std::to_string(kShowMaxPayload) + " B): use --rank K to return fewer lines, or "
+                "a smaller --show N");
+  if (sshow.cap_text < T || sshow.cap_spans < S) {
+    const u64 cap_t = std::max<u64>(align_up(T, (u64)1 << 16), 1u << 16);
+    const u64 cap_s = std::max<u64>(align_up(S, (u64)1 << 12), 1u << 12);
+    if (sshow.cap_text < T) {
+      if (d_show_text) LOCUST_HIP_CHECK(hipFree(d_show_text));
+      d_show_text = nullptr;
+      sshow.text = nullptr;
+      sshow.cap_text = 0;
+    }
+    if (sshow.cap_spans < S) {
+      if (d_show_spans) LOCUST_HIP_CHECK(hipFree(d_show_spans));
+      d_show_spans = nullptr;
+      sshow.spans = nullptr;
+      sshow.cap_spans = 0;
+    }
+    const u64 bytes = (sshow.text ? 0 : cap_t) + (sshow.spans ? 0 : cap_s * 3 * sizeof(u32));
+    LOCUST_HIP_CHECK(hipMemGetInfo(&fr, &tot));
+    if ((double)bytes > kHbmUsable * (double)fr)
+      throw Error("show: the batch's payload (" + std::to_string(payload) + " B: " +
+                  std::to_string(T) + " text bytes and " + std::to_string(S) + " spans of " +
+                  std::to_string(E) + " returned lines) does not fit the free device memory (" +
+                  std::to_string(fr) + " B free of " + std::to_string(tot) +
+                  " B): use --rank K to return fewer lines, or a smaller --show N");
+    if (!sshow.text) {
+      LOCUST_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&d_show_text), cap_t));
+      sshow.text = d_show_text;
+      sshow.cap_text = cap_t;
+    }
+    if (!sshow.spans) {
+      LOCUST_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&d_show_spans), cap_s * 3 * sizeof(u32)));
+      sshow.spans = d_show_spans;
+      sshow.cap_spans = cap_s;
+    }
+  }
+  if (h_show_cap < need) {
+    pinned_free(h_show);
+    h_show = nullptr;
+    h_show_cap = 0;
+    const u64 cap = align_up(need, (u64)1 << 20);
+    h_show = static_cast<char*>(pinned_alloc(cap, hipHostMallocDefault, "show payload"));
+    h_show_cap = cap;
+    h_ctr = reinterpret_cast<ShowCounters*>(h_show);
+  }
+  launch_show_write(idx_view, sbatch, Q, shits.lines, offsets, E, sshow, stream);
+  u64* h_toff = reinterpret_cast<u64*>(h_show + align_up(sizeof(ShowCounters), 256));
+  u64* h_soff = h_toff + (E + 1);
+  u32* h_spans =
+      reinterpret_cast<u32*>(reinterpret_cast<char*>(h_toff) + align_up(2 * off_bytes, 256));
+  char* h_text = reinterpret_cast<char*>(h_spans) + align_up(S * 3 * sizeof(u32), 256);
+  LOCUST_HIP_CHECK(hipMemcpyAsync(h_toff, sshow.text_off, off_bytes, hipMemcpyDeviceToHost,
+                                  stream));
+  LOCUST_HIP_CHECK(hipMemcpyAsync(h_soff, sshow.span_off, off_bytes, hipMemcpyDeviceToHost,
+                                  stream));
+  if (S)
+    LOCUST_HIP_CHECK(hipMemcpyAsync(h_spans, sshow.spans, S * 3 * sizeof(u32),
+                                    hipMemcpyDeviceToHost, stream));
+  if (T) LOCUST_HIP_CHECK(hipMemcpyAsync(h_text, sshow.text, T, hipMemcpyDeviceToHost, stream));
+  LOCUST_HIP_CHECK(hipMemcpyAsync(h_ctr, sshow.ctr, sizeof(ShowCounters), hipMemcpyDeviceToHost,
+                                  stream));
+  LOCUST_HIP_CHECK(hipEventRecord(ev_show[1], stream));
+  sync();
+  if (h_ctr->mismatch || h_ctr->text != T || h_ctr->spans != S || h_toff[E] != T || h_soff[E] != S)
+    throw Error("show: the write pass disagrees with the measure pass on " +
+                std::to_string(h_ctr->mismatch) + " of " + std::to_string(E) + " entries (" +
+                std::to_string(h_soff[E]) + " of " + std::to_string(S) + " spans, " +
+                std::to_string(h_toff[E]) + " of " + std::to_string(T) + " text bytes)");
+  r->text_off.assign(h_toff, h_toff + E + 1);
+  r->span_off.assign(h_soff, h_soff + E + 1);
+  r->spans.assign(h_spans, h_spans + S * 3);
+  r->text.assign(h_text, (size_t)T);
+  r->cut_lines = cut;
+  r->show_ms = ms_between(ev_show[0], ev_show[1]);
+  r->wire_bytes += payload + 2 * sizeof(ShowCounters);
+}
+
 void DevicePipeline::search_stage(const std::vector<SearchQuery>& queries, u64 rank_k,
-                                  bool ignore_case, SearchResult* r) {
+                                  bool ignore_case, u32 show, SearchResult* r) {
   TraceRange tr("locust:search");
   const u32 Q = (u32)queries.size();
   r->queries = queries;
@@ -2171,6 +2305,7 @@ void DevicePipeline::search_stage(const std::vector<SearchQuery>& queries, u64 r
   if (Q == 0) {
     LOCUST_HIP_CHECK(hipEventRecord(ev_search[1], stream));
     sync();
+    if (show) show_stage(0, nullptr, 0, show, r);
     return;
   }
   // the batch: q_meta | the terms' keys, packed exactly as the map packs them | the windows,
@@ -2325,6 +2460,7 @@ void DevicePipeline::search_stage(const std::vector<SearchQuery>& queries, u64 r
     for (u64 i = 0; i < (u64)Q * kSearchMaxTerms; ++i) r->term_counts[i] = h_tlen[i];
     r->wire_bytes = ((u64)Q + 1) * sizeof(u64) + (u64)Q * sizeof(u32) + 2 * R * sizeof(u32) +
                     (u64)Q * kSearchMaxTerms * sizeof(u32) + 3 * sizeof(SearchCounters);
+    if (show) show_stage(Q, sbatch.out_off, R, show, r);
     return;
   }
   // order + emit
@@ -2350,13 +2486,15 @@ void DevicePipeline::search_stage(const std::vector<SearchQuery>& queries, u64 r
   for (u64 i = 0; i < (u64)Q * kSearchMaxTerms; ++i) r->term_counts[i] = h_tlen[i];
   r->wire_bytes = ((u64)Q + 1) * sizeof(u64) + H * sizeof(u32) +
                   (u64)Q * kSearchMaxTerms * sizeof(u32) + 3 * sizeof(SearchCounters);
+  if (show) show_stage(Q, sbatch.offsets, H, show, r);
 }
 
 SearchResult DevicePipeline::run_search(const TextInput& in,
                                         const std::vector<SearchQuery>& queries, u64 rank_k,
-                                        bool ignore_case) {
+                                        bool ignore_case, u64 show) {
   TraceRange tr("locust:search_job");
   check_search_batch(queries, rank_k, ignore_case);  // (a refused batch starts nothing)
+  check_search_show(show, in.bytes);
   idx_resident = false;         // (until this job has left its index)
   SearchResult r;
   WordCountResult w;
@@ -2366,7 +2504,7 @@ SearchResult DevicePipeline::run_search(const TextInput& in,
   sync();
   check_index_counters(n, T);
   keep_index(in, w, n, T);
-  search_stage(queries, rank_k, ignore_case, &r);
+  search_stage(queries, rank_k, ignore_case, (u32)show, &r);
   r.index_ms = ms_between(ev_index[0], ev_index[1]);
   r.search_ms = ms_between(ev_search[0], ev_search[1]);
   r.wire_bytes += sizeof(IndexCounters) + sizeof(MapCounters);
@@ -2374,25 +2512,26 @@ SearchResult DevicePipeline::run_search(const TextInput& in,
   r.times.map_ms = ms_between(ev[1], ev[2]);
   r.times.process_ms = ms_between(ev[2], ev[3]);
   r.times.reduce_ms = ms_between(ev[3], ev[4]);
-  r.times.gpu_ms = ms_between(ev[0], ev_search[1]);
+  r.times.gpu_ms = ms_between(ev[0], ev_search[1]) + r.show_ms;
   r.times.wall_ms = (now_ns() - t0) * 1e-6;
   if (cfg.check) validate_search(r);
   return r;
 }
 
 SearchResult DevicePipeline::search_resident(const std::vector<SearchQuery>& queries,
-                                             u64 rank_k, bool ignore_case) {
+                                             u64 rank_k, bool ignore_case, u64 show) {
   TraceRange tr("locust:search_resident");
   check_search_batch(queries, rank_k, ignore_case);
+  check_search_show(show, idx_view.bytes);
   if (!idx_resident)
     throw Error("search_resident: the index on the device is stale -- this engine's last job "
                 "was not a run_index or a run_search (any other job, a refused one included, "
                 "overwrites what the index reads); run one of them first");
   SearchResult r;
   const u64 t0 = now_ns();
-  search_stage(queries, rank_k, ignore_case, &r);
+  search_stage(queries, rank_k, ignore_case, (u32)show, &r);
   r.search_ms = ms_between(ev_search[0], ev_search[1]);
-  r.times.gpu_ms = r.search_ms;
+  r.times.gpu_ms = r.search_ms + r.show_ms;
   r.times.wall_ms = (now_ns() - t0) * 1e-6;
   if (cfg.check) validate_search(r);
   return r;

@@ -832,12 +832,31 @@ struct DevicePipeline {
   // The batch over idx_view on `stream`, timed by ev_search; synchronises (the bound, the
   // number of hits, the result) and fills r's lists, statistics and wire_bytes.
   // rank_k != 0: the ranked answer (engine.hpp "ranked search").
+  // show != 0: show_stage behind it, over the lines and offsets it left on the device.
   void search_stage(const std::vector<SearchQuery>& queries, u64 rank_k, bool ignore_case,
-                    SearchResult* r);
+                    u32 show, SearchResult* r);
   SearchResult run_search(const TextInput& in, const std::vector<SearchQuery>& queries,
-                          u64 rank_k, bool ignore_case);
+                          u64 rank_k, bool ignore_case, u64 show);
   SearchResult search_resident(const std::vector<SearchQuery>& queries, u64 rank_k,
-                               bool ignore_case);
+                               bool ignore_case, u64 show);
+  // ---- show (kernels/show.hip) ----
+  // The stage's arrays are allocations of their own, made by the engine's first show batch and
+  // grown on demand: the per-entry part (by the batch's entries), the payload's text and
+  // spans (by the totals the measure pass reports; checked against free HBM and
+  // kShowMaxPayload), and the pinned buffer the payload comes back to.  A batch without show
+  // touches none of them.
+  ShowBuffers sshow{};
+  char* d_show_entries = nullptr;
+  u64 show_entry_cap_bytes = 0;
+  char* d_show_text = nullptr;
+  u32* d_show_spans = nullptr;
+  char* h_show = nullptr;  // pinned [ShowCounters | text_off | span_off | spans | text]
+  u64 h_show_cap = 0;
+  hipEvent_t ev_show[2] = {};
+  // measure + scan + (the one readback) + write over the `entries` returned lines of the batch
+  // search_stage has just answered (offsets: the device's per-query segments); fills r's show
+  // fields and adds what it copied to r->wire_bytes.
+  void show_stage(u32 queries, const u64* offsets, u64 entries, u32 show, SearchResult* r);
 
   // ---------------------------------------------------------------------------------
   // Streaming: an input larger than the engine's text capacity is processed in

@@ -12,6 +12,7 @@
 #include <iterator>
 #include <memory>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "locust/common.hpp"
@@ -522,6 +523,38 @@ void format_index_output(const IndexResult& r, std::string* out);
 // The device finds a pattern term's words by a scan of the dictionary (kernels.hpp
 // "search.hip": match, scatter): (pattern slots) x (dictionary words) matcher calls per batch,
 // twice for the slots that cover two or more words.
+//
+// ---- show: the returned lines' text and match spans ----
+// A search job may ask for show = N, a u32 with 1 <= N <= kShowMaxBytes = 65536; show == 0,
+// the default, is the answer described above, bit for bit.  With show = N every entry i of
+// `lines` -- in result order: unranked, per query ascending; ranked, the min(K, matches)
+// winners in rank order -- also gets:
+//   text   the line's bytes from its start to its end, cut to the first N bytes.  The end is
+//     the '\n', the end of the input, or a NUL: exactly where the tokenisers stop.  cut_lines
+//     counts the entries whose line was longer than N.
+//   spans  one (start, len, mask) triple of u32 for every emitted token of the line (ordinal <
+//     emits_per_line) that matches at least one positive term of that entry's query, in token
+//     order.  start is the byte offset from the line's start; len the token's full length up to
+//     the next delimiter or the line's end, cut neither to max_key_len nor to N; mask bit j is
+//     set when the token matches positive term j.  A token matches a term as the phrase and
+//     `near` verification match them: equality of cut keys, a prefix term's bytes, a pattern
+//     term's matcher, under the batch's fold with ignore_case.  A term that repeats an earlier
+//     one sets its own bit too.  Exclusion terms never produce a span.  The rule is the same in
+//     every mode: in `phrase` and `near` every token that matches a term is a span, not only
+//     those inside an occurrence or a window.  A token past the emit cap produces nothing, as
+//     everywhere else.
+// The same line returned for two queries is two entries, each with its own spans.  Entry i's
+// text is text[text_off[i] .. text_off[i + 1]), its triples spans[3 * span_off[i] .. 3 *
+// span_off[i + 1]).  Refused with a clear error: N out of range; a job whose text window holds
+// 2^32 bytes or more (a span's start is a u32); on the device, a payload (text, spans and both
+// offset arrays) that does not fit the free device memory or the pinned buffer
+// (kShowMaxPayload) -- the index stays resident behind a refused show.
+// The device stage (kernels/show.hip) runs behind the search stage on the resident text, line
+// starts, keys and returned lines: the text itself never crosses PCIe, only the shown bytes and
+// spans do (wire_bytes counts them).  The host evaluation needs the text: the four-argument
+// search_index.
+constexpr u32 kShowMaxBytes = 65536;
+constexpr u64 kShowMaxPayload = 4ull << 30;  // bytes of one batch's show payload on the device
 constexpr u32 kSearchMaxQueries = 1024;
 constexpr u32 kSearchMaxTerms = 8;
 constexpr u64 kRankMaxEmits = 65536;
@@ -565,6 +598,14 @@ struct SearchResult {
   double index_ms = 0;   // device time of the index stage (0: built on the host, or resident)
   double search_ms = 0;  // device time of the search stage (host evaluation: its wall time)
   u64 wire_bytes = 0;    // bytes the device wrote to host memory for the result
+  // "show" above (show_bytes == 0: none of these is filled)
+  u32 show_bytes = 0;          // N
+  std::string text;            // the entries' shown bytes, one after the other
+  std::vector<u64> text_off;   // [entries + 1]
+  std::vector<u32> spans;      // (start, len, mask) triples
+  std::vector<u64> span_off;   // [entries + 1], in triples
+  u64 cut_lines = 0;           // entries whose line was longer than N
+  double show_ms = 0;  // device time of the show stage (host evaluation: its wall time)
   u64 hits() const { return lines.size(); }
 };
 // A term's key: its first min(size, cfg.max_key_len) bytes, packed as the map packs keys.
@@ -608,6 +649,9 @@ void check_search_merge(u64 queries, u64 elements);
 // Throws unless rank_k is 0 (unranked) or a u32 >= 1 with cfg.emits_per_line <= kRankMaxEmits
 // (patterns: the batch holds a pattern term -- kRankMaxEmits / kSearchMaxTerms).
 void check_search_rank(u64 rank_k, const JobConfig& cfg, bool patterns = false);
+// Throws unless show is 0 (no show) or 1 <= show <= kShowMaxBytes and the window holds fewer
+// than 2^32 bytes ("show" above).
+void check_search_show(u64 show, u64 text_bytes);
 // The host evaluation over an index result, any number of queries (cfg: the index job's
 // delimiters and max_key_len).  Throws for a phrase query and for a `near` query of two or
 // more terms: the index holds no positions, so they need the text -- the four-argument
@@ -615,21 +659,26 @@ void check_search_rank(u64 rank_k, const JobConfig& cfg, bool patterns = false);
 // rank_k != 0 ranks every query (scores come from the postings alone).
 // ignore_case: "pattern terms" above.  Pattern terms' words come from a scan of the entries
 // with the shared matcher.
+// show != 0 is refused: the shown lines come from the text (the four-argument overload).
 SearchResult search_index(const IndexResult& x, const std::vector<SearchQuery>& queries,
-                          const JobConfig& cfg, u64 rank_k = 0, bool ignore_case = false);
+                          const JobConfig& cfg, u64 rank_k = 0, bool ignore_case = false,
+                          u64 show = 0);
 // The same with the text the index was built from (the same window: text.first_line ==
 // x.first_line; cfg also gives emits_per_line): a phrase's or a `near` query's candidates
 // come from the `all` evaluation and are verified by tokenising their lines with the CPU
-// engine's tokeniser.
+// engine's tokeniser.  show = N: "show" above, from the same tokeniser and the shared matcher.
 SearchResult search_index(const IndexResult& x, const TextInput& text,
                           const std::vector<SearchQuery>& queries, const JobConfig& cfg,
-                          u64 rank_k = 0, bool ignore_case = false);
+                          u64 rank_k = 0, bool ignore_case = false, u64 show = 0);
 // LOCUST_CHECK invariants of a search result: offsets monotone from 0 to lines.size(), every
 // line inside [first_line, first_line + num_lines), one `matches` per query.  Unranked: every
 // query's lines strictly ascending, matches == the hit counts, no scores.  Ranked: one score
 // per line, each in [1, 32 * emits_per_line] (a batch with a pattern term: times 8), per query
 // non-increasing with equal scores on ascending lines, and at most min(rank_k, matches) lines
-// per query.
+// per query.  With show: both offset arrays monotone from 0 to their array's size, every text
+// length <= N, and per entry the spans strictly ascending and non-overlapping, start + len
+// inside the line (the shown bytes, when the line was not cut), masks non-zero and without a
+// bit at or above the query's positive-term count.
 void validate_search(const SearchResult& r);
 // The result lines of a search, one per query:
 //   "print query: <terms joined by one space> \t hits: <h> \t lines: <l0> <l1> ...\n"
@@ -638,7 +687,10 @@ void validate_search(const SearchResult& r);
 // with exclusion terms prints " \t not: <those joined by one space>" before " \t hits:")
 // ranked (hits: the matches; nothing after "top:" when nothing matched):
 //   "print query: <terms> \t hits: <matches> \t top: <l0>:<s0> <l1>:<s1> ...\n"
-void format_search_output(const SearchResult& r, std::string* out);
+// A result with show prints one line per entry under its query's line:
+//   "  <global line number>: <the shown bytes>\n"
+// mark: the part of every span that lies inside the shown bytes stands between ">>" and "<<".
+void format_search_output(const SearchResult& r, std::string* out, bool mark = false);
 
 // Text read piece by piece (a file too large to hold): whole lines go straight into the
 // engine's pinned staging, so host memory stays bounded by two chunks whatever the input.
@@ -773,13 +825,14 @@ class GpuWordCount {
   // per-term counts and the counters cross PCIe.  run_index's refusals apply.  The text
   // stays in device memory beside the index (the engine's own copy, not the staging
   // buffer): phrase queries are verified against it.
+  // show = N: the show stage behind it ("show": kernels/show.hip).
   SearchResult run_search(const TextInput& in, const std::vector<SearchQuery>& queries,
-                          u64 rank_k = 0, bool ignore_case = false);
+                          u64 rank_k = 0, bool ignore_case = false, u64 show = 0);
   // Another batch from the index this engine's last job left on the device.  That job must
   // have been a run_index or a run_search: any other job (a refused one that had started
   // to write included) marks the index stale, and this then throws.
   SearchResult search_resident(const std::vector<SearchQuery>& queries, u64 rank_k = 0,
-                               bool ignore_case = false);
+                               bool ignore_case = false, u64 show = 0);
 
   const JobConfig& config() const;
   u64 token_capacity() const;
@@ -829,7 +882,7 @@ class CpuWordCount {
   // run_index() + the host evaluation (search_index with the text), any size, any number
   // of queries and every mode.
   SearchResult run_search(const TextInput& in, const std::vector<SearchQuery>& queries,
-                          u64 rank_k = 0, bool ignore_case = false);
+                          u64 rank_k = 0, bool ignore_case = false, u64 show = 0);
   std::vector<PackedKey> run_map_stage(const TextInput& in, WordCountResult* stats);
   WordCountResult run_reduce_stage(const PackedKey* keys, u64 n);
 
@@ -839,8 +892,9 @@ class CpuWordCount {
 
 // Tokenize one line with the reference rules (delimiters, emit cap, truncation).  Used by
 // the CPU engine and the tests; returns the number of tokens dropped by the emit cap.
+// at (word keys only): per emitted token its byte offset in the line and its full length.
 int tokenize_line(const char* line, u64 len, const JobConfig& cfg, std::vector<PackedKey>* out,
-                  u64* truncated);
+                  u64* truncated, std::vector<std::pair<u32, u32>>* at = nullptr);
 
 // Sorted unique keys + counts -> entries with val = exclusive prefix of counts.
 void entries_from_sorted_tokens(const PackedKey* sorted, u64 n, std::vector<WordCountEntry>* out);

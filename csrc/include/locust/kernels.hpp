@@ -917,6 +917,61 @@ void launch_search_order(const SearchIndex& ix, const SearchBatch& b, u32 querie
 void launch_search_rank(const SearchIndex& ix, const SearchBatch& b, u32 queries, u64 hits,
                         u32 k, SearchHits& h, SortPlan* h_plan, hipStream_t s);
 
+// ---------------- show.hip ----------------
+// The show stage of a search batch (engine.hpp "show"): for each of the E returned lines, in
+// result order (h.lines; the per-query segments in b.offsets, ranked: b.out_off), the line's
+// first N bytes and the spans of its emitted tokens that match a positive term of the entry's
+// query.  Everything it reads is resident: the text, nl_pos, the batch's keys and pattern
+// arrays, the returned lines.
+//   measure  one wave per entry, up to 64 consecutive entries per wave and round (lane i finds
+//            entry i's query by a binary search in the offsets; the query's keys go to the
+//            wave's LDS, reloaded only when the query changes).  The verify kernels' walk, 64
+//            bytes per step with the 32-byte look-ahead row: the step's matching emitted tokens
+//            are counted by ballot and popcount.  Per entry n_spans and t_len = min(line
+//            length, N); the lines longer than N count in ShowCounters::cut
+//   scan     one workgroup: exclusive u64 scans of both arrays into span_off and text_off
+//            [E + 1]; the totals also to ShowCounters::spans and ::text
+//   (the host reads the counters: it sizes, or refuses, the payload)
+//   write    the same walk: a step's spans go to span_off[i] + (spans so far) + lanes_below;
+//            a token that runs past its step stays open, wave-uniformly, and its length is
+//            written when a later step (or the line's end) closes it; the step's 64 bytes go to
+//            text_off[i] + the step's offset while below t_len.  Every word is written once, at
+//            a determined place: no atomics, no compaction.  An entry whose spans do not number
+//            what measure counted adds to ShowCounters::mismatch (the host throws)
+// A batch that has a pattern term runs the siblings compiled with the matcher
+// (show_globmeasure_kernel, show_globwrite_kernel).
+struct ShowCounters {  // zeroed per show batch
+  u64 text;       // T: the payload's text bytes
+  u64 spans;      // S: its span triples
+  u32 cut;        // entries whose line is longer than N
+  u32 mismatch;   // write: entries whose spans do not number what measure counted
+  u32 pad[2];
+};
+static_assert(sizeof(ShowCounters) == 32, "one readback");
+// The stage's arrays: the per-entry part (sized by E) and the payload (sized by T and S), two
+// allocations of the engine's, grown on demand.
+struct ShowBuffers {
+  ShowCounters* ctr = nullptr;
+  u32* n_spans = nullptr;   // [E]
+  u32* t_len = nullptr;     // [E]
+  u64* span_off = nullptr;  // [E + 1]
+  u64* text_off = nullptr;  // [E + 1]
+  u64 cap_entries = 0;
+  char* text = nullptr;     // [cap_text]
+  u32* spans = nullptr;     // [cap_spans][3]: start, len, mask
+  u64 cap_text = 0, cap_spans = 0;
+};
+u64 show_entry_bytes(u64 entries);
+void show_entry_carve(char* base, u64 entries, ShowBuffers* sb);
+// measure + scan over the `entries` lines at `lines` (offsets: [queries + 1], their per-query
+// segments).  sb.ctr is complete when `s` has drained.
+void launch_show_measure(const SearchIndex& ix, const SearchBatch& b, u32 queries,
+                         const u32* lines, const u64* offsets, u64 entries, u32 show,
+                         const ShowBuffers& sb, hipStream_t s);
+// write: sb.text[0 .. T) and sb.spans[0 .. 3 S) (T <= sb.cap_text, S <= sb.cap_spans).
+void launch_show_write(const SearchIndex& ix, const SearchBatch& b, u32 queries, const u32* lines,
+                       const u64* offsets, u64 entries, const ShowBuffers& sb, hipStream_t s);
+
 // ---- device self-test of the string library (tests only; StringTestOut in engine.hpp) ----
 void launch_string_selftest(const char* blob, const u32* off, u32 n, const char* delims,
                             const int* ints, StringTestOut* out, hipStream_t s);
@@ -938,6 +993,7 @@ void warm_module_psort();
 void warm_module_radix_sort();
 void warm_module_reduce();
 void warm_module_search();  // (as index: the code object only, no buffers)
+void warm_module_show();  // (as search: the code object only, no buffers)
 void warm_module_shuffle();
 void warm_module_signal();
 void warm_module_tokenize();
@@ -957,6 +1013,7 @@ inline void warm_kernel_modules() {
   warm_module_radix_sort();
   warm_module_reduce();
   warm_module_search();
+  warm_module_show();
   warm_module_shuffle();
   warm_module_signal();
   warm_module_tokenize();

@@ -74,6 +74,7 @@
 #include "locust/device/glob.hpp"
 #include "locust/device/linetok.hpp"
 #include "locust/device/rank.hpp"
+#include "locust/device/termmask.hpp"
 #include "locust/device/wave.hpp"
 #include "locust/hip_check.hpp"
 #include "locust/kernels.hpp"
@@ -609,47 +610,6 @@ __global__ __launch_bounds__(kSearchBlock) void search_hit_kernel(
       commit_hits(hit, q, line - first_line, pairs, pair_cap, q_hits, ctr);
     }
   }
-}
-
-// A pointer kept in vector registers from here on.  The verify kernels' walk keeps 97 scalar
-// registers live, and the matcher's divergent loop needs about twenty more for its masks: their
-// glob siblings move the pointers they rarely use out of the scalar file instead of spilling.
-template <class T>
-__device__ __forceinline__ T* in_vgprs(T* p) {
-  u64 v = reinterpret_cast<u64>(p);
-  asm volatile("" : "+v"(v));
-  return reinterpret_cast<T*>(v);
-}
-
-// Bit j: the token that starts at row[at] matches term j of the m keys at qk -- it equals
-// the key, or (pre bit j: a prefix term) starts with the key's bytes.  kGlob (a batch with
-// pattern terms): or (pt bit j: a pattern term) the key is a pattern that matches the token's
-// cut key, qm[j] its metacharacter map and pt's kSearchFold the batch's fold.
-template <bool kGlob>
-__device__ __forceinline__ u32 token_term_mask(const unsigned char* row, int at,
-                                               const DelimMask& dm, int max_key_len,
-                                               const u64* qk, u32 m, u32 pre, u32 pt,
-                                               const u32* qm) {
-  u64 w0, w1, w2, w3;
-  dev::pack_row_key(row, at, dm, max_key_len, &w0, &w1, &w2, &w3);
-  u32 eq = 0;
-  for (u32 j = 0; j < m; ++j) {
-    const u64* k = qk + j * kKeyWords;
-    if (kGlob && ((pt >> j) & 1u)) {  // (wave-uniform)
-      eq |= (u32)glob_match(k[0], k[1], k[2], k[3], qm[j], w0, w1, w2, w3,
-                            (pt & kSearchFold) != 0)
-            << j;
-      continue;
-    }
-    if ((pre >> j) & 1u) {  // (wave-uniform) the token starts with the term's bytes
-      eq |= (u32)(k[0] == (w0 & key_word_mask(k[0])) && k[1] == (w1 & key_word_mask(k[1])) &&
-                  k[2] == (w2 & key_word_mask(k[2])) && k[3] == (w3 & key_word_mask(k[3])))
-            << j;
-      continue;
-    }
-    eq |= (u32)(k[0] == w0 && k[1] == w1 && k[2] == w2 && k[3] == w3) << j;
-  }
-  return eq;
 }
 
 // One wave per candidate; a wave takes `group` (<= 64) consecutive candidates per round,

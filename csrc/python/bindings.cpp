@@ -99,7 +99,7 @@ struct PyIndexResult {
                         const std::vector<int>& any, const py::object& rank, bool wildcard,
                         const std::vector<u64>& within,
                         const std::vector<std::vector<std::string>>& exclude, bool glob,
-                        bool ignore_case) const;
+                        bool ignore_case, const py::object& show) const;
   py::list entries() const { return PyResult{x.words}.entries(); }
   py::list postings() const {
     py::list out;
@@ -189,12 +189,44 @@ struct PySearchResult {
     d["gpu_ms"] = r.times.gpu_ms;
     d["index_ms"] = r.index_ms;
     d["search_ms"] = r.search_ms;
+    d["show_ms"] = r.show_ms;
     return d;
   }
-  py::bytes format() const {
+  py::bytes format(bool mark) const {
     std::string s;
-    format_search_output(r, &s);
+    format_search_output(r, &s, mark);
     return py::bytes(s);
+  }
+  // show: query i's entries -- the shown bytes of each, and each one's (start, len, mask) spans
+  py::list text(size_t i) const {
+    check(i);
+    py::list out;
+    if (r.show_bytes)
+      for (u64 j = r.offsets[i]; j < r.offsets[i + 1]; ++j)
+        out.append(py::bytes(r.text.data() + r.text_off[j], r.text_off[j + 1] - r.text_off[j]));
+    return out;
+  }
+  py::list text_off() const {
+    py::list out;
+    for (const u64 o : r.text_off) out.append(o);
+    return out;
+  }
+  py::list span_off() const {
+    py::list out;
+    for (const u64 o : r.span_off) out.append(o);
+    return out;
+  }
+  py::list spans(size_t i) const {
+    check(i);
+    py::list out;
+    if (r.show_bytes)
+      for (u64 j = r.offsets[i]; j < r.offsets[i + 1]; ++j) {
+        py::list one;
+        for (u64 k = r.span_off[j]; k < r.span_off[j + 1]; ++k)
+          one.append(py::make_tuple(r.spans[3 * k], r.spans[3 * k + 1], r.spans[3 * k + 2]));
+        out.append(one);
+      }
+    return out;
   }
 };
 
@@ -239,15 +271,30 @@ u64 to_rank(const py::object& rank) {
   return (u64)k;
 }
 
+// show: None or 0 (no show), or N -> the engines' show.
+u64 to_show(const py::object& show) {
+  if (show.is_none()) return 0;
+  long long n = -1;
+  try {
+    n = show.cast<long long>();
+  } catch (const py::cast_error&) {  // (not an integer, or one past 64 bits)
+  }
+  LOCUST_CHECK_ARG(n >= 0 && n <= (long long)kShowMaxBytes,
+                   "search: show takes None or 1 <= N <= " + std::to_string(kShowMaxBytes) +
+                       ", not " + py::str(show).cast<std::string>());
+  return (u64)n;
+}
+
 PySearchResult PyIndexResult::search(const std::vector<std::vector<std::string>>& queries,
                                      const std::vector<int>& any, const py::object& rank,
                                      bool wildcard, const std::vector<u64>& within,
                                      const std::vector<std::vector<std::string>>& exclude, bool glob,
-                        bool ignore_case) const {
+                        bool ignore_case, const py::object& show) const {
   const std::vector<SearchQuery> q = to_queries(queries, any, wildcard, within, exclude, glob);
   const u64 k = to_rank(rank);
+  const u64 n = to_show(show);
   py::gil_scoped_release nogil;
-  return PySearchResult{search_index(x, q, cfg, k, ignore_case)};
+  return PySearchResult{search_index(x, q, cfg, k, ignore_case, n)};
 }
 
 TextInput as_input(const std::string& text, u64 first_line = 0) {
@@ -384,11 +431,12 @@ class PyGpuEngine {
                             const py::object& rank, bool wildcard,
                             const std::vector<u64>& within,
                             const std::vector<std::vector<std::string>>& exclude, bool glob,
-                        bool ignore_case) {
+                        bool ignore_case, const py::object& show) {
     const std::vector<SearchQuery> q = to_queries(queries, any, wildcard, within, exclude, glob);
     const u64 k = to_rank(rank);
+    const u64 n = to_show(show);
     py::gil_scoped_release nogil;
-    return PySearchResult{eng_.run_search(as_input(text, first_line), q, k, ignore_case)};
+    return PySearchResult{eng_.run_search(as_input(text, first_line), q, k, ignore_case, n)};
   }
   PySearchResult run_search_text(const HostText& t,
                                  const std::vector<std::vector<std::string>>& queries,
@@ -396,21 +444,23 @@ class PyGpuEngine {
                                  const py::object& rank, bool wildcard,
                             const std::vector<u64>& within,
                             const std::vector<std::vector<std::string>>& exclude, bool glob,
-                        bool ignore_case) {
+                        bool ignore_case, const py::object& show) {
     const std::vector<SearchQuery> q = to_queries(queries, any, wildcard, within, exclude, glob);
     const u64 k = to_rank(rank);
+    const u64 n = to_show(show);
     py::gil_scoped_release nogil;
-    return PySearchResult{eng_.run_search(t.input(first_line), q, k, ignore_case)};
+    return PySearchResult{eng_.run_search(t.input(first_line), q, k, ignore_case, n)};
   }
   PySearchResult search_resident(const std::vector<std::vector<std::string>>& queries,
                                  const std::vector<int>& any, const py::object& rank,
                                  bool wildcard, const std::vector<u64>& within,
                                  const std::vector<std::vector<std::string>>& exclude, bool glob,
-                        bool ignore_case) {
+                        bool ignore_case, const py::object& show) {
     const std::vector<SearchQuery> q = to_queries(queries, any, wildcard, within, exclude, glob);
     const u64 k = to_rank(rank);
+    const u64 n = to_show(show);
     py::gil_scoped_release nogil;
-    return PySearchResult{eng_.search_resident(q, k, ignore_case)};
+    return PySearchResult{eng_.search_resident(q, k, ignore_case, n)};
   }
   // records: (key bytes, count), sorted by key with distinct keys -- the kernels alone.
   PyTopResult top_counts(const std::vector<std::pair<std::string, u64>>& records, u32 k) {
@@ -879,7 +929,7 @@ PYBIND11_MODULE(_locust, m) {
            py::arg("rank") = py::none(), py::arg("wildcard") = false,
            py::arg("within") = std::vector<u64>(),
            py::arg("exclude") = std::vector<std::vector<std::string>>(),
-           py::arg("glob") = false, py::arg("ignore_case") = false,
+           py::arg("glob") = false, py::arg("ignore_case") = false, py::arg("show") = py::none(),
            "The host evaluation of all/any queries (any[i]: query i's mode) over this index.")
       .def("times", &PyIndexResult::times)
       .def("format", &PyIndexResult::format)
@@ -905,7 +955,24 @@ PYBIND11_MODULE(_locust, m) {
       .def_property_readonly("rank_k", [](const PySearchResult& p) { return p.r.rank_k; },
                              "the batch's K; 0: unranked")
       .def("times", &PySearchResult::times)
-      .def("format", &PySearchResult::format)
+      .def("format", &PySearchResult::format, py::arg("mark") = false,
+           "the CLI's result lines (mark: the shown spans between >> and <<)")
+      .def("text", &PySearchResult::text, py::arg("i"),
+           "show: the shown bytes of every entry of query i; without show: empty")
+      .def("spans", &PySearchResult::spans, py::arg("i"),
+           "show: per entry of query i its (start, len, mask) spans; without show: empty")
+      .def("text_off", &PySearchResult::text_off,
+           "show: [entries + 1] byte offsets of the entries' texts, in result order")
+      .def("span_off", &PySearchResult::span_off,
+           "show: [entries + 1] span offsets of the entries, in result order")
+      .def_property_readonly("show_bytes", [](const PySearchResult& p) { return p.r.show_bytes; },
+                             "the batch's N; 0: no show")
+      .def_property_readonly("show_ms", [](const PySearchResult& p) { return p.r.show_ms; })
+      .def_property_readonly("cut_lines", [](const PySearchResult& p) { return p.r.cut_lines; },
+                             "show: entries whose line was longer than N")
+      .def_property_readonly("span_count",
+                             [](const PySearchResult& p) { return p.r.spans.size() / 3; },
+                             "show: the spans of all entries")
       .def_property_readonly("queries", [](const PySearchResult& p) { return p.r.queries.size(); })
       .def_property_readonly("first_line", [](const PySearchResult& p) { return p.r.first_line; })
       .def_property_readonly("num_lines", [](const PySearchResult& p) { return p.r.num_lines; })
@@ -923,6 +990,7 @@ PYBIND11_MODULE(_locust, m) {
                              "bytes the device wrote to host memory for the result");
   m.attr("kSearchMaxQueries") = kSearchMaxQueries;
   m.attr("kSearchMaxTerms") = kSearchMaxTerms;
+  m.attr("kShowMaxBytes") = kShowMaxBytes;
   m.attr("kRankMaxEmits") = kRankMaxEmits;
   m.attr("kTopKMax") = kTopKMax;
   m.attr("kMaxNgram") = kMaxNgram;
@@ -964,18 +1032,18 @@ PYBIND11_MODULE(_locust, m) {
            py::arg("any"), py::arg("first_line") = 0, py::arg("rank") = py::none(),
            py::arg("wildcard") = false, py::arg("within") = std::vector<u64>(),
            py::arg("exclude") = std::vector<std::vector<std::string>>(),
-           py::arg("glob") = false, py::arg("ignore_case") = false,
+           py::arg("glob") = false, py::arg("ignore_case") = false, py::arg("show") = py::none(),
            "WordCount of text, its index, and all/any queries answered on the device.")
       .def("run_search_text", &PyGpuEngine::run_search_text, py::arg("text"), py::arg("queries"),
            py::arg("any"), py::arg("first_line") = 0, py::arg("rank") = py::none(),
            py::arg("wildcard") = false, py::arg("within") = std::vector<u64>(),
            py::arg("exclude") = std::vector<std::vector<std::string>>(),
-           py::arg("glob") = false, py::arg("ignore_case") = false)
+           py::arg("glob") = false, py::arg("ignore_case") = false, py::arg("show") = py::none())
       .def("search_resident", &PyGpuEngine::search_resident, py::arg("queries"), py::arg("any"),
            py::arg("rank") = py::none(), py::arg("wildcard") = false,
            py::arg("within") = std::vector<u64>(),
            py::arg("exclude") = std::vector<std::vector<std::string>>(),
-           py::arg("glob") = false, py::arg("ignore_case") = false,
+           py::arg("glob") = false, py::arg("ignore_case") = false, py::arg("show") = py::none(),
            "Another batch from the index the last run_index / run_search left on the device.")
       .def("top_counts", &PyGpuEngine::top_counts, py::arg("records"), py::arg("k"),
            "The selection kernels alone over key-sorted (key, count) records.")
@@ -999,16 +1067,38 @@ PYBIND11_MODULE(_locust, m) {
                              const py::object& rank, bool wildcard,
                              const std::vector<u64>& within,
                              const std::vector<std::vector<std::string>>& exclude, bool glob,
-                        bool ignore_case) {
+                        bool ignore_case, const py::object& show) {
     CpuWordCount eng(cfg);
     return PySearchResult{eng.run_search(as_input(text, first_line),
                                          to_queries(queries, any, wildcard, within, exclude, glob),
-                                         to_rank(rank), ignore_case)};
+                                         to_rank(rank), ignore_case, to_show(show))};
   }, py::arg("cfg"), py::arg("text"), py::arg("queries"), py::arg("any"),
         py::arg("first_line") = 0, py::arg("rank") = py::none(), py::arg("wildcard") = false,
         py::arg("within") = std::vector<u64>(),
            py::arg("exclude") = std::vector<std::vector<std::string>>(),
-           py::arg("glob") = false, py::arg("ignore_case") = false);
+           py::arg("glob") = false, py::arg("ignore_case") = false, py::arg("show") = py::none());
+  m.def("check_search_show", &check_search_show, py::arg("show"), py::arg("text_bytes"),
+        "Throws unless show is 0 or 1 <= N <= kShowMaxBytes over a window of < 2^32 bytes.");
+  m.def("validate_show", [](const std::vector<std::string>& terms, const std::vector<u32>& lines,
+                            const std::vector<u64>& text_lens, const std::vector<u32>& spans,
+                            const std::vector<u64>& span_off, u32 show) {
+    // validate_search over a one-query unranked result made of these parts (tests)
+    SearchResult r;
+    r.queries.push_back(make_search_query(terms, SearchMode::kAny, false));
+    r.lines = lines;
+    r.offsets = {0, lines.size()};
+    r.matches = {lines.size()};
+    r.num_lines = lines.empty() ? 0 : (u64)lines.back() + 1;
+    r.term_counts.assign(kSearchMaxTerms, 0);
+    r.show_bytes = show;
+    r.text_off.assign(1, 0);
+    for (const u64 l : text_lens) r.text_off.push_back(r.text_off.back() + l);
+    r.text.assign((size_t)r.text_off.back(), 'x');
+    r.spans = spans;
+    r.span_off = span_off;
+    validate_search(r);
+  }, py::arg("terms"), py::arg("lines"), py::arg("text_lens"), py::arg("spans"),
+        py::arg("span_off"), py::arg("show"));
   m.def("check_search_merge", &check_search_merge, py::arg("queries"), py::arg("elements"),
         "Throws when a device batch's prefix terms would merge 2^32 list elements or more.");
   m.def("cpu_map_stage", [](const JobConfig& cfg, const std::string& text) {

@@ -70,15 +70,16 @@ def _search_args(queries, mode, within=None, exclude=None):
 
 
 def _index_search(self, queries, mode="all", rank=None, wildcard=False, within=None,
-                  exclude=None, glob=False, ignore_case=False):
+                  exclude=None, glob=False, ignore_case=False, show=None):
     """All/any word queries over this index, evaluated on the host (``SearchResult``):
     ``queries``, ``mode``, ``rank``, ``within`` and ``exclude`` as ``Engine.run_search`` takes
     them, any number of queries.  A ``"phrase"`` query, and a ``"near"`` query of two or more
     positive terms, is refused: the index holds no positions, so they need the text
-    (``Engine.run_search``, ``search_text``).  ``glob`` and ``ignore_case`` as there."""
+    (``Engine.run_search``, ``search_text``).  ``glob`` and ``ignore_case`` as there.
+    ``show=N`` is refused like a phrase: the shown lines come from the text."""
     queries, flags, windows, exclude = _search_args(queries, mode, within, exclude)
     return self._search(queries, flags, rank, bool(wildcard), windows, exclude, bool(glob),
-                        bool(ignore_case))
+                        bool(ignore_case), show)
 
 
 _C.IndexResult.search = _index_search
@@ -121,7 +122,8 @@ class Engine:
         return self._eng.run_index(text, first_line)
 
     def run_search(self, text: bytes, queries, mode="all", first_line: int = 0, rank=None,
-                   wildcard=False, within=None, exclude=None, glob=False, ignore_case=False):
+                   wildcard=False, within=None, exclude=None, glob=False, ignore_case=False,
+                   show=None):
         """WordCount of ``text``, its inverted index, and a batch of word queries answered
         from it (``SearchResult``).  ``queries`` is a list of term lists (1 to 8 byte-string
         terms each); ``mode`` is ``"all"`` (lines that hold every term), ``"any"`` (lines
@@ -173,28 +175,37 @@ class Engine:
         words -- (pattern terms) x (dictionary words) matcher calls per batch -- and their
         lists are merged on the device, counted in ``merged``.  A ranked batch with a pattern
         term takes ``emits_per_line <= 8192``: its lists may overlap, and a score reaches
-        ``32 * emits_per_line * 8``."""
+        ``32 * emits_per_line * 8``.
+
+        ``show=N`` (``1 <= N <= 65536``; ``None`` or ``0``: no show) also returns, for every
+        returned line, its first ``N`` bytes and the spans of its tokens that match one of the
+        query's own terms (``oracle.show`` states the rules): ``text(i)`` is the list of query
+        ``i``'s shown lines, ``spans(i)`` per line a list of ``(start, len, mask)`` with bit
+        ``j`` of ``mask`` set when the token matches term ``j``; ``cut_lines`` counts the lines
+        longer than ``N`` and ``format(mark=True)`` prints the lines with the spans between
+        ``>>`` and ``<<``.  On the GPU the lines and spans are gathered on the device from the
+        resident text (``show_ms``), and only they cross PCIe."""
         queries, flags, windows, exclude = _search_args(queries, mode, within, exclude)
         if self.cpu:
             return _C.cpu_run_search(self.cfg, text, queries, flags, first_line, rank,
                                      bool(wildcard), windows, exclude, bool(glob),
-                                     bool(ignore_case))
+                                     bool(ignore_case), show)
         return self._eng.run_search(text, queries, flags, first_line, rank, bool(wildcard),
-                                    windows, exclude, bool(glob), bool(ignore_case))
+                                    windows, exclude, bool(glob), bool(ignore_case), show)
 
     def search_resident(self, queries, mode="all", rank=None, wildcard=False, within=None,
-                        exclude=None, glob=False, ignore_case=False):
+                        exclude=None, glob=False, ignore_case=False, show=None):
         """Another batch from the index this engine's last job left on the device; that
         job must have been a ``run_index`` or a ``run_search`` (GPU engines only).  Every
         mode of ``run_search``: the job's text is resident too, so phrases and near queries
-        are answered.  ``rank``, ``within``, ``exclude``, ``glob`` and ``ignore_case`` as
-        ``run_search`` takes them."""
+        are answered.  ``rank``, ``within``, ``exclude``, ``glob``, ``ignore_case`` and ``show``
+        as ``run_search`` takes them."""
         if self.cpu:
             raise _C.LocustError("search_resident needs a GPU engine: the CPU engine keeps "
                                  "no index (use run_index(text).search(...))")
         queries, flags, windows, exclude = _search_args(queries, mode, within, exclude)
         return self._eng.search_resident(queries, flags, rank, bool(wildcard), windows, exclude,
-                                         bool(glob), bool(ignore_case))
+                                         bool(glob), bool(ignore_case), show)
 
     def top_counts(self, records: list[tuple[bytes, int]], k: int):
         """The selection alone over (key, count) records sorted by key with distinct
@@ -290,24 +301,25 @@ def index_file(path: str, line_start: int = -1, line_end: int = -1, backend: str
 
 def search_text(text: bytes, queries, mode="all", backend: str = "gpu", cfg=None,
                 first_line: int = 0, rank=None, wildcard=False, within=None, exclude=None,
-                glob=False, ignore_case=False, **kw):
+                glob=False, ignore_case=False, show=None, **kw):
     """All/any/phrase/near word queries over ``text`` (``SearchResult``); see
     ``Engine.run_search``."""
     cfg = cfg if cfg is not None else make_config(backend, **kw)
     nlines = text.count(b"\n") + (1 if text and not text.endswith(b"\n") else 0)
     return Engine(cfg, max(len(text), 1), max(nlines, 1)).run_search(
-        text, queries, mode, first_line, rank, wildcard, within, exclude, glob, ignore_case)
+        text, queries, mode, first_line, rank, wildcard, within, exclude, glob, ignore_case,
+        show)
 
 
 def search_file(path: str, queries, mode="all", line_start: int = -1, line_end: int = -1,
                 backend: str = "gpu", cfg=None, rank=None, wildcard=False, within=None,
-                exclude=None, glob=False, ignore_case=False, **kw):
+                exclude=None, glob=False, ignore_case=False, show=None, **kw):
     """All/any/phrase/near word queries over a file or its line window, answered with the file's
     own (global) line numbers."""
     cfg = cfg if cfg is not None else make_config(backend, **kw)
     text, nlines, first, _total = _C.load_lines(path, line_start, line_end, cfg.ref_compat)
     return Engine(cfg, max(len(text), 1), max(nlines, 1)).run_search(
-        text, queries, mode, first, rank, wildcard, within, exclude, glob, ignore_case)
+        text, queries, mode, first, rank, wildcard, within, exclude, glob, ignore_case, show)
 
 
 def map_stage(path: str, spill: str, line_start: int = -1, line_end: int = -1,

@@ -702,6 +702,93 @@ def format_ranked(queries, tops, matches, *, exclude=None) -> bytes:
         for q, t, m in zip(_query_text(queries, exclude), tops, matches))
 
 
+SHOW_MAX_BYTES = 65536
+
+SHOW_RULES = """
+    Show (``show=N``): the returned lines' text and match spans.
+
+    - ``N`` is an integer with 1 <= N <= 65536 (``ValueError`` otherwise).  Every returned line
+      of a query, in result order (unranked ascending; ranked the winners in rank order), is
+      one entry; the same line returned for two queries is two entries.
+    - text: the line's bytes from its start to its end -- the newline, the end of the input or
+      a NUL, where the tokeniser stops -- cut to the first ``N`` bytes.  ``cut`` counts the
+      entries whose line was longer than ``N``.
+    - spans: one ``(start, len, mask)`` for every emitted token of the line (one of its first
+      ``emits`` tokens) that matches at least one of the query's own terms, in token order.
+      ``start`` is the byte offset from the line's start, ``len`` the token's full length up to
+      the next delimiter or the line's end (cut neither to ``max_key`` nor to ``N``), ``mask``
+      bit ``j`` is set when the token matches term ``j``: the token's key, cut to ``max_key``,
+      equals a plain term, starts with a prefix term's bytes, or is matched by a pattern term,
+      with ``ignore_case`` folding ASCII letters.  A repeated term sets its own bit too.
+    - Exclusion terms never produce a span, a token past the emit cap produces nothing, and the
+      rule is the same in every mode: in a phrase or near query every token that matches a term
+      is a span, not only those of an occurrence or a window.
+"""
+
+
+def line_tokens(line: bytes, delims: bytes = DEFAULT_DELIMS, emits: int = 20):
+    """``(start, token)`` of the first ``emits`` tokens of one line, uncut; a NUL ends them."""
+    dset = set(delims)
+    out, at = [], None
+    for i, c in enumerate(line + b"\0"):
+        if c == 0 or c in dset:
+            if at is not None:
+                out.append((at, line[at:i]))
+                at = None
+            if c == 0:
+                break
+        elif at is None:
+            at = i
+    return out[:emits]
+
+
+def show(text: bytes, lines, terms, n: int, delims: bytes = DEFAULT_DELIMS, emits: int = 20,
+         max_key: int = 29, first_line: int = 0, *, wildcard: bool = False, glob: bool = False,
+         ignore_case: bool = False):
+    """What ``show=n`` adds to one query's answer ``lines`` (global numbers, in result order):
+    ``(texts, spans, cut)`` -- per entry the shown bytes and the ``(start, len, mask)`` list,
+    and the number of entries whose line was longer than ``n`` (``SHOW_RULES``).  ``terms`` are
+    the query's own terms, without its exclusion terms."""
+    if isinstance(n, bool) or not isinstance(n, int) or not 1 <= n <= SHOW_MAX_BYTES:
+        raise ValueError("show takes 1 <= N <= %d, not %r" % (SHOW_MAX_BYTES, n))
+    if len(text) >= 1 << 32:
+        raise ValueError("show takes a text of less than 2^32 bytes")
+    want = query_terms(list(terms), wildcard, glob, ignore_case, delims, max_key)
+    all_lines = split_lines(text)
+    texts, spans, cut = [], [], 0
+    for l in lines:
+        line = all_lines[l - first_line].split(b"\0", 1)[0]
+        cut += len(line) > n
+        texts.append(line[:n])
+        one = []
+        for start, tok in line_tokens(line, delims, emits):
+            mask = sum(1 << j for j, term in enumerate(want) if term.fits(tok[:max_key]))
+            if mask:
+                one.append((start, len(tok), mask))
+        spans.append(one)
+    return texts, spans, cut
+
+
+def format_show(first: bytes, lines, texts, spans=None, mark: bool = False) -> bytes:
+    """One query's part of the CLI's ``--search ... --show N`` output: ``first``, its
+    ``print query:`` line (``format_search`` / ``format_ranked`` of the query alone), then per
+    entry two spaces, the global line number, ``: `` and the shown bytes.  ``mark``: the part of
+    every span that lies inside the shown bytes stands between ``>>`` and ``<<``."""
+    out = [first]
+    for i, (l, t) in enumerate(zip(lines, texts)):
+        if mark:
+            parts, done = [], 0
+            for start, ln, _mask in spans[i]:
+                if start >= len(t):
+                    break
+                end = min(start + ln, len(t))
+                parts += [t[done:start], b">>", t[start:end], b"<<"]
+                done = end
+            t = b"".join(parts) + t[done:]
+        out.append(b"  %d: %s\n" % (l, t))
+    return b"".join(out)
+
+
 def format_gpu(entries) -> bytes:
     """The reference GPU build's result lines (main.cu:132)."""
     return b"".join(b"print key: %s \t val: %d \t count: %d\n" % (k, v, c) for k, v, c in entries)

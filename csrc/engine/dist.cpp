@@ -248,12 +248,15 @@ DistResult run_distributed_job(const DistConfig& cfg, Communicator& comm, ShardE
   // size) are identical everywhere without another collective.
   bool mapped = false;
   i32 st_slot = 0;
+  // (the root's merge is enqueued before any header is known: the shape must fit it now,
+  // the token total is checked against the headers below)
+  const u32 slot_recs = eng.slot_records ? eng.slot_records : kSlotRecordsMin;
   const bool slot_path = plan == DistStrategy::kGather && cfg.gather && cfg.job.combine &&
-                         cfg.strategy != DistStrategy::kShuffle && P <= kMaxSlotRanks &&
-                         comm.device_buffers() && eng.device_buffers();
+                         cfg.strategy != DistStrategy::kShuffle &&
+                         slot_merge_fits((u64)P, slot_recs, 0) && comm.device_buffers() &&
+                         eng.device_buffers();
   if (slot_path) {
     TraceRange tr("locust:slot_gather");
-    const u32 slot_recs = eng.slot_records ? eng.slot_records : kSlotRecordsMin;
     const u64 slot_bytes = ((u64)kSlotHeaderRecords + slot_recs) * sizeof(KeyCount);
     // One graph for the whole job when the collective can be captured (RCCL); every rank
     // enters the all-gather exactly once either way.
@@ -302,10 +305,11 @@ DistResult run_distributed_job(const DistConfig& cfg, Communicator& comm, ShardE
       if (hd[p].status == kSlotFailed)
         throw Error(std::string("distributed job failed in stage 'map' on rank ") +
                     std::to_string(p) + (p == me ? ": " + local_msg : ""));
-    u64 sum = 0, max_n = 0, min_cap = ~0ull;
+    u64 sum = 0, max_n = 0, min_cap = ~0ull, tokens = 0;
     bool fallback = false;
     for (int p = 0; p < P; ++p) {
       sum += hd[p].n;
+      tokens = hd[p].tokens > ~0ull - tokens ? ~0ull : tokens + hd[p].tokens;
       max_n = std::max(max_n, hd[p].n);
       min_cap = std::min(min_cap, hd[p].slot_cap);
       fallback |= hd[p].status != kSlotOk || hd[p].n > slot_recs;
@@ -316,6 +320,8 @@ DistResult run_distributed_job(const DistConfig& cfg, Communicator& comm, ShardE
     const u64 want = align_up(max_n + max_n / 16 + 1, 256);
     eng.slot_records = (u32)std::max<u64>(kSlotRecordsMin, std::min<u64>(want, min_cap));
     fallback |= cfg.strategy == DistStrategy::kAuto && sum > cfg.gather_max_records;
+    // more tokens than the merge's scan can count: its totals are not to be used
+    fallback |= !slot_merge_fits((u64)P, slot_recs, tokens);
     st_slot = local("map", [&] {
       n_local = eng.complete_map_slot(shard);
       eng.map_stats(&local_stats);

@@ -1,10 +1,13 @@
 // Stage-level entry points of the device-resident shuffle (locust/exch_stage.hpp): one
-// launch_* of exchange.hip / shuffle.hip per call, on plain device buffers of its own.
+// launch_* of exchange.hip / shuffle.hip / merge.hip per call, on plain device buffers of
+// its own.
 // Every size a kernel indexes by is checked here first, so no launch can leave its buffers.
 #include "locust/exch_stage.hpp"
 
 #include <algorithm>
 #include <cstring>
+#include <memory>
+#include <utility>
 
 #include "locust/hip_check.hpp"
 #include "locust/kernels.hpp"
@@ -310,6 +313,233 @@ ExchStageReport exch_stage_report(const std::vector<SlotHeader>& headers, u32 sl
   d_msg.download(&out.msg, 1);
   out.acc.resize(acc.size());
   d_acc.download(out.acc.data(), out.acc.size());
+  return out;
+}
+
+// ---- the shuffle tail (merge.hip) ----
+namespace {
+
+static_assert(sizeof(OutRecord) == sizeof(KeyCount), "output records read back as KeyCount");
+
+// Host image of the slot buffer: pattern bytes, then each slot's header and records.
+std::vector<KeyCount> slot_image(const std::vector<ExchStageMergeSlot>& slots, u32 slot_records) {
+  LOCUST_CHECK_ARG(slots.size() >= 1 && slots.size() <= (size_t)kMaxMergeRunsHost,
+                   "merge stage: 1..64 slots");
+  LOCUST_CHECK_ARG(slot_records >= 1 && (u64)slots.size() * slot_records <= kMergeMaxRecords,
+                   "merge stage: too many records to merge");
+  const u64 stride = (u64)kSlotHeaderRecords + slot_records;
+  std::vector<KeyCount> img(slots.size() * stride);
+  std::memset(img.data(), kExchStagePattern, img.size() * sizeof(KeyCount));
+  for (size_t q = 0; q < slots.size(); ++q) {
+    LOCUST_CHECK_ARG(slots[q].records.size() <= slot_records, "merge stage: slot overfilled");
+    // whatever its status: no reading of the header may take pattern bytes for records
+    LOCUST_CHECK_ARG(std::min<u64>(slots[q].header.n, slot_records) <= slots[q].records.size(),
+                     "merge stage: a header announces records the slot does not hold");
+    std::memcpy(&img[q * stride], &slots[q].header, sizeof(SlotHeader));
+    if (!slots[q].records.empty())
+      std::memcpy(&img[q * stride + kSlotHeaderRecords], slots[q].records.data(),
+                  slots[q].records.size() * sizeof(KeyCount));
+  }
+  return img;
+}
+
+// What the kernels will take as run q: the records of the image, pattern ones included.
+std::pair<const KeyCount*, u64> effective_run(const std::vector<KeyCount>& img, size_t q,
+                                              u32 slot_records) {
+  const u64 stride = (u64)kSlotHeaderRecords + slot_records;
+  SlotHeader h;
+  std::memcpy(&h, &img[q * stride], sizeof h);
+  const u64 len = h.status == kSlotOk ? std::min<u64>(h.n, slot_records) : 0;
+  return {&img[q * stride + kSlotHeaderRecords], len};
+}
+
+u64 distinct_keys(const std::vector<KeyCount>& img, size_t nslots, u32 slot_records) {
+  std::vector<PackedKey> keys;
+  for (size_t q = 0; q < nslots; ++q) {
+    const auto run = effective_run(img, q, slot_records);
+    for (u64 i = 0; i < run.second; ++i) {
+      PackedKey k;
+      std::memcpy(k.w, run.first[i].w, sizeof k.w);
+      keys.push_back(k);
+    }
+  }
+  std::sort(keys.begin(), keys.end(), key_less);
+  return (u64)(std::unique(keys.begin(), keys.end(),
+                           [](const PackedKey& a, const PackedKey& b) {
+                             return key_compare(a.w, b.w) == 0;
+                           }) - keys.begin());
+}
+
+struct MergeScratch {  // merged array + look-back words + tile counter, pattern-filled
+  DevBuf<KeyCount> merged;
+  DevBuf<u64> status;
+  DevBuf<u32> tile;
+  explicit MergeScratch(u64 cap) : merged(cap), status(merge_scratch_words(cap)), tile(1) {
+    merged.fill(kExchStagePattern);
+    status.fill(kExchStagePattern);
+    tile.fill(kExchStagePattern);
+  }
+  LookbackScratch lb() { return LookbackScratch{status.p, tile.p}; }
+};
+
+ExchStageCtr stage_ctr(const MapCounters& c) {
+  ExchStageCtr o;
+  o.num_records = c.num_records;
+  o.num_unique = c.num_unique;
+  o.total_count = c.total_count;
+  return o;
+}
+
+}  // namespace
+
+ExchStageMerge exch_stage_merge_slots(const std::vector<ExchStageMergeSlot>& slots,
+                                      u32 slot_records) {
+  const std::vector<KeyCount> img = slot_image(slots, slot_records);
+  const u32 nslots = (u32)slots.size();
+  const u64 cap = (u64)nslots * slot_records;
+  // The count sum is "checked by the caller" (the emit's look-back value holds 40 bits of
+  // it).  Summed over every record given, also those no run holds: whatever subset a merge
+  // reads, its scan cannot carry into the record count it places the output by.
+  u64 sum = 0;
+  for (const ExchStageMergeSlot& sl : slots)
+    for (const KeyCount& r : sl.records) {
+      LOCUST_CHECK_ARG(r.count <= kMergeMaxCount && sum + r.count <= kMergeMaxCount,
+                       "merge stage: count sum too large to merge");
+      sum += r.count;
+    }
+  constexpr u64 kGuard = 128;  // output records behind the last one the merge may write
+  DevBuf<KeyCount> d_slots(img.size());
+  d_slots.upload(img.data(), img.size());
+  MergeScratch scratch(cap);
+  // (the emit sums whatever counts lie in `merged`: zeros, so that a slot the rank kernel
+  // left unwritten is skipped like a duplicate and shows as a missing record)
+  scratch.merged.fill(0);
+  DevBuf<MapCounters> d_ctr(1), d_ctr_out(1);
+  d_ctr.fill(kExchStagePattern);
+  d_ctr_out.fill(kExchStagePattern);
+  DevBuf<OutRecord> d_out(cap + kGuard);
+  d_out.fill(kExchStagePattern);
+  DevBuf<SlotHeader> d_hdr(nslots);
+  d_hdr.fill(kExchStagePattern);
+  launch_merge_slots(d_slots.p, nslots, slot_records, scratch.merged.p, d_ctr.p, d_out.p,
+                     d_ctr_out.p, scratch.lb(), d_hdr.p, nullptr);
+  sync();
+  ExchStageMerge r;
+  MapCounters c;
+  d_ctr.download(&c, 1);
+  r.ctr = stage_ctr(c);
+  d_ctr_out.download(&c, 1);
+  r.ctr_out = stage_ctr(c);
+  r.headers.resize(nslots);
+  d_hdr.download(r.headers.data(), nslots);
+  std::vector<KeyCount> all(cap + kGuard);
+  d_out.download(reinterpret_cast<OutRecord*>(all.data()), all.size());
+  const u64 held = std::min<u64>(r.ctr.num_unique, cap);
+  r.tail_intact = all_pattern(reinterpret_cast<const char*>(all.data() + held),
+                              (all.size() - held) * sizeof(KeyCount));
+  all.resize(held);
+  r.out = std::move(all);
+  return r;
+}
+
+ExchStageRank exch_stage_rank_slots(const std::vector<ExchStageMergeSlot>& slots,
+                                    u32 slot_records) {
+  const std::vector<KeyCount> img = slot_image(slots, slot_records);
+  const u32 nslots = (u32)slots.size();
+  const u64 cap = (u64)nslots * slot_records;
+  DevBuf<KeyCount> d_slots(img.size());
+  d_slots.upload(img.data(), img.size());
+  MergeScratch scratch(cap);
+  DevBuf<u64> d_acc(3 * kMergeAccSpread);
+  d_acc.fill(0);
+  launch_merge_rank_slots(d_slots.p, nslots, slot_records, scratch.merged.p, d_acc.p, scratch.lb(),
+                          nullptr);
+  sync();
+  ExchStageRank r;
+  r.merged.resize(cap);
+  scratch.merged.download(r.merged.data(), cap);
+  r.acc.resize(3 * kMergeAccSpread);
+  d_acc.download(r.acc.data(), r.acc.size());
+  return r;
+}
+
+std::vector<ExchStageEmit> exch_stage_emit_compact(const std::vector<ExchStageEmitJob>& jobs,
+                                                   u32 slot_records, bool use_root_region,
+                                                   u64 root_region, u64 region, u32 regions,
+                                                   u64 region_records, u32 me,
+                                                   u32 gather_records, u64 seq) {
+  LOCUST_CHECK_ARG(jobs.size() >= 1 && jobs.size() <= 4, "merge stage: 1..4 jobs");
+  const u32 P = (u32)jobs[0].msg3.size();
+  LOCUST_CHECK_ARG(P >= 1 && P <= kExchMaxRanks, "exchange: bad shape");
+  LOCUST_CHECK_ARG(me < P, "merge stage: this rank is not one of the P ranks");
+  LOCUST_CHECK_ARG(regions <= 1024 && region_records <= kMergeMaxRecords,
+                   "merge stage: output too large");
+  std::vector<std::vector<KeyCount>> imgs;
+  u64 cap = 0;
+  for (const ExchStageEmitJob& j : jobs) {
+    LOCUST_CHECK_ARG(j.msg3.size() == P, "merge stage: every job needs P reports");
+    imgs.push_back(slot_image(j.slots, slot_records));
+    cap = std::max<u64>(cap, (u64)j.slots.size() * slot_records);
+    // an accepted emit writes the first copies behind the lower ranks' records and trusts
+    // its own report for their number: it must cover them, or the range leaves its region
+    LOCUST_CHECK_ARG(distinct_keys(imgs.back(), j.slots.size(), slot_records) <= j.msg3[me].n_out,
+                     "merge stage: the report must cover the merged range");
+  }
+  // the guard: a region more and five words per merged slot -- an emit into region
+  // `regions`, or of every slot, neither of which may happen, would still land in dst
+  const u64 guard = (region_records + cap) * kOutWords + kExchStageEmitGuard;
+  const u64 dst_words = (u64)regions * region_records * kOutWords + guard;
+  const size_t J = jobs.size();
+  std::vector<std::unique_ptr<DevBuf<KeyCount>>> d_slots;
+  std::vector<std::unique_ptr<DevBuf<ExchMsg3>>> d_msg3;
+  std::vector<std::unique_ptr<DevBuf<u64>>> d_dst, d_stamps, d_acc_snap;
+  DevBuf<u32> d_done(1), d_done_snap(J);
+  d_done.fill(0);
+  d_done_snap.fill(kExchStagePattern);
+  for (size_t j = 0; j < J; ++j) {
+    d_slots.emplace_back(new DevBuf<KeyCount>(imgs[j].size()));
+    d_slots.back()->upload(imgs[j].data(), imgs[j].size());
+    d_msg3.emplace_back(new DevBuf<ExchMsg3>(P));
+    d_msg3.back()->upload(jobs[j].msg3.data(), P);
+    d_dst.emplace_back(new DevBuf<u64>(dst_words));
+    d_dst.back()->fill(kExchStagePattern);
+    d_stamps.emplace_back(new DevBuf<u64>(P));
+    d_stamps.back()->fill(kExchStagePattern);
+    d_acc_snap.emplace_back(new DevBuf<u64>(3 * kMergeAccSpread));
+  }
+  ExchMsg1 root{};
+  root.out_region = root_region;
+  DevBuf<ExchMsg1> d_root(1);
+  d_root.upload(&root, 1);
+  MergeScratch scratch(cap);
+  DevBuf<u64> d_acc(3 * kMergeAccSpread);
+  for (size_t j = 0; j < J; ++j) {
+    const u32 nslots = (u32)jobs[j].slots.size();
+    LOCUST_HIP_CHECK(hipMemsetAsync(d_acc.p, 0, 3 * kMergeAccSpread * sizeof(u64), nullptr));
+    launch_merge_rank_slots(d_slots[j]->p, nslots, slot_records, scratch.merged.p, d_acc.p,
+                            scratch.lb(), nullptr);
+    launch_merge_emit_compact(d_slots[j]->p, nslots, slot_records, scratch.merged.p, d_msg3[j]->p,
+                              use_root_region ? d_root.p : nullptr, region, regions,
+                              region_records, P, me, gather_records, d_dst[j]->p, d_stamps[j]->p,
+                              seq + j, d_done.p, scratch.lb(), nullptr);
+    LOCUST_HIP_CHECK(hipMemcpyAsync(d_done_snap.p + j, d_done.p, sizeof(u32),
+                                    hipMemcpyDeviceToDevice, nullptr));
+    LOCUST_HIP_CHECK(hipMemcpyAsync(d_acc_snap[j]->p, d_acc.p, 3 * kMergeAccSpread * sizeof(u64),
+                                    hipMemcpyDeviceToDevice, nullptr));
+  }
+  sync();
+  std::vector<u32> done(J);
+  d_done_snap.download(done.data(), J);
+  std::vector<ExchStageEmit> out(J);
+  for (size_t j = 0; j < J; ++j) {
+    out[j].dst.resize(dst_words);
+    d_dst[j]->download(out[j].dst.data(), dst_words);
+    out[j].stamps.resize(P);
+    d_stamps[j]->download(out[j].stamps.data(), P);
+    out[j].done = done[j];
+    out[j].acc.resize(3 * kMergeAccSpread);
+    d_acc_snap[j]->download(out[j].acc.data(), out[j].acc.size());
+  }
   return out;
 }
 

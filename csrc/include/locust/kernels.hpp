@@ -419,8 +419,7 @@ void launch_merge_sorted_runs(const KeyCount* own, const KeyCount* recv, const u
 void launch_merge_slots(const KeyCount* slots, u32 nslots, u32 slot_records, KeyCount* merged,
                         MapCounters* ctr, OutRecord* out, MapCounters* ctr_out,
                         LookbackScratch lb, SlotHeader* hdr_out, hipStream_t s);
-constexpr u64 kMergeMaxRecords = (1ull << 22) - 1;
-constexpr u64 kMergeMaxCount = (1ull << 40) - 1;
+// (kMergeMaxRecords, kMergeMaxCount: locust/slot.hpp)
 
 // Hash every token (with its count; null = 1) into the table; distinct keys land in
 // ukeys[0 .. ctr->num_unique) with summed counts in ucount.

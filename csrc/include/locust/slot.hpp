@@ -27,5 +27,16 @@ constexpr i32 kSlotOk = 0, kSlotFailed = 1, kSlotRedo = 2;
 constexpr u32 kSlotRecordsMin = 2048;
 // Most ranks the one-all-gather gather strategy merges (the merge kernels' run table).
 constexpr int kMaxSlotRanks = 64;
+// What the merge kernels can take: their look-back value holds 22 bits of distinct keys
+// and 40 bits of counts.  Checked by whoever launches them.
+constexpr u64 kMergeMaxRecords = (1ull << 22) - 1;
+constexpr u64 kMergeMaxCount = (1ull << 40) - 1;
+// Whether the root may merge `nslots` all-gathered slots of `slot_records` records whose
+// headers announce `tokens` tokens in all (0 before the headers are known: the shape
+// alone).  Otherwise the job takes the standard path.
+inline bool slot_merge_fits(u64 nslots, u64 slot_records, u64 tokens) {
+  return nslots <= (u64)kMaxSlotRanks && slot_records <= kMergeMaxRecords &&
+         nslots * slot_records <= kMergeMaxRecords && tokens <= kMergeMaxCount;
+}
 
 }  // namespace locust

@@ -800,6 +800,36 @@ py::dict exch_plan_dict(const ExchStagePlan& p, u32 P) {
   return d;
 }
 
+// A slot of the shuffle tail's stage entry points: (80 header bytes, key blob, counts).
+using PyMergeSlot = std::tuple<std::string, std::string, std::vector<u64>>;
+std::vector<ExchStageMergeSlot> merge_slots_from(const std::vector<PyMergeSlot>& slots) {
+  std::vector<ExchStageMergeSlot> out(slots.size());
+  for (size_t q = 0; q < slots.size(); ++q) {
+    const std::string& h = std::get<0>(slots[q]);
+    LOCUST_CHECK_ARG(h.size() == sizeof(SlotHeader), "a slot header holds 80 bytes");
+    std::memcpy(&out[q].header, h.data(), sizeof(SlotHeader));
+    out[q].records = records_from(std::get<1>(slots[q]), std::get<2>(slots[q]));
+  }
+  return out;
+}
+std::vector<u64> counts_of(const std::vector<KeyCount>& recs) {
+  std::vector<u64> c(recs.size());
+  for (size_t i = 0; i < c.size(); ++i) c[i] = recs[i].count;
+  return c;
+}
+// A report of the compact emit's stage entry point: (status, flags, n_out).
+using PyMsg3 = std::tuple<i32, u32, u64>;
+std::vector<ExchMsg3> msg3_from(const std::vector<PyMsg3>& in) {
+  std::vector<ExchMsg3> out(in.size());
+  for (size_t q = 0; q < in.size(); ++q) {
+    out[q] = ExchMsg3{};
+    out[q].status = std::get<0>(in[q]);
+    out[q].flags = std::get<1>(in[q]);
+    out[q].n_out = std::get<2>(in[q]);
+  }
+  return out;
+}
+
 }  // namespace
 
 PYBIND11_MODULE(_locust, m) {
@@ -1545,6 +1575,89 @@ PYBIND11_MODULE(_locust, m) {
   }, py::arg("headers"), py::arg("slot_records"), py::arg("flags"), py::arg("max_bucket"),
         py::arg("acc"), py::arg("gather_records"),
         "launch_exch_report over P received (status, n) slot headers.");
+  m.attr("MERGE_MAX_RECORDS") = kMergeMaxRecords;
+  m.attr("MERGE_MAX_COUNT") = kMergeMaxCount;
+  m.attr("MAX_SLOT_RANKS") = kMaxSlotRanks;
+  m.def("slot_merge_fits", &slot_merge_fits, py::arg("nslots"), py::arg("slot_records"),
+        py::arg("tokens"),
+        "Whether the gather strategy's root may merge this many all-gathered slots holding "
+        "this many tokens (slot.hpp; no GPU); otherwise the job takes the standard path.");
+  m.def("exch_merge_slots", [](const std::vector<PyMergeSlot>& slots, u32 slot_records) {
+    const std::vector<ExchStageMergeSlot> in = merge_slots_from(slots);
+    ExchStageMerge r;
+    {
+      py::gil_scoped_release nogil;
+      r = exch_stage_merge_slots(in, slot_records);
+    }
+    py::dict d;
+    d["keys"] = blob_from_keys(r.out.data(), r.out.size());
+    d["counts"] = counts_of(r.out);
+    d["ctr"] = py::make_tuple(r.ctr.num_records, r.ctr.num_unique, r.ctr.total_count);
+    d["ctr_out"] = py::make_tuple(r.ctr_out.num_records, r.ctr_out.num_unique,
+                                  r.ctr_out.total_count);
+    py::list hs;
+    for (const SlotHeader& h : r.headers)
+      hs.append(py::bytes(reinterpret_cast<const char*>(&h), sizeof h));
+    d["headers"] = hs;
+    d["tail_intact"] = r.tail_intact;
+    return d;
+  }, py::arg("slots"), py::arg("slot_records"),
+        "launch_merge_slots over (header bytes, keys, counts) slots: the output records, "
+        "(num_records, num_unique, total_count) of ctr and ctr_out, the copied headers.");
+  m.def("exch_rank_slots", [](const std::vector<PyMergeSlot>& slots, u32 slot_records) {
+    const std::vector<ExchStageMergeSlot> in = merge_slots_from(slots);
+    ExchStageRank r;
+    {
+      py::gil_scoped_release nogil;
+      r = exch_stage_rank_slots(in, slot_records);
+    }
+    py::dict d;
+    d["keys"] = blob_from_keys(r.merged.data(), r.merged.size());
+    d["counts"] = counts_of(r.merged);
+    d["acc"] = r.acc;
+    return d;
+  }, py::arg("slots"), py::arg("slot_records"),
+        "launch_merge_rank_slots: the whole merged array and the accumulator triples.");
+  m.def("exch_emit_compact", [](const std::vector<PyMergeSlot>& slots, u32 slot_records,
+                                const std::vector<PyMsg3>& msg3_all, const py::object& root_region,
+                                u64 region, u32 regions, u64 region_records, u32 me,
+                                u32 gather_records, u64 seq, int jobs, const py::object& slots2,
+                                const py::object& msg3_all2) {
+    LOCUST_CHECK_ARG(jobs == 1 || jobs == 2, "merge stage: 1 or 2 jobs");
+    std::vector<ExchStageEmitJob> in(jobs);
+    in[0].slots = merge_slots_from(slots);
+    in[0].msg3 = msg3_from(msg3_all);
+    if (jobs == 2) {
+      LOCUST_CHECK_ARG(!slots2.is_none() && !msg3_all2.is_none(),
+                       "merge stage: the second job needs slots2 and msg3_all2");
+      in[1].slots = merge_slots_from(slots2.cast<std::vector<PyMergeSlot>>());
+      in[1].msg3 = msg3_from(msg3_all2.cast<std::vector<PyMsg3>>());
+    }
+    const bool use_root = !root_region.is_none();
+    const u64 root = use_root ? root_region.cast<u64>() : 0;
+    std::vector<ExchStageEmit> r;
+    {
+      py::gil_scoped_release nogil;
+      r = exch_stage_emit_compact(in, slot_records, use_root, root, region, regions,
+                                  region_records, me, gather_records, seq);
+    }
+    py::list out;
+    for (const ExchStageEmit& e : r) {
+      py::dict d;
+      d["dst"] = e.dst;
+      d["stamps"] = e.stamps;
+      d["done"] = e.done;
+      d["acc"] = e.acc;
+      out.append(d);
+    }
+    return out;
+  }, py::arg("slots"), py::arg("slot_records"), py::arg("msg3_all"), py::arg("root_region"),
+        py::arg("region"), py::arg("regions"), py::arg("region_records"), py::arg("me"),
+        py::arg("gather_records"), py::arg("seq"), py::arg("jobs") = 1,
+        py::arg("slots2") = py::none(), py::arg("msg3_all2") = py::none(),
+        "launch_merge_rank_slots + launch_merge_emit_compact per job (the second on slots2 / "
+        "msg3_all2, seq + 1, the same scratch): per job dst (with its guard), stamps, done "
+        "and the accumulators.  msg3_all: (status, flags, n_out) per rank.");
   m.def("write_spill",
         [](const std::string& path, const std::vector<std::pair<std::string, u64>>& recs,
            const std::string& fmt) {

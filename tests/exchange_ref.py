@@ -21,6 +21,26 @@ Written from the documented rules, in exact integer arithmetic (Python ints, no 
 A key is its 32-byte packed form: the key's bytes (no NUL, at most 31) padded with NULs,
 which is the big-endian image of the four packed u64 words, so ``bytes`` comparison is the
 packed comparison.
+
+The shuffle's tail (csrc/kernels/merge.hip), from the rules in kernels.hpp, slot.hpp and the
+format comment of kv.hpp:
+
+* a slot is (status, n, records); its run is empty unless the status is ok, else its first
+  ``min(n, slot_records)`` records.  A run is a list of (key, count), ascending and distinct;
+* the merged array holds every record of every run in stable (key, run index) order; the
+  first copy of a key carries the key's count summed over all runs, every later copy 0;
+* the output is the first copies in that order; the counters are the number of records, of
+  distinct keys and the count total (every count is at least 1);
+* the accumulators sum to (distinct keys, count total, words of the compact records);
+* a compact record of (key, count), kb = the key's length: count < 2^24 -> one word [key
+  bytes 0-3 : 32][count : 24][0][kb : 6][0] (high to low) and ceil((kb - 4) / 8) words of the
+  key bytes from 4 on; otherwise one word [count : 56][0][kb : 6][1] and ceil(kb / 8) words of
+  the key; key bytes big-endian, NUL padded;
+* the compact emit of rank ``me`` refuses (writes nothing) when any rank's report has a
+  status or a flag, when its own n_out exceeds gather_records, when the region is not below
+  ``regions``, or when r + n_out[me] exceeds region_records, r being the lower ranks' n_out,
+  each clamped to gather_records; else its records start at word
+  5 (region x region_records + r).
 """
 from bisect import bisect_left
 
@@ -130,3 +150,97 @@ def report(headers, slot_records, ctl_flags, max_bucket, acc, gather_records):
     return {"status": 0, "flags": flags, "max_bucket": max_bucket, "n_out": n_out,
             "total": 0 if dead else sum(acc[1::3]),
             "out_words": 0 if dead else sum(acc[2::3])}
+
+
+# ---- the shuffle's tail: slot merge, accumulators, compact emit ----
+
+OUT_WORDS = 5              # 8-B words of a 40-B output record
+COMPACT_SHORT_MAX = (1 << 24) - 1
+MERGE_MAX_RECORDS, MERGE_MAX_COUNT = (1 << 22) - 1, (1 << 40) - 1
+ACC_SPREAD = 64
+REFUSED = "refused"
+
+
+def pad32(key: bytes) -> bytes:
+    """As pad(), for keys of up to 32 bytes (a key of 32 fills all four words)."""
+    assert 1 <= len(key) <= KEY_BYTES and b"\0" not in key, key
+    return key.ljust(KEY_BYTES, b"\0")
+
+
+def slot_runs(slots, slot_records):
+    """The effective runs of (status, n, records) slots."""
+    runs = []
+    for status, n, records in slots:
+        held = min(n, slot_records) if status == SLOT_OK else 0
+        assert held <= len(records), "the slot does not hold what its header announces"
+        runs.append(list(records[:held]))
+    return runs
+
+
+def _totals(runs):
+    tot = {}
+    for run in runs:
+        assert [k for k, _ in run] == sorted({k for k, _ in run}), "a run ascends, distinct"
+        for k, c in run:
+            tot[k] = tot.get(k, 0) + c
+    return tot
+
+
+def merged_ref(runs):
+    """The merged array: (key, count) in stable (key, run) order, the sum on the first copy."""
+    tot = _totals(runs)
+    order = sorted((k, q) for q, run in enumerate(runs) for k, _ in run)
+    out, seen = [], set()
+    for k, _q in order:
+        out.append((k, 0 if k in seen else tot[k]))
+        seen.add(k)
+    return out
+
+
+def merge_out_ref(runs):
+    """(output records, (num_records, num_unique, total_count))."""
+    tot = _totals(runs)
+    recs = sorted(tot.items())
+    return recs, (sum(len(r) for r in runs), len(recs), sum(tot.values()))
+
+
+def compact_words_ref(key: bytes, count: int) -> int:
+    kb = len(key.rstrip(b"\0"))
+    if count <= COMPACT_SHORT_MAX:
+        return 1 + (-(-(kb - 4) // 8) if kb > 4 else 0)
+    return 1 + -(-kb // 8)
+
+
+def compact_record_ref(key: bytes, count: int):
+    """kv.hpp's compact record, written independently: short form (count < 2^24) packs key
+    bytes 0-3 into the header word, then key bytes 4.. in 8-byte words; long form keeps a
+    56-bit count and the packed key words."""
+    kb = len(key.rstrip(b"\0"))
+    if count < (1 << 24):
+        head = (int.from_bytes(key[:4].ljust(4, b"\0"), "big") << 32) | (count << 8) | (kb << 1)
+        rest = key[4:kb]
+        extra = [int.from_bytes(rest[i:i + 8].ljust(8, b"\0"), "big") for i in range(0, len(rest), 8)]
+        return [head] + extra
+    full = key.ljust(KEY_BYTES, b"\0")
+    w = [int.from_bytes(full[8 * j:8 * j + 8], "big") for j in range(4)]
+    return [(count << 8) | (kb << 1) | 1] + w[:(kb + 7) // 8]
+
+
+def acc_ref(runs):
+    """(firsts, tokens, words): what the 64 accumulator triples sum to."""
+    recs, (_n, uniq, total) = merge_out_ref(runs)
+    return uniq, total, sum(compact_words_ref(k, c) for k, c in recs)
+
+
+def emit_ref(runs, msg3_all, region, regions, region_records, me, gather_records):
+    """REFUSED, or (first word, the words) of rank me's compact emit.  msg3_all: (status,
+    flags, n_out) of every rank; region: the one in force (the host's or the root's)."""
+    n = msg3_all[me][2]
+    r = sum(min(n_out, gather_records) for _st, _fl, n_out in msg3_all[:me])
+    if (any(st != 0 or fl != 0 for st, fl, _n in msg3_all) or n > gather_records
+            or region >= regions or r + n > region_records):
+        return REFUSED
+    words = []
+    for k, c in merge_out_ref(runs)[0]:
+        words += compact_record_ref(k, c)
+    return OUT_WORDS * (region * region_records + r), words

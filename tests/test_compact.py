@@ -4,31 +4,12 @@ per virtual partition, and EntryList decodes them on the fly.  Here: the host de
 hand-built segments against the packed-key oracle; the GPU twin (the kernels' own compact
 output byte-identical to the CPU engine, and the wire bytes it saves) is
 tests/test_gpu_engine.py::test_compact_output_*."""
-import struct
-
 import pytest
 
 import locust_amd as lc
 from locust_amd.utils import oracle
 
-
-def _pack(key: bytes):
-    key = key.ljust(32, b"\0")
-    return [struct.unpack(">Q", key[8 * j:8 * j + 8])[0] for j in range(4)]
-
-
-def _record(key: bytes, count: int):
-    """kv.hpp's compact record, written independently: short form (count < 2^24) packs key
-    bytes 0-3 into the header word, then key bytes 4.. in 8-byte words; long form keeps a
-    56-bit count and the packed key words."""
-    kb = len(key.rstrip(b"\0"))
-    if count < (1 << 24):
-        head = (int.from_bytes(key[:4].ljust(4, b"\0"), "big") << 32) | (count << 8) | (kb << 1)
-        rest = key[4:kb]
-        extra = [int.from_bytes(rest[i:i + 8].ljust(8, b"\0"), "big") for i in range(0, len(rest), 8)]
-        return [head] + extra
-    w = _pack(key)
-    return [(count << 8) | (kb << 1) | 1] + w[:(kb + 7) // 8]
+from exchange_ref import compact_record_ref as _record  # (lived here before)
 
 
 def test_decode_segments_with_gaps_and_empty():

@@ -190,3 +190,112 @@ def test_reference_report_by_hand():
     assert ref.report([(ref.SLOT_REDO, 1)], 4, 0, 7, acc, 3)["flags"] == ref.RECV_TRUNCATED
     dead = ref.report(ok, 4, ref.ABORT, 7, acc, 0)
     assert (dead["flags"], dead["n_out"], dead["total"], dead["out_words"]) == (ref.ABORT, 0, 0, 0)
+
+
+# ---- the tail's reference: slot runs, merge, accumulators, compact records, emit ----
+
+A, B, Cc, D = K(b"a"), K(b"b"), K(b"c"), K(b"d")
+RUNS = [[(A, 1), (Cc, 2)], [(A, 10), (B, 20), (Cc, 30)], [(Cc, 100), (D, 5)]]
+
+
+def test_tail_constants_match_the_headers():
+    assert (ref.MERGE_MAX_RECORDS, ref.MERGE_MAX_COUNT) == (C.MERGE_MAX_RECORDS, C.MERGE_MAX_COUNT)
+    assert ref.MAX_RANKS == C.MAX_SLOT_RANKS
+    assert ref.pad32(b"x" * 32) == b"x" * 32 and ref.pad32(b"x") == ref.pad(b"x")
+
+
+def test_reference_slot_runs_by_hand():
+    """slot_records = 3.  Only an ok slot counts, by min(n, 3): a failed and a redone slot
+    with records are empty, n = 2 hides the third record, n = 4 and n = 2^40 clamp to 3."""
+    recs = [(A, 1), (B, 2), (Cc, 3)]
+    slots = [(ref.SLOT_OK, 2, recs), (ref.SLOT_FAILED, 2, recs), (ref.SLOT_REDO, 1, recs),
+             (ref.SLOT_OK, 4, recs), (ref.SLOT_OK, 1 << 40, recs), (ref.SLOT_OK, 0, recs),
+             (ref.SLOT_OK, 3, recs)]
+    assert ref.slot_runs(slots, 3) == [recs[:2], [], [], recs, recs, [], recs]
+
+
+def test_reference_merge_by_hand():
+    """a: runs 0, 1 (1 + 10); b: run 1; c: runs 0, 1, 2 (2 + 30 + 100); d: run 2."""
+    assert ref.merged_ref(RUNS) == [(A, 11), (A, 0), (B, 20), (Cc, 132), (Cc, 0), (Cc, 0), (D, 5)]
+    assert ref.merge_out_ref(RUNS) == ([(A, 11), (B, 20), (Cc, 132), (D, 5)], (7, 4, 168))
+    assert ref.acc_ref(RUNS) == (4, 168, 4)  # four one-byte keys: one word each
+    # empty runs anywhere change nothing; no run at all gives nothing
+    assert ref.merged_ref([[], RUNS[0], [], RUNS[1], RUNS[2], []]) == ref.merged_ref(RUNS)
+    assert ref.merge_out_ref([[], []]) == ([], (0, 0, 0)) and ref.acc_ref([[]]) == (0, 0, 0)
+    # no key shared: the runs interleave, every count its own
+    two = [[(A, 1), (Cc, 3)], [(B, 2), (D, 1 << 32)]]
+    assert ref.merged_ref(two) == [(A, 1), (B, 2), (Cc, 3), (D, 1 << 32)]
+    assert ref.acc_ref(two) == (4, 6 + (1 << 32), 1 + 1 + 1 + 2)  # d takes the long form
+
+
+def test_reference_compact_records_by_hand():
+    """Short: [key bytes 0-3][count : 24][0][kb : 6][0].  'ab' x 3: 0x6162_0000, 3 << 8,
+    2 << 1.  'abcdef' x 5: bytes 4-5 'ef' open a second word.  Long, 'abcde' x 2^24:
+    2^24 << 8 | 5 << 1 | 1, then the packed key word."""
+    assert ref.compact_record_ref(b"ab", 3) == [0x6162000000000304]
+    assert ref.compact_record_ref(b"abcdef", 5) == [0x616263640000050C, 0x6566000000000000]
+    assert ref.compact_record_ref(b"abcde", 1 << 24) == [0x10000000B, 0x6162636465000000]
+    assert ref.compact_record_ref(K(b"ab"), 3) == [0x6162000000000304]  # padded or not
+    words = {(1, 1): 1, (4, 1): 1, (5, 1): 2, (12, 1): 2, (13, 1): 3, (20, 1): 3, (21, 1): 4,
+             (28, 1): 4, (29, 1): 5, (32, 1): 5, (4, (1 << 24) - 1): 1,
+             (1, 1 << 24): 2, (8, 1 << 24): 2, (9, 1 << 24): 3, (16, 1 << 40): 3,
+             (17, 1 << 40): 4, (24, 1 << 24): 4, (25, 1 << 24): 5, (32, 1 << 40): 5}
+    for (kb, count), want in words.items():
+        key = ref.pad32(b"k" * kb)
+        assert ref.compact_words_ref(key, count) == want, (kb, count)
+        assert len(ref.compact_record_ref(key, count)) == want, (kb, count)
+
+
+def test_reference_emit_by_hand():
+    """Three ranks with ranges of 3, 4 and 9 keys, gather_records = 4, regions of 10 records.
+    Rank 1 in region 1: r = 3, 3 + 4 <= 10, first word 5 (10 + 3) = 65.  Rank 2: its own
+    9 > 4 is refused; with gather_records = 9, r = 7 and 7 + 9 > 10 is refused, 7 + 3 fits."""
+    m = [(0, 0, 3), (0, 0, 4), (0, 0, 9)]
+    words = [(0x61 << 56) | (11 << 8) | 2, (0x62 << 56) | (20 << 8) | 2,
+             (0x63 << 56) | (132 << 8) | 2, (0x64 << 56) | (5 << 8) | 2]
+    assert ref.emit_ref(RUNS, m, 1, 2, 10, 1, 4) == (65, words)
+    assert ref.emit_ref(RUNS, m, 0, 2, 10, 0, 4) == (0, words)
+    assert ref.emit_ref(RUNS, m, 0, 1, 10, 2, 4) == ref.REFUSED
+    assert ref.emit_ref(RUNS, m, 0, 1, 10, 2, 9) == ref.REFUSED
+    assert ref.emit_ref(RUNS, m[:2] + [(0, 0, 3)], 0, 1, 10, 2, 9) == (35, words)
+    assert ref.emit_ref(RUNS, m[:2] + [(0, 0, 4)], 0, 1, 10, 2, 9) == ref.REFUSED
+    # a lower rank's n_out above gather_records counts as gather_records
+    assert ref.emit_ref(RUNS, [(0, 0, 50), (0, 0, 4)], 0, 1, 10, 1, 4) == (20, words)
+    # the region must exist; any status, any flag, of any rank refuses
+    assert ref.emit_ref(RUNS, m, 2, 2, 10, 1, 4) == ref.REFUSED
+    assert ref.emit_ref(RUNS, [(0, 0, 3), (0, 0, 4), (1, 0, 9)], 1, 2, 10, 1, 4) == ref.REFUSED
+    assert ref.emit_ref(RUNS, [(0, 16, 3), (0, 0, 4), (0, 0, 9)], 1, 2, 10, 1, 4) == ref.REFUSED
+    # nothing merged: accepted, no words
+    assert ref.emit_ref([[], []], [(0, 0, 0)], 0, 1, 10, 0, 4) == (0, [])
+
+
+@pytest.mark.parametrize("count", [1, (1 << 24) - 1, 1 << 24, (1 << 40) - 1])
+def test_reference_compact_records_decode(count):
+    """Every key length through the host decoder (Result.from_compact)."""
+    keys = [bytes([0x41 + n % 26]) + bytes((0x80 + 7 * i) % 256 or 0xff for i in range(n - 1))
+            for n in range(1, 33)]
+    keys.sort()
+    assert sorted(len(k) for k in keys) == list(range(1, 33)) and all(b"\0" not in k for k in keys)
+    words = []
+    for k in keys:
+        rec = ref.compact_record_ref(ref.pad32(k), count)
+        assert len(rec) == ref.compact_words_ref(ref.pad32(k), count)
+        words += rec
+    r = C.Result.from_compact(words, [(0, len(keys))])
+    assert [(k, c) for k, _v, c in r.entries()] == [(k, count) for k in keys]
+
+
+def test_slot_gather_takes_the_standard_path_beyond_the_merge_bounds():
+    """The gather strategy's root merge is enqueued behind the all-gather, before any header
+    is known; its look-back value holds 22 bits of records and 40 bits of counts.  The job
+    enters it only for a shape that fits and falls back when the headers announce more
+    tokens than it can count."""
+    fits = C.slot_merge_fits
+    assert fits(1, 2048, 0) and fits(8, 2048, 12345) and fits(64, 65535, 0)
+    assert fits(64, 65536, 0) is False  # 2^22 records
+    assert fits(3, (1 << 22) // 3, 0) and not fits(3, (1 << 22) // 3 + 1, 0)
+    assert fits(1, (1 << 22) - 1, 0) and not fits(1, 1 << 22, 0)
+    assert not fits(65, 1, 0)
+    assert not fits(1 << 32, 1 << 32, 0)  # (the product does not wrap)
+    assert fits(8, 2048, (1 << 40) - 1) and not fits(8, 2048, 1 << 40)
+    assert not fits(8, 2048, 2**64 - 1)

@@ -63,6 +63,7 @@ GpuWordCount::Stats GpuWordCount::stats() const {
   s.retunes = impl_->pm_retunes;
   s.fallbacks = impl_->fallbacks;
   s.planned_passes = impl_->planned_passes;
+  s.process_path = impl_->process_path;
   s.devplan_failed = impl_->devplan_failed;
   s.device_bytes = impl_->device_bytes();
   s.hbm_free = impl_->hbm_free;
@@ -165,16 +166,26 @@ WordCountResult GpuWordCount::run_reduce_stage(const PackedKey* keys, u64 n) {
 }
 
 std::vector<u32> GpuWordCount::sort_keys(const PackedKey* keys, u64 n,
-                                         std::vector<PackedKey>* sorted) {
+                                         std::vector<PackedKey>* sorted, const u64* counts,
+                                         std::vector<u64>* sorted_counts) {
   Impl& m = *impl_;
   m.idx_resident = false;
   m.sync_clean = false;  // this entry point dirties d_sync
   m.upload_tokens(keys, n);
-  m.enqueue_process(0, false, false, n);
+  if (counts && n)  // (n <= cap: upload_tokens checked it)
+    LOCUST_HIP_CHECK(hipMemcpyAsync(m.d_counts, counts, n * sizeof(u64), hipMemcpyHostToDevice,
+                                    m.stream));
+  m.enqueue_process(0, false, counts != nullptr, n);
   std::vector<u32> perm(n);
   if (n)
     LOCUST_HIP_CHECK(hipMemcpyAsync(perm.data(), m.d_perm, n * sizeof(u32),
                                     hipMemcpyDeviceToHost, m.stream));
+  if (counts && sorted_counts) {
+    sorted_counts->resize(n);
+    if (n)
+      LOCUST_HIP_CHECK(hipMemcpyAsync(sorted_counts->data(), m.d_sorted_counts, n * sizeof(u64),
+                                      hipMemcpyDeviceToHost, m.stream));
+  }
   m.sync();
   if (sorted) m.download_keys(m.sorted, n, sorted);
   return perm;

@@ -772,7 +772,10 @@ void DevicePipeline::launch_dict_graph(const TextInput& in, bool compat) {
   graph_ordered = hit->ordered;
   job_self_cleaned = hit->clean;
   ord_compact = hit->compact;
-  if (cfg.sort_path == SortPath::kRadix) psort_used = hit->ordered;
+  if (cfg.sort_path == SortPath::kRadix) {  // what the replayed job took when it was captured
+    psort_used = hit->ordered;
+    process_path = psort_used ? kPathPsort : radix_path_name();
+  }
   parts_ready = cfg.map_path == MapPath::kFast;  // what enqueue_map sets when not replaying
   part_tiles = cfg.map_path != MapPath::kFast ? 0u : pieces.empty() ? table_tiles(in.bytes)
                                                                        : piece_tiles();
@@ -882,9 +885,11 @@ void DevicePipeline::enqueue_process(u32 num_lines, bool compat, bool with_count
     // one kernel, one workgroup per key range of the map's partition table (psort.hip)
     launch_psort(tokens, d_part_off, part_tiles, cap, sorted, d_ctr, d_pw, stream, ord_trace());
     psort_used = true;
+    process_path = kPathPsort;
     return;
   }
   psort_used = false;
+  process_path = radix_path_name();
   if (compat)
     launch_compact_slots(d_line_counts, num_lines, cfg.emits_per_line, slots, tokens, d_ctr,
                          lb_compact, stream);
@@ -923,6 +928,7 @@ void DevicePipeline::enqueue_radix_job(u32 num_lines, bool compat, hipEvent_t af
     }
     launch_psort_reduce(tokens, d_part_off, part_tiles, cap, d_ctr, d_pw, ra, stream, ord_trace());
     psort_used = true;
+    process_path = kPathPsort;
     if (after_process) LOCUST_HIP_CHECK(hipEventRecord(after_process, stream));
     if (after_reduce) LOCUST_HIP_CHECK(hipEventRecord(after_reduce, stream));
     return;

@@ -536,6 +536,13 @@ struct DevicePipeline {
            cap <= kPartBuildMaxTokens;
   }
   bool psort_used = false;  // the last enqueue_process took the partitioned sort
+  // ... and its name (GpuWordCount::Stats::process_path): the partitioned sort, or the
+  // device-wide sort under the planner it ran with
+  static constexpr const char* kPathPsort = "psort";
+  const char* radix_path_name() const {
+    return cfg.sync_plan ? "radix-host-plan" : "radix-device-plan";
+  }
+  const char* process_path = "none";
 
   // Process + Reduce of the reference algorithm (sort every token, boundary mark + head
   // compaction + adjacent difference), records packed into the host-mapped output with a

@@ -771,6 +771,12 @@ class GpuWordCount {
     u64 chunk_bytes = 0, map_window = 0;
     // device bytes of the search stage's workspace (0 until the first search job)
     u64 search_bytes = 0;
+    // what the last Process stage of the reference algorithm (every token sorted) used:
+    // "psort" (the partitioned LDS sort), "radix-host-plan" (the device-wide sort, live
+    // passes launched from the plan read back) or "radix-device-plan" (every pass launched,
+    // liveness and buffers decided on the device); "none" before the first such stage
+    // (a dictionary job sorts no tokens)
+    const char* process_path = "none";
   };
   Stats stats() const;
 
@@ -788,7 +794,11 @@ class GpuWordCount {
   WordCountResult run_reduce_stage(const PackedKey* keys, u64 n);
 
   // Sort arbitrary packed keys on the device (used by tests and the shuffle receiver).
-  std::vector<u32> sort_keys(const PackedKey* keys, u64 n, std::vector<PackedKey>* sorted);
+  // counts (n of them, optional) travel with their keys: *sorted_counts gets them in
+  // sorted order, through the sort's fused count gather.
+  std::vector<u32> sort_keys(const PackedKey* keys, u64 n, std::vector<PackedKey>* sorted,
+                             const u64* counts = nullptr,
+                             std::vector<u64>* sorted_counts = nullptr);
 
   // Single-stage entry points for the kernel unit tests.
   // Stable compaction of the compat map's fixed slots (main.cu:411): slot_keys holds

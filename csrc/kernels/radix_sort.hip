@@ -22,6 +22,7 @@
 
 #include "locust/device/lds_radix.hpp"
 #include "locust/device/lookback.hpp"
+#include "locust/device/radix_sched.hpp"
 #include "locust/device/wave.hpp"
 #include "locust/hip_check.hpp"
 #include "locust/kernels.hpp"
@@ -40,30 +41,8 @@ constexpr u32 kRxValMask = (1u << 30) - 1;
 
 LOCUST_HD inline u32 pos_shift(int pos) { return 56u - 8u * (u32)(pos & 7); }
 
-// Ping-pong parity of the pass schedule, from the 32-bit mask of live digit positions
-// (bit p = position p).  Passes of word w run bytes 7..0 and alternate buffers starting
-// at buffer 0 (the word's prepare kernel writes it); buffer 2 = identity permutation.
-LOCUST_HD inline u32 word_bits(u32 act, int w) { return (act >> (8 * w)) & 0xffu; }
-LOCUST_HD inline u32 popc32(u32 x) {
-  u32 c = 0;
-  for (; x; x &= x - 1) ++c;
-  return c;
-}
-LOCUST_HD inline u32 pass_src(u32 act, int pos) {
-  const int w = pos / 8, b = pos % 8;
-  return popc32(word_bits(act, w) >> (b + 1)) & 1u;  // live passes of this word before it
-}
-LOCUST_HD inline u32 word_src(u32 act, int w) {  // buffer holding the permutation at word start
-  for (int v = w + 1; v < kKeyWords; ++v)
-    if (word_bits(act, v))  // the nearest higher live word ran last: ended in popc & 1
-      return popc32(word_bits(act, v)) & 1u;
-  return 2u;
-}
-LOCUST_HD inline u32 final_src(u32 act) {
-  for (int v = 0; v < kKeyWords; ++v)
-    if (word_bits(act, v)) return popc32(word_bits(act, v)) & 1u;
-  return 2u;
-}
+// (the ping-pong parity of the pass schedule -- word_bits, pass_src, word_src, final_src --
+// is locust/device/radix_sched.hpp)
 
 // Live-position mask read by one wave: lanes 0..31 load a flag each, one ballot.
 __device__ __forceinline__ u32 live_mask(const SortPlan* plan) {

@@ -7,10 +7,12 @@
 #include <pybind11/stl.h>
 
 #include <cstring>
+#include <optional>
 #include <string>
 #include <tuple>
 
 #include "locust/devcache.hpp"
+#include "locust/device/radix_sched.hpp"
 #include "locust/dist.hpp"
 #include "locust/dstring.hpp"
 #include "locust/engine.hpp"
@@ -320,6 +322,7 @@ class PyGpuEngine {
     d["retunes"] = st.retunes;
     d["fallbacks"] = st.fallbacks;
     d["planned_passes"] = st.planned_passes;
+    d["process_path"] = std::string(st.process_path);
     d["devplan_failed"] = st.devplan_failed;
     d["device_bytes"] = st.device_bytes;
     d["hbm_free"] = st.hbm_free;
@@ -353,17 +356,25 @@ class PyGpuEngine {
     py::gil_scoped_release nogil;
     return PyResult{eng_.run_reduce_stage(toks.data(), toks.size())};
   }
-  py::tuple sort_keys(const std::vector<std::string>& keys) {
+  // counts: None, or one u64 per key; then the sorted counts are a third element.
+  py::tuple sort_keys(const std::vector<std::string>& keys,
+                      const std::optional<std::vector<u64>>& counts) {
+    LOCUST_CHECK_ARG(!counts || counts->size() == keys.size(), "sort_keys: one count per key");
     std::vector<PackedKey> toks;
     for (const auto& s : keys) toks.push_back(to_key(s));
     std::vector<PackedKey> sorted;
     std::vector<u32> perm;
+    std::vector<u64> sorted_counts;
     {
       py::gil_scoped_release nogil;
-      perm = eng_.sort_keys(toks.data(), toks.size(), &sorted);
+      // (an empty vector's data() may be null, which would read as "no counts")
+      static const u64 none = 0;
+      const u64* c = !counts ? nullptr : counts->empty() ? &none : counts->data();
+      perm = eng_.sort_keys(toks.data(), toks.size(), &sorted, c, &sorted_counts);
     }
     std::vector<py::bytes> out;
     for (const auto& k : sorted) out.emplace_back(key_to_string(k));
+    if (counts) return py::make_tuple(out, perm, sorted_counts);
     return py::make_tuple(out, perm);
   }
   std::vector<py::bytes> compact_slots(const std::vector<u32>& line_counts,
@@ -1046,7 +1057,7 @@ PYBIND11_MODULE(_locust, m) {
            "Stream a file through this (streaming) engine, piece by piece.")
       .def("map_stage", &PyGpuEngine::map_stage)
       .def("reduce_stage", &PyGpuEngine::reduce_stage)
-      .def("sort_keys", &PyGpuEngine::sort_keys)
+      .def("sort_keys", &PyGpuEngine::sort_keys, py::arg("keys"), py::arg("counts") = py::none())
       .def("compact_slots", &PyGpuEngine::compact_slots)
       .def("reduce_sorted", &PyGpuEngine::reduce_sorted)
       .def("merge_runs", &PyGpuEngine::merge_runs)
@@ -1137,6 +1148,14 @@ PYBIND11_MODULE(_locust, m) {
     for (const auto& k : eng.run_map_stage(as_input(text), nullptr)) out.emplace_back(key_to_string(k));
     return out;
   });
+  m.def("radix_schedule", [](u32 act) {
+    std::vector<u32> ws(kKeyWords), ps(kKeyBytes);
+    for (int w = 0; w < kKeyWords; ++w) ws[w] = word_src(act, w);
+    for (int p = 0; p < kKeyBytes; ++p) ps[p] = pass_src(act, p);
+    return py::make_tuple(ws, ps, final_src(act));
+  }, py::arg("act"),
+        "The device-wide radix sort's buffer schedule for a mask of live digit positions: "
+        "(word_src[4], pass_src[32], final_src), the functions its kernels call.");
   m.def("run_multi_schedule", &run_multi_schedule, py::arg("text"), py::arg("schedule"),
         py::arg("comm") = "auto",
         "Several jobs back to back on the same in-process ranks; [(Result, info)] of rank 0.");

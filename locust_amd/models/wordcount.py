@@ -231,12 +231,18 @@ class Engine:
             return _C.cpu_run(self.cfg, text)
         return self._eng.reduce_stage(keys)
 
-    def sort_keys(self, keys: list[bytes]):
-        """Device radix sort of byte-string keys: (sorted keys, permutation)."""
+    def sort_keys(self, keys: list[bytes], counts: list[int] | None = None):
+        """Device radix sort of byte-string keys: (sorted keys, permutation).  With
+        ``counts`` (one u64 per key) they travel with their keys through the sort's fused
+        gather: (sorted keys, permutation, sorted counts)."""
+        if counts is not None and len(counts) != len(keys):
+            raise ValueError("sort_keys: one count per key")
         if self.cpu:
             perm = sorted(range(len(keys)), key=lambda i: keys[i])
+            if counts is not None:
+                return [keys[i] for i in perm], perm, [counts[i] for i in perm]
             return [keys[i] for i in perm], perm
-        return self._eng.sort_keys(keys)
+        return self._eng.sort_keys(keys, counts)
 
     def compact_slots(self, line_counts: list[int], slot_keys: list[bytes]) -> list[bytes]:
         """Stable compaction of fixed [line * emits_per_line + k] slots (compat engine):

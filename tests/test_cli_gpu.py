@@ -62,6 +62,17 @@ def test_whole_file(cli, hamlet, extra):
     assert p.stdout.count(b"print key:") == 5608
 
 
+@pytest.mark.parametrize("reduce_path", ["lds", "global"])
+def test_whole_file_no_sync_plan(cli, hamlet, reduce_path):
+    """--no-sync-plan with the compat map and the radix sort: every token goes through the
+    device-planned device-wide sort (test_gpu_engine.py pins that this configuration takes
+    it)."""
+    p = run(cli, "data/hamlet.txt", "--no-sync-plan", "--sort", "radix", "--map-path", "compat",
+            "--reduce-path", reduce_path)
+    check_protocol(p.stdout, hamlet)
+    assert p.stdout.count(b"print key:") == 5608
+
+
 def test_ref_compat_and_ref_timers(cli, hamlet):
     p = run(cli, "data/hamlet.txt", "--ref-compat", "--ref-timers")
     text = oracle.window(hamlet, ref_compat=True)

@@ -1,6 +1,13 @@
-"""GPU pipeline vs oracle: every kernel path (map compat/fast, reduce lds/global, planned
-and device-planned radix passes), edge cases, and sizes around the reference's 32,768-thread
-truncation (bug B3)."""
+"""GPU pipeline vs oracle: every kernel path (map compat/fast, reduce lds/global, the
+dictionary build, the partitioned sort, and the device-wide radix sort planned on the host
+and on the device), edge cases, and sizes around the reference's 32,768-thread truncation
+(bug B3).
+
+An entry of PATHS without ``sort`` takes the default dictionary build, which sorts no
+tokens: ``sync_plan=False`` alone (PATHS[6]) reaches no radix pass, and with ``sort="radix"``
+the fast map's tokens take the partitioned sort.  The device-planned radix passes are the
+last two entries (compat map, ``sort="radix"``, ``sync_plan=False``);
+test_paths_reach_the_sort_they_name pins which sort each of them ran."""
 import random
 
 import pytest
@@ -20,6 +27,8 @@ PATHS = [
     dict(map_path="fast", reduce_path="lds", sync_plan=False),
     dict(map_path="fast", reduce_path="lds", sort="dict", zero_copy_text=0),
     dict(map_path="fast", reduce_path="lds", sort="dict", zero_copy_text=1),
+    dict(map_path="compat", reduce_path="lds", sort="radix", sync_plan=False),
+    dict(map_path="compat", reduce_path="global", sort="radix", sync_plan=False),
 ]
 
 
@@ -36,6 +45,30 @@ def test_hamlet_matches_oracle(hamlet, opts, start, end):
     assert r.num_tokens == ntok
     assert r.entries() == ent
     assert r.format() == oracle.format_gpu(ent)
+
+
+def test_paths_reach_the_sort_they_name(hamlet):
+    """Which Process stage a whole-Hamlet job ran, by the engine's own account: the last
+    two entries of PATHS take the device-planned radix sort; PATHS[6] (fast map,
+    sync_plan=False) never does -- with the radix sort its tokens take the partitioned sort,
+    and as written (no ``sort``: the dictionary build unless LOCUST_SORT says otherwise) no
+    token is sorted at all."""
+    want = oracle.wordcount(hamlet)[0]
+
+    def path_of(opts):
+        eng = lc._C.GpuEngine(lc.make_config("gpu", check=True, **opts), len(hamlet) + 1, 5000)
+        assert eng.stats()["process_path"] == "none"
+        assert eng.run(hamlet).entries() == want
+        return eng.stats()["process_path"]
+
+    for opts in PATHS[-2:]:
+        assert (opts["map_path"], opts["sort"], opts["sync_plan"]) == ("compat", "radix", False)
+        assert path_of(opts) == "radix-device-plan"
+    assert PATHS[6] == dict(map_path="fast", reduce_path="lds", sync_plan=False)
+    assert path_of(dict(PATHS[6], sort="radix")) == "psort"
+    dict_default = lc.make_config("gpu", **PATHS[6]).sort_path == lc._C.SortPath.dict
+    assert path_of(PATHS[6]) == ("none" if dict_default else "psort")
+    assert path_of(dict(PATHS[5], sort="radix")) == "radix-host-plan"
 
 
 def test_hamlet_known_numbers(hamlet):

@@ -35,18 +35,41 @@ def test_hamlet_radix_repeated_with_retune(hamlet, graph):
     assert eng.run(hamlet).entries() == want
 
 
-def test_partition_over_lds_capacity_falls_back():
-    """One first byte with > kPsortMax (5,120) tokens: that partition overflows and the
-    device-wide sort redoes the pass; the result is identical."""
+def radix_with_path(text, **kw):
+    """One job on an engine of its own: (result, the Process stage it ended on)."""
+    cfg = lc.make_config("gpu", sort="radix", check=True, **kw)
+    eng = lc._C.GpuEngine(cfg, max(len(text), 1), max(text.count(b"\n") + 1, 1))
+    r = eng.run(text)
+    return r, eng.stats()["process_path"]
+
+
+def over_capacity_text():
     rng = random.Random(3)
     words = [b"a%d" % rng.randint(0, 5000) for _ in range(20000)]
     words += [b"b%d" % rng.randint(0, 50) for _ in range(3000)]
-    text = lines_of(words)
+    return lines_of(words)
+
+
+def test_partition_over_lds_capacity_falls_back():
+    """One first byte with > kPsortMax (5,120) tokens: that partition overflows and the
+    device-wide sort redoes the pass; the result is identical."""
+    text = over_capacity_text()
     ent, ntok, _ = oracle.wordcount(text)
     r = radix(text, graph=0)
     assert r.num_tokens == ntok and r.entries() == ent
     r = radix(text, graph=1)
     assert r.entries() == ent
+
+
+@pytest.mark.parametrize("graph", [0, 1])
+def test_partition_over_lds_capacity_falls_back_to_device_plan(graph):
+    """The same overflow with sync_plan=False: the pass is redone by the device-planned
+    device-wide sort (every pass launched, liveness and buffers decided on the device)."""
+    text = over_capacity_text()
+    ent, ntok, _ = oracle.wordcount(text)
+    r, path = radix_with_path(text, graph=graph, sync_plan=False)
+    assert path == "radix-device-plan"
+    assert r.num_tokens == ntok and r.entries() == ent
 
 
 @pytest.mark.parametrize("width", [7, 8, 9, 15, 16, 17, 23, 24, 25, 29, 35])
@@ -64,19 +87,33 @@ def test_long_keys_reach_every_word(width):
     assert r.num_tokens == ntok and r.entries() == ent
 
 
-def test_psort_matches_device_wide_sort(hamlet, monkeypatch):
-    """A/B: identical output with the partitioned sort and the device-wide LSD sort."""
+def vocab_text_30000():
     rng = random.Random(17)
     vocab = [bytes(rng.choice(b"abcdefghijklmnopqrstuvwxyzABC'") for _ in range(rng.randint(1, 14)))
              for _ in range(4000)]
-    texts = [hamlet, oracle.window(hamlet, 100, 900),
-             lines_of([rng.choice(vocab) for _ in range(30000)], 12)]
+    return lines_of([rng.choice(vocab) for _ in range(30000)], 12)
+
+
+def test_psort_matches_device_wide_sort(hamlet, monkeypatch):
+    """A/B: identical output with the partitioned sort and the device-wide LSD sort."""
+    texts = [hamlet, oracle.window(hamlet, 100, 900), vocab_text_30000()]
     for text in texts:
         a = radix(text, graph=0)
         monkeypatch.setenv("LOCUST_PSORT", "0")
         b = radix(text, graph=0)
         monkeypatch.delenv("LOCUST_PSORT")
         assert a.entries() == b.entries() == oracle.wordcount(text)[0]
+
+
+def test_device_wide_sort_device_plan(monkeypatch):
+    """LOCUST_PSORT=0 with sync_plan=False: the fast map's 30,000 tokens go through the
+    device-planned device-wide sort."""
+    text = vocab_text_30000()
+    ent, ntok, _ = oracle.wordcount(text)
+    monkeypatch.setenv("LOCUST_PSORT", "0")
+    r, path = radix_with_path(text, graph=0, sync_plan=False)
+    assert path == "radix-device-plan"
+    assert r.num_tokens == ntok and r.entries() == ent
 
 
 def test_ref_timers_and_map_stage(hamlet):

@@ -11,60 +11,15 @@
 
 #include "locust/hip_check.hpp"
 #include "locust/kernels.hpp"
+#include "stage_buf.hpp"
 
 namespace locust {
 namespace {
 
-constexpr u64 kStageMaxBytes = 1ull << 30;  // largest single buffer of a stage call
-
-template <class T>
-struct DevBuf {  // a plain device allocation of max(n, 1) elements
-  T* p = nullptr;
-  u64 n;
-  explicit DevBuf(u64 count) : n(std::max<u64>(count, 1)) {
-    LOCUST_CHECK_ARG(n * sizeof(T) <= kStageMaxBytes, "exchange stage: buffer too large");
-    LOCUST_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&p), n * sizeof(T)));
-  }
-  ~DevBuf() { (void)hipFree(p); }
-  DevBuf(const DevBuf&) = delete;
-  DevBuf& operator=(const DevBuf&) = delete;
-  void upload(const T* src, u64 count) {
-    if (count) LOCUST_HIP_CHECK(hipMemcpy(p, src, count * sizeof(T), hipMemcpyHostToDevice));
-  }
-  void download(T* dst, u64 count) const {
-    if (count) LOCUST_HIP_CHECK(hipMemcpy(dst, p, count * sizeof(T), hipMemcpyDeviceToHost));
-  }
-  void fill(unsigned char byte) { LOCUST_HIP_CHECK(hipMemset(p, byte, n * sizeof(T))); }
-};
-
-struct DevKeys {  // packed keys, structure-of-arrays
-  DevBuf<u64> w0, w1, w2, w3;
-  explicit DevKeys(u64 n) : w0(n), w1(n), w2(n), w3(n) {}
-  u64* word(int j) { return j == 0 ? w0.p : j == 1 ? w1.p : j == 2 ? w2.p : w3.p; }
-  KeysSoA soa() {
-    KeysSoA k;
-    for (int j = 0; j < kKeyWords; ++j) k.w[j] = word(j);
-    return k;
-  }
-  template <class Rec>  // PackedKey or KeyCount: anything with w[kKeyWords]
-  void upload(const Rec* recs, u64 n) {
-    std::vector<u64> col(n);
-    for (int j = 0; j < kKeyWords; ++j) {
-      for (u64 i = 0; i < n; ++i) col[i] = recs[i].w[j];
-      if (n) LOCUST_HIP_CHECK(hipMemcpy(word(j), col.data(), n * sizeof(u64), hipMemcpyHostToDevice));
-    }
-  }
-  void download(PackedKey* out, u64 n) {
-    std::vector<u64> col(n);
-    for (int j = 0; j < kKeyWords; ++j) {
-      if (n) LOCUST_HIP_CHECK(hipMemcpy(col.data(), word(j), n * sizeof(u64), hipMemcpyDeviceToHost));
-      for (u64 i = 0; i < n; ++i) out[i].w[j] = col[i];
-    }
-  }
-};
-static_assert(kKeyWords == 4, "DevKeys holds four word arrays");
-
-void sync() { LOCUST_HIP_CHECK(hipStreamSynchronize(nullptr)); }
+using stage::DevBuf;
+using stage::DevKeys;
+using stage::kStageMaxBytes;
+using stage::sync;
 
 bool all_pattern(const char* p, u64 bytes) {
   for (u64 i = 0; i < bytes; ++i)

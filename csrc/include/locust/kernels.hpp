@@ -422,9 +422,12 @@ void launch_merge_slots(const KeyCount* slots, u32 nslots, u32 slot_records, Key
 // (kMergeMaxRecords, kMergeMaxCount: locust/slot.hpp)
 
 // Hash every token (with its count; null = 1) into the table; distinct keys land in
-// ukeys[0 .. ctr->num_unique) with summed counts in ucount.
+// ukeys[0 .. ctr->num_unique) with summed counts in ucount.  At most max_blocks workgroups
+// (each streams its share of the tokens through one LDS cache; past 2^18 tokens a workgroup
+// takes more than one chunk -- a stage test asks for fewer to stream a small input).
 void launch_dict_insert(ConstKeysSoA tokens, const u64* counts, const u32* d_n, u64 cap,
-                        const DictWorkspace& dw, MapCounters* ctr, hipStream_t s);
+                        const DictWorkspace& dw, MapCounters* ctr, hipStream_t s,
+                        u32 max_blocks = 1024);
 // rank[i] = number of keys smaller than key i (distinct keys; rank zeroed by the caller);
 // with counts/val also val[i] = total count of the smaller keys (zeroed by the caller).
 // Early-exits (device-side) when *d_u > kRankSortMax.

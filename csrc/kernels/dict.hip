@@ -26,6 +26,7 @@
 #include <algorithm>
 #include <type_traits>
 
+#include "locust/device/dict_consts.hpp"
 #include "locust/device/hash.hpp"
 #include "locust/device/lds_radix.hpp"
 #include "locust/device/lookback.hpp"
@@ -41,11 +42,7 @@ using dev::ballot;
 using dev::lane_id;
 using dev::wave_id;
 
-// Words 1..3 are stored XOR kWordMagic: a packed key word can never equal kWordMagic
-// (bytes 00 00 FF FF 00 00 FF FF: a NUL followed by non-NUL bytes), so a stored 0 means
-// "not written yet" and a zero-initialised table needs no sentinel fill.
-constexpr u64 kWordMagic = 0x0000FFFF0000FFFFull;
-constexpr u32 kIdFull = 0xFFFFFFFFu;  // slot id of a key that did not fit the dense arrays
+// (kWordMagic, kIdFull and the table sizes: locust/device/dict_consts.hpp)
 
 using dev::key_hash;
 using dev::key_part;
@@ -114,10 +111,6 @@ __device__ bool global_insert(const DictWorkspace& dw, const u64* k, u64 count,
 // goes straight to the HBM table.  Frequent keys get cached by the first chunks and stay
 // cached for the whole stream, so a Zipfian input costs ~one HBM atomic per frequent key
 // per workgroup.  The cache is flushed to the HBM table at the end.
-constexpr int kInsBlock = 256;
-constexpr int kLdsSlots = 1024;
-constexpr int kLdsProbes = 8;
-
 struct LdsSlot {
   u64 w[kKeyWords];  // w[0] raw (0 = empty), w[1..3] XOR kWordMagic (0 = not written)
   u64 count;
@@ -211,10 +204,7 @@ __device__ __forceinline__ void load_key(ConstKeysSoA t, u32 i, u64* k) {
   }
 }
 
-constexpr int kPartBlock = 1024;       // 16 waves: latency hiding for the gathers
-constexpr int kPartSlots = 2048;       // 80 KB of LDS
 static_assert(kPartSlots == kPartSlotsHost, "partial slot size");
-constexpr int kPartWindow = kPartBlock * 16;  // partition bytes scanned per round
 constexpr u32 kOrdTagWindow = kPartBlock * 32;  // ordered build: tags scanned per round
 constexpr int kPartPerThread = kPartSlots / kPartBlock;
 // The ordered kernel's tile-source partitions clear only the first kSmallTable slots of
@@ -223,11 +213,6 @@ constexpr int kPartPerThread = kPartSlots / kPartBlock;
 constexpr u32 kSmallTable = 512;
 constexpr u32 kSmallTableTokens = kSmallTable * 3 / 4;
 
-// A key not placed within kPartProbes slots reports the table full (the caller falls back):
-// probing a nearly full table to the end made an overflowing pass quadratic.  (512: a
-// planned range holds up to ~1,500 of the 2,048 slots; linear probing at 75 % load runs
-// clusters past 128.)
-constexpr int kPartProbes = 512;
 // occ (optional, LDS, zeroed with the table): the table's claimed slots.  With it a key
 // probes past kPartProbes -- up to the whole table -- while the table is below 31/32 full,
 // so a planned range that lands at ~95 % load (in-job plans of large passes: measured up to
@@ -1828,10 +1813,8 @@ __global__ __launch_bounds__(kPartBlock) void dict_ordered_kernel(
   ordered_partition(src, ctr, out, ctr_out, status, tile_ctr, trace, ex, blockIdx.x);
 }
 
-// rank[i] += #{ j in tile : key[j] < key[i] }, persistent over (i-tile, j-tile) pairs.
-constexpr int kRankI = 256;
-constexpr int kRankJ = 256;
-
+// rank[i] += #{ j in tile : key[j] < key[i] }, persistent over (i-tile, j-tile) pairs of
+// kRankI x kRankJ keys.
 __device__ __forceinline__ bool key_lt(const u64* a, const u64* b) {
 #pragma unroll
   for (int j = 0; j < kKeyWords; ++j)
@@ -1983,8 +1966,6 @@ __global__ __launch_bounds__(256) void rank_scatter_kernel(ConstKeysSoA keys,
 }
 
 // Exclusive scan of the sorted counts (look-back) fused with the output records.
-constexpr int kPackItems = 8;
-constexpr int kPackTile = 256 * kPackItems;
 __global__ __launch_bounds__(256) void scan_pack_kernel(ConstKeysSoA sorted,
                                                         const u64* __restrict__ counts,
                                                         MapCounters* __restrict__ ctr,
@@ -2050,8 +2031,9 @@ u32 grid_for(u64 n, u32 block, u32 max_blocks = 2048) {
 }  // namespace
 
 void launch_dict_insert(ConstKeysSoA tokens, const u64* counts, const u32* d_n, u64 cap,
-                        const DictWorkspace& dw, MapCounters* ctr, hipStream_t s) {
-  dict_insert_kernel<<<dim3(grid_for(cap, kInsBlock, 1024)), dim3(kInsBlock), 0, s>>>(
+                        const DictWorkspace& dw, MapCounters* ctr, hipStream_t s, u32 max_blocks) {
+  LOCUST_CHECK_ARG(max_blocks >= 1 && max_blocks <= 1024, "dict insert: 1..1024 workgroups");
+  dict_insert_kernel<<<dim3(grid_for(cap, kInsBlock, max_blocks)), dim3(kInsBlock), 0, s>>>(
       tokens, counts, d_n, dw, ctr, (u32)std::min<u64>(cap, 0xFFFFFFFFu));
   LOCUST_HIP_LAUNCH_CHECK();
 }

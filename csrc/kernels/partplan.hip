@@ -12,6 +12,7 @@
 // those distinct keys: every range gets ~1/256 of the estimated vocabulary of the whole
 // pass, the measure that bounds the LDS tables.  Hot words stay cheap anyway: the
 // combining map folds their repeats per tile.
+#include "locust/device/dict_consts.hpp"
 #include "locust/device/wave.hpp"
 #include "locust/hip_check.hpp"
 #include "locust/kernels.hpp"
@@ -20,16 +21,8 @@ namespace locust {
 namespace {
 
 constexpr int kPlanBlock = 1024;
-// Sizing, from an offline replay of the plan on the generator's 1M-line text (fullest range
-// of the whole pass, in distinct keys; the mean is 792): 2,048 samples of a 512 KiB prefix
-// 3,100 (sampling noise, ~8 samples per range); 8,192 1,800; 8,192 of a 1 MiB prefix,
-// singletons weighted 9x, 1,768 -- the setting here; 16,384 of 1.5 MiB 1,477, but the
-// larger sample and sort cost ~0.4 ms of compute in front of the first piece's map.
-constexpr u32 kPlanSamples = 8192;
+// (kPlanSamples, kSingletonWeight: locust/device/dict_consts.hpp)
 constexpr u32 kPlanPer = kPlanSamples / kPlanBlock;
-// A key the prefix saw once (a hapax) stands for the rare keys of the whole pass the prefix
-// has not seen yet (Good-Turing): it weighs kSingletonWeight, a repeated key 1.
-constexpr u32 kSingletonWeight = 9;
 
 // One workgroup: kPlanSamples of the U distinct keys (dense, in hash-arrival order -- no
 // key order) with their weights, bitonic-sorted in LDS by first word (72 KB); range q

@@ -13,6 +13,7 @@
 
 #include "locust/devcache.hpp"
 #include "locust/device/radix_sched.hpp"
+#include "locust/dict_stage.hpp"
 #include "locust/dist.hpp"
 #include "locust/dstring.hpp"
 #include "locust/engine.hpp"
@@ -839,6 +840,53 @@ std::vector<ExchMsg3> msg3_from(const std::vector<PyMsg3>& in) {
     out[q].n_out = std::get<2>(in[q]);
   }
   return out;
+}
+
+// ---- stage entry points of the dictionary kernels (locust/dict_stage.hpp) ----
+DictStageCounters stage_counters_from(const py::dict& d) {
+  auto get = [&](const char* k) -> u64 { return d.contains(k) ? d[k].cast<u64>() : 0; };
+  DictStageCounters c;
+  c.num_records = (u32)get("num_records");
+  c.map_tokens = (u32)get("map_tokens");
+  c.num_unique = (u32)get("num_unique");
+  c.overflow_lines = (u32)get("overflow_lines");
+  c.truncated = (u32)get("truncated");
+  c.num_newlines = (u32)get("num_newlines");
+  c.max_key_len = (u32)get("max_key_len");
+  c.flags = (u32)get("flags");
+  c.total_count = get("total_count");
+  return c;
+}
+py::dict stage_counters_dict(const DictStageCounters& c) {
+  py::dict d;
+  d["num_records"] = c.num_records;
+  d["map_tokens"] = c.map_tokens;
+  d["num_unique"] = c.num_unique;
+  d["overflow_lines"] = c.overflow_lines;
+  d["truncated"] = c.truncated;
+  d["num_newlines"] = c.num_newlines;
+  d["max_key_len"] = c.max_key_len;
+  d["flags"] = c.flags;
+  d["total_count"] = c.total_count;
+  return d;
+}
+py::dict dict_dense_dict(const DictStageDense& r, bool part_build) {
+  py::dict d;
+  d["num_unique"] = r.num_unique;
+  d["flags"] = r.flags;
+  d["keys"] = blob_from_keys(r.keys.data(), r.keys.size());
+  d["counts"] = r.counts;
+  d["tail_intact"] = r.tail_intact;
+  if (part_build) {
+    d["uval"] = r.uval;
+    d["urank"] = r.urank;
+  } else {
+    py::list table;
+    for (const DictStageSlot& s : r.table)
+      table.append(py::make_tuple(s.slot, s.id, blob_from_keys(&s.key, 1)));
+    d["table"] = table;
+  }
+  return d;
 }
 
 }  // namespace
@@ -1677,6 +1725,133 @@ PYBIND11_MODULE(_locust, m) {
         "launch_merge_rank_slots + launch_merge_emit_compact per job (the second on slots2 / "
         "msg3_all2, seq + 1, the same scratch): per job dst (with its guard), stamps, done "
         "and the accumulators.  msg3_all: (status, flags, n_out) per rank.");
+  // ---- the dictionary kernels and the partition plan, each alone (locust/dict_stage.hpp) ----
+  m.def("dict_constants", [] {
+    py::dict d;
+    for (const auto& kv : dict_stage_constants()) d[py::str(kv.first)] = kv.second;
+    return d;
+  }, "Kernel constants of dict.hip / partplan.hip by name (device/dict_consts.hpp; no GPU).");
+  m.def("dict_valid_key", [](const std::string& key) {
+    const std::vector<PackedKey> k = keys_from_blob(key);
+    LOCUST_CHECK_ARG(k.size() == 1, "one 32-byte key");
+    return dict_stage_valid_key(k[0].w);
+  }, "Whether 32 bytes are a valid packed key: bytes, then NUL padding only (no GPU).");
+  m.def("dict_insert", [](const std::string& keys, const py::object& counts, u32 d_n, u64 cap,
+                          u64 table_slots, u32 ucap, u32 max_blocks) {
+    const std::vector<PackedKey> k = keys_from_blob(keys);
+    std::vector<u64> c;
+    if (!counts.is_none()) c = counts.cast<std::vector<u64>>();
+    DictStageDense r;
+    {
+      py::gil_scoped_release nogil;
+      r = dict_stage_insert(k, counts.is_none() ? nullptr : &c, d_n, cap, table_slots, ucap,
+                            max_blocks);
+    }
+    return dict_dense_dict(r, false);
+  }, py::arg("keys"), py::arg("counts"), py::arg("d_n"), py::arg("cap"), py::arg("table_slots"),
+        py::arg("ucap"), py::arg("max_blocks") = 1024,
+        "launch_dict_insert on a zeroed table: num_unique, flags, the dense keys / counts "
+        "[0, min(num_unique, ucap)), tail_intact and the occupied slots (slot, id, key).");
+  m.def("dict_part_build", [](const std::string& keys, const py::object& counts,
+                              const std::string& parts, u32 d_n, u64 cap, u32 ucap) {
+    const std::vector<PackedKey> k = keys_from_blob(keys);
+    std::vector<u64> c;
+    if (!counts.is_none()) c = counts.cast<std::vector<u64>>();
+    const std::vector<u8> p(parts.begin(), parts.end());
+    DictStageDense r;
+    {
+      py::gil_scoped_release nogil;
+      r = dict_stage_part_build(k, counts.is_none() ? nullptr : &c, p, d_n, cap, ucap);
+    }
+    return dict_dense_dict(r, true);
+  }, py::arg("keys"), py::arg("counts"), py::arg("parts"), py::arg("d_n"), py::arg("cap"),
+        py::arg("ucap"),
+        "launch_dict_part_build: the dense view as dict_insert's, with uval / urank of the "
+        "dense ids.");
+  m.def("dict_rank", [](const std::string& keys, const py::object& counts, u32 d_u, u64 cap) {
+    const std::vector<PackedKey> k = keys_from_blob(keys);
+    std::vector<u64> c;
+    if (!counts.is_none()) c = counts.cast<std::vector<u64>>();
+    DictStageRank r;
+    {
+      py::gil_scoped_release nogil;
+      r = dict_stage_rank(k, counts.is_none() ? nullptr : &c, d_u, cap);
+    }
+    py::dict d;
+    d["rank"] = r.rank;
+    d["val"] = r.val;
+    d["tail_intact"] = r.tail_intact;
+    return d;
+  }, py::arg("keys"), py::arg("counts"), py::arg("d_u"), py::arg("cap"),
+        "launch_rank_sort on zeroed rank / val: both whole arrays (cap entries).");
+  m.def("dict_emit", [](const std::string& keys, const std::vector<u64>& counts,
+                        const std::vector<u32>& rank, const std::vector<u64>& val,
+                        const py::dict& ctr, u64 cap) {
+    const std::vector<PackedKey> k = keys_from_blob(keys);
+    const DictStageCounters c = stage_counters_from(ctr);
+    DictStageEmit r;
+    {
+      py::gil_scoped_release nogil;
+      r = dict_stage_emit(k, counts, rank, val, c, cap);
+    }
+    py::dict d;
+    d["keys"] = blob_from_keys(r.records.data(), r.records.size());
+    d["counts"] = counts_of(r.records);
+    d["ctr_out"] = stage_counters_dict(r.ctr_out);
+    d["tail_intact"] = r.tail_intact;
+    d["untouched"] = r.untouched;
+    return d;
+  }, py::arg("keys"), py::arg("counts"), py::arg("rank"), py::arg("val"), py::arg("ctr"),
+        py::arg("cap"),
+        "launch_rank_emit: the records [0, min(num_unique, cap)), ctr_out field by field, "
+        "whether the output behind the records (tail_intact) or all of it (untouched) still "
+        "holds the pattern.");
+  m.def("dict_scatter", [](const std::string& keys, const std::vector<u64>& counts,
+                           const std::vector<u32>& rank, u32 d_u, u64 cap) {
+    const std::vector<PackedKey> k = keys_from_blob(keys);
+    DictStageScatter r;
+    {
+      py::gil_scoped_release nogil;
+      r = dict_stage_scatter(k, counts, rank, d_u, cap);
+    }
+    py::dict d;
+    d["keys"] = blob_from_keys(r.sorted.data(), r.sorted.size());
+    d["counts"] = r.counts;
+    d["tail_intact"] = r.tail_intact;
+    return d;
+  }, py::arg("keys"), py::arg("counts"), py::arg("rank"), py::arg("d_u"), py::arg("cap"),
+        "launch_rank_scatter: the whole sorted keys / counts (cap entries, pattern where "
+        "unwritten).");
+  m.def("dict_scan_pack", [](const std::string& keys, const std::vector<u64>& counts,
+                             u32 num_unique, u64 cap, u32 emit_limit, bool with_ctr_out,
+                             const py::dict& ctr) {
+    const std::vector<PackedKey> k = keys_from_blob(keys);
+    DictStageCounters c = stage_counters_from(ctr);
+    c.num_unique = num_unique;
+    DictStageScanPack r;
+    {
+      py::gil_scoped_release nogil;
+      r = dict_stage_scan_pack(k, counts, c, cap, emit_limit, with_ctr_out);
+    }
+    py::dict d;
+    d["keys"] = blob_from_keys(r.records.data(), r.records.size());
+    d["counts"] = counts_of(r.records);
+    d["total_count"] = r.total_count;
+    d["ctr_out"] = stage_counters_dict(r.ctr_out);
+    d["tail_intact"] = r.tail_intact;
+    d["untouched"] = r.untouched;
+    return d;
+  }, py::arg("keys"), py::arg("counts"), py::arg("num_unique"), py::arg("cap"),
+        py::arg("emit_limit") = 0xFFFFFFFFu, py::arg("with_ctr_out") = true,
+        py::arg("ctr") = py::dict(),
+        "launch_scan_pack on zeroed look-back scratch: the records [0, num_unique), "
+        "ctr.total_count (pattern bytes if unwritten), ctr_out, tail_intact, untouched.");
+  m.def("part_plan", [](const std::vector<u64>& w0, const std::vector<u64>& counts, u32 d_u,
+                        u32 ucap) {
+    py::gil_scoped_release nogil;
+    return dict_stage_part_plan(w0, counts, d_u, ucap);
+  }, py::arg("w0"), py::arg("counts"), py::arg("d_u"), py::arg("ucap"),
+        "launch_part_plan over first words and sample counts: the 257 range starts.");
   m.def("write_spill",
         [](const std::string& path, const std::vector<std::pair<std::string, u64>>& recs,
            const std::string& fmt) {

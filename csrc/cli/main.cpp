@@ -26,6 +26,8 @@
 //   --rank K (with --search: each query's K best lines with their scores, best first)
 //   --wildcard (with --search: a word that ends in * is a prefix term, "ham*")
 //   --glob (with --search: * and ? anywhere in a word, "*ing", "h?mlet"; a superset of --wildcard)
+//   --fuzzy (with --search: a word that ends in ~1 or ~2 also finds the words within that many
+//            byte edits of it, "Hamlet~1", "quene~2")
 //   --ignore-case (with --search: the ASCII letters of every word match either case)
 //   --show N (with --search: under each query's line, every returned line's first N bytes)
 //   --mark (with --show: the matching tokens of a shown line stand between >> and <<)
@@ -105,6 +107,7 @@ struct CliArgs {
   u64 rank = 0;  // --rank K: every query answers its K best lines, scored (0: all its lines)
   bool wildcard = false;  // --wildcard: a --search word that ends in * is a prefix term
   bool glob = false;      // --glob: * and ? anywhere in a --search word (pattern terms)
+  bool fuzzy = false;     // --fuzzy: a --search word that ends in ~1 or ~2 is a fuzzy term
   bool ignore_case = false;  // --ignore-case: the batch's ASCII letters match either case
   u64 show = 0;       // --show N: the returned lines' first N bytes (0: line numbers only)
   bool mark = false;  // --mark: the shown lines' matching tokens between >> and <<
@@ -183,11 +186,20 @@ void help() {
       "                             is one of stars alone.  With every --match, --rank, --not,\n"
       "                             --within and --backend cpu; --rank then takes\n"
       "                             --emits-per-line <= 8192)\n"
+      "  --fuzzy                    (--search: a word that ends in ~1 or ~2 stands for every word\n"
+      "                             within that many edits of what precedes the ~ -- one byte\n"
+      "                             inserted, deleted or replaced is one edit: \"Hamlet~1\" finds\n"
+      "                             Hamlet! and [Hamlet too, \"quene~2\" finds queen.  It counts as\n"
+      "                             one word whose lines are all of theirs; the device scans the\n"
+      "                             dictionary for them.  The word is never cut and is longer than\n"
+      "                             its budget; another digit than 1 or 2 is refused, and so is a *\n"
+      "                             or ? in the word under --wildcard or --glob.  A ~ anywhere else\n"
+      "                             is literal.  With everything --glob goes with, and --glob)\n"
       "  --show N                   (--search: under each query's result line, one line per\n"
       "                             returned line: two spaces, its number, \": \" and its first N\n"
       "                             bytes, 1 <= N <= 65536; the lines are gathered on the device.\n"
       "                             With every --match, --rank (the winners, in rank order),\n"
-      "                             --not, --wildcard, --glob and --ignore-case)\n"
+      "                             --not, --wildcard, --glob, --fuzzy and --ignore-case)\n"
       "  --mark                     (--show: every token of a shown line that matches one of the\n"
       "                             query's words -- not its --not words -- stands between >>\n"
       "                             and <<, as far as it lies inside the N bytes)\n"
@@ -341,6 +353,8 @@ bool parse(int argc, char** argv, CliArgs* a) {
       a->wildcard = true;
     } else if (s == "--glob") {
       a->glob = true;
+    } else if (s == "--fuzzy") {
+      a->fuzzy = true;
     } else if (s == "--ignore-case") {
       a->ignore_case = true;
     } else if (s == "--show") {
@@ -429,6 +443,8 @@ bool parse(int argc, char** argv, CliArgs* a) {
     throw Error("--wildcard selects how --search reads a word that ends in *: give --search too");
   if (a->glob && a->search_args.empty())
     throw Error("--glob selects how --search reads * and ? in a word: give --search too");
+  if (a->fuzzy && a->search_args.empty())
+    throw Error("--fuzzy selects how --search reads a word that ends in ~1 or ~2: give --search too");
   if (a->ignore_case && a->search_args.empty())
     throw Error("--ignore-case selects how --search compares letters: give --search too");
   if (a->show && a->search_args.empty())
@@ -465,10 +481,21 @@ bool parse(int argc, char** argv, CliArgs* a) {
   const auto words = [&](const std::string& arg) {
     std::vector<std::string> terms;
     std::string cur;
-    for (const char c : arg) {
+    const auto delim = [&](char c) {
       // (--glob: a metacharacter is part of its word even when the job splits text at it)
       const bool meta = a->glob && (c == '*' || c == '?');
-      if (!meta && a->cfg.delimiters.find(c) != std::string::npos) {
+      return !meta && a->cfg.delimiters.find(c) != std::string::npos;
+    };
+    for (size_t i = 0; i < arg.size(); ++i) {
+      const char c = arg[i];
+      // (--fuzzy: so is a word's trailing ~d, the `~` and the digit)
+      if (a->fuzzy && c == '~' && !cur.empty() && i + 1 < arg.size() && arg[i + 1] >= '0' &&
+          arg[i + 1] <= '9' && (i + 2 == arg.size() || delim(arg[i + 2]))) {
+        cur.push_back(c);
+        cur.push_back(arg[++i]);
+        continue;
+      }
+      if (delim(c)) {
         if (!cur.empty()) terms.push_back(cur);
         cur.clear();
       } else {
@@ -488,7 +515,8 @@ bool parse(int argc, char** argv, CliArgs* a) {
     if (terms.empty()) throw Error("--search \"" + arg + "\" holds no word");
     // (a --not that holds no word excludes nothing)
     const std::vector<std::string> exclude = words(a->not_args[i]);
-    a->queries.push_back(make_search_query(terms, mode, a->wildcard, a->within, exclude, a->glob));
+    a->queries.push_back(make_search_query(terms, mode, a->wildcard, a->within, exclude, a->glob,
+                                           a->fuzzy));
   }
   if (!a->queries.empty()) {
     check_search_queries(a->queries, a->cfg);

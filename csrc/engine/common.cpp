@@ -11,6 +11,7 @@
 #include <thread>
 
 #include "locust/config.hpp"
+#include "locust/device/fuzzy.hpp"
 #include "locust/device/glob.hpp"
 #include "locust/dstring.hpp"
 #include "locust/engine.hpp"
@@ -383,17 +384,43 @@ PackedKey search_term_key(const std::string& term, const JobConfig& cfg) {
 
 SearchQuery make_search_query(const std::vector<std::string>& terms, SearchMode mode,
                               bool wildcard, u64 within, const std::vector<std::string>& exclude,
-                              bool glob) {
+                              bool glob, bool fuzzy) {
   SearchQuery q;
   q.terms = terms;
   q.terms.insert(q.terms.end(), exclude.begin(), exclude.end());
   q.excluded = (u32)exclude.size();
   q.mode = mode;
   q.within = within;
+  // the fuzzy reading comes first: a trailing ~d, and the word before it
+  std::vector<u8> fz(q.terms.size(), 0);
+  if (fuzzy) {
+    bool any_fuzzy = false;
+    for (size_t t = 0; t < q.terms.size(); ++t) {
+      std::string& s = q.terms[t];
+      if (s.size() < 3 || s[s.size() - 2] != '~' || s.back() < '0' || s.back() > '9') continue;
+      const u32 d = (u32)(s.back() - '0');
+      LOCUST_CHECK_ARG(d >= 1 && d <= kFuzzyMaxBudget,
+                       "search: the fuzzy term " + s + " asks for a budget of " +
+                           std::to_string(d) + " edits; a budget is 1 or 2 (word~1, word~2)");
+      s.resize(s.size() - 2);
+      LOCUST_CHECK_ARG(s.size() > (size_t)d,
+                       "search: the fuzzy term " + s + "~" + std::to_string(d) + " has a word of " +
+                           std::to_string(s.size()) + " bytes; a fuzzy term's word is longer than "
+                           "its budget (it would match every word of up to " +
+                           std::to_string(s.size() + d) + " bytes)");
+      LOCUST_CHECK_ARG(!(glob || wildcard) || s.find_first_of("*?") == std::string::npos,
+                       "search: the fuzzy term " + s + "~" + std::to_string(d) + " holds a * or a "
+                       "? while wildcard or glob is on; a term is fuzzy or a pattern, never both");
+      fz[t] = (u8)d;
+      any_fuzzy = true;
+    }
+    if (any_fuzzy) q.fuzzy = fz;
+  }
   if (glob) {
     bool any_prefix = false, any_pattern = false;
     std::vector<u8> prefix(q.terms.size(), 0), pattern(q.terms.size(), 0);
     for (size_t t = 0; t < q.terms.size(); ++t) {
+      if (fz[t]) continue;  // a fuzzy term: its word is literal
       std::string& s = q.terms[t];
       std::string c;  // runs of stars collapsed
       for (const char ch : s)
@@ -420,6 +447,7 @@ SearchQuery make_search_query(const std::vector<std::string>& terms, SearchMode 
   bool any = false;
   std::vector<u8> prefix(q.terms.size(), 0);
   for (size_t t = 0; t < q.terms.size(); ++t) {
+    if (fz[t]) continue;  // a fuzzy term: its word is literal
     std::string& s = q.terms[t];
     LOCUST_CHECK_ARG(s != "*", "search: a lone * is no prefix term: give the prefix before "
                                "the star (ham*)");
@@ -462,10 +490,33 @@ void check_search_queries(const std::vector<SearchQuery>& queries, const JobConf
                      "search: query " + std::to_string(i) + " has " +
                          std::to_string(q.pattern.size()) + " pattern flags for " +
                          std::to_string(q.terms.size()) + " terms; give none or one per term");
+    LOCUST_CHECK_ARG(q.fuzzy.empty() || q.fuzzy.size() == q.terms.size(),
+                     "search: query " + std::to_string(i) + " has " +
+                         std::to_string(q.fuzzy.size()) + " fuzzy budgets for " +
+                         std::to_string(q.terms.size()) + " terms; give none or one per term");
     for (size_t ti = 0; ti < q.terms.size(); ++ti) {
       const std::string& t = q.terms[ti];
       LOCUST_CHECK_ARG(!t.empty(), "search: query " + std::to_string(i) + " has an empty term");
       const bool pat = q.is_pattern(ti);
+      if (const u32 d = q.fuzzy_budget(ti)) {
+        LOCUST_CHECK_ARG(!q.is_prefix(ti) && !pat,
+                         "search: term " + std::to_string(ti) + " of query " + std::to_string(i) +
+                             " is flagged as a fuzzy term and as a prefix or pattern term; it is "
+                             "one or the other");
+        LOCUST_CHECK_ARG(d <= kFuzzyMaxBudget,
+                         "search: the fuzzy term " + t + " of query " + std::to_string(i) +
+                             " has a budget of " + std::to_string(d) +
+                             " edits; a budget is 1 or 2");
+        LOCUST_CHECK_ARG(t.size() > (size_t)d,
+                         "search: the fuzzy term " + t + "~" + std::to_string(d) + " of query " +
+                             std::to_string(i) + " has a word of " + std::to_string(t.size()) +
+                             " bytes; a fuzzy term's word is longer than its budget");
+        LOCUST_CHECK_ARG(t.size() <= (size_t)cfg.max_key_len,
+                         "search: the fuzzy term " + t + "~" + std::to_string(d) + " of query " +
+                             std::to_string(i) + " has a word of " + std::to_string(t.size()) +
+                             " bytes; a fuzzy term's word is never cut and takes at most "
+                             "max_key_len = " + std::to_string(cfg.max_key_len));
+      }
       if (pat) {
         LOCUST_CHECK_ARG(!q.is_prefix(ti), "search: term " + std::to_string(ti) + " of query " +
                                                std::to_string(i) +
@@ -502,12 +553,22 @@ void check_search_merge(u64 queries, u64 elements) {
 bool search_term_pattern(const SearchQuery& q, size_t t, const JobConfig& cfg, bool ignore_case,
                          SearchPattern* out) {
   const bool pat = q.is_pattern(t);
-  if (!pat && !ignore_case) return false;
+  const u32 budget = q.fuzzy_budget(t);
+  if (!pat && !budget && !ignore_case) return false;
   if (!out) return true;
   const std::string& s = q.terms[t];
   char bytes[kKeyBytes];
   u32 meta = 0;
   int n = 0;
+  if (budget) {  // the word as asked, every byte literal: never cut (check_search_queries)
+    for (; n < (int)s.size() && n < kKeyBytes; ++n) bytes[n] = s[(size_t)n];
+    if (ignore_case)
+      for (int i = 0; i < n; ++i)
+        if (bytes[i] >= 'A' && bytes[i] <= 'Z') bytes[i] = (char)(bytes[i] | 0x20);
+    pack_key(bytes, n, out->p.w);
+    out->meta = kFuzzyMeta | budget;
+    return true;
+  }
   if (pat) {  // as asked: never cut (check_search_queries), star runs collapsed
     for (const char ch : s) {
       if (n == kKeyBytes) break;
@@ -537,6 +598,13 @@ bool search_has_patterns(const std::vector<SearchQuery>& queries, bool ignore_ca
   for (const SearchQuery& q : queries)
     for (const u8 f : q.pattern)
       if (f) return true;
+  return search_has_fuzzy(queries);
+}
+
+bool search_has_fuzzy(const std::vector<SearchQuery>& queries) {
+  for (const SearchQuery& q : queries)
+    for (const u8 d : q.fuzzy)
+      if (d) return true;
   return false;
 }
 
@@ -545,7 +613,7 @@ void check_search_rank(u64 rank_k, const JobConfig& cfg, bool patterns) {
   LOCUST_CHECK_ARG(rank_k <= 0xffffffffull,
                    "search: rank takes 1 <= K < 2^32, not " + std::to_string(rank_k));
   LOCUST_CHECK_ARG(!patterns || (u64)cfg.emits_per_line <= kRankMaxEmits / kSearchMaxTerms,
-                   "search: a ranked search with a pattern term (glob, ignore_case) takes "
+                   "search: a ranked search with a pattern term (glob, fuzzy, ignore_case) takes "
                    "emits_per_line <= kRankMaxEmits / " + std::to_string(kSearchMaxTerms) + " = " +
                        std::to_string(kRankMaxEmits / kSearchMaxTerms) +
                        " (pattern terms' lists may overlap: a score reaches 32 * emits_per_line "
@@ -583,7 +651,7 @@ struct TokenTerms {
 // Does the token match term j?
 bool token_matches(const PackedKey& tok, size_t j, const TokenTerms& tt) {
   if (!tt.pats.empty() && tt.is_pat[j])
-    return glob_match(tt.pats[j].p.w, tt.pats[j].meta, tok.w, tt.fold);
+    return term_match(tt.pats[j].p.w, tt.pats[j].meta, tok.w, tt.fold);
   if (tt.masks.empty()) return key_compare(tok.w, tt.keys[j].w) == 0;
   bool same = true;
   for (int i = 0; i < kKeyWords; ++i) same &= (tok.w[i] & tt.masks[j].w[i]) == tt.keys[j].w[i];
@@ -793,7 +861,7 @@ SearchResult search_index_impl(const IndexResult& x, const TextInput* text,
         std::vector<size_t> words;
         u64 len = 0;
         for (size_t i = 0; i < n; ++i)
-          if (glob_match(sp.p.w, sp.meta, ent[i].key.w, ignore_case)) {
+          if (term_match(sp.p.w, sp.meta, ent[i].key.w, ignore_case)) {
             words.push_back(i);
             len += ent[i].count;
           }
@@ -1059,6 +1127,10 @@ void format_search_output(const SearchResult& r, std::string* out, bool mark) {
       out->push_back(' ');
       out->append(r.queries[q].terms[t]);
       if (r.queries[q].is_prefix(t)) out->push_back('*');
+      if (const u32 d = r.queries[q].fuzzy_budget(t)) {
+        out->push_back('~');
+        out->push_back((char)('0' + d));
+      }
     }
     out->append(" \t hits: ");
     out->append(std::to_string(r.rank_k ? r.matches[q] : r.offsets[q + 1] - r.offsets[q]));

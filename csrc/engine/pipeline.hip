@@ -4,6 +4,8 @@
 // here instead of in every translation unit that includes the header.
 #include "pipeline.hpp"
 
+#include "locust/device/fuzzy.hpp"
+
 namespace locust {
 namespace detail {
 
@@ -2307,6 +2309,9 @@ void DevicePipeline::search_stage(const std::vector<SearchQuery>& queries, u64 r
   const bool patterns = Q != 0 && search_has_patterns(queries, ignore_case);
   if (patterns) ensure_search_patterns();
   sbatch.pat = patterns ? d_spat : nullptr;
+  // ... and one with a fuzzy term (engine.hpp "fuzzy terms") the kernels compiled with both
+  // matchers (kernels.hpp "fuzzy.hip"): per batch, so the next one is routed afresh
+  sbatch.fuzzy = patterns && search_has_fuzzy(queries);
   LOCUST_HIP_CHECK(hipEventRecord(ev_search[0], stream));
   if (Q == 0) {
     LOCUST_HIP_CHECK(hipEventRecord(ev_search[1], stream));
@@ -2346,6 +2351,8 @@ void DevicePipeline::search_stage(const std::vector<SearchQuery>& queries, u64 r
         // the slot's key words (q_meta's prefix bit stays clear: a prefix term under
         // ignore_case is the pattern p*)
         h_spat[q] |= (1u << t) | (ignore_case ? kSearchFold : 0u);
+        // (a fuzzy term: its word in the key words, kFuzzyMeta | its budget as the map)
+        if (sp.meta & kFuzzyMeta) h_spat[q] |= 1u << (kSearchFuzzyShift + (int)t);
         h_spat[kSearchPatMeta + (u64)q * kSearchMaxTerms + t] = sp.meta;
         std::memcpy(keys + ((u64)q * kSearchMaxTerms + t) * kKeyWords, sp.p.w, sizeof(PackedKey));
         continue;

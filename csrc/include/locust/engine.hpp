@@ -524,6 +524,47 @@ void format_index_output(const IndexResult& r, std::string* out);
 // "search.hip": match, scatter): (pattern slots) x (dictionary words) matcher calls per batch,
 // twice for the slots that cover two or more words.
 //
+// ---- fuzzy terms: `Hamlet~1`, `quene~2` ----
+// A term may be a fuzzy term of a word w with a budget d (SearchQuery::fuzzy[t] == d, 1 or 2,
+// terms[t] holding w without the suffix).  make_search_query's `fuzzy` makes them, and only it:
+// without it `Hamlet~1` is the literal word it has always been.
+//   Syntax.  With `fuzzy`, a term t of three or more bytes whose last byte is a decimal digit
+//     and whose last byte but one is `~` is the fuzzy term of w = t without its last two bytes
+//     and d = the digit.  d must be 1 or 2: any other digit is refused.  A `~` anywhere else is
+//     a literal byte of its word: with no digit behind it, with two digits behind it, or with
+//     `~1` in the middle of a word.  This reading comes before the wildcard and glob reading of
+//     the term.
+//   The word.  w is validated byte for byte as a term is: no NUL, no newline, no delimiter.  w
+//     is never cut: len(w) > max_key_len is refused, as for a pattern.  w must be longer than
+//     its budget: len(w) <= d is refused (`a~1` would match every word of one or two bytes).
+//     With glob or wildcard also on, a w that holds `*` or `?` is refused: a term is fuzzy or a
+//     pattern, never both.  `fuzzy` does not imply wildcard or glob, and combines with both and
+//     with ignore_case.
+//   Words.  A fuzzy term's words are the index keys k, as the index holds them (cut to
+//     max_key_len, their length the bytes before the NUL padding), with lev(w, k) <= d.  lev is
+//     the Levenshtein distance over bytes: one insertion, deletion or substitution of a byte
+//     costs 1; there is no transposition and no UTF-8 awareness.  Two bytes are equal as the
+//     pattern matcher's literal bytes are (glob_byte_eq): under the batch's ignore_case ASCII
+//     letters match either case, and nothing else folds.  A long word cut to max_key_len
+//     matches as its merged key, the rule the index uses everywhere.  (device/fuzzy.hpp: the
+//     one matcher both engines use.)
+//   Everything else is a pattern term's rule with this matcher in place of the pattern's.  The
+//     term's list is the multiset union of its words' postings, its count the sum of their
+//     counts, and without a word it is absent.  In `all`, `any`, exclusion and the candidate
+//     stage it is a word with that list; in `phrase` and `near` verification and in show spans a
+//     token matches when its cut key is within d of w under the same fold.  search_has_patterns
+//     is true for a batch that holds a fuzzy term: the ranked bound is 32 * emits_per_line * 8,
+//     and a ranked batch is refused when emits_per_line > kRankMaxEmits / 8.  `merged` counts a
+//     fuzzy term that covers two or more words and repeats no earlier term of its query; one
+//     with exactly one word uses that list in place.  The `any`-bound overflow rule holds.
+//   Identity.  Two fuzzy terms of a query are the same term when their w bytes and their budget
+//     are equal -- under ignore_case: the bytes after lower-casing ASCII.  `ham~1` and `ham~2`
+//     are different terms.  A fuzzy term is never the same as a plain, prefix or pattern term,
+//     and takes no part in the laminar nesting rule.
+//   term_counts keep their order, and format_search_output prints the term as asked: `Hamlet~1`.
+// The device finds a fuzzy term's words by the pattern terms' scan of the dictionary, and a
+// batch that holds one runs kernels compiled with both matchers (kernels.hpp "fuzzy.hip").
+//
 // ---- show: the returned lines' text and match spans ----
 // A search job may ask for show = N, a u32 with 1 <= N <= kShowMaxBytes = 65536; show == 0,
 // the default, is the answer described above, bit for bit.  With show = N every entry i of
@@ -568,7 +609,10 @@ struct SearchQuery {
   std::vector<u8> prefix;  // empty: no prefix term; else parallel to terms, != 0: a prefix term
   u32 excluded = 0;  // the last `excluded` entries of terms are exclusion terms ("not")
   std::vector<u8> pattern;  // empty: no pattern term; else parallel to terms, != 0: a pattern term
+  std::vector<u8> fuzzy;  // empty: no fuzzy term; else parallel to terms, 1 or 2: a fuzzy term's
+                          // budget (terms[t]: its word, without the `~d`), 0: none
   bool is_prefix(size_t t) const { return t < prefix.size() && prefix[t] != 0; }
+  u32 fuzzy_budget(size_t t) const { return t < fuzzy.size() ? fuzzy[t] : 0u; }
   bool is_pattern(size_t t) const { return t < pattern.size() && pattern[t] != 0; }
   // the positive terms: terms[0 .. positives())
   size_t positives() const { return excluded < terms.size() ? terms.size() - excluded : 0; }
@@ -621,24 +665,32 @@ inline bool search_term_prefix(const SearchQuery& q, size_t t, const JobConfig& 
 // within: the window of a `near` query (0: none).  exclude: the query's exclusion terms, read
 // as `terms` are and appended behind them.  glob: "pattern terms" above (runs of `*` collapse;
 // a lone star, or a run of them, is an error); with glob, wildcard changes nothing.
+// fuzzy: "fuzzy terms" above (a trailing `~1` or `~2` makes a fuzzy term, read before the
+// wildcard and glob reading; another digit, a word no longer than its budget and -- with
+// wildcard or glob -- a word that holds `*` or `?` are errors).
 SearchQuery make_search_query(const std::vector<std::string>& terms, SearchMode mode,
                               bool wildcard, u64 within = 0,
-                              const std::vector<std::string>& exclude = {}, bool glob = false);
+                              const std::vector<std::string>& exclude = {}, bool glob = false,
+                              bool fuzzy = false);
 // A term as the pattern it is evaluated as: the packed bytes (kv.hpp) and the map of its
-// metacharacters (device/glob.hpp).
+// metacharacters (device/glob.hpp) -- a fuzzy term: its word's bytes and kFuzzyMeta | its
+// budget (device/fuzzy.hpp; term_match evaluates either kind).
 struct SearchPattern {
   PackedKey p;
   u32 meta = 0;
 };
-// Is term t of q evaluated as a pattern term -- a pattern term, or any term under
+// Is term t of q evaluated as a pattern term -- a pattern term, a fuzzy term, or any term under
 // ignore_case?  If so *out (when given) is its pattern: a pattern term's bytes as asked, a
 // prefix term's cut prefix and a star, a plain term's cut bytes, all literal; under ignore_case
 // with the ASCII letters lower-cased (two terms are the same term when their patterns are
 // equal).
 bool search_term_pattern(const SearchQuery& q, size_t t, const JobConfig& cfg, bool ignore_case,
                          SearchPattern* out = nullptr);
-// Does a batch of these queries hold a term that is evaluated as a pattern term?
+// Does a batch of these queries hold a term that is evaluated as a pattern term?  (A fuzzy
+// term is.)
 bool search_has_patterns(const std::vector<SearchQuery>& queries, bool ignore_case);
+// Does it hold a fuzzy term?
+bool search_has_fuzzy(const std::vector<SearchQuery>& queries);
 // Throws unless every query has 1..kSearchMaxTerms valid terms for cfg's delimiter set, at
 // least one of them positive (and `prefix` empty or as long as `terms`), a `near` query a
 // window in [1, kSearchMaxWithin] and every other query none (within == 0).
@@ -682,7 +734,8 @@ SearchResult search_index(const IndexResult& x, const TextInput& text,
 void validate_search(const SearchResult& r);
 // The result lines of a search, one per query:
 //   "print query: <terms joined by one space> \t hits: <h> \t lines: <l0> <l1> ...\n"
-// (a prefix term as it was asked: with its star; a pattern term as it was asked, too;
+// (a prefix term as it was asked: with its star; a pattern term as it was asked, too; a fuzzy
+// term with its `~d`;
 // <terms> are the positive terms, and a query
 // with exclusion terms prints " \t not: <those joined by one space>" before " \t hits:")
 // ranked (hits: the matches; nothing after "top:" when nothing matched):

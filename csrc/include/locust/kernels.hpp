@@ -742,7 +742,9 @@ void launch_index(const IndexJob& job, IndexWorkspace& ws, SortPlan* h_plan, hip
 //            (search_globphrase_kernel, search_globnear_kernel: the same bodies, compiled with
 //            the matcher): a token matches a pattern term when glob_match says so of its cut
 //            key, with the batch's fold; plain and prefix terms of such a batch match as ever.
-//            Every other batch runs the kernels it ran before, at their resources
+//            Every other batch runs the kernels it ran before, at their resources.  A batch
+//            that has a fuzzy term runs fuzzy.hip's match, scatter, phrase and near kernels:
+//            the same bodies once more, with the fuzzy matcher beside the pattern matcher
 //   seal    one thread: the sort's length, capped by the workspace
 //   (the host reads the number of hits H: the sort takes its regime from it)
 //   order    radix_sort() of the pair words as one-word keys
@@ -807,7 +809,14 @@ constexpr u32 kSearchSlots = kSearchMaxQueries * kSearchMaxTerms;  // (query, te
 //          distinct, and the index holds fewer postings than that)
 //   rank   [kSearchSlots] the rank of one matching word (the word, when there is just one)
 //   cursor [kSearchSlots] the scatter kernel's fill of the slot's part of [0, X)
+// A fuzzy term (engine.hpp "fuzzy terms") is a pattern slot too: its flag bit t is set, so the
+// lookup, gather and strip stages treat it as they treat any pattern slot, and besides
+//   flags  bit kSearchFuzzyShift + t: the slot's `keys` words hold the word w, no pattern
+//   meta   kFuzzyMeta | d (device/fuzzy.hpp): the budget, and a bit no metacharacter map has,
+//          so a fuzzy slot never compares equal to a pattern slot in the lookup's identity rule
+// A batch with such a bit sets SearchBatch::fuzzy and runs fuzzy.hip's kernels.
 constexpr u32 kSearchFold = 1u << 8;
+constexpr int kSearchFuzzyShift = 16;
 constexpr u64 kSearchPatMeta = kSearchMaxQueries;
 constexpr u64 kSearchPatWords = kSearchPatMeta + kSearchSlots;
 constexpr u64 kSearchPatLen = kSearchPatWords + kSearchSlots;
@@ -859,6 +868,9 @@ struct SearchBatch {
   u32* pat = nullptr;      // the pattern arrays (above) of a batch that has a pattern term; null
                            // in every other batch (the engine sets it per batch), and then no
                            // pattern stage runs
+  bool fuzzy = false;      // the batch has a fuzzy term (pat is set, too): the dictionary scan,
+                           // the verify and the show kernels are fuzzy.hip's (the engine sets it
+                           // per batch)
   u32* q_bound = nullptr;  // [Q]
   u64* q_start = nullptr;  // [Q + 1]
   u64* offsets = nullptr;  // [Q + 1]
@@ -941,7 +953,7 @@ void launch_search_rank(const SearchIndex& ix, const SearchBatch& b, u32 queries
 //            a determined place: no atomics, no compaction.  An entry whose spans do not number
 //            what measure counted adds to ShowCounters::mismatch (the host throws)
 // A batch that has a pattern term runs the siblings compiled with the matcher
-// (show_globmeasure_kernel, show_globwrite_kernel).
+// (show_globmeasure_kernel, show_globwrite_kernel); one with a fuzzy term fuzzy.hip's.
 struct ShowCounters {  // zeroed per show batch
   u64 text;       // T: the payload's text bytes
   u64 spans;      // S: its span triples
@@ -974,6 +986,28 @@ void launch_show_measure(const SearchIndex& ix, const SearchBatch& b, u32 querie
 void launch_show_write(const SearchIndex& ix, const SearchBatch& b, u32 queries, const u32* lines,
                        const u64* offsets, u64 entries, const ShowBuffers& sb, hipStream_t s);
 
+// ---------------- fuzzy.hip ----------------
+// The kernels of a batch that has a fuzzy term (engine.hpp "fuzzy terms"; SearchBatch::fuzzy):
+// the bodies search.hip and show.hip instantiate (device/dictscan.hpp, device/verify.hpp,
+// device/showwalk.hpp), compiled once more with the fuzzy matcher (device/fuzzy.hpp) beside the
+// pattern matcher -- such a batch may hold pattern terms and the fold as well:
+//   match    fuzzy_match_kernel: the dictionary scan; a fuzzy slot's words are the keys within
+//            its budget of its word
+//   scatter  fuzzy_scatter_kernel: the same walk and match over the wide slots
+//   phrase   fuzzy_phrase_kernel, near: fuzzy_near_kernel: a token matches a fuzzy term when
+//            its cut key is within the budget of the word, under the batch's fold
+//   show     fuzzy_showmeasure_kernel, fuzzy_showwrite_kernel: the same token rule
+// launch_search_lookup, launch_search_expand, launch_search_hits, launch_show_measure and
+// launch_show_write call these in place of their own kernels for such a batch, with the grids
+// and arguments of the siblings they replace; every other batch launches none of them.
+void launch_fuzzy_match(const SearchIndex& ix, const SearchBatch& b, u32 queries, hipStream_t s);
+void launch_fuzzy_scatter(const SearchIndex& ix, const SearchBatch& b, u32 queries, u64 x,
+                          const SearchHits& h, hipStream_t s);
+void launch_fuzzy_phrase(const SearchIndex& ix, const SearchBatch& b, u32 queries, u64 bound,
+                         const SearchHits& h, hipStream_t s);
+void launch_fuzzy_near(const SearchIndex& ix, const SearchBatch& b, u32 queries, u64 bound,
+                       const SearchHits& h, hipStream_t s);
+
 // ---- device self-test of the string library (tests only; StringTestOut in engine.hpp) ----
 void launch_string_selftest(const char* blob, const u32* off, u32 n, const char* delims,
                             const int* ints, StringTestOut* out, hipStream_t s);
@@ -986,6 +1020,7 @@ void launch_string_selftest(const char* blob, const u32* off, u32 n, const char*
 // 573 MB fat binary), +1.3 GB of host memory and ~150 ms per process.
 void warm_module_dict();
 void warm_module_exchange();
+void warm_module_fuzzy();  // (as search: the code object only, no buffers)
 void warm_module_index();  // (as topk below: the code object only, no buffers)
 void warm_module_map();
 void warm_module_merge();
@@ -1006,6 +1041,7 @@ void warm_module_topk();
 inline void warm_kernel_modules() {
   warm_module_dict();
   warm_module_exchange();
+  warm_module_fuzzy();
   warm_module_index();
   warm_module_map();
   warm_module_merge();

@@ -71,10 +71,12 @@
 // look-back); this file adds no polled word.
 #include <algorithm>
 
+#include "locust/device/dictscan.hpp"
 #include "locust/device/glob.hpp"
 #include "locust/device/linetok.hpp"
 #include "locust/device/rank.hpp"
 #include "locust/device/termmask.hpp"
+#include "locust/device/verify.hpp"
 #include "locust/device/wave.hpp"
 #include "locust/hip_check.hpp"
 #include "locust/kernels.hpp"
@@ -86,53 +88,14 @@ constexpr int kTerms = (int)kSearchMaxTerms;
 constexpr int kLookupQueries = kSearchBlock / kTerms;  // queries per lookup workgroup
 static_assert(kTerms == 8 && kSearchBlock % kTerms == 0, "eight term threads per query");
 static_assert(kSearchMaxQueries % kSearchBlock == 0, "the scan walks whole blocks");
-constexpr int kPhraseBlock = 256;
-constexpr int kPhraseWaves = kPhraseBlock / 64;
-constexpr int kPhraseMaxBlocks = 2048;  // 8 workgroups per CU
 
-// ---- pattern terms: the dictionary scan ----
-// The walk the match and the scatter kernel share: grid x strides over the records in tiles
-// of kSearchBlock, one record per thread; grid y takes every gridDim.y-th query.  A tile's
-// waves are whole (the tail's dead lanes match nothing), so every ballot below is converged.
-constexpr u32 kMatchMaxBlocks = 1024;  // the grid: x * y workgroups at most
-
+// ---- pattern terms: the dictionary scan (the bodies: device/dictscan.hpp) ----
 // words[slot] += the records the slot's pattern matches, len[slot] += their counts, rank[slot]
 // = one of them (pw: words | len | rank, zeroed per batch).
 __global__ __launch_bounds__(kSearchBlock) void search_match_kernel(
     const OutRecord* __restrict__ recs, u32 n, const u64* __restrict__ keys,
     const u32* __restrict__ pq, u32 Q, u32* __restrict__ pw) {
-  const int lane = dev::lane_id();
-  for (u32 base = blockIdx.x * kSearchBlock; base < n; base += gridDim.x * kSearchBlock) {
-    const u32 rank = base + threadIdx.x;
-    const bool live = rank < n;
-    u64 k0 = 0, k1 = 0, k2 = 0, k3 = 0;
-    u32 cnt = 0;
-    if (live) {
-      k0 = recs[rank].w[0];
-      k1 = recs[rank].w[1];
-      k2 = recs[rank].w[2];
-      k3 = recs[rank].w[3];
-      cnt = (u32)recs[rank].count;  // (the index holds < 2^32 postings in all)
-    }
-    for (u32 q = blockIdx.y; q < Q; q += gridDim.y) {  // (uniform)
-      const u32 fl = pq[q];
-      const bool fold = (fl & kSearchFold) != 0;
-      for (u32 pm = fl & 0xffu; pm; pm &= pm - 1u) {  // (uniform) the query's pattern terms
-        const u32 slot = q * kTerms + (u32)__ffs((int)pm) - 1u;
-        const u64* p = keys + (u64)slot * kKeyWords;
-        const bool m = live && glob_match(p[0], p[1], p[2], p[3], pq[kSearchPatMeta + slot], k0,
-                                          k1, k2, k3, fold);
-        const u64 bm = dev::ballot(m);
-        if (bm == 0) continue;  // (wave-uniform)
-        const u32 sum = dev::wave_reduce_sum(m ? cnt : 0u);
-        if (lane == __ffsll((unsigned long long)bm) - 1) {
-          atomicAdd(&pw[slot], (u32)__popcll(bm));
-          atomicAdd(&pw[kSearchSlots + slot], sum);
-          pw[2 * kSearchSlots + slot] = rank;
-        }
-      }
-    }
-  }
+  search_match_body<1>(recs, n, keys, pq, Q, pw);
 }
 
 __global__ __launch_bounds__(kSearchBlock) void search_lookup_kernel(
@@ -336,62 +299,16 @@ __global__ __launch_bounds__(kSearchBlock) void search_gather_kernel(
 }
 
 // The wide pattern slots' part of the keys (x_len != 0 and a pattern slot): the match kernel's
-// walk and match; the matching words of a wave and pattern take consecutive room in the slot's
-// part of [0, X) -- a wave prefix sum of their counts behind one atomic on the slot's cursor --
-// and the wave copies their postings word by word, 64 elements per step.  Reads stay inside
-// the CSR (a word's val range), writes inside [x_start[slot], x_start[slot + 1]), whatever
-// the cursor says: a slot that does not fill exactly counts as unmerged in the strip.
+// walk and match, and the whole wave copies each matching word's postings
+// (device/dictscan.hpp).
 __global__ __launch_bounds__(kSearchBlock) void search_scatter_kernel(
     const OutRecord* __restrict__ recs, u32 n, const u64* __restrict__ val,
     const u32* __restrict__ postings, u32 first_line, const u64* __restrict__ pkeys,
     const u32* __restrict__ pq, u32 Q, const u32* __restrict__ x_len,
     const u64* __restrict__ x_start, u64 X, u64 cap, u32* __restrict__ cursor,
     u64* __restrict__ keys) {
-  if (x_start[Q * kTerms] != X || X > cap) return;  // (uniform; as the gather kernel)
-  const int lane = dev::lane_id();
-  for (u32 base = blockIdx.x * kSearchBlock; base < n; base += gridDim.x * kSearchBlock) {
-    const u32 rank = base + threadIdx.x;
-    const bool live = rank < n;
-    u64 k0 = 0, k1 = 0, k2 = 0, k3 = 0;
-    u32 src = 0, cnt = 0;
-    if (live) {
-      k0 = recs[rank].w[0];
-      k1 = recs[rank].w[1];
-      k2 = recs[rank].w[2];
-      k3 = recs[rank].w[3];
-      src = (u32)val[rank];  // (the index holds < 2^32 postings in all)
-      cnt = (u32)(val[rank + 1] - val[rank]);
-    }
-    for (u32 q = blockIdx.y; q < Q; q += gridDim.y) {  // (uniform)
-      const u32 fl = pq[q];
-      const bool fold = (fl & kSearchFold) != 0;
-      for (u32 pm = fl & 0xffu; pm; pm &= pm - 1u) {  // (uniform) the query's pattern terms
-        const u32 slot = q * kTerms + (u32)__ffs((int)pm) - 1u;
-        if (x_len[slot] == 0u) continue;  // (uniform) not wide: nothing to merge
-        const u64* p = pkeys + (u64)slot * kKeyWords;
-        const bool m = live && glob_match(p[0], p[1], p[2], p[3], pq[kSearchPatMeta + slot], k0,
-                                          k1, k2, k3, fold);
-        u64 bm = dev::ballot(m);
-        if (bm == 0) continue;  // (wave-uniform)
-        const u32 mine = m ? cnt : 0u;
-        const u32 incl = dev::wave_inclusive_scan(mine);
-        const u32 total = (u32)__shfl((int)incl, 63, 64);
-        u32 at = 0;
-        if (lane == 0) at = atomicAdd(&cursor[slot], total);
-        at = (u32)__shfl((int)at, 0, 64) + incl - mine;  // this lane's word, inside the slot
-        const u64 lo = x_start[slot], hi = x_start[slot + 1];
-        for (; bm; bm &= bm - 1) {  // (wave-uniform) word by word, the whole wave copying
-          const int l = __ffsll((unsigned long long)bm) - 1;
-          const u32 wsrc = (u32)__shfl((int)src, l, 64);
-          const u32 wcnt = (u32)__shfl((int)cnt, l, 64);
-          const u64 dst = lo + (u32)__shfl((int)at, l, 64);
-          for (u32 i = (u32)lane; i < wcnt; i += 64u)
-            if (dst + i < hi)
-              keys[dst + i] = ((u64)slot << 32) | (u64)(postings[wsrc + i] - first_line);
-        }
-      }
-    }
-  }
+  search_scatter_body<1>(recs, n, val, postings, first_line, pkeys, pq, Q, x_len, x_start, X, cap,
+                         cursor, keys);
 }
 
 // merged[e] = first_line + the key's line; a key outside its slot's x_start range counts as
@@ -476,33 +393,6 @@ __device__ __forceinline__ const u32* term_list(const u32* __restrict__ postings
   return ((tv & kSearchMerged) ? merged : postings) + (tv & ~kSearchMerged);
 }
 
-// The hits of one converged wave step (hit: this lane has one, of query q on local line
-// rel_line): one atomic reserves the step's slots in `pairs`, one atomic per distinct query
-// of the wave adds to its hit count.
-__device__ __forceinline__ void commit_hits(bool hit, u32 q, u32 rel_line, u64* __restrict__ pairs,
-                                            u64 pair_cap, u32* __restrict__ q_hits,
-                                            SearchCounters* __restrict__ ctr) {
-  const int lane = dev::lane_id();
-  const u64 hm = dev::ballot(hit);
-  if (hm == 0) return;  // (wave-uniform)
-  const int first = __ffsll((unsigned long long)hm) - 1;
-  u32 at = 0;
-  if (lane == first) at = atomicAdd(&ctr->written, (u32)__popcll(hm));
-  at = (u32)__shfl((int)at, first, 64);
-  if (hit) {
-    const u64 slot = (u64)at + dev::lanes_below(hm);
-    if (slot < pair_cap) pairs[slot] = ((u64)q << 32) | (u64)rel_line;
-  }
-  // per query: one atomic for all of the wave's hits of that query
-  u64 rem = hm;
-  while (rem) {  // (wave-uniform)
-    const int leader = __ffsll((unsigned long long)rem) - 1;
-    const u32 ql = (u32)__shfl((int)q, leader, 64);
-    const u64 same = dev::ballot(hit && q == ql);
-    if (lane == leader) atomicAdd(&q_hits[ql], (u32)__popcll(same));
-    rem &= ~same;
-  }
-}
 
 __global__ __launch_bounds__(kSearchBlock) void search_hit_kernel(
     const u32* __restrict__ postings, const u32* __restrict__ merged, u32 first_line,
@@ -612,232 +502,9 @@ __global__ __launch_bounds__(kSearchBlock) void search_hit_kernel(
   }
 }
 
-// One wave per candidate; a wave takes `group` (<= 64) consecutive candidates per round,
-// grid-stride over the rounds.  The candidates' number comes from device memory (the hit
-// kernel's counter): no host round trip between the two kernels.  Lane i keeps candidate
-// i's verdict, so a round ends like a step of the hit kernel: ONE atomic for its slots and
-// one per distinct query -- one atomic per verified line would serialise on ctr->written as
-// index_map_kernel's comment (index.hip) records for 10^6 lines.
-template <bool kGlob>
-__device__ __forceinline__ void search_phrase_body(
-    unsigned char* row, u64* qk, u32* qm, const u32* __restrict__ pq,
-    const char* __restrict__ text, u64 bytes, const u64* __restrict__ nl_pos,
-    const MapCounters* __restrict__ lctr, const DelimMask& dm, int emits_per_line,
-    int max_key_len, u32 group, const u32* __restrict__ q_meta, const u64* __restrict__ keys,
-    u32 Q, const u64* __restrict__ cands, u64* __restrict__ pairs, u64 pair_cap,
-    u32* __restrict__ q_hits, SearchCounters* __restrict__ ctr) {
-  // row, qk, qm: this wave's LDS -- the line step, the query's term keys and (kGlob) its
-  // pattern terms' metacharacter maps; pq: the batch's pattern flags and maps (kGlob)
-  if (kGlob) {  // (in_vgprs: room in the scalar file for the matcher)
-    pq = in_vgprs(pq);
-    nl_pos = in_vgprs(nl_pos);
-    q_meta = in_vgprs(q_meta);
-    keys = in_vgprs(keys);
-    cands = in_vgprs(cands);
-    pairs = in_vgprs(pairs);
-    q_hits = in_vgprs(q_hits);
-    ctr = in_vgprs(ctr);
-    lctr = in_vgprs(lctr);
-  }
-  const int lane = dev::lane_id();
-  const u64 num_nl = lctr->num_newlines;
-  const u64 num_lines = bytes ? num_nl + 1 : 0;
-  const u64 C = ctr->cands <= pair_cap ? ctr->cands : 0;  // (an overflow: the host throws)
-  const u64 wave = (u64)blockIdx.x * kPhraseWaves + dev::wave_id();
-  const u64 nwaves = (u64)gridDim.x * kPhraseWaves;
-  const u64 below = lane ? (~0ull >> (64 - lane)) : 0ull;  // the lanes below this one
-  const u32 E = (u32)emits_per_line;
-  for (u64 g0 = wave * group; g0 < C; g0 += nwaves * group) {  // (wave-uniform)
-    const u32 cnt = (u32)(g0 + group < C ? group : C - g0);
-    const u64 mine = (u32)lane < cnt ? cands[g0 + lane] : 0ull;  // lane i: candidate i
-    bool hit = false;
-    u32 q_loaded = ~0u;  // the query whose term keys the wave's LDS row holds
-    for (u32 i = 0; i < cnt; ++i) {
-      const u32 q = (u32)__shfl((int)(u32)(mine >> 32), (int)i, 64);
-      const u64 line = (u32)__shfl((int)(u32)mine, (int)i, 64);
-      if (q >= Q || line >= num_lines) continue;  // (wave-uniform; never: the hit kernel's words)
-      const u32 meta = q_meta[q];
-      // the positive terms, which stand first: exclusion terms are no part of the match
-      const u32 m = (meta & 0xffu) - (u32)__popc(meta >> kSearchExcludeShift);
-      if (m == 0 || m > (u32)kTerms) continue;    // (never: the host checked the batch)
-      const u32 pre = (meta >> kSearchPrefixShift) & 0xffu;  // bit j: term j is a prefix term
-      const u32 pt = kGlob ? pq[q] : 0u;  // bit j: term j is a pattern term | kSearchFold
-      if (q != q_loaded) {  // (wave-uniform) neighbours mostly share their query
-        __builtin_amdgcn_wave_barrier();  // the previous candidate's key reads are done
-        if (lane < kTerms * kKeyWords) qk[lane] = keys[(u64)q * kTerms * kKeyWords + lane];
-        if (kGlob && lane < kTerms) qm[lane] = pq[kSearchPatMeta + (u64)q * kTerms + lane];
-        __builtin_amdgcn_wave_barrier();
-        q_loaded = q;
-      }
-      const u64 start = line ? nl_pos[line - 1] + 1 : 0;
-      const u64 end = line < num_nl ? nl_pos[line] : bytes;
-      const u32 accept = 1u << (m - 1);
-      u32 seen = 0;   // token starts of this line before the current step
-      u32 state = 0;  // bit j: the last j + 1 tokens equal terms 0 .. j
-      u64 carry = 0;
-      bool match = false;
-      for (u64 pos = start; pos < end && seen < E && !match; pos += 64) {
-        const u64 p = pos + lane;
-        const unsigned c = p < end ? (unsigned char)text[p] : 0u;
-        const u64 p2 = pos + 64 + lane;
-        const unsigned c2 = (lane < 32 && p2 < end) ? (unsigned char)text[p2] : 0u;
-        __builtin_amdgcn_wave_barrier();  // the previous step's key reads are done
-        row[lane] = (unsigned char)c;
-        if (lane < 32) row[64 + lane] = (unsigned char)c2;
-        __builtin_amdgcn_wave_barrier();
-        bool last;
-        const u64 starts = dev::step_starts(c, dm, &carry, &last);
-        const u32 ord = seen + (u32)__popcll(starts & below);
-        const bool emit = ((starts >> lane) & 1ull) && ord < E;
-        u32 eq = 0;  // bit j: this lane's token equals term j
-        if (emit) eq = token_term_mask<kGlob>(row, lane, dm, max_key_len, qk, m, pre, pt, qm);
-        // the automaton over the step's emitted tokens in order (all wave-uniform)
-        u64 em = dev::ballot(emit);
-        if (dev::ballot(eq != 0u) == 0) {
-          if (em) state = 0;  // no token of this step equals any term
-        } else {
-          while (em) {
-            const int tl = __ffsll((unsigned long long)em) - 1;
-            const u32 e = (u32)__shfl((int)eq, tl, 64);
-            state = ((state << 1) | 1u) & e;
-            if (state & accept) {
-              match = true;
-              break;
-            }
-            em &= em - 1;
-          }
-        }
-        seen += (u32)__popcll(starts);
-        if (last) break;  // a NUL, or the line end, inside this step
-      }
-      if ((u32)lane == i) hit = match;
-    }
-    if (lane == 0) atomicAdd(&ctr->verified, cnt);
-    commit_hits(hit, (u32)(mine >> 32), (u32)mine, pairs, pair_cap, q_hits, ctr);
-  }
-}
 
-// The phrase kernel's sibling for `near` queries (engine.hpp "index search"): the same rounds
-// over the near candidates, which the hit kernel wrote from cands[pair_cap - 1] downwards,
-// the same walk and the same token masks.  In place of the automaton: per term the ordinal
-// of the last token that matched it.  Lane j < 8 keeps term j's in one register (updated by
-// a select: no indexing, no scratch; 0: not seen yet); eight scalars and a set of seen terms
-// instead cost 104 SGPRs and a wave of occupancy.  Only the step's tokens whose mask is
-// non-zero are walked, in order; behind each, the minimum over lanes 0 .. 7 (three DPP
-// steps) tells whether every term has been seen and where the shortest covering window that
-// ends there starts: the line matches when ord - min < W.  (A minimal covering window always
-// ends at a matching token.)  The state carries across the 64-byte steps; ordinals and W
-// are full u32.
-template <bool kGlob>
-__device__ __forceinline__ void search_near_body(
-    unsigned char* row, u64* qk, u32* qm, const u32* __restrict__ pq,
-    const char* __restrict__ text, u64 bytes, const u64* __restrict__ nl_pos,
-    const MapCounters* __restrict__ lctr, const DelimMask& dm, int emits_per_line,
-    int max_key_len, u32 group, const u32* __restrict__ q_meta, const u64* __restrict__ keys,
-    u32 Q, const u64* __restrict__ cands, u64* __restrict__ pairs, u64 pair_cap,
-    u32* __restrict__ q_hits, SearchCounters* __restrict__ ctr) {
-  // row, qk, qm: this wave's LDS -- the line step, the query's term keys and (kGlob) its
-  // pattern terms' metacharacter maps; pq: the batch's pattern flags and maps (kGlob)
-  if (kGlob) {  // (in_vgprs: room in the scalar file for the matcher)
-    pq = in_vgprs(pq);
-    nl_pos = in_vgprs(nl_pos);
-    q_meta = in_vgprs(q_meta);
-    keys = in_vgprs(keys);
-    cands = in_vgprs(cands);
-    pairs = in_vgprs(pairs);
-    q_hits = in_vgprs(q_hits);
-    ctr = in_vgprs(ctr);
-    lctr = in_vgprs(lctr);
-  }
-  const int lane = dev::lane_id();
-  const u64 num_nl = lctr->num_newlines;  // (bytes > 0, the launch's check: num_nl + 1 lines)
-  const u32 C = ctr->ncands <= pair_cap ? ctr->ncands : 0u;  // (an overflow: the host throws)
-  const u32 wave = blockIdx.x * kPhraseWaves + dev::wave_id();
-  // a round of all waves: at most kPhraseMaxBlocks * kPhraseWaves * 64 = 2^19 candidates
-  const u32 stride = gridDim.x * kPhraseWaves * group;
-  const u64 below = lane ? (~0ull >> (64 - lane)) : 0ull;  // the lanes below this one
-  const u32 E = (u32)emits_per_line;
-  for (u64 g0 = (u64)wave * group; g0 < C; g0 += stride) {  // (wave-uniform)
-    const u32 cnt = (u32)(g0 + group < C ? group : C - g0);
-    // lane i: candidate i (g0 + lane < C <= pair_cap: inside cands)
-    const u64 mine = (u32)lane < cnt ? cands[pair_cap - 1 - (g0 + lane)] : 0ull;
-    bool hit = false;
-    u32 q_loaded = ~0u;  // the query whose term keys the wave's LDS row holds
-    for (u32 i = 0; i < cnt; ++i) {
-      const u32 q = (u32)__shfl((int)(u32)(mine >> 32), (int)i, 64);
-      const u64 line = (u32)__shfl((int)(u32)mine, (int)i, 64);
-      if (q >= Q || line > num_nl) continue;  // (wave-uniform; never: the hit kernel's words)
-      const u32 meta = q_meta[q];
-      // the positive terms, which stand first: exclusion terms are no part of the match
-      const u32 m = (meta & 0xffu) - (u32)__popc(meta >> kSearchExcludeShift);
-      if (m == 0 || m > (u32)kTerms) continue;    // (never: the host checked the batch)
-      const u32 pre = (meta >> kSearchPrefixShift) & 0xffu;  // bit j: term j is a prefix term
-      const u32 pt = kGlob ? pq[q] : 0u;  // bit j: term j is a pattern term | kSearchFold
-      // the batch's windows stand behind its keys (search_within)
-      const u32 W = reinterpret_cast<const u32*>(keys + (u64)Q * kTerms * kKeyWords)[q];
-      if (q != q_loaded) {  // (wave-uniform) neighbours mostly share their query
-        __builtin_amdgcn_wave_barrier();  // the previous candidate's key reads are done
-        if (lane < kTerms * kKeyWords) qk[lane] = keys[(u64)q * kTerms * kKeyWords + lane];
-        if (kGlob && lane < kTerms) qm[lane] = pq[kSearchPatMeta + (u64)q * kTerms + lane];
-        __builtin_amdgcn_wave_barrier();
-        q_loaded = q;
-      }
-      const u64 start = line ? nl_pos[line - 1] + 1 : 0;
-      const u64 end = line < num_nl ? nl_pos[line] : bytes;
-      u32 seen = 0;  // token starts of this line before the current step
-      // lane j < 8: 1 + the ordinal of the last token that matched term min(j, m - 1) (the
-      // lanes behind the query's terms repeat its last one), 0: none yet
-      const u32 term = min((u32)(lane & 7), m - 1u);
-      u32 lastv = 0;
-      u64 carry = 0;
-      bool match = false;
-      for (u64 pos = start; pos < end && seen < E && !match; pos += 64) {
-        const u64 p = pos + lane;
-        const unsigned c = p < end ? (unsigned char)text[p] : 0u;
-        const u64 p2 = pos + 64 + lane;
-        const unsigned c2 = (lane < 32 && p2 < end) ? (unsigned char)text[p2] : 0u;
-        __builtin_amdgcn_wave_barrier();  // the previous step's key reads are done
-        row[lane] = (unsigned char)c;
-        if (lane < 32) row[64 + lane] = (unsigned char)c2;
-        __builtin_amdgcn_wave_barrier();
-        bool last;
-        const u64 starts = dev::step_starts(c, dm, &carry, &last);
-        const u32 ord = seen + (u32)__popcll(starts & below);
-        const bool emit = ((starts >> lane) & 1ull) && ord < E;
-        u32 eq = 0;  // bit j: this lane's token matches term j
-        if (emit) eq = token_term_mask<kGlob>(row, lane, dm, max_key_len, qk, m, pre, pt, qm);
-        // the step's matching tokens in order (all wave-uniform)
-        u64 mm = dev::ballot(eq != 0u);
-        while (mm) {
-          const int tl = __ffsll((unsigned long long)mm) - 1;
-          const u32 e = (u32)__builtin_amdgcn_readlane((int)eq, tl);
-          const u32 o = (u32)__builtin_amdgcn_readlane((int)ord, tl);  // its ordinal
-          lastv = ((e >> term) & 1u) ? o + 1u : lastv;  // (lanes >= 8: never read)
-          // lane 7: the minimum over lanes 0 .. 7 (row_shr 1, 2, 4; a lane without a source
-          // reads 0, which never reaches lane 7)
-          u32 x = lastv;
-          x = min(x, dev::dpp_mov<0x111, 0xf>(x));
-          x = min(x, dev::dpp_mov<0x112, 0xf>(x));
-          x = min(x, dev::dpp_mov<0x114, 0xf>(x));
-          const u32 first = (u32)__builtin_amdgcn_readlane((int)x, 7);
-          // every term seen, and the tokens first - 1 .. o are at most W
-          if (first != 0u && o + 1u - first < W) {
-            match = true;
-            break;
-          }
-          mm &= mm - 1;
-        }
-        seen += (u32)__popcll(starts);
-        if (last) break;  // a NUL, or the line end, inside this step
-      }
-      if ((u32)lane == i) hit = match;
-    }
-    if (lane == 0) atomicAdd(&ctr->nverified, cnt);
-    commit_hits(hit, (u32)(mine >> 32), (u32)mine, pairs, pair_cap, q_hits, ctr);
-  }
-}
-
-// The verify kernels: the two bodies above, without and with the pattern matcher.
+// The verify kernels: the phrase and the near body (device/verify.hpp), without and with the
+// pattern matcher.
 __global__ __launch_bounds__(kPhraseBlock) void search_phrase_kernel(
     const char* __restrict__ text, u64 bytes, const u64* __restrict__ nl_pos,
     const MapCounters* __restrict__ lctr, DelimMask dm, int emits_per_line, int max_key_len,
@@ -846,7 +513,7 @@ __global__ __launch_bounds__(kPhraseBlock) void search_phrase_kernel(
     u32* __restrict__ q_hits, SearchCounters* __restrict__ ctr) {
   __shared__ unsigned char s_row[kPhraseWaves][dev::kLineRow];
   __shared__ u64 s_keys[kPhraseWaves][kTerms * kKeyWords];
-  search_phrase_body<false>(s_row[dev::wave_id()], s_keys[dev::wave_id()], nullptr, nullptr, text,
+  search_phrase_body<0>(s_row[dev::wave_id()], s_keys[dev::wave_id()], nullptr, nullptr, text,
                         bytes, nl_pos, lctr, dm, emits_per_line, max_key_len, group, q_meta, keys,
                         Q, cands, pairs, pair_cap, q_hits, ctr);
 }
@@ -861,7 +528,7 @@ __global__ __launch_bounds__(kPhraseBlock) void search_globphrase_kernel(
   __shared__ unsigned char s_row[kPhraseWaves][dev::kLineRow];
   __shared__ u64 s_keys[kPhraseWaves][kTerms * kKeyWords];
   __shared__ u32 s_meta[kPhraseWaves][kTerms];
-  search_phrase_body<true>(s_row[dev::wave_id()], s_keys[dev::wave_id()], s_meta[dev::wave_id()], pq,
+  search_phrase_body<1>(s_row[dev::wave_id()], s_keys[dev::wave_id()], s_meta[dev::wave_id()], pq,
                        text, bytes, nl_pos, lctr, dm, emits_per_line, max_key_len, group, q_meta,
                        keys, Q, cands, pairs, pair_cap, q_hits, ctr);
 }
@@ -874,7 +541,7 @@ __global__ __launch_bounds__(kPhraseBlock) void search_near_kernel(
     u32* __restrict__ q_hits, SearchCounters* __restrict__ ctr) {
   __shared__ unsigned char s_row[kPhraseWaves][dev::kLineRow];
   __shared__ u64 s_keys[kPhraseWaves][kTerms * kKeyWords];
-  search_near_body<false>(s_row[dev::wave_id()], s_keys[dev::wave_id()], nullptr, nullptr, text,
+  search_near_body<0>(s_row[dev::wave_id()], s_keys[dev::wave_id()], nullptr, nullptr, text,
                         bytes, nl_pos, lctr, dm, emits_per_line, max_key_len, group, q_meta, keys,
                         Q, cands, pairs, pair_cap, q_hits, ctr);
 }
@@ -889,7 +556,7 @@ __global__ __launch_bounds__(kPhraseBlock) void search_globnear_kernel(
   __shared__ unsigned char s_row[kPhraseWaves][dev::kLineRow];
   __shared__ u64 s_keys[kPhraseWaves][kTerms * kKeyWords];
   __shared__ u32 s_meta[kPhraseWaves][kTerms];
-  search_near_body<true>(s_row[dev::wave_id()], s_keys[dev::wave_id()], s_meta[dev::wave_id()], pq,
+  search_near_body<1>(s_row[dev::wave_id()], s_keys[dev::wave_id()], s_meta[dev::wave_id()], pq,
                        text, bytes, nl_pos, lctr, dm, emits_per_line, max_key_len, group, q_meta,
                        keys, Q, cands, pairs, pair_cap, q_hits, ctr);
 }
@@ -1111,15 +778,6 @@ void search_hits_carve(char* base, u64 cap, SearchHits* h) {
   h->cap = cap;
 }
 
-namespace {
-// The dictionary scan's grid: x over the record tiles, y over the queries while there are few
-// tiles (a small dictionary would otherwise leave most of the device idle).
-dim3 match_grid(u32 n, u32 queries) {
-  const u32 x = (u32)std::min<u64>(div_up((u64)std::max(n, 1u), (u64)kSearchBlock), kMatchMaxBlocks);
-  const u32 y = std::min(queries, std::max(1u, kMatchMaxBlocks / x));
-  return dim3(x, y);
-}
-}  // namespace
 
 void launch_search_lookup(const SearchIndex& ix, const SearchBatch& b, u32 queries,
                           hipStream_t s) {
@@ -1130,7 +788,9 @@ void launch_search_lookup(const SearchIndex& ix, const SearchBatch& b, u32 queri
   if (b.pat) {  // match: the pattern slots' words, lengths and cursors start from zero
     LOCUST_HIP_CHECK(hipMemsetAsync(b.pat + kSearchPatWords, 0,
                                     (kSearchPatEnd - kSearchPatWords) * sizeof(u32), s));
-    if (ix.n) {
+    if (ix.n && b.fuzzy) {  // (a batch that has a fuzzy term: fuzzy.hip's scan)
+      launch_fuzzy_match(ix, b, queries, s);
+    } else if (ix.n) {
       search_match_kernel<<<match_grid(ix.n, queries), dim3(kSearchBlock), 0, s>>>(
           ix.recs, ix.n, b.keys, b.pat, queries, b.pat + kSearchPatWords);
       LOCUST_HIP_LAUNCH_CHECK();
@@ -1161,7 +821,9 @@ void launch_search_expand(const SearchIndex& ix, const SearchBatch& b, u32 queri
   search_gather_kernel<<<dim3(gblocks), dim3(kSearchBlock), 0, s>>>(
       ix.postings, ix.first_line, b.x_start, b.t_val, slots, x, h.cap, h.pairs, b.ctr, b.pat);
   LOCUST_HIP_LAUNCH_CHECK();
-  if (b.pat && ix.n) {  // the wide pattern slots' part of the keys
+  if (b.pat && ix.n && b.fuzzy) {
+    launch_fuzzy_scatter(ix, b, queries, x, h, s);
+  } else if (b.pat && ix.n) {  // the wide pattern slots' part of the keys
     search_scatter_kernel<<<match_grid(ix.n, queries), dim3(kSearchBlock), 0, s>>>(
         ix.recs, ix.n, ix.val, ix.postings, ix.first_line, b.keys, b.pat, queries, b.x_len,
         b.x_start, x, h.cap, b.pat + kSearchPatCursor, h.pairs);
@@ -1206,7 +868,9 @@ void launch_search_hits(const SearchIndex& ix, const SearchBatch& b, u32 queries
     const u32 group = (u32)std::min<u64>(div_up(bound, (u64)kPhraseMaxBlocks), 64);
     const u32 blocks = (u32)std::min<u64>(div_up(div_up(bound, (u64)group), (u64)kPhraseWaves),
                                           (u64)kPhraseMaxBlocks);
-    if (b.pat)  // (a batch that has a pattern term: the sibling with the matcher)
+    if (b.fuzzy)  // (a batch that has a fuzzy term: fuzzy.hip's sibling)
+      launch_fuzzy_phrase(ix, b, queries, bound, h, s);
+    else if (b.pat)  // (a batch that has a pattern term: the sibling with the matcher)
       search_globphrase_kernel<<<dim3(blocks), dim3(kPhraseBlock), 0, s>>>(
           ix.text, ix.bytes, ix.nl_pos, ix.lctr, ix.dm, ix.emits_per_line, ix.max_key_len, group,
           b.q_meta, b.keys, queries, h.cands, h.pairs, h.cap, b.q_hits, b.ctr, b.pat);
@@ -1224,7 +888,9 @@ void launch_search_hits(const SearchIndex& ix, const SearchBatch& b, u32 queries
     const u32 group = (u32)std::min<u64>(div_up(bound, (u64)kPhraseMaxBlocks), 64);
     const u32 blocks = (u32)std::min<u64>(div_up(div_up(bound, (u64)group), (u64)kPhraseWaves),
                                           (u64)kPhraseMaxBlocks);
-    if (b.pat)
+    if (b.fuzzy)
+      launch_fuzzy_near(ix, b, queries, bound, h, s);
+    else if (b.pat)
       search_globnear_kernel<<<dim3(blocks), dim3(kPhraseBlock), 0, s>>>(
           ix.text, ix.bytes, ix.nl_pos, ix.lctr, ix.dm, ix.emits_per_line, ix.max_key_len, group,
           b.q_meta, b.keys, queries, h.cands, h.pairs, h.cap, b.q_hits, b.ctr, b.pat);

@@ -16,9 +16,11 @@
 //    that reaches the step's last byte stays open -- wave-uniform state: where its triple
 //    lies and its length so far -- and the step that holds its end (a ballot's trailing ones)
 //    or the line's end writes its length.  No per-lane byte loop, no atomics on the output.
-// A batch with a pattern term runs the siblings compiled with the matcher.
+// A batch with a pattern term runs the siblings compiled with the matcher; one with a fuzzy term
+// runs fuzzy.hip's (launch_fuzzy_show).
 #include <algorithm>
 
+#include "locust/device/showwalk.hpp"
 #include "locust/device/termmask.hpp"
 #include "locust/device/wave.hpp"
 #include "locust/hip_check.hpp"
@@ -28,237 +30,21 @@ namespace locust {
 namespace {
 
 constexpr int kTerms = (int)kSearchMaxTerms;
-constexpr int kShowBlock = 256;
-constexpr int kShowWaves = kShowBlock / 64;
-constexpr int kShowMaxBlocks = 2048;  // 8 workgroups per CU, as the verify kernels
 constexpr int kScanBlock = 512;
 constexpr int kScanItems = 8;  // consecutive entries per thread and tile
 
-// What a show kernel reads and writes (one kernel argument).
-struct ShowJob {
-  const char* text;
-  u64 bytes;
-  const u64* nl_pos;
-  const MapCounters* lctr;
-  DelimMask dm;
-  int emits_per_line, max_key_len;
-  u32 group, Q, first_line, show;
-  const u32* q_meta;
-  const u64* keys;
-  const u32* pq;       // the batch's pattern flags and maps (the glob siblings)
-  const u32* lines;    // [E] the returned lines, global numbers
-  const u64* offsets;  // [Q + 1] their per-query segments
-  u64 E;
-  ShowCounters* ctr;
-  u32* n_spans;        // measure writes, the scan reads
-  u32* t_len;
-  const u64* span_off;  // write reads
-  const u64* text_off;
-  u32* spans;
-  char* out;
-};
-
-template <bool kGlob, bool kWrite>
-__device__ __forceinline__ void show_body(unsigned char* row, u64* qk, u32* qm, const ShowJob& j) {
-  // row, qk, qm: this wave's LDS -- the line step, the query's term keys and (kGlob) its
-  // pattern terms' metacharacter maps
-  const char* __restrict__ text = j.text;
-  const u64* __restrict__ nl_pos = j.nl_pos;
-  const u32* __restrict__ q_meta = j.q_meta;
-  const u64* __restrict__ keys = j.keys;
-  const u32* __restrict__ pq = j.pq;
-  const u32* __restrict__ lines = j.lines;
-  const u64* __restrict__ offsets = j.offsets;
-  const u64* __restrict__ span_off = j.span_off;
-  const u64* __restrict__ text_off = j.text_off;
-  u32* __restrict__ spans = j.spans;
-  char* __restrict__ out = j.out;
-  u32* __restrict__ n_spans = j.n_spans;
-  u32* __restrict__ t_len = j.t_len;
-  ShowCounters* __restrict__ ctr = j.ctr;
-  if (kGlob) {  // (in_vgprs: room in the scalar file for the matcher)
-    pq = in_vgprs(pq);
-    nl_pos = in_vgprs(nl_pos);
-    q_meta = in_vgprs(q_meta);
-    keys = in_vgprs(keys);
-    lines = in_vgprs(lines);
-    offsets = in_vgprs(offsets);
-    span_off = in_vgprs(span_off);
-    text_off = in_vgprs(text_off);
-    spans = in_vgprs(spans);
-    out = in_vgprs(out);
-    n_spans = in_vgprs(n_spans);
-    t_len = in_vgprs(t_len);
-    ctr = in_vgprs(ctr);
-  }
-  const DelimMask& dm = j.dm;
-  const int lane = dev::lane_id();
-  const u32 bytes = (u32)j.bytes;  // (a window holds < 2^32 bytes: the launch's check)
-  // (line numbers are u32, and the launch checked bytes > 0: num_nl + 1 lines)
-  const u32 num_nl = (u32)j.lctr->num_newlines;
-  const u64 E = j.E;
-  const u32 Q = j.Q, group = j.group, N = j.show;
-  const u32 wave = blockIdx.x * kShowWaves + dev::wave_id();
-  // a round of all waves: at most kShowMaxBlocks * kShowWaves * 64 = 2^19 entries
-  const u32 stride = gridDim.x * kShowWaves * group;
-  const u64 below = lane ? (~0ull >> (64 - lane)) : 0ull;  // the lanes below this one
-  const u32 EM = (u32)j.emits_per_line;
-  for (u64 g0 = (u64)wave * group; g0 < E; g0 += stride) {  // (wave-uniform)
-    const u32 cnt = (u32)(g0 + group < E ? group : E - g0);
-    // lane i: entry i -- its line, and its query: offsets[q] <= e < offsets[q + 1]
-    u32 myq = Q, myline = 0;
-    if ((u32)lane < cnt) {
-      const u64 e = g0 + lane;
-      myline = lines[e] - j.first_line;
-      u32 lo = 0, hi = Q;
-      while (hi - lo > 1) {
-        const u32 mid = lo + ((hi - lo) >> 1);
-        if (offsets[mid] <= e)
-          lo = mid;
-        else
-          hi = mid;
-      }
-      myq = lo;
-    }
-    u32 my_spans = 0, my_len = 0;  // measure: lane i keeps entry i's figures
-    bool my_cut = false;
-    u32 bad = 0;           // write: entries whose spans do not number what measure counted
-    u32 q_loaded = ~0u;    // the query whose term keys the wave's LDS row holds
-    for (u32 i = 0; i < cnt; ++i) {
-      const u32 q = (u32)__shfl((int)myq, (int)i, 64);
-      const u32 line = (u32)__shfl((int)myline, (int)i, 64);
-      if (q >= Q || line > num_nl) continue;  // (wave-uniform; never: the search's own lines)
-      const u32 meta = q_meta[q];
-      // the positive terms, which stand first: exclusion terms never produce a span
-      const u32 m = (meta & 0xffu) - (u32)__popc(meta >> kSearchExcludeShift);
-      if (m == 0 || m > (u32)kTerms) continue;  // (never: the host checked the batch)
-      const u32 pre = (meta >> kSearchPrefixShift) & 0xffu;  // bit j: term j is a prefix term
-      const u32 pt = kGlob ? pq[q] : 0u;  // bit j: term j is a pattern term | kSearchFold
-      if (q != q_loaded) {  // (wave-uniform) neighbours mostly share their query
-        __builtin_amdgcn_wave_barrier();  // the previous entry's key reads are done
-        if (lane < kTerms * kKeyWords) qk[lane] = keys[(u64)q * kTerms * kKeyWords + lane];
-        if (kGlob && lane < kTerms) qm[lane] = pq[kSearchPatMeta + (u64)q * kTerms + lane];
-        __builtin_amdgcn_wave_barrier();
-        q_loaded = q;
-      }
-      const u32 start = line ? (u32)nl_pos[line - 1] + 1u : 0u;
-      const u32 end = line < num_nl ? (u32)nl_pos[line] : bytes;
-      // write: where the entry's spans and bytes go, and how many measure counted
-      u64 s_at = 0, s_end = 0, t_at = 0;
-      u32 tl = 0;
-      if (kWrite) {
-        s_at = span_off[g0 + i];
-        s_end = span_off[g0 + i + 1];
-        t_at = text_off[g0 + i];
-        tl = (u32)(text_off[g0 + i + 1] - t_at);  // (<= N)
-      }
-      u32 len = end - start;  // the line's length, unless a NUL (or the early end) cuts it
-      u32 seen = 0;           // token starts of this line before the current step
-      u32 nsp = 0;            // spans of this line before the current step
-      u64 carry = 0;
-      bool open = false;  // a matching token of an earlier step has not ended yet:
-      u32 open_len = 0;   // its bytes so far,
-      u64 open_at = 0;    // and its triple
-      for (u32 pos = start; pos < end; pos += 64u) {
-        const u32 left = end - pos;  // (>= 1)
-        const unsigned c = (u32)lane < left ? (unsigned char)text[(u64)pos + lane] : 0u;
-        const unsigned c2 =
-            (lane < 32 && 64u + (u32)lane < left) ? (unsigned char)text[(u64)pos + 64 + lane] : 0u;
-        const u32 off = pos - start + (u32)lane;
-        // (below t_len every byte is the line's: t_len <= its length, which ends at a NUL)
-        if (kWrite && off < tl) out[t_at + off] = (char)c;
-        __builtin_amdgcn_wave_barrier();  // the previous step's key reads are done
-        row[lane] = (unsigned char)c;
-        if (lane < 32) row[64 + lane] = (unsigned char)c2;
-        __builtin_amdgcn_wave_barrier();
-        // dev::step_starts, with the token bytes kept: they give the tokens' ends
-        const u64 z = dev::ballot(c == 0u);
-        u64 tm = dev::ballot(c != 0u && !mask_is_delim(dm, c));
-        if (z) tm &= (z & (~z + 1)) - 1;  // nothing at or behind the first NUL (or the end)
-        const u64 starts = tm & ~((tm << 1) | carry);
-        carry = tm >> 63;
-        if (open) {  // (wave-uniform) the open token goes on for the step's leading token bytes
-          const u32 lead = tm == ~0ull ? 64u : (u32)__ffsll((unsigned long long)~tm) - 1u;
-          open_len += lead;
-          if (lead < 64u) {
-            if (kWrite && lane == 0 && open_at < s_end) spans[open_at * 3 + 1] = open_len;
-            open = false;
-          }
-        }
-        const u32 ord = seen + (u32)__popcll(starts & below);
-        const bool emit = ((starts >> lane) & 1ull) && ord < EM;
-        u32 eq = 0;  // bit t: this lane's token matches term t
-        if (emit) eq = token_term_mask<kGlob>(row, lane, dm, j.max_key_len, qk, m, pre, pt, qm);
-        const u64 mm = dev::ballot(eq != 0u);
-        if (mm) {  // (wave-uniform)
-          // the token's end: the first byte at or behind its start that is no token byte
-          const u64 rest = ~tm & (~0ull << lane);
-          if (kWrite && eq != 0u) {
-            const u64 at = s_at + nsp + dev::lanes_below(mm);
-            if (at < s_end) {
-              spans[at * 3] = off;
-              // (a token that reaches the step's last byte: the closing step writes its length)
-              if (rest) spans[at * 3 + 1] = (u32)__ffsll((unsigned long long)rest) - 1u - (u32)lane;
-              spans[at * 3 + 2] = eq;
-            }
-          }
-          // the step's last matching token is open when token bytes fill the step behind it
-          const int hl = 63 - __clzll((long long)mm);
-          if ((tm >> hl) == (~0ull >> hl)) {
-            open = true;
-            open_len = 64u - (u32)hl;
-            open_at = s_at + nsp + (u32)__popcll(mm) - 1u;
-          }
-          nsp += (u32)__popcll(mm);
-        }
-        seen += (u32)__popcll(starts);
-        if (z) {  // a NUL, or the line end, inside this step
-          len = pos - start + (u32)__ffsll((unsigned long long)z) - 1u;
-          break;
-        }
-        // every token that can match has ended, and enough of the line is known: measure
-        // needs byte N to tell a cut line, write the bytes below t_len
-        if (left <= 64u) break;  // the line ends with the step
-        const u32 walked = pos - start + 64u;
-        if (seen >= EM && !open && (kWrite ? walked >= tl : walked > N)) {
-          len = walked;  // (N < walked < the line's length: the line is cut)
-          break;
-        }
-      }
-      // the line ended with the open token
-      if (kWrite && open && lane == 0 && open_at < s_end) spans[open_at * 3 + 1] = open_len;
-      if (kWrite) {
-        bad += s_at + nsp != s_end ? 1u : 0u;
-      } else if ((u32)lane == i) {
-        my_spans = nsp;
-        my_len = (u32)(len < N ? len : N);
-        my_cut = len > N;
-      }
-    }
-    if (kWrite) {
-      if (bad && lane == 0) atomicAdd(&ctr->mismatch, bad);
-    } else {
-      if ((u32)lane < cnt) {
-        n_spans[g0 + lane] = my_spans;
-        t_len[g0 + lane] = my_len;
-      }
-      const u64 cm = dev::ballot(my_cut);
-      if (cm && lane == 0) atomicAdd(&ctr->cut, (u32)__popcll(cm));
-    }
-  }
-}
-
-// The show kernels: the body above, measuring or writing, without and with the matcher.
+// The show kernels: the walk (device/showwalk.hpp), measuring or writing, without and with the
+// matcher.
 __global__ __launch_bounds__(kShowBlock) void show_measure_kernel(ShowJob j) {
   __shared__ unsigned char s_row[kShowWaves][dev::kLineRow];
   __shared__ u64 s_keys[kShowWaves][kTerms * kKeyWords];
-  show_body<false, false>(s_row[dev::wave_id()], s_keys[dev::wave_id()], nullptr, j);
+  show_body<0, false>(s_row[dev::wave_id()], s_keys[dev::wave_id()], nullptr, j);
 }
 
 __global__ __launch_bounds__(kShowBlock) void show_write_kernel(ShowJob j) {
   __shared__ unsigned char s_row[kShowWaves][dev::kLineRow];
   __shared__ u64 s_keys[kShowWaves][kTerms * kKeyWords];
-  show_body<false, true>(s_row[dev::wave_id()], s_keys[dev::wave_id()], nullptr, j);
+  show_body<0, true>(s_row[dev::wave_id()], s_keys[dev::wave_id()], nullptr, j);
 }
 
 // ... of a batch that has a pattern term (j.pq: its pattern flags and maps).
@@ -266,14 +52,14 @@ __global__ __launch_bounds__(kShowBlock) void show_globmeasure_kernel(ShowJob j)
   __shared__ unsigned char s_row[kShowWaves][dev::kLineRow];
   __shared__ u64 s_keys[kShowWaves][kTerms * kKeyWords];
   __shared__ u32 s_meta[kShowWaves][kTerms];
-  show_body<true, false>(s_row[dev::wave_id()], s_keys[dev::wave_id()], s_meta[dev::wave_id()], j);
+  show_body<1, false>(s_row[dev::wave_id()], s_keys[dev::wave_id()], s_meta[dev::wave_id()], j);
 }
 
 __global__ __launch_bounds__(kShowBlock) void show_globwrite_kernel(ShowJob j) {
   __shared__ unsigned char s_row[kShowWaves][dev::kLineRow];
   __shared__ u64 s_keys[kShowWaves][kTerms * kKeyWords];
   __shared__ u32 s_meta[kShowWaves][kTerms];
-  show_body<true, true>(s_row[dev::wave_id()], s_keys[dev::wave_id()], s_meta[dev::wave_id()], j);
+  show_body<1, true>(s_row[dev::wave_id()], s_keys[dev::wave_id()], s_meta[dev::wave_id()], j);
 }
 
 // One workgroup: span_off[0 .. E] and text_off[0 .. E] = the exclusive scans of n_spans and
@@ -434,7 +220,9 @@ void launch_show_measure(const SearchIndex& ix, const SearchBatch& b, u32 querie
   u32 blocks = 0;
   const ShowJob j = make_job(ix, b, queries, lines, offsets, entries, show, sb, &blocks);
   LOCUST_HIP_CHECK(hipMemsetAsync(sb.ctr, 0, sizeof(ShowCounters), s));
-  if (b.pat)  // (a batch that has a pattern term: the sibling with the matcher)
+  if (b.fuzzy)  // (a batch that has a fuzzy term: fuzzy.hip's sibling)
+    launch_fuzzy_show(j, blocks, false, s);
+  else if (b.pat)  // (a batch that has a pattern term: the sibling with the matcher)
     show_globmeasure_kernel<<<dim3(blocks), dim3(kShowBlock), 0, s>>>(j);
   else
     show_measure_kernel<<<dim3(blocks), dim3(kShowBlock), 0, s>>>(j);
@@ -450,7 +238,9 @@ void launch_show_write(const SearchIndex& ix, const SearchBatch& b, u32 queries,
   // (N = 1: write takes every length from text_off)
   const ShowJob j = make_job(ix, b, queries, lines, offsets, entries, 1, sb, &blocks);
   LOCUST_CHECK_ARG(sb.text && sb.spans, "show: the payload buffers are missing");
-  if (b.pat)
+  if (b.fuzzy)
+    launch_fuzzy_show(j, blocks, true, s);
+  else if (b.pat)
     show_globwrite_kernel<<<dim3(blocks), dim3(kShowBlock), 0, s>>>(j);
   else
     show_write_kernel<<<dim3(blocks), dim3(kShowBlock), 0, s>>>(j);

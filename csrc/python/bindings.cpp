@@ -102,7 +102,7 @@ struct PyIndexResult {
                         const std::vector<int>& any, const py::object& rank, bool wildcard,
                         const std::vector<u64>& within,
                         const std::vector<std::vector<std::string>>& exclude, bool glob,
-                        bool ignore_case, const py::object& show) const;
+                        bool ignore_case, const py::object& show, bool fuzzy) const;
   py::list entries() const { return PyResult{x.words}.entries(); }
   py::list postings() const {
     py::list out;
@@ -237,12 +237,13 @@ struct PySearchResult {
 // value `any` (any.size() == queries.size()).  wildcard: make_search_query's rule for a
 // trailing `*`.  within: empty, or one window per query (0: none; check_search_queries holds
 // it against the mode).  exclude: empty, or one list of exclusion terms per query (an empty
-// list: none).  glob: make_search_query's rule for `*` and `?` anywhere in a term.
+// list: none).  glob: make_search_query's rule for `*` and `?` anywhere in a term; fuzzy: its
+// rule for a trailing `~1` or `~2`.
 std::vector<SearchQuery> to_queries(const std::vector<std::vector<std::string>>& queries,
                                     const std::vector<int>& any, bool wildcard,
                                     const std::vector<u64>& within,
                                     const std::vector<std::vector<std::string>>& exclude,
-                                    bool glob) {
+                                    bool glob, bool fuzzy = false) {
   LOCUST_CHECK_ARG(any.size() == queries.size(), "search: one mode per query");
   LOCUST_CHECK_ARG(within.empty() || within.size() == queries.size(),
                    "search: one window (within) per query, or none");
@@ -256,7 +257,8 @@ std::vector<SearchQuery> to_queries(const std::vector<std::vector<std::string>>&
                                : any[i] == 3 ? SearchMode::kNear
                                              : SearchMode::kAny,
                                wildcard, within.empty() ? 0 : within[i],
-                               exclude.empty() ? std::vector<std::string>() : exclude[i], glob);
+                               exclude.empty() ? std::vector<std::string>() : exclude[i], glob,
+                               fuzzy);
   return out;
 }
 
@@ -292,8 +294,8 @@ PySearchResult PyIndexResult::search(const std::vector<std::vector<std::string>>
                                      const std::vector<int>& any, const py::object& rank,
                                      bool wildcard, const std::vector<u64>& within,
                                      const std::vector<std::vector<std::string>>& exclude, bool glob,
-                        bool ignore_case, const py::object& show) const {
-  const std::vector<SearchQuery> q = to_queries(queries, any, wildcard, within, exclude, glob);
+                        bool ignore_case, const py::object& show, bool fuzzy) const {
+  const std::vector<SearchQuery> q = to_queries(queries, any, wildcard, within, exclude, glob, fuzzy);
   const u64 k = to_rank(rank);
   const u64 n = to_show(show);
   py::gil_scoped_release nogil;
@@ -443,8 +445,8 @@ class PyGpuEngine {
                             const py::object& rank, bool wildcard,
                             const std::vector<u64>& within,
                             const std::vector<std::vector<std::string>>& exclude, bool glob,
-                        bool ignore_case, const py::object& show) {
-    const std::vector<SearchQuery> q = to_queries(queries, any, wildcard, within, exclude, glob);
+                        bool ignore_case, const py::object& show, bool fuzzy) {
+    const std::vector<SearchQuery> q = to_queries(queries, any, wildcard, within, exclude, glob, fuzzy);
     const u64 k = to_rank(rank);
     const u64 n = to_show(show);
     py::gil_scoped_release nogil;
@@ -456,8 +458,8 @@ class PyGpuEngine {
                                  const py::object& rank, bool wildcard,
                             const std::vector<u64>& within,
                             const std::vector<std::vector<std::string>>& exclude, bool glob,
-                        bool ignore_case, const py::object& show) {
-    const std::vector<SearchQuery> q = to_queries(queries, any, wildcard, within, exclude, glob);
+                        bool ignore_case, const py::object& show, bool fuzzy) {
+    const std::vector<SearchQuery> q = to_queries(queries, any, wildcard, within, exclude, glob, fuzzy);
     const u64 k = to_rank(rank);
     const u64 n = to_show(show);
     py::gil_scoped_release nogil;
@@ -467,8 +469,8 @@ class PyGpuEngine {
                                  const std::vector<int>& any, const py::object& rank,
                                  bool wildcard, const std::vector<u64>& within,
                                  const std::vector<std::vector<std::string>>& exclude, bool glob,
-                        bool ignore_case, const py::object& show) {
-    const std::vector<SearchQuery> q = to_queries(queries, any, wildcard, within, exclude, glob);
+                        bool ignore_case, const py::object& show, bool fuzzy) {
+    const std::vector<SearchQuery> q = to_queries(queries, any, wildcard, within, exclude, glob, fuzzy);
     const u64 k = to_rank(rank);
     const u64 n = to_show(show);
     py::gil_scoped_release nogil;
@@ -1019,6 +1021,7 @@ PYBIND11_MODULE(_locust, m) {
            py::arg("within") = std::vector<u64>(),
            py::arg("exclude") = std::vector<std::vector<std::string>>(),
            py::arg("glob") = false, py::arg("ignore_case") = false, py::arg("show") = py::none(),
+           py::arg("fuzzy") = false,
            "The host evaluation of all/any queries (any[i]: query i's mode) over this index.")
       .def("times", &PyIndexResult::times)
       .def("format", &PyIndexResult::format)
@@ -1122,17 +1125,20 @@ PYBIND11_MODULE(_locust, m) {
            py::arg("wildcard") = false, py::arg("within") = std::vector<u64>(),
            py::arg("exclude") = std::vector<std::vector<std::string>>(),
            py::arg("glob") = false, py::arg("ignore_case") = false, py::arg("show") = py::none(),
+           py::arg("fuzzy") = false,
            "WordCount of text, its index, and all/any queries answered on the device.")
       .def("run_search_text", &PyGpuEngine::run_search_text, py::arg("text"), py::arg("queries"),
            py::arg("any"), py::arg("first_line") = 0, py::arg("rank") = py::none(),
            py::arg("wildcard") = false, py::arg("within") = std::vector<u64>(),
            py::arg("exclude") = std::vector<std::vector<std::string>>(),
-           py::arg("glob") = false, py::arg("ignore_case") = false, py::arg("show") = py::none())
+           py::arg("glob") = false, py::arg("ignore_case") = false, py::arg("show") = py::none(),
+           py::arg("fuzzy") = false)
       .def("search_resident", &PyGpuEngine::search_resident, py::arg("queries"), py::arg("any"),
            py::arg("rank") = py::none(), py::arg("wildcard") = false,
            py::arg("within") = std::vector<u64>(),
            py::arg("exclude") = std::vector<std::vector<std::string>>(),
            py::arg("glob") = false, py::arg("ignore_case") = false, py::arg("show") = py::none(),
+           py::arg("fuzzy") = false,
            "Another batch from the index the last run_index / run_search left on the device.")
       .def("top_counts", &PyGpuEngine::top_counts, py::arg("records"), py::arg("k"),
            "The selection kernels alone over key-sorted (key, count) records.")
@@ -1156,16 +1162,17 @@ PYBIND11_MODULE(_locust, m) {
                              const py::object& rank, bool wildcard,
                              const std::vector<u64>& within,
                              const std::vector<std::vector<std::string>>& exclude, bool glob,
-                        bool ignore_case, const py::object& show) {
+                        bool ignore_case, const py::object& show, bool fuzzy) {
     CpuWordCount eng(cfg);
     return PySearchResult{eng.run_search(as_input(text, first_line),
-                                         to_queries(queries, any, wildcard, within, exclude, glob),
+                                         to_queries(queries, any, wildcard, within, exclude, glob, fuzzy),
                                          to_rank(rank), ignore_case, to_show(show))};
   }, py::arg("cfg"), py::arg("text"), py::arg("queries"), py::arg("any"),
         py::arg("first_line") = 0, py::arg("rank") = py::none(), py::arg("wildcard") = false,
         py::arg("within") = std::vector<u64>(),
            py::arg("exclude") = std::vector<std::vector<std::string>>(),
-           py::arg("glob") = false, py::arg("ignore_case") = false, py::arg("show") = py::none());
+           py::arg("glob") = false, py::arg("ignore_case") = false, py::arg("show") = py::none(),
+           py::arg("fuzzy") = false);
   m.def("check_search_show", &check_search_show, py::arg("show"), py::arg("text_bytes"),
         "Throws unless show is 0 or 1 <= N <= kShowMaxBytes over a window of < 2^32 bytes.");
   m.def("validate_show", [](const std::vector<std::string>& terms, const std::vector<u32>& lines,

@@ -70,16 +70,17 @@ def _search_args(queries, mode, within=None, exclude=None):
 
 
 def _index_search(self, queries, mode="all", rank=None, wildcard=False, within=None,
-                  exclude=None, glob=False, ignore_case=False, show=None):
+                  exclude=None, glob=False, ignore_case=False, show=None, fuzzy=False):
     """All/any word queries over this index, evaluated on the host (``SearchResult``):
     ``queries``, ``mode``, ``rank``, ``within`` and ``exclude`` as ``Engine.run_search`` takes
     them, any number of queries.  A ``"phrase"`` query, and a ``"near"`` query of two or more
     positive terms, is refused: the index holds no positions, so they need the text
-    (``Engine.run_search``, ``search_text``).  ``glob`` and ``ignore_case`` as there.
+    (``Engine.run_search``, ``search_text``).  ``glob``, ``fuzzy`` and ``ignore_case`` as
+    there.
     ``show=N`` is refused like a phrase: the shown lines come from the text."""
     queries, flags, windows, exclude = _search_args(queries, mode, within, exclude)
     return self._search(queries, flags, rank, bool(wildcard), windows, exclude, bool(glob),
-                        bool(ignore_case), show)
+                        bool(ignore_case), show, bool(fuzzy))
 
 
 _C.IndexResult.search = _index_search
@@ -123,7 +124,7 @@ class Engine:
 
     def run_search(self, text: bytes, queries, mode="all", first_line: int = 0, rank=None,
                    wildcard=False, within=None, exclude=None, glob=False, ignore_case=False,
-                   show=None):
+                   show=None, fuzzy=False):
         """WordCount of ``text``, its inverted index, and a batch of word queries answered
         from it (``SearchResult``).  ``queries`` is a list of term lists (1 to 8 byte-string
         terms each); ``mode`` is ``"all"`` (lines that hold every term), ``"any"`` (lines
@@ -177,6 +178,16 @@ class Engine:
         term takes ``emits_per_line <= 8192``: its lists may overlap, and a score reaches
         ``32 * emits_per_line * 8``.
 
+        ``fuzzy=True`` reads a term that ends in ``~1`` or ``~2`` as a fuzzy term: ``Hamlet~1``
+        stands for every word within one byte edit (an insertion, a deletion or a substitution;
+        no transposition) of ``Hamlet`` -- ``Hamlet!`` and ``[Hamlet`` among them -- and
+        ``quene~2`` finds ``queen``.  It behaves as one word with their merged lists, exactly as
+        a pattern term does (``oracle.search`` with ``fuzzy=True`` states the rules), under
+        ``ignore_case`` too.  The word is never cut and must be longer than its budget; a digit
+        other than 1 or 2 is refused, and so is a ``*`` or ``?`` in the word when ``wildcard``
+        or ``glob`` is on.  A ``~`` anywhere else is literal, and without ``fuzzy`` every ``~``
+        is.  On the GPU the dictionary scan finds the words with a banded edit-distance matcher.
+
         ``show=N`` (``1 <= N <= 65536``; ``None`` or ``0``: no show) also returns, for every
         returned line, its first ``N`` bytes and the spans of its tokens that match one of the
         query's own terms (``oracle.show`` states the rules): ``text(i)`` is the list of query
@@ -189,23 +200,24 @@ class Engine:
         if self.cpu:
             return _C.cpu_run_search(self.cfg, text, queries, flags, first_line, rank,
                                      bool(wildcard), windows, exclude, bool(glob),
-                                     bool(ignore_case), show)
+                                     bool(ignore_case), show, bool(fuzzy))
         return self._eng.run_search(text, queries, flags, first_line, rank, bool(wildcard),
-                                    windows, exclude, bool(glob), bool(ignore_case), show)
+                                    windows, exclude, bool(glob), bool(ignore_case), show,
+                                    bool(fuzzy))
 
     def search_resident(self, queries, mode="all", rank=None, wildcard=False, within=None,
-                        exclude=None, glob=False, ignore_case=False, show=None):
+                        exclude=None, glob=False, ignore_case=False, show=None, fuzzy=False):
         """Another batch from the index this engine's last job left on the device; that
         job must have been a ``run_index`` or a ``run_search`` (GPU engines only).  Every
         mode of ``run_search``: the job's text is resident too, so phrases and near queries
-        are answered.  ``rank``, ``within``, ``exclude``, ``glob``, ``ignore_case`` and ``show``
-        as ``run_search`` takes them."""
+        are answered.  ``rank``, ``within``, ``exclude``, ``glob``, ``ignore_case``, ``show`` and
+        ``fuzzy`` as ``run_search`` takes them."""
         if self.cpu:
             raise _C.LocustError("search_resident needs a GPU engine: the CPU engine keeps "
                                  "no index (use run_index(text).search(...))")
         queries, flags, windows, exclude = _search_args(queries, mode, within, exclude)
         return self._eng.search_resident(queries, flags, rank, bool(wildcard), windows, exclude,
-                                         bool(glob), bool(ignore_case), show)
+                                         bool(glob), bool(ignore_case), show, bool(fuzzy))
 
     def top_counts(self, records: list[tuple[bytes, int]], k: int):
         """The selection alone over (key, count) records sorted by key with distinct
@@ -307,25 +319,26 @@ def index_file(path: str, line_start: int = -1, line_end: int = -1, backend: str
 
 def search_text(text: bytes, queries, mode="all", backend: str = "gpu", cfg=None,
                 first_line: int = 0, rank=None, wildcard=False, within=None, exclude=None,
-                glob=False, ignore_case=False, show=None, **kw):
+                glob=False, ignore_case=False, show=None, fuzzy=False, **kw):
     """All/any/phrase/near word queries over ``text`` (``SearchResult``); see
     ``Engine.run_search``."""
     cfg = cfg if cfg is not None else make_config(backend, **kw)
     nlines = text.count(b"\n") + (1 if text and not text.endswith(b"\n") else 0)
     return Engine(cfg, max(len(text), 1), max(nlines, 1)).run_search(
         text, queries, mode, first_line, rank, wildcard, within, exclude, glob, ignore_case,
-        show)
+        show, fuzzy)
 
 
 def search_file(path: str, queries, mode="all", line_start: int = -1, line_end: int = -1,
                 backend: str = "gpu", cfg=None, rank=None, wildcard=False, within=None,
-                exclude=None, glob=False, ignore_case=False, show=None, **kw):
+                exclude=None, glob=False, ignore_case=False, show=None, fuzzy=False, **kw):
     """All/any/phrase/near word queries over a file or its line window, answered with the file's
     own (global) line numbers."""
     cfg = cfg if cfg is not None else make_config(backend, **kw)
     text, nlines, first, _total = _C.load_lines(path, line_start, line_end, cfg.ref_compat)
     return Engine(cfg, max(len(text), 1), max(nlines, 1)).run_search(
-        text, queries, mode, first, rank, wildcard, within, exclude, glob, ignore_case, show)
+        text, queries, mode, first, rank, wildcard, within, exclude, glob, ignore_case, show,
+        fuzzy)
 
 
 def map_stage(path: str, spill: str, line_start: int = -1, line_end: int = -1,

@@ -9,6 +9,7 @@ matches them exactly.
 """
 from __future__ import annotations
 
+import functools
 import re
 
 from collections import Counter
@@ -198,18 +199,81 @@ PATTERN_RULES = """
 """
 
 
-class QueryTerm:
-    """One term as it is evaluated: ``kind`` is ``"plain"``, ``"prefix"`` or ``"pattern"``;
-    ``p`` the cut bytes of a plain or prefix term; ``rx`` a pattern's compiled expression and
-    ``ident`` what makes two pattern terms the same term."""
+FUZZY_RULES = """
+    Fuzzy terms (``fuzzy=True``): ``Hamlet~1``, ``quene~2``.
 
-    def __init__(self, kind, p=b"", rx=None, ident=None):
-        self.kind, self.p, self.rx, self.ident = kind, p, rx, ident
+    - Syntax.  With ``fuzzy``, a term ``t`` with ``len(t) >= 3``, ``t[-2] == '~'`` and ``t[-1]``
+      a decimal digit is a fuzzy term of the word ``w = t[:-2]`` with budget ``d = t[-1]``.
+      ``d`` must be 1 or 2 (``ValueError`` otherwise).  A ``~`` anywhere else is a literal byte
+      of its word: no digit behind it, two digits behind it, or ``~1`` in the middle of a word.
+      Without ``fuzzy``, ``Hamlet~1`` is the literal word.  This reading comes before the
+      wildcard and glob reading of the term.
+    - The word.  ``w`` is validated byte for byte as a term is.  It is never cut: ``len(w) >
+      max_key`` is refused.  It must be longer than its budget: ``len(w) <= d`` is refused.
+      With ``glob`` or ``wildcard`` also on, a ``w`` that holds ``*`` or ``?`` is refused.
+      ``fuzzy`` implies neither and combines with both and with ``ignore_case``.
+    - Words.  A fuzzy term's words are the index keys ``k`` (cut to ``max_key`` as the index
+      holds them) with ``lev(w, k) <= d``: the Levenshtein distance over bytes, one insertion,
+      deletion or substitution costing 1, no transposition, no UTF-8 awareness.  Under
+      ``ignore_case`` ASCII letters match either case and nothing else folds.
+    - Everything else is a pattern term's rule (``PATTERN_RULES``) with this matcher: the list,
+      the count, absence, the modes, phrase / near verification and show spans (a token matches
+      when its cut key is within ``d`` of ``w``), the ranked bound and refusal, ``merged``.
+    - Identity.  Two fuzzy terms are the same term when their ``w`` bytes (under ``ignore_case``:
+      after lower-casing ASCII) and their budget are equal; ``ham~1`` and ``ham~2`` differ.  A
+      fuzzy term is never the same as a plain, prefix or pattern term and takes no part in the
+      nesting rule.
+    - Output prints the term as asked: ``Hamlet~1``.
+
+    The matching here is independent of the engines' banded matcher: a plain full-matrix
+    dynamic program over the two byte strings.
+"""
+
+
+def _fold(c: int) -> int:
+    return c | 0x20 if 0x41 <= c <= 0x5A else c
+
+
+@functools.lru_cache(maxsize=1 << 16)
+def levenshtein(a: bytes, b: bytes, fold: bool = False) -> int:
+    """The edit distance of two byte strings, the whole matrix row by row.  (Cached: a text's
+    tokens repeat.)"""
+    if fold:
+        a, b = bytes(map(_fold, a)), bytes(map(_fold, b))
+    prev = list(range(len(b) + 1))
+    for i, ca in enumerate(a, 1):
+        row = [i]
+        for j, cb in enumerate(b, 1):
+            row.append(min(prev[j] + 1, row[j - 1] + 1, prev[j - 1] + (ca != cb)))
+        prev = row
+    return prev[-1]
+
+
+class QueryTerm:
+    """One term as it is evaluated: ``kind`` is ``"plain"``, ``"prefix"``, ``"pattern"`` or
+    ``"fuzzy"``; ``p`` the cut bytes of a plain or prefix term, a fuzzy term's word; ``rx`` a
+    pattern's compiled expression; ``d`` and ``fold`` a fuzzy term's budget and fold; ``ident``
+    what makes two pattern terms, or two fuzzy terms, the same term."""
+
+    def __init__(self, kind, p=b"", rx=None, ident=None, d=0, fold=False):
+        self.kind, self.p, self.rx, self.ident, self.d, self.fold = kind, p, rx, ident, d, fold
+
+    @property
+    def scattered(self) -> bool:
+        """A term whose words are no key range: told apart by ``ident``, outside the nesting."""
+        return self.kind in ("pattern", "fuzzy")
 
     def fits(self, tok: bytes) -> bool:
+        if self.kind == "fuzzy":
+            return levenshtein(self.p, tok, self.fold) <= self.d
         if self.kind == "pattern":
             return self.rx.fullmatch(tok) is not None
         return tok[:len(self.p)] == self.p if self.kind == "prefix" else tok == self.p
+
+
+def _fuzzy_term(w: bytes, d: int, fold: bool) -> QueryTerm:
+    ident = ("fuzzy", bytes(map(_fold, w)) if fold else w, d)
+    return QueryTerm("fuzzy", p=w, ident=ident, d=d, fold=fold)
 
 
 def _pattern_term(cells, fold: bool) -> QueryTerm:
@@ -228,12 +292,28 @@ def _pattern_term(cells, fold: bool) -> QueryTerm:
 
 
 def query_terms(terms, wildcard: bool = False, glob: bool = False, ignore_case: bool = False,
-                delims: bytes = DEFAULT_DELIMS, max_key: int = 29):
+                delims: bytes = DEFAULT_DELIMS, max_key: int = 29, *, fuzzy: bool = False):
     """The terms of a query as ``QueryTerm`` objects, validated and cut: ``prefix_terms``'
-    sibling for ``glob`` and ``ignore_case`` (``PATTERN_RULES``)."""
+    sibling for ``glob`` and ``ignore_case`` (``PATTERN_RULES``) and ``fuzzy``
+    (``FUZZY_RULES``)."""
     bad = set(delims) | {0, 0x0A}
     out = []
     for t in terms:
+        if fuzzy and len(t) >= 3 and t[-2] == 0x7E and 0x30 <= t[-1] <= 0x39:
+            w, d = t[:-2], t[-1] - 0x30  # (read before the wildcard and glob reading)
+            if d not in (1, 2):
+                raise ValueError("the fuzzy term %r: a budget is 1 or 2" % (t,))
+            if len(w) <= d:
+                raise ValueError("the fuzzy term %r: its word is no longer than its budget" % (t,))
+            if len(w) > max_key:
+                raise ValueError("the fuzzy term %r: its word is longer than max_key" % (t,))
+            if (glob or wildcard) and any(c in b"*?" for c in w):
+                raise ValueError("the fuzzy term %r holds a * or ?: fuzzy or a pattern, never "
+                                 "both" % (t,))
+            if any(c in bad for c in w):
+                raise ValueError("invalid term %r" % (t,))
+            out.append(_fuzzy_term(w, d, ignore_case))
+            continue
         cells = None  # a pattern term's (byte, is_meta) pairs
         if glob:
             t = re.sub(rb"\*+", b"*", t)
@@ -324,11 +404,12 @@ def _check_exclude(terms, exclude):
 
 
 def _excluded_by_index(entries, postings, exclude, wildcard, delims, max_key, glob=False,
-                       ignore_case=False):
+                       ignore_case=False, fuzzy=False):
     """``(lines, counts)`` of exclusion terms over an index: the union of the terms' lines as
     a set, and every term's count (its word's, or its merged count; 0: absent)."""
     out, counts = set(), []
-    for term in query_terms(exclude, wildcard, glob, ignore_case, delims, max_key):
+    for term in query_terms(exclude, wildcard, glob, ignore_case, delims, max_key,
+                       fuzzy=fuzzy):
         lines = _term_list(entries, postings, _qt_words(entries, term))
         counts.append(len(lines))
         out.update(lines)
@@ -336,10 +417,11 @@ def _excluded_by_index(entries, postings, exclude, wildcard, delims, max_key, gl
 
 
 def _excluded_by_text(text, exclude, wildcard, delims, emits, max_key, first_line, glob=False,
-                      ignore_case=False):
+                      ignore_case=False, fuzzy=False):
     """The same from the text: a line is excluded when one of its emitted tokens (the index
     holds no other) matches an exclusion term; a term's count is its matching tokens."""
-    want = query_terms(exclude, wildcard, glob, ignore_case, delims, max_key)
+    want = query_terms(exclude, wildcard, glob, ignore_case, delims, max_key,
+                       fuzzy=fuzzy)
     out, counts = set(), [0] * len(want)
     for i, line in enumerate(split_lines(text)):
         toks, _dropped = tokenize(line, delims, emits, max_key)
@@ -353,6 +435,7 @@ def _excluded_by_text(text, exclude, wildcard, delims, emits, max_key, first_lin
 
 def merged_elements(entries, queries, delims: bytes = DEFAULT_DELIMS, max_key: int = 29, *,
                     exclude=None, glob: bool = False, ignore_case: bool = False,
+                    fuzzy: bool = False,
                     wildcard: bool = True) -> int:
     """``SearchResult.merged`` of a device batch of wildcard ``queries`` (term lists): over
     the batch's prefix terms that cover two or more words, a term whose words repeat an
@@ -373,10 +456,11 @@ def merged_elements(entries, queries, delims: bytes = DEFAULT_DELIMS, max_key: i
         queries = [list(q) + _check_exclude(list(q), x) for q, x in zip(queries, exclude)]
     for terms in queries:
         seen = []
-        for term in query_terms(terms, wildcard, glob, ignore_case, delims, max_key):
+        for term in query_terms(terms, wildcard, glob, ignore_case, delims, max_key,
+                       fuzzy=fuzzy):
             words = _qt_words(entries, term)
             # what a later term must repeat: a pattern term's pattern, another term's words
-            same = term.ident if term.kind == "pattern" else words
+            same = term.ident if term.scattered else words
             if len(words) >= 2 and same not in seen:
                 total += sum(entries[i][2] for i in words)
             seen.append(same)
@@ -385,7 +469,7 @@ def merged_elements(entries, queries, delims: bytes = DEFAULT_DELIMS, max_key: i
 
 def search(entries, postings, terms, mode: str = "all", delims: bytes = DEFAULT_DELIMS,
            max_key: int = 29, *, wildcard: bool = False, exclude=None, glob: bool = False,
-           ignore_case: bool = False):
+           ignore_case: bool = False, fuzzy: bool = False):
     """One all/any word query over an index: ``(lines, counts)``.
 
     ``entries`` and ``postings`` are ``index``'s output.  A query is 1 to 8 ``terms`` and a
@@ -413,15 +497,16 @@ def search(entries, postings, terms, mode: str = "all", delims: bytes = DEFAULT_
     if exclude is not None:
         exclude = _check_exclude(terms, exclude)
         lines, counts = search(entries, postings, terms, mode, delims, max_key,
-                               wildcard=wildcard, glob=glob, ignore_case=ignore_case)
+                               wildcard=wildcard, glob=glob, ignore_case=ignore_case, fuzzy=fuzzy)
         gone, xcounts = _excluded_by_index(entries, postings, exclude, wildcard, delims,
-                                           max_key, glob, ignore_case)
+                                           max_key, glob, ignore_case, fuzzy)
         return [l for l in lines if l not in gone], counts + xcounts
     if not 1 <= len(terms) <= MAX_SEARCH_TERMS:
         raise ValueError("a query takes 1 to %d terms" % MAX_SEARCH_TERMS)
-    if wildcard or glob or ignore_case:  # (``glob`` / ``ignore_case``: PATTERN_RULES)
+    if wildcard or glob or ignore_case or fuzzy:  # (``glob`` / ``ignore_case``: PATTERN_RULES)
         sets, counts = [], []
-        for term in query_terms(terms, wildcard, glob, ignore_case, delims, max_key):
+        for term in query_terms(terms, wildcard, glob, ignore_case, delims, max_key,
+                       fuzzy=fuzzy):
             lines = _term_list(entries, postings, _qt_words(entries, term))
             counts.append(len(lines))
             sets.append(set(lines))
@@ -443,7 +528,7 @@ def search(entries, postings, terms, mode: str = "all", delims: bytes = DEFAULT_
 
 def phrase(text: bytes, terms, delims: bytes = DEFAULT_DELIMS, emits: int = 20,
            max_key: int = 29, first_line: int = 0, *, wildcard: bool = False, exclude=None,
-           glob: bool = False, ignore_case: bool = False):
+           glob: bool = False, ignore_case: bool = False, fuzzy: bool = False):
     """One phrase query over ``text``: ``(lines, counts)``, as ``search`` answers.
 
     `phrase` answers the lines on which the terms occur as consecutive tokens, in order.
@@ -474,14 +559,15 @@ def phrase(text: bytes, terms, delims: bytes = DEFAULT_DELIMS, emits: int = 20,
     if exclude is not None:
         exclude = _check_exclude(terms, exclude)
         lines, counts = phrase(text, terms, delims, emits, max_key, first_line,
-                               wildcard=wildcard, glob=glob, ignore_case=ignore_case)
+                               wildcard=wildcard, glob=glob, ignore_case=ignore_case, fuzzy=fuzzy)
         gone, xcounts = _excluded_by_text(text, exclude, wildcard, delims, emits, max_key,
-                                          first_line, glob, ignore_case)
+                                          first_line, glob, ignore_case, fuzzy)
         return [l for l in lines if l not in gone], counts + xcounts
     if not 1 <= len(terms) <= MAX_SEARCH_TERMS:
         raise ValueError("a query takes 1 to %d terms" % MAX_SEARCH_TERMS)
-    if wildcard or glob or ignore_case:  # (``glob`` / ``ignore_case``: PATTERN_RULES)
-        want = query_terms(terms, wildcard, glob, ignore_case, delims, max_key)
+    if wildcard or glob or ignore_case or fuzzy:  # (``glob`` / ``ignore_case``: PATTERN_RULES)
+        want = query_terms(terms, wildcard, glob, ignore_case, delims, max_key,
+                       fuzzy=fuzzy)
         m = len(want)
 
         def fits(tok, term):
@@ -519,7 +605,7 @@ MAX_SEARCH_WITHIN = (1 << 32) - 1
 
 def near(text: bytes, terms, within: int, delims: bytes = DEFAULT_DELIMS, emits: int = 20,
          max_key: int = 29, first_line: int = 0, *, wildcard: bool = False, exclude=None,
-         glob: bool = False, ignore_case: bool = False):
+         glob: bool = False, ignore_case: bool = False, fuzzy: bool = False):
     """One proximity query over ``text``: ``(lines, counts)``, as ``search`` answers.
 
     `near` answers the lines on which the terms occur within ``within`` = W tokens of one
@@ -547,9 +633,9 @@ def near(text: bytes, terms, within: int, delims: bytes = DEFAULT_DELIMS, emits:
     if exclude is not None:
         exclude = _check_exclude(terms, exclude)
         lines, counts = near(text, terms, within, delims, emits, max_key, first_line,
-                             wildcard=wildcard, glob=glob, ignore_case=ignore_case)
+                             wildcard=wildcard, glob=glob, ignore_case=ignore_case, fuzzy=fuzzy)
         gone, xcounts = _excluded_by_text(text, exclude, wildcard, delims, emits, max_key,
-                                          first_line, glob, ignore_case)
+                                          first_line, glob, ignore_case, fuzzy)
         return [l for l in lines if l not in gone], counts + xcounts
     if not 1 <= len(terms) <= MAX_SEARCH_TERMS:
         raise ValueError("a query takes 1 to %d terms" % MAX_SEARCH_TERMS)
@@ -557,7 +643,8 @@ def near(text: bytes, terms, within: int, delims: bytes = DEFAULT_DELIMS, emits:
             not 1 <= within <= MAX_SEARCH_WITHIN:
         raise ValueError("a near query takes a window 1 <= W < 2^32, not %r" % (within,))
     # (``glob`` / ``ignore_case``: PATTERN_RULES)
-    want = query_terms(terms, wildcard, glob, ignore_case, delims, max_key)
+    want = query_terms(terms, wildcard, glob, ignore_case, delims, max_key,
+                       fuzzy=fuzzy)
 
     def fits(tok, term):
         return term.fits(tok)
@@ -607,7 +694,7 @@ RANK_MAX_EMITS = 65536
 
 def rank(entries, postings, lines, terms, k: int, max_key: int = 29, *,
          wildcard: bool = False, delims: bytes = DEFAULT_DELIMS, exclude=None,
-         glob: bool = False, ignore_case: bool = False, emits=None):
+         glob: bool = False, ignore_case: bool = False, fuzzy: bool = False, emits=None):
     """The ranked answer of one query: ``(top, matches)``.
 
     ``lines`` is the query's matching set, as ``search`` or ``phrase`` answered it; ranking
@@ -640,31 +727,33 @@ def rank(entries, postings, lines, terms, k: int, max_key: int = 29, *,
     if k < 1:
         raise ValueError("rank takes k >= 1")
     if emits is not None:
-        pat = any(t.kind == "pattern" for t in query_terms(
-            list(terms) + list(exclude or []), wildcard, glob, ignore_case, delims, max_key))
+        pat = any(t.scattered for t in query_terms(
+            list(terms) + list(exclude or []), wildcard, glob, ignore_case, delims, max_key,
+                       fuzzy=fuzzy))
         if emits > (RANK_MAX_EMITS // MAX_SEARCH_TERMS if pat else RANK_MAX_EMITS):
             raise ValueError("a ranked search takes emits_per_line <= %d"
                              % (RANK_MAX_EMITS // MAX_SEARCH_TERMS if pat else RANK_MAX_EMITS))
     if exclude is not None:
         exclude = _check_exclude(list(terms), exclude)
         gone, _counts = _excluded_by_index(entries, postings, exclude, wildcard, delims,
-                                           max_key, glob, ignore_case)
+                                           max_key, glob, ignore_case, fuzzy)
         return rank(entries, postings, [l for l in lines if l not in gone], terms, k,
                     max_key, wildcard=wildcard, delims=delims, glob=glob,
-                    ignore_case=ignore_case)
-    if wildcard or glob or ignore_case:
+                    ignore_case=ignore_case, fuzzy=fuzzy)
+    if wildcard or glob or ignore_case or fuzzy:
         n = len(postings)
-        want = query_terms(terms, wildcard, glob, ignore_case, delims, max_key)
+        want = query_terms(terms, wildcard, glob, ignore_case, delims, max_key,
+                       fuzzy=fuzzy)
         ranges = [set(_qt_words(entries, t)) for t in want]
         lists = []
         for j, rj in enumerate(ranges):
             if not rj:  # absent
                 continue
-            if want[j].kind == "pattern":  # once per distinct pattern; no nesting rule
-                if any(want[i].kind == "pattern" and want[i].ident == want[j].ident
+            if want[j].scattered:  # once per distinct pattern; no nesting rule
+                if any(want[i].scattered and want[i].ident == want[j].ident
                        for i in range(j)):
                     continue
-            elif any(ri and i != j and want[i].kind != "pattern" and rj <= ri and
+            elif any(ri and i != j and not want[i].scattered and rj <= ri and
                      (rj != ri or i < j) for i, ri in enumerate(ranges)):
                 continue
             merged = _term_list(entries, postings, sorted(rj))
@@ -744,7 +833,7 @@ def line_tokens(line: bytes, delims: bytes = DEFAULT_DELIMS, emits: int = 20):
 
 def show(text: bytes, lines, terms, n: int, delims: bytes = DEFAULT_DELIMS, emits: int = 20,
          max_key: int = 29, first_line: int = 0, *, wildcard: bool = False, glob: bool = False,
-         ignore_case: bool = False):
+         ignore_case: bool = False, fuzzy: bool = False):
     """What ``show=n`` adds to one query's answer ``lines`` (global numbers, in result order):
     ``(texts, spans, cut)`` -- per entry the shown bytes and the ``(start, len, mask)`` list,
     and the number of entries whose line was longer than ``n`` (``SHOW_RULES``).  ``terms`` are
@@ -753,7 +842,8 @@ def show(text: bytes, lines, terms, n: int, delims: bytes = DEFAULT_DELIMS, emit
         raise ValueError("show takes 1 <= N <= %d, not %r" % (SHOW_MAX_BYTES, n))
     if len(text) >= 1 << 32:
         raise ValueError("show takes a text of less than 2^32 bytes")
-    want = query_terms(list(terms), wildcard, glob, ignore_case, delims, max_key)
+    want = query_terms(list(terms), wildcard, glob, ignore_case, delims, max_key,
+                       fuzzy=fuzzy)
     all_lines = split_lines(text)
     texts, spans, cut = [], [], 0
     for l in lines:

@@ -21,6 +21,7 @@
 //     words, the words as consecutive tokens in that order, or the words within --within W
 //     tokens of one another; repeat --search for a batch: answered from the index on the
 //     device, or by --backend cpu)
+//     --match expr: the argument is a Boolean expression, "( to AND be ) OR ( Ham* AND NOT Hamlet )"
 //   --within W (with --match near: the window in tokens, W >= 1)
 //   --not "w1 w2" (after a --search: lines that hold one of these words are no answer of it)
 //   --rank K (with --search: each query's K best lines with their scores, best first)
@@ -153,11 +154,18 @@ void help() {
       "                             like the text; repeat --search for a batch.  Answered from the\n"
       "                             index in device memory, or by --backend cpu.  Restrictions\n"
       "                             as --index, and not with --index)\n"
-      "  --match all|any|phrase|near\n"
+      "  --match all|any|phrase|near|expr\n"
       "                             (--search: lines with every word (default), with any, with\n"
       "                             the words as consecutive tokens in the order given, whatever\n"
       "                             delimiters stand between them, or with every word inside some\n"
-      "                             --within W consecutive tokens of the line, in any order)\n"
+      "                             --within W consecutive tokens of the line, in any order.\n"
+      "                             expr: the --search argument is a Boolean expression over up to\n"
+      "                             8 words, \"( to AND be ) OR ( Ham* AND NOT Hamlet )\": AND, OR\n"
+      "                             and NOT in upper case, NOT > AND > OR, parentheses, words side\n"
+      "                             by side joined by AND; split at blanks and parentheses only.\n"
+      "                             Refused: an expression true of a line with none of its words\n"
+      "                             (\"NOT a\"), and --not or --within with it.  With --rank,\n"
+      "                             --show, --wildcard, --glob, --fuzzy, --ignore-case)\n"
       "  --within W                 (--match near, which needs it: the window in tokens,\n"
       "                             1 <= W < 2^32; with W = 2 two words must be neighbours)\n"
       "  --not \"w1 w2 ...\"          (exclusion words of the nearest --search before it, split\n"
@@ -338,8 +346,10 @@ bool parse(int argc, char** argv, CliArgs* a) {
       a->not_args.back() += " " + v;
     } else if (s == "--match") {
       a->match = need("--match");
-      if (a->match != "all" && a->match != "any" && a->match != "phrase" && a->match != "near")
-        throw Error("--match takes all, any, phrase or near (how --search combines its words)");
+      if (a->match != "all" && a->match != "any" && a->match != "phrase" && a->match != "near" &&
+          a->match != "expr")
+        throw Error("--match takes all, any, phrase, near or expr (how --search combines its "
+                    "words; expr: the --search argument is a Boolean expression)");
     } else if (s == "--within") {
       const std::string v = need("--within");
       char* endp = nullptr;
@@ -507,6 +517,15 @@ bool parse(int argc, char** argv, CliArgs* a) {
   };
   for (size_t i = 0; i < a->search_args.size(); ++i) {
     const std::string& arg = a->search_args[i];
+    if (a->match == "expr") {
+      // the argument is the expression: split at blanks and parentheses only (make_search_expr),
+      // so a term that holds a delimiter is refused, not cut in two
+      if (!a->not_args[i].empty())
+        throw Error("--not does not combine with --match expr: write NOT in the expression (\"" +
+                    arg + " AND NOT ...\")");
+      a->queries.push_back(make_search_expr(arg, a->cfg, a->wildcard, a->glob, a->fuzzy));
+      continue;
+    }
     const SearchMode mode = a->match == "any"      ? SearchMode::kAny
                             : a->match == "phrase" ? SearchMode::kPhrase
                             : a->match == "near"   ? SearchMode::kNear
@@ -689,6 +708,8 @@ void json_search(JsonOut& j, const CliArgs& a) {
     j.u("cut_lines", g_search->cut_lines);
     j.u("spans", g_search->spans.size() / 3);
     j.u("wire_bytes", g_search->wire_bytes);
+    j.u("merged", g_search->merged);
+    j.u("walked", g_search->walked);
   }
 }
 

@@ -461,9 +461,181 @@ SearchQuery make_search_query(const std::vector<std::string>& terms, SearchMode 
   return q;
 }
 
+// ---- boolean expressions (engine.hpp): tokens -> terms and a 256-bit truth table ----
+namespace {
+
+using Truth = std::array<u32, kExprTruthWords>;
+
+// The table of the variable t: bit m set when mask m holds term t.
+Truth truth_of_term(u32 t) {
+  static const u32 kLow[5] = {0xaaaaaaaau, 0xccccccccu, 0xf0f0f0f0u, 0xff00ff00u, 0xffff0000u};
+  Truth r{};
+  for (u32 w = 0; w < (u32)kExprTruthWords; ++w)
+    r[w] = t < 5 ? kLow[t] : (((w >> (t - 5)) & 1u) ? ~0u : 0u);
+  return r;
+}
+
+// Recursive descent over the tokens: or := and (OR and)*; and := not ((AND)? not)*;
+// not := NOT* atom; atom := term | ( or ).  The recursion is one level per open parenthesis,
+// at most kExprMaxDepth; a run of NOT is a loop.
+struct ExprParser {
+  const std::vector<std::string>& tok;
+  bool wildcard, glob, fuzzy;
+  SearchQuery* q;
+  std::vector<u8> prefix, pattern, fz;
+  size_t at = 0;
+
+  static bool is_op(const std::string& s) { return s == "AND" || s == "OR" || s == "NOT"; }
+  bool done() const { return at == tok.size(); }
+  // does an operand start here?
+  bool operand_ahead() const {
+    return !done() && tok[at] != ")" && tok[at] != "AND" && tok[at] != "OR";
+  }
+
+  u32 term_number(const std::string& asked) {
+    const SearchQuery one = make_search_query({asked}, SearchMode::kAll, wildcard, 0, {}, glob, fuzzy);
+    const u8 pre = one.is_prefix(0) ? 1 : 0, pat = one.is_pattern(0) ? 1 : 0;
+    const u8 bud = (u8)one.fuzzy_budget(0);
+    for (size_t t = 0; t < q->terms.size(); ++t)
+      if (q->terms[t] == one.terms[0] && prefix[t] == pre && pattern[t] == pat && fz[t] == bud)
+        return (u32)t;
+    LOCUST_CHECK_ARG(q->terms.size() < (size_t)kSearchMaxTerms,
+                     "search: the expression has more than " + std::to_string(kSearchMaxTerms) +
+                         " distinct terms (" + asked + " is one too many)");
+    q->terms.push_back(one.terms[0]);
+    prefix.push_back(pre);
+    pattern.push_back(pat);
+    fz.push_back(bud);
+    return (u32)q->terms.size() - 1;
+  }
+
+  Truth parse_atom(int depth) {
+    bool neg = false;
+    while (!done() && tok[at] == "NOT") {
+      neg = !neg;
+      ++at;
+    }
+    LOCUST_CHECK_ARG(!done(), "search: the expression ends behind a dangling operator (" +
+                                  (at ? tok[at - 1] : std::string("nothing")) +
+                                  "): an operand is missing");
+    const std::string& s = tok[at];
+    LOCUST_CHECK_ARG(s != "AND" && s != "OR",
+                     "search: a dangling operator: " + s + " stands where an operand belongs");
+    LOCUST_CHECK_ARG(s != ")", at && tok[at - 1] == "("
+                                   ? std::string("search: () holds no operand")
+                                   : std::string("search: a dangling operator: ) stands where an "
+                                                 "operand belongs"));
+    Truth r;
+    if (s == "(") {
+      LOCUST_CHECK_ARG(depth < kExprMaxDepth,
+                       "search: the expression nests parentheses deeper than kExprMaxDepth = " +
+                           std::to_string(kExprMaxDepth));
+      ++at;
+      LOCUST_CHECK_ARG(done() || tok[at] != ")", "search: () holds no operand");
+      r = parse_or(depth + 1);
+      LOCUST_CHECK_ARG(!done() && tok[at] == ")",
+                       "search: unbalanced parentheses: a ( is never closed");
+      ++at;
+    } else {
+      r = truth_of_term(term_number(s));
+      ++at;
+    }
+    if (neg)
+      for (u32& w : r) w = ~w;
+    return r;
+  }
+  Truth parse_and(int depth) {
+    Truth r = parse_atom(depth);
+    for (;;) {
+      if (!done() && tok[at] == "AND")
+        ++at;
+      else if (!operand_ahead())
+        return r;
+      const Truth o = parse_atom(depth);
+      for (int w = 0; w < kExprTruthWords; ++w) r[w] &= o[w];
+    }
+  }
+  Truth parse_or(int depth) {
+    Truth r = parse_and(depth);
+    while (!done() && tok[at] == "OR") {
+      ++at;
+      const Truth o = parse_and(depth);
+      for (int w = 0; w < kExprTruthWords; ++w) r[w] |= o[w];
+    }
+    return r;
+  }
+};
+
+}  // namespace
+
+SearchQuery make_search_expr(const std::string& expr, const JobConfig& cfg, bool wildcard,
+                             bool glob, bool fuzzy) {
+  std::vector<std::string> tok;
+  std::string cur;
+  const auto flush = [&] {
+    if (!cur.empty()) tok.push_back(cur);
+    cur.clear();
+  };
+  for (const char ch : expr) {
+    if (ch == ' ' || ch == '\t') {
+      flush();
+    } else if (ch == '(' || ch == ')') {
+      flush();
+      tok.emplace_back(1, ch);
+    } else {
+      cur.push_back(ch);
+    }
+  }
+  flush();
+  LOCUST_CHECK_ARG(!tok.empty(), "search: an empty expression");
+  SearchQuery q;
+  q.mode = SearchMode::kExpr;
+  // as asked: runs of blanks collapsed to one space, the ends trimmed
+  cur.clear();
+  bool gap = false;
+  for (const char ch : expr) {
+    if (ch == ' ' || ch == '\t') {
+      gap = !cur.empty();
+      continue;
+    }
+    if (gap) cur.push_back(' ');
+    gap = false;
+    cur.push_back(ch);
+  }
+  q.expr = cur;
+  ExprParser p{tok, wildcard, glob, fuzzy, &q, {}, {}, {}, 0};
+  q.truth = p.parse_or(0);
+  LOCUST_CHECK_ARG(p.done(), p.tok[p.at] == ")"
+                                 ? std::string("search: unbalanced parentheses: a ) closes nothing")
+                                 : "search: a dangling operator: " + p.tok[p.at] +
+                                       " stands where the expression should end");
+  // (only the masks over the query's own terms matter: the others repeat them)
+  for (const u8 f : p.prefix)
+    if (f) q.prefix = p.prefix;
+  for (const u8 f : p.pattern)
+    if (f) q.pattern = p.pattern;
+  for (const u8 f : p.fz)
+    if (f) q.fuzzy = p.fz;
+  check_search_queries({q}, cfg);
+  return q;
+}
+
 void check_search_queries(const std::vector<SearchQuery>& queries, const JobConfig& cfg) {
   for (size_t i = 0; i < queries.size(); ++i) {
     const SearchQuery& q = queries[i];
+    if (q.mode == SearchMode::kExpr) {
+      LOCUST_CHECK_ARG(q.excluded == 0 && q.within == 0,
+                       "search: query " + std::to_string(i) + " is an expression: it takes no "
+                       "exclusion terms (exclude, --not) and no window (within): write NOT in the "
+                       "expression instead");
+      LOCUST_CHECK_ARG(!q.expr.empty(), "search: query " + std::to_string(i) +
+                                            " is an expression query without an expression (use "
+                                            "make_search_expr)");
+      LOCUST_CHECK_ARG(!q.truth_at(0),
+                       "search: the expression " + q.expr + " is true of a line that holds none of "
+                       "its words (as NOT a, or a OR NOT b, is): the index cannot list such lines; "
+                       "combine the NOT with a positive term (b AND NOT a)");
+    }
     LOCUST_CHECK_ARG(!q.terms.empty() && q.terms.size() <= (size_t)kSearchMaxTerms,
                      "search: query " + std::to_string(i) + " has " +
                          std::to_string(q.terms.size()) + " terms; a query takes 1 to " +
@@ -845,6 +1017,7 @@ SearchResult search_index_impl(const IndexResult& x, const TextInput* text,
     std::vector<std::vector<u32>> own;  // the merged lists of this query's prefix terms
     const size_t npos = q.positives();
     bool absent = false;
+    std::vector<int> list_of(q.terms.size(), -1);  // kExpr: term t's list in `lists` (-1: absent)
     for (size_t t = 0; t < q.terms.size(); ++t) {
       const bool pos = t < npos;
       SearchPattern sp;
@@ -856,6 +1029,7 @@ SearchResult search_index_impl(const IndexResult& x, const TextInput* text,
           if (o.is_pat && o.pat.meta == sp.meta && key_compare(o.pat.p.w, sp.p.w) == 0) same = &o;
         if (same) {  // repeats an earlier term: the same count, no second list
           r.term_counts[qi * kSearchMaxTerms + t] = same->len;
+          if (pos) list_of[t] = (int)(same - lists.data());
           continue;
         }
         std::vector<size_t> words;
@@ -881,6 +1055,7 @@ SearchResult search_index_impl(const IndexResult& x, const TextInput* text,
           std::sort(own.back().begin(), own.back().end());
           l.p = own.back().data();
         }
+        if (pos) list_of[t] = (int)lists.size();
         into.push_back(l);
         continue;
       }
@@ -908,7 +1083,11 @@ SearchResult search_index_impl(const IndexResult& x, const TextInput* text,
       r.term_counts[qi * kSearchMaxTerms + t] = val[hi] - val[lo];
       std::vector<List>& into = pos ? lists : not_lists;
       bool dup = false;
-      for (const List& o : into) dup |= o.lo == lo && o.hi == hi;
+      for (const List& o : into) {
+        if (o.is_pat || o.lo != lo || o.hi != hi) continue;
+        dup = true;
+        if (pos) list_of[t] = (int)(&o - lists.data());
+      }
       if (dup) continue;
       List l{x.postings.data() + val[lo], val[hi] - val[lo], lo, hi, false, SearchPattern{}};
       if (hi - lo >= 2) {  // a concatenation of sorted lists: merge
@@ -916,6 +1095,7 @@ SearchResult search_index_impl(const IndexResult& x, const TextInput* text,
         std::sort(own.back().begin(), own.back().end());
         l.p = own.back().data();
       }
+      if (pos) list_of[t] = (int)lists.size();
       into.push_back(l);
     }
     // is the line one of the query's excluded lines?
@@ -933,7 +1113,24 @@ SearchResult search_index_impl(const IndexResult& x, const TextInput* text,
         inside |= &o != &l && !o.is_pat && !l.is_pat && o.lo <= l.lo && l.hi <= o.hi;
       if (!inside) scored.push_back(l);
     }
-    if (q.mode != SearchMode::kAny) {
+    if (q.mode == SearchMode::kExpr) {
+      // "boolean expressions": every line of a present term's list, each once; its mask from
+      // the terms' lists, the truth table decides (truth[0] is clear: no other line matches)
+      for (const List& l : lists) r.lines.insert(r.lines.end(), l.p, l.p + l.len);
+      std::sort(r.lines.begin() + (std::ptrdiff_t)from, r.lines.end());
+      r.lines.erase(std::unique(r.lines.begin() + (std::ptrdiff_t)from, r.lines.end()),
+                    r.lines.end());
+      const auto no_match = [&](u32 line) {
+        u32 in_list = 0, mask = 0;  // bit i: the line is in lists[i]; bit t: in term t's list
+        for (size_t i = 0; i < lists.size(); ++i)
+          in_list |= (u32)std::binary_search(lists[i].p, lists[i].p + lists[i].len, line) << i;
+        for (size_t t = 0; t < q.terms.size(); ++t)
+          if (list_of[t] >= 0) mask |= ((in_list >> list_of[t]) & 1u) << t;
+        return !q.truth_at(mask);
+      };
+      r.lines.erase(std::remove_if(r.lines.begin() + (std::ptrdiff_t)from, r.lines.end(), no_match),
+                    r.lines.end());
+    } else if (q.mode != SearchMode::kAny) {
       const bool phrase = q.mode == SearchMode::kPhrase && npos >= 2;
       // (W >= emits_per_line: no line has more tokens, the `all` answer stands)
       const bool near = q.mode == SearchMode::kNear && npos >= 2 &&
@@ -1122,7 +1319,12 @@ void format_search_output(const SearchResult& r, std::string* out, bool mark) {
   for (size_t q = 0; q < r.queries.size(); ++q) {
     out->append("print query:");
     const size_t npos = r.queries[q].positives();
-    for (size_t t = 0; t < r.queries[q].terms.size(); ++t) {
+    const bool expr = r.queries[q].mode == SearchMode::kExpr;
+    if (expr) {  // the expression as asked, where the other modes print the joined terms
+      out->push_back(' ');
+      out->append(r.queries[q].expr);
+    }
+    for (size_t t = 0; !expr && t < r.queries[q].terms.size(); ++t) {
       if (t == npos) out->append(" \t not:");
       out->push_back(' ');
       out->append(r.queries[q].terms[t]);

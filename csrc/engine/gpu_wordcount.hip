@@ -73,7 +73,8 @@ GpuWordCount::Stats GpuWordCount::stats() const {
   s.map_window = impl_->map_window;
   s.search_bytes = impl_->sbatch_bytes + impl_->shits_bytes +
                    impl_->sbatch.merged_cap * sizeof(u32) +
-                   (impl_->d_spat ? search_pattern_bytes() : 0) + impl_->show_entry_cap_bytes +
+                   (impl_->d_spat ? search_pattern_bytes() : 0) +
+                   (impl_->d_sexpr ? search_expr_bytes() : 0) + impl_->show_entry_cap_bytes +
                    impl_->sshow.cap_text + impl_->sshow.cap_spans * 3 * sizeof(u32);
   return s;
 }

@@ -561,6 +561,8 @@ DevicePipeline::~DevicePipeline() {
   if (d_smerged) (void)hipFree(d_smerged);
   if (d_spat) (void)hipFree(d_spat);
   pinned_free(h_spat);
+  if (d_sexpr) (void)hipFree(d_sexpr);
+  pinned_free(h_sexpr);
   pinned_free(h_supload);
   pinned_free(h_sres);
   pinned_free(h_slines);
@@ -2146,6 +2148,15 @@ void DevicePipeline::ensure_search_patterns() {
       pinned_alloc(search_pattern_upload_bytes(), hipHostMallocDefault, "search patterns"));
 }
 
+void DevicePipeline::ensure_search_expr() {
+  if (d_sexpr) return;
+  // first batch of this engine with an `expr` query (engines that never see one keep their
+  // footprint)
+  LOCUST_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&d_sexpr), search_expr_bytes()));
+  h_sexpr = static_cast<u32*>(pinned_alloc(search_expr_upload_bytes(kSearchMaxQueries),
+                                           hipHostMallocDefault, "search expressions"));
+}
+
 void DevicePipeline::check_search_batch(const std::vector<SearchQuery>& queries, u64 rank_k,
                                         bool ignore_case) const {
   LOCUST_CHECK_ARG(queries.size() <= (size_t)kSearchMaxQueries,
@@ -2312,6 +2323,12 @@ void DevicePipeline::search_stage(const std::vector<SearchQuery>& queries, u64 r
   // ... and one with a fuzzy term (engine.hpp "fuzzy terms") the kernels compiled with both
   // matchers (kernels.hpp "fuzzy.hip"): per batch, so the next one is routed afresh
   sbatch.fuzzy = patterns && search_has_fuzzy(queries);
+  // ... and one with an `expr` query (engine.hpp "boolean expressions") the plan and the hit
+  // kernel of kernels.hpp "expr.hip"; a batch without one launches what it always launched
+  bool exprs = false;
+  for (const SearchQuery& sq : queries) exprs |= sq.mode == SearchMode::kExpr;
+  if (exprs) ensure_search_expr();
+  sbatch.expr = exprs ? d_sexpr : nullptr;
   LOCUST_HIP_CHECK(hipEventRecord(ev_search[0], stream));
   if (Q == 0) {
     LOCUST_HIP_CHECK(hipEventRecord(ev_search[1], stream));
@@ -2336,6 +2353,7 @@ void DevicePipeline::search_stage(const std::vector<SearchQuery>& queries, u64 r
     const bool qnear = sq.mode == SearchMode::kNear && npos >= 2 &&
                        sq.within < (u64)cfg.emits_per_line;
     meta[q] = (u32)sq.terms.size() | (sq.mode == SearchMode::kAny      ? kSearchAny
+                                      : sq.mode == SearchMode::kExpr   ? kSearchAny | kSearchExpr
                                       : sq.mode == SearchMode::kPhrase ? kSearchPhrase
                                       : qnear                          ? kSearchNear
                                                                        : 0u);
@@ -2361,11 +2379,34 @@ void DevicePipeline::search_stage(const std::vector<SearchQuery>& queries, u64 r
       const PackedKey k = search_term_key(sq.terms[t], cfg);
       std::memcpy(keys + ((u64)q * kSearchMaxTerms + t) * kKeyWords, k.w, sizeof(PackedKey));
     }
+    if (!exprs) continue;
+    // the expression arrays' upload: the truth table, and which pattern slots are the same term
+    // (equal patterns, as the lookup's identity rule compares them)
+    u32 alias = 0;
+    u32* truth = h_sexpr + kExprTruth + (u64)q * kSearchMaxTerms;
+    std::memset(truth, 0, kSearchMaxTerms * sizeof(u32));
+    if (sq.mode == SearchMode::kExpr) {
+      std::memcpy(truth, sq.truth.data(), kSearchMaxTerms * sizeof(u32));
+      SearchPattern pats[kSearchMaxTerms];
+      for (size_t t = 0; t < sq.terms.size(); ++t) {
+        if (!search_term_pattern(sq, t, cfg, ignore_case, &pats[t])) continue;
+        size_t first = t;
+        for (size_t i = 0; i < t && first == t; ++i)
+          if (((alias >> (24 + i)) & 1u) && pats[i].meta == pats[t].meta &&
+              key_compare(pats[i].p.w, pats[t].p.w) == 0)
+            first = i;
+        alias |= (1u << (24 + (int)t)) | ((u32)first << (3 * (int)t));
+      }
+    }
+    h_sexpr[kExprAlias + q] = alias;
   }
   LOCUST_HIP_CHECK(hipMemcpyAsync(sbatch.upload, h_supload, search_upload_bytes(Q, near),
                                   hipMemcpyHostToDevice, stream));
   if (patterns)
     LOCUST_HIP_CHECK(hipMemcpyAsync(d_spat, h_spat, search_pattern_upload_bytes(),
+                                    hipMemcpyHostToDevice, stream));
+  if (exprs)
+    LOCUST_HIP_CHECK(hipMemcpyAsync(d_sexpr, h_sexpr, search_expr_upload_bytes(Q),
                                     hipMemcpyHostToDevice, stream));
   // lookup (behind the match stage, in a pattern batch): the terms' lists and the bound on the
   // hits
@@ -2378,7 +2419,9 @@ void DevicePipeline::search_stage(const std::vector<SearchQuery>& queries, u64 r
   LOCUST_HIP_CHECK(hipMemcpyAsync(h_tlen, sbatch.t_len, (u64)Q * kSearchMaxTerms * sizeof(u32),
                                   hipMemcpyDeviceToHost, stream));
   sync();
-  const u64 B = h_sc->bound;
+  // B: what search_hit_kernel walks; E: what expr_hit_kernel walks (0 without an `expr` query;
+  // saturated at 2^32 - 1, which the second check below refuses)
+  const u64 B = h_sc->bound, E = exprs ? (u64)h_sc->ebound : 0;
   if (h_sc->anyover)
     throw Error("search: " + std::to_string(h_sc->anyover) + " `any` queries of the batch walk "
                 "2^32 list elements or more each (their pattern terms' lists overlap): split "
@@ -2387,19 +2430,28 @@ void DevicePipeline::search_stage(const std::vector<SearchQuery>& queries, u64 r
     throw Error("search: the batch's " + std::to_string(Q) + " queries walk " + std::to_string(B) +
                 " list elements, which does not fit the 32-bit slot counter (2^32): split "
                 "the batch");
+  // (E == 2^32 - 1: saturated -- the expressions alone walk that many elements or more)
+  if (E == 0xffffffffull || B + E >= (1ull << 32))
+    throw Error("search: the batch's " + std::to_string(Q) + " queries walk " +
+                (E == 0xffffffffull ? "2^32 - 1 or more" : std::to_string(B + E)) +
+                " list elements, " + (E == 0xffffffffull ? "at least " : "") + std::to_string(E) +
+                " of them for its expressions, which does not fit the 32-bit slot counter "
+                "(2^32): split the batch");
   // X: the list elements of the prefix terms that cover two or more words (0: no such term,
   // and nothing below differs from a batch without prefix terms)
   const u64 X = h_sc->merge;
   check_search_merge(Q, X);
-  ensure_search_hits(std::max(B, X));  // (the expand stage's scratch: idle until the hits)
+  ensure_search_hits(std::max(B + E, X));  // (the expand stage's scratch: idle until the hits)
   if (X) {
     // expand: the merged lists, which the hit, phrase and score kernels read as any list
     ensure_search_merged(X);
     launch_search_expand(idx_view, sbatch, Q, X, shits, h_plan, stream);
   }
   r->merged = X;
+  r->walked = B + E;
   // hits; a phrase's and a near query's candidates are verified against the resident text
-  // behind them
+  // behind them.  The `expr` queries' hits come first: the seal behind the others closes both
+  if (E) launch_expr_hits(idx_view, sbatch, Q, E, shits, stream);
   launch_search_hits(idx_view, sbatch, Q, B, verify, near, shits, stream);
   LOCUST_HIP_CHECK(hipMemcpyAsync(h_sc, sbatch.ctr, sizeof(SearchCounters), hipMemcpyDeviceToHost,
                                   stream));
@@ -2413,9 +2465,9 @@ void DevicePipeline::search_stage(const std::vector<SearchQuery>& queries, u64 r
     throw Error("search: " + std::to_string(h_sc->merge_n) + " of " + std::to_string(X) +
                 " list elements of prefix terms merged, " + std::to_string(h_sc->unmerged) +
                 " of them outside their term's range");
-  if (H > B || h_sc->sort_n != H)
+  if (H > B + E || h_sc->sort_n != H)
     throw Error("search: " + std::to_string(H) + " hits written, the lists hold " +
-                std::to_string(B) + " elements");
+                std::to_string(B + E) + " elements");
   if (C > B || h_sc->verified != C || (C && !verify))
     throw Error("search: " + std::to_string(C) + " phrase candidates, " +
                 std::to_string(h_sc->verified) + " of them verified, the lists hold " +

@@ -836,6 +836,11 @@ struct DevicePipeline {
   u32* d_spat = nullptr;
   u32* h_spat = nullptr;
   void ensure_search_patterns();
+  // The expression arrays (kernels.hpp search_expr_*): device words and the pinned upload part,
+  // made by the engine's first batch with an `expr` query.
+  u32* d_sexpr = nullptr;
+  u32* h_sexpr = nullptr;
+  void ensure_search_expr();
   // The batch over idx_view on `stream`, timed by ev_search; synchronises (the bound, the
   // number of hits, the result) and fills r's lists, statistics and wire_bytes.
   // rank_k != 0: the ranked answer (engine.hpp "ranked search").

@@ -1,7 +1,8 @@
 // The verify stage of a search batch (kernels.hpp "search.hip": phrase, near): the bodies of the
 // two kernels that walk a candidate line against its query's terms, compiled per matcher level
 // -- search.hip's kernels without a matcher (kMatch 0) and with the pattern matcher (1),
-// fuzzy.hip's with the fuzzy matcher beside it (2) -- and how a converged wave commits its hits.
+// fuzzy.hip's with the fuzzy matcher beside it (2) -- how a converged wave commits its hits, and how the hit kernels (search.hip, expr.hip) read a
+// term's list.
 #pragma once
 
 #include <algorithm>
@@ -43,6 +44,27 @@ __device__ __forceinline__ void commit_hits(bool hit, u32 q, u32 rel_line, u64* 
     if (lane == leader) atomicAdd(&q_hits[ql], (u32)__popcll(same));
     rem &= ~same;
   }
+}
+
+// Is `line` among the len sorted postings at p?  (Never reads outside [p, p + len).)
+__device__ __forceinline__ bool list_has(const u32* __restrict__ p, u32 len, u32 line) {
+  u32 lo = 0, hi = len;
+  while (lo < hi) {
+    const u32 mid = lo + ((hi - lo) >> 1);
+    if (p[mid] < line)
+      lo = mid + 1;
+    else
+      hi = mid;
+  }
+  return lo < len && p[lo] == line;
+}
+
+// A term's list: at its CSR offset in the postings, or (kSearchMerged, a prefix term of two
+// or more words behind the expand stage) at its offset in `merged`.  Either way t_len
+// elements, and list_has / list_tf stay inside them.
+__device__ __forceinline__ const u32* term_list(const u32* __restrict__ postings,
+                                                const u32* __restrict__ merged, u64 tv) {
+  return ((tv & kSearchMerged) ? merged : postings) + (tv & ~kSearchMerged);
 }
 
 // One wave per candidate; a wave takes `group` (<= 64) consecutive candidates per round,

@@ -8,6 +8,7 @@
 // CpuWordCount is the golden oracle and the `--backend cpu` path (main.cu:489-527).
 #pragma once
 
+#include <array>
 #include <cstddef>
 #include <iterator>
 #include <memory>
@@ -565,6 +566,60 @@ void format_index_output(const IndexResult& r, std::string* out);
 // The device finds a fuzzy term's words by the pattern terms' scan of the dictionary, and a
 // batch that holds one runs kernels compiled with both matchers (kernels.hpp "fuzzy.hip").
 //
+// ---- boolean expressions: `( to AND be ) OR ( Ham* AND NOT Hamlet )` ----
+// A fifth mode, `expr` (SearchMode::kExpr; make_search_expr makes the query), answers a Boolean
+// expression over up to kSearchMaxTerms terms.
+//   Syntax.  An expression is a byte string.  Blanks and tabs separate tokens; `(` and `)` are
+//     always grouping tokens by themselves, wherever they stand (`(to AND be)`).  The tokens
+//     `AND`, `OR` and `NOT`, exactly these upper-case bytes, are operators; every other token is
+//     a term.  Precedence: NOT > AND > OR; AND and OR associate to the left.  Two operands side by
+//     side are joined by an implicit AND: `to be` is `to AND be`.  `and`, `or` and `not` in lower
+//     case are ordinary words; the literal word `AND` cannot be asked for in this mode.
+//   Terms.  A term is read exactly as a term of make_search_query is, under the same wildcard,
+//     glob and fuzzy settings (and the batch's ignore_case) and with their errors, and is cut to
+//     max_key_len at evaluation as every term is.  A term that holds a NUL, a newline or a byte
+//     of the job's delimiter set is refused.  Two operands are the same term when they read to
+//     the same bytes and the same kind (plain, prefix, pattern, fuzzy with its budget).  A query
+//     has 1 to kSearchMaxTerms distinct terms, numbered in order of first occurrence;
+//     SearchQuery::terms, prefix, pattern and fuzzy hold them as for any query, excluded == 0.
+//     SearchQuery::expr is the text as asked, runs of blanks and tabs collapsed to one space and
+//     the ends trimmed; SearchQuery::truth is the expression's truth table, 8 x u32: bit m (bit
+//     m % 32 of word m / 32) is its value when exactly the terms in mask m hold.
+//   Meaning.  A term's lines are the distinct lines of its list (a prefix, pattern or fuzzy term:
+//     of its merged list).  An absent term has no lines: its bit is never set, and it does not
+//     empty the answer.  A line's mask has bit t set when the line is among term t's lines, and
+//     the line matches when truth[mask] is set.  The answer is a pure function of the index:
+//     ascending global line numbers, each once.  term_counts are in term order; `merged` is the
+//     existing rule over the query's terms.
+//   Refused, with an error that names the cause: an empty expression, unbalanced parentheses,
+//     `()`, a dangling operator (`a AND`, `OR b`, `NOT`), more than kSearchMaxTerms distinct
+//     terms, parentheses nested deeper than kExprMaxDepth (the parser recurses once per open
+//     parenthesis and never deeper; runs of NOT are folded in a loop), and an expression with
+//     truth[0] set -- one that is true of a line holding none of its words, such as `NOT a` or
+//     `a OR NOT b`: the index cannot enumerate such lines.  `exclude` and `within` on an `expr`
+//     query are refused: use NOT.  `a AND NOT a` is legal and answers nothing.
+//   Ranked.  The matching set is as above.  The score is `any`'s: the sum over the distinct
+//     present terms of the expression of weight(t) * tf(t, line), whether or not a term stands
+//     under a NOT, with the nesting rule of prefix terms unchanged (and a pattern identical to an
+//     earlier one under ignore_case counted once).  Every match holds at least one present term
+//     (truth[0] is clear), so it scores at least 1; the score bound and the emits_per_line limits
+//     are unchanged.
+//   Show and mark work as for `any`: every emitted token that matches one of the expression's
+//     terms is a span, under a NOT or not, and mask bit t names term t.
+//   Output.  The query's result line prints `expr` where the other modes print the joined terms.
+// The walked set.  The device does not walk the union of all terms' lists (`to AND NOT the` would
+// read the's list to find lines that all come from to's) but the lists of a set S of terms.
+// Let P be the present terms.  S covers when every mask m that is a subset of P and has truth[m]
+// set meets S: then every matching line lies in a list of S.  S is chosen greedily from the list
+// lengths: start with S = P; take the terms in order of list length descending, of equal lengths
+// the higher term number first; drop a term from S when the rest still covers.  If no m inside P
+// has truth[m] set, S is empty and the query walks nothing.  SearchResult::walked is the number
+// of list elements the device's hit stage walked for the batch: the sum over its queries of
+// their bounds (`all`: the driver's list, `any`: the distinct lists, `expr`: the lists of S).  A
+// host evaluation reports 0.
+// The device stage (kernels/expr.hip) looks an `expr` query up as `any` over all its terms, plans
+// S per query, walks S's lists and decides every first occurrence of a line by one lookup in the
+// 256-bit table: no expression tree is interpreted in a kernel.
 // ---- show: the returned lines' text and match spans ----
 // A search job may ask for show = N, a u32 with 1 <= N <= kShowMaxBytes = 65536; show == 0,
 // the default, is the answer described above, bit for bit.  With show = N every entry i of
@@ -601,7 +656,9 @@ constexpr u32 kSearchMaxTerms = 8;
 constexpr u64 kRankMaxEmits = 65536;
 constexpr u32 kRankScoreMax = 32u * (u32)kRankMaxEmits;  // 2^21
 constexpr u64 kSearchMaxWithin = 0xffffffffull;  // a `near` window: 1 <= W <= 2^32 - 1
-enum class SearchMode { kAll, kAny, kPhrase, kNear };
+constexpr int kExprMaxDepth = 64;  // "boolean expressions": open parentheses around one operand
+constexpr int kExprTruthWords = 8;  // the 256-bit truth table of kSearchMaxTerms terms
+enum class SearchMode { kAll, kAny, kPhrase, kNear, kExpr };
 struct SearchQuery {
   std::vector<std::string> terms;
   SearchMode mode = SearchMode::kAll;
@@ -611,6 +668,9 @@ struct SearchQuery {
   std::vector<u8> pattern;  // empty: no pattern term; else parallel to terms, != 0: a pattern term
   std::vector<u8> fuzzy;  // empty: no fuzzy term; else parallel to terms, 1 or 2: a fuzzy term's
                           // budget (terms[t]: its word, without the `~d`), 0: none
+  std::string expr;       // kExpr: the expression as asked, blanks collapsed ("boolean expressions")
+  std::array<u32, kExprTruthWords> truth{};  // kExpr: bit m: the value when exactly mask m holds
+  bool truth_at(u32 m) const { return (truth[(m >> 5) & 7u] >> (m & 31u)) & 1u; }
   bool is_prefix(size_t t) const { return t < prefix.size() && prefix[t] != 0; }
   u32 fuzzy_budget(size_t t) const { return t < fuzzy.size() ? fuzzy[t] : 0u; }
   bool is_pattern(size_t t) const { return t < pattern.size() && pattern[t] != 0; }
@@ -629,6 +689,8 @@ struct SearchResult {
   u64 emits_per_line = 0;            // the job's (a ranked score is at most 32 * this)
   u64 merged = 0;                    // list elements the device merged for prefix terms (0:
                                      // none, or the host evaluation)
+  u64 walked = 0;                    // list elements the device's hit stage walked: the sum of
+                                     // the queries' bounds (0: the host evaluation)
   bool ignore_case = false;          // the batch was evaluated with ignore_case
   u64 first_line = 0;
   // the word job's statistics, as in TopResult
@@ -672,6 +734,12 @@ SearchQuery make_search_query(const std::vector<std::string>& terms, SearchMode 
                               bool wildcard, u64 within = 0,
                               const std::vector<std::string>& exclude = {}, bool glob = false,
                               bool fuzzy = false);
+// The `expr` query of an expression ("boolean expressions" above): the parser, the terms'
+// identification and the truth table.  Every term is read by make_search_query's rules under
+// wildcard, glob and fuzzy, and validated for cfg (check_search_queries).  Throws with the cause
+// for every refusal listed there.
+SearchQuery make_search_expr(const std::string& expr, const JobConfig& cfg, bool wildcard = false,
+                             bool glob = false, bool fuzzy = false);
 // A term as the pattern it is evaluated as: the packed bytes (kv.hpp) and the map of its
 // metacharacters (device/glob.hpp) -- a fuzzy term: its word's bytes and kFuzzyMeta | its
 // budget (device/fuzzy.hpp; term_match evaluates either kind).
@@ -693,7 +761,8 @@ bool search_has_patterns(const std::vector<SearchQuery>& queries, bool ignore_ca
 bool search_has_fuzzy(const std::vector<SearchQuery>& queries);
 // Throws unless every query has 1..kSearchMaxTerms valid terms for cfg's delimiter set, at
 // least one of them positive (and `prefix` empty or as long as `terms`), a `near` query a
-// window in [1, kSearchMaxWithin] and every other query none (within == 0).
+// window in [1, kSearchMaxWithin] and every other query none (within == 0).  An `expr` query:
+// no exclusion term, no window, and truth[0] clear.
 void check_search_queries(const std::vector<SearchQuery>& queries, const JobConfig& cfg);
 // Throws when the `elements` list elements a device batch's prefix terms merge
 // (SearchResult::merged) do not fit the merge's 32-bit element counter.
@@ -734,6 +803,7 @@ SearchResult search_index(const IndexResult& x, const TextInput& text,
 void validate_search(const SearchResult& r);
 // The result lines of a search, one per query:
 //   "print query: <terms joined by one space> \t hits: <h> \t lines: <l0> <l1> ...\n"
+// (an `expr` query: its expression, SearchQuery::expr, in place of the joined terms)
 // (a prefix term as it was asked: with its star; a pattern term as it was asked, too; a fuzzy
 // term with its `~d`;
 // <terms> are the positive terms, and a query

@@ -780,9 +780,10 @@ struct SearchCounters {  // zeroed per batch
   u32 unmerged;   // sorted merge keys outside their slot's x_start range
   u32 ncands;     // `near` candidates the hit kernel wrote (from the end of `cands` down)
   u32 nverified;  // `near` candidates the near kernel has decided
-  u32 anyover;    // `any` queries whose bound (the sum of their lists' lengths; pattern terms'
+  u32 anyover;    // `any` (and `expr`: looked up as `any`, planned by expr.hip) queries whose bound (the sum of their lists' lengths; pattern terms'
                   // lists may overlap) does not fit 32 bits: the host throws
-  u32 pad;
+  u32 ebound;     // E: the elements expr_hit_kernel walks ("expr.hip"), saturated at 2^32 - 1
+                  // (the host refuses a batch that walks 2^32 elements or more anyway)
 };
 static_assert(sizeof(SearchCounters) <= 64, "the counters share one 64-byte block");
 constexpr int kSearchBlock = 256;
@@ -793,6 +794,8 @@ constexpr u32 kSearchAny = 1u << 8;                        // q_meta: nterms | m
 constexpr u32 kSearchPhrase = 1u << 9;                     // (neither bit: `all`)
 constexpr u32 kSearchNear = 1u << 10;  // a `near` query to verify (W < emits_per_line, two or
                                        // more terms); every other `near` query goes as `all`
+constexpr u32 kSearchExpr = 1u << 11;  // an `expr` query (kernels.hpp "expr.hip"): looked up as
+                                       // `any` (kSearchAny is set too), walked by expr.hip
 constexpr int kSearchPrefixShift = 16;  // q_meta bit 16 + t: term t is a prefix term
 constexpr int kSearchExcludeShift = 24;  // q_meta bit 24 + t: term t is an exclusion term (the
                                          // last terms of the query: positive terms stand first)
@@ -871,6 +874,9 @@ struct SearchBatch {
   bool fuzzy = false;      // the batch has a fuzzy term (pat is set, too): the dictionary scan,
                            // the verify and the show kernels are fuzzy.hip's (the engine sets it
                            // per batch)
+  u32* expr = nullptr;     // the expression arrays ("expr.hip") of a batch that has an `expr` query;
+                           // null in every other batch (the engine sets it per batch), and then
+                           // nothing of expr.hip runs
   u32* q_bound = nullptr;  // [Q]
   u64* q_start = nullptr;  // [Q + 1]
   u64* offsets = nullptr;  // [Q + 1]
@@ -904,7 +910,7 @@ u64 search_hits_bytes(u64 cap);
 // Carves `base` (search_hits_bytes(cap) bytes, 256-B aligned).  The caller zeroes h->zeros once.
 void search_hits_carve(char* base, u64 cap, SearchHits* h);
 // lookup + scan: b.ctr->bound, b.ctr->merge, b.t_len and b.q_start are complete when `s` has
-// drained.
+// drained.  A batch with b.expr runs launch_expr_plan between the two.
 void launch_search_lookup(const SearchIndex& ix, const SearchBatch& b, u32 queries, hipStream_t s);
 // expand (only when the lookup reported merge = X > 0): scan + gather + order + strip.
 // b.merged[0 .. X) holds the merged lists and b.t_val names them when `s` has drained; the
@@ -930,6 +936,65 @@ void launch_search_order(const SearchIndex& ix, const SearchBatch& b, u32 querie
 // kRankMaxEmits.  Synchronises as launch_search_order does.
 void launch_search_rank(const SearchIndex& ix, const SearchBatch& b, u32 queries, u64 hits,
                         u32 k, SearchHits& h, SortPlan* h_plan, hipStream_t s);
+
+// ---------------- expr.hip ----------------
+// `expr` queries (engine.hpp "boolean expressions"): a batch that has one carries, in an
+// allocation of its own made by the engine's first such batch, these u32 words.  The first two
+// parts are uploaded per batch (kSearchMaxQueries + Q * 8 words), the rest written by the plan:
+//   alias  [kSearchMaxQueries] the host's identification of the query's pattern slots: bits
+//          24 + t: term t is a pattern slot; bits 3 t .. 3 t + 2 of such a slot: the query's
+//          first term with an equal pattern (itself, mostly).  0 for a query of another mode
+//   truth  [kSearchSlots] query q's truth table in words q * 8 .. q * 8 + 7
+//   plan   [kSearchMaxQueries] S | P << 8: the walked set and the present terms
+//   src    [kSearchMaxQueries] bits 3 t .. 3 t + 2: the query's first term with term t's list
+//   bound  [kSearchMaxQueries] the elements the query walks: the lengths of S's lists
+//   start  [kSearchMaxQueries + 1] u64: the exclusive scan of bound; start[Q] = the batch's E
+//          (also, saturated, in SearchCounters::ebound: the lookup's readback brings it)
+// The lookup treats an `expr` query (q_meta: kSearchExpr | kSearchAny) as `any` over all its
+// terms, which gives t_val, t_len, x_len and the score mask.  Then, for such a batch only:
+//   plan     expr_plan_kernel, one workgroup, one thread per query, between the lookup and the
+//            scan of the bounds, so before the expand stage rewrites t_val.  src: a pattern slot takes the
+//            host's identification; any other present term the first earlier non-pattern term
+//            with equal t_val and t_len (the same CSR range: the same words).  A wide term that
+//            repeats an earlier term's words is not merged, so its own t_val names an unsorted
+//            concatenation: every later reader goes through src.  S: the greedy choice of
+//            engine.hpp "the walked set" -- "some m inside U has truth[m] set" is eight masked
+//            word tests on the table in registers.  bound = the summed lengths of S's lists
+//            (past 32 bits: ctr->anyover, as `any`); q_bound[q] = 0, so search_hit_kernel never
+//            sees the query.  A query of another mode gets bound 0 here.  The same pass scans
+//            the bounds into start[0 .. Q] (a block scan per 256 queries, the carry in a
+//            register) and leaves E in ctr->ebound: one launch, no copy of its own
+//   (the host reads E with the lookup's readback; B + E sizes the hit workspace and joins the
+//   batch's 2^32 check)
+//   hits     expr_hit_kernel, in front of search_hit_kernel: the element space [0, E) in tiles of
+//            kSearchTile, grid-stride.  An element finds its query by a binary search in start,
+//            then its term of S and its position in that term's list.  It counts when it is the
+//            first of its line in the list and no earlier list of S holds the line; its mask
+//            comes from list_has over the other present terms (each distinct list searched
+//            once), and the table bit decides.  Hits go through commit_hits into the same
+//            pairs and q_hits: seal, order, emit, rank and show run unchanged.  No polled word,
+//            no LDS, no scratch
+constexpr u64 kExprAlias = 0;
+constexpr u64 kExprTruth = kExprAlias + kSearchMaxQueries;
+constexpr u64 kExprPlan = kExprTruth + kSearchSlots;
+constexpr u64 kExprSrc = kExprPlan + kSearchMaxQueries;
+constexpr u64 kExprBound = kExprSrc + kSearchMaxQueries;
+constexpr u64 kExprStart = kExprBound + kSearchMaxQueries;  // (u64 words: an even offset)
+constexpr u64 kExprEnd = kExprStart + 2 * ((u64)kSearchMaxQueries + 1);
+static_assert(kExprStart % 2 == 0, "start holds u64 words");
+inline u64 search_expr_bytes() { return kExprEnd * sizeof(u32); }
+inline u64 search_expr_upload_bytes(u32 queries) {
+  return (kExprTruth + (u64)queries * kSearchMaxTerms) * sizeof(u32);
+}
+LOCUST_HD inline const u64* search_expr_start(const u32* expr) {
+  return reinterpret_cast<const u64*>(expr + kExprStart);
+}
+// plan and scan in one launch (called by launch_search_lookup for a batch with b.expr).
+void launch_expr_plan(const SearchBatch& b, u32 queries, hipStream_t s);
+// hits over the `ebound` elements the plan reported (b.expr's start[Q]); before
+// launch_search_hits, whose seal closes the batch's hits.  ebound + the plain bound <= h.cap.
+void launch_expr_hits(const SearchIndex& ix, const SearchBatch& b, u32 queries, u64 ebound,
+                      const SearchHits& h, hipStream_t s);
 
 // ---------------- show.hip ----------------
 // The show stage of a search batch (engine.hpp "show"): for each of the E returned lines, in
@@ -1020,6 +1085,7 @@ void launch_string_selftest(const char* blob, const u32* off, u32 n, const char*
 // 573 MB fat binary), +1.3 GB of host memory and ~150 ms per process.
 void warm_module_dict();
 void warm_module_exchange();
+void warm_module_expr();  // (as search: the code object only, no buffers)
 void warm_module_fuzzy();  // (as search: the code object only, no buffers)
 void warm_module_index();  // (as topk below: the code object only, no buffers)
 void warm_module_map();
@@ -1041,6 +1107,7 @@ void warm_module_topk();
 inline void warm_kernel_modules() {
   warm_module_dict();
   warm_module_exchange();
+  warm_module_expr();
   warm_module_fuzzy();
   warm_module_index();
   warm_module_map();

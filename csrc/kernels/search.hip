@@ -340,19 +340,7 @@ __global__ __launch_bounds__(256) void search_strip_kernel(
   }
 }
 
-// Is `line` among the len sorted postings at p?  (Never reads outside [p, p + len).)
-__device__ __forceinline__ bool list_has(const u32* __restrict__ p, u32 len, u32 line) {
-  u32 lo = 0, hi = len;
-  while (lo < hi) {
-    const u32 mid = lo + ((hi - lo) >> 1);
-    if (p[mid] < line)
-      lo = mid + 1;
-    else
-      hi = mid;
-  }
-  return lo < len && p[lo] == line;
-}
-
+// (list_has and term_list, which expr.hip shares: device/verify.hpp)
 // How often does `line` occur among the len sorted postings at p?  (Never reads outside
 // [p, p + len).)
 __device__ __forceinline__ u32 list_tf(const u32* __restrict__ p, u32 len, u32 line) {
@@ -383,14 +371,6 @@ __device__ __forceinline__ u32 list_tf(const u32* __restrict__ p, u32 len, u32 l
       hi = mid;
   }
   return lo - first;
-}
-
-// A term's list: at its CSR offset in the postings, or (kSearchMerged, a prefix term of two
-// or more words behind the expand stage) at its offset in `merged`.  Either way t_len
-// elements, and list_has / list_tf stay inside them.
-__device__ __forceinline__ const u32* term_list(const u32* __restrict__ postings,
-                                                const u32* __restrict__ merged, u64 tv) {
-  return ((tv & kSearchMerged) ? merged : postings) + (tv & ~kSearchMerged);
 }
 
 
@@ -801,6 +781,8 @@ void launch_search_lookup(const SearchIndex& ix, const SearchBatch& b, u32 queri
       ix.recs, ix.n, ix.val, b.keys, b.q_meta, queries, b.t_val, b.t_len, b.q_info, b.q_bound,
       b.x_len, b.ctr, b.pat, b.pat ? b.pat + kSearchPatWords : nullptr);
   LOCUST_HIP_LAUNCH_CHECK();
+  // (a batch that has an `expr` query: their walked sets and bounds; they leave q_bound)
+  if (b.expr) launch_expr_plan(b, queries, s);
   search_scan_kernel<<<dim3(1), dim3(kSearchBlock), 0, s>>>(b.q_bound, queries, ~0u, b.q_start,
                                                             &b.ctr->bound);
   LOCUST_HIP_LAUNCH_CHECK();

@@ -238,8 +238,11 @@ struct PySearchResult {
 // trailing `*`.  within: empty, or one window per query (0: none; check_search_queries holds
 // it against the mode).  exclude: empty, or one list of exclusion terms per query (an empty
 // list: none).  glob: make_search_query's rule for `*` and `?` anywhere in a term; fuzzy: its
-// rule for a trailing `~1` or `~2`.
-std::vector<SearchQuery> to_queries(const std::vector<std::vector<std::string>>& queries,
+// rule for a trailing `~1` or `~2`.  any[i] == 4: an `expr` query -- queries[i] holds one
+// element, the expression (make_search_expr; cfg: the job's delimiters); a window or exclusion
+// terms given for it are refused by the engines' check_search_queries.
+std::vector<SearchQuery> to_queries(const JobConfig& cfg,
+                                    const std::vector<std::vector<std::string>>& queries,
                                     const std::vector<int>& any, bool wildcard,
                                     const std::vector<u64>& within,
                                     const std::vector<std::vector<std::string>>& exclude,
@@ -250,7 +253,21 @@ std::vector<SearchQuery> to_queries(const std::vector<std::vector<std::string>>&
   LOCUST_CHECK_ARG(exclude.empty() || exclude.size() == queries.size(),
                    "search: one list of exclusion terms (exclude) per query, or none");
   std::vector<SearchQuery> out(queries.size());
-  for (size_t i = 0; i < queries.size(); ++i)
+  for (size_t i = 0; i < queries.size(); ++i) {
+    if (any[i] == 4) {
+      LOCUST_CHECK_ARG(queries[i].size() == 1,
+                       "search: an expr query is one expression (bytes, or a one-element list), "
+                       "not " + std::to_string(queries[i].size()) + " terms");
+      out[i] = make_search_expr(queries[i][0], cfg, wildcard, glob, fuzzy);
+      // (a window or exclusion terms on it: carried along as given, for check_search_queries,
+      // which every engine runs before anything else, to refuse)
+      if (!within.empty()) out[i].within = within[i];
+      if (!exclude.empty() && !exclude[i].empty()) {
+        out[i].terms.insert(out[i].terms.end(), exclude[i].begin(), exclude[i].end());
+        out[i].excluded = (u32)exclude[i].size();
+      }
+      continue;
+    }
     out[i] = make_search_query(queries[i],
                                any[i] == 0   ? SearchMode::kAll
                                : any[i] == 2 ? SearchMode::kPhrase
@@ -259,6 +276,7 @@ std::vector<SearchQuery> to_queries(const std::vector<std::vector<std::string>>&
                                wildcard, within.empty() ? 0 : within[i],
                                exclude.empty() ? std::vector<std::string>() : exclude[i], glob,
                                fuzzy);
+  }
   return out;
 }
 
@@ -295,7 +313,8 @@ PySearchResult PyIndexResult::search(const std::vector<std::vector<std::string>>
                                      bool wildcard, const std::vector<u64>& within,
                                      const std::vector<std::vector<std::string>>& exclude, bool glob,
                         bool ignore_case, const py::object& show, bool fuzzy) const {
-  const std::vector<SearchQuery> q = to_queries(queries, any, wildcard, within, exclude, glob, fuzzy);
+  const std::vector<SearchQuery> q =
+      to_queries(cfg, queries, any, wildcard, within, exclude, glob, fuzzy);
   const u64 k = to_rank(rank);
   const u64 n = to_show(show);
   py::gil_scoped_release nogil;
@@ -446,7 +465,8 @@ class PyGpuEngine {
                             const std::vector<u64>& within,
                             const std::vector<std::vector<std::string>>& exclude, bool glob,
                         bool ignore_case, const py::object& show, bool fuzzy) {
-    const std::vector<SearchQuery> q = to_queries(queries, any, wildcard, within, exclude, glob, fuzzy);
+    const std::vector<SearchQuery> q =
+        to_queries(eng_.config(), queries, any, wildcard, within, exclude, glob, fuzzy);
     const u64 k = to_rank(rank);
     const u64 n = to_show(show);
     py::gil_scoped_release nogil;
@@ -459,7 +479,8 @@ class PyGpuEngine {
                             const std::vector<u64>& within,
                             const std::vector<std::vector<std::string>>& exclude, bool glob,
                         bool ignore_case, const py::object& show, bool fuzzy) {
-    const std::vector<SearchQuery> q = to_queries(queries, any, wildcard, within, exclude, glob, fuzzy);
+    const std::vector<SearchQuery> q =
+        to_queries(eng_.config(), queries, any, wildcard, within, exclude, glob, fuzzy);
     const u64 k = to_rank(rank);
     const u64 n = to_show(show);
     py::gil_scoped_release nogil;
@@ -470,7 +491,8 @@ class PyGpuEngine {
                                  bool wildcard, const std::vector<u64>& within,
                                  const std::vector<std::vector<std::string>>& exclude, bool glob,
                         bool ignore_case, const py::object& show, bool fuzzy) {
-    const std::vector<SearchQuery> q = to_queries(queries, any, wildcard, within, exclude, glob, fuzzy);
+    const std::vector<SearchQuery> q =
+        to_queries(eng_.config(), queries, any, wildcard, within, exclude, glob, fuzzy);
     const u64 k = to_rank(rank);
     const u64 n = to_show(show);
     py::gil_scoped_release nogil;
@@ -1076,6 +1098,9 @@ PYBIND11_MODULE(_locust, m) {
       .def_property_readonly("max_key_len", [](const PySearchResult& p) { return p.r.max_key_len; })
       .def_property_readonly("index_ms", [](const PySearchResult& p) { return p.r.index_ms; })
       .def_property_readonly("search_ms", [](const PySearchResult& p) { return p.r.search_ms; })
+      .def_property_readonly("walked", [](const PySearchResult& p) { return p.r.walked; },
+                             "list elements the device's hit stage walked for the batch: the sum "
+                             "of the queries' bounds (0: evaluated on the host)")
       .def_property_readonly("merged", [](const PySearchResult& p) { return p.r.merged; },
                              "list elements the device merged for prefix terms")
       .def_property_readonly("wire_bytes", [](const PySearchResult& p) { return p.r.wire_bytes; },
@@ -1165,7 +1190,7 @@ PYBIND11_MODULE(_locust, m) {
                         bool ignore_case, const py::object& show, bool fuzzy) {
     CpuWordCount eng(cfg);
     return PySearchResult{eng.run_search(as_input(text, first_line),
-                                         to_queries(queries, any, wildcard, within, exclude, glob, fuzzy),
+                                         to_queries(cfg, queries, any, wildcard, within, exclude, glob, fuzzy),
                                          to_rank(rank), ignore_case, to_show(show))};
   }, py::arg("cfg"), py::arg("text"), py::arg("queries"), py::arg("any"),
         py::arg("first_line") = 0, py::arg("rank") = py::none(), py::arg("wildcard") = false,
@@ -1173,6 +1198,30 @@ PYBIND11_MODULE(_locust, m) {
            py::arg("exclude") = std::vector<std::vector<std::string>>(),
            py::arg("glob") = false, py::arg("ignore_case") = false, py::arg("show") = py::none(),
            py::arg("fuzzy") = false);
+  m.def("make_search_expr", [](const JobConfig& cfg, const std::string& expr, bool wildcard,
+                               bool glob, bool fuzzy) {
+    // engine.hpp "boolean expressions": the parsed query's parts (tests, tools)
+    const SearchQuery q = make_search_expr(expr, cfg, wildcard, glob, fuzzy);
+    py::dict d;
+    py::list terms, kinds, truth;
+    for (size_t t = 0; t < q.terms.size(); ++t) {
+      terms.append(py::bytes(q.terms[t]));
+      kinds.append(q.fuzzy_budget(t) ? "fuzzy" : q.is_pattern(t) ? "pattern"
+                   : q.is_prefix(t)  ? "prefix" : "plain");
+    }
+    for (const u32 w : q.truth) truth.append(w);
+    d["expr"] = py::bytes(q.expr);
+    d["terms"] = terms;
+    d["kinds"] = kinds;
+    d["truth"] = truth;
+    d["excluded"] = q.excluded;
+    return d;
+  }, py::arg("cfg"), py::arg("expr"), py::arg("wildcard") = false, py::arg("glob") = false,
+        py::arg("fuzzy") = false,
+        "The `expr` query of an expression: its text with blanks collapsed, its distinct terms in "
+        "order of first occurrence, their kinds and the 8 x u32 truth table; throws for every "
+        "refused expression.");
+  m.attr("kExprMaxDepth") = kExprMaxDepth;
   m.def("check_search_show", &check_search_show, py::arg("show"), py::arg("text_bytes"),
         "Throws unless show is 0 or 1 <= N <= kShowMaxBytes over a window of < 2^32 bytes.");
   m.def("validate_show", [](const std::vector<std::string>& terms, const std::vector<u32>& lines,

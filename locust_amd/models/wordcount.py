@@ -15,7 +15,7 @@ from ..config import make_config, make_dist_config
 _C = load()
 
 
-_SEARCH_MODES = {"all": 0, "any": 1, "phrase": 2, "near": 3}
+_SEARCH_MODES = {"all": 0, "any": 1, "phrase": 2, "near": 3, "expr": 4}
 
 
 def _search_exclude(exclude, n):
@@ -36,18 +36,30 @@ def _search_exclude(exclude, n):
 
 
 def _search_args(queries, mode, within=None, exclude=None):
-    """(term lists, one mode flag per query: 0 all, 1 any, 2 phrase, 3 near, one window per
+    """(term lists, one mode flag per query: 0 all, 1 any, 2 phrase, 3 near, 4 expr, one window per
     query: 0 none, one list of exclusion terms per query or none at all) for the native search
     entry points."""
-    queries = [list(q) for q in queries]
-    exclude = _search_exclude(exclude, len(queries))
+    queries = list(queries)
     modes = [mode] * len(queries) if isinstance(mode, str) else list(mode)
     if len(modes) != len(queries):
         raise ValueError("search: one mode per query")
+    # (an 'expr' query may be given as the expression itself: bytes, not a list of terms)
+    queries = [[q] if m == "expr" and isinstance(q, (bytes, str)) else list(q)
+               for q, m in zip(queries, modes)]
+    exclude = _search_exclude(exclude, len(queries))
     for m in modes:
         if m not in _SEARCH_MODES:
-            raise ValueError("search: mode must be 'all', 'any', 'phrase' or 'near', not %r"
-                             % (m,))
+            raise ValueError("search: mode must be 'all', 'any', 'phrase', 'near' or 'expr', "
+                             "not %r" % (m,))
+    for q, m, x in zip(queries, modes, exclude or [[]] * len(queries)):
+        if m != "expr":
+            continue
+        if len(q) != 1:
+            raise ValueError("search: an 'expr' query is one expression (bytes, or a "
+                             "one-element list), not %d terms" % len(q))
+        if x:
+            raise ValueError("search: an 'expr' query takes no exclusion terms (exclude): "
+                             "write NOT in the expression instead")
     if not isinstance(within, (list, tuple)):  # one window for the batch's near queries
         windows = [within if m == "near" else None for m in modes]
         if within is not None and "near" not in modes:
@@ -134,7 +146,16 @@ class Engine:
         states the rules), or a list with one mode per query.  ``within`` is the window of
         the ``"near"`` queries, which need one: an int ``W`` with ``1 <= W < 2**32`` for all
         of them, or a list with one entry per query, ``None`` for a query that is not
-        ``"near"``.  ``lines(i)`` are query
+        ``"near"``.  ``"expr"`` answers a Boolean expression: the query is one bytes
+        expression (or a one-element list) such as ``b"( to AND be ) OR ( Ham* AND NOT
+        Hamlet )"`` -- ``AND``, ``OR``, ``NOT`` in upper case, parentheses, side-by-side operands
+        joined by ``AND``, at most 8 distinct terms read under ``wildcard`` / ``glob`` /
+        ``fuzzy`` as any term is (``oracle.EXPR_RULES`` states the rules).  An expression that
+        is true of a line with none of its words (``NOT a``) is refused, and so are
+        ``exclude`` and ``within`` on such a query.  It may share a batch with queries of the
+        other modes.  On the GPU the query walks only a covering set of its terms' lists;
+        ``walked`` is the number of list elements the batch's hit stage walked.
+        ``lines(i)`` are query
         ``i``'s global line numbers, ascending, each once.  On the GPU the index stays in
         device memory and only the answers cross PCIe (at most ``_C.kSearchMaxQueries``
         queries per batch; ``run_index(text).search(...)`` evaluates any number of all/any

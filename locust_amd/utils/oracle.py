@@ -664,6 +664,199 @@ def near(text: bytes, terms, within: int, delims: bytes = DEFAULT_DELIMS, emits:
     return lines, counts
 
 
+EXPR_RULES = """
+    Boolean expressions (``mode="expr"``): ``( to AND be ) OR ( Ham* AND NOT Hamlet )``.
+
+    - Syntax.  An expression is a byte string.  Blanks and tabs separate tokens; ``(`` and ``)``
+      are grouping tokens by themselves wherever they stand.  The tokens ``AND``, ``OR`` and
+      ``NOT``, exactly these upper-case bytes, are operators; every other token is a term.
+      ``NOT`` binds tighter than ``AND``, ``AND`` tighter than ``OR``; ``AND`` and ``OR``
+      associate to the left; two operands side by side are joined by ``AND``.  ``and``, ``or``
+      and ``not`` in lower case are words; the word ``AND`` cannot be asked for.
+    - Terms.  A term is read exactly as a term of any query is (``query_terms``: ``wildcard``,
+      ``glob``, ``fuzzy``, ``ignore_case``, the cut to ``max_key``) and with the same errors; one
+      that holds a NUL, a newline or a delimiter is refused.  Two operands are the same term when
+      they read to the same bytes and the same kind.  A query has 1 to 8 distinct terms, numbered
+      in order of first occurrence.
+    - Meaning.  A term's lines are the distinct lines of its (merged) list; an absent term has
+      none and does not empty the answer.  A line matches when the expression holds with every
+      term replaced by "the line is among the term's lines".  Ascending line numbers, each once.
+      ``counts`` are in term order.
+    - Refused (``ValueError``): an empty expression, unbalanced parentheses, ``()``, a dangling
+      operator, more than 8 distinct terms, parentheses nested deeper than ``EXPR_MAX_DEPTH``, and
+      an expression that holds for a line with none of its words (``NOT a``, ``a OR NOT b``).
+      ``a AND NOT a`` is legal and answers nothing.
+    - Ranked: the matching set as above, the score ``any``'s over the expression's terms (``rank``
+      with these terms), under a ``NOT`` or not.  Show: ``show`` with these terms.
+    - Output: the result line prints the expression, runs of blanks collapsed to one space and
+      the ends trimmed (``expr_text``), where the other modes print the joined terms.
+    - The walked set (``expr_walked``).  P: the present terms.  A set S of terms covers when every
+      set m of terms inside P for which the expression holds (exactly the terms of m holding)
+      meets S.  Greedy: S = P; the terms by list length descending, of equal lengths the higher
+      term number first; a term is dropped when the rest still covers.  If the expression holds
+      for no m inside P, S is empty.  The device walks the summed lengths of S's lists.
+
+    The evaluation here shares nothing with the engines' truth table: the parsed tree is
+    evaluated per line with set membership.
+"""
+
+EXPR_MAX_DEPTH = 64
+
+
+def expr_tokens(expr: bytes):
+    out, cur = [], bytearray()
+    for c in expr:
+        if c in b" \t()":
+            if cur:
+                out.append(bytes(cur))
+                cur = bytearray()
+            if c in b"()":
+                out.append(bytes([c]))
+        else:
+            cur.append(c)
+    if cur:
+        out.append(bytes(cur))
+    return out
+
+
+def expr_text(expr: bytes) -> bytes:
+    """The expression as a result line prints it."""
+    return b" ".join(p for p in re.split(rb"[ \t]+", expr) if p)
+
+
+def expr_parse(expr: bytes, delims: bytes = DEFAULT_DELIMS, max_key: int = 29, *,
+               wildcard: bool = False, glob: bool = False, fuzzy: bool = False):
+    """``(tree, terms)`` of an expression (``EXPR_RULES``): ``terms`` are its distinct terms as
+    asked, in order of first occurrence; ``tree`` is ``("term", t)``, ``("not", x)``,
+    ``("and", x, y)`` or ``("or", x, y)``.  ``ValueError`` for every refused expression, the one
+    that holds for no word among them."""
+    toks = expr_tokens(expr)
+    if not toks:
+        raise ValueError("an empty expression")
+    terms, idents = [], []
+    pos = 0
+
+    def number(tok):
+        query_terms([tok], wildcard, glob, False, delims, max_key, fuzzy=fuzzy)  # its errors
+        t, = query_terms([tok], wildcard, glob, False, delims, 1 << 30, fuzzy=fuzzy)
+        ident = (t.kind, t.ident if t.scattered else t.p)
+        if ident in idents:
+            return idents.index(ident)
+        if len(terms) == MAX_SEARCH_TERMS:
+            raise ValueError("more than %d distinct terms" % MAX_SEARCH_TERMS)
+        terms.append(tok)
+        idents.append(ident)
+        return len(terms) - 1
+
+    def atom(depth):
+        nonlocal pos
+        neg = False
+        while pos < len(toks) and toks[pos] == b"NOT":
+            neg, pos = not neg, pos + 1
+        if pos == len(toks) or toks[pos] in (b"AND", b"OR"):
+            raise ValueError("a dangling operator")
+        if toks[pos] == b")":
+            raise ValueError("() holds no operand" if pos and toks[pos - 1] == b"("
+                             else "a dangling operator before )")
+        if toks[pos] == b"(":
+            if depth >= EXPR_MAX_DEPTH:
+                raise ValueError("parentheses nested deeper than %d" % EXPR_MAX_DEPTH)
+            pos += 1
+            x = either(depth + 1)
+            if pos == len(toks) or toks[pos] != b")":
+                raise ValueError("unbalanced parentheses")
+            pos += 1
+        else:
+            x = ("term", number(toks[pos]))
+            pos += 1
+        return ("not", x) if neg else x
+
+    def both(depth):
+        nonlocal pos
+        x = atom(depth)
+        while pos < len(toks) and toks[pos] not in (b")", b"OR"):
+            if toks[pos] == b"AND":
+                pos += 1
+            x = ("and", x, atom(depth))
+        return x
+
+    def either(depth):
+        nonlocal pos
+        x = both(depth)
+        while pos < len(toks) and toks[pos] == b"OR":
+            pos += 1
+            x = ("or", x, both(depth))
+        return x
+
+    tree = either(0)
+    if pos != len(toks):
+        raise ValueError("unbalanced parentheses")
+    if expr_holds(tree, set()):
+        raise ValueError("the expression holds for a line with none of its words")
+    return tree, terms
+
+
+def expr_holds(tree, have) -> bool:
+    """The tree's value when exactly the terms in the set ``have`` hold."""
+    stack, todo = [], [tree]  # (iterative post-order: a left-deep chain may be long)
+    while todo:
+        n = todo.pop()
+        if isinstance(n, str):
+            if n == "not":
+                stack.append(not stack.pop())
+            else:
+                b, a = stack.pop(), stack.pop()
+                stack.append((a and b) if n == "and" else (a or b))
+        elif n[0] == "term":
+            stack.append(n[1] in have)
+        else:
+            todo.append(n[0])
+            todo.extend(reversed(n[1:]))
+    return stack[0]
+
+
+def _expr_lists(entries, postings, terms, delims, max_key, wildcard, glob, ignore_case, fuzzy):
+    return [_term_list(entries, postings, _qt_words(entries, t))
+            for t in query_terms(terms, wildcard, glob, ignore_case, delims, max_key, fuzzy=fuzzy)]
+
+
+def expr_search(entries, postings, expr: bytes, delims: bytes = DEFAULT_DELIMS,
+                max_key: int = 29, *, wildcard: bool = False, glob: bool = False,
+                ignore_case: bool = False, fuzzy: bool = False):
+    """One ``expr`` query over an index: ``(lines, counts, terms)`` (``EXPR_RULES``)."""
+    tree, terms = expr_parse(expr, delims, max_key, wildcard=wildcard, glob=glob, fuzzy=fuzzy)
+    lists = _expr_lists(entries, postings, terms, delims, max_key, wildcard, glob, ignore_case,
+                        fuzzy)
+    sets = [set(l) for l in lists]
+    lines = [line for line in sorted(set().union(*sets))
+             if expr_holds(tree, {t for t, s in enumerate(sets) if line in s})]
+    return lines, [len(l) for l in lists], terms
+
+
+def expr_walked(entries, postings, expr: bytes, delims: bytes = DEFAULT_DELIMS,
+                max_key: int = 29, *, wildcard: bool = False, glob: bool = False,
+                ignore_case: bool = False, fuzzy: bool = False) -> int:
+    """The list elements the device walks for one ``expr`` query: the summed list lengths of
+    the greedy covering set (``EXPR_RULES``, the walked set)."""
+    tree, terms = expr_parse(expr, delims, max_key, wildcard=wildcard, glob=glob, fuzzy=fuzzy)
+    lens = [len(l) for l in _expr_lists(entries, postings, terms, delims, max_key, wildcard, glob,
+                                        ignore_case, fuzzy)]
+    present = [t for t, n in enumerate(lens) if n]
+    true_sets = []  # the sets of present terms for which the expression holds
+    for bits in range(1, 1 << len(present)):
+        m = {present[i] for i in range(len(present)) if bits >> i & 1}
+        if expr_holds(tree, m):
+            true_sets.append(m)
+    if not true_sets:
+        return 0
+    keep = set(present)
+    for t in sorted(present, key=lambda t: (-lens[t], -t)):
+        rest = keep - {t}
+        if all(m & rest for m in true_sets):
+            keep = rest
+    return sum(lens[t] for t in keep)
+
+
 def _query_text(queries, exclude):
     """Each query's text in a result line: its terms joined by one space and, when it has
     exclusion terms, `` \t not: `` and those joined by one space."""

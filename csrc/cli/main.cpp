@@ -29,6 +29,8 @@
 //   --glob (with --search: * and ? anywhere in a word, "*ing", "h?mlet"; a superset of --wildcard)
 //   --fuzzy (with --search: a word that ends in ~1 or ~2 also finds the words within that many
 //            byte edits of it, "Hamlet~1", "quene~2")
+//   --regex (with --search: a word written /re/ is a regular expression over whole words,
+//            "/(king|queen)[!?]?/", "/[A-Z][A-Z]+/")
 //   --ignore-case (with --search: the ASCII letters of every word match either case)
 //   --show N (with --search: under each query's line, every returned line's first N bytes)
 //   --mark (with --show: the matching tokens of a shown line stand between >> and <<)
@@ -109,6 +111,7 @@ struct CliArgs {
   bool wildcard = false;  // --wildcard: a --search word that ends in * is a prefix term
   bool glob = false;      // --glob: * and ? anywhere in a --search word (pattern terms)
   bool fuzzy = false;     // --fuzzy: a --search word that ends in ~1 or ~2 is a fuzzy term
+  bool regex = false;     // --regex: a --search word written /re/ is a regex term
   bool ignore_case = false;  // --ignore-case: the batch's ASCII letters match either case
   u64 show = 0;       // --show N: the returned lines' first N bytes (0: line numbers only)
   bool mark = false;  // --mark: the shown lines' matching tokens between >> and <<
@@ -203,6 +206,15 @@ void help() {
       "                             its budget; another digit than 1 or 2 is refused, and so is a *\n"
       "                             or ? in the word under --wildcard or --glob.  A ~ anywhere else\n"
       "                             is literal.  With everything --glob goes with, and --glob)\n"
+      "  --regex                    (--search: a word written /re/ is a regular expression that a\n"
+      "                             whole word must match: literals, \\x escapes, ., [a-z], [^...],\n"
+      "                             ( ), |, *, + and ?, over bytes, at most 32 positions and 128\n"
+      "                             bytes: \"/(king|queen)[!?]?/\", \"/[A-Z][A-Z]+/\".  Delimiters and\n"
+      "                             blanks between the slashes belong to it; write \\/ for a slash.\n"
+      "                             It counts as one word whose lines are all of its words'; the\n"
+      "                             device scans the dictionary for them.  {m,n}, anchors, \\d and\n"
+      "                             \\w are refused.  With everything --glob goes with, --glob and\n"
+      "                             --fuzzy)\n"
       "  --show N                   (--search: under each query's result line, one line per\n"
       "                             returned line: two spaces, its number, \": \" and its first N\n"
       "                             bytes, 1 <= N <= 65536; the lines are gathered on the device.\n"
@@ -365,6 +377,8 @@ bool parse(int argc, char** argv, CliArgs* a) {
       a->glob = true;
     } else if (s == "--fuzzy") {
       a->fuzzy = true;
+    } else if (s == "--regex") {
+      a->regex = true;
     } else if (s == "--ignore-case") {
       a->ignore_case = true;
     } else if (s == "--show") {
@@ -455,6 +469,8 @@ bool parse(int argc, char** argv, CliArgs* a) {
     throw Error("--glob selects how --search reads * and ? in a word: give --search too");
   if (a->fuzzy && a->search_args.empty())
     throw Error("--fuzzy selects how --search reads a word that ends in ~1 or ~2: give --search too");
+  if (a->regex && a->search_args.empty())
+    throw Error("--regex selects how --search reads a word written /re/: give --search too");
   if (a->ignore_case && a->search_args.empty())
     throw Error("--ignore-case selects how --search compares letters: give --search too");
   if (a->show && a->search_args.empty())
@@ -498,6 +514,21 @@ bool parse(int argc, char** argv, CliArgs* a) {
     };
     for (size_t i = 0; i < arg.size(); ++i) {
       const char c = arg[i];
+      // (--regex: a word that begins with / runs to the next unescaped /, delimiters and blanks
+      // included, and its closing slash ends the word)
+      if (a->regex && c == '/' && cur.empty()) {
+        size_t j = i + 1;
+        while (j < arg.size() && arg[j] != '/') j += arg[j] == '\\' ? 2 : 1;
+        if (j >= arg.size())
+          throw Error("--search \"" + arg + "\": the regex term that starts at byte " +
+                      std::to_string(i) + " has no closing /");
+        if (j + 1 < arg.size() && !delim(arg[j + 1]))
+          throw Error("--search \"" + arg + "\": the closing / of the regex term " +
+                      arg.substr(i, j + 1 - i) + " must be followed by a delimiter or the end");
+        terms.push_back(arg.substr(i, j + 1 - i));
+        i = j;
+        continue;
+      }
       // (--fuzzy: so is a word's trailing ~d, the `~` and the digit)
       if (a->fuzzy && c == '~' && !cur.empty() && i + 1 < arg.size() && arg[i + 1] >= '0' &&
           arg[i + 1] <= '9' && (i + 2 == arg.size() || delim(arg[i + 2]))) {
@@ -523,7 +554,8 @@ bool parse(int argc, char** argv, CliArgs* a) {
       if (!a->not_args[i].empty())
         throw Error("--not does not combine with --match expr: write NOT in the expression (\"" +
                     arg + " AND NOT ...\")");
-      a->queries.push_back(make_search_expr(arg, a->cfg, a->wildcard, a->glob, a->fuzzy));
+      a->queries.push_back(make_search_expr(arg, a->cfg, a->wildcard, a->glob, a->fuzzy,
+                                            a->regex));
       continue;
     }
     const SearchMode mode = a->match == "any"      ? SearchMode::kAny
@@ -535,7 +567,7 @@ bool parse(int argc, char** argv, CliArgs* a) {
     // (a --not that holds no word excludes nothing)
     const std::vector<std::string> exclude = words(a->not_args[i]);
     a->queries.push_back(make_search_query(terms, mode, a->wildcard, a->within, exclude, a->glob,
-                                           a->fuzzy));
+                                           a->fuzzy, a->regex));
   }
   if (!a->queries.empty()) {
     check_search_queries(a->queries, a->cfg);
@@ -695,6 +727,7 @@ void json_search(JsonOut& j, const CliArgs& a) {
   if (a.queries.empty()) return;
   j.kv("search", "true");
   j.u("queries", a.queries.size());
+  j.kv("regex", a.regex ? "true" : "false");
   if (g_search) {
     j.u("hits", g_search->lines.size());
     u64 matches = 0;

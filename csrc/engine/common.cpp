@@ -13,6 +13,7 @@
 #include "locust/config.hpp"
 #include "locust/device/fuzzy.hpp"
 #include "locust/device/glob.hpp"
+#include "locust/device/regex.hpp"
 #include "locust/dstring.hpp"
 #include "locust/engine.hpp"
 
@@ -382,20 +383,244 @@ PackedKey search_term_key(const std::string& term, const JobConfig& cfg) {
   return k;
 }
 
+// ---- regex terms (engine.hpp): source -> the Glushkov position automaton ----
+namespace {
+
+// Recursive descent: alt := concat (`|` concat)*; concat := repeat*; repeat := atom [*+?];
+// atom := literal | `.` | class | `(` alt `)`.  Every atom but a group is a new position; a
+// fragment is the (first, last, nullable) of what it has read, and follow grows as fragments
+// are joined.  The recursion is one level per open parenthesis, at most kRegexMaxDepth.
+struct RegexCompiler {
+  const std::string& src;
+  bool fold;
+  std::vector<u32>& prog;
+  size_t at = 0;
+  u32 npos = 0;
+
+  struct Frag {
+    u32 first = 0, last = 0;
+    bool nullable = true;
+  };
+
+  [[noreturn]] void refuse(const std::string& why) const {
+    std::string shown;  // (a NUL would end the message, a newline break it)
+    for (const char ch : src) shown += ch == '\0' ? "\\0" : ch == '\n' ? "\\n" : std::string(1, ch);
+    throw Error("search: the regex /" + shown + "/ " + why);
+  }
+  bool done() const { return at == src.size(); }
+
+  // the byte behind a backslash (at: the backslash)
+  unsigned char escaped() {
+    if (at + 1 >= src.size()) refuse("ends in a backslash that escapes nothing");
+    const unsigned char c = (unsigned char)src[at + 1];
+    if ((c >= '0' && c <= '9') || (c >= 'a' && c <= 'z') || (c >= 'A' && c <= 'Z'))
+      refuse(std::string("holds \\") + (char)c +
+             ": a backslash before a letter or digit is reserved (there is no \\d or \\w)");
+    at += 2;
+    return c;
+  }
+
+  // a new position that accepts `set` (taken before a class's negation)
+  Frag position(bool (&set)[256], bool negate) {
+    if (npos == (u32)kRegexMaxPos)
+      refuse("has more than kRegexMaxPos = " + std::to_string(kRegexMaxPos) +
+             " positions (literals, dots and classes)");
+    if (fold)
+      for (int c = 'a'; c <= 'z'; ++c) set[c] = set[c ^ 0x20] = set[c] || set[c ^ 0x20];
+    const u32 bit = 1u << npos++;
+    for (int c = 1; c < 256; ++c)  // (B[0] stays 0: nothing accepts the padding)
+      if (set[c] != negate) prog[(size_t)(kRegexB + c)] |= bit;
+    Frag f;
+    f.first = f.last = bit;
+    f.nullable = false;
+    return f;
+  }
+
+  Frag parse_class() {  // (at: behind the `[`)
+    bool set[256] = {};
+    bool negate = false, any = false;
+    if (!done() && src[at] == '^') {
+      negate = true;
+      ++at;
+    }
+    for (;;) {
+      if (done()) refuse("holds an unterminated class: a [ without its ]");
+      if (src[at] == ']') {
+        ++at;
+        break;
+      }
+      unsigned char lo;
+      if (src[at] == '\\') {
+        lo = escaped();
+      } else {
+        lo = (unsigned char)src[at++];
+      }
+      unsigned char hi = lo;
+      // a range: a `-` that is not the class's last byte
+      if (at + 1 < src.size() && src[at] == '-' && src[at + 1] != ']') {
+        ++at;
+        if (src[at] == '\\') {
+          hi = escaped();
+        } else {
+          hi = (unsigned char)src[at++];
+        }
+        if (lo > hi)
+          refuse(std::string("holds the range ") + (char)lo + "-" + (char)hi +
+                 ", whose first byte lies behind its last (lo > hi)");
+      }
+      for (int c = lo; c <= hi; ++c) set[c] = true;
+      any = true;
+    }
+    if (!any) refuse("holds an empty class: [] and [^] have no member (escape a ] as \\])");
+    return position(set, negate);
+  }
+
+  Frag parse_atom(int depth) {
+    const char ch = src[at];
+    if (ch == '(') {
+      if (depth >= kRegexMaxDepth)
+        refuse("nests parentheses deeper than kRegexMaxDepth = " + std::to_string(kRegexMaxDepth));
+      ++at;
+      const Frag f = parse_alt(depth + 1);
+      if (done() || src[at] != ')') refuse("has unbalanced parentheses: a ( is never closed");
+      ++at;
+      return f;
+    }
+    bool set[256] = {};
+    if (ch == '[') {
+      ++at;
+      return parse_class();
+    }
+    if (ch == '.') {
+      ++at;
+      for (int c = 1; c < 256; ++c) set[c] = true;
+      return position(set, false);
+    }
+    if (ch == '{' || ch == '}' || ch == '^' || ch == '$')
+      refuse(std::string("holds an unescaped ") + ch +
+             " outside a class: counted repeats and anchors are not supported (a term is "
+             "anchored at both ends already); write \\" + ch + " for the byte");
+    if (ch == '\\') {
+      set[escaped()] = true;
+    } else {
+      set[(unsigned char)ch] = true;
+      ++at;
+    }
+    return position(set, false);
+  }
+
+  Frag parse_repeat(int depth) {
+    const char ch = src[at];
+    if (ch == '*' || ch == '+' || ch == '?')
+      refuse(std::string("holds a quantifier ") + ch + " with nothing to repeat");
+    Frag f = parse_atom(depth);
+    if (done()) return f;
+    const char qc = src[at];
+    if (qc != '*' && qc != '+' && qc != '?') return f;
+    ++at;
+    if (qc != '?')
+      for (u32 i = 0; i < npos; ++i)
+        if ((f.last >> i) & 1u) prog[(size_t)(kRegexFollow + (int)i)] |= f.first;
+    if (qc != '+') f.nullable = true;
+    if (!done() && (src[at] == '*' || src[at] == '+' || src[at] == '?'))
+      refuse(std::string("holds the quantifier ") + src[at] + " directly after the quantifier " +
+             qc + ": lazy and stacked quantifiers are not supported");
+    return f;
+  }
+
+  Frag parse_concat(int depth) {
+    Frag r;  // the empty string
+    while (!done() && src[at] != '|' && src[at] != ')') {
+      const Frag f = parse_repeat(depth);
+      for (u32 i = 0; i < npos; ++i)
+        if ((r.last >> i) & 1u) prog[(size_t)(kRegexFollow + (int)i)] |= f.first;
+      const Frag a = r;
+      r.first = a.first | (a.nullable ? f.first : 0u);
+      r.last = f.last | (f.nullable ? a.last : 0u);
+      r.nullable = a.nullable && f.nullable;
+    }
+    return r;
+  }
+
+  Frag parse_alt(int depth) {
+    Frag r = parse_concat(depth);
+    while (!done() && src[at] == '|') {
+      ++at;
+      const Frag f = parse_concat(depth);
+      r.first |= f.first;
+      r.last |= f.last;
+      r.nullable = r.nullable || f.nullable;
+    }
+    return r;
+  }
+};
+
+}  // namespace
+
+std::vector<u32> compile_regex(const std::string& source, bool ignore_case) {
+  std::vector<u32> prog((size_t)kRegexWords, 0u);
+  RegexCompiler c{source, ignore_case, prog};
+  if (source.empty()) c.refuse("has an empty source: give an expression between the slashes");
+  if (source.size() > kRegexMaxSource)
+    c.refuse("has a source of " + std::to_string(source.size()) +
+             " bytes; a source takes at most kRegexMaxSource = " +
+             std::to_string(kRegexMaxSource));
+  for (const char ch : source)
+    if (ch == '\0' || ch == '\n')
+      c.refuse("holds a NUL or a newline, which no word can hold");
+  const RegexCompiler::Frag f = c.parse_alt(0);
+  if (!c.done()) c.refuse("has unbalanced parentheses: a ) closes nothing");
+  prog[kRegexFirst] = f.first;
+  prog[kRegexLast] = f.last;
+  prog[kRegexNullable] = f.nullable ? 1u : 0u;
+  prog[kRegexNpos] = c.npos;
+  return prog;
+}
+
+bool SearchPattern::matches(const u64* key, bool fold) const {
+  if (regex) return regex_match(rx.data(), key);  // (the fold: compiled in)
+  if (budget)
+    return fuzzy_match(p.w[0], p.w[1], p.w[2], p.w[3], budget, key[0], key[1], key[2], key[3],
+                       fold);
+  return glob_match(p.w, meta, key, fold);
+}
+
 SearchQuery make_search_query(const std::vector<std::string>& terms, SearchMode mode,
                               bool wildcard, u64 within, const std::vector<std::string>& exclude,
-                              bool glob, bool fuzzy) {
+                              bool glob, bool fuzzy, bool regex) {
   SearchQuery q;
   q.terms = terms;
   q.terms.insert(q.terms.end(), exclude.begin(), exclude.end());
   q.excluded = (u32)exclude.size();
   q.mode = mode;
   q.within = within;
-  // the fuzzy reading comes first: a trailing ~d, and the word before it
-  std::vector<u8> fz(q.terms.size(), 0);
+  // the regex reading comes before every other: /source/, and nothing inside it is read again
+  std::vector<u8> fz(q.terms.size(), 0);  // (a regex term: 0xff, so the readings below skip it)
+  if (regex) {
+    std::vector<u8> rx(q.terms.size(), 0);
+    bool any_regex = false;
+    for (size_t t = 0; t < q.terms.size(); ++t) {
+      std::string& s = q.terms[t];
+      if (s.empty() || s[0] != '/') continue;
+      size_t slashes = 0;  // the backslashes before the last byte
+      while (s.size() >= 3 && slashes < s.size() - 2 && s[s.size() - 2 - slashes] == '\\') ++slashes;
+      LOCUST_CHECK_ARG(s.size() >= 3 && s.back() == '/' && slashes % 2 == 0,
+                       "search: the term " + s + " starts with / but is no regex term: a regex "
+                       "term is /source/, at least three bytes that end in a / that is not "
+                       "escaped");
+      s = s.substr(1, s.size() - 2);
+      (void)compile_regex(s, false);  // (throws with the cause)
+      rx[t] = 1;
+      fz[t] = 0xff;
+      any_regex = true;
+    }
+    if (any_regex) q.regex = std::move(rx);
+  }
+  // the fuzzy reading comes next: a trailing ~d, and the word before it
   if (fuzzy) {
     bool any_fuzzy = false;
     for (size_t t = 0; t < q.terms.size(); ++t) {
+      if (fz[t]) continue;  // a regex term
       std::string& s = q.terms[t];
       if (s.size() < 3 || s[s.size() - 2] != '~' || s.back() < '0' || s.back() > '9') continue;
       const u32 d = (u32)(s.back() - '0');
@@ -414,7 +639,11 @@ SearchQuery make_search_query(const std::vector<std::string>& terms, SearchMode 
       fz[t] = (u8)d;
       any_fuzzy = true;
     }
-    if (any_fuzzy) q.fuzzy = fz;
+    if (any_fuzzy) {
+      q.fuzzy = fz;
+      for (u8& d : q.fuzzy)
+        if (d == 0xff) d = 0;
+    }
   }
   if (glob) {
     bool any_prefix = false, any_pattern = false;
@@ -480,9 +709,9 @@ Truth truth_of_term(u32 t) {
 // at most kExprMaxDepth; a run of NOT is a loop.
 struct ExprParser {
   const std::vector<std::string>& tok;
-  bool wildcard, glob, fuzzy;
+  bool wildcard, glob, fuzzy, regex;
   SearchQuery* q;
-  std::vector<u8> prefix, pattern, fz;
+  std::vector<u8> prefix, pattern, fz, rx;
   size_t at = 0;
 
   static bool is_op(const std::string& s) { return s == "AND" || s == "OR" || s == "NOT"; }
@@ -493,11 +722,13 @@ struct ExprParser {
   }
 
   u32 term_number(const std::string& asked) {
-    const SearchQuery one = make_search_query({asked}, SearchMode::kAll, wildcard, 0, {}, glob, fuzzy);
+    const SearchQuery one =
+        make_search_query({asked}, SearchMode::kAll, wildcard, 0, {}, glob, fuzzy, regex);
     const u8 pre = one.is_prefix(0) ? 1 : 0, pat = one.is_pattern(0) ? 1 : 0;
-    const u8 bud = (u8)one.fuzzy_budget(0);
+    const u8 bud = (u8)one.fuzzy_budget(0), re = one.is_regex(0) ? 1 : 0;
     for (size_t t = 0; t < q->terms.size(); ++t)
-      if (q->terms[t] == one.terms[0] && prefix[t] == pre && pattern[t] == pat && fz[t] == bud)
+      if (q->terms[t] == one.terms[0] && prefix[t] == pre && pattern[t] == pat && fz[t] == bud &&
+          rx[t] == re)
         return (u32)t;
     LOCUST_CHECK_ARG(q->terms.size() < (size_t)kSearchMaxTerms,
                      "search: the expression has more than " + std::to_string(kSearchMaxTerms) +
@@ -506,6 +737,7 @@ struct ExprParser {
     prefix.push_back(pre);
     pattern.push_back(pat);
     fz.push_back(bud);
+    rx.push_back(re);
     return (u32)q->terms.size() - 1;
   }
 
@@ -569,17 +801,48 @@ struct ExprParser {
 }  // namespace
 
 SearchQuery make_search_expr(const std::string& expr, const JobConfig& cfg, bool wildcard,
-                             bool glob, bool fuzzy) {
+                             bool glob, bool fuzzy, bool regex) {
   std::vector<std::string> tok;
   std::string cur;
   const auto flush = [&] {
     if (!cur.empty()) tok.push_back(cur);
     cur.clear();
   };
-  for (const char ch : expr) {
+  // as asked: runs of blanks collapsed to one space, the ends trimmed (a regex token's bytes kept)
+  std::string asked;
+  bool gap = false;
+  const auto keep = [&](char ch) {
+    if (gap) asked.push_back(' ');
+    gap = false;
+    asked.push_back(ch);
+  };
+  for (size_t i = 0; i < expr.size(); ++i) {
+    const char ch = expr[i];
+    if (regex && ch == '/' && cur.empty()) {
+      // "regex terms": a token that begins with / runs to the next unescaped /, blanks and
+      // parentheses included
+      size_t j = i + 1;
+      while (j < expr.size() && expr[j] != '/') j += expr[j] == '\\' ? 2 : 1;
+      LOCUST_CHECK_ARG(j < expr.size(), "search: the regex term that starts at byte " +
+                                            std::to_string(i) + " of the expression has no "
+                                            "closing /");
+      LOCUST_CHECK_ARG(j + 1 == expr.size() || expr[j + 1] == ' ' || expr[j + 1] == '\t' ||
+                           expr[j + 1] == '(' || expr[j + 1] == ')',
+                       "search: the regex term " + expr.substr(i, j + 1 - i) + " is followed by "
+                       "the byte " + std::string(1, expr[j + 1 < expr.size() ? j + 1 : j]) +
+                           "; its closing / must be followed by a blank, a parenthesis or the end");
+      for (size_t k = i; k <= j; ++k) keep(expr[k]);
+      tok.push_back(expr.substr(i, j + 1 - i));
+      i = j;
+      continue;
+    }
     if (ch == ' ' || ch == '\t') {
       flush();
-    } else if (ch == '(' || ch == ')') {
+      gap = !asked.empty();
+      continue;
+    }
+    keep(ch);
+    if (ch == '(' || ch == ')') {
       flush();
       tok.emplace_back(1, ch);
     } else {
@@ -590,20 +853,8 @@ SearchQuery make_search_expr(const std::string& expr, const JobConfig& cfg, bool
   LOCUST_CHECK_ARG(!tok.empty(), "search: an empty expression");
   SearchQuery q;
   q.mode = SearchMode::kExpr;
-  // as asked: runs of blanks collapsed to one space, the ends trimmed
-  cur.clear();
-  bool gap = false;
-  for (const char ch : expr) {
-    if (ch == ' ' || ch == '\t') {
-      gap = !cur.empty();
-      continue;
-    }
-    if (gap) cur.push_back(' ');
-    gap = false;
-    cur.push_back(ch);
-  }
-  q.expr = cur;
-  ExprParser p{tok, wildcard, glob, fuzzy, &q, {}, {}, {}, 0};
+  q.expr = asked;
+  ExprParser p{tok, wildcard, glob, fuzzy, regex, &q, {}, {}, {}, {}, 0};
   q.truth = p.parse_or(0);
   LOCUST_CHECK_ARG(p.done(), p.tok[p.at] == ")"
                                  ? std::string("search: unbalanced parentheses: a ) closes nothing")
@@ -616,6 +867,8 @@ SearchQuery make_search_expr(const std::string& expr, const JobConfig& cfg, bool
     if (f) q.pattern = p.pattern;
   for (const u8 f : p.fz)
     if (f) q.fuzzy = p.fz;
+  for (const u8 f : p.rx)
+    if (f) q.regex = p.rx;
   check_search_queries({q}, cfg);
   return q;
 }
@@ -666,10 +919,22 @@ void check_search_queries(const std::vector<SearchQuery>& queries, const JobConf
                      "search: query " + std::to_string(i) + " has " +
                          std::to_string(q.fuzzy.size()) + " fuzzy budgets for " +
                          std::to_string(q.terms.size()) + " terms; give none or one per term");
+    LOCUST_CHECK_ARG(q.regex.empty() || q.regex.size() == q.terms.size(),
+                     "search: query " + std::to_string(i) + " has " +
+                         std::to_string(q.regex.size()) + " regex flags for " +
+                         std::to_string(q.terms.size()) + " terms; give none or one per term");
     for (size_t ti = 0; ti < q.terms.size(); ++ti) {
       const std::string& t = q.terms[ti];
       LOCUST_CHECK_ARG(!t.empty(), "search: query " + std::to_string(i) + " has an empty term");
       const bool pat = q.is_pattern(ti);
+      if (q.is_regex(ti)) {
+        LOCUST_CHECK_ARG(!q.is_prefix(ti) && !pat && !q.fuzzy_budget(ti),
+                         "search: term " + std::to_string(ti) + " of query " + std::to_string(i) +
+                             " is flagged as a regex term and as a prefix, pattern or fuzzy term; "
+                             "it is one or the other");
+        (void)compile_regex(t, false);  // (throws with the cause; a delimiter in it is legal)
+        continue;
+      }
       if (const u32 d = q.fuzzy_budget(ti)) {
         LOCUST_CHECK_ARG(!q.is_prefix(ti) && !pat,
                          "search: term " + std::to_string(ti) + " of query " + std::to_string(i) +
@@ -726,9 +991,21 @@ bool search_term_pattern(const SearchQuery& q, size_t t, const JobConfig& cfg, b
                          SearchPattern* out) {
   const bool pat = q.is_pattern(t);
   const u32 budget = q.fuzzy_budget(t);
-  if (!pat && !budget && !ignore_case) return false;
+  if (!pat && !budget && !ignore_case && !q.is_regex(t)) return false;
   if (!out) return true;
   const std::string& s = q.terms[t];
+  out->rx.clear();
+  out->src.clear();
+  out->budget = 0;
+  out->regex = false;
+  if (q.is_regex(t)) {  // the program for the batch's fold; the source is the term's identity
+    out->p = PackedKey{};
+    out->meta = 0;
+    out->regex = true;
+    out->rx = compile_regex(s, ignore_case);
+    out->src = s;
+    return true;
+  }
   char bytes[kKeyBytes];
   u32 meta = 0;
   int n = 0;
@@ -738,7 +1015,8 @@ bool search_term_pattern(const SearchQuery& q, size_t t, const JobConfig& cfg, b
       for (int i = 0; i < n; ++i)
         if (bytes[i] >= 'A' && bytes[i] <= 'Z') bytes[i] = (char)(bytes[i] | 0x20);
     pack_key(bytes, n, out->p.w);
-    out->meta = kFuzzyMeta | budget;
+    out->meta = kFuzzyMeta | budget;  // (the device's meta word; the host reads `budget`)
+    out->budget = budget;
     return true;
   }
   if (pat) {  // as asked: never cut (check_search_queries), star runs collapsed
@@ -770,7 +1048,14 @@ bool search_has_patterns(const std::vector<SearchQuery>& queries, bool ignore_ca
   for (const SearchQuery& q : queries)
     for (const u8 f : q.pattern)
       if (f) return true;
-  return search_has_fuzzy(queries);
+  return search_has_fuzzy(queries) || search_has_regex(queries);
+}
+
+bool search_has_regex(const std::vector<SearchQuery>& queries) {
+  for (const SearchQuery& q : queries)
+    for (const u8 f : q.regex)
+      if (f) return true;
+  return false;
 }
 
 bool search_has_fuzzy(const std::vector<SearchQuery>& queries) {
@@ -823,7 +1108,7 @@ struct TokenTerms {
 // Does the token match term j?
 bool token_matches(const PackedKey& tok, size_t j, const TokenTerms& tt) {
   if (!tt.pats.empty() && tt.is_pat[j])
-    return term_match(tt.pats[j].p.w, tt.pats[j].meta, tok.w, tt.fold);
+    return tt.pats[j].matches(tok.w, tt.fold);
   if (tt.masks.empty()) return key_compare(tok.w, tt.keys[j].w) == 0;
   bool same = true;
   for (int i = 0; i < kKeyWords; ++i) same &= (tok.w[i] & tt.masks[j].w[i]) == tt.keys[j].w[i];
@@ -1026,7 +1311,7 @@ SearchResult search_index_impl(const IndexResult& x, const TextInput* text,
         std::vector<List>& into = pos ? lists : not_lists;
         const List* same = nullptr;
         for (const List& o : into)
-          if (o.is_pat && o.pat.meta == sp.meta && key_compare(o.pat.p.w, sp.p.w) == 0) same = &o;
+          if (o.is_pat && o.pat.same(sp)) same = &o;
         if (same) {  // repeats an earlier term: the same count, no second list
           r.term_counts[qi * kSearchMaxTerms + t] = same->len;
           if (pos) list_of[t] = (int)(same - lists.data());
@@ -1035,7 +1320,7 @@ SearchResult search_index_impl(const IndexResult& x, const TextInput* text,
         std::vector<size_t> words;
         u64 len = 0;
         for (size_t i = 0; i < n; ++i)
-          if (term_match(sp.p.w, sp.meta, ent[i].key.w, ignore_case)) {
+          if (sp.matches(ent[i].key.w, ignore_case)) {
             words.push_back(i);
             len += ent[i].count;
           }
@@ -1327,7 +1612,9 @@ void format_search_output(const SearchResult& r, std::string* out, bool mark) {
     for (size_t t = 0; !expr && t < r.queries[q].terms.size(); ++t) {
       if (t == npos) out->append(" \t not:");
       out->push_back(' ');
+      if (r.queries[q].is_regex(t)) out->push_back('/');
       out->append(r.queries[q].terms[t]);
+      if (r.queries[q].is_regex(t)) out->push_back('/');
       if (r.queries[q].is_prefix(t)) out->push_back('*');
       if (const u32 d = r.queries[q].fuzzy_budget(t)) {
         out->push_back('~');

@@ -4,7 +4,10 @@
 // here instead of in every translation unit that includes the header.
 #include "pipeline.hpp"
 
+#include <map>
+
 #include "locust/device/fuzzy.hpp"
+#include "locust/device/regex.hpp"
 
 namespace locust {
 namespace detail {
@@ -561,6 +564,8 @@ DevicePipeline::~DevicePipeline() {
   if (d_smerged) (void)hipFree(d_smerged);
   if (d_spat) (void)hipFree(d_spat);
   pinned_free(h_spat);
+  if (d_srx) (void)hipFree(d_srx);
+  pinned_free(h_srx);
   if (d_sexpr) (void)hipFree(d_sexpr);
   pinned_free(h_sexpr);
   pinned_free(h_supload);
@@ -2148,6 +2153,22 @@ void DevicePipeline::ensure_search_patterns() {
       pinned_alloc(search_pattern_upload_bytes(), hipHostMallocDefault, "search patterns"));
 }
 
+void DevicePipeline::ensure_search_regex(u64 programs) {
+  if (programs <= srx_cap) return;
+  // first batch of this engine with a regex term, or one with more distinct programs than any
+  // before: the program table and its pinned half, grown to what the batch holds (engines that
+  // never see a regex keep their footprint; the batch before has drained)
+  if (d_srx) LOCUST_HIP_CHECK(hipFree(d_srx));
+  d_srx = nullptr;
+  pinned_free(h_srx);
+  h_srx = nullptr;
+  srx_cap = 0;
+  const u64 bytes = programs * kRegexWords * sizeof(u32);
+  LOCUST_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&d_srx), bytes));
+  h_srx = static_cast<u32*>(pinned_alloc(bytes, hipHostMallocDefault, "search regex programs"));
+  srx_cap = programs;
+}
+
 void DevicePipeline::ensure_search_expr() {
   if (d_sexpr) return;
   // first batch of this engine with an `expr` query (engines that never see one keep their
@@ -2323,6 +2344,22 @@ void DevicePipeline::search_stage(const std::vector<SearchQuery>& queries, u64 r
   // ... and one with a fuzzy term (engine.hpp "fuzzy terms") the kernels compiled with both
   // matchers (kernels.hpp "fuzzy.hip"): per batch, so the next one is routed afresh
   sbatch.fuzzy = patterns && search_has_fuzzy(queries);
+  // ... and one with a regex term (engine.hpp "regex terms") the kernels compiled with all three
+  // (kernels.hpp "regex.hip") and the batch's compiled programs: set below, per batch
+  sbatch.regex = nullptr;
+  std::map<std::string, u32> rx_index;  // a source's program in the batch's table
+  std::vector<u32> rx_progs;            // the distinct programs, in index order
+  // a regex term's slot: its program's index (identical sources share one), which is its meta
+  // word and, behind the tag, its key words
+  const auto regex_slot = [&](SearchPattern* sp) {
+    if (!sp->regex) return;
+    const auto it = rx_index.emplace(sp->src, (u32)rx_index.size());
+    if (it.second) rx_progs.insert(rx_progs.end(), sp->rx.begin(), sp->rx.end());
+    sp->meta = it.first->second;
+    sp->p = PackedKey{};
+    sp->p.w[0] = kRegexKeyTag;
+    sp->p.w[1] = it.first->second;
+  };
   // ... and one with an `expr` query (engine.hpp "boolean expressions") the plan and the hit
   // kernel of kernels.hpp "expr.hip"; a batch without one launches what it always launched
   bool exprs = false;
@@ -2369,8 +2406,14 @@ void DevicePipeline::search_stage(const std::vector<SearchQuery>& queries, u64 r
         // the slot's key words (q_meta's prefix bit stays clear: a prefix term under
         // ignore_case is the pattern p*)
         h_spat[q] |= (1u << t) | (ignore_case ? kSearchFold : 0u);
-        // (a fuzzy term: its word in the key words, kFuzzyMeta | its budget as the map)
-        if (sp.meta & kFuzzyMeta) h_spat[q] |= 1u << (kSearchFuzzyShift + (int)t);
+        // (a regex term: the tag and its program's index in the key words, the index as the map)
+        if (sp.regex) {
+          h_spat[q] |= 1u << (kSearchRegexShift + (int)t);
+          regex_slot(&sp);
+        } else if (sp.budget) {
+          // (a fuzzy term: its word in the key words, kFuzzyMeta | its budget as the map)
+          h_spat[q] |= 1u << (kSearchFuzzyShift + (int)t);
+        }
         h_spat[kSearchPatMeta + (u64)q * kSearchMaxTerms + t] = sp.meta;
         std::memcpy(keys + ((u64)q * kSearchMaxTerms + t) * kKeyWords, sp.p.w, sizeof(PackedKey));
         continue;
@@ -2392,9 +2435,7 @@ void DevicePipeline::search_stage(const std::vector<SearchQuery>& queries, u64 r
         if (!search_term_pattern(sq, t, cfg, ignore_case, &pats[t])) continue;
         size_t first = t;
         for (size_t i = 0; i < t && first == t; ++i)
-          if (((alias >> (24 + i)) & 1u) && pats[i].meta == pats[t].meta &&
-              key_compare(pats[i].p.w, pats[t].p.w) == 0)
-            first = i;
+          if (((alias >> (24 + i)) & 1u) && pats[i].same(pats[t])) first = i;
         alias |= (1u << (24 + (int)t)) | ((u32)first << (3 * (int)t));
       }
     }
@@ -2405,6 +2446,13 @@ void DevicePipeline::search_stage(const std::vector<SearchQuery>& queries, u64 r
   if (patterns)
     LOCUST_HIP_CHECK(hipMemcpyAsync(d_spat, h_spat, search_pattern_upload_bytes(),
                                     hipMemcpyHostToDevice, stream));
+  if (!rx_progs.empty()) {  // the programs in use, and nothing more
+    ensure_search_regex(rx_index.size());
+    std::memcpy(h_srx, rx_progs.data(), rx_progs.size() * sizeof(u32));
+    LOCUST_HIP_CHECK(hipMemcpyAsync(d_srx, h_srx, rx_progs.size() * sizeof(u32),
+                                    hipMemcpyHostToDevice, stream));
+    sbatch.regex = d_srx;
+  }
   if (exprs)
     LOCUST_HIP_CHECK(hipMemcpyAsync(d_sexpr, h_sexpr, search_expr_upload_bytes(Q),
                                     hipMemcpyHostToDevice, stream));

@@ -836,6 +836,12 @@ struct DevicePipeline {
   u32* d_spat = nullptr;
   u32* h_spat = nullptr;
   void ensure_search_patterns();
+  // the regex program table of a batch with a regex term (kernels.hpp "regex.hip"): made by the
+  // first such batch, grown to the distinct programs a batch holds
+  u32* d_srx = nullptr;
+  u32* h_srx = nullptr;
+  u64 srx_cap = 0;  // programs
+  void ensure_search_regex(u64 programs);
   // The expression arrays (kernels.hpp search_expr_*): device words and the pinned upload part,
   // made by the engine's first batch with an `expr` query.
   u32* d_sexpr = nullptr;

@@ -1,6 +1,7 @@
 // The dictionary scan of a batch that has a pattern term (kernels.hpp "search.hip": match,
 // scatter): the bodies of its two kernels, compiled per matcher level -- search.hip's kernels
-// with the pattern matcher (kMatch 1), fuzzy.hip's with the fuzzy matcher beside it (kMatch 2).
+// with the pattern matcher (kMatch 1), fuzzy.hip's with the fuzzy matcher beside it (kMatch 2),
+// regex.hip's with the regex matcher as well (kMatch 3).
 //
 // The walk the match and the scatter kernel share: grid x strides over the records in tiles
 // of kSearchBlock, one record per thread; grid y takes every gridDim.y-th query.  A tile's
@@ -11,6 +12,7 @@
 
 #include "locust/device/fuzzy.hpp"
 #include "locust/device/glob.hpp"
+#include "locust/device/regex.hpp"
 #include "locust/device/wave.hpp"
 #include "locust/kernels.hpp"
 
@@ -28,11 +30,15 @@ inline dim3 match_grid(u32 n, u32 queries) {
 
 // Does the key match pattern slot `slot` of a query whose flag word is fl?  (All but the key
 // wave-uniform.)  kMatch 2: a slot with its fuzzy bit holds a word and, in its meta word, a
-// budget.
+// budget.  kMatch 3: a slot with its regex bit holds, in its meta word, the index of its program
+// in the table rx.
 template <int kMatch>
 __device__ __forceinline__ bool slot_match(const u64* __restrict__ p, u32 fl, u32 slot, bool fold,
-                                           u32 meta, u64 k0, u64 k1, u64 k2, u64 k3) {
-  if (kMatch == 2 && ((fl >> (kSearchFuzzyShift + slot % kSearchMaxTerms)) & 1u))  // (uniform)
+                                           u32 meta, u64 k0, u64 k1, u64 k2, u64 k3,
+                                           const u32* __restrict__ rx = nullptr) {
+  if (kMatch == 3 && ((fl >> (kSearchRegexShift + slot % kSearchMaxTerms)) & 1u))  // (uniform)
+    return regex_match(rx + (u64)meta * kRegexWords, k0, k1, k2, k3);
+  if (kMatch >= 2 && ((fl >> (kSearchFuzzyShift + slot % kSearchMaxTerms)) & 1u))  // (uniform)
     return fuzzy_match(p[0], p[1], p[2], p[3], meta & kFuzzyBudgetMask, k0, k1, k2, k3, fold);
   return glob_match(p[0], p[1], p[2], p[3], meta, k0, k1, k2, k3, fold);
 }
@@ -43,7 +49,8 @@ template <int kMatch>
 __device__ __forceinline__ void search_match_body(const OutRecord* __restrict__ recs, u32 n,
                                                   const u64* __restrict__ keys,
                                                   const u32* __restrict__ pq, u32 Q,
-                                                  u32* __restrict__ pw) {
+                                                  u32* __restrict__ pw,
+                                                  const u32* __restrict__ rx = nullptr) {
   constexpr u32 kTerms = kSearchMaxTerms;
   const int lane = dev::lane_id();
   for (u32 base = blockIdx.x * kSearchBlock; base < n; base += gridDim.x * kSearchBlock) {
@@ -65,7 +72,7 @@ __device__ __forceinline__ void search_match_body(const OutRecord* __restrict__ 
         const u32 slot = q * kTerms + (u32)__ffs((int)pm) - 1u;
         const u64* p = keys + (u64)slot * kKeyWords;
         const bool m = live && slot_match<kMatch>(p, fl, slot, fold, pq[kSearchPatMeta + slot],
-                                                  k0, k1, k2, k3);
+                                                  k0, k1, k2, k3, rx);
         const u64 bm = dev::ballot(m);
         if (bm == 0) continue;  // (wave-uniform)
         const u32 sum = dev::wave_reduce_sum(m ? cnt : 0u);
@@ -91,7 +98,7 @@ __device__ __forceinline__ void search_scatter_body(
     const u32* __restrict__ postings, u32 first_line, const u64* __restrict__ pkeys,
     const u32* __restrict__ pq, u32 Q, const u32* __restrict__ x_len,
     const u64* __restrict__ x_start, u64 X, u64 cap, u32* __restrict__ cursor,
-    u64* __restrict__ keys) {
+    u64* __restrict__ keys, const u32* __restrict__ rx = nullptr) {
   constexpr u32 kTerms = kSearchMaxTerms;
   if (x_start[Q * kTerms] != X || X > cap) return;  // (uniform; as the gather kernel)
   const int lane = dev::lane_id();
@@ -116,7 +123,7 @@ __device__ __forceinline__ void search_scatter_body(
         if (x_len[slot] == 0u) continue;  // (uniform) not wide: nothing to merge
         const u64* p = pkeys + (u64)slot * kKeyWords;
         const bool m = live && slot_match<kMatch>(p, fl, slot, fold, pq[kSearchPatMeta + slot],
-                                                  k0, k1, k2, k3);
+                                                  k0, k1, k2, k3, rx);
         u64 bm = dev::ballot(m);
         if (bm == 0) continue;  // (wave-uniform)
         const u32 mine = m ? cnt : 0u;

@@ -1,7 +1,8 @@
 // The show stage's walk (kernels.hpp "show.hip": measure, write): the body of its kernels,
 // compiled per matcher level -- show.hip's kernels without a matcher (kMatch 0) and with the
-// pattern matcher (1), fuzzy.hip's with the fuzzy matcher beside it (2) -- and the one
-// argument they take.
+// pattern matcher (1), fuzzy.hip's with the fuzzy matcher beside it (2), regex.hip's with the
+// regex matcher as well (3; they take the program table beside it) -- and the one argument they
+// take.
 #pragma once
 
 #include "locust/device/termmask.hpp"
@@ -41,9 +42,12 @@ struct ShowJob {
 // fuzzy.hip's siblings of the show kernels (kernels.hpp "fuzzy.hip"): the measure or the write
 // walk of job j over `blocks` workgroups, for a batch that has a fuzzy term.
 void launch_fuzzy_show(const ShowJob& j, u32 blocks, bool write, hipStream_t s);
+// regex.hip's (kernels.hpp "regex.hip"), for a batch that has a regex term; rx: its program table.
+void launch_regex_show(const ShowJob& j, const u32* rx, u32 blocks, bool write, hipStream_t s);
 
 template <int kMatch, bool kWrite>
-__device__ __forceinline__ void show_body(unsigned char* row, u64* qk, u32* qm, const ShowJob& j) {
+__device__ __forceinline__ void show_body(unsigned char* row, u64* qk, u32* qm, const ShowJob& j,
+                                          const u32* __restrict__ rx = nullptr) {
   constexpr int kTerms = (int)kSearchMaxTerms;
   // row, qk, qm: this wave's LDS -- the line step, the query's term keys and (kMatch) its
   // pattern terms' metacharacter maps
@@ -78,11 +82,12 @@ __device__ __forceinline__ void show_body(unsigned char* row, u64* qk, u32* qm, 
   }
   int max_key_len = j.max_key_len;
   u32 first_line = j.first_line;
-  if (kMatch == 2) {  // (two matchers in the term loop: more room still)
+  if (kMatch >= 2) {  // (two matchers in the term loop: more room still)
     text = in_vgprs(text);
     max_key_len = value_in_vgprs(max_key_len);
     first_line = value_in_vgprs(first_line);
   }
+  if (kMatch == 3) rx = in_vgprs(rx);  // (three: the program table leaves the scalar file, too)
   const DelimMask& dm = j.dm;
   const int lane = dev::lane_id();
   const u32 bytes = (u32)j.bytes;  // (a window holds < 2^32 bytes: the launch's check)
@@ -90,12 +95,12 @@ __device__ __forceinline__ void show_body(unsigned char* row, u64* qk, u32* qm, 
   const u32 num_nl = (u32)j.lctr->num_newlines;
   const u64 E = j.E;
   // (the fuzzy siblings park N and the emit cap, too)
-  const u32 Q = j.Q, group = j.group, N = parked<kMatch == 2>(j.show);
+  const u32 Q = j.Q, group = j.group, N = parked<kMatch >= 2>(j.show);
   const u32 wave = blockIdx.x * kShowWaves + dev::wave_id();
   // a round of all waves: at most kShowMaxBlocks * kShowWaves * 64 = 2^19 entries
   const u32 stride = gridDim.x * kShowWaves * group;
   const u64 below = lane ? (~0ull >> (64 - lane)) : 0ull;  // the lanes below this one
-  const u32 EM = parked<kMatch == 2>((u32)j.emits_per_line);
+  const u32 EM = parked<kMatch >= 2>((u32)j.emits_per_line);
   for (u64 g0 = (u64)wave * group; g0 < E; g0 += stride) {  // (wave-uniform)
     const u32 cnt = (u32)(g0 + group < E ? group : E - g0);
     // lane i: entry i -- its line, and its query: offsets[q] <= e < offsets[q + 1]
@@ -129,8 +134,9 @@ __device__ __forceinline__ void show_body(unsigned char* row, u64* qk, u32* qm, 
       const u32 pt = kMatch ? pq[q] : 0u;  // bit j: term j is a pattern term | kSearchFold
       if (q != q_loaded) {  // (wave-uniform) neighbours mostly share their query
         __builtin_amdgcn_wave_barrier();  // the previous entry's key reads are done
-        if (lane < kTerms * kKeyWords) qk[lane] = keys[(u64)q * kTerms * kKeyWords + lane];
-        if (kMatch && lane < kTerms) qm[lane] = pq[kSearchPatMeta + (u64)q * kTerms + lane];
+        const int ql = lane_here<kMatch == 3>(lane);
+        if (ql < kTerms * kKeyWords) qk[ql] = keys[(u64)q * kTerms * kKeyWords + ql];
+        if (kMatch && ql < kTerms) qm[ql] = pq[kSearchPatMeta + (u64)q * kTerms + ql];
         __builtin_amdgcn_wave_barrier();
         q_loaded = q;
       }
@@ -155,14 +161,15 @@ __device__ __forceinline__ void show_body(unsigned char* row, u64* qk, u32* qm, 
       for (u32 pos = start; pos < end; pos += 64u) {
         const u32 left = end - pos;  // (>= 1)
         const unsigned c = (u32)lane < left ? (unsigned char)text[(u64)pos + lane] : 0u;
+        const int sl = lane_here<kMatch == 3>(lane);  // (a step's own compares with 32)
         const unsigned c2 =
-            (lane < 32 && 64u + (u32)lane < left) ? (unsigned char)text[(u64)pos + 64 + lane] : 0u;
+            (sl < 32 && 64u + (u32)lane < left) ? (unsigned char)text[(u64)pos + 64 + lane] : 0u;
         const u32 off = pos - start + (u32)lane;
         // (below t_len every byte is the line's: t_len <= its length, which ends at a NUL)
         if (kWrite && off < tl) out[t_at + off] = (char)c;
         __builtin_amdgcn_wave_barrier();  // the previous step's key reads are done
         row[lane] = (unsigned char)c;
-        if (lane < 32) row[64 + lane] = (unsigned char)c2;
+        if (sl < 32) row[64 + lane] = (unsigned char)c2;
         __builtin_amdgcn_wave_barrier();
         // dev::step_starts, with the token bytes kept: they give the tokens' ends
         const u64 z = dev::ballot(c == 0u);
@@ -181,7 +188,7 @@ __device__ __forceinline__ void show_body(unsigned char* row, u64* qk, u32* qm, 
         const u32 ord = seen + (u32)__popcll(starts & below);
         const bool emit = ((starts >> lane) & 1ull) && ord < EM;
         u32 eq = 0;  // bit t: this lane's token matches term t
-        if (emit) eq = token_term_mask<kMatch>(row, lane, dm, max_key_len, qk, m, pre, pt, qm);
+        if (emit) eq = token_term_mask<kMatch>(row, lane, dm, max_key_len, qk, m, pre, pt, qm, rx);
         const u64 mm = dev::ballot(eq != 0u);
         if (mm) {  // (wave-uniform)
           // the token's end: the first byte at or behind its start that is no token byte
@@ -213,8 +220,8 @@ __device__ __forceinline__ void show_body(unsigned char* row, u64* qk, u32* qm, 
         // needs byte N to tell a cut line, write the bytes below t_len
         if (left <= 64u) break;  // the line ends with the step
         const u32 walked = pos - start + 64u;
-        if (seen >= unparked<kMatch == 2>(EM) && !open &&
-            (kWrite ? walked >= tl : walked > unparked<kMatch == 2>(N))) {
+        if (seen >= unparked<kMatch >= 2>(EM) && !open &&
+            (kWrite ? walked >= tl : walked > unparked<kMatch >= 2>(N))) {
           len = walked;  // (N < walked < the line's length: the line is cut)
           break;
         }
@@ -230,14 +237,14 @@ __device__ __forceinline__ void show_body(unsigned char* row, u64* qk, u32* qm, 
       }
     }
     if (kWrite) {
-      if (bad && lane == 0) atomicAdd(&ctr->mismatch, bad);
+      if (bad && lane_here<kMatch == 3>(lane) == 0) atomicAdd(&ctr->mismatch, bad);
     } else {
       if ((u32)lane < cnt) {
         n_spans[g0 + lane] = my_spans;
         t_len[g0 + lane] = my_len;
       }
       const u64 cm = dev::ballot(my_cut);
-      if (cm && lane == 0) atomicAdd(&ctr->cut, (u32)__popcll(cm));
+      if (cm && lane_here<kMatch == 3>(lane) == 0) atomicAdd(&ctr->cut, (u32)__popcll(cm));
     }
   }
 }

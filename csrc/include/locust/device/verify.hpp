@@ -1,8 +1,9 @@
 // The verify stage of a search batch (kernels.hpp "search.hip": phrase, near): the bodies of the
 // two kernels that walk a candidate line against its query's terms, compiled per matcher level
 // -- search.hip's kernels without a matcher (kMatch 0) and with the pattern matcher (1),
-// fuzzy.hip's with the fuzzy matcher beside it (2) -- how a converged wave commits its hits, and how the hit kernels (search.hip, expr.hip) read a
-// term's list.
+// fuzzy.hip's with the fuzzy matcher beside it (2), regex.hip's with the regex matcher as well
+// (3) -- how a converged wave commits its hits, and how the hit kernels (search.hip, expr.hip)
+// read a term's list.
 #pragma once
 
 #include <algorithm>
@@ -80,7 +81,8 @@ __device__ __forceinline__ void search_phrase_body(
     const MapCounters* __restrict__ lctr, const DelimMask& dm, int emits_per_line,
     int max_key_len, u32 group, const u32* __restrict__ q_meta, const u64* __restrict__ keys,
     u32 Q, const u64* __restrict__ cands, u64* __restrict__ pairs, u64 pair_cap,
-    u32* __restrict__ q_hits, SearchCounters* __restrict__ ctr) {
+    u32* __restrict__ q_hits, SearchCounters* __restrict__ ctr,
+    const u32* __restrict__ rx = nullptr) {
   constexpr int kTerms = (int)kSearchMaxTerms;
   // row, qk, qm: this wave's LDS -- the line step, the query's term keys and (kMatch) its
   // pattern terms' metacharacter maps; pq: the batch's pattern flags and maps (kMatch)
@@ -95,23 +97,35 @@ __device__ __forceinline__ void search_phrase_body(
     ctr = in_vgprs(ctr);
     lctr = in_vgprs(lctr);
   }
-  if (kMatch == 2) {  // (two matchers in the term loop: more room still)
+  if (kMatch >= 2) {  // (two matchers in the term loop: more room still)
     text = in_vgprs(text);
   }
+  if (kMatch == 3) rx = in_vgprs(rx);  // (three: the program table leaves the scalar file, too)
   const int lane = dev::lane_id();
   const u64 num_nl = lctr->num_newlines;
   const u64 num_lines = bytes ? num_nl + 1 : 0;
   const u64 C = ctr->cands <= pair_cap ? ctr->cands : 0;  // (an overflow: the host throws)
-  if (kMatch == 2) {  // (from here on only lanes compare with pair_cap; Q is read back)
+  if (kMatch >= 2) {  // (from here on only lanes compare with pair_cap; Q is read back)
     pair_cap = value_in_vgprs(pair_cap);
     Q = parked<true>(Q);
   }
   const u64 wave = (u64)blockIdx.x * kPhraseWaves + dev::wave_id();
   const u64 nwaves = (u64)gridDim.x * kPhraseWaves;
   const u64 below = lane ? (~0ull >> (64 - lane)) : 0ull;  // the lanes below this one
-  const u32 E = parked<kMatch == 2>((u32)emits_per_line);  // (the fuzzy siblings park the cap)
-  for (u64 g0 = wave * group; g0 < C; g0 += nwaves * group) {  // (wave-uniform)
-    const u32 cnt = (u32)(g0 + group < C ? group : C - g0);
+  const u32 E = parked<kMatch >= 2>((u32)emits_per_line);  // (the fuzzy siblings park the cap)
+  // Level 3 parks what only a round reads -- its stride, its end, its group size -- in vector
+  // registers and reads them back once per round (parked64 / unparked64, device/termmask.hpp);
+  // below level 3 these are the values themselves.  Only this body does: without it the level-3
+  // phrase kernel spills scalar registers, while the near body, whose per-term state lives in
+  // lanes, compiles without spills as it stands (profiles/regex/resources.txt).
+  const u64 stride_p = parked64<kMatch == 3>(nwaves * group), end_p = parked64<kMatch == 3>(C);
+  const u32 group_p = parked<kMatch == 3>(group);
+  if (kMatch == 3) max_key_len = value_in_vgprs(max_key_len);
+  for (u64 g0 = wave * group; g0 < unparked64<kMatch == 3>(end_p);
+       g0 += unparked64<kMatch == 3>(stride_p)) {  // (wave-uniform)
+    const u64 round_end = unparked64<kMatch == 3>(end_p);
+    const u32 round_group = unparked<kMatch == 3>(group_p);
+    const u32 cnt = (u32)(g0 + round_group < round_end ? round_group : round_end - g0);
     const u64 mine = (u32)lane < cnt ? cands[g0 + lane] : 0ull;  // lane i: candidate i
     bool hit = false;
     u32 q_loaded = ~0u;  // the query whose term keys the wave's LDS row holds
@@ -119,7 +133,7 @@ __device__ __forceinline__ void search_phrase_body(
       const u32 q = (u32)__shfl((int)(u32)(mine >> 32), (int)i, 64);
       const u64 line = (u32)__shfl((int)(u32)mine, (int)i, 64);
       // (wave-uniform; never: the hit kernel's words)
-      if (q >= unparked<kMatch == 2>(Q) || line >= num_lines) continue;
+      if (q >= unparked<kMatch >= 2>(Q) || line >= num_lines) continue;
       const u32 meta = q_meta[q];
       // the positive terms, which stand first: exclusion terms are no part of the match
       const u32 m = (meta & 0xffu) - (u32)__popc(meta >> kSearchExcludeShift);
@@ -128,8 +142,9 @@ __device__ __forceinline__ void search_phrase_body(
       const u32 pt = kMatch ? pq[q] : 0u;  // bit j: term j is a pattern term | kSearchFold
       if (q != q_loaded) {  // (wave-uniform) neighbours mostly share their query
         __builtin_amdgcn_wave_barrier();  // the previous candidate's key reads are done
-        if (lane < kTerms * kKeyWords) qk[lane] = keys[(u64)q * kTerms * kKeyWords + lane];
-        if (kMatch && lane < kTerms) qm[lane] = pq[kSearchPatMeta + (u64)q * kTerms + lane];
+        const int ql = lane_here<kMatch == 3>(lane);
+        if (ql < kTerms * kKeyWords) qk[ql] = keys[(u64)q * kTerms * kKeyWords + ql];
+        if (kMatch && ql < kTerms) qm[ql] = pq[kSearchPatMeta + (u64)q * kTerms + ql];
         __builtin_amdgcn_wave_barrier();
         q_loaded = q;
       }
@@ -140,21 +155,22 @@ __device__ __forceinline__ void search_phrase_body(
       u32 state = 0;  // bit j: the last j + 1 tokens equal terms 0 .. j
       u64 carry = 0;
       bool match = false;
-      for (u64 pos = start; pos < end && seen < unparked<kMatch == 2>(E) && !match; pos += 64) {
+      for (u64 pos = start; pos < end && seen < unparked<kMatch >= 2>(E) && !match; pos += 64) {
         const u64 p = pos + lane;
         const unsigned c = p < end ? (unsigned char)text[p] : 0u;
         const u64 p2 = pos + 64 + lane;
-        const unsigned c2 = (lane < 32 && p2 < end) ? (unsigned char)text[p2] : 0u;
+        const int sl = lane_here<kMatch == 3>(lane);  // (a step's own compares with 32)
+        const unsigned c2 = (sl < 32 && p2 < end) ? (unsigned char)text[p2] : 0u;
         __builtin_amdgcn_wave_barrier();  // the previous step's key reads are done
         row[lane] = (unsigned char)c;
-        if (lane < 32) row[64 + lane] = (unsigned char)c2;
+        if (sl < 32) row[64 + lane] = (unsigned char)c2;
         __builtin_amdgcn_wave_barrier();
         bool last;
         const u64 starts = dev::step_starts(c, dm, &carry, &last);
         const u32 ord = seen + (u32)__popcll(starts & below);
         const bool emit = ((starts >> lane) & 1ull) && ord < E;
         u32 eq = 0;  // bit j: this lane's token equals term j
-        if (emit) eq = token_term_mask<kMatch>(row, lane, dm, max_key_len, qk, m, pre, pt, qm);
+        if (emit) eq = token_term_mask<kMatch>(row, lane, dm, max_key_len, qk, m, pre, pt, qm, rx);
         // the automaton over the step's emitted tokens in order (all wave-uniform)
         u64 em = dev::ballot(emit);
         if (dev::ballot(eq != 0u) == 0) {
@@ -176,7 +192,7 @@ __device__ __forceinline__ void search_phrase_body(
       }
       if ((u32)lane == i) hit = match;
     }
-    if (lane == 0) atomicAdd(&ctr->verified, cnt);
+    if (lane_here<kMatch == 3>(lane) == 0) atomicAdd(&ctr->verified, cnt);
     commit_hits(hit, (u32)(mine >> 32), (u32)mine, pairs, pair_cap, q_hits, ctr);
   }
 }
@@ -199,7 +215,8 @@ __device__ __forceinline__ void search_near_body(
     const MapCounters* __restrict__ lctr, const DelimMask& dm, int emits_per_line,
     int max_key_len, u32 group, const u32* __restrict__ q_meta, const u64* __restrict__ keys,
     u32 Q, const u64* __restrict__ cands, u64* __restrict__ pairs, u64 pair_cap,
-    u32* __restrict__ q_hits, SearchCounters* __restrict__ ctr) {
+    u32* __restrict__ q_hits, SearchCounters* __restrict__ ctr,
+    const u32* __restrict__ rx = nullptr) {
   constexpr int kTerms = (int)kSearchMaxTerms;
   // row, qk, qm: this wave's LDS -- the line step, the query's term keys and (kMatch) its
   // pattern terms' metacharacter maps; pq: the batch's pattern flags and maps (kMatch)
@@ -214,18 +231,19 @@ __device__ __forceinline__ void search_near_body(
     ctr = in_vgprs(ctr);
     lctr = in_vgprs(lctr);
   }
-  if (kMatch == 2) {  // (two matchers in the term loop: more room still)
+  if (kMatch >= 2) {  // (two matchers in the term loop: more room still)
     text = in_vgprs(text);
   }
+  if (kMatch == 3) rx = in_vgprs(rx);  // (three: the program table leaves the scalar file, too)
   const int lane = dev::lane_id();
   const u64 num_nl = lctr->num_newlines;  // (bytes > 0, the launch's check: num_nl + 1 lines)
   const u32 C = ctr->ncands <= pair_cap ? ctr->ncands : 0u;  // (an overflow: the host throws)
-  if (kMatch == 2) pair_cap = value_in_vgprs(pair_cap);  // (from here on only lanes read it)
+  if (kMatch >= 2) pair_cap = value_in_vgprs(pair_cap);  // (from here on only lanes read it)
   const u32 wave = blockIdx.x * kPhraseWaves + dev::wave_id();
   // a round of all waves: at most kPhraseMaxBlocks * kPhraseWaves * 64 = 2^19 candidates
   const u32 stride = gridDim.x * kPhraseWaves * group;
   const u64 below = lane ? (~0ull >> (64 - lane)) : 0ull;  // the lanes below this one
-  const u32 E = parked<kMatch == 2>((u32)emits_per_line);  // (the fuzzy siblings park the cap)
+  const u32 E = parked<kMatch >= 2>((u32)emits_per_line);  // (the fuzzy siblings park the cap)
   for (u64 g0 = (u64)wave * group; g0 < C; g0 += stride) {  // (wave-uniform)
     const u32 cnt = (u32)(g0 + group < C ? group : C - g0);
     // lane i: candidate i (g0 + lane < C <= pair_cap: inside cands)
@@ -246,8 +264,9 @@ __device__ __forceinline__ void search_near_body(
       const u32 W = reinterpret_cast<const u32*>(keys + (u64)Q * kTerms * kKeyWords)[q];
       if (q != q_loaded) {  // (wave-uniform) neighbours mostly share their query
         __builtin_amdgcn_wave_barrier();  // the previous candidate's key reads are done
-        if (lane < kTerms * kKeyWords) qk[lane] = keys[(u64)q * kTerms * kKeyWords + lane];
-        if (kMatch && lane < kTerms) qm[lane] = pq[kSearchPatMeta + (u64)q * kTerms + lane];
+        const int ql = lane_here<kMatch == 3>(lane);
+        if (ql < kTerms * kKeyWords) qk[ql] = keys[(u64)q * kTerms * kKeyWords + ql];
+        if (kMatch && ql < kTerms) qm[ql] = pq[kSearchPatMeta + (u64)q * kTerms + ql];
         __builtin_amdgcn_wave_barrier();
         q_loaded = q;
       }
@@ -260,21 +279,22 @@ __device__ __forceinline__ void search_near_body(
       u32 lastv = 0;
       u64 carry = 0;
       bool match = false;
-      for (u64 pos = start; pos < end && seen < unparked<kMatch == 2>(E) && !match; pos += 64) {
+      for (u64 pos = start; pos < end && seen < unparked<kMatch >= 2>(E) && !match; pos += 64) {
         const u64 p = pos + lane;
         const unsigned c = p < end ? (unsigned char)text[p] : 0u;
         const u64 p2 = pos + 64 + lane;
-        const unsigned c2 = (lane < 32 && p2 < end) ? (unsigned char)text[p2] : 0u;
+        const int sl = lane_here<kMatch == 3>(lane);  // (a step's own compares with 32)
+        const unsigned c2 = (sl < 32 && p2 < end) ? (unsigned char)text[p2] : 0u;
         __builtin_amdgcn_wave_barrier();  // the previous step's key reads are done
         row[lane] = (unsigned char)c;
-        if (lane < 32) row[64 + lane] = (unsigned char)c2;
+        if (sl < 32) row[64 + lane] = (unsigned char)c2;
         __builtin_amdgcn_wave_barrier();
         bool last;
         const u64 starts = dev::step_starts(c, dm, &carry, &last);
         const u32 ord = seen + (u32)__popcll(starts & below);
         const bool emit = ((starts >> lane) & 1ull) && ord < E;
         u32 eq = 0;  // bit j: this lane's token matches term j
-        if (emit) eq = token_term_mask<kMatch>(row, lane, dm, max_key_len, qk, m, pre, pt, qm);
+        if (emit) eq = token_term_mask<kMatch>(row, lane, dm, max_key_len, qk, m, pre, pt, qm, rx);
         // the step's matching tokens in order (all wave-uniform)
         u64 mm = dev::ballot(eq != 0u);
         while (mm) {
@@ -301,7 +321,7 @@ __device__ __forceinline__ void search_near_body(
       }
       if ((u32)lane == i) hit = match;
     }
-    if (lane == 0) atomicAdd(&ctr->nverified, cnt);
+    if (lane_here<kMatch == 3>(lane) == 0) atomicAdd(&ctr->nverified, cnt);
     commit_hits(hit, (u32)(mine >> 32), (u32)mine, pairs, pair_cap, q_hits, ctr);
   }
 }

@@ -566,6 +566,61 @@ void format_index_output(const IndexResult& r, std::string* out);
 // The device finds a fuzzy term's words by the pattern terms' scan of the dictionary, and a
 // batch that holds one runs kernels compiled with both matchers (kernels.hpp "fuzzy.hip").
 //
+// ---- regex terms: `/\[?Hamlet[!?\]]?/`, `/(king|queen)[!?]?/` ----
+// A term may be a regex term (SearchQuery::regex[t] != 0, terms[t] holding the source without
+// the slashes).  make_search_query's and make_search_expr's `regex` makes them, and only it:
+// without it `/x/` is the literal word it has always been.
+//   Reading.  With `regex`, a term that starts with `/` is a regex term.  It must be at least
+//     three bytes long and end in a `/` that is not escaped; its source is what stands between
+//     the slashes, and `\/` in the source is a literal slash.  A term that starts with `/` and
+//     is not of that shape (`/`, `//`, `/ab`) is refused.  This reading comes before the fuzzy,
+//     wildcard and glob readings, and nothing inside the slashes is read by them.  `regex`
+//     implies none of the other switches and combines with all of them, ignore_case included.
+//   Syntax.  Bytes, not characters: no UTF-8 awareness.  A literal byte.  `\` followed by a byte
+//     that is no ASCII letter or digit: that byte, literally; `\` followed by a letter or digit
+//     is refused (reserved: there is no `\d` or `\w`).  `.`: any one byte.  `[...]` and `[^...]`:
+//     a class whose members are single bytes or ranges `a-z`; `\` escapes inside it and `]` must
+//     be escaped; `-` first or last is literal; `^` is special only as the first byte; a range
+//     with lo > hi, an empty class and an unterminated class are refused.  `( ... )` groups and
+//     `|` alternates; `*`, `+`, `?` repeat the atom before them.  An empty branch or group
+//     matches the empty string: `(a|)` and `()` are legal.  Refused, with an error that names the
+//     cause: the empty source; a quantifier with nothing to repeat or directly after another
+//     quantifier (`a**`, `a*?`, `(?`); an unescaped `{`, `}`, `^` or `$` outside a class;
+//     unbalanced parentheses; a NUL or a newline anywhere in the source; nesting deeper than
+//     kRegexMaxDepth = 32; a source longer than kRegexMaxSource = 128 bytes; more than
+//     kRegexMaxPos = 32 positions, a position being one literal, one `.` or one class.  A byte
+//     of the job's delimiter set in the source is legal (`.`, `(`, `)` and `-` are default
+//     delimiters and syntax here): a literal delimiter simply matches no key.  A regex is never
+//     cut to max_key_len.
+//   Words.  A regex term's words are the index keys whose whole key the expression matches --
+//     keys as the index holds them (cut to max_key_len, their length the bytes before the NUL
+//     padding), the match anchored at both ends.  `.` and a negated class never match the
+//     padding: `/ab./` does not match the key `ab`.  A long word cut to max_key_len matches as
+//     its merged key, as everywhere.
+//   ignore_case.  The fold is the batch's.  A position's byte set, taken before a class's
+//     negation, is closed under the ASCII letter case swap and then negated: `/[^a]/` matches
+//     neither `a` nor `A`.  Only A-Z and a-z fold.
+//   Everything else is a pattern term's rule with this matcher (device/regex.hpp: the one
+//     matcher both engines use, over the program compile_regex builds).  The list is the
+//     multiset union of the words' postings, the count the sum of their counts; without a word
+//     the term is absent; one word uses its list in place, two or more are merged and counted in
+//     `merged`.  In `all`, `any`, `expr`, exclusion and the candidate stage it is a word with
+//     that list; in `phrase` and `near` verification and in show spans a token matches when its
+//     cut key matches the regex under the batch's fold.  search_has_patterns is true for a batch
+//     that holds one (the 32 * emits_per_line * 8 score bound, the kRankMaxEmits / 8 refusal),
+//     and the `any`-bound overflow rule holds.
+//   Identity.  Two regex terms of a query are the same term when their source bytes are equal,
+//     byte for byte, also under ignore_case.  A regex term is never the same as a term of
+//     another kind, and takes no part in the nesting rule.
+//   term_counts keep their order, and format_search_output prints the term as asked, slashes
+//     included.
+//   `expr` mode.  With `regex`, a token of an expression that begins with `/` runs to the next
+//     unescaped `/`: blanks and parentheses inside belong to it.  The closing slash must be
+//     followed by a blank, a parenthesis or the end.
+// The device finds a regex term's words by the pattern terms' scan of the dictionary with the
+// compiled programs in a device table, and a batch that holds one runs kernels compiled with all
+// three matchers (kernels.hpp "regex.hip").
+//
 // ---- boolean expressions: `( to AND be ) OR ( Ham* AND NOT Hamlet )` ----
 // A fifth mode, `expr` (SearchMode::kExpr; make_search_expr makes the query), answers a Boolean
 // expression over up to kSearchMaxTerms terms.
@@ -658,6 +713,8 @@ constexpr u32 kRankScoreMax = 32u * (u32)kRankMaxEmits;  // 2^21
 constexpr u64 kSearchMaxWithin = 0xffffffffull;  // a `near` window: 1 <= W <= 2^32 - 1
 constexpr int kExprMaxDepth = 64;  // "boolean expressions": open parentheses around one operand
 constexpr int kExprTruthWords = 8;  // the 256-bit truth table of kSearchMaxTerms terms
+constexpr int kRegexMaxDepth = 32;     // "regex terms": open parentheses around one atom
+constexpr size_t kRegexMaxSource = 128;  // ... the bytes of a source
 enum class SearchMode { kAll, kAny, kPhrase, kNear, kExpr };
 struct SearchQuery {
   std::vector<std::string> terms;
@@ -668,12 +725,15 @@ struct SearchQuery {
   std::vector<u8> pattern;  // empty: no pattern term; else parallel to terms, != 0: a pattern term
   std::vector<u8> fuzzy;  // empty: no fuzzy term; else parallel to terms, 1 or 2: a fuzzy term's
                           // budget (terms[t]: its word, without the `~d`), 0: none
+  std::vector<u8> regex;  // empty: no regex term; else parallel to terms, != 0: a regex term
+                          // (terms[t]: its source, without the slashes)
   std::string expr;       // kExpr: the expression as asked, blanks collapsed ("boolean expressions")
   std::array<u32, kExprTruthWords> truth{};  // kExpr: bit m: the value when exactly mask m holds
   bool truth_at(u32 m) const { return (truth[(m >> 5) & 7u] >> (m & 31u)) & 1u; }
   bool is_prefix(size_t t) const { return t < prefix.size() && prefix[t] != 0; }
   u32 fuzzy_budget(size_t t) const { return t < fuzzy.size() ? fuzzy[t] : 0u; }
   bool is_pattern(size_t t) const { return t < pattern.size() && pattern[t] != 0; }
+  bool is_regex(size_t t) const { return t < regex.size() && regex[t] != 0; }
   // the positive terms: terms[0 .. positives())
   size_t positives() const { return excluded < terms.size() ? terms.size() - excluded : 0; }
 };
@@ -730,22 +790,46 @@ inline bool search_term_prefix(const SearchQuery& q, size_t t, const JobConfig& 
 // fuzzy: "fuzzy terms" above (a trailing `~1` or `~2` makes a fuzzy term, read before the
 // wildcard and glob reading; another digit, a word no longer than its budget and -- with
 // wildcard or glob -- a word that holds `*` or `?` are errors).
+// regex: "regex terms" above (a term that starts with `/` is `/source/`, read before every other
+// reading; a malformed term and a source compile_regex refuses are errors).
 SearchQuery make_search_query(const std::vector<std::string>& terms, SearchMode mode,
                               bool wildcard, u64 within = 0,
                               const std::vector<std::string>& exclude = {}, bool glob = false,
-                              bool fuzzy = false);
+                              bool fuzzy = false, bool regex = false);
 // The `expr` query of an expression ("boolean expressions" above): the parser, the terms'
 // identification and the truth table.  Every term is read by make_search_query's rules under
 // wildcard, glob and fuzzy, and validated for cfg (check_search_queries).  Throws with the cause
 // for every refusal listed there.
+// regex: a token that begins with `/` runs to the next unescaped `/` ("regex terms").
 SearchQuery make_search_expr(const std::string& expr, const JobConfig& cfg, bool wildcard = false,
-                             bool glob = false, bool fuzzy = false);
+                             bool glob = false, bool fuzzy = false, bool regex = false);
+// A regex term's compiled program ("regex terms"; the layout: device/regex.hpp, kRegexWords u32
+// words): the Glushkov position automaton of `source` -- first, last, nullable, follow[32] and
+// the byte table B[256] with the fold compiled in.  Throws with the cause for every refusal
+// listed there.
+std::vector<u32> compile_regex(const std::string& source, bool ignore_case);
 // A term as the pattern it is evaluated as: the packed bytes (kv.hpp) and the map of its
 // metacharacters (device/glob.hpp) -- a fuzzy term: its word's bytes and kFuzzyMeta | its
-// budget (device/fuzzy.hpp; term_match evaluates either kind).
+// budget as the device's meta word (device/fuzzy.hpp).
+// The host reads the kind from fields of its own, never from a bit of `meta`: a pattern of 31
+// bytes uses every bit of its map below bit 31, and a star behind 31 cut bytes would be bit 31
+// itself.  `budget` != 0: a fuzzy term, matched by fuzzy_match.  `regex`: a regex term -- no
+// bytes, meta 0, `rx` its compiled program (device/regex.hpp) and `src` its source, which is its
+// identity.
 struct SearchPattern {
   PackedKey p;
   u32 meta = 0;
+  u32 budget = 0;
+  bool regex = false;
+  std::vector<u32> rx;
+  std::string src;
+  // the same term, as the identity rules say
+  bool same(const SearchPattern& o) const {
+    return regex == o.regex && budget == o.budget && meta == o.meta &&
+           key_compare(p.w, o.p.w) == 0 && src == o.src;
+  }
+  // does the key (an index key, a token's cut key) match?
+  bool matches(const u64* key, bool fold) const;
 };
 // Is term t of q evaluated as a pattern term -- a pattern term, a fuzzy term, or any term under
 // ignore_case?  If so *out (when given) is its pattern: a pattern term's bytes as asked, a
@@ -759,6 +843,8 @@ bool search_term_pattern(const SearchQuery& q, size_t t, const JobConfig& cfg, b
 bool search_has_patterns(const std::vector<SearchQuery>& queries, bool ignore_case);
 // Does it hold a fuzzy term?
 bool search_has_fuzzy(const std::vector<SearchQuery>& queries);
+// Does it hold a regex term?
+bool search_has_regex(const std::vector<SearchQuery>& queries);
 // Throws unless every query has 1..kSearchMaxTerms valid terms for cfg's delimiter set, at
 // least one of them positive (and `prefix` empty or as long as `terms`), a `near` query a
 // window in [1, kSearchMaxWithin] and every other query none (within == 0).  An `expr` query:
@@ -805,7 +891,7 @@ void validate_search(const SearchResult& r);
 //   "print query: <terms joined by one space> \t hits: <h> \t lines: <l0> <l1> ...\n"
 // (an `expr` query: its expression, SearchQuery::expr, in place of the joined terms)
 // (a prefix term as it was asked: with its star; a pattern term as it was asked, too; a fuzzy
-// term with its `~d`;
+// term with its `~d`, a regex term between its slashes;
 // <terms> are the positive terms, and a query
 // with exclusion terms prints " \t not: <those joined by one space>" before " \t hits:")
 // ranked (hits: the matches; nothing after "top:" when nothing matched):

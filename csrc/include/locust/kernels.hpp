@@ -744,7 +744,8 @@ void launch_index(const IndexJob& job, IndexWorkspace& ws, SortPlan* h_plan, hip
 //            key, with the batch's fold; plain and prefix terms of such a batch match as ever.
 //            Every other batch runs the kernels it ran before, at their resources.  A batch
 //            that has a fuzzy term runs fuzzy.hip's match, scatter, phrase and near kernels:
-//            the same bodies once more, with the fuzzy matcher beside the pattern matcher
+//            the same bodies once more, with the fuzzy matcher beside the pattern matcher; one
+//            that has a regex term regex.hip's
 //   seal    one thread: the sort's length, capped by the workspace
 //   (the host reads the number of hits H: the sort takes its regime from it)
 //   order    radix_sort() of the pair words as one-word keys
@@ -818,8 +819,16 @@ constexpr u32 kSearchSlots = kSearchMaxQueries * kSearchMaxTerms;  // (query, te
 //   meta   kFuzzyMeta | d (device/fuzzy.hpp): the budget, and a bit no metacharacter map has,
 //          so a fuzzy slot never compares equal to a pattern slot in the lookup's identity rule
 // A batch with such a bit sets SearchBatch::fuzzy and runs fuzzy.hip's kernels.
+// A regex term (engine.hpp "regex terms") is a pattern slot as well, and besides
+//   flags  bit kSearchRegexShift + t: the slot stands for a compiled program
+//   meta   the program's index in the batch's program table (SearchBatch::regex)
+//   keys   kRegexKeyTag (device/regex.hpp), the index, 0, 0: equal for the identical sources of
+//          a batch, which share one program, and equal to no pattern's or fuzzy term's bytes --
+//          the tag's top byte is NUL -- in the lookup's identity rule
+// A batch with such a bit sets SearchBatch::regex and runs regex.hip's kernels.
 constexpr u32 kSearchFold = 1u << 8;
 constexpr int kSearchFuzzyShift = 16;
+constexpr int kSearchRegexShift = 24;
 constexpr u64 kSearchPatMeta = kSearchMaxQueries;
 constexpr u64 kSearchPatWords = kSearchPatMeta + kSearchSlots;
 constexpr u64 kSearchPatLen = kSearchPatWords + kSearchSlots;
@@ -874,6 +883,10 @@ struct SearchBatch {
   bool fuzzy = false;      // the batch has a fuzzy term (pat is set, too): the dictionary scan,
                            // the verify and the show kernels are fuzzy.hip's (the engine sets it
                            // per batch)
+  const u32* regex = nullptr;  // the batch has a regex term (pat is set, too): its program table,
+                           // [programs][kRegexWords] (device/regex.hpp), and the dictionary
+                           // scan, the verify and the show kernels are regex.hip's (the engine
+                           // sets it per batch; null in every other batch)
   u32* expr = nullptr;     // the expression arrays ("expr.hip") of a batch that has an `expr` query;
                            // null in every other batch (the engine sets it per batch), and then
                            // nothing of expr.hip runs
@@ -1018,7 +1031,8 @@ void launch_expr_hits(const SearchIndex& ix, const SearchBatch& b, u32 queries, 
 //            a determined place: no atomics, no compaction.  An entry whose spans do not number
 //            what measure counted adds to ShowCounters::mismatch (the host throws)
 // A batch that has a pattern term runs the siblings compiled with the matcher
-// (show_globmeasure_kernel, show_globwrite_kernel); one with a fuzzy term fuzzy.hip's.
+// (show_globmeasure_kernel, show_globwrite_kernel); one with a fuzzy term fuzzy.hip's, one
+// with a regex term regex.hip's.
 struct ShowCounters {  // zeroed per show batch
   u64 text;       // T: the payload's text bytes
   u64 spans;      // S: its span triples
@@ -1073,6 +1087,33 @@ void launch_fuzzy_phrase(const SearchIndex& ix, const SearchBatch& b, u32 querie
 void launch_fuzzy_near(const SearchIndex& ix, const SearchBatch& b, u32 queries, u64 bound,
                        const SearchHits& h, hipStream_t s);
 
+// ---------------- regex.hip ----------------
+// The kernels of a batch that has a regex term (engine.hpp "regex terms"; SearchBatch::regex):
+// the same bodies a third time, with the regex matcher (device/regex.hpp) beside the pattern and
+// the fuzzy matcher -- such a batch may hold pattern and fuzzy terms and the fold as well.  Every
+// kernel takes the batch's program table; a regex slot's meta word indexes it:
+//   match    regex_match_kernel: the dictionary scan, one key per lane; a regex slot's words are
+//            the keys its program accepts
+//   scatter  regex_scatter_kernel: the same walk and match over the wide slots
+//   phrase   regex_phrase_kernel, near: regex_near_kernel: one token per lane; a token matches a
+//            regex term when the program accepts its cut key
+//   show     regex_showmeasure_kernel, regex_showwrite_kernel: the same token rule
+// The programs are read from global memory: first, last, follow[] and the position count by
+// scalar loads (the program is wave-uniform), B[] through the vector cache, each lane by its own
+// byte.  Nothing is staged in LDS: a program is 1168 bytes that every wave of a launch reads
+// over and over, so it stays in the caches, while a staged copy would cost the scan a workgroup
+// barrier pair per (tile, slot) and the walks up to eight tables per wave.
+// A regex batch's launch functions call these in place of their own kernels (before the fuzzy
+// siblings), with the grids and arguments of the siblings they replace; every other batch
+// launches none of them.
+void launch_regex_match(const SearchIndex& ix, const SearchBatch& b, u32 queries, hipStream_t s);
+void launch_regex_scatter(const SearchIndex& ix, const SearchBatch& b, u32 queries, u64 x,
+                          const SearchHits& h, hipStream_t s);
+void launch_regex_phrase(const SearchIndex& ix, const SearchBatch& b, u32 queries, u64 bound,
+                         const SearchHits& h, hipStream_t s);
+void launch_regex_near(const SearchIndex& ix, const SearchBatch& b, u32 queries, u64 bound,
+                       const SearchHits& h, hipStream_t s);
+
 // ---- device self-test of the string library (tests only; StringTestOut in engine.hpp) ----
 void launch_string_selftest(const char* blob, const u32* off, u32 n, const char* delims,
                             const int* ints, StringTestOut* out, hipStream_t s);
@@ -1087,6 +1128,7 @@ void warm_module_dict();
 void warm_module_exchange();
 void warm_module_expr();  // (as search: the code object only, no buffers)
 void warm_module_fuzzy();  // (as search: the code object only, no buffers)
+void warm_module_regex();  // (as fuzzy)
 void warm_module_index();  // (as topk below: the code object only, no buffers)
 void warm_module_map();
 void warm_module_merge();
@@ -1109,6 +1151,7 @@ inline void warm_kernel_modules() {
   warm_module_exchange();
   warm_module_expr();
   warm_module_fuzzy();
+  warm_module_regex();
   warm_module_index();
   warm_module_map();
   warm_module_merge();

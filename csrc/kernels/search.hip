@@ -768,7 +768,9 @@ void launch_search_lookup(const SearchIndex& ix, const SearchBatch& b, u32 queri
   if (b.pat) {  // match: the pattern slots' words, lengths and cursors start from zero
     LOCUST_HIP_CHECK(hipMemsetAsync(b.pat + kSearchPatWords, 0,
                                     (kSearchPatEnd - kSearchPatWords) * sizeof(u32), s));
-    if (ix.n && b.fuzzy) {  // (a batch that has a fuzzy term: fuzzy.hip's scan)
+    if (ix.n && b.regex) {  // (a batch that has a regex term: regex.hip's scan)
+      launch_regex_match(ix, b, queries, s);
+    } else if (ix.n && b.fuzzy) {  // (a batch that has a fuzzy term: fuzzy.hip's scan)
       launch_fuzzy_match(ix, b, queries, s);
     } else if (ix.n) {
       search_match_kernel<<<match_grid(ix.n, queries), dim3(kSearchBlock), 0, s>>>(
@@ -803,7 +805,9 @@ void launch_search_expand(const SearchIndex& ix, const SearchBatch& b, u32 queri
   search_gather_kernel<<<dim3(gblocks), dim3(kSearchBlock), 0, s>>>(
       ix.postings, ix.first_line, b.x_start, b.t_val, slots, x, h.cap, h.pairs, b.ctr, b.pat);
   LOCUST_HIP_LAUNCH_CHECK();
-  if (b.pat && ix.n && b.fuzzy) {
+  if (b.pat && ix.n && b.regex) {
+    launch_regex_scatter(ix, b, queries, x, h, s);
+  } else if (b.pat && ix.n && b.fuzzy) {
     launch_fuzzy_scatter(ix, b, queries, x, h, s);
   } else if (b.pat && ix.n) {  // the wide pattern slots' part of the keys
     search_scatter_kernel<<<match_grid(ix.n, queries), dim3(kSearchBlock), 0, s>>>(
@@ -850,7 +854,9 @@ void launch_search_hits(const SearchIndex& ix, const SearchBatch& b, u32 queries
     const u32 group = (u32)std::min<u64>(div_up(bound, (u64)kPhraseMaxBlocks), 64);
     const u32 blocks = (u32)std::min<u64>(div_up(div_up(bound, (u64)group), (u64)kPhraseWaves),
                                           (u64)kPhraseMaxBlocks);
-    if (b.fuzzy)  // (a batch that has a fuzzy term: fuzzy.hip's sibling)
+    if (b.regex)  // (a batch that has a regex term: regex.hip's sibling)
+      launch_regex_phrase(ix, b, queries, bound, h, s);
+    else if (b.fuzzy)  // (a batch that has a fuzzy term: fuzzy.hip's sibling)
       launch_fuzzy_phrase(ix, b, queries, bound, h, s);
     else if (b.pat)  // (a batch that has a pattern term: the sibling with the matcher)
       search_globphrase_kernel<<<dim3(blocks), dim3(kPhraseBlock), 0, s>>>(
@@ -870,7 +876,9 @@ void launch_search_hits(const SearchIndex& ix, const SearchBatch& b, u32 queries
     const u32 group = (u32)std::min<u64>(div_up(bound, (u64)kPhraseMaxBlocks), 64);
     const u32 blocks = (u32)std::min<u64>(div_up(div_up(bound, (u64)group), (u64)kPhraseWaves),
                                           (u64)kPhraseMaxBlocks);
-    if (b.fuzzy)
+    if (b.regex)
+      launch_regex_near(ix, b, queries, bound, h, s);
+    else if (b.fuzzy)
       launch_fuzzy_near(ix, b, queries, bound, h, s);
     else if (b.pat)
       search_globnear_kernel<<<dim3(blocks), dim3(kPhraseBlock), 0, s>>>(

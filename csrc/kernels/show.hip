@@ -17,7 +17,7 @@
 //    lies and its length so far -- and the step that holds its end (a ballot's trailing ones)
 //    or the line's end writes its length.  No per-lane byte loop, no atomics on the output.
 // A batch with a pattern term runs the siblings compiled with the matcher; one with a fuzzy term
-// runs fuzzy.hip's (launch_fuzzy_show).
+// runs fuzzy.hip's (launch_fuzzy_show), one with a regex term regex.hip's (launch_regex_show).
 #include <algorithm>
 
 #include "locust/device/showwalk.hpp"
@@ -220,7 +220,9 @@ void launch_show_measure(const SearchIndex& ix, const SearchBatch& b, u32 querie
   u32 blocks = 0;
   const ShowJob j = make_job(ix, b, queries, lines, offsets, entries, show, sb, &blocks);
   LOCUST_HIP_CHECK(hipMemsetAsync(sb.ctr, 0, sizeof(ShowCounters), s));
-  if (b.fuzzy)  // (a batch that has a fuzzy term: fuzzy.hip's sibling)
+  if (b.regex)  // (a batch that has a regex term: regex.hip's sibling)
+    launch_regex_show(j, b.regex, blocks, false, s);
+  else if (b.fuzzy)  // (a batch that has a fuzzy term: fuzzy.hip's sibling)
     launch_fuzzy_show(j, blocks, false, s);
   else if (b.pat)  // (a batch that has a pattern term: the sibling with the matcher)
     show_globmeasure_kernel<<<dim3(blocks), dim3(kShowBlock), 0, s>>>(j);
@@ -238,7 +240,9 @@ void launch_show_write(const SearchIndex& ix, const SearchBatch& b, u32 queries,
   // (N = 1: write takes every length from text_off)
   const ShowJob j = make_job(ix, b, queries, lines, offsets, entries, 1, sb, &blocks);
   LOCUST_CHECK_ARG(sb.text && sb.spans, "show: the payload buffers are missing");
-  if (b.fuzzy)
+  if (b.regex)
+    launch_regex_show(j, b.regex, blocks, true, s);
+  else if (b.fuzzy)
     launch_fuzzy_show(j, blocks, true, s);
   else if (b.pat)
     show_globwrite_kernel<<<dim3(blocks), dim3(kShowBlock), 0, s>>>(j);

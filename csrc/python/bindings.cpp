@@ -16,6 +16,7 @@
 #include "locust/dict_stage.hpp"
 #include "locust/dist.hpp"
 #include "locust/dstring.hpp"
+#include "locust/device/regex.hpp"
 #include "locust/engine.hpp"
 #include "locust/exch_stage.hpp"
 #include "locust/gen.hpp"
@@ -102,7 +103,7 @@ struct PyIndexResult {
                         const std::vector<int>& any, const py::object& rank, bool wildcard,
                         const std::vector<u64>& within,
                         const std::vector<std::vector<std::string>>& exclude, bool glob,
-                        bool ignore_case, const py::object& show, bool fuzzy) const;
+                        bool ignore_case, const py::object& show, bool fuzzy, bool regex) const;
   py::list entries() const { return PyResult{x.words}.entries(); }
   py::list postings() const {
     py::list out;
@@ -246,7 +247,7 @@ std::vector<SearchQuery> to_queries(const JobConfig& cfg,
                                     const std::vector<int>& any, bool wildcard,
                                     const std::vector<u64>& within,
                                     const std::vector<std::vector<std::string>>& exclude,
-                                    bool glob, bool fuzzy = false) {
+                                    bool glob, bool fuzzy = false, bool regex = false) {
   LOCUST_CHECK_ARG(any.size() == queries.size(), "search: one mode per query");
   LOCUST_CHECK_ARG(within.empty() || within.size() == queries.size(),
                    "search: one window (within) per query, or none");
@@ -258,7 +259,7 @@ std::vector<SearchQuery> to_queries(const JobConfig& cfg,
       LOCUST_CHECK_ARG(queries[i].size() == 1,
                        "search: an expr query is one expression (bytes, or a one-element list), "
                        "not " + std::to_string(queries[i].size()) + " terms");
-      out[i] = make_search_expr(queries[i][0], cfg, wildcard, glob, fuzzy);
+      out[i] = make_search_expr(queries[i][0], cfg, wildcard, glob, fuzzy, regex);
       // (a window or exclusion terms on it: carried along as given, for check_search_queries,
       // which every engine runs before anything else, to refuse)
       if (!within.empty()) out[i].within = within[i];
@@ -275,7 +276,7 @@ std::vector<SearchQuery> to_queries(const JobConfig& cfg,
                                              : SearchMode::kAny,
                                wildcard, within.empty() ? 0 : within[i],
                                exclude.empty() ? std::vector<std::string>() : exclude[i], glob,
-                               fuzzy);
+                               fuzzy, regex);
   }
   return out;
 }
@@ -312,9 +313,9 @@ PySearchResult PyIndexResult::search(const std::vector<std::vector<std::string>>
                                      const std::vector<int>& any, const py::object& rank,
                                      bool wildcard, const std::vector<u64>& within,
                                      const std::vector<std::vector<std::string>>& exclude, bool glob,
-                        bool ignore_case, const py::object& show, bool fuzzy) const {
+                        bool ignore_case, const py::object& show, bool fuzzy, bool regex) const {
   const std::vector<SearchQuery> q =
-      to_queries(cfg, queries, any, wildcard, within, exclude, glob, fuzzy);
+      to_queries(cfg, queries, any, wildcard, within, exclude, glob, fuzzy, regex);
   const u64 k = to_rank(rank);
   const u64 n = to_show(show);
   py::gil_scoped_release nogil;
@@ -464,9 +465,9 @@ class PyGpuEngine {
                             const py::object& rank, bool wildcard,
                             const std::vector<u64>& within,
                             const std::vector<std::vector<std::string>>& exclude, bool glob,
-                        bool ignore_case, const py::object& show, bool fuzzy) {
+                        bool ignore_case, const py::object& show, bool fuzzy, bool regex) {
     const std::vector<SearchQuery> q =
-        to_queries(eng_.config(), queries, any, wildcard, within, exclude, glob, fuzzy);
+        to_queries(eng_.config(), queries, any, wildcard, within, exclude, glob, fuzzy, regex);
     const u64 k = to_rank(rank);
     const u64 n = to_show(show);
     py::gil_scoped_release nogil;
@@ -478,9 +479,9 @@ class PyGpuEngine {
                                  const py::object& rank, bool wildcard,
                             const std::vector<u64>& within,
                             const std::vector<std::vector<std::string>>& exclude, bool glob,
-                        bool ignore_case, const py::object& show, bool fuzzy) {
+                        bool ignore_case, const py::object& show, bool fuzzy, bool regex) {
     const std::vector<SearchQuery> q =
-        to_queries(eng_.config(), queries, any, wildcard, within, exclude, glob, fuzzy);
+        to_queries(eng_.config(), queries, any, wildcard, within, exclude, glob, fuzzy, regex);
     const u64 k = to_rank(rank);
     const u64 n = to_show(show);
     py::gil_scoped_release nogil;
@@ -490,9 +491,9 @@ class PyGpuEngine {
                                  const std::vector<int>& any, const py::object& rank,
                                  bool wildcard, const std::vector<u64>& within,
                                  const std::vector<std::vector<std::string>>& exclude, bool glob,
-                        bool ignore_case, const py::object& show, bool fuzzy) {
+                        bool ignore_case, const py::object& show, bool fuzzy, bool regex) {
     const std::vector<SearchQuery> q =
-        to_queries(eng_.config(), queries, any, wildcard, within, exclude, glob, fuzzy);
+        to_queries(eng_.config(), queries, any, wildcard, within, exclude, glob, fuzzy, regex);
     const u64 k = to_rank(rank);
     const u64 n = to_show(show);
     py::gil_scoped_release nogil;
@@ -1043,7 +1044,7 @@ PYBIND11_MODULE(_locust, m) {
            py::arg("within") = std::vector<u64>(),
            py::arg("exclude") = std::vector<std::vector<std::string>>(),
            py::arg("glob") = false, py::arg("ignore_case") = false, py::arg("show") = py::none(),
-           py::arg("fuzzy") = false,
+           py::arg("fuzzy") = false, py::arg("regex") = false,
            "The host evaluation of all/any queries (any[i]: query i's mode) over this index.")
       .def("times", &PyIndexResult::times)
       .def("format", &PyIndexResult::format)
@@ -1150,20 +1151,20 @@ PYBIND11_MODULE(_locust, m) {
            py::arg("wildcard") = false, py::arg("within") = std::vector<u64>(),
            py::arg("exclude") = std::vector<std::vector<std::string>>(),
            py::arg("glob") = false, py::arg("ignore_case") = false, py::arg("show") = py::none(),
-           py::arg("fuzzy") = false,
+           py::arg("fuzzy") = false, py::arg("regex") = false,
            "WordCount of text, its index, and all/any queries answered on the device.")
       .def("run_search_text", &PyGpuEngine::run_search_text, py::arg("text"), py::arg("queries"),
            py::arg("any"), py::arg("first_line") = 0, py::arg("rank") = py::none(),
            py::arg("wildcard") = false, py::arg("within") = std::vector<u64>(),
            py::arg("exclude") = std::vector<std::vector<std::string>>(),
            py::arg("glob") = false, py::arg("ignore_case") = false, py::arg("show") = py::none(),
-           py::arg("fuzzy") = false)
+           py::arg("fuzzy") = false, py::arg("regex") = false)
       .def("search_resident", &PyGpuEngine::search_resident, py::arg("queries"), py::arg("any"),
            py::arg("rank") = py::none(), py::arg("wildcard") = false,
            py::arg("within") = std::vector<u64>(),
            py::arg("exclude") = std::vector<std::vector<std::string>>(),
            py::arg("glob") = false, py::arg("ignore_case") = false, py::arg("show") = py::none(),
-           py::arg("fuzzy") = false,
+           py::arg("fuzzy") = false, py::arg("regex") = false,
            "Another batch from the index the last run_index / run_search left on the device.")
       .def("top_counts", &PyGpuEngine::top_counts, py::arg("records"), py::arg("k"),
            "The selection kernels alone over key-sorted (key, count) records.")
@@ -1187,26 +1188,26 @@ PYBIND11_MODULE(_locust, m) {
                              const py::object& rank, bool wildcard,
                              const std::vector<u64>& within,
                              const std::vector<std::vector<std::string>>& exclude, bool glob,
-                        bool ignore_case, const py::object& show, bool fuzzy) {
+                        bool ignore_case, const py::object& show, bool fuzzy, bool regex) {
     CpuWordCount eng(cfg);
     return PySearchResult{eng.run_search(as_input(text, first_line),
-                                         to_queries(cfg, queries, any, wildcard, within, exclude, glob, fuzzy),
+                                         to_queries(cfg, queries, any, wildcard, within, exclude, glob, fuzzy, regex),
                                          to_rank(rank), ignore_case, to_show(show))};
   }, py::arg("cfg"), py::arg("text"), py::arg("queries"), py::arg("any"),
         py::arg("first_line") = 0, py::arg("rank") = py::none(), py::arg("wildcard") = false,
         py::arg("within") = std::vector<u64>(),
            py::arg("exclude") = std::vector<std::vector<std::string>>(),
            py::arg("glob") = false, py::arg("ignore_case") = false, py::arg("show") = py::none(),
-           py::arg("fuzzy") = false);
+           py::arg("fuzzy") = false, py::arg("regex") = false);
   m.def("make_search_expr", [](const JobConfig& cfg, const std::string& expr, bool wildcard,
-                               bool glob, bool fuzzy) {
+                               bool glob, bool fuzzy, bool regex) {
     // engine.hpp "boolean expressions": the parsed query's parts (tests, tools)
-    const SearchQuery q = make_search_expr(expr, cfg, wildcard, glob, fuzzy);
+    const SearchQuery q = make_search_expr(expr, cfg, wildcard, glob, fuzzy, regex);
     py::dict d;
     py::list terms, kinds, truth;
     for (size_t t = 0; t < q.terms.size(); ++t) {
       terms.append(py::bytes(q.terms[t]));
-      kinds.append(q.fuzzy_budget(t) ? "fuzzy" : q.is_pattern(t) ? "pattern"
+      kinds.append(q.is_regex(t) ? "regex" : q.fuzzy_budget(t) ? "fuzzy" : q.is_pattern(t) ? "pattern"
                    : q.is_prefix(t)  ? "prefix" : "plain");
     }
     for (const u32 w : q.truth) truth.append(w);
@@ -1217,11 +1218,36 @@ PYBIND11_MODULE(_locust, m) {
     d["excluded"] = q.excluded;
     return d;
   }, py::arg("cfg"), py::arg("expr"), py::arg("wildcard") = false, py::arg("glob") = false,
-        py::arg("fuzzy") = false,
+        py::arg("fuzzy") = false, py::arg("regex") = false,
         "The `expr` query of an expression: its text with blanks collapsed, its distinct terms in "
         "order of first occurrence, their kinds and the 8 x u32 truth table; throws for every "
         "refused expression.");
   m.attr("kExprMaxDepth") = kExprMaxDepth;
+  m.def("compile_regex", [](const std::string& source, bool ignore_case) {
+    return compile_regex(source, ignore_case);
+  }, py::arg("source"), py::arg("ignore_case") = false,
+        "A regex term's compiled program (engine.hpp \"regex terms\"; device/regex.hpp: first, "
+        "last, nullable, positions, follow[32], B[256]); throws for every refused source.");
+  m.def("make_search_query", [](const std::vector<std::string>& terms, bool wildcard, bool glob,
+                                bool fuzzy, bool regex) {
+    // how the terms of a query read (tests, tools): (bytes, kind) per term
+    const SearchQuery q =
+        make_search_query(terms, SearchMode::kAll, wildcard, 0, {}, glob, fuzzy, regex);
+    py::list out;
+    for (size_t t = 0; t < q.terms.size(); ++t)
+      out.append(py::make_tuple(py::bytes(q.terms[t]),
+                                q.is_regex(t)        ? "regex"
+                                : q.fuzzy_budget(t)  ? "fuzzy"
+                                : q.is_pattern(t)    ? "pattern"
+                                : q.is_prefix(t)     ? "prefix"
+                                                     : "plain"));
+    return out;
+  }, py::arg("terms"), py::arg("wildcard") = false, py::arg("glob") = false,
+        py::arg("fuzzy") = false, py::arg("regex") = false,
+        "The terms of a query as make_search_query reads them: (bytes, kind) per term.");
+  m.attr("kRegexMaxDepth") = kRegexMaxDepth;
+  m.attr("kRegexMaxSource") = kRegexMaxSource;
+  m.attr("kRegexMaxPos") = kRegexMaxPos;
   m.def("check_search_show", &check_search_show, py::arg("show"), py::arg("text_bytes"),
         "Throws unless show is 0 or 1 <= N <= kShowMaxBytes over a window of < 2^32 bytes.");
   m.def("validate_show", [](const std::vector<std::string>& terms, const std::vector<u32>& lines,

@@ -82,7 +82,7 @@ def _search_args(queries, mode, within=None, exclude=None):
 
 
 def _index_search(self, queries, mode="all", rank=None, wildcard=False, within=None,
-                  exclude=None, glob=False, ignore_case=False, show=None, fuzzy=False):
+                  exclude=None, glob=False, ignore_case=False, show=None, fuzzy=False, regex=False):
     """All/any word queries over this index, evaluated on the host (``SearchResult``):
     ``queries``, ``mode``, ``rank``, ``within`` and ``exclude`` as ``Engine.run_search`` takes
     them, any number of queries.  A ``"phrase"`` query, and a ``"near"`` query of two or more
@@ -92,7 +92,7 @@ def _index_search(self, queries, mode="all", rank=None, wildcard=False, within=N
     ``show=N`` is refused like a phrase: the shown lines come from the text."""
     queries, flags, windows, exclude = _search_args(queries, mode, within, exclude)
     return self._search(queries, flags, rank, bool(wildcard), windows, exclude, bool(glob),
-                        bool(ignore_case), show, bool(fuzzy))
+                        bool(ignore_case), show, bool(fuzzy), bool(regex))
 
 
 _C.IndexResult.search = _index_search
@@ -136,7 +136,7 @@ class Engine:
 
     def run_search(self, text: bytes, queries, mode="all", first_line: int = 0, rank=None,
                    wildcard=False, within=None, exclude=None, glob=False, ignore_case=False,
-                   show=None, fuzzy=False):
+                   show=None, fuzzy=False, regex=False):
         """WordCount of ``text``, its inverted index, and a batch of word queries answered
         from it (``SearchResult``).  ``queries`` is a list of term lists (1 to 8 byte-string
         terms each); ``mode`` is ``"all"`` (lines that hold every term), ``"any"`` (lines
@@ -209,6 +209,16 @@ class Engine:
         or ``glob`` is on.  A ``~`` anywhere else is literal, and without ``fuzzy`` every ``~``
         is.  On the GPU the dictionary scan finds the words with a banded edit-distance matcher.
 
+        ``regex=True`` reads a term written ``/re/`` as a regular expression that a whole word
+        must match: ``/(king|queen)[!?]?/``, ``/[A-Z][A-Z]+/``, ``/\\[?Hamlet[!?\\]]?/``.  The
+        syntax is literals, ``\\x`` escapes of non-alphanumeric bytes, ``.``, classes ``[a-z]``
+        and ``[^...]``, groups, ``|``, ``*``, ``+`` and ``?``, over bytes; at most 32 positions
+        and 128 source bytes; ``{m,n}``, anchors, ``\\d`` and ``\\w`` are refused
+        (``oracle.REGEX_RULES`` states the rules).  It behaves as one word with its words' merged
+        lists, exactly as a pattern term does, under ``ignore_case`` too, and is read before the
+        fuzzy, wildcard and glob readings.  Without ``regex`` a ``/x/`` is a literal word.  On
+        the GPU the dictionary scan runs the compiled position automaton, one key per lane.
+
         ``show=N`` (``1 <= N <= 65536``; ``None`` or ``0``: no show) also returns, for every
         returned line, its first ``N`` bytes and the spans of its tokens that match one of the
         query's own terms (``oracle.show`` states the rules): ``text(i)`` is the list of query
@@ -221,13 +231,13 @@ class Engine:
         if self.cpu:
             return _C.cpu_run_search(self.cfg, text, queries, flags, first_line, rank,
                                      bool(wildcard), windows, exclude, bool(glob),
-                                     bool(ignore_case), show, bool(fuzzy))
+                                     bool(ignore_case), show, bool(fuzzy), bool(regex))
         return self._eng.run_search(text, queries, flags, first_line, rank, bool(wildcard),
                                     windows, exclude, bool(glob), bool(ignore_case), show,
-                                    bool(fuzzy))
+                                    bool(fuzzy), bool(regex))
 
     def search_resident(self, queries, mode="all", rank=None, wildcard=False, within=None,
-                        exclude=None, glob=False, ignore_case=False, show=None, fuzzy=False):
+                        exclude=None, glob=False, ignore_case=False, show=None, fuzzy=False, regex=False):
         """Another batch from the index this engine's last job left on the device; that
         job must have been a ``run_index`` or a ``run_search`` (GPU engines only).  Every
         mode of ``run_search``: the job's text is resident too, so phrases and near queries
@@ -238,7 +248,7 @@ class Engine:
                                  "no index (use run_index(text).search(...))")
         queries, flags, windows, exclude = _search_args(queries, mode, within, exclude)
         return self._eng.search_resident(queries, flags, rank, bool(wildcard), windows, exclude,
-                                         bool(glob), bool(ignore_case), show, bool(fuzzy))
+                                         bool(glob), bool(ignore_case), show, bool(fuzzy), bool(regex))
 
     def top_counts(self, records: list[tuple[bytes, int]], k: int):
         """The selection alone over (key, count) records sorted by key with distinct
@@ -340,26 +350,26 @@ def index_file(path: str, line_start: int = -1, line_end: int = -1, backend: str
 
 def search_text(text: bytes, queries, mode="all", backend: str = "gpu", cfg=None,
                 first_line: int = 0, rank=None, wildcard=False, within=None, exclude=None,
-                glob=False, ignore_case=False, show=None, fuzzy=False, **kw):
+                glob=False, ignore_case=False, show=None, fuzzy=False, regex=False, **kw):
     """All/any/phrase/near word queries over ``text`` (``SearchResult``); see
     ``Engine.run_search``."""
     cfg = cfg if cfg is not None else make_config(backend, **kw)
     nlines = text.count(b"\n") + (1 if text and not text.endswith(b"\n") else 0)
     return Engine(cfg, max(len(text), 1), max(nlines, 1)).run_search(
         text, queries, mode, first_line, rank, wildcard, within, exclude, glob, ignore_case,
-        show, fuzzy)
+        show, fuzzy, regex)
 
 
 def search_file(path: str, queries, mode="all", line_start: int = -1, line_end: int = -1,
                 backend: str = "gpu", cfg=None, rank=None, wildcard=False, within=None,
-                exclude=None, glob=False, ignore_case=False, show=None, fuzzy=False, **kw):
+                exclude=None, glob=False, ignore_case=False, show=None, fuzzy=False, regex=False, **kw):
     """All/any/phrase/near word queries over a file or its line window, answered with the file's
     own (global) line numbers."""
     cfg = cfg if cfg is not None else make_config(backend, **kw)
     text, nlines, first, _total = _C.load_lines(path, line_start, line_end, cfg.ref_compat)
     return Engine(cfg, max(len(text), 1), max(nlines, 1)).run_search(
         text, queries, mode, first, rank, wildcard, within, exclude, glob, ignore_case, show,
-        fuzzy)
+        fuzzy, regex)
 
 
 def map_stage(path: str, spill: str, line_start: int = -1, line_end: int = -1,

@@ -230,6 +230,217 @@ FUZZY_RULES = """
 """
 
 
+REGEX_RULES = r"""
+    Regex terms (``regex=True``): ``/\[?Hamlet[!?\]]?/``, ``/(king|queen)[!?]?/``.
+
+    - Reading.  With ``regex`` a term that starts with ``/`` is a regex term: at least three
+      bytes, ending in a ``/`` that an odd run of backslashes does not escape; the source is what
+      stands between the slashes.  ``/``, ``//`` and ``/ab`` are refused.  The reading comes
+      before the fuzzy, wildcard and glob readings; nothing inside the slashes is read by them.
+      Without ``regex`` the term is the literal word.
+    - Syntax, over bytes.  A literal byte; ``\x`` for a byte ``x`` that is no ASCII letter or
+      digit (a letter or digit behind a backslash is refused); ``.`` any one byte; ``[...]`` and
+      ``[^...]`` with single bytes and ranges ``a-z``, ``\`` escapes, ``]`` escaped, ``-`` first
+      or last literal, ``^`` special only first; ``( )`` groups, ``|`` alternates, ``*``, ``+``,
+      ``?`` repeat the atom before them; an empty branch or group matches the empty string.
+      Refused: the empty source; a quantifier with nothing to repeat or directly behind another;
+      an unescaped ``{``, ``}``, ``^``, ``$`` outside a class; unbalanced parentheses; a range
+      with lo > hi, an empty or unterminated class; a NUL or newline; nesting deeper than 32; a
+      source longer than 128 bytes; more than 32 positions (literals, dots, classes).
+      Delimiter bytes are legal in the source and match no key.  A regex is never cut.
+    - Words.  The index keys (cut to ``max_key``) that the whole expression matches, anchored at
+      both ends.  Nothing matches beyond the key's bytes.
+    - ``ignore_case``.  A position's byte set -- a literal's byte, a class's members before its
+      negation -- is closed under the ASCII case swap, then negated: ``[^a]`` matches neither
+      ``a`` nor ``A``.
+    - Identity.  Two regex terms are the same term when their sources are equal byte for byte,
+      also under ``ignore_case``; never the same as a term of another kind; outside the nesting.
+    - Everything else is a pattern term's rule (``PATTERN_RULES``).
+
+    The evaluation here is independent of the engines' position automaton: the source is parsed
+    into a tree, and a token matches when the set of offsets reachable through the tree from
+    offset 0 holds its length.
+"""
+
+REGEX_MAX_DEPTH = 32
+REGEX_MAX_SOURCE = 128
+REGEX_MAX_POS = 32
+
+
+def regex_source(term: bytes) -> bytes:
+    """The source of the regex term ``/source/`` (``REGEX_RULES``, reading)."""
+    back = len(term) - len(term[:-1].rstrip(b"\\")) - 1 if len(term) >= 3 else 0
+    if len(term) < 3 or term[-1] != 0x2F or back % 2:
+        raise ValueError("the term %r starts with / but is no /source/" % (term,))
+    return term[1:-1]
+
+
+def regex_parse(src: bytes):
+    """The tree of a regex source: ``("set", frozenset, negated)``, ``("cat", (..))``,
+    ``("alt", (..))``, ``("rep", node, lo, unbounded)``.  ``ValueError`` for every refusal."""
+    if not src:
+        raise ValueError("an empty regex source")
+    if len(src) > REGEX_MAX_SOURCE:
+        raise ValueError("a regex source longer than %d bytes" % REGEX_MAX_SOURCE)
+    if 0 in src or 0x0A in src:
+        raise ValueError("a regex source holds a NUL or a newline")
+    pos, count = 0, 0
+
+    def escape():
+        nonlocal pos
+        if pos + 1 >= len(src):
+            raise ValueError("a trailing backslash")
+        c = src[pos + 1]
+        if bytes([c]).isalnum() and c < 0x80:
+            raise ValueError("a backslash before a letter or digit is reserved")
+        pos += 2
+        return c
+
+    def leaf(members, negated=False):
+        nonlocal count
+        count += 1
+        if count > REGEX_MAX_POS:
+            raise ValueError("more than %d positions" % REGEX_MAX_POS)
+        return ("set", frozenset(members), negated)
+
+    def klass():
+        nonlocal pos
+        negated = pos < len(src) and src[pos] == 0x5E
+        pos += negated
+        members = set()
+        while True:
+            if pos >= len(src):
+                raise ValueError("an unterminated class")
+            if src[pos] == 0x5D:
+                pos += 1
+                break
+            if src[pos] == 0x5C:
+                lo = escape()
+            else:
+                lo, pos = src[pos], pos + 1
+            hi = lo
+            if pos + 1 < len(src) and src[pos] == 0x2D and src[pos + 1] != 0x5D:
+                pos += 1
+                if src[pos] == 0x5C:
+                    hi = escape()
+                else:
+                    hi, pos = src[pos], pos + 1
+                if lo > hi:
+                    raise ValueError("a range with lo > hi")
+            members.update(range(lo, hi + 1))
+        if not members:
+            raise ValueError("an empty class")
+        return leaf(members, negated)
+
+    def atom(depth):
+        nonlocal pos
+        c = src[pos]
+        if c == 0x28:
+            if depth >= REGEX_MAX_DEPTH:
+                raise ValueError("nesting deeper than %d" % REGEX_MAX_DEPTH)
+            pos += 1
+            x = alt(depth + 1)
+            if pos >= len(src) or src[pos] != 0x29:
+                raise ValueError("unbalanced parentheses")
+            pos += 1
+            return x
+        if c == 0x5B:
+            pos += 1
+            return klass()
+        if c == 0x2E:
+            pos += 1
+            return leaf(range(256))
+        if c in b"{}^$":
+            raise ValueError("an unescaped %r outside a class" % chr(c))
+        if c in b"*+?":
+            raise ValueError("a quantifier with nothing to repeat")
+        if c == 0x5C:
+            return leaf([escape()])
+        pos += 1
+        return leaf([c])
+
+    def cat(depth):
+        nonlocal pos
+        parts = []
+        while pos < len(src) and src[pos] not in b"|)":
+            x = atom(depth)
+            if pos < len(src) and src[pos] in b"*+?":
+                q = src[pos]
+                pos += 1
+                x = ("rep", x, 1 if q == 0x2B else 0, q != 0x3F)
+                if pos < len(src) and src[pos] in b"*+?":
+                    raise ValueError("a quantifier directly after another quantifier")
+            parts.append(x)
+        return ("cat", parts)
+
+    def alt(depth):
+        nonlocal pos
+        branches = [cat(depth)]
+        while pos < len(src) and src[pos] == 0x7C:
+            pos += 1
+            branches.append(cat(depth))
+        return ("alt", branches)
+
+    tree = alt(0)
+    if pos != len(src):
+        raise ValueError("unbalanced parentheses")
+    return _freeze(tree)
+
+
+def _freeze(node):
+    """The tree with tuples for lists: hashable, so a (tree, token) verdict can be cached."""
+    if node[0] in ("cat", "alt"):
+        return (node[0], tuple(_freeze(x) for x in node[1]))
+    if node[0] == "rep":
+        return ("rep", _freeze(node[1]), node[2], node[3])
+    return node
+
+
+def _swap_case(c: int) -> int:
+    return c ^ 0x20 if 0x41 <= c <= 0x5A or 0x61 <= c <= 0x7A else c
+
+
+def _regex_ends(node, tok: bytes, starts: frozenset, fold: bool) -> frozenset:
+    """The offsets behind a match of ``node`` that starts at one of ``starts``."""
+    kind = node[0]
+    if kind == "set":
+        _k, members, negated = node
+        out = set()
+        for o in starts:
+            if o < len(tok):
+                c = tok[o]
+                inside = c in members or (fold and _swap_case(c) in members)
+                if inside != negated:
+                    out.add(o + 1)
+        return frozenset(out)
+    if kind == "cat":
+        for part in node[1]:
+            starts = _regex_ends(part, tok, starts, fold)
+            if not starts:
+                break
+        return starts
+    if kind == "alt":
+        out = set()
+        for branch in node[1]:
+            out |= _regex_ends(branch, tok, starts, fold)
+        return frozenset(out)
+    _k, inner, lo, unbounded = node  # "rep"
+    once = _regex_ends(inner, tok, starts, fold)
+    if not unbounded:  # `?`
+        return starts | once
+    reached, frontier = set(once), once
+    while frontier:  # the offsets behind one, two, ... rounds
+        frontier = _regex_ends(inner, tok, frozenset(frontier), fold) - reached
+        reached |= frontier
+    return frozenset(reached) | (starts if lo == 0 else frozenset())
+
+
+@functools.lru_cache(maxsize=1 << 16)
+def regex_fits(tree, tok: bytes, fold: bool = False) -> bool:
+    """Does the whole token match the tree (``regex_parse``)?  (Cached: a text's tokens repeat.)"""
+    return len(tok) in _regex_ends(tree, tok, frozenset([0]), fold)
+
+
 def _fold(c: int) -> int:
     return c | 0x20 if 0x41 <= c <= 0x5A else c
 
@@ -261,9 +472,11 @@ class QueryTerm:
     @property
     def scattered(self) -> bool:
         """A term whose words are no key range: told apart by ``ident``, outside the nesting."""
-        return self.kind in ("pattern", "fuzzy")
+        return self.kind in ("pattern", "fuzzy", "regex")
 
     def fits(self, tok: bytes) -> bool:
+        if self.kind == "regex":
+            return regex_fits(self.rx, tok, self.fold)
         if self.kind == "fuzzy":
             return levenshtein(self.p, tok, self.fold) <= self.d
         if self.kind == "pattern":
@@ -292,13 +505,18 @@ def _pattern_term(cells, fold: bool) -> QueryTerm:
 
 
 def query_terms(terms, wildcard: bool = False, glob: bool = False, ignore_case: bool = False,
-                delims: bytes = DEFAULT_DELIMS, max_key: int = 29, *, fuzzy: bool = False):
+                delims: bytes = DEFAULT_DELIMS, max_key: int = 29, *, fuzzy: bool = False, regex: bool = False):
     """The terms of a query as ``QueryTerm`` objects, validated and cut: ``prefix_terms``'
     sibling for ``glob`` and ``ignore_case`` (``PATTERN_RULES``) and ``fuzzy``
     (``FUZZY_RULES``)."""
     bad = set(delims) | {0, 0x0A}
     out = []
     for t in terms:
+        if regex and t[:1] == b"/":  # (read before every other reading: REGEX_RULES)
+            src = regex_source(t)
+            out.append(QueryTerm("regex", p=src, rx=regex_parse(src), ident=("regex", src),
+                                 fold=ignore_case))
+            continue
         if fuzzy and len(t) >= 3 and t[-2] == 0x7E and 0x30 <= t[-1] <= 0x39:
             w, d = t[:-2], t[-1] - 0x30  # (read before the wildcard and glob reading)
             if d not in (1, 2):
@@ -404,12 +622,12 @@ def _check_exclude(terms, exclude):
 
 
 def _excluded_by_index(entries, postings, exclude, wildcard, delims, max_key, glob=False,
-                       ignore_case=False, fuzzy=False):
+                       ignore_case=False, fuzzy=False, regex=False):
     """``(lines, counts)`` of exclusion terms over an index: the union of the terms' lines as
     a set, and every term's count (its word's, or its merged count; 0: absent)."""
     out, counts = set(), []
     for term in query_terms(exclude, wildcard, glob, ignore_case, delims, max_key,
-                       fuzzy=fuzzy):
+                       fuzzy=fuzzy, regex=regex):
         lines = _term_list(entries, postings, _qt_words(entries, term))
         counts.append(len(lines))
         out.update(lines)
@@ -417,11 +635,11 @@ def _excluded_by_index(entries, postings, exclude, wildcard, delims, max_key, gl
 
 
 def _excluded_by_text(text, exclude, wildcard, delims, emits, max_key, first_line, glob=False,
-                      ignore_case=False, fuzzy=False):
+                      ignore_case=False, fuzzy=False, regex=False):
     """The same from the text: a line is excluded when one of its emitted tokens (the index
     holds no other) matches an exclusion term; a term's count is its matching tokens."""
     want = query_terms(exclude, wildcard, glob, ignore_case, delims, max_key,
-                       fuzzy=fuzzy)
+                       fuzzy=fuzzy, regex=regex)
     out, counts = set(), [0] * len(want)
     for i, line in enumerate(split_lines(text)):
         toks, _dropped = tokenize(line, delims, emits, max_key)
@@ -435,7 +653,7 @@ def _excluded_by_text(text, exclude, wildcard, delims, emits, max_key, first_lin
 
 def merged_elements(entries, queries, delims: bytes = DEFAULT_DELIMS, max_key: int = 29, *,
                     exclude=None, glob: bool = False, ignore_case: bool = False,
-                    fuzzy: bool = False,
+                    fuzzy: bool = False, regex: bool = False,
                     wildcard: bool = True) -> int:
     """``SearchResult.merged`` of a device batch of wildcard ``queries`` (term lists): over
     the batch's prefix terms that cover two or more words, a term whose words repeat an
@@ -457,7 +675,7 @@ def merged_elements(entries, queries, delims: bytes = DEFAULT_DELIMS, max_key: i
     for terms in queries:
         seen = []
         for term in query_terms(terms, wildcard, glob, ignore_case, delims, max_key,
-                       fuzzy=fuzzy):
+                       fuzzy=fuzzy, regex=regex):
             words = _qt_words(entries, term)
             # what a later term must repeat: a pattern term's pattern, another term's words
             same = term.ident if term.scattered else words
@@ -469,7 +687,7 @@ def merged_elements(entries, queries, delims: bytes = DEFAULT_DELIMS, max_key: i
 
 def search(entries, postings, terms, mode: str = "all", delims: bytes = DEFAULT_DELIMS,
            max_key: int = 29, *, wildcard: bool = False, exclude=None, glob: bool = False,
-           ignore_case: bool = False, fuzzy: bool = False):
+           ignore_case: bool = False, fuzzy: bool = False, regex: bool = False):
     """One all/any word query over an index: ``(lines, counts)``.
 
     ``entries`` and ``postings`` are ``index``'s output.  A query is 1 to 8 ``terms`` and a
@@ -497,16 +715,16 @@ def search(entries, postings, terms, mode: str = "all", delims: bytes = DEFAULT_
     if exclude is not None:
         exclude = _check_exclude(terms, exclude)
         lines, counts = search(entries, postings, terms, mode, delims, max_key,
-                               wildcard=wildcard, glob=glob, ignore_case=ignore_case, fuzzy=fuzzy)
+                               wildcard=wildcard, glob=glob, ignore_case=ignore_case, fuzzy=fuzzy, regex=regex)
         gone, xcounts = _excluded_by_index(entries, postings, exclude, wildcard, delims,
-                                           max_key, glob, ignore_case, fuzzy)
+                                           max_key, glob, ignore_case, fuzzy, regex)
         return [l for l in lines if l not in gone], counts + xcounts
     if not 1 <= len(terms) <= MAX_SEARCH_TERMS:
         raise ValueError("a query takes 1 to %d terms" % MAX_SEARCH_TERMS)
-    if wildcard or glob or ignore_case or fuzzy:  # (``glob`` / ``ignore_case``: PATTERN_RULES)
+    if wildcard or glob or ignore_case or fuzzy or regex:  # (``glob`` / ``ignore_case``: PATTERN_RULES)
         sets, counts = [], []
         for term in query_terms(terms, wildcard, glob, ignore_case, delims, max_key,
-                       fuzzy=fuzzy):
+                       fuzzy=fuzzy, regex=regex):
             lines = _term_list(entries, postings, _qt_words(entries, term))
             counts.append(len(lines))
             sets.append(set(lines))
@@ -528,7 +746,7 @@ def search(entries, postings, terms, mode: str = "all", delims: bytes = DEFAULT_
 
 def phrase(text: bytes, terms, delims: bytes = DEFAULT_DELIMS, emits: int = 20,
            max_key: int = 29, first_line: int = 0, *, wildcard: bool = False, exclude=None,
-           glob: bool = False, ignore_case: bool = False, fuzzy: bool = False):
+           glob: bool = False, ignore_case: bool = False, fuzzy: bool = False, regex: bool = False):
     """One phrase query over ``text``: ``(lines, counts)``, as ``search`` answers.
 
     `phrase` answers the lines on which the terms occur as consecutive tokens, in order.
@@ -559,15 +777,15 @@ def phrase(text: bytes, terms, delims: bytes = DEFAULT_DELIMS, emits: int = 20,
     if exclude is not None:
         exclude = _check_exclude(terms, exclude)
         lines, counts = phrase(text, terms, delims, emits, max_key, first_line,
-                               wildcard=wildcard, glob=glob, ignore_case=ignore_case, fuzzy=fuzzy)
+                               wildcard=wildcard, glob=glob, ignore_case=ignore_case, fuzzy=fuzzy, regex=regex)
         gone, xcounts = _excluded_by_text(text, exclude, wildcard, delims, emits, max_key,
-                                          first_line, glob, ignore_case, fuzzy)
+                                          first_line, glob, ignore_case, fuzzy, regex)
         return [l for l in lines if l not in gone], counts + xcounts
     if not 1 <= len(terms) <= MAX_SEARCH_TERMS:
         raise ValueError("a query takes 1 to %d terms" % MAX_SEARCH_TERMS)
-    if wildcard or glob or ignore_case or fuzzy:  # (``glob`` / ``ignore_case``: PATTERN_RULES)
+    if wildcard or glob or ignore_case or fuzzy or regex:  # (``glob`` / ``ignore_case``: PATTERN_RULES)
         want = query_terms(terms, wildcard, glob, ignore_case, delims, max_key,
-                       fuzzy=fuzzy)
+                       fuzzy=fuzzy, regex=regex)
         m = len(want)
 
         def fits(tok, term):
@@ -605,7 +823,7 @@ MAX_SEARCH_WITHIN = (1 << 32) - 1
 
 def near(text: bytes, terms, within: int, delims: bytes = DEFAULT_DELIMS, emits: int = 20,
          max_key: int = 29, first_line: int = 0, *, wildcard: bool = False, exclude=None,
-         glob: bool = False, ignore_case: bool = False, fuzzy: bool = False):
+         glob: bool = False, ignore_case: bool = False, fuzzy: bool = False, regex: bool = False):
     """One proximity query over ``text``: ``(lines, counts)``, as ``search`` answers.
 
     `near` answers the lines on which the terms occur within ``within`` = W tokens of one
@@ -633,9 +851,9 @@ def near(text: bytes, terms, within: int, delims: bytes = DEFAULT_DELIMS, emits:
     if exclude is not None:
         exclude = _check_exclude(terms, exclude)
         lines, counts = near(text, terms, within, delims, emits, max_key, first_line,
-                             wildcard=wildcard, glob=glob, ignore_case=ignore_case, fuzzy=fuzzy)
+                             wildcard=wildcard, glob=glob, ignore_case=ignore_case, fuzzy=fuzzy, regex=regex)
         gone, xcounts = _excluded_by_text(text, exclude, wildcard, delims, emits, max_key,
-                                          first_line, glob, ignore_case, fuzzy)
+                                          first_line, glob, ignore_case, fuzzy, regex)
         return [l for l in lines if l not in gone], counts + xcounts
     if not 1 <= len(terms) <= MAX_SEARCH_TERMS:
         raise ValueError("a query takes 1 to %d terms" % MAX_SEARCH_TERMS)
@@ -644,7 +862,7 @@ def near(text: bytes, terms, within: int, delims: bytes = DEFAULT_DELIMS, emits:
         raise ValueError("a near query takes a window 1 <= W < 2^32, not %r" % (within,))
     # (``glob`` / ``ignore_case``: PATTERN_RULES)
     want = query_terms(terms, wildcard, glob, ignore_case, delims, max_key,
-                       fuzzy=fuzzy)
+                       fuzzy=fuzzy, regex=regex)
 
     def fits(tok, term):
         return term.fits(tok)
@@ -703,9 +921,28 @@ EXPR_RULES = """
 EXPR_MAX_DEPTH = 64
 
 
-def expr_tokens(expr: bytes):
+def _regex_token_end(expr: bytes, i: int) -> int:
+    """The index of the slash that closes the regex token starting at ``expr[i] == '/'``."""
+    j = i + 1
+    while j < len(expr) and expr[j] != 0x2F:
+        j += 2 if expr[j] == 0x5C else 1
+    if j >= len(expr):
+        raise ValueError("a regex term without its closing /")
+    if j + 1 < len(expr) and expr[j + 1] not in b" \t()":
+        raise ValueError("a regex term's closing / is followed by a blank, a parenthesis or the end")
+    return j
+
+
+def expr_tokens(expr: bytes, regex: bool = False):
     out, cur = [], bytearray()
-    for c in expr:
+    skip = -1
+    for i, c in enumerate(expr):
+        if i <= skip:
+            continue
+        if regex and c == 0x2F and not cur:  # a regex token: blanks and parentheses belong to it
+            skip = _regex_token_end(expr, i)
+            out.append(expr[i:skip + 1])
+            continue
         if c in b" \t()":
             if cur:
                 out.append(bytes(cur))
@@ -719,26 +956,45 @@ def expr_tokens(expr: bytes):
     return out
 
 
-def expr_text(expr: bytes) -> bytes:
-    """The expression as a result line prints it."""
-    return b" ".join(p for p in re.split(rb"[ \t]+", expr) if p)
+def expr_text(expr: bytes, regex: bool = False) -> bytes:
+    """The expression as a result line prints it (a regex token's blanks are its own)."""
+    if not regex:
+        return b" ".join(p for p in re.split(rb"[ \t]+", expr) if p)
+    out, gap, skip, start = bytearray(), False, -1, True
+    for i, c in enumerate(expr):
+        if i <= skip:
+            continue
+        if c in b" \t":
+            gap, start = bool(out), True
+            continue
+        if gap:
+            out.append(0x20)
+        gap = False
+        if c == 0x2F and start:
+            skip = _regex_token_end(expr, i)
+            out += expr[i:skip + 1]
+            start = False
+            continue
+        out.append(c)
+        start = c in b"()"
+    return bytes(out)
 
 
 def expr_parse(expr: bytes, delims: bytes = DEFAULT_DELIMS, max_key: int = 29, *,
-               wildcard: bool = False, glob: bool = False, fuzzy: bool = False):
+               wildcard: bool = False, glob: bool = False, fuzzy: bool = False, regex: bool = False):
     """``(tree, terms)`` of an expression (``EXPR_RULES``): ``terms`` are its distinct terms as
     asked, in order of first occurrence; ``tree`` is ``("term", t)``, ``("not", x)``,
     ``("and", x, y)`` or ``("or", x, y)``.  ``ValueError`` for every refused expression, the one
     that holds for no word among them."""
-    toks = expr_tokens(expr)
+    toks = expr_tokens(expr, regex)
     if not toks:
         raise ValueError("an empty expression")
     terms, idents = [], []
     pos = 0
 
     def number(tok):
-        query_terms([tok], wildcard, glob, False, delims, max_key, fuzzy=fuzzy)  # its errors
-        t, = query_terms([tok], wildcard, glob, False, delims, 1 << 30, fuzzy=fuzzy)
+        query_terms([tok], wildcard, glob, False, delims, max_key, fuzzy=fuzzy, regex=regex)  # its errors
+        t, = query_terms([tok], wildcard, glob, False, delims, 1 << 30, fuzzy=fuzzy, regex=regex)
         ident = (t.kind, t.ident if t.scattered else t.p)
         if ident in idents:
             return idents.index(ident)
@@ -815,18 +1071,18 @@ def expr_holds(tree, have) -> bool:
     return stack[0]
 
 
-def _expr_lists(entries, postings, terms, delims, max_key, wildcard, glob, ignore_case, fuzzy):
+def _expr_lists(entries, postings, terms, delims, max_key, wildcard, glob, ignore_case, fuzzy, regex):
     return [_term_list(entries, postings, _qt_words(entries, t))
-            for t in query_terms(terms, wildcard, glob, ignore_case, delims, max_key, fuzzy=fuzzy)]
+            for t in query_terms(terms, wildcard, glob, ignore_case, delims, max_key, fuzzy=fuzzy, regex=regex)]
 
 
 def expr_search(entries, postings, expr: bytes, delims: bytes = DEFAULT_DELIMS,
                 max_key: int = 29, *, wildcard: bool = False, glob: bool = False,
-                ignore_case: bool = False, fuzzy: bool = False):
+                ignore_case: bool = False, fuzzy: bool = False, regex: bool = False):
     """One ``expr`` query over an index: ``(lines, counts, terms)`` (``EXPR_RULES``)."""
-    tree, terms = expr_parse(expr, delims, max_key, wildcard=wildcard, glob=glob, fuzzy=fuzzy)
+    tree, terms = expr_parse(expr, delims, max_key, wildcard=wildcard, glob=glob, fuzzy=fuzzy, regex=regex)
     lists = _expr_lists(entries, postings, terms, delims, max_key, wildcard, glob, ignore_case,
-                        fuzzy)
+                        fuzzy, regex)
     sets = [set(l) for l in lists]
     lines = [line for line in sorted(set().union(*sets))
              if expr_holds(tree, {t for t, s in enumerate(sets) if line in s})]
@@ -835,12 +1091,12 @@ def expr_search(entries, postings, expr: bytes, delims: bytes = DEFAULT_DELIMS,
 
 def expr_walked(entries, postings, expr: bytes, delims: bytes = DEFAULT_DELIMS,
                 max_key: int = 29, *, wildcard: bool = False, glob: bool = False,
-                ignore_case: bool = False, fuzzy: bool = False) -> int:
+                ignore_case: bool = False, fuzzy: bool = False, regex: bool = False) -> int:
     """The list elements the device walks for one ``expr`` query: the summed list lengths of
     the greedy covering set (``EXPR_RULES``, the walked set)."""
-    tree, terms = expr_parse(expr, delims, max_key, wildcard=wildcard, glob=glob, fuzzy=fuzzy)
+    tree, terms = expr_parse(expr, delims, max_key, wildcard=wildcard, glob=glob, fuzzy=fuzzy, regex=regex)
     lens = [len(l) for l in _expr_lists(entries, postings, terms, delims, max_key, wildcard, glob,
-                                        ignore_case, fuzzy)]
+                                        ignore_case, fuzzy, regex)]
     present = [t for t, n in enumerate(lens) if n]
     true_sets = []  # the sets of present terms for which the expression holds
     for bits in range(1, 1 << len(present)):
@@ -887,7 +1143,7 @@ RANK_MAX_EMITS = 65536
 
 def rank(entries, postings, lines, terms, k: int, max_key: int = 29, *,
          wildcard: bool = False, delims: bytes = DEFAULT_DELIMS, exclude=None,
-         glob: bool = False, ignore_case: bool = False, fuzzy: bool = False, emits=None):
+         glob: bool = False, ignore_case: bool = False, fuzzy: bool = False, regex: bool = False, emits=None):
     """The ranked answer of one query: ``(top, matches)``.
 
     ``lines`` is the query's matching set, as ``search`` or ``phrase`` answered it; ranking
@@ -922,21 +1178,21 @@ def rank(entries, postings, lines, terms, k: int, max_key: int = 29, *,
     if emits is not None:
         pat = any(t.scattered for t in query_terms(
             list(terms) + list(exclude or []), wildcard, glob, ignore_case, delims, max_key,
-                       fuzzy=fuzzy))
+                       fuzzy=fuzzy, regex=regex))
         if emits > (RANK_MAX_EMITS // MAX_SEARCH_TERMS if pat else RANK_MAX_EMITS):
             raise ValueError("a ranked search takes emits_per_line <= %d"
                              % (RANK_MAX_EMITS // MAX_SEARCH_TERMS if pat else RANK_MAX_EMITS))
     if exclude is not None:
         exclude = _check_exclude(list(terms), exclude)
         gone, _counts = _excluded_by_index(entries, postings, exclude, wildcard, delims,
-                                           max_key, glob, ignore_case, fuzzy)
+                                           max_key, glob, ignore_case, fuzzy, regex)
         return rank(entries, postings, [l for l in lines if l not in gone], terms, k,
                     max_key, wildcard=wildcard, delims=delims, glob=glob,
-                    ignore_case=ignore_case, fuzzy=fuzzy)
-    if wildcard or glob or ignore_case or fuzzy:
+                    ignore_case=ignore_case, fuzzy=fuzzy, regex=regex)
+    if wildcard or glob or ignore_case or fuzzy or regex:
         n = len(postings)
         want = query_terms(terms, wildcard, glob, ignore_case, delims, max_key,
-                       fuzzy=fuzzy)
+                       fuzzy=fuzzy, regex=regex)
         ranges = [set(_qt_words(entries, t)) for t in want]
         lists = []
         for j, rj in enumerate(ranges):
@@ -1026,7 +1282,7 @@ def line_tokens(line: bytes, delims: bytes = DEFAULT_DELIMS, emits: int = 20):
 
 def show(text: bytes, lines, terms, n: int, delims: bytes = DEFAULT_DELIMS, emits: int = 20,
          max_key: int = 29, first_line: int = 0, *, wildcard: bool = False, glob: bool = False,
-         ignore_case: bool = False, fuzzy: bool = False):
+         ignore_case: bool = False, fuzzy: bool = False, regex: bool = False):
     """What ``show=n`` adds to one query's answer ``lines`` (global numbers, in result order):
     ``(texts, spans, cut)`` -- per entry the shown bytes and the ``(start, len, mask)`` list,
     and the number of entries whose line was longer than ``n`` (``SHOW_RULES``).  ``terms`` are
@@ -1036,7 +1292,7 @@ def show(text: bytes, lines, terms, n: int, delims: bytes = DEFAULT_DELIMS, emit
     if len(text) >= 1 << 32:
         raise ValueError("show takes a text of less than 2^32 bytes")
     want = query_terms(list(terms), wildcard, glob, ignore_case, delims, max_key,
-                       fuzzy=fuzzy)
+                       fuzzy=fuzzy, regex=regex)
     all_lines = split_lines(text)
     texts, spans, cut = [], [], 0
     for l in lines:

@@ -22,10 +22,11 @@ TopResult GpuWordCount::run_top_source(TextSource&, u32) { no_gpu(); }
 TopResult GpuWordCount::top_counts(const KeyCount*, u64, u32) { no_gpu(); }
 IndexResult GpuWordCount::run_index(const TextInput&) { no_gpu(); }
 SearchResult GpuWordCount::run_search(const TextInput&, const std::vector<SearchQuery>&, u64,
-                                      bool, u64) {
+                                      bool, u64, u64) {
   no_gpu();
 }
-SearchResult GpuWordCount::search_resident(const std::vector<SearchQuery>&, u64, bool, u64) {
+SearchResult GpuWordCount::search_resident(const std::vector<SearchQuery>&, u64, bool, u64,
+                                           u64) {
   no_gpu();
 }
 char* GpuWordCount::input_buffer() { no_gpu(); }

@@ -34,6 +34,7 @@
 //   --ignore-case (with --search: the ASCII letters of every word match either case)
 //   --show N (with --search: under each query's line, every returned line's first N bytes)
 //   --mark (with --show: the matching tokens of a shown line stand between >> and <<)
+//   --tally K (with --search: under each query's line, the K most frequent words of its lines)
 // and a synthetic-text generator (BASELINE configs "1M lines" / "10 GB"):
 //   MapReduce --gen FILE (--gen-lines N | --gen-bytes N) [--seed S] [--vocab V]
 #include <sys/stat.h>
@@ -115,6 +116,7 @@ struct CliArgs {
   bool ignore_case = false;  // --ignore-case: the batch's ASCII letters match either case
   u64 show = 0;       // --show N: the returned lines' first N bytes (0: line numbers only)
   bool mark = false;  // --mark: the shown lines' matching tokens between >> and <<
+  u64 tally = 0;      // --tally K: the K most frequent words of every query's returned lines
   std::string gen_out;  // generator mode
   GenSpec gen;
 };
@@ -223,6 +225,13 @@ void help() {
       "  --mark                     (--show: every token of a shown line that matches one of the\n"
       "                             query's words -- not its --not words -- stands between >>\n"
       "                             and <<, as far as it lies inside the N bytes)\n"
+      "  --tally K                  (--search: under each query's result line and its shown\n"
+      "                             lines, \"  words: W \\t tokens: T\" -- the distinct words and\n"
+      "                             the tokens of the lines the query returns -- and the K most\n"
+      "                             frequent of those words, \"  word: <key> \\t count: <n>\", by\n"
+      "                             count and then by key, 1 <= K <= 4096; counted on the device.\n"
+      "                             With every --match, --rank (the winners' words), --show,\n"
+      "                             --not and both backends)\n"
       "  --ignore-case              (--search: the ASCII letters of every word of every query,\n"
       "                             --not words too, match either case: \"to be\" finds \"To be\".\n"
       "                             Other bytes match only themselves.  With --glob, --wildcard and\n"
@@ -389,6 +398,14 @@ bool parse(int argc, char** argv, CliArgs* a) {
         throw Error("--show N (the first N bytes of every line a --search query returns) needs "
                     "an integer N with 1 <= N <= " + std::to_string(kShowMaxBytes));
       a->show = (u64)n;
+    } else if (s == "--tally") {
+      const std::string v = need("--tally");
+      char* endp = nullptr;
+      const long long n = std::strtoll(v.c_str(), &endp, 10);
+      if (v.empty() || *endp || n < 1 || n > (long long)kTopKMax)
+        throw Error("--tally K (the K most frequent words of the lines every --search query "
+                    "returns) needs an integer K with 1 <= K <= " + std::to_string(kTopKMax));
+      a->tally = (u64)n;
     } else if (s == "--mark") {
       a->mark = true;
     } else if (s == "--rank") {
@@ -475,6 +492,9 @@ bool parse(int argc, char** argv, CliArgs* a) {
     throw Error("--ignore-case selects how --search compares letters: give --search too");
   if (a->show && a->search_args.empty())
     throw Error("--show N prints the lines a --search query returns: give --search too");
+  if (a->tally && a->search_args.empty())
+    throw Error("--tally K counts the words of the lines a --search query returns: give --search "
+                "too (--top K is the same count over the whole text)");
   if (a->mark && !a->show)
     throw Error("--mark marks the matching tokens of the lines --show prints: give --show too");
   if (a->index && !a->search_args.empty())
@@ -740,6 +760,9 @@ void json_search(JsonOut& j, const CliArgs& a) {
     j.num("show_ms", g_search->show_ms);
     j.u("cut_lines", g_search->cut_lines);
     j.u("spans", g_search->spans.size() / 3);
+    j.u("tally", g_search->tally_k);
+    j.num("tally_ms", g_search->tally_ms);
+    j.u("tallied", g_search->tallied);
     j.u("wire_bytes", g_search->wire_bytes);
     j.u("merged", g_search->merged);
     j.u("walked", g_search->walked);
@@ -1317,7 +1340,8 @@ int run(const CliArgs& a) {
     for (int i = 0; i < a.warmup; ++i) eng.run(text.input);
     for (int i = 0; i < a.iters; ++i) {
       if (!a.queries.empty()) {
-        cpu_search = eng.run_search(text.input, a.queries, a.rank, a.ignore_case, a.show);
+        cpu_search =
+            eng.run_search(text.input, a.queries, a.rank, a.ignore_case, a.show, a.tally);
         r = search_stats(cpu_search);
       } else if (a.index) {
         cpu_index = eng.run_index(text.input);
@@ -1338,7 +1362,7 @@ int run(const CliArgs& a) {
     if (!a.queries.empty()) {  // the word job, the index stage and the search stage
       SearchResult sr;
       for (int i = 0; i < a.warmup + a.iters; ++i) {
-        sr = eng.run_search(text.input, a.queries, a.rank, a.ignore_case, a.show);
+        sr = eng.run_search(text.input, a.queries, a.rank, a.ignore_case, a.show, a.tally);
         if (i >= a.warmup) walls.push_back(sr.times.wall_ms);
       }
       print_gpu_result(a, search_stats(sr), walls, nullptr, nullptr, &sr);

@@ -1091,7 +1091,80 @@ void check_search_show(u64 show, u64 text_bytes) {
                    "a u32), not " + std::to_string(text_bytes) + ": search a line window");
 }
 
+void check_search_tally(u64 tally) {
+  if (tally == 0) return;
+  LOCUST_CHECK_ARG(tally <= kTopKMax,
+                   "search: tally takes 1 <= K <= kTopKMax = " + std::to_string(kTopKMax) +
+                       " words per query, not " + std::to_string(tally) +
+                       ": ask for fewer words (entries() of the index lists every word)");
+}
+
+TallyKeySplit tally_key_split(u64 n, u64 tokens) {
+  const auto bit_length = [](u64 v) { return v ? 64u - (u32)__builtin_clzll(v) : 0u; };
+  LOCUST_CHECK_ARG(tokens < (1ull << 32),
+                   "search: the tally's returned lines hold " + std::to_string(tokens) +
+                       " tokens, which does not fit the 32-bit pair counter (2^32): use --rank K "
+                       "to return fewer lines, or fewer queries");
+  TallyKeySplit ks;
+  ks.r = bit_length(n ? n - 1 : 0);
+  ks.c = bit_length(tokens);
+  ks.cmask = ks.c ? (~0ull >> (64 - ks.c)) : 0ull;
+  LOCUST_CHECK_ARG(ks.c + ks.r <= 54,
+                   "search: the tally's rank key needs " + std::to_string(ks.c) +
+                       " count bits (" + std::to_string(tokens) + " tokens) and " +
+                       std::to_string(ks.r) + " rank bits (" + std::to_string(n) +
+                       " index words), more than the 54 below the query: use --rank K to return "
+                       "fewer lines, or fewer queries");
+  return ks;
+}
+
 namespace {
+
+// engine.hpp "tally": per query a bitmap of its returned lines, then one pass over the postings,
+// word by word.  Needs no text.
+void tally_lines(const IndexResult& x, u64 k, SearchResult* r) {
+  const u64 t0 = now_ns();
+  const size_t Q = r->queries.size();
+  const size_t n = x.words.entries.size();
+  const WordCountEntry* ent = x.words.entries.data();
+  r->tally_k = k;
+  r->tally_off.assign(1, 0);
+  r->tally_words.assign(Q, 0);
+  r->tally_tokens.assign(Q, 0);
+  std::vector<u8> returned((size_t)r->num_lines, 0);
+  std::vector<std::pair<u64, size_t>> counted;  // (count, word) of one query's words
+  for (size_t q = 0; q < Q; ++q) {
+    counted.clear();
+    if (r->offsets[q + 1] > r->offsets[q]) {
+      for (u64 e = r->offsets[q]; e < r->offsets[q + 1]; ++e)
+        returned[(size_t)(r->lines[e] - r->first_line)] = 1;
+      u64 at = 0;
+      for (size_t w = 0; w < n; ++w) {
+        u64 c = 0;
+        for (const u64 end = at + ent[w].count; at < end; ++at)
+          c += returned[(size_t)(x.postings[(size_t)at] - x.first_line)];
+        if (c) counted.emplace_back(c, w);
+        r->tally_tokens[q] += c;
+      }
+      for (u64 e = r->offsets[q]; e < r->offsets[q + 1]; ++e)
+        returned[(size_t)(r->lines[e] - r->first_line)] = 0;
+    }
+    r->tally_words[q] = counted.size();
+    // count descending, key ascending: the entries stand in key order, so a word's index decides
+    const size_t take = (size_t)std::min<u64>(k, counted.size());
+    std::partial_sort(counted.begin(), counted.begin() + (std::ptrdiff_t)take, counted.end(),
+                      [](const auto& a, const auto& b) {
+                        return a.first != b.first ? a.first > b.first : a.second < b.second;
+                      });
+    for (size_t i = 0; i < take; ++i) {
+      r->tally_keys.push_back(ent[counted[i].second].key);
+      r->tally_counts.push_back(counted[i].first);
+    }
+    r->tally_off.push_back(r->tally_keys.size());
+  }
+  r->tally_ms = (now_ns() - t0) * 1e-6;
+  r->times.wall_ms += r->tally_ms;
+}
 
 // The positive terms a line's tokens are matched against.  masks: empty, or per key and word
 // the bytes a token must share with it (a prefix term: key_word_mask of its words; a plain
@@ -1224,7 +1297,7 @@ void show_lines(const TextInput& text, const std::vector<u64>& line_at, const Jo
 
 SearchResult search_index_impl(const IndexResult& x, const TextInput* text,
                                const std::vector<SearchQuery>& queries, const JobConfig& cfg,
-                               u64 rank_k, bool ignore_case, u64 show) {
+                               u64 rank_k, bool ignore_case, u64 show, u64 tally) {
   check_search_queries(queries, cfg);
   const bool patterns = search_has_patterns(queries, ignore_case);
   check_search_rank(rank_k, cfg, patterns);
@@ -1233,6 +1306,7 @@ SearchResult search_index_impl(const IndexResult& x, const TextInput* text,
                    "search_index(index, text, queries, cfg, ...), the four-argument overload, or "
                    "run_search on an engine");
   check_search_show(show, text ? text->bytes : 0);
+  check_search_tally(tally);
   bool verify = false;  // a phrase, or a near query, of two or more positive terms
   for (const SearchQuery& q : queries)
     verify |= (q.mode == SearchMode::kPhrase || q.mode == SearchMode::kNear) &&
@@ -1489,6 +1563,7 @@ SearchResult search_index_impl(const IndexResult& x, const TextInput* text,
   r.search_ms = (now_ns() - t0) * 1e-6;
   r.times.wall_ms += r.search_ms;
   if (show) show_lines(*text, line_at, cfg, patterns, (u32)show, &r);
+  if (tally) tally_lines(x, tally, &r);
   if (cfg.check) validate_search(r);
   return r;
 }
@@ -1496,15 +1571,72 @@ SearchResult search_index_impl(const IndexResult& x, const TextInput* text,
 }  // namespace
 
 SearchResult search_index(const IndexResult& x, const std::vector<SearchQuery>& queries,
-                          const JobConfig& cfg, u64 rank_k, bool ignore_case, u64 show) {
-  return search_index_impl(x, nullptr, queries, cfg, rank_k, ignore_case, show);
+                          const JobConfig& cfg, u64 rank_k, bool ignore_case, u64 show,
+                          u64 tally) {
+  return search_index_impl(x, nullptr, queries, cfg, rank_k, ignore_case, show, tally);
 }
 
 SearchResult search_index(const IndexResult& x, const TextInput& text,
                           const std::vector<SearchQuery>& queries, const JobConfig& cfg,
-                          u64 rank_k, bool ignore_case, u64 show) {
-  return search_index_impl(x, &text, queries, cfg, rank_k, ignore_case, show);
+                          u64 rank_k, bool ignore_case, u64 show, u64 tally) {
+  return search_index_impl(x, &text, queries, cfg, rank_k, ignore_case, show, tally);
 }
+
+namespace {
+
+// validate_search's part for engine.hpp "tally".
+void validate_tally(const SearchResult& r) {
+  if (r.tally_k == 0) {
+    if (!r.tally_off.empty() || !r.tally_keys.empty() || !r.tally_counts.empty() ||
+        !r.tally_words.empty() || !r.tally_tokens.empty() || r.tallied)
+      throw Error("LOCUST_CHECK: search result without tally holds tallied words");
+    return;
+  }
+  const size_t Q = r.queries.size();
+  if (r.tally_k > kTopKMax)
+    throw Error("LOCUST_CHECK: tally K = " + std::to_string(r.tally_k) + " above kTopKMax");
+  if (r.tally_off.size() != Q + 1 || r.tally_off.front() != 0 ||
+      r.tally_off.back() != r.tally_keys.size() || r.tally_counts.size() != r.tally_keys.size() ||
+      r.tally_words.size() != Q || r.tally_tokens.size() != Q)
+    throw Error("LOCUST_CHECK: tally offsets do not span the " +
+                std::to_string(r.tally_keys.size()) + " words of " + std::to_string(Q) +
+                " queries");
+  for (size_t q = 0; q < Q; ++q) {
+    if (r.tally_off[q + 1] < r.tally_off[q] || r.tally_off[q + 1] > r.tally_keys.size())
+      throw Error("LOCUST_CHECK: tally offsets decrease at query " + std::to_string(q));
+    const u64 got = r.tally_off[q + 1] - r.tally_off[q];
+    if (got > std::min<u64>(r.tally_k, r.tally_words[q]))
+      throw Error("LOCUST_CHECK: query " + std::to_string(q) + " tallies " + std::to_string(got) +
+                  " words, more than min(K = " + std::to_string(r.tally_k) + ", " +
+                  std::to_string(r.tally_words[q]) + " words)");
+    if (r.tally_words[q] > r.tally_tokens[q] ||
+        (r.tally_words[q] == 0) != (r.tally_tokens[q] == 0))
+      throw Error("LOCUST_CHECK: query " + std::to_string(q) + " tallies " +
+                  std::to_string(r.tally_words[q]) + " words over " +
+                  std::to_string(r.tally_tokens[q]) + " tokens");
+    u64 sum = 0;
+    for (u64 j = r.tally_off[q]; j < r.tally_off[q + 1]; ++j) {
+      const u64 c = r.tally_counts[j];
+      if (c < 1)
+        throw Error("LOCUST_CHECK: tallied word " + std::to_string(j - r.tally_off[q]) +
+                    " of query " + std::to_string(q) + " has count 0");
+      if (j > r.tally_off[q] &&
+          (c > r.tally_counts[j - 1] ||
+           (c == r.tally_counts[j - 1] &&
+            key_compare(r.tally_keys[j - 1].w, r.tally_keys[j].w) >= 0)))
+        throw Error("LOCUST_CHECK: tallied words of query " + std::to_string(q) +
+                    " not in (count descending, key ascending) order at position " +
+                    std::to_string(j - r.tally_off[q]));
+      sum += c;
+    }
+    if (sum > r.tally_tokens[q])
+      throw Error("LOCUST_CHECK: the tallied counts of query " + std::to_string(q) +
+                  " add up to " + std::to_string(sum) + ", more than its " +
+                  std::to_string(r.tally_tokens[q]) + " tokens");
+  }
+}
+
+}  // namespace
 
 void validate_search(const SearchResult& r) {
   if (r.offsets.size() != r.queries.size() + 1 || r.offsets.front() != 0 ||
@@ -1550,6 +1682,7 @@ void validate_search(const SearchResult& r) {
                     " not strictly ascending at position " + std::to_string(j - r.offsets[q]));
     }
   }
+  validate_tally(r);
   if (r.show_bytes == 0) {
     if (!r.text.empty() || !r.text_off.empty() || !r.spans.empty() || !r.span_off.empty() ||
         r.cut_lines)
@@ -1633,8 +1766,7 @@ void format_search_output(const SearchResult& r, std::string* out, bool mark) {
       }
     }
     out->push_back('\n');
-    if (!r.show_bytes) continue;
-    for (u64 e = r.offsets[q]; e < r.offsets[q + 1]; ++e) {
+    for (u64 e = r.offsets[q]; r.show_bytes && e < r.offsets[q + 1]; ++e) {
       out->append("  ");
       out->append(std::to_string(r.lines[e]));
       out->append(": ");
@@ -1652,6 +1784,21 @@ void format_search_output(const SearchResult& r, std::string* out, bool mark) {
           done = en;
         }
       out->append(t + done, (size_t)(tl - done));
+      out->push_back('\n');
+    }
+    if (!r.tally_k) continue;
+    out->append("  words: ");
+    out->append(std::to_string(r.tally_words[q]));
+    out->append(" \t tokens: ");
+    out->append(std::to_string(r.tally_tokens[q]));
+    out->push_back('\n');
+    char buf[kKeyBytes + 1];
+    for (u64 j = r.tally_off[q]; j < r.tally_off[q + 1]; ++j) {
+      const int kn = unpack_key(r.tally_keys[j].w, buf);
+      out->append("  word: ");
+      out->append(buf, (size_t)kn);
+      out->append(" \t count: ");
+      out->append(std::to_string(r.tally_counts[j]));
       out->push_back('\n');
     }
   }

@@ -51,12 +51,12 @@ TopResult GpuWordCount::top_counts(const KeyCount* recs, u64 n, u32 k) {
 IndexResult GpuWordCount::run_index(const TextInput& in) { return impl_->run_index(in); }
 SearchResult GpuWordCount::run_search(const TextInput& in,
                                       const std::vector<SearchQuery>& queries, u64 rank_k,
-                                      bool ignore_case, u64 show) {
-  return impl_->run_search(in, queries, rank_k, ignore_case, show);
+                                      bool ignore_case, u64 show, u64 tally) {
+  return impl_->run_search(in, queries, rank_k, ignore_case, show, tally);
 }
 SearchResult GpuWordCount::search_resident(const std::vector<SearchQuery>& queries, u64 rank_k,
-                                           bool ignore_case, u64 show) {
-  return impl_->search_resident(queries, rank_k, ignore_case, show);
+                                           bool ignore_case, u64 show, u64 tally) {
+  return impl_->search_resident(queries, rank_k, ignore_case, show, tally);
 }
 GpuWordCount::Stats GpuWordCount::stats() const {
   Stats s;
@@ -75,7 +75,8 @@ GpuWordCount::Stats GpuWordCount::stats() const {
                    impl_->sbatch.merged_cap * sizeof(u32) +
                    (impl_->d_spat ? search_pattern_bytes() : 0) +
                    (impl_->d_sexpr ? search_expr_bytes() : 0) + impl_->show_entry_cap_bytes +
-                   impl_->sshow.cap_text + impl_->sshow.cap_spans * 3 * sizeof(u32);
+                   impl_->sshow.cap_text + impl_->sshow.cap_spans * 3 * sizeof(u32) +
+                   impl_->tally_entry_cap_bytes + impl_->tally_pair_cap_bytes;
   return s;
 }
 

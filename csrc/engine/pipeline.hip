@@ -577,6 +577,11 @@ DevicePipeline::~DevicePipeline() {
   if (d_show_text) (void)hipFree(d_show_text);
   if (d_show_spans) (void)hipFree(d_show_spans);
   pinned_free(h_show);
+  if (d_tally_entries) (void)hipFree(d_tally_entries);
+  if (d_tally_pairs) (void)hipFree(d_tally_pairs);
+  pinned_free(h_tally);
+  for (auto& e : ev_tally)
+    if (e) (void)hipEventDestroy(e);
   for (auto& e : ev_show)
     if (e) (void)hipEventDestroy(e);
 }
@@ -2317,8 +2322,162 @@ void DevicePipeline::show_stage(u32 Q, const u64* offsets, u64 E, u32 N, SearchR
   r->wire_bytes += payload + 2 * sizeof(ShowCounters);
 }
 
+void DevicePipeline::tally_stage(u32 Q, const u64* offsets, u64 E, u32 K, SearchResult* r) {
+  TraceRange tr("locust:tally");
+  r->tally_k = K;
+  r->tally_off.assign((size_t)Q + 1, 0);
+  r->tally_words.assign((size_t)Q, 0);
+  r->tally_tokens.assign((size_t)Q, 0);
+  if (E == 0) return;  // nothing returned: nothing to tally, nothing launched
+  if (!ev_tally[0])
+    for (auto& e : ev_tally) LOCUST_HIP_CHECK(hipEventCreate(&e));
+  size_t fr = 0, tot = 0;
+  if (stally.cap_entries < E) {
+    // (the stream is drained: search_stage, or show_stage, has synchronised)
+    if (d_tally_entries) LOCUST_HIP_CHECK(hipFree(d_tally_entries));
+    d_tally_entries = nullptr;
+    stally.cap_entries = 0;
+    tally_entry_cap_bytes = 0;
+    const u64 cap = align_up(E, (u64)4096);
+    const u64 bytes = tally_entry_bytes(cap);
+    LOCUST_HIP_CHECK(hipMemGetInfo(&fr, &tot));
+    if ((double)bytes > kHbmUsable * (double)fr)
+      throw Error("tally: the stage's per-entry arrays (" + std::to_string(bytes) + " B for " +
+                  std::to_string(E) + " returned lines) do not fit the free device memory (" +
+                  std::to_string(fr) + " B free of " + std::to_string(tot) +
+                  " B): use --rank K to return fewer lines, or fewer queries");
+    LOCUST_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&d_tally_entries), bytes));
+    tally_entry_cap_bytes = bytes;
+    tally_entry_carve(d_tally_entries, cap, &stally);
+  }
+  // the pinned answer: [counters | q_words | words | tokens | out_off | the winners' records]
+  const u64 kHdr = sizeof(TallyCounters) + (u64)kSearchMaxQueries * sizeof(u32) +
+                   (3 * (u64)kSearchMaxQueries + 1) * sizeof(u64);
+  if (h_tally_cap < kHdr) {
+    h_tally_cap = 1u << 20;
+    h_tally = static_cast<char*>(pinned_alloc(h_tally_cap, hipHostMallocDefault, "tally answer"));
+  }
+  TallyCounters* h_ctr = reinterpret_cast<TallyCounters*>(h_tally);
+  LOCUST_HIP_CHECK(hipEventRecord(ev_tally[0], stream));
+  launch_tally_measure(idx_view, shits.lines, E, stally, stream);
+  // the stage's sizing readback: the pair words size, or refuse, the workspace and fix the key
+  LOCUST_HIP_CHECK(hipMemcpyAsync(h_ctr, stally.ctr, sizeof(TallyCounters), hipMemcpyDeviceToHost,
+                                  stream));
+  LOCUST_HIP_CHECK(hipEventRecord(ev_tally[1], stream));
+  sync();
+  const u64 T = h_ctr->tokens;
+  if (T > E * (u64)cfg.emits_per_line)
+    throw Error("tally: the measure pass reports " + std::to_string(T) + " tokens for " +
+                std::to_string(E) + " entries of at most " + std::to_string(cfg.emits_per_line));
+  r->wire_bytes += sizeof(TallyCounters);
+  if (T == 0) {  // empty lines only: every query's answer is 0, 0 and no word
+    r->tally_ms = ms_between(ev_tally[0], ev_tally[1]);
+    return;
+  }
+  const TallyKeySplit ks = tally_key_split(idx_view.n, T);
+  const u64 out_need = std::min<u64>(T, (u64)Q * std::min<u64>(K, idx_view.n));
+  if (stally.cap_pairs < T || stally.cap_out < out_need) {
+    if (d_tally_pairs) LOCUST_HIP_CHECK(hipFree(d_tally_pairs));
+    d_tally_pairs = nullptr;
+    stally.cap_pairs = stally.cap_out = 0;
+    stally.rx.cap = 0;
+    tally_pair_cap_bytes = 0;
+    const u64 cap_p = align_up(T, (u64)kSortTile);
+    const u64 cap_o = align_up(out_need, (u64)4096);
+    const u64 bytes = tally_pair_bytes(cap_p, cap_o);
+    LOCUST_HIP_CHECK(hipMemGetInfo(&fr, &tot));
+    if ((double)bytes > kHbmUsable * (double)fr)
+      throw Error("tally: the batch's workspace (" + std::to_string(bytes) + " B: " +
+                  std::to_string(T) + " tokens on " + std::to_string(E) +
+                  " returned lines) does not fit the free device memory (" + std::to_string(fr) +
+                  " B free of " + std::to_string(tot) +
+                  " B): use --rank K to return fewer lines, or fewer queries");
+    LOCUST_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&d_tally_pairs), bytes));
+    tally_pair_cap_bytes = bytes;
+    tally_pair_carve(d_tally_pairs, cap_p, cap_o, &stally);
+    LOCUST_HIP_CHECK(hipMemsetAsync(stally.zeros, 0, cap_p * sizeof(u64), stream));
+  }
+  launch_tally_map(idx_view, Q, shits.lines, offsets, E, T, ks, stally, h_plan, stream);
+  // U and the words per query: the second sort takes its regime from U, and they size what
+  // comes back
+  u32* h_qw = reinterpret_cast<u32*>(h_tally + sizeof(TallyCounters));
+  LOCUST_HIP_CHECK(hipMemcpyAsync(h_ctr, stally.zero, sizeof(TallyCounters) + (u64)Q * sizeof(u32),
+                                  hipMemcpyDeviceToHost, stream));
+  sync();
+  if (h_ctr->miss || h_ctr->mismatch || h_ctr->sort_n != T || h_ctr->tokens != T)
+    throw Error("tally: the map pass disagrees with the index (" + std::to_string(h_ctr->miss) +
+                " tokens whose key it does not hold) or with the measure pass (" +
+                std::to_string(h_ctr->mismatch) + " of " + std::to_string(E) + " entries; " +
+                std::to_string(h_ctr->sort_n) + " of " + std::to_string(T) + " pair words sorted)");
+  const u64 U = h_ctr->runs;
+  u64 W = 0, R = 0;
+  for (u32 q = 0; q < Q; ++q) {
+    W += h_qw[q];
+    R += std::min<u64>(h_qw[q], K);
+  }
+  if (U < 1 || U > T || W != U || h_ctr->misplaced || R > out_need)
+    throw Error("tally: " + std::to_string(U) + " runs among " + std::to_string(T) +
+                " sorted pair words, " + std::to_string(W) + " of them counted for the queries, " +
+                std::to_string(h_ctr->misplaced) + " naming no query, word or count");
+  const u64 need = align_up(kHdr, 256) + R * sizeof(OutRecord);
+  if (h_tally_cap < need) {
+    std::vector<u32> keep(h_qw, h_qw + Q);
+    pinned_free(h_tally);
+    h_tally = nullptr;
+    h_tally_cap = 0;
+    const u64 cap = align_up(need, (u64)1 << 20);
+    h_tally = static_cast<char*>(pinned_alloc(cap, hipHostMallocDefault, "tally answer"));
+    h_tally_cap = cap;
+    h_ctr = reinterpret_cast<TallyCounters*>(h_tally);
+    h_qw = reinterpret_cast<u32*>(h_tally + sizeof(TallyCounters));
+    std::copy(keep.begin(), keep.end(), h_qw);
+  }
+  launch_tally_top(idx_view, Q, offsets, U, K, ks, stally, h_plan, stream);
+  u64* h_words = reinterpret_cast<u64*>(h_qw + kSearchMaxQueries);
+  u64* h_tokens = h_words + kSearchMaxQueries;
+  u64* h_off = h_tokens + kSearchMaxQueries;
+  OutRecord* h_recs = reinterpret_cast<OutRecord*>(h_tally + align_up(kHdr, 256));
+  LOCUST_HIP_CHECK(hipMemcpyAsync(h_words, stally.words, (u64)Q * sizeof(u64),
+                                  hipMemcpyDeviceToHost, stream));
+  LOCUST_HIP_CHECK(hipMemcpyAsync(h_tokens, stally.tokens, (u64)Q * sizeof(u64),
+                                  hipMemcpyDeviceToHost, stream));
+  LOCUST_HIP_CHECK(hipMemcpyAsync(h_off, stally.out_off, ((u64)Q + 1) * sizeof(u64),
+                                  hipMemcpyDeviceToHost, stream));
+  LOCUST_HIP_CHECK(hipMemcpyAsync(h_recs, stally.out, R * sizeof(OutRecord),
+                                  hipMemcpyDeviceToHost, stream));
+  LOCUST_HIP_CHECK(hipMemcpyAsync(h_ctr, stally.ctr, sizeof(TallyCounters), hipMemcpyDeviceToHost,
+                                  stream));
+  LOCUST_HIP_CHECK(hipEventRecord(ev_tally[1], stream));
+  sync();
+  u64 tok_sum = 0;
+  bool agree = h_off[Q] == R && h_off[0] == 0;
+  for (u32 q = 0; q < Q; ++q) {
+    agree &= h_words[q] == h_qw[q] && h_off[q + 1] - h_off[q] == std::min<u64>(h_qw[q], K);
+    tok_sum += h_tokens[q];
+  }
+  if (h_ctr->misplaced || !agree || tok_sum != T)
+    throw Error("tally: " + std::to_string(h_ctr->misplaced) + " of " + std::to_string(U) +
+                " sorted rank keys lie outside their query's range or name no word; the output "
+                "offsets end at " + std::to_string(h_off[Q]) + " (the runs give " +
+                std::to_string(R) + "), the queries' tokens add up to " + std::to_string(tok_sum) +
+                " of " + std::to_string(T));
+  r->tally_off.assign(h_off, h_off + Q + 1);
+  r->tally_words.assign(h_words, h_words + Q);
+  r->tally_tokens.assign(h_tokens, h_tokens + Q);
+  r->tally_keys.resize((size_t)R);
+  r->tally_counts.resize((size_t)R);
+  for (u64 i = 0; i < R; ++i) {
+    std::memcpy(r->tally_keys[i].w, h_recs[i].w, sizeof(PackedKey));
+    r->tally_counts[i] = h_recs[i].count;
+  }
+  r->tallied = T;
+  r->tally_ms = ms_between(ev_tally[0], ev_tally[1]);
+  r->wire_bytes += R * sizeof(OutRecord) + (3 * (u64)Q + 1) * sizeof(u64) +
+                   (u64)Q * sizeof(u32) + 2 * sizeof(TallyCounters);
+}
+
 void DevicePipeline::search_stage(const std::vector<SearchQuery>& queries, u64 rank_k,
-                                  bool ignore_case, u32 show, SearchResult* r) {
+                                  bool ignore_case, u32 show, u32 tally, SearchResult* r) {
   TraceRange tr("locust:search");
   const u32 Q = (u32)queries.size();
   r->queries = queries;
@@ -2371,6 +2530,7 @@ void DevicePipeline::search_stage(const std::vector<SearchQuery>& queries, u64 r
     LOCUST_HIP_CHECK(hipEventRecord(ev_search[1], stream));
     sync();
     if (show) show_stage(0, nullptr, 0, show, r);
+    if (tally) tally_stage(0, nullptr, 0, tally, r);
     return;
   }
   // the batch: q_meta | the terms' keys, packed exactly as the map packs them | the windows,
@@ -2574,6 +2734,7 @@ void DevicePipeline::search_stage(const std::vector<SearchQuery>& queries, u64 r
     r->wire_bytes = ((u64)Q + 1) * sizeof(u64) + (u64)Q * sizeof(u32) + 2 * R * sizeof(u32) +
                     (u64)Q * kSearchMaxTerms * sizeof(u32) + 3 * sizeof(SearchCounters);
     if (show) show_stage(Q, sbatch.out_off, R, show, r);
+    if (tally) tally_stage(Q, sbatch.out_off, R, tally, r);
     return;
   }
   // order + emit
@@ -2600,14 +2761,16 @@ void DevicePipeline::search_stage(const std::vector<SearchQuery>& queries, u64 r
   r->wire_bytes = ((u64)Q + 1) * sizeof(u64) + H * sizeof(u32) +
                   (u64)Q * kSearchMaxTerms * sizeof(u32) + 3 * sizeof(SearchCounters);
   if (show) show_stage(Q, sbatch.offsets, H, show, r);
+  if (tally) tally_stage(Q, sbatch.offsets, H, tally, r);
 }
 
 SearchResult DevicePipeline::run_search(const TextInput& in,
                                         const std::vector<SearchQuery>& queries, u64 rank_k,
-                                        bool ignore_case, u64 show) {
+                                        bool ignore_case, u64 show, u64 tally) {
   TraceRange tr("locust:search_job");
   check_search_batch(queries, rank_k, ignore_case);  // (a refused batch starts nothing)
   check_search_show(show, in.bytes);
+  check_search_tally(tally);
   idx_resident = false;         // (until this job has left its index)
   SearchResult r;
   WordCountResult w;
@@ -2617,7 +2780,7 @@ SearchResult DevicePipeline::run_search(const TextInput& in,
   sync();
   check_index_counters(n, T);
   keep_index(in, w, n, T);
-  search_stage(queries, rank_k, ignore_case, (u32)show, &r);
+  search_stage(queries, rank_k, ignore_case, (u32)show, (u32)tally, &r);
   r.index_ms = ms_between(ev_index[0], ev_index[1]);
   r.search_ms = ms_between(ev_search[0], ev_search[1]);
   r.wire_bytes += sizeof(IndexCounters) + sizeof(MapCounters);
@@ -2625,26 +2788,28 @@ SearchResult DevicePipeline::run_search(const TextInput& in,
   r.times.map_ms = ms_between(ev[1], ev[2]);
   r.times.process_ms = ms_between(ev[2], ev[3]);
   r.times.reduce_ms = ms_between(ev[3], ev[4]);
-  r.times.gpu_ms = ms_between(ev[0], ev_search[1]) + r.show_ms;
+  r.times.gpu_ms = ms_between(ev[0], ev_search[1]) + r.show_ms + r.tally_ms;
   r.times.wall_ms = (now_ns() - t0) * 1e-6;
   if (cfg.check) validate_search(r);
   return r;
 }
 
 SearchResult DevicePipeline::search_resident(const std::vector<SearchQuery>& queries,
-                                             u64 rank_k, bool ignore_case, u64 show) {
+                                             u64 rank_k, bool ignore_case, u64 show,
+                                             u64 tally) {
   TraceRange tr("locust:search_resident");
   check_search_batch(queries, rank_k, ignore_case);
   check_search_show(show, idx_view.bytes);
+  check_search_tally(tally);
   if (!idx_resident)
     throw Error("search_resident: the index on the device is stale -- this engine's last job "
                 "was not a run_index or a run_search (any other job, a refused one included, "
                 "overwrites what the index reads); run one of them first");
   SearchResult r;
   const u64 t0 = now_ns();
-  search_stage(queries, rank_k, ignore_case, (u32)show, &r);
+  search_stage(queries, rank_k, ignore_case, (u32)show, (u32)tally, &r);
   r.search_ms = ms_between(ev_search[0], ev_search[1]);
-  r.times.gpu_ms = r.search_ms + r.show_ms;
+  r.times.gpu_ms = r.search_ms + r.show_ms + r.tally_ms;
   r.times.wall_ms = (now_ns() - t0) * 1e-6;
   if (cfg.check) validate_search(r);
   return r;

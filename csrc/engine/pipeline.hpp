@@ -851,12 +851,13 @@ struct DevicePipeline {
   // number of hits, the result) and fills r's lists, statistics and wire_bytes.
   // rank_k != 0: the ranked answer (engine.hpp "ranked search").
   // show != 0: show_stage behind it, over the lines and offsets it left on the device.
+  // tally != 0: tally_stage behind both, over the same lines and offsets.
   void search_stage(const std::vector<SearchQuery>& queries, u64 rank_k, bool ignore_case,
-                    u32 show, SearchResult* r);
+                    u32 show, u32 tally, SearchResult* r);
   SearchResult run_search(const TextInput& in, const std::vector<SearchQuery>& queries,
-                          u64 rank_k, bool ignore_case, u64 show);
+                          u64 rank_k, bool ignore_case, u64 show, u64 tally);
   SearchResult search_resident(const std::vector<SearchQuery>& queries, u64 rank_k,
-                               bool ignore_case, u64 show);
+                               bool ignore_case, u64 show, u64 tally);
   // ---- show (kernels/show.hip) ----
   // The stage's arrays are allocations of their own, made by the engine's first show batch and
   // grown on demand: the per-entry part (by the batch's entries), the payload's text and
@@ -875,6 +876,25 @@ struct DevicePipeline {
   // search_stage has just answered (offsets: the device's per-query segments); fills r's show
   // fields and adds what it copied to r->wire_bytes.
   void show_stage(u32 queries, const u64* offsets, u64 entries, u32 show, SearchResult* r);
+  // ---- tally (kernels/tally.hip) ----
+  // The stage's arrays are allocations of their own, made by the engine's first tally batch and
+  // grown on demand: the per-entry and per-query part (by the batch's entries) and the pair
+  // part (by the pair words the measure pass reports and the records that come back; checked
+  // against free HBM), and the pinned buffer the answer comes back to.  A batch without tally
+  // touches none of them.
+  TallyBuffers stally{};
+  char* d_tally_entries = nullptr;
+  u64 tally_entry_cap_bytes = 0;
+  char* d_tally_pairs = nullptr;
+  u64 tally_pair_cap_bytes = 0;
+  char* h_tally = nullptr;  // pinned [TallyCounters | q_words | words | tokens | out_off | records]
+  u64 h_tally_cap = 0;
+  hipEvent_t ev_tally[2] = {};
+  // measure + scan + (the sizing readback) + map + order + runs + (U and the words per query) +
+  // order + offsets + top over the `entries` returned lines of the batch search_stage has just
+  // answered (behind show_stage, when both are asked: it leaves the shown payload alone); fills
+  // r's tally fields and adds what it copied to r->wire_bytes.
+  void tally_stage(u32 queries, const u64* offsets, u64 entries, u32 k, SearchResult* r);
 
   // ---------------------------------------------------------------------------------
   // Streaming: an input larger than the engine's text capacity is processed in

@@ -704,6 +704,43 @@ void format_index_output(const IndexResult& r, std::string* out);
 // starts, keys and returned lines: the text itself never crosses PCIe, only the shown bytes and
 // spans do (wire_bytes counts them).  The host evaluation needs the text: the four-argument
 // search_index.
+// ---- tally: the words of the returned lines ----
+// A search job may ask for tally = K, a u32 with 1 <= K <= kTopKMax; tally == 0, the default, is
+// the answer described above, bit for bit, and launches nothing new.  With tally = K every query
+// q of the batch also gets the counts of the index's words over its returned lines:
+//   returned lines  exactly the entries show would print: unranked, the whole matching set;
+//     ranked, the min(rank_k, matches) winners.  The same line returned for two queries counts
+//     for each of them.
+//   count(q, w)  the number of postings of word w whose line is a returned line of q: a pure
+//     function of the index and the returned lines.  A token past the emit cap does not exist,
+//     long tokens merged under truncation count as their merged key, a word twice on a line
+//     counts twice.  Equivalently: the word job's count of w over the returned lines alone, under
+//     the job's own delimiters, emit cap and key cut.
+//   The mode, the window, exclusion terms, prefix, pattern, fuzzy and regex terms and
+//   ignore_case decide which lines are returned, and nothing else: keys are counted as the index
+//   holds them (`To` and `to` are two words even under ignore_case), the query's own words like
+//   any other.
+// Per query: tally_words[q], the words with count > 0; tally_tokens[q], the sum of all counts
+// (the emitted tokens of the returned lines); and the first min(K, tally_words[q]) words in the
+// order count descending, key ascending in unsigned-byte order (the top-K order above: total),
+// each with its key and u64 count.  A word with count 0 is never returned; a query that returns
+// no line gets 0, 0 and no word.  `tallied` is the sum of tally_tokens over the batch: the pair
+// words the device stage sorts (0 for the host evaluation, as merged and walked are).
+// Refused with a clear error: K out of range; tally without a search; on the device, a
+// workspace that does not fit the free device memory (the index stays resident behind the
+// refusal, as behind a refused show) and a batch whose rank key does not fit: with r =
+// bit_length(n - 1) rank bits for n index words and c = bit_length(T) count bits for T pair
+// words, T >= 2^32 or c + r > 54 (the key is query << 54 | (2^c - 1 - count) << r | rank).
+// The device stage (kernels/tally.hip) re-tokenises the returned lines from the resident text;
+// the host evaluation walks the postings word by word against a bitmap of each query's returned
+// lines and needs no text.  Only the winners' records, three per-query arrays and the counters
+// cross PCIe (wire_bytes counts them).
+struct TallyKeySplit {
+  u32 r = 0, c = 0;
+  u64 cmask = 0;
+};
+// The split for n index words and `tokens` pair words; throws as described above.
+TallyKeySplit tally_key_split(u64 n, u64 tokens);
 constexpr u32 kShowMaxBytes = 65536;
 constexpr u64 kShowMaxPayload = 4ull << 30;  // bytes of one batch's show payload on the device
 constexpr u32 kSearchMaxQueries = 1024;
@@ -772,6 +809,15 @@ struct SearchResult {
   std::vector<u64> span_off;   // [entries + 1], in triples
   u64 cut_lines = 0;           // entries whose line was longer than N
   double show_ms = 0;  // device time of the show stage (host evaluation: its wall time)
+  // "tally" above (tally_k == 0: none of these is filled)
+  u64 tally_k = 0;                     // K
+  std::vector<u64> tally_off;          // [queries + 1]: query i's words, [tally_off[i], tally_off[i+1])
+  std::vector<PackedKey> tally_keys;   // count descending, key ascending per query
+  std::vector<u64> tally_counts;       // parallel to tally_keys
+  std::vector<u64> tally_words;        // [queries] words with count > 0
+  std::vector<u64> tally_tokens;       // [queries] the sum of all counts
+  u64 tallied = 0;                     // pair words the device stage sorted (0: host evaluation)
+  double tally_ms = 0;  // device time of the tally stage (host evaluation: its wall time)
   u64 hits() const { return lines.size(); }
 };
 // A term's key: its first min(size, cfg.max_key_len) bytes, packed as the map packs keys.
@@ -859,6 +905,8 @@ void check_search_rank(u64 rank_k, const JobConfig& cfg, bool patterns = false);
 // Throws unless show is 0 (no show) or 1 <= show <= kShowMaxBytes and the window holds fewer
 // than 2^32 bytes ("show" above).
 void check_search_show(u64 show, u64 text_bytes);
+// Throws unless tally is 0 (no tally) or 1 <= tally <= kTopKMax ("tally" above).
+void check_search_tally(u64 tally);
 // The host evaluation over an index result, any number of queries (cfg: the index job's
 // delimiters and max_key_len).  Throws for a phrase query and for a `near` query of two or
 // more terms: the index holds no positions, so they need the text -- the four-argument
@@ -867,16 +915,18 @@ void check_search_show(u64 show, u64 text_bytes);
 // ignore_case: "pattern terms" above.  Pattern terms' words come from a scan of the entries
 // with the shared matcher.
 // show != 0 is refused: the shown lines come from the text (the four-argument overload).
+// tally = K: "tally" above, answered here too -- the rule needs no text.
 SearchResult search_index(const IndexResult& x, const std::vector<SearchQuery>& queries,
                           const JobConfig& cfg, u64 rank_k = 0, bool ignore_case = false,
-                          u64 show = 0);
+                          u64 show = 0, u64 tally = 0);
 // The same with the text the index was built from (the same window: text.first_line ==
 // x.first_line; cfg also gives emits_per_line): a phrase's or a `near` query's candidates
 // come from the `all` evaluation and are verified by tokenising their lines with the CPU
 // engine's tokeniser.  show = N: "show" above, from the same tokeniser and the shared matcher.
 SearchResult search_index(const IndexResult& x, const TextInput& text,
                           const std::vector<SearchQuery>& queries, const JobConfig& cfg,
-                          u64 rank_k = 0, bool ignore_case = false, u64 show = 0);
+                          u64 rank_k = 0, bool ignore_case = false, u64 show = 0,
+                          u64 tally = 0);
 // LOCUST_CHECK invariants of a search result: offsets monotone from 0 to lines.size(), every
 // line inside [first_line, first_line + num_lines), one `matches` per query.  Unranked: every
 // query's lines strictly ascending, matches == the hit counts, no scores.  Ranked: one score
@@ -885,7 +935,10 @@ SearchResult search_index(const IndexResult& x, const TextInput& text,
 // per query.  With show: both offset arrays monotone from 0 to their array's size, every text
 // length <= N, and per entry the spans strictly ascending and non-overlapping, start + len
 // inside the line (the shown bytes, when the line was not cut), masks non-zero and without a
-// bit at or above the query's positive-term count.
+// bit at or above the query's positive-term count.  With tally: tally_off monotone from 0 to
+// the keys' number, at most min(K, tally_words) words per query, every count >= 1, counts
+// non-increasing with equal counts on ascending keys, their sum <= tally_tokens, tally_words <=
+// tally_tokens, and tally_words == 0 exactly when tally_tokens == 0.
 void validate_search(const SearchResult& r);
 // The result lines of a search, one per query:
 //   "print query: <terms joined by one space> \t hits: <h> \t lines: <l0> <l1> ...\n"
@@ -899,6 +952,9 @@ void validate_search(const SearchResult& r);
 // A result with show prints one line per entry under its query's line:
 //   "  <global line number>: <the shown bytes>\n"
 // mark: the part of every span that lies inside the shown bytes stands between ">>" and "<<".
+// A result with tally prints, under the query's line and its shown lines:
+//   "  words: <tally_words> \t tokens: <tally_tokens>\n"
+//   "  word: <key> \t count: <count>\n"   (one per returned word)
 void format_search_output(const SearchResult& r, std::string* out, bool mark = false);
 
 // Text read piece by piece (a file too large to hold): whole lines go straight into the
@@ -1045,13 +1101,15 @@ class GpuWordCount {
   // stays in device memory beside the index (the engine's own copy, not the staging
   // buffer): phrase queries are verified against it.
   // show = N: the show stage behind it ("show": kernels/show.hip).
+  // tally = K: the tally stage behind both ("tally": kernels/tally.hip).
   SearchResult run_search(const TextInput& in, const std::vector<SearchQuery>& queries,
-                          u64 rank_k = 0, bool ignore_case = false, u64 show = 0);
+                          u64 rank_k = 0, bool ignore_case = false, u64 show = 0,
+                          u64 tally = 0);
   // Another batch from the index this engine's last job left on the device.  That job must
   // have been a run_index or a run_search: any other job (a refused one that had started
   // to write included) marks the index stale, and this then throws.
   SearchResult search_resident(const std::vector<SearchQuery>& queries, u64 rank_k = 0,
-                               bool ignore_case = false, u64 show = 0);
+                               bool ignore_case = false, u64 show = 0, u64 tally = 0);
 
   const JobConfig& config() const;
   u64 token_capacity() const;
@@ -1101,7 +1159,8 @@ class CpuWordCount {
   // run_index() + the host evaluation (search_index with the text), any size, any number
   // of queries and every mode.
   SearchResult run_search(const TextInput& in, const std::vector<SearchQuery>& queries,
-                          u64 rank_k = 0, bool ignore_case = false, u64 show = 0);
+                          u64 rank_k = 0, bool ignore_case = false, u64 show = 0,
+                          u64 tally = 0);
   std::vector<PackedKey> run_map_stage(const TextInput& in, WordCountResult* stats);
   WordCountResult run_reduce_stage(const PackedKey* keys, u64 n);
 

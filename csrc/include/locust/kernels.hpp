@@ -1065,6 +1065,104 @@ void launch_show_measure(const SearchIndex& ix, const SearchBatch& b, u32 querie
 void launch_show_write(const SearchIndex& ix, const SearchBatch& b, u32 queries, const u32* lines,
                        const u64* offsets, u64 entries, const ShowBuffers& sb, hipStream_t s);
 
+// ---------------- tally.hip ----------------
+// The tally stage of a search batch (engine.hpp "tally: the words of the returned lines"): for
+// every query the K most frequent index words of its returned lines.  It reads what the show
+// stage reads -- the text, nl_pos, the returned lines (h.lines) and their per-query segments
+// (b.offsets, ranked: b.out_off) -- and the key-ordered records; it is independent of how the
+// lines were found, so one set of kernels serves every batch (no matcher siblings).
+// A sequence of kernels on `s`; data moves between workgroups only across the kernel boundaries
+// (the radix sort it reuses keeps its own look-back), no polled word:
+//   measure  one wave per entry, up to 64 consecutive entries per wave and round: index.hip's
+//            counting walk (step_starts ballots, the emit cap).  Per entry n_tok
+//   scan     one workgroup: tok_off[0 .. E] = exclusive u64 scan of n_tok, the total T to
+//            TallyCounters::tokens
+//   (the host reads the counters: it sizes, or refuses, the workspace and fixes the key split)
+//   map      the same walk with the look-ahead row: every emitted token's key is packed
+//            (pack_row_key) and ranked (find_rank); token `ord` of entry i, which belongs to
+//            query q (lane i's binary search in the offsets), writes the pair word
+//            q << 32 | rank at tok_off[i] + ord.  Every word is written once at a determined
+//            place, below the entry's end and the capacity: no atomics on the output.  A key not
+//            among the records counts in `miss`, an entry whose tokens do not number what
+//            measure counted in `mismatch` (the host throws for either)
+//   seal     one thread: sort_n = T when the map agreed with the measure pass and the index,
+//            else 0 -- the sort never runs over words nobody wrote
+//   order    radix_sort() of the pair words as one-word keys: (query, rank)
+//   runs     one thread per sorted word.  A run head (j == 0 or s[j] != s[j - 1]) finds its
+//            run's end by an upper-bound binary search of its own word in the sorted array (a
+//            run of `the` is thousands long: never walked) and writes the rank key
+//            q << 54 | (cmask - count) << r | rank; its slot comes from one atomic per wave
+//            (ballot + popcount) on TallyCounters::runs, in arbitrary order: the next sort
+//            decides.  One more atomic per wave and distinct query counts the query's words
+//            (q_words), which the host reads with U = runs: they size what comes back
+//   (the host reads U and q_words: the second sort takes its regime from U, as the search's
+//   order stage takes its from the hits)
+//   order    radix_sort() of the U rank keys: (query, count descending, rank ascending); the
+//            keys are distinct, so the order is total
+//   offsets  one workgroup: run_off[q] = the lower bound of q << 54 among the sorted keys
+//            (run_off[Q] = U), words[q] their difference, out_off = the exclusive scan of
+//            min(K, words), tokens[q] = tok_off[offsets[q + 1]] - tok_off[offsets[q]]
+//   top      one thread per sorted key at j: pos = j - run_off[q]; when pos < K the record
+//            {recs[rank].w[0 .. 3], count} goes to out[out_off[q] + pos].  A key whose query or
+//            rank is out of range, whose count is 0 or which lies outside its query's run_off
+//            range counts as misplaced (the host throws).  No atomics on the output
+struct TallyCounters {  // zeroed per tally batch
+  u64 tokens;     // T: the emitted tokens of the returned lines = the pair words
+  u32 miss;       // map: emitted tokens whose key is not among the records
+  u32 mismatch;   // map: entries whose tokens do not number what measure counted
+  u32 sort_n;     // pair words handed to the first sort: T if the map agreed, else 0
+  u32 runs;       // U: the distinct (query, word) runs = the rank keys
+  u32 misplaced;  // runs or sorted rank keys that name no query, no word, no count or lie
+                  // outside their query's range
+  u32 pad[9];
+};
+static_assert(sizeof(TallyCounters) == 64, "one readback");
+// (the rank key's split: TallyKeySplit, tally_key_split -- engine.hpp, a pure host function)
+// The stage's arrays: the per-entry and per-query part (sized by E) and the pair part (sized by
+// T and the records that come back), two allocations of the engine's, made by its first tally
+// batch and grown on demand.
+struct TallyBuffers {
+  char* zero = nullptr;      // [TallyCounters | q_words], zeroed per tally batch
+  u64 zero_bytes = 0;
+  TallyCounters* ctr = nullptr;
+  u32* q_words = nullptr;    // [kSearchMaxQueries] the runs kernel's count of each query's words
+  u32* n_tok = nullptr;      // [E]
+  u64* tok_off = nullptr;    // [E + 1]
+  u64* run_off = nullptr;    // [kSearchMaxQueries + 1]
+  u64* words = nullptr;      // [kSearchMaxQueries] tally_words
+  u64* tokens = nullptr;     // [kSearchMaxQueries] tally_tokens
+  u64* out_off = nullptr;    // [kSearchMaxQueries + 1]
+  u64 cap_entries = 0;
+  u64* pairs = nullptr;      // [cap_pairs] the pair words; behind the first sort: the rank keys
+  u64* zeros = nullptr;      // [cap_pairs] zero: key words 1..3 of the sorts
+  u64* sorted = nullptr;     // [cap_pairs] the sorted pair words; behind the runs: the rank keys
+  u64* spare = nullptr;      // [cap_pairs]
+  OutRecord* out = nullptr;  // [cap_out] the winners' records
+  RadixWorkspace rx{};
+  u64 cap_pairs = 0, cap_out = 0;
+};
+u64 tally_entry_bytes(u64 entries);
+void tally_entry_carve(char* base, u64 entries, TallyBuffers* tb);
+u64 tally_pair_bytes(u64 pairs, u64 out);
+// Carves `base` (tally_pair_bytes(...) bytes, 256-B aligned).  The caller zeroes tb->zeros once.
+void tally_pair_carve(char* base, u64 pairs, u64 out, TallyBuffers* tb);
+// measure + scan over the `entries` lines at `lines`.  tb.ctr->tokens is complete when `s` has
+// drained.
+void launch_tally_measure(const SearchIndex& ix, const u32* lines, u64 entries,
+                          const TallyBuffers& tb, hipStream_t s);
+// map + seal + order + runs over the `tokens` pair words the measure pass reported (tokens <=
+// tb.cap_pairs; offsets: [queries + 1], the entries' per-query segments).  tb.ctr and tb.q_words
+// are complete when `s` has drained.  More than kSmallSortMax pair words read the sort's plan
+// back through h_plan and synchronise `s` once, as radix_sort does.
+void launch_tally_map(const SearchIndex& ix, u32 queries, const u32* lines, const u64* offsets,
+                      u64 entries, u64 tokens, const TallyKeySplit& ks, TallyBuffers& tb,
+                      SortPlan* h_plan, hipStream_t s);
+// order + offsets + top over the `runs` rank keys the runs kernel wrote (runs <= tb.cap_pairs):
+// tb.words, tb.tokens, tb.out_off, tb.out[0 .. out_off[queries]) and tb.ctr->misplaced.
+// Synchronises as launch_tally_map does.
+void launch_tally_top(const SearchIndex& ix, u32 queries, const u64* offsets, u64 runs, u32 k,
+                      const TallyKeySplit& ks, TallyBuffers& tb, SortPlan* h_plan, hipStream_t s);
+
 // ---------------- fuzzy.hip ----------------
 // The kernels of a batch that has a fuzzy term (engine.hpp "fuzzy terms"; SearchBatch::fuzzy):
 // the bodies search.hip and show.hip instantiate (device/dictscan.hpp, device/verify.hpp,
@@ -1141,6 +1239,7 @@ void warm_module_search();  // (as index: the code object only, no buffers)
 void warm_module_show();  // (as search: the code object only, no buffers)
 void warm_module_shuffle();
 void warm_module_signal();
+void warm_module_tally();  // (as show: the code object only, no buffers)
 void warm_module_tokenize();
 // The selection's code object is loaded with the others (every kernel file is: a first top
 // job does no one-time loading either, tests/test_cold_path.py); its workspace and pinned
@@ -1164,6 +1263,7 @@ inline void warm_kernel_modules() {
   warm_module_show();
   warm_module_shuffle();
   warm_module_signal();
+  warm_module_tally();
   warm_module_tokenize();
   warm_module_topk();
 }

@@ -103,7 +103,8 @@ struct PyIndexResult {
                         const std::vector<int>& any, const py::object& rank, bool wildcard,
                         const std::vector<u64>& within,
                         const std::vector<std::vector<std::string>>& exclude, bool glob,
-                        bool ignore_case, const py::object& show, bool fuzzy, bool regex) const;
+                        bool ignore_case, const py::object& show, bool fuzzy, bool regex,
+                        const py::object& tally) const;
   py::list entries() const { return PyResult{x.words}.entries(); }
   py::list postings() const {
     py::list out;
@@ -194,6 +195,7 @@ struct PySearchResult {
     d["index_ms"] = r.index_ms;
     d["search_ms"] = r.search_ms;
     d["show_ms"] = r.show_ms;
+    d["tally_ms"] = r.tally_ms;
     return d;
   }
   py::bytes format(bool mark) const {
@@ -208,6 +210,25 @@ struct PySearchResult {
     if (r.show_bytes)
       for (u64 j = r.offsets[i]; j < r.offsets[i + 1]; ++j)
         out.append(py::bytes(r.text.data() + r.text_off[j], r.text_off[j + 1] - r.text_off[j]));
+    return out;
+  }
+  // tally: query i's words, [(key bytes, count)], count descending, key ascending
+  py::list tally(size_t i) const {
+    check(i);
+    py::list out;
+    if (r.tally_k)
+      for (u64 j = r.tally_off[i]; j < r.tally_off[i + 1]; ++j)
+        out.append(py::make_tuple(py::bytes(key_to_string(r.tally_keys[j])), r.tally_counts[j]));
+    return out;
+  }
+  py::list tally_words() const {
+    py::list out;
+    for (const u64 w : r.tally_words) out.append(w);
+    return out;
+  }
+  py::list tally_tokens() const {
+    py::list out;
+    for (const u64 w : r.tally_tokens) out.append(w);
     return out;
   }
   py::list text_off() const {
@@ -309,17 +330,33 @@ u64 to_show(const py::object& show) {
   return (u64)n;
 }
 
+// tally: None or 0 (no tally), or K -> the engines' tally.
+u64 to_tally(const py::object& tally) {
+  if (tally.is_none()) return 0;
+  long long n = -1;
+  try {
+    n = tally.cast<long long>();
+  } catch (const py::cast_error&) {  // (not an integer, or one past 64 bits)
+  }
+  LOCUST_CHECK_ARG(n >= 0 && n <= (long long)kTopKMax,
+                   "search: tally takes None or 1 <= K <= kTopKMax = " + std::to_string(kTopKMax) +
+                       ", not " + py::str(tally).cast<std::string>());
+  return (u64)n;
+}
+
 PySearchResult PyIndexResult::search(const std::vector<std::vector<std::string>>& queries,
                                      const std::vector<int>& any, const py::object& rank,
                                      bool wildcard, const std::vector<u64>& within,
                                      const std::vector<std::vector<std::string>>& exclude, bool glob,
-                        bool ignore_case, const py::object& show, bool fuzzy, bool regex) const {
+                        bool ignore_case, const py::object& show, bool fuzzy, bool regex,
+                        const py::object& tally) const {
   const std::vector<SearchQuery> q =
       to_queries(cfg, queries, any, wildcard, within, exclude, glob, fuzzy, regex);
   const u64 k = to_rank(rank);
   const u64 n = to_show(show);
+  const u64 tk = to_tally(tally);
   py::gil_scoped_release nogil;
-  return PySearchResult{search_index(x, q, cfg, k, ignore_case, n)};
+  return PySearchResult{search_index(x, q, cfg, k, ignore_case, n, tk)};
 }
 
 TextInput as_input(const std::string& text, u64 first_line = 0) {
@@ -465,13 +502,15 @@ class PyGpuEngine {
                             const py::object& rank, bool wildcard,
                             const std::vector<u64>& within,
                             const std::vector<std::vector<std::string>>& exclude, bool glob,
-                        bool ignore_case, const py::object& show, bool fuzzy, bool regex) {
+                        bool ignore_case, const py::object& show, bool fuzzy, bool regex,
+                        const py::object& tally) {
     const std::vector<SearchQuery> q =
         to_queries(eng_.config(), queries, any, wildcard, within, exclude, glob, fuzzy, regex);
     const u64 k = to_rank(rank);
     const u64 n = to_show(show);
+    const u64 tk = to_tally(tally);
     py::gil_scoped_release nogil;
-    return PySearchResult{eng_.run_search(as_input(text, first_line), q, k, ignore_case, n)};
+    return PySearchResult{eng_.run_search(as_input(text, first_line), q, k, ignore_case, n, tk)};
   }
   PySearchResult run_search_text(const HostText& t,
                                  const std::vector<std::vector<std::string>>& queries,
@@ -479,25 +518,29 @@ class PyGpuEngine {
                                  const py::object& rank, bool wildcard,
                             const std::vector<u64>& within,
                             const std::vector<std::vector<std::string>>& exclude, bool glob,
-                        bool ignore_case, const py::object& show, bool fuzzy, bool regex) {
+                        bool ignore_case, const py::object& show, bool fuzzy, bool regex,
+                        const py::object& tally) {
     const std::vector<SearchQuery> q =
         to_queries(eng_.config(), queries, any, wildcard, within, exclude, glob, fuzzy, regex);
     const u64 k = to_rank(rank);
     const u64 n = to_show(show);
+    const u64 tk = to_tally(tally);
     py::gil_scoped_release nogil;
-    return PySearchResult{eng_.run_search(t.input(first_line), q, k, ignore_case, n)};
+    return PySearchResult{eng_.run_search(t.input(first_line), q, k, ignore_case, n, tk)};
   }
   PySearchResult search_resident(const std::vector<std::vector<std::string>>& queries,
                                  const std::vector<int>& any, const py::object& rank,
                                  bool wildcard, const std::vector<u64>& within,
                                  const std::vector<std::vector<std::string>>& exclude, bool glob,
-                        bool ignore_case, const py::object& show, bool fuzzy, bool regex) {
+                        bool ignore_case, const py::object& show, bool fuzzy, bool regex,
+                        const py::object& tally) {
     const std::vector<SearchQuery> q =
         to_queries(eng_.config(), queries, any, wildcard, within, exclude, glob, fuzzy, regex);
     const u64 k = to_rank(rank);
     const u64 n = to_show(show);
+    const u64 tk = to_tally(tally);
     py::gil_scoped_release nogil;
-    return PySearchResult{eng_.search_resident(q, k, ignore_case, n)};
+    return PySearchResult{eng_.search_resident(q, k, ignore_case, n, tk)};
   }
   // records: (key bytes, count), sorted by key with distinct keys -- the kernels alone.
   PyTopResult top_counts(const std::vector<std::pair<std::string, u64>>& records, u32 k) {
@@ -1044,7 +1087,7 @@ PYBIND11_MODULE(_locust, m) {
            py::arg("within") = std::vector<u64>(),
            py::arg("exclude") = std::vector<std::vector<std::string>>(),
            py::arg("glob") = false, py::arg("ignore_case") = false, py::arg("show") = py::none(),
-           py::arg("fuzzy") = false, py::arg("regex") = false,
+           py::arg("fuzzy") = false, py::arg("regex") = false, py::arg("tally") = py::none(),
            "The host evaluation of all/any queries (any[i]: query i's mode) over this index.")
       .def("times", &PyIndexResult::times)
       .def("format", &PyIndexResult::format)
@@ -1083,6 +1126,17 @@ PYBIND11_MODULE(_locust, m) {
       .def_property_readonly("show_bytes", [](const PySearchResult& p) { return p.r.show_bytes; },
                              "the batch's N; 0: no show")
       .def_property_readonly("show_ms", [](const PySearchResult& p) { return p.r.show_ms; })
+      .def("tally", &PySearchResult::tally, py::arg("i"),
+           "tally: query i's most frequent words, [(key bytes, count)]; without tally: empty")
+      .def("tally_words", &PySearchResult::tally_words,
+           "tally: per query the words with count > 0 on its returned lines")
+      .def("tally_tokens", &PySearchResult::tally_tokens,
+           "tally: per query the emitted tokens of its returned lines")
+      .def_property_readonly("tally_k", [](const PySearchResult& p) { return p.r.tally_k; },
+                             "the batch's K; 0: no tally")
+      .def_property_readonly("tally_ms", [](const PySearchResult& p) { return p.r.tally_ms; })
+      .def_property_readonly("tallied", [](const PySearchResult& p) { return p.r.tallied; },
+                             "tally: pair words the device stage sorted (0: the host evaluation)")
       .def_property_readonly("cut_lines", [](const PySearchResult& p) { return p.r.cut_lines; },
                              "show: entries whose line was longer than N")
       .def_property_readonly("span_count",
@@ -1151,20 +1205,20 @@ PYBIND11_MODULE(_locust, m) {
            py::arg("wildcard") = false, py::arg("within") = std::vector<u64>(),
            py::arg("exclude") = std::vector<std::vector<std::string>>(),
            py::arg("glob") = false, py::arg("ignore_case") = false, py::arg("show") = py::none(),
-           py::arg("fuzzy") = false, py::arg("regex") = false,
+           py::arg("fuzzy") = false, py::arg("regex") = false, py::arg("tally") = py::none(),
            "WordCount of text, its index, and all/any queries answered on the device.")
       .def("run_search_text", &PyGpuEngine::run_search_text, py::arg("text"), py::arg("queries"),
            py::arg("any"), py::arg("first_line") = 0, py::arg("rank") = py::none(),
            py::arg("wildcard") = false, py::arg("within") = std::vector<u64>(),
            py::arg("exclude") = std::vector<std::vector<std::string>>(),
            py::arg("glob") = false, py::arg("ignore_case") = false, py::arg("show") = py::none(),
-           py::arg("fuzzy") = false, py::arg("regex") = false)
+           py::arg("fuzzy") = false, py::arg("regex") = false, py::arg("tally") = py::none())
       .def("search_resident", &PyGpuEngine::search_resident, py::arg("queries"), py::arg("any"),
            py::arg("rank") = py::none(), py::arg("wildcard") = false,
            py::arg("within") = std::vector<u64>(),
            py::arg("exclude") = std::vector<std::vector<std::string>>(),
            py::arg("glob") = false, py::arg("ignore_case") = false, py::arg("show") = py::none(),
-           py::arg("fuzzy") = false, py::arg("regex") = false,
+           py::arg("fuzzy") = false, py::arg("regex") = false, py::arg("tally") = py::none(),
            "Another batch from the index the last run_index / run_search left on the device.")
       .def("top_counts", &PyGpuEngine::top_counts, py::arg("records"), py::arg("k"),
            "The selection kernels alone over key-sorted (key, count) records.")
@@ -1188,17 +1242,19 @@ PYBIND11_MODULE(_locust, m) {
                              const py::object& rank, bool wildcard,
                              const std::vector<u64>& within,
                              const std::vector<std::vector<std::string>>& exclude, bool glob,
-                        bool ignore_case, const py::object& show, bool fuzzy, bool regex) {
+                        bool ignore_case, const py::object& show, bool fuzzy, bool regex,
+                        const py::object& tally) {
     CpuWordCount eng(cfg);
     return PySearchResult{eng.run_search(as_input(text, first_line),
                                          to_queries(cfg, queries, any, wildcard, within, exclude, glob, fuzzy, regex),
-                                         to_rank(rank), ignore_case, to_show(show))};
+                                         to_rank(rank), ignore_case, to_show(show),
+                                         to_tally(tally))};
   }, py::arg("cfg"), py::arg("text"), py::arg("queries"), py::arg("any"),
         py::arg("first_line") = 0, py::arg("rank") = py::none(), py::arg("wildcard") = false,
         py::arg("within") = std::vector<u64>(),
            py::arg("exclude") = std::vector<std::vector<std::string>>(),
            py::arg("glob") = false, py::arg("ignore_case") = false, py::arg("show") = py::none(),
-           py::arg("fuzzy") = false, py::arg("regex") = false);
+           py::arg("fuzzy") = false, py::arg("regex") = false, py::arg("tally") = py::none());
   m.def("make_search_expr", [](const JobConfig& cfg, const std::string& expr, bool wildcard,
                                bool glob, bool fuzzy, bool regex) {
     // engine.hpp "boolean expressions": the parsed query's parts (tests, tools)
@@ -1270,6 +1326,36 @@ PYBIND11_MODULE(_locust, m) {
     validate_search(r);
   }, py::arg("terms"), py::arg("lines"), py::arg("text_lens"), py::arg("spans"),
         py::arg("span_off"), py::arg("show"));
+  m.def("check_search_tally", &check_search_tally, py::arg("tally"),
+        "Throws unless tally is 0 or 1 <= K <= kTopKMax.");
+  m.def("tally_key_split", [](u64 n, u64 tokens) {
+    const TallyKeySplit ks = tally_key_split(n, tokens);
+    return py::make_tuple(ks.r, ks.c, ks.cmask);
+  }, py::arg("n"), py::arg("tokens"),
+        "The tally's rank-key split (r, c, cmask) for n index words and `tokens` pair words; "
+        "throws when tokens >= 2^32 or c + r > 54.");
+  m.def("validate_tally", [](const std::vector<std::string>& terms, const std::vector<u32>& lines,
+                             u64 k, const std::vector<std::pair<std::string, u64>>& words,
+                             u64 tally_words, u64 tally_tokens) {
+    // validate_search over a one-query unranked result with these tallied words (tests)
+    SearchResult r;
+    r.queries.push_back(make_search_query(terms, SearchMode::kAny, false));
+    r.lines = lines;
+    r.offsets = {0, lines.size()};
+    r.matches = {lines.size()};
+    r.num_lines = lines.empty() ? 0 : (u64)lines.back() + 1;
+    r.term_counts.assign(kSearchMaxTerms, 0);
+    r.tally_k = k;
+    for (const auto& w : words) {
+      r.tally_keys.push_back(to_key(w.first));
+      r.tally_counts.push_back(w.second);
+    }
+    r.tally_off = {0, words.size()};
+    r.tally_words = {tally_words};
+    r.tally_tokens = {tally_tokens};
+    validate_search(r);
+  }, py::arg("terms"), py::arg("lines"), py::arg("k"), py::arg("words"), py::arg("tally_words"),
+        py::arg("tally_tokens"));
   m.def("check_search_merge", &check_search_merge, py::arg("queries"), py::arg("elements"),
         "Throws when a device batch's prefix terms would merge 2^32 list elements or more.");
   m.def("cpu_map_stage", [](const JobConfig& cfg, const std::string& text) {

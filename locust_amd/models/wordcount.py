@@ -82,17 +82,19 @@ def _search_args(queries, mode, within=None, exclude=None):
 
 
 def _index_search(self, queries, mode="all", rank=None, wildcard=False, within=None,
-                  exclude=None, glob=False, ignore_case=False, show=None, fuzzy=False, regex=False):
+                  exclude=None, glob=False, ignore_case=False, show=None, fuzzy=False, regex=False,
+                  tally=None):
     """All/any word queries over this index, evaluated on the host (``SearchResult``):
     ``queries``, ``mode``, ``rank``, ``within`` and ``exclude`` as ``Engine.run_search`` takes
     them, any number of queries.  A ``"phrase"`` query, and a ``"near"`` query of two or more
     positive terms, is refused: the index holds no positions, so they need the text
     (``Engine.run_search``, ``search_text``).  ``glob``, ``fuzzy`` and ``ignore_case`` as
     there.
-    ``show=N`` is refused like a phrase: the shown lines come from the text."""
+    ``show=N`` is refused like a phrase: the shown lines come from the text.
+    ``tally=K`` is answered here too (``Engine.run_search``): the rule needs no text."""
     queries, flags, windows, exclude = _search_args(queries, mode, within, exclude)
     return self._search(queries, flags, rank, bool(wildcard), windows, exclude, bool(glob),
-                        bool(ignore_case), show, bool(fuzzy), bool(regex))
+                        bool(ignore_case), show, bool(fuzzy), bool(regex), tally)
 
 
 _C.IndexResult.search = _index_search
@@ -136,7 +138,7 @@ class Engine:
 
     def run_search(self, text: bytes, queries, mode="all", first_line: int = 0, rank=None,
                    wildcard=False, within=None, exclude=None, glob=False, ignore_case=False,
-                   show=None, fuzzy=False, regex=False):
+                   show=None, fuzzy=False, regex=False, tally=None):
         """WordCount of ``text``, its inverted index, and a batch of word queries answered
         from it (``SearchResult``).  ``queries`` is a list of term lists (1 to 8 byte-string
         terms each); ``mode`` is ``"all"`` (lines that hold every term), ``"any"`` (lines
@@ -226,29 +228,41 @@ class Engine:
         ``j`` of ``mask`` set when the token matches term ``j``; ``cut_lines`` counts the lines
         longer than ``N`` and ``format(mark=True)`` prints the lines with the spans between
         ``>>`` and ``<<``.  On the GPU the lines and spans are gathered on the device from the
-        resident text (``show_ms``), and only they cross PCIe."""
+        resident text (``show_ms``), and only they cross PCIe.
+
+        ``tally=K`` (``1 <= K <= 4096``; ``None`` or ``0``: no tally) also counts, for every
+        query, the index's words over the lines it returns -- ranked: its winners -- however
+        they were found (``oracle.TALLY_RULES`` states the rules): ``tally(i)`` is query
+        ``i``'s ``K`` most frequent words as ``[(key, count)]``, count descending and key
+        ascending; ``tally_words()`` and ``tally_tokens()`` give per query the distinct words
+        and the tokens of those lines.  Keys are counted as the index holds them (``To`` and
+        ``to`` apart, under ``ignore_case`` too).  On the GPU the returned lines are tokenised,
+        sorted and counted on the device (``tally_ms``; ``tallied`` pair words), and only the
+        winners cross PCIe."""
         queries, flags, windows, exclude = _search_args(queries, mode, within, exclude)
         if self.cpu:
             return _C.cpu_run_search(self.cfg, text, queries, flags, first_line, rank,
                                      bool(wildcard), windows, exclude, bool(glob),
-                                     bool(ignore_case), show, bool(fuzzy), bool(regex))
+                                     bool(ignore_case), show, bool(fuzzy), bool(regex), tally)
         return self._eng.run_search(text, queries, flags, first_line, rank, bool(wildcard),
                                     windows, exclude, bool(glob), bool(ignore_case), show,
-                                    bool(fuzzy), bool(regex))
+                                    bool(fuzzy), bool(regex), tally)
 
     def search_resident(self, queries, mode="all", rank=None, wildcard=False, within=None,
-                        exclude=None, glob=False, ignore_case=False, show=None, fuzzy=False, regex=False):
+                        exclude=None, glob=False, ignore_case=False, show=None, fuzzy=False,
+                        regex=False, tally=None):
         """Another batch from the index this engine's last job left on the device; that
         job must have been a ``run_index`` or a ``run_search`` (GPU engines only).  Every
         mode of ``run_search``: the job's text is resident too, so phrases and near queries
-        are answered.  ``rank``, ``within``, ``exclude``, ``glob``, ``ignore_case``, ``show`` and
-        ``fuzzy`` as ``run_search`` takes them."""
+        are answered.  ``rank``, ``within``, ``exclude``, ``glob``, ``ignore_case``, ``show``,
+        ``fuzzy`` and ``tally`` as ``run_search`` takes them."""
         if self.cpu:
             raise _C.LocustError("search_resident needs a GPU engine: the CPU engine keeps "
                                  "no index (use run_index(text).search(...))")
         queries, flags, windows, exclude = _search_args(queries, mode, within, exclude)
         return self._eng.search_resident(queries, flags, rank, bool(wildcard), windows, exclude,
-                                         bool(glob), bool(ignore_case), show, bool(fuzzy), bool(regex))
+                                         bool(glob), bool(ignore_case), show, bool(fuzzy),
+                                         bool(regex), tally)
 
     def top_counts(self, records: list[tuple[bytes, int]], k: int):
         """The selection alone over (key, count) records sorted by key with distinct
@@ -350,26 +364,28 @@ def index_file(path: str, line_start: int = -1, line_end: int = -1, backend: str
 
 def search_text(text: bytes, queries, mode="all", backend: str = "gpu", cfg=None,
                 first_line: int = 0, rank=None, wildcard=False, within=None, exclude=None,
-                glob=False, ignore_case=False, show=None, fuzzy=False, regex=False, **kw):
+                glob=False, ignore_case=False, show=None, fuzzy=False, regex=False, tally=None,
+                **kw):
     """All/any/phrase/near word queries over ``text`` (``SearchResult``); see
     ``Engine.run_search``."""
     cfg = cfg if cfg is not None else make_config(backend, **kw)
     nlines = text.count(b"\n") + (1 if text and not text.endswith(b"\n") else 0)
     return Engine(cfg, max(len(text), 1), max(nlines, 1)).run_search(
         text, queries, mode, first_line, rank, wildcard, within, exclude, glob, ignore_case,
-        show, fuzzy, regex)
+        show, fuzzy, regex, tally)
 
 
 def search_file(path: str, queries, mode="all", line_start: int = -1, line_end: int = -1,
                 backend: str = "gpu", cfg=None, rank=None, wildcard=False, within=None,
-                exclude=None, glob=False, ignore_case=False, show=None, fuzzy=False, regex=False, **kw):
+                exclude=None, glob=False, ignore_case=False, show=None, fuzzy=False, regex=False,
+                tally=None, **kw):
     """All/any/phrase/near word queries over a file or its line window, answered with the file's
     own (global) line numbers."""
     cfg = cfg if cfg is not None else make_config(backend, **kw)
     text, nlines, first, _total = _C.load_lines(path, line_start, line_end, cfg.ref_compat)
     return Engine(cfg, max(len(text), 1), max(nlines, 1)).run_search(
         text, queries, mode, first, rank, wildcard, within, exclude, glob, ignore_case, show,
-        fuzzy, regex)
+        fuzzy, regex, tally)
 
 
 def map_stage(path: str, spill: str, line_start: int = -1, line_end: int = -1,

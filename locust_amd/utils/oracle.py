@@ -1124,18 +1124,77 @@ def _query_text(queries, exclude):
             for q, x in zip(queries, exclude)]
 
 
-def format_search(queries, answers, *, exclude=None) -> bytes:
+TALLY_MAX_K = 4096
+
+TALLY_RULES = """
+    Tally (``tally=K``): the most frequent words of the lines a query returns.
+
+    - ``K`` is an integer with 1 <= K <= 4096 (``ValueError`` otherwise), and a tally goes with
+      a search only.
+    - The returned lines of a query are the entries ``show`` would print: unranked, every
+      matching line; ranked, the ``min(rank, matches)`` winners.  A line returned for two queries
+      counts for each.
+    - ``count(q, w)`` is the number of postings of index word ``w`` on a returned line of ``q``:
+      what the word job would count over those lines alone, with its delimiters, its emit cap
+      (a token past it does not exist) and its key cut (long tokens that merge under the cut
+      count as the merged key).  A word twice on a line counts twice.
+    - How the lines were found changes nothing: mode, window, exclusion, prefix, pattern, fuzzy
+      and regex terms and ``ignore_case`` select lines only.  Keys are the index's own bytes, so
+      ``To`` and ``to`` are two words under ``ignore_case`` too; the query's words count like any.
+    - Per query: ``words`` = the words with a count above 0, ``tokens`` = the sum of the counts,
+      and the first ``min(K, words)`` words by (count descending, key ascending in unsigned-byte
+      order) -- ``top``'s order -- each as ``(key, count)``.  No word with count 0 is returned; a
+      query without a returned line has ``(0, 0, [])``.
+"""
+
+
+def tally(entries, postings, lines, k: int):
+    """One query's tally over an index (``TALLY_RULES``): ``(words, tokens, top)`` for the
+    returned ``lines`` (global numbers, any order, each once).  The index is turned round --
+    per line the keys of its postings -- and the returned lines' keys are counted."""
+    if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= TALLY_MAX_K:
+        raise ValueError("tally takes 1 <= K <= %d, not %r" % (TALLY_MAX_K, k))
+    on_line = {}
+    for key, val, count in entries:
+        for l in postings[val:val + count]:
+            on_line.setdefault(l, []).append(key)
+    counts = {}
+    for l in lines:
+        for key in on_line.get(l, ()):
+            counts[key] = counts.get(key, 0) + 1
+    ordered = sorted(counts.items(), key=lambda kc: (-kc[1], kc[0]))
+    return len(counts), sum(counts.values()), ordered[:k]
+
+
+def format_tally(words: int, tokens: int, top) -> bytes:
+    """One query's tally lines in the CLI's ``--search ... --tally K`` output, which stand under
+    its ``print query:`` line and its shown lines."""
+    return b"  words: %d \t tokens: %d\n" % (words, tokens) + b"".join(
+        b"  word: %s \t count: %d\n" % (key, c) for key, c in top)
+
+
+def _tally_lines(tallies, n):
+    if tallies is None:
+        return [b""] * n
+    if len(tallies) != n:
+        raise ValueError("tallies takes one (words, tokens, top) per query")
+    return [format_tally(*t) for t in tallies]
+
+
+def format_search(queries, answers, *, exclude=None, tallies=None) -> bytes:
     """The CLI's ``--search`` result lines: one per query, ``queries[i]`` its terms and
     ``answers[i]`` its lines (every line number after one space; none after "lines:" when
     the query has no hit).
 
     ``exclude``: one entry per query, ``None`` or its exclusion terms; a query with exclusion
     terms prints `` \t not: <terms joined by one space>`` between its text and ``hits:``
-    (terms as they were asked: a prefix term with its star)."""
+    (terms as they were asked: a prefix term with its star).
+    ``tallies``: one ``tally`` answer per query, printed under its line (``format_tally``)."""
     return b"".join(
         b"print query: %s \t hits: %d \t lines:%s\n"
-        % (q, len(a), b"".join(b" %d" % l for l in a))
-        for q, a in zip(_query_text(queries, exclude), answers))
+        % (q, len(a), b"".join(b" %d" % l for l in a)) + t
+        for q, a, t in zip(_query_text(queries, exclude), answers,
+                           _tally_lines(tallies, len(queries))))
 
 
 RANK_MAX_EMITS = 65536
@@ -1229,15 +1288,16 @@ def rank(entries, postings, lines, terms, k: int, max_key: int = 29, *,
     return [(line, score) for score, line in scored[:k]], len(lines)
 
 
-def format_ranked(queries, tops, matches, *, exclude=None) -> bytes:
+def format_ranked(queries, tops, matches, *, exclude=None, tallies=None) -> bytes:
     """The CLI's ``--search ... --rank K`` result lines: one per query, ``queries[i]`` its
     terms, ``tops[i]`` its ``(line, score)`` pairs and ``matches[i]`` its number of matching
-    lines (nothing after "top:" when nothing matched).  ``exclude`` as ``format_search``
-    takes it."""
+    lines (nothing after "top:" when nothing matched).  ``exclude`` and ``tallies`` as
+    ``format_search`` takes them."""
     return b"".join(
         b"print query: %s \t hits: %d \t top:%s\n"
-        % (q, m, b"".join(b" %d:%d" % (l, s) for l, s in t))
-        for q, t, m in zip(_query_text(queries, exclude), tops, matches))
+        % (q, m, b"".join(b" %d:%d" % (l, s) for l, s in t)) + ta
+        for q, t, m, ta in zip(_query_text(queries, exclude), tops, matches,
+                               _tally_lines(tallies, len(queries))))
 
 
 SHOW_MAX_BYTES = 65536

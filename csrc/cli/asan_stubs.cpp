@@ -29,6 +29,8 @@ SearchResult GpuWordCount::search_resident(const std::vector<SearchQuery>&, u64,
                                            u64) {
   no_gpu();
 }
+IndexAppend GpuWordCount::append_index(const TextInput&) { no_gpu(); }
+IndexResult GpuWordCount::index_resident() { no_gpu(); }
 char* GpuWordCount::input_buffer() { no_gpu(); }
 GpuWordCount::Stats GpuWordCount::stats() const { no_gpu(); }
 bool GpuWordCount::partition_map(std::vector<u64>*) { no_gpu(); }

@@ -35,6 +35,8 @@
 //   --show N (with --search: under each query's line, every returned line's first N bytes)
 //   --mark (with --show: the matching tokens of a shown line stand between >> and <<)
 //   --tally K (with --search: under each query's line, the K most frequent words of its lines)
+//   --block-kb N (with --index or --search: the index is built from line-aligned blocks of at
+//     most N KiB, the first indexed, the rest appended to the index in device memory)
 // and a synthetic-text generator (BASELINE configs "1M lines" / "10 GB"):
 //   MapReduce --gen FILE (--gen-lines N | --gen-bytes N) [--seed S] [--vocab V]
 #include <sys/stat.h>
@@ -117,6 +119,8 @@ struct CliArgs {
   u64 show = 0;       // --show N: the returned lines' first N bytes (0: line numbers only)
   bool mark = false;  // --mark: the shown lines' matching tokens between >> and <<
   u64 tally = 0;      // --tally K: the K most frequent words of every query's returned lines
+  bool block_given = false;
+  u64 block_kb = 0;   // --block-kb N: --index / --search build the index in blocks of N KiB
   std::string gen_out;  // generator mode
   GenSpec gen;
 };
@@ -232,6 +236,14 @@ void help() {
       "                             count and then by key, 1 <= K <= 4096; counted on the device.\n"
       "                             With every --match, --rank (the winners' words), --show,\n"
       "                             --not and both backends)\n"
+      "  --block-kb N               (--index, --search: the index is built block by block -- the\n"
+      "                             text is cut into blocks of whole lines of at most N KiB, N >= 1,\n"
+      "                             the first is indexed and every further one indexed alone and\n"
+      "                             merged into the index in device memory, so the engine is sized to\n"
+      "                             one block and the text need not fit one device pass, only device\n"
+      "                             memory.  The result lines are those of the run without it.  A line\n"
+      "                             longer than a block is refused.  With --backend cpu the blocks'\n"
+      "                             indexes are merged on the host.  Not with --chunk-mb)\n"
       "  --ignore-case              (--search: the ASCII letters of every word of every query,\n"
       "                             --not words too, match either case: \"to be\" finds \"To be\".\n"
       "                             Other bytes match only themselves.  With --glob, --wildcard and\n"
@@ -426,6 +438,14 @@ bool parse(int argc, char** argv, CliArgs* a) {
       a->cfg.ngram = (int)n;
     } else if (s == "--chunk-mb") {
       a->cfg.chunk_bytes = (u64)std::atoll(need("--chunk-mb").c_str()) << 20;
+    } else if (s == "--block-kb") {
+      const std::string v = need("--block-kb");
+      char* endp = nullptr;
+      const long long n = std::strtoll(v.c_str(), &endp, 10);
+      if (v.empty() || *endp || n < 1 || n > (1ll << 40))
+        throw Error("--block-kb N needs an integer N >= 1 (KiB per block)");
+      a->block_given = true;
+      a->block_kb = (u64)n;
     } else if (s == "--gen") {
       a->gen_out = need("--gen");
     } else if (s == "--gen-lines") {
@@ -497,6 +517,12 @@ bool parse(int argc, char** argv, CliArgs* a) {
                 "too (--top K is the same count over the whole text)");
   if (a->mark && !a->show)
     throw Error("--mark marks the matching tokens of the lines --show prints: give --show too");
+  if (a->block_given && !a->index && a->search_args.empty())
+    throw Error("--block-kb N builds the index of --index or --search block by block: give one of "
+                "them too");
+  if (a->block_given && a->cfg.chunk_bytes)
+    throw Error("--block-kb and --chunk-mb do not combine: --chunk-mb streams a word count, "
+                "--block-kb builds an index block by block");
   if (a->index && !a->search_args.empty())
     throw Error("--index and --search do not combine: --index prints the whole index, "
                 "--search the lines of its queries");
@@ -514,7 +540,8 @@ bool parse(int argc, char** argv, CliArgs* a) {
       throw Error(f + " runs on one GPU or the CPU: not with --gpus N > 1");
     if (a->cfg.chunk_bytes)
       throw Error(f + " takes one device pass: not with --chunk-mb (a streamed index is "
-                  "not built; use --backend cpu for larger inputs)");
+                  "not built; use --backend cpu for larger inputs, or --block-kb N to build "
+                  "the index block by block)");
     if (!a->export_kiv.empty()) throw Error(f + " and --export-kiv do not combine");
     if (a->cfg.ref_timers) throw Error(f + " and --ref-timers do not combine");
     if (a->cfg.backend == Backend::kGpu && a->cfg.sort_path == SortPath::kRadix)
@@ -728,10 +755,21 @@ void json_top(JsonOut& j, const CliArgs& a) {
 
 // --index: "index": true in the record, the postings' number, and where the device built
 // it its device time and the bytes it wrote to host memory for the result.
+// --block-kb: the blocks, the merges' device time (their sum) and the index store's size.
+u64 g_blocks = 0, g_store_bytes = 0;
+double g_append_ms = 0;
+void json_blocks(JsonOut& j, const CliArgs& a) {
+  if (!a.block_given) return;
+  j.u("blocks", g_blocks);
+  j.num("append_ms", g_append_ms);
+  j.u("index_store_bytes", g_store_bytes);
+}
+
 const IndexResult* g_index = nullptr;
 void json_index(JsonOut& j, const CliArgs& a) {
   if (!a.index) return;
   j.kv("index", "true");
+  json_blocks(j, a);
   if (g_index) {
     j.num("index_ms", g_index->index_ms);
     j.u("postings", g_index->postings.size());
@@ -746,6 +784,7 @@ const SearchResult* g_search = nullptr;
 void json_search(JsonOut& j, const CliArgs& a) {
   if (a.queries.empty()) return;
   j.kv("search", "true");
+  json_blocks(j, a);
   j.u("queries", a.queries.size());
   j.kv("regex", a.regex ? "true" : "false");
   if (g_search) {
@@ -1339,7 +1378,33 @@ int run(const CliArgs& a) {
     CpuWordCount eng(a.cfg);
     for (int i = 0; i < a.warmup; ++i) eng.run(text.input);
     for (int i = 0; i < a.iters; ++i) {
-      if (!a.queries.empty()) {
+      if (a.block_given) {
+        // per block an index of its own, joined on the host (merge_index); a search then runs
+        // over the merged index and the whole text
+        const u64 t0 = now_ns();
+        const std::vector<TextInput> blocks = split_blocks(text.input, a.block_kb << 10);
+        IndexResult x = eng.run_index(blocks[0]);
+        for (size_t b = 1; b < blocks.size(); ++b) {
+          const IndexResult y = eng.run_index(blocks[b]);
+          StageTimes tm = x.words.times;
+          tm.map_ms += y.words.times.map_ms;
+          tm.process_ms += y.words.times.process_ms;
+          tm.reduce_ms += y.words.times.reduce_ms;
+          x = merge_index(x, y);
+          x.words.times = tm;
+        }
+        g_blocks = blocks.size();
+        if (!a.queries.empty()) {
+          cpu_search = search_index(x, text.input, a.queries, a.cfg, a.rank, a.ignore_case,
+                                    a.show, a.tally);
+          r = search_stats(cpu_search);
+          r.times = x.words.times;
+        } else {
+          cpu_index = std::move(x);
+          r = cpu_index.words;
+        }
+        r.times.wall_ms = (now_ns() - t0) * 1e-6;
+      } else if (!a.queries.empty()) {
         cpu_search =
             eng.run_search(text.input, a.queries, a.rank, a.ignore_case, a.show, a.tally);
         r = search_stats(cpu_search);
@@ -1358,6 +1423,55 @@ int run(const CliArgs& a) {
     std::printf("CPU sorting %lld nanoseconds \n", ns(r.times.process_ms));
     std::printf("CPU reducing %lld nanoseconds \n", ns(r.times.reduce_ms));
   } else {
+    if (a.block_given) {
+      // the first block indexed, the rest appended on the device; the engine holds one block
+      const std::vector<TextInput> blocks = split_blocks(text.input, a.block_kb << 10);
+      u64 max_bytes = 1, max_lines = 1;
+      for (const TextInput& b : blocks) {
+        max_bytes = std::max(max_bytes, b.bytes);
+        max_lines = std::max(max_lines, b.num_lines);
+      }
+      GpuWordCount eng(a.cfg, max_bytes, max_lines);
+      IndexResult x;
+      SearchResult sr;
+      for (int i = 0; i < a.warmup + a.iters; ++i) {
+        const u64 t0 = now_ns();
+        StageTimes tm = eng.run_index(blocks[0]).words.times;
+        double index_ms = 0, append_ms = 0;
+        for (size_t b = 1; b < blocks.size(); ++b) {
+          const IndexAppend ap = eng.append_index(blocks[b]);
+          tm.h2d_ms += ap.times.h2d_ms;
+          tm.map_ms += ap.times.map_ms;
+          tm.process_ms += ap.times.process_ms;
+          tm.reduce_ms += ap.times.reduce_ms;
+          tm.gpu_ms += ap.times.gpu_ms;
+          index_ms += ap.index_ms;
+          append_ms += ap.append_ms;
+        }
+        if (!a.queries.empty()) {
+          sr = eng.search_resident(a.queries, a.rank, a.ignore_case, a.show, a.tally);
+          tm.gpu_ms += sr.times.gpu_ms;
+          sr.times = tm;
+          sr.index_ms = index_ms;
+          sr.times.wall_ms = (now_ns() - t0) * 1e-6;
+          if (i >= a.warmup) walls.push_back(sr.times.wall_ms);
+        } else {
+          x = eng.index_resident();
+          x.words.times = tm;
+          x.index_ms = index_ms;
+          x.words.times.wall_ms = (now_ns() - t0) * 1e-6;
+          if (i >= a.warmup) walls.push_back(x.words.times.wall_ms);
+        }
+        g_blocks = blocks.size();
+        g_append_ms = append_ms;
+        g_store_bytes = eng.stats().index_store_bytes;
+      }
+      if (!a.queries.empty())
+        print_gpu_result(a, search_stats(sr), walls, nullptr, nullptr, &sr);
+      else
+        print_gpu_result(a, x.words, walls, nullptr, &x);
+      return 0;
+    }
     GpuWordCount eng(a.cfg, text.input.bytes, text.input.num_lines);
     if (!a.queries.empty()) {  // the word job, the index stage and the search stage
       SearchResult sr;

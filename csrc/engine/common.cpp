@@ -376,6 +376,105 @@ void format_index_output(const IndexResult& r, std::string* out) {
   }
 }
 
+// ---- appending to the index: the host twin of kernels/append.hip (engine.hpp) ----
+IndexResult merge_index(const IndexResult& a, const IndexResult& b) {
+  LOCUST_CHECK_ARG(b.first_line == a.first_line + a.words.num_lines,
+                   "merge_index: the second index starts at line " + std::to_string(b.first_line) +
+                       ", the first one ends before line " +
+                       std::to_string(a.first_line + a.words.num_lines));
+  LOCUST_CHECK_ARG(b.first_line + b.words.num_lines <= (1ull << 32),
+                   "index: line numbers past 2^32 do not fit a u32 posting");
+  IndexResult c;
+  c.first_line = a.first_line;
+  WordCountResult& w = c.words;
+  w.num_lines = a.words.num_lines + b.words.num_lines;
+  w.num_tokens = a.words.num_tokens + b.words.num_tokens;
+  w.overflow_lines = a.words.overflow_lines + b.words.overflow_lines;
+  w.truncated = a.words.truncated + b.words.truncated;
+  w.max_key_len = std::max(a.words.max_key_len, b.words.max_key_len);
+  std::vector<WordCountEntry> e;
+  e.reserve(a.words.entries.size() + b.words.entries.size());
+  c.postings.reserve(a.postings.size() + b.postings.size());
+  auto ia = a.words.entries.begin(), ib = b.words.entries.begin();
+  const auto ea = a.words.entries.end(), eb = b.words.entries.end();
+  u64 at_a = 0, at_b = 0, misplaced = 0;
+  const auto take = [&](const IndexResult& x, u64* at, u64 count) {
+    if (*at + count > x.postings.size())
+      throw Error("merge_index: the counts of an index exceed its " +
+                  std::to_string(x.postings.size()) + " postings");
+    c.postings.insert(c.postings.end(), x.postings.begin() + (std::ptrdiff_t)*at,
+                      x.postings.begin() + (std::ptrdiff_t)(*at + count));
+    *at += count;
+  };
+  while (ia != ea || ib != eb) {
+    const int cmp = ia == ea ? 1 : ib == eb ? -1 : key_compare((*ia).key.w, (*ib).key.w);
+    WordCountEntry x = cmp <= 0 ? *ia : *ib;
+    if (!e.empty() && key_compare(e.back().key.w, x.key.w) >= 0) ++misplaced;  // key order
+    if (cmp <= 0) {
+      take(a, &at_a, x.count);
+      ++ia;
+    }
+    if (cmp >= 0) {
+      const u64 cb = (*ib).count;
+      take(b, &at_b, cb);
+      if (cmp == 0) x.count += cb;
+      ++ib;
+    }
+    e.push_back(x);
+  }
+  if (misplaced)
+    throw Error("merge_index: " + std::to_string(misplaced) +
+                " keys out of order: both indexes must hold their words in key order");
+  if (at_a != a.postings.size() || at_b != b.postings.size() ||
+      c.postings.size() != w.num_tokens)
+    throw Error("merge_index: " + std::to_string(c.postings.size()) + " postings moved, " +
+                std::to_string(w.num_tokens) + " tokens in the two indexes");
+  LOCUST_CHECK_ARG(e.size() < (1ull << 32) && w.num_tokens < (1ull << 32),
+                   "index: " + std::to_string(e.size()) + " words / " +
+                       std::to_string(w.num_tokens) +
+                       " tokens do not fit the 32-bit halves of a pair word");
+  w.entries = std::move(e);
+  w.num_unique = w.entries.size();
+  return c;
+}
+
+std::vector<TextInput> split_blocks(const TextInput& in, u64 block_bytes) {
+  LOCUST_CHECK_ARG(block_bytes > 0, "split_blocks: block_bytes must be > 0 (--block-kb N, N >= 1)");
+  LOCUST_CHECK_ARG(!in.source, "split_blocks takes a text held in memory, not a source");
+  std::vector<TextInput> out;
+  const char* p = in.data;
+  const char* end = in.data + in.bytes;
+  u64 line = in.first_line;
+  while (p < end) {
+    TextInput b;
+    b.data = p;
+    b.first_line = line;
+    while (p < end) {  // whole lines while they fit
+      const char* nl = static_cast<const char*>(memchr(p, '\n', (size_t)(end - p)));
+      const char* next = nl ? nl + 1 : end;
+      if ((u64)(next - b.data) > block_bytes) {
+        if (p == b.data)
+          throw Error("line " + std::to_string(line) + " holds " + std::to_string(next - p) +
+                      " bytes, more than a block of " + std::to_string(block_bytes) +
+                      " bytes: a block is whole lines (raise --block-kb)");
+        break;
+      }
+      p = next;
+      ++line;
+    }
+    b.bytes = (u64)(p - b.data);
+    b.num_lines = line - b.first_line;
+    out.push_back(b);
+  }
+  if (out.empty()) {  // an empty text is one empty block
+    TextInput b;
+    b.data = in.data;
+    b.first_line = in.first_line;
+    out.push_back(b);
+  }
+  return out;
+}
+
 // ---- index search: the host evaluation (engine.hpp) ----
 PackedKey search_term_key(const std::string& term, const JobConfig& cfg) {
   PackedKey k;

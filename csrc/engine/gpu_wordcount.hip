@@ -58,8 +58,11 @@ SearchResult GpuWordCount::search_resident(const std::vector<SearchQuery>& queri
                                            bool ignore_case, u64 show, u64 tally) {
   return impl_->search_resident(queries, rank_k, ignore_case, show, tally);
 }
+IndexAppend GpuWordCount::append_index(const TextInput& in) { return impl_->append_index(in); }
+IndexResult GpuWordCount::index_resident() { return impl_->index_resident(); }
 GpuWordCount::Stats GpuWordCount::stats() const {
   Stats s;
+  s.index_store_bytes = impl_->store_bytes();
   s.retunes = impl_->pm_retunes;
   s.fallbacks = impl_->fallbacks;
   s.planned_passes = impl_->planned_passes;

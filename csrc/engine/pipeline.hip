@@ -270,6 +270,7 @@ u64 DevicePipeline::device_bytes() const {
   b += index_bytes;                  // (0 until the first index job)
   b += sbatch_bytes + shits_bytes;   // (0 until the first search job)
   b += sbatch.merged_cap * sizeof(u32);  // (0 until a batch merges a prefix term's lists)
+  b += store_bytes();                    // (0 until the first append)
   return b;
 }
 
@@ -558,6 +559,12 @@ DevicePipeline::~DevicePipeline() {
   pinned_free(h_post);
   pinned_free(h_ictr);
   for (auto& e : ev_index)
+    if (e) (void)hipEventDestroy(e);
+  for (auto& h : store)
+    if (h.base) (void)hipFree(h.base);
+  if (d_append) (void)hipFree(d_append);
+  pinned_free(h_actr);
+  for (auto& e : ev_append)
     if (e) (void)hipEventDestroy(e);
   if (d_sbatch) (void)hipFree(d_sbatch);
   if (d_shits) (void)hipFree(d_shits);
@@ -2047,6 +2054,8 @@ void DevicePipeline::keep_index(const TextInput& in, const WordCountResult& r, u
   idx_view.max_key_len = cfg.max_key_len;
   idx_num_lines = in.num_lines;
   idx_tokens = T;
+  idx_in_store = false;  // (it lives in the pass buffers until an append moves it)
+  idx_ends_nl = in.bytes == 0 || in.data[in.bytes - 1] == '\n';
   idx_resident = true;
 }
 
@@ -2813,6 +2822,273 @@ SearchResult DevicePipeline::search_resident(const std::vector<SearchQuery>& que
   r.times.wall_ms = (now_ns() - t0) * 1e-6;
   if (cfg.check) validate_search(r);
   return r;
+}
+
+// =====================================================================================
+// Index store and append
+// =====================================================================================
+void DevicePipeline::ensure_store_half(int h, u64 recs, u64 posts, u64 text_bytes, u64 lines) {
+  IndexStoreHalf& st = store[h];
+  if (st.base && st.rec_cap >= recs && st.post_cap >= posts && st.text_cap >= text_bytes &&
+      st.line_cap >= lines)
+    return;
+  sync();  // nothing in flight may still use the half being replaced
+  if (st.base) LOCUST_HIP_CHECK(hipFree(st.base));
+  st = IndexStoreHalf{};
+  // half as much again as this merge needs: the destination is rewritten whole, so growing
+  // copies nothing, and a run of appends reallocates a half only every few merges
+  const auto grow = [](u64 need) { return std::max<u64>(need + need / 2, 1); };
+  const u64 rec_cap = grow(recs), post_cap = grow(posts), text_cap = grow(text_bytes),
+            line_cap = grow(lines);
+  u64 off[7];
+  u64 b = 0;
+  int k = 0;
+  for (const u64 part : {rec_cap * sizeof(OutRecord), (rec_cap + 1) * 8, post_cap * 4,
+                         text_cap + 16, (line_cap + 1) * 8, (u64)64}) {
+    b = align_up(b, 256);
+    off[k++] = b;
+    b += part;
+  }
+  const u64 bytes = align_up(b, 256);
+  size_t fr = 0, tot = 0;
+  LOCUST_HIP_CHECK(hipMemGetInfo(&fr, &tot));
+  if ((double)bytes > kHbmUsable * (double)fr)
+    throw Error("index store (" + std::to_string(bytes) + " B needed for " +
+                std::to_string(rec_cap) + " records, " + std::to_string(post_cap) +
+                " postings, " + std::to_string(text_cap) + " text bytes and " +
+                std::to_string(line_cap) + " lines) does not fit the free device memory (" +
+                std::to_string(fr) + " B free of " + std::to_string(tot) + " B)");
+  LOCUST_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&st.base), bytes));
+  st.bytes = bytes;
+  st.ix.recs = reinterpret_cast<OutRecord*>(st.base + off[0]);
+  st.ix.val = reinterpret_cast<u64*>(st.base + off[1]);
+  st.ix.postings = reinterpret_cast<u32*>(st.base + off[2]);
+  st.ix.text = st.base + off[3];
+  st.ix.nl_pos = reinterpret_cast<u64*>(st.base + off[4]);
+  st.ix.lctr = reinterpret_cast<MapCounters*>(st.base + off[5]);
+  st.rec_cap = rec_cap;
+  st.post_cap = post_cap;
+  st.text_cap = text_cap;
+  st.line_cap = line_cap;
+}
+
+void DevicePipeline::ensure_append_scratch(u64 recs_a, u64 recs_b) {
+  if (!h_actr) {
+    // first append of this engine: the pinned counters and the events
+    h_actr = static_cast<AppendCounters*>(
+        pinned_alloc(sizeof(AppendCounters), hipHostMallocDefault, "append counters"));
+    for (auto& e : ev_append) LOCUST_HIP_CHECK(hipEventCreate(&e));
+  }
+  if (d_append && append_ws.rec_cap_a >= recs_a && append_ws.rec_cap_b >= recs_b) return;
+  sync();
+  if (d_append) LOCUST_HIP_CHECK(hipFree(d_append));
+  d_append = nullptr;
+  append_ws = AppendScratch{};
+  append_bytes = 0;
+  const u64 cap_a = std::max<u64>(recs_a + recs_a / 2, 1), cap_b = std::max<u64>(recs_b + recs_b / 2, 1);
+  const u64 bytes = append_scratch_bytes(cap_a, cap_b);
+  size_t fr = 0, tot = 0;
+  LOCUST_HIP_CHECK(hipMemGetInfo(&fr, &tot));
+  if ((double)bytes > kHbmUsable * (double)fr)
+    throw Error("append scratch (" + std::to_string(bytes) + " B needed for " +
+                std::to_string(cap_a) + " + " + std::to_string(cap_b) +
+                " records) does not fit the free device memory (" + std::to_string(fr) +
+                " B free of " + std::to_string(tot) + " B)");
+  LOCUST_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&d_append), bytes));
+  append_bytes = bytes;
+  append_scratch_carve(d_append, cap_a, cap_b, &append_ws);
+}
+
+void DevicePipeline::ensure_line_index(u64 bytes, u64 n, u64 T) {
+  if (bytes == 0 || (n != 0 && T != 0)) return;  // launch_index built it (or there is no text)
+  LOCUST_HIP_CHECK(hipMemsetAsync(index.zero, 0, index.zero_bytes, stream));
+  launch_line_index(d_text, bytes, index.nl_pos, index.lctr, index.lb, stream);
+}
+
+AppendIndex DevicePipeline::resident_as_append() const {
+  AppendIndex a;
+  a.recs = const_cast<OutRecord*>(idx_view.recs);
+  a.val = const_cast<u64*>(idx_view.val);
+  a.postings = const_cast<u32*>(idx_view.postings);
+  a.text = const_cast<char*>(idx_view.text);
+  a.nl_pos = const_cast<u64*>(idx_view.nl_pos);
+  a.lctr = const_cast<MapCounters*>(idx_view.lctr);
+  a.n = idx_view.n;
+  a.tokens = idx_tokens;
+  a.bytes = idx_view.bytes;
+  a.lines = idx_num_lines;
+  return a;
+}
+
+IndexAppend DevicePipeline::append_index(const TextInput& in) {
+  TraceRange tr("locust:index_append");
+  // ---- refusals: nothing is enqueued, the resident index stays as it is ----
+  if (!idx_resident)
+    throw Error("append_index: the index on the device is stale -- this engine's last job "
+                "was not a run_index, a run_search or an append_index (any other job, a refused "
+                "one included, overwrites what the index reads); run one of them first");
+  const u64 next_line = (u64)idx_view.first_line + idx_num_lines;
+  LOCUST_CHECK_ARG(in.first_line == next_line,
+                   "append_index: the block starts at line " + std::to_string(in.first_line) +
+                       ", the resident index ends before line " + std::to_string(next_line));
+  LOCUST_CHECK_ARG(!in.source && in.bytes <= pass_bytes && in.num_lines <= cap_lines,
+                   "append_index: a block (" + std::to_string(in.bytes) + " B, " +
+                       std::to_string(in.num_lines) + " lines) is indexed in one device pass (" +
+                       std::to_string(pass_bytes) + " B, " + std::to_string(cap_lines) +
+                       " lines here): append smaller blocks");
+  check_index_job(in);
+  LOCUST_CHECK_ARG(idx_view.bytes == 0 || idx_ends_nl,
+                   "append_index: the resident text does not end in a newline -- the block's "
+                   "first line would continue its last one");
+  LOCUST_CHECK_ARG(next_line + in.num_lines <= (1ull << 32),
+                   "index: line numbers past 2^32 do not fit a u32 posting");
+  IndexAppend out;
+  const u64 t0 = now_ns();
+  if (!idx_in_store) {
+    // the resident index lives in the pass buffers, which the block's job overwrites: into a
+    // half first.  (A refusal of the allocation still leaves it where it was.)
+    const AppendIndex a = resident_as_append();
+    ensure_store_half(0, a.n, a.tokens, a.bytes, a.lines);
+    ensure_line_index(a.bytes, a.n, a.tokens);
+    AppendIndex& d = store[0].ix;
+    const auto d2d = [&](void* dst, const void* src, u64 bytes) {
+      if (bytes) LOCUST_HIP_CHECK(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, stream));
+    };
+    d2d(d.recs, a.recs, a.n * sizeof(OutRecord));
+    d2d(d.val, a.val, (a.n + 1) * 8);
+    d2d(d.postings, a.postings, a.tokens * 4);
+    d2d(d.text, a.text, a.bytes);
+    LOCUST_HIP_CHECK(hipMemsetAsync(d.text + a.bytes, 0, 16, stream));
+    d2d(d.nl_pos, a.nl_pos, std::min<u64>(a.lines, index.line_cap) * 8);
+    d2d(d.lctr, a.lctr, sizeof(MapCounters));
+    sync();
+    d.n = a.n;
+    d.tokens = a.tokens;
+    d.bytes = a.bytes;
+    d.lines = a.lines;
+    idx_view.recs = d.recs;
+    idx_view.val = d.val;
+    idx_view.postings = d.postings;
+    idx_view.text = d.text;
+    idx_view.nl_pos = d.nl_pos;
+    idx_view.lctr = d.lctr;
+    store_cur = 0;
+    idx_in_store = true;
+  }
+  // ---- the block's own index, in the pass buffers ----
+  idx_resident = false;  // (until the merged index stands: any failure from here leaves it stale)
+  WordCountResult w;
+  u64 nb = 0, tb = 0;
+  enqueue_index_job(in, w, /*ship_postings=*/false, &nb, &tb);
+  sync();
+  check_index_counters(nb, tb);
+  ensure_line_index(in.bytes, nb, tb);
+  const AppendIndex a = store[store_cur].ix;
+  LOCUST_CHECK_ARG(a.n + nb < (1ull << 32) && a.tokens + tb < (1ull << 32),
+                   "index: " + std::to_string(a.n + nb) + " words / " +
+                       std::to_string(a.tokens + tb) +
+                       " tokens do not fit the 32-bit halves of a pair word");
+  AppendIndex b;
+  b.recs = d_out;
+  b.val = index.val;
+  b.postings = index.postings;
+  b.text = d_text;
+  b.nl_pos = index.nl_pos;
+  b.lctr = index.lctr;
+  b.n = nb;
+  b.tokens = tb;
+  b.bytes = in.bytes;
+  b.lines = in.num_lines;
+  // ---- the merge, into the other half ----
+  const int dst = 1 - store_cur;
+  ensure_store_half(dst, a.n + nb, a.tokens + tb, a.bytes + b.bytes, a.lines + b.lines);
+  ensure_append_scratch(a.n, nb);
+  AppendIndex c = store[dst].ix;
+  c.n = store[dst].rec_cap;
+  c.tokens = store[dst].post_cap;
+  c.bytes = store[dst].text_cap + 16;
+  c.lines = store[dst].line_cap;
+  LOCUST_HIP_CHECK(hipEventRecord(ev_append[0], stream));
+  launch_append(a, b, c, append_ws, stream);
+  LOCUST_HIP_CHECK(hipMemcpyAsync(h_actr, append_ws.ctr, sizeof(AppendCounters),
+                                  hipMemcpyDeviceToHost, stream));
+  LOCUST_HIP_CHECK(hipEventRecord(ev_append[1], stream));
+  sync();
+  const AppendCounters ac = *h_actr;
+  if (ac.misplaced)
+    throw Error("append: " + std::to_string(ac.misplaced) +
+                " records or postings misplaced (a position outside the merged index, or keys "
+                "out of order)");
+  if (ac.moved != a.tokens + tb)
+    throw Error("append: " + std::to_string(ac.moved) + " postings moved, the two indexes hold " +
+                std::to_string(a.tokens + tb));
+  if (ac.fresh > nb || ac.records != a.n + ac.fresh)
+    throw Error("append: " + std::to_string(ac.records) + " records written, expected " +
+                std::to_string(a.n) + " + " + std::to_string(ac.fresh) + " fresh words");
+  // ---- the merged index is the resident one ----
+  AppendIndex& m = store[dst].ix;
+  m.n = a.n + ac.fresh;
+  m.tokens = a.tokens + tb;
+  m.bytes = a.bytes + b.bytes;
+  m.lines = a.lines + b.lines;
+  store_cur = dst;
+  idx_view.recs = m.recs;
+  idx_view.val = m.val;
+  idx_view.postings = m.postings;
+  idx_view.n = (u32)m.n;
+  idx_view.text = m.text;
+  idx_view.bytes = m.bytes;
+  idx_view.nl_pos = m.nl_pos;
+  idx_view.lctr = m.lctr;
+  idx_num_lines = m.lines;
+  idx_tokens = m.tokens;
+  idx_words.num_lines = m.lines;
+  idx_words.num_tokens = m.tokens;
+  idx_words.num_unique = m.n;
+  idx_words.overflow_lines += w.overflow_lines;
+  idx_words.truncated += w.truncated;
+  idx_words.max_key_len = std::max(idx_words.max_key_len, w.max_key_len);
+  if (in.bytes) idx_ends_nl = in.data[in.bytes - 1] == '\n';
+  idx_resident = true;
+  out.block_lines = in.num_lines;
+  out.block_tokens = tb;
+  out.block_unique = nb;
+  out.num_lines = m.lines;
+  out.num_tokens = m.tokens;
+  out.num_unique = m.n;
+  out.fresh_words = ac.fresh;
+  out.index_ms = ms_between(ev_index[0], ev_index[1]);
+  out.append_ms = ms_between(ev_append[0], ev_append[1]);
+  out.times.h2d_ms = ms_between(ev[0], ev[1]);
+  out.times.map_ms = ms_between(ev[1], ev[2]);
+  out.times.process_ms = ms_between(ev[2], ev[3]);
+  out.times.reduce_ms = ms_between(ev[3], ev[4]);
+  out.times.gpu_ms = ms_between(ev[0], ev_index[1]) + out.append_ms;
+  out.times.wall_ms = (now_ns() - t0) * 1e-6;
+  out.store_bytes = store_bytes();
+  return out;
+}
+
+IndexResult DevicePipeline::index_resident() {
+  if (!idx_resident)
+    throw Error("index_resident: the index on the device is stale -- this engine's last job "
+                "was not a run_index, a run_search or an append_index (any other job, a refused "
+                "one included, overwrites what the index reads); run one of them first");
+  IndexResult x;
+  x.first_line = idx_view.first_line;
+  x.words = idx_words;  // the statistics
+  const u64 n = idx_view.n, T = idx_tokens;
+  grow_host_out(n);
+  if (n) launch_copy_to_mapped(d_out_mapped, idx_view.recs, n * sizeof(OutRecord), stream);
+  x.postings.resize(T);
+  sync();
+  if (T)
+    LOCUST_HIP_CHECK(hipMemcpy(x.postings.data(), idx_view.postings, T * sizeof(u32),
+                               hipMemcpyDeviceToHost));
+  copy_out(x.words.entries, n);
+  x.wire_bytes = T * sizeof(u32) + n * sizeof(OutRecord);
+  if (cfg.check) validate_index(x);
+  return x;
 }
 
 bool DevicePipeline::host_pinned(const void* p) {

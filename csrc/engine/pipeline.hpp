@@ -858,6 +858,40 @@ struct DevicePipeline {
                           u64 rank_k, bool ignore_case, u64 show, u64 tally);
   SearchResult search_resident(const std::vector<SearchQuery>& queries, u64 rank_k,
                                bool ignore_case, u64 show, u64 tally);
+  // ---- index store and append (kernels/append.hip; engine.hpp "appending to the index") ----
+  // Two buffer sets ("halves") of the engine's own, apart from the pass buffers: a merge reads
+  // the resident index from one half and the block's index from the pass buffers (d_out,
+  // index.*, d_text), writes the other half whole, and the halves swap.  Before a merge the
+  // destination is reallocated when it is too small for the merged records, postings, text or
+  // line starts (half as much again as needed; checked against free HBM) -- nothing is copied
+  // to grow, the destination is rewritten whole.  The first append after a run_index /
+  // run_search finds the resident index in the pass buffers, which the block's job overwrites:
+  // it is moved into a half by device-to-device copies first.  The merge's scratch, the pinned
+  // counters and the events are made by the first append; a job that never appends allocates
+  // nothing here.
+  struct IndexStoreHalf {
+    char* base = nullptr;
+    u64 bytes = 0;
+    AppendIndex ix{};  // the arrays, and what they hold
+    u64 rec_cap = 0, post_cap = 0, text_cap = 0, line_cap = 0;
+  };
+  IndexStoreHalf store[2];
+  int store_cur = 0;          // the half idx_view points into, when idx_in_store
+  bool idx_in_store = false;  // false: the resident index lives in the pass buffers
+  bool idx_ends_nl = true;    // the resident text ends in '\n' (or is empty)
+  char* d_append = nullptr;
+  u64 append_bytes = 0;
+  AppendScratch append_ws{};
+  AppendCounters* h_actr = nullptr;  // pinned copy of the merge's counters
+  hipEvent_t ev_append[2] = {};
+  u64 store_bytes() const { return store[0].bytes + store[1].bytes + append_bytes; }
+  void ensure_store_half(int h, u64 recs, u64 posts, u64 text_bytes, u64 lines);
+  void ensure_append_scratch(u64 recs_a, u64 recs_b);
+  // launch_index builds no line index for a text without tokens: the merge needs one.
+  void ensure_line_index(u64 bytes, u64 n, u64 T);
+  AppendIndex resident_as_append() const;
+  IndexAppend append_index(const TextInput& in);
+  IndexResult index_resident();
   // ---- show (kernels/show.hip) ----
   // The stage's arrays are allocations of their own, made by the engine's first show batch and
   // grown on demand: the per-entry part (by the batch's entries), the payload's text and

@@ -44,6 +44,44 @@ __device__ __forceinline__ u32 find_rank(const OutRecord* __restrict__ recs, u32
   return n;
 }
 
+// The lower bound of key (w0..w3) among the n sorted, distinct records: the number of records
+// below it (append.hip); *equal: the record there holds the key.
+__device__ __forceinline__ u32 lower_rank(const OutRecord* __restrict__ recs, u32 n, u64 w0, u64 w1,
+                                          u64 w2, u64 w3, bool* equal) {
+  u32 lo = 0, hi = n;
+  while (lo < hi) {
+    const u32 mid = lo + ((hi - lo) >> 1);
+    const OutRecord* r = recs + mid;
+    bool less;  // recs[mid] < key
+    const u64 a0 = r->w[0];
+    if (a0 != w0) {
+      less = a0 < w0;
+    } else {
+      const u64 a1 = r->w[1];
+      if (a1 != w1) {
+        less = a1 < w1;
+      } else {
+        const u64 a2 = r->w[2];
+        if (a2 != w2) {
+          less = a2 < w2;
+        } else {
+          less = r->w[3] < w3;
+        }
+      }
+    }
+    if (less)
+      lo = mid + 1;
+    else
+      hi = mid;
+  }
+  *equal = false;
+  if (lo < n) {
+    const OutRecord* r = recs + lo;
+    *equal = r->w[0] == w0 && r->w[1] == w1 && r->w[2] == w2 && r->w[3] == w3;
+  }
+  return lo;
+}
+
 // The rank range [*lo, *hi) of the records whose key starts with the prefix p = the non-zero
 // bytes of (w0..w3) (a key holds no NUL before its padding): *lo is the lower bound of p
 // padded with 0x00, which is (w0..w3) itself, *hi the upper bound of p padded with 0xff to

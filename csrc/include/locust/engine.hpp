@@ -341,6 +341,41 @@ void validate_index(const IndexResult& r);
 //   "print key: <key> \t count: <count> \t lines: <l0> <l1> ...\n"
 void format_index_output(const IndexResult& r, std::string* out);
 
+// ---- appending to the index ----
+// An index may be built block by block.  After run_index(t0) (or run_search), then
+// append_index(t1), ..., append_index(tk), the index in device memory is exactly the index of
+// the text t0 + t1 + ... + tk with t0's first_line: the same records, postings, text and line
+// starts a single pass over the concatenation would have left, so every search answers the
+// same.  A block is whole lines numbered behind all resident lines, so for every word the
+// merged postings list is the resident list followed by the block's: the block is indexed by
+// the one-pass kernels, then merged with the resident index on the device (kernels/
+// append.hip), a linear pass.  The text need not fit one pass any more, only device memory.
+//  * Refused before anything is enqueued, the resident index intact and still searchable: no
+//    resident index or a stale one; a block whose first_line is not the resident first_line +
+//    lines; a block larger than the engine's pass; a resident text that is non-empty and does
+//    not end in '\n' (the concatenation would join two lines); line numbers past 2^32.
+//  * Any failure after the block's job has started leaves the index stale, merged totals of
+//    2^32 tokens or words included.
+//  * An empty block and an empty resident text are legal; the last block may lack its '\n'.
+// Only counters cross PCIe.
+struct IndexAppend {
+  u64 block_lines = 0, block_tokens = 0, block_unique = 0;  // the block's own index
+  u64 num_lines = 0, num_tokens = 0, num_unique = 0;        // the resident index after the merge
+  u64 fresh_words = 0;    // words of the block the resident index did not hold
+  double index_ms = 0;    // device time of the block's index stage
+  double append_ms = 0;   // device time of the merge
+  StageTimes times;       // the block's word job
+  u64 store_bytes = 0;    // device bytes of the index store (both halves and the merge's scratch)
+};
+// The host twin of the device merge: the index of a's text followed by b's, from the two
+// indexes alone, with the same checks (keys strictly ascending on either side, the counts
+// adding up to the postings).  Throws unless b.first_line == a.first_line + a.words.num_lines.
+IndexResult merge_index(const IndexResult& a, const IndexResult& b);
+// `in` cut into line-aligned blocks of at most block_bytes bytes, num_lines and first_line
+// filled in; every block but the last ends in '\n', and a text that fits is one block.  A
+// single line longer than block_bytes is an error (it names the CLI's --block-kb).
+std::vector<TextInput> split_blocks(const TextInput& in, u64 block_bytes);
+
 // ---- index search: all/any/phrase/near word queries over the inverted index ----
 // A query is 1 to kSearchMaxTerms terms and a mode.  A term is a non-empty byte string
 // without NUL, newline or a byte of the job's delimiter set; one longer than max_key_len is
@@ -1036,6 +1071,8 @@ class GpuWordCount {
     u64 chunk_bytes = 0, map_window = 0;
     // device bytes of the search stage's workspace (0 until the first search job)
     u64 search_bytes = 0;
+    // device bytes of the index store (0 until the first append_index)
+    u64 index_store_bytes = 0;
     // what the last Process stage of the reference algorithm (every token sorted) used:
     // "psort" (the partitioned LDS sort), "radix-host-plan" (the device-wide sort, live
     // passes launched from the plan read back) or "radix-device-plan" (every pass launched,
@@ -1110,6 +1147,13 @@ class GpuWordCount {
   // to write included) marks the index stale, and this then throws.
   SearchResult search_resident(const std::vector<SearchQuery>& queries, u64 rank_k = 0,
                                bool ignore_case = false, u64 show = 0, u64 tally = 0);
+  // One more block of whole lines into the resident index ("appending to the index" above):
+  // the block's word job and index stage, then the merge on the device into the engine's
+  // index store.  in.first_line must be the resident first_line + lines.
+  IndexAppend append_index(const TextInput& in);
+  // The resident index downloaded (entries, postings, statistics), whatever it was built from;
+  // throws as search_resident does when it is stale.
+  IndexResult index_resident();
 
   const JobConfig& config() const;
   u64 token_capacity() const;

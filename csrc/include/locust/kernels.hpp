@@ -621,6 +621,69 @@ struct IndexJob {
 // h_plan (pinned) and synchronises `s` once, as radix_sort does.
 void launch_index(const IndexJob& job, IndexWorkspace& ws, SortPlan* h_plan, hipStream_t s);
 
+// ---------------- append.hip ----------------
+// The merge of two indexes in device memory (engine.hpp "appending to the index"): A, the
+// resident one, and B, what launch_index just left for a block whose first line follows A's
+// last, so B's postings are global already.  C, in buffers of its own, is the index a single
+// pass over A's text followed by B's would have left.
+//
+// A sequence of kernels on `s`; data crosses between workgroups only at kernel boundaries, no
+// output array is written with atomics and every output word has exactly one writer:
+//   locate    one thread per record: a B record's lower bound among A's records (and whether
+//             its key is absent there: fresh), an A record's lower bound among B's
+//   scan      sB = exclusive scan of fresh (tile sums, one-workgroup scan of the tile array,
+//             per-tile scan); nC = nA + sB[nB]
+//   records   pos(A[i]) = i + sB[lbB[i]], pos(B[j]) = lbA[j] + sB[j].  The A thread writes the
+//             coalesced record (countA + countB when B holds the key), a B thread only a fresh
+//             key; both leave their record's position for the postings kernel
+//   offsets   valC = exclusive scan of C's counts (the same three kernels), valC[nC] = TA + TB
+//   postings  tiles of kAppendTile source elements, A's tiles then B's.  A tile finds the
+//             words its elements belong to by two binary searches in the source val, stages
+//             their source offsets and destination shifts in LDS, and every element then finds
+//             its word there: a list of any length is moved by as many workgroups as it has
+//             tiles, and each element moves exactly once
+//   lines     nl_posC = nl_posA ++ (nl_posB + bytesA), num_newlines = nlA + nlB
+// The text is two device-to-device copies and 16 zero bytes behind them.
+struct AppendCounters {  // one 64-byte readback, zeroed per append
+  u64 moved;      // postings moved
+  u32 records;    // records written to C
+  u32 fresh;      // words of B that A did not hold
+  u32 misplaced;  // a destination outside [valC[p], valC[p+1]), a record position >= nC, a
+                  // key order violation seen by the records kernel
+  u32 pad[11];
+};
+static_assert(sizeof(AppendCounters) == 64, "AppendCounters: one 64-byte readback");
+constexpr int kAppendBlock = 256;
+constexpr int kAppendItems = 4;
+constexpr int kAppendTile = kAppendBlock * kAppendItems;  // postings per workgroup
+// One side of a merge, or its destination (device memory).
+struct AppendIndex {
+  OutRecord* recs = nullptr;    // [n] key order
+  u64* val = nullptr;           // [n + 1]
+  u32* postings = nullptr;      // [tokens]
+  char* text = nullptr;
+  u64* nl_pos = nullptr;        // [num_newlines]
+  MapCounters* lctr = nullptr;  // num_newlines
+  u64 n = 0, tokens = 0, bytes = 0;
+  u64 lines = 0;  // the text's lines: bounds num_newlines (a destination: its capacity)
+};
+struct AppendScratch {
+  AppendCounters* ctr = nullptr;
+  u32* a_pos = nullptr;     // [nA] lbB, then pos(A[i])
+  u32* b_pos = nullptr;     // [nB] lbA, then pos(B[j])
+  u64* fresh = nullptr;     // [nB] 1: B's key is absent from A (the scans read u64 words)
+  u64* sb = nullptr;        // [nB + 1]
+  u64* tile_val = nullptr;  // [div_up(nA + nB, kIndexTile) + 1]
+  u64 rec_cap_a = 0, rec_cap_b = 0;
+};
+u64 append_scratch_bytes(u64 rec_cap_a, u64 rec_cap_b);
+void append_scratch_carve(char* base, u64 rec_cap_a, u64 rec_cap_b, AppendScratch* ws);
+// Enqueues the merge of a and b into c (c's arrays hold a.n + b.n records, a.tokens + b.tokens
+// postings, a.bytes + b.bytes + 16 text bytes and a.lines + b.lines line starts); ws.ctr is
+// complete when `s` has drained.
+void launch_append(const AppendIndex& a, const AppendIndex& b, const AppendIndex& c,
+                   AppendScratch& ws, hipStream_t s);
+
 // ---------------- search.hip ----------------
 // All/any/phrase/near word queries over the inverted index launch_index left on the device
 // (engine.hpp "index search"): the key-ordered records, the CSR offsets `val` and the sorted
@@ -1222,6 +1285,7 @@ void launch_string_selftest(const char* blob, const u32* off, u32 n, const char*
 // loads every kernel file of this library up front (engine construction) -- and only them:
 // HIP_ENABLE_DEFERRED_LOADING=0 would also load the RCCL library's device code (a
 // 573 MB fat binary), +1.3 GB of host memory and ~150 ms per process.
+void warm_module_append();  // (as index: the code object only, no buffers)
 void warm_module_dict();
 void warm_module_exchange();
 void warm_module_expr();  // (as search: the code object only, no buffers)
@@ -1246,6 +1310,7 @@ void warm_module_tokenize();
 // buffer are made by an engine's first top job only.
 void warm_module_topk();
 inline void warm_kernel_modules() {
+  warm_module_append();
   warm_module_dict();
   warm_module_exchange();
   warm_module_expr();

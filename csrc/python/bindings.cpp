@@ -391,6 +391,7 @@ class PyGpuEngine {
     d["chunk_bytes"] = st.chunk_bytes;
     d["map_window"] = st.map_window;
     d["search_bytes"] = st.search_bytes;
+    d["index_store_bytes"] = st.index_store_bytes;
     return d;
   }
   PyGpuEngine(const JobConfig& cfg, u64 max_bytes, u64 max_lines)
@@ -541,6 +542,16 @@ class PyGpuEngine {
     const u64 tk = to_tally(tally);
     py::gil_scoped_release nogil;
     return PySearchResult{eng_.search_resident(q, k, ignore_case, n, tk)};
+  }
+  // One more block of whole lines into the resident index, merged on the device.
+  IndexAppend append_index(const std::string& text, u64 first_line) {
+    py::gil_scoped_release nogil;
+    return eng_.append_index(as_input(text, first_line));
+  }
+  // The resident index downloaded, whatever it was built from.
+  PyIndexResult index_resident() {
+    py::gil_scoped_release nogil;
+    return PyIndexResult{eng_.index_resident(), eng_.config()};
   }
   // records: (key bytes, count), sorted by key with distinct keys -- the kernels alone.
   PyTopResult top_counts(const std::vector<std::pair<std::string, u64>>& records, u32 k) {
@@ -1220,6 +1231,10 @@ PYBIND11_MODULE(_locust, m) {
            py::arg("glob") = false, py::arg("ignore_case") = false, py::arg("show") = py::none(),
            py::arg("fuzzy") = false, py::arg("regex") = false, py::arg("tally") = py::none(),
            "Another batch from the index the last run_index / run_search left on the device.")
+      .def("append_index", &PyGpuEngine::append_index, py::arg("text"), py::arg("first_line"),
+           "One more block of whole lines into the resident index, merged on the device.")
+      .def("index_resident", &PyGpuEngine::index_resident,
+           "The resident index downloaded (IndexResult), whatever it was built from.")
       .def("top_counts", &PyGpuEngine::top_counts, py::arg("records"), py::arg("k"),
            "The selection kernels alone over key-sorted (key, count) records.")
       .def_property_readonly("capacity", &PyGpuEngine::capacity);
@@ -1236,6 +1251,57 @@ PYBIND11_MODULE(_locust, m) {
     CpuWordCount eng(cfg);
     return PyIndexResult{eng.run_index(as_input(text, first_line)), cfg};
   }, py::arg("cfg"), py::arg("text"), py::arg("first_line") = 0);
+  py::class_<IndexAppend>(m, "IndexAppend")
+      .def_readonly("block_lines", &IndexAppend::block_lines)
+      .def_readonly("block_tokens", &IndexAppend::block_tokens)
+      .def_readonly("block_unique", &IndexAppend::block_unique)
+      .def_readonly("num_lines", &IndexAppend::num_lines)
+      .def_readonly("num_tokens", &IndexAppend::num_tokens)
+      .def_readonly("num_unique", &IndexAppend::num_unique)
+      .def_readonly("fresh_words", &IndexAppend::fresh_words)
+      .def_readonly("index_ms", &IndexAppend::index_ms)
+      .def_readonly("append_ms", &IndexAppend::append_ms)
+      .def_readonly("store_bytes", &IndexAppend::store_bytes)
+      .def("times", [](const IndexAppend& a) {
+        py::dict d;
+        d["h2d_ms"] = a.times.h2d_ms;
+        d["map_ms"] = a.times.map_ms;
+        d["process_ms"] = a.times.process_ms;
+        d["reduce_ms"] = a.times.reduce_ms;
+        d["gpu_ms"] = a.times.gpu_ms;
+        d["wall_ms"] = a.times.wall_ms;
+        d["index_ms"] = a.index_ms;
+        d["append_ms"] = a.append_ms;
+        return d;
+      });
+  m.def("merge_index", [](const PyIndexResult& a, const PyIndexResult& b) {
+    py::gil_scoped_release nogil;
+    return PyIndexResult{merge_index(a.x, b.x), a.cfg};
+  }, py::arg("a"), py::arg("b"),
+        "The index of a's text followed by b's (b.first_line == a.first_line + a's lines).");
+  // the host evaluation over an index and the text it was built from (every mode)
+  m.def("search_index_text", [](const PyIndexResult& x, const std::string& text,
+                                const std::vector<std::vector<std::string>>& queries,
+                                const std::vector<int>& any, const py::object& rank, bool wildcard,
+                                const std::vector<u64>& within,
+                                const std::vector<std::vector<std::string>>& exclude, bool glob,
+                                bool ignore_case, const py::object& show, bool fuzzy, bool regex,
+                                const py::object& tally) {
+    const std::vector<SearchQuery> q =
+        to_queries(x.cfg, queries, any, wildcard, within, exclude, glob, fuzzy, regex);
+    const u64 k = to_rank(rank), n = to_show(show), tk = to_tally(tally);
+    py::gil_scoped_release nogil;
+    return PySearchResult{
+        search_index(x.x, as_input(text, x.x.first_line), q, x.cfg, k, ignore_case, n, tk)};
+  });
+  m.def("split_blocks", [](const std::string& text, u64 block_bytes, u64 first_line) {
+    std::vector<std::tuple<u64, u64, u64, u64>> out;
+    const TextInput in = as_input(text, first_line);
+    for (const TextInput& b : split_blocks(in, block_bytes))
+      out.emplace_back((u64)(b.data - in.data), b.bytes, b.num_lines, b.first_line);
+    return out;
+  }, py::arg("text"), py::arg("block_bytes"), py::arg("first_line") = 0,
+        "Line-aligned blocks of at most block_bytes: [(offset, bytes, lines, first_line)].");
   m.def("cpu_run_search", [](const JobConfig& cfg, const std::string& text,
                              const std::vector<std::vector<std::string>>& queries,
                              const std::vector<int>& any, u64 first_line,

@@ -49,10 +49,12 @@ from .models.wordcount import (  # noqa: E402
     index_file,
     index_text,
     map_stage,
+    merge_index,
     reduce_stage,
     run_multi,
     search_file,
     search_text,
+    split_blocks,
     top_words_file,
     top_words_text,
     wordcount_file,
@@ -84,6 +86,8 @@ __all__ = [
     "index_text",
     "search_file",
     "search_text",
+    "merge_index",
+    "split_blocks",
     "JobConfig",
     "DistConfig",
     "LocustError",

@@ -107,6 +107,7 @@ class Engine:
         self.cfg = cfg if cfg is not None else make_config()
         self.cpu = self.cfg.backend == _C.Backend.cpu
         self._eng = None if self.cpu else _C.GpuEngine(self.cfg, max_bytes, max_lines)
+        self._next_line = 0  # the line behind the resident index (append_index)
 
     @property
     def capacity(self) -> int:
@@ -134,7 +135,9 @@ class Engine:
         the word job (one pass, dictionary engine, fast map, word keys)."""
         if self.cpu:
             return _C.cpu_run_index(self.cfg, text, first_line)
-        return self._eng.run_index(text, first_line)
+        res = self._eng.run_index(text, first_line)
+        self._next_line = first_line + res.num_lines
+        return res
 
     def run_search(self, text: bytes, queries, mode="all", first_line: int = 0, rank=None,
                    wildcard=False, within=None, exclude=None, glob=False, ignore_case=False,
@@ -244,9 +247,11 @@ class Engine:
             return _C.cpu_run_search(self.cfg, text, queries, flags, first_line, rank,
                                      bool(wildcard), windows, exclude, bool(glob),
                                      bool(ignore_case), show, bool(fuzzy), bool(regex), tally)
-        return self._eng.run_search(text, queries, flags, first_line, rank, bool(wildcard),
-                                    windows, exclude, bool(glob), bool(ignore_case), show,
-                                    bool(fuzzy), bool(regex), tally)
+        res = self._eng.run_search(text, queries, flags, first_line, rank, bool(wildcard),
+                                   windows, exclude, bool(glob), bool(ignore_case), show,
+                                   bool(fuzzy), bool(regex), tally)
+        self._next_line = first_line + res.num_lines
+        return res
 
     def search_resident(self, queries, mode="all", rank=None, wildcard=False, within=None,
                         exclude=None, glob=False, ignore_case=False, show=None, fuzzy=False,
@@ -263,6 +268,29 @@ class Engine:
         return self._eng.search_resident(queries, flags, rank, bool(wildcard), windows, exclude,
                                          bool(glob), bool(ignore_case), show, bool(fuzzy),
                                          bool(regex), tally)
+
+    def append_index(self, text: bytes):
+        """One more block of whole lines into the index this engine holds on the device
+        (``IndexAppend``): afterwards the resident index is the index of everything indexed and
+        appended so far, one text after the other, and ``search_resident`` answers from it.
+        The block's lines are numbered behind the resident ones; it is indexed in one pass of
+        this engine and merged on the device.  Refused with the resident index intact: no
+        resident index, a block larger than the engine's pass, a resident text that does not
+        end in a newline (GPU engines only)."""
+        if self.cpu:
+            raise _C.LocustError("append_index needs a GPU engine: the CPU engine keeps no "
+                                 "index (use merge_index(a, b) on two IndexResults)")
+        res = self._eng.append_index(text, self._next_line)
+        self._next_line += res.block_lines
+        return res
+
+    def index_resident(self):
+        """The index this engine holds on the device, downloaded (``IndexResult``), whatever it
+        was built from: a ``run_index``, a ``run_search``, or those and appends."""
+        if self.cpu:
+            raise _C.LocustError("index_resident needs a GPU engine: the CPU engine keeps no "
+                                 "index (use run_index(text))")
+        return self._eng.index_resident()
 
     def top_counts(self, records: list[tuple[bytes, int]], k: int):
         """The selection alone over (key, count) records sorted by key with distinct
@@ -345,30 +373,82 @@ def top_words_file(path: str, k: int, line_start: int = -1, line_end: int = -1,
     return Engine(cfg, max(len(text), 1), max(nlines, 1)).run_top(text, k)
 
 
-def index_text(text: bytes, backend: str = "gpu", cfg=None, first_line: int = 0, **kw):
+def merge_index(a, b):
+    """The index of ``a``'s text followed by ``b``'s, from the two ``IndexResult`` alone: the
+    host twin of the device merge.  ``b.first_line`` must be ``a.first_line + a.num_lines``."""
+    return _C.merge_index(a, b)
+
+
+def split_blocks(text: bytes, block_bytes: int, first_line: int = 0):
+    """``text`` cut into line-aligned blocks of at most ``block_bytes`` bytes:
+    ``[(offset, bytes, lines, first_line)]``.  Every block but the last ends in a newline; a
+    line longer than a block is refused."""
+    return _C.split_blocks(text, block_bytes, first_line)
+
+
+def _blocks(text, block_bytes, first_line):
+    return [(text[o:o + n], lines, first) for o, n, lines, first in
+            _C.split_blocks(text, block_bytes, first_line)]
+
+
+def _index_blocks(cfg, text, first_line, block_bytes):
+    """(engine holding the index of ``text`` built block by block, or None on the CPU; the CPU
+    backend's merged IndexResult, or None)."""
+    blocks = _blocks(text, block_bytes, first_line)
+    if cfg.backend == _C.Backend.cpu:
+        x = _C.cpu_run_index(cfg, blocks[0][0], first_line)
+        for piece, _lines, first in blocks[1:]:
+            x = _C.merge_index(x, _C.cpu_run_index(cfg, piece, first))
+        return None, x
+    eng = Engine(cfg, max(max(len(b[0]) for b in blocks), 1), max(max(b[1] for b in blocks), 1))
+    eng.run_index(blocks[0][0], first_line)
+    for piece, _lines, _first in blocks[1:]:
+        eng.append_index(piece)
+    return eng, None
+
+
+def index_text(text: bytes, backend: str = "gpu", cfg=None, first_line: int = 0,
+               block_bytes=None, **kw):
     """The inverted index of ``text`` (``IndexResult``); lines are numbered from
-    ``first_line``."""
+    ``first_line``.  ``block_bytes=N``: built block by block (``split_blocks``), the first
+    block indexed and the rest appended, so the engine is sized to one block."""
     cfg = cfg if cfg is not None else make_config(backend, **kw)
+    if block_bytes is not None:
+        eng, x = _index_blocks(cfg, text, first_line, block_bytes)
+        return x if eng is None else eng.index_resident()
     nlines = text.count(b"\n") + (1 if text and not text.endswith(b"\n") else 0)
     return Engine(cfg, max(len(text), 1), max(nlines, 1)).run_index(text, first_line)
 
 
 def index_file(path: str, line_start: int = -1, line_end: int = -1, backend: str = "gpu",
-               cfg=None, **kw):
+               cfg=None, block_bytes=None, **kw):
     """The inverted index of a file or of its line window, with the file's own (global)
-    line numbers."""
+    line numbers.  ``block_bytes`` as ``index_text`` takes it."""
     cfg = cfg if cfg is not None else make_config(backend, **kw)
     text, nlines, first, _total = _C.load_lines(path, line_start, line_end, cfg.ref_compat)
+    if block_bytes is not None:
+        return index_text(text, cfg=cfg, first_line=first, block_bytes=block_bytes)
     return Engine(cfg, max(len(text), 1), max(nlines, 1)).run_index(text, first)
 
 
 def search_text(text: bytes, queries, mode="all", backend: str = "gpu", cfg=None,
                 first_line: int = 0, rank=None, wildcard=False, within=None, exclude=None,
                 glob=False, ignore_case=False, show=None, fuzzy=False, regex=False, tally=None,
-                **kw):
+                block_bytes=None, **kw):
     """All/any/phrase/near word queries over ``text`` (``SearchResult``); see
-    ``Engine.run_search``."""
+    ``Engine.run_search``.  ``block_bytes=N``: the index is built block by block
+    (``index_text``) and the batch answered from it (on the CPU: from the merged index and the
+    whole text)."""
     cfg = cfg if cfg is not None else make_config(backend, **kw)
+    if block_bytes is not None:
+        eng, x = _index_blocks(cfg, text, first_line, block_bytes)
+        if eng is not None:
+            return eng.search_resident(queries, mode, rank, wildcard, within, exclude, glob,
+                                       ignore_case, show, fuzzy, regex, tally)
+        queries, flags, windows, exclude = _search_args(queries, mode, within, exclude)
+        return _C.search_index_text(x, text, queries, flags, rank, bool(wildcard), windows,
+                                    exclude, bool(glob), bool(ignore_case), show, bool(fuzzy),
+                                    bool(regex), tally)
     nlines = text.count(b"\n") + (1 if text and not text.endswith(b"\n") else 0)
     return Engine(cfg, max(len(text), 1), max(nlines, 1)).run_search(
         text, queries, mode, first_line, rank, wildcard, within, exclude, glob, ignore_case,
@@ -378,11 +458,16 @@ def search_text(text: bytes, queries, mode="all", backend: str = "gpu", cfg=None
 def search_file(path: str, queries, mode="all", line_start: int = -1, line_end: int = -1,
                 backend: str = "gpu", cfg=None, rank=None, wildcard=False, within=None,
                 exclude=None, glob=False, ignore_case=False, show=None, fuzzy=False, regex=False,
-                tally=None, **kw):
+                tally=None, block_bytes=None, **kw):
     """All/any/phrase/near word queries over a file or its line window, answered with the file's
-    own (global) line numbers."""
+    own (global) line numbers.  ``block_bytes`` as ``search_text`` takes it."""
     cfg = cfg if cfg is not None else make_config(backend, **kw)
     text, nlines, first, _total = _C.load_lines(path, line_start, line_end, cfg.ref_compat)
+    if block_bytes is not None:
+        return search_text(text, queries, mode, cfg=cfg, first_line=first, rank=rank,
+                           wildcard=wildcard, within=within, exclude=exclude, glob=glob,
+                           ignore_case=ignore_case, show=show, fuzzy=fuzzy, regex=regex,
+                           tally=tally, block_bytes=block_bytes)
     return Engine(cfg, max(len(text), 1), max(nlines, 1)).run_search(
         text, queries, mode, first, rank, wildcard, within, exclude, glob, ignore_case, show,
         fuzzy, regex, tally)

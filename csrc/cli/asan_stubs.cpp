@@ -30,6 +30,7 @@ SearchResult GpuWordCount::search_resident(const std::vector<SearchQuery>&, u64,
   no_gpu();
 }
 IndexAppend GpuWordCount::append_index(const TextInput&) { no_gpu(); }
+IndexDrop GpuWordCount::drop_index(u64) { no_gpu(); }
 IndexResult GpuWordCount::index_resident() { no_gpu(); }
 char* GpuWordCount::input_buffer() { no_gpu(); }
 GpuWordCount::Stats GpuWordCount::stats() const { no_gpu(); }

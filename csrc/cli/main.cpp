@@ -37,6 +37,8 @@
 //   --tally K (with --search: under each query's line, the K most frequent words of its lines)
 //   --block-kb N (with --index or --search: the index is built from line-aligned blocks of at
 //     most N KiB, the first indexed, the rest appended to the index in device memory)
+//   --keep-blocks M (with --block-kb: a sliding window -- once more than M blocks are resident the
+//     oldest block's lines are dropped from the index, on the device)
 // and a synthetic-text generator (BASELINE configs "1M lines" / "10 GB"):
 //   MapReduce --gen FILE (--gen-lines N | --gen-bytes N) [--seed S] [--vocab V]
 #include <sys/stat.h>
@@ -121,6 +123,8 @@ struct CliArgs {
   u64 tally = 0;      // --tally K: the K most frequent words of every query's returned lines
   bool block_given = false;
   u64 block_kb = 0;   // --block-kb N: --index / --search build the index in blocks of N KiB
+  bool keep_given = false;
+  u64 keep_blocks = 0;  // --keep-blocks M: at most M blocks stay in the index (0: all of them)
   std::string gen_out;  // generator mode
   GenSpec gen;
 };
@@ -244,6 +248,14 @@ void help() {
       "                             memory.  The result lines are those of the run without it.  A line\n"
       "                             longer than a block is refused.  With --backend cpu the blocks'\n"
       "                             indexes are merged on the host.  Not with --chunk-mb)\n"
+      "  --keep-blocks M            (--block-kb: a sliding window over the text -- whenever an append\n"
+      "                             leaves more than M blocks in the index, M >= 1, the oldest block's\n"
+      "                             lines are dropped from it: their postings, the words that empty\n"
+      "                             out, their text and line starts, compacted on the device.  The\n"
+      "                             result lines are those of the run without --block-kb and\n"
+      "                             --keep-blocks over the lines from the first line of block\n"
+      "                             blocks - M on; line numbers stay global.  With --backend cpu the\n"
+      "                             merged index is trimmed on the host)\n"
       "  --ignore-case              (--search: the ASCII letters of every word of every query,\n"
       "                             --not words too, match either case: \"to be\" finds \"To be\".\n"
       "                             Other bytes match only themselves.  With --glob, --wildcard and\n"
@@ -446,6 +458,14 @@ bool parse(int argc, char** argv, CliArgs* a) {
         throw Error("--block-kb N needs an integer N >= 1 (KiB per block)");
       a->block_given = true;
       a->block_kb = (u64)n;
+    } else if (s == "--keep-blocks") {
+      const std::string v = need("--keep-blocks");
+      char* endp = nullptr;
+      const long long n = std::strtoll(v.c_str(), &endp, 10);
+      if (v.empty() || *endp || n < 1 || n > (1ll << 40))
+        throw Error("--keep-blocks M needs an integer M >= 1 (blocks kept in the index)");
+      a->keep_given = true;
+      a->keep_blocks = (u64)n;
     } else if (s == "--gen") {
       a->gen_out = need("--gen");
     } else if (s == "--gen-lines") {
@@ -520,6 +540,9 @@ bool parse(int argc, char** argv, CliArgs* a) {
   if (a->block_given && !a->index && a->search_args.empty())
     throw Error("--block-kb N builds the index of --index or --search block by block: give one of "
                 "them too");
+  if (a->keep_given && !a->block_given)
+    throw Error("--keep-blocks M keeps the last M blocks of an index built block by block: give "
+                "--block-kb N too");
   if (a->block_given && a->cfg.chunk_bytes)
     throw Error("--block-kb and --chunk-mb do not combine: --chunk-mb streams a word count, "
                 "--block-kb builds an index block by block");
@@ -756,13 +779,19 @@ void json_top(JsonOut& j, const CliArgs& a) {
 // --index: "index": true in the record, the postings' number, and where the device built
 // it its device time and the bytes it wrote to host memory for the result.
 // --block-kb: the blocks, the merges' device time (their sum) and the index store's size.
-u64 g_blocks = 0, g_store_bytes = 0;
-double g_append_ms = 0;
+// --keep-blocks: the blocks dropped, the drops' device time (their sum) and the window's first
+// line.
+u64 g_blocks = 0, g_store_bytes = 0, g_dropped_blocks = 0, g_first_line = 0;
+double g_append_ms = 0, g_drop_ms = 0;
 void json_blocks(JsonOut& j, const CliArgs& a) {
   if (!a.block_given) return;
   j.u("blocks", g_blocks);
   j.num("append_ms", g_append_ms);
   j.u("index_store_bytes", g_store_bytes);
+  if (!a.keep_given) return;
+  j.u("dropped_blocks", g_dropped_blocks);
+  j.num("drop_ms", g_drop_ms);
+  j.u("first_line", g_first_line);
 }
 
 const IndexResult* g_index = nullptr;
@@ -1384,18 +1413,33 @@ int run(const CliArgs& a) {
         const u64 t0 = now_ns();
         const std::vector<TextInput> blocks = split_blocks(text.input, a.block_kb << 10);
         IndexResult x = eng.run_index(blocks[0]);
+        // --keep-blocks: the dropped lines' statistics come from each block's own index
+        std::vector<std::pair<u64, u64>> stats{{x.words.overflow_lines, x.words.truncated}};
+        size_t oldest = 0;  // the first block still in the index
         for (size_t b = 1; b < blocks.size(); ++b) {
           const IndexResult y = eng.run_index(blocks[b]);
           StageTimes tm = x.words.times;
           tm.map_ms += y.words.times.map_ms;
           tm.process_ms += y.words.times.process_ms;
           tm.reduce_ms += y.words.times.reduce_ms;
+          stats.emplace_back(y.words.overflow_lines, y.words.truncated);
           x = merge_index(x, y);
+          if (a.keep_given && b + 1 - oldest > a.keep_blocks) {
+            x = trim_index(x, blocks[oldest].num_lines, stats[oldest].first, stats[oldest].second);
+            ++oldest;
+          }
           x.words.times = tm;
         }
         g_blocks = blocks.size();
+        g_dropped_blocks = oldest;
+        g_first_line = x.first_line;
+        TextInput window = text.input;  // the lines still in the index
+        window.data = blocks[oldest].data;
+        window.bytes = (u64)(text.input.data + text.input.bytes - window.data);
+        window.first_line = blocks[oldest].first_line;
+        window.num_lines = text.input.first_line + text.input.num_lines - window.first_line;
         if (!a.queries.empty()) {
-          cpu_search = search_index(x, text.input, a.queries, a.cfg, a.rank, a.ignore_case,
+          cpu_search = search_index(x, window, a.queries, a.cfg, a.rank, a.ignore_case,
                                     a.show, a.tally);
           r = search_stats(cpu_search);
           r.times = x.words.times;
@@ -1437,7 +1481,9 @@ int run(const CliArgs& a) {
       for (int i = 0; i < a.warmup + a.iters; ++i) {
         const u64 t0 = now_ns();
         StageTimes tm = eng.run_index(blocks[0]).words.times;
-        double index_ms = 0, append_ms = 0;
+        double index_ms = 0, append_ms = 0, drop_ms = 0;
+        size_t oldest = 0;  // the first block still in the index
+        u64 first_line = blocks[0].first_line;
         for (size_t b = 1; b < blocks.size(); ++b) {
           const IndexAppend ap = eng.append_index(blocks[b]);
           tm.h2d_ms += ap.times.h2d_ms;
@@ -1447,6 +1493,12 @@ int run(const CliArgs& a) {
           tm.gpu_ms += ap.times.gpu_ms;
           index_ms += ap.index_ms;
           append_ms += ap.append_ms;
+          if (a.keep_given && b + 1 - oldest > a.keep_blocks) {
+            const IndexDrop dr = eng.drop_index(blocks[oldest++].num_lines);
+            tm.gpu_ms += dr.drop_ms;
+            drop_ms += dr.drop_ms;
+            first_line = dr.first_line;
+          }
         }
         if (!a.queries.empty()) {
           sr = eng.search_resident(a.queries, a.rank, a.ignore_case, a.show, a.tally);
@@ -1465,6 +1517,9 @@ int run(const CliArgs& a) {
         g_blocks = blocks.size();
         g_append_ms = append_ms;
         g_store_bytes = eng.stats().index_store_bytes;
+        g_dropped_blocks = oldest;
+        g_drop_ms = drop_ms;
+        g_first_line = first_line;
       }
       if (!a.queries.empty())
         print_gpu_result(a, search_stats(sr), walls, nullptr, nullptr, &sr);

@@ -438,6 +438,69 @@ IndexResult merge_index(const IndexResult& a, const IndexResult& b) {
   return c;
 }
 
+// ---- dropping the oldest lines: the host twin of kernels/drop.hip (engine.hpp) ----
+IndexResult trim_index(const IndexResult& x, u64 lines, u64 dropped_overflow_lines,
+                       u64 dropped_truncated) {
+  LOCUST_CHECK_ARG(lines <= x.words.num_lines,
+                   "trim_index: " + std::to_string(lines) + " lines to drop, the index holds " +
+                       std::to_string(x.words.num_lines));
+  LOCUST_CHECK_ARG(dropped_overflow_lines <= x.words.overflow_lines &&
+                       dropped_truncated <= x.words.truncated,
+                   "trim_index: the dropped lines' statistics (" +
+                       std::to_string(dropped_overflow_lines) + " lines over the emit cap, " +
+                       std::to_string(dropped_truncated) + " truncated tokens) exceed the index's (" +
+                       std::to_string(x.words.overflow_lines) + ", " +
+                       std::to_string(x.words.truncated) + ")");
+  const u64 cut = x.first_line + lines;
+  IndexResult c;
+  c.first_line = cut;
+  WordCountResult& w = c.words;
+  w.num_lines = x.words.num_lines - lines;
+  w.overflow_lines = x.words.overflow_lines - dropped_overflow_lines;
+  w.truncated = x.words.truncated - dropped_truncated;
+  w.max_key_len = x.words.max_key_len;  // (a maximum: the longest the index has held)
+  w.times = x.words.times;
+  std::vector<WordCountEntry> e;
+  e.reserve(x.words.entries.size());
+  c.postings.reserve(x.postings.size());
+  u64 at = 0, misplaced = 0, dropped = 0;
+  PackedKey prev{};
+  bool have_prev = false;
+  for (const WordCountEntry r : x.words.entries) {  // either entry form
+    if (at + r.count > x.postings.size())
+      throw Error("trim_index: the counts of the index exceed its " +
+                  std::to_string(x.postings.size()) + " postings");
+    if (have_prev && key_compare(prev.w, r.key.w) >= 0) ++misplaced;  // key order
+    prev = r.key;
+    have_prev = true;
+    const auto first = x.postings.begin() + (std::ptrdiff_t)at;
+    const auto last = first + (std::ptrdiff_t)r.count;
+    if (!std::is_sorted(first, last)) ++misplaced;  // a list that decreases
+    const auto keep = std::lower_bound(first, last, cut,
+                                       [](u32 l, u64 line) { return (u64)l < line; });
+    dropped += (u64)(keep - first);
+    if (keep != last) {
+      WordCountEntry k = r;
+      k.count = (u64)(last - keep);
+      e.push_back(k);
+      c.postings.insert(c.postings.end(), keep, last);
+    }
+    at += r.count;
+  }
+  if (misplaced)
+    throw Error("trim_index: " + std::to_string(misplaced) +
+                " keys or postings out of order: the index must hold its words in key order and "
+                "every list ascending");
+  if (at != x.postings.size() || c.postings.size() + dropped != x.words.num_tokens)
+    throw Error("trim_index: " + std::to_string(c.postings.size()) + " postings moved and " +
+                std::to_string(dropped) + " dropped, " + std::to_string(x.words.num_tokens) +
+                " tokens in the index");
+  w.num_tokens = c.postings.size();
+  w.entries = std::move(e);
+  w.num_unique = w.entries.size();
+  return c;
+}
+
 std::vector<TextInput> split_blocks(const TextInput& in, u64 block_bytes) {
   LOCUST_CHECK_ARG(block_bytes > 0, "split_blocks: block_bytes must be > 0 (--block-kb N, N >= 1)");
   LOCUST_CHECK_ARG(!in.source, "split_blocks takes a text held in memory, not a source");

@@ -59,6 +59,7 @@ SearchResult GpuWordCount::search_resident(const std::vector<SearchQuery>& queri
   return impl_->search_resident(queries, rank_k, ignore_case, show, tally);
 }
 IndexAppend GpuWordCount::append_index(const TextInput& in) { return impl_->append_index(in); }
+IndexDrop GpuWordCount::drop_index(u64 lines) { return impl_->drop_index(lines); }
 IndexResult GpuWordCount::index_resident() { return impl_->index_resident(); }
 GpuWordCount::Stats GpuWordCount::stats() const {
   Stats s;

@@ -566,6 +566,10 @@ DevicePipeline::~DevicePipeline() {
   pinned_free(h_actr);
   for (auto& e : ev_append)
     if (e) (void)hipEventDestroy(e);
+  if (d_drop) (void)hipFree(d_drop);
+  pinned_free(h_dctr);
+  for (auto& e : ev_drop)
+    if (e) (void)hipEventDestroy(e);
   if (d_sbatch) (void)hipFree(d_sbatch);
   if (d_shits) (void)hipFree(d_shits);
   if (d_smerged) (void)hipFree(d_smerged);
@@ -3066,6 +3070,137 @@ IndexAppend DevicePipeline::append_index(const TextInput& in) {
   out.times.gpu_ms = ms_between(ev[0], ev_index[1]) + out.append_ms;
   out.times.wall_ms = (now_ns() - t0) * 1e-6;
   out.store_bytes = store_bytes();
+  return out;
+}
+
+void DevicePipeline::ensure_drop_scratch(u64 recs) {
+  if (!h_dctr) {
+    // first drop of this engine: the pinned counters and the events
+    h_dctr = static_cast<DropCounters*>(
+        pinned_alloc(sizeof(DropCounters), hipHostMallocDefault, "drop counters"));
+    for (auto& e : ev_drop) LOCUST_HIP_CHECK(hipEventCreate(&e));
+  }
+  if (d_drop && drop_ws.rec_cap >= recs) return;
+  sync();
+  if (d_drop) LOCUST_HIP_CHECK(hipFree(d_drop));
+  d_drop = nullptr;
+  drop_ws = DropScratch{};
+  drop_bytes = 0;
+  const u64 cap = std::max<u64>(recs + recs / 2, 1);
+  const u64 bytes = drop_scratch_bytes(cap);
+  size_t fr = 0, tot = 0;
+  LOCUST_HIP_CHECK(hipMemGetInfo(&fr, &tot));
+  if ((double)bytes > kHbmUsable * (double)fr)
+    throw Error("drop scratch (" + std::to_string(bytes) + " B needed for " +
+                std::to_string(cap) + " records) does not fit the free device memory (" +
+                std::to_string(fr) + " B free of " + std::to_string(tot) + " B)");
+  LOCUST_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&d_drop), bytes));
+  drop_bytes = bytes;
+  drop_scratch_carve(d_drop, cap, &drop_ws);
+}
+
+IndexDrop DevicePipeline::drop_index(u64 lines) {
+  TraceRange tr("locust:index_drop");
+  // ---- refusals: nothing is enqueued, the resident index stays as it is ----
+  if (!idx_resident)
+    throw Error("drop_index: the index on the device is stale -- this engine's last job "
+                "was not a run_index, a run_search, an append_index or a drop_index (any other "
+                "job, a refused one included, overwrites what the index reads); run one of them "
+                "first");
+  LOCUST_CHECK_ARG(lines <= idx_num_lines,
+                   "drop_index: " + std::to_string(lines) + " lines to drop, the resident index "
+                       "holds " + std::to_string(idx_num_lines));
+  const u64 cut_line = (u64)idx_view.first_line + lines;
+  LOCUST_CHECK_ARG(cut_line < (1ull << 32),
+                   "index: line numbers past 2^32 do not fit a u32 posting");
+  IndexDrop out;
+  const auto report = [&] {
+    out.first_line = idx_view.first_line;
+    out.num_lines = idx_num_lines;
+    out.num_tokens = idx_tokens;
+    out.num_unique = idx_view.n;
+    out.store_bytes = store_bytes();
+  };
+  if (lines == 0) {  // a no-op: nothing is enqueued or allocated
+    report();
+    return out;
+  }
+  // ---- the source where it lives, the destination the other half ----
+  const AppendIndex a = idx_in_store ? store[store_cur].ix : resident_as_append();
+  const int dst = idx_in_store ? 1 - store_cur : 0;
+  ensure_store_half(dst, a.n, a.tokens, a.bytes, a.lines - lines);
+  ensure_drop_scratch(a.n);
+  idx_resident = false;  // (until the compacted index stands: any failure from here leaves it stale)
+  if (!idx_in_store) ensure_line_index(a.bytes, a.n, a.tokens);
+  AppendIndex c = store[dst].ix;
+  c.n = store[dst].rec_cap;
+  c.tokens = store[dst].post_cap;
+  c.bytes = store[dst].text_cap + 16;
+  c.lines = store[dst].line_cap;
+  DropRules rules;
+  rules.dm = idx_view.dm;
+  rules.emits_per_line = idx_view.emits_per_line;
+  rules.max_key_len = idx_view.max_key_len;
+  LOCUST_HIP_CHECK(hipEventRecord(ev_drop[0], stream));
+  launch_drop(a, c, (u32)cut_line, lines, rules, drop_ws, stream);
+  LOCUST_HIP_CHECK(hipMemcpyAsync(h_dctr, drop_ws.ctr, sizeof(DropCounters),
+                                  hipMemcpyDeviceToHost, stream));
+  LOCUST_HIP_CHECK(hipEventRecord(ev_drop[1], stream));
+  sync();
+  const DropCounters dc = *h_dctr;
+  if (dc.misplaced)
+    throw Error("drop: " + std::to_string(dc.misplaced) +
+                " records or postings misplaced (a position outside the index that is left, keys "
+                "out of order, or offsets that do not ascend)");
+  if (dc.moved + dc.dropped != a.tokens)
+    throw Error("drop: " + std::to_string(dc.moved) + " postings moved and " +
+                std::to_string(dc.dropped) + " dropped, the index holds " +
+                std::to_string(a.tokens));
+  if ((u64)dc.records + dc.vanished != a.n || dc.records != dc.nc)
+    throw Error("drop: " + std::to_string(dc.records) + " records written and " +
+                std::to_string(dc.vanished) + " words emptied, the index holds " +
+                std::to_string(a.n));
+  if (dc.cut_byte > a.bytes || dc.overflow_lines > idx_words.overflow_lines ||
+      dc.truncated > idx_words.truncated)
+    throw Error("drop: the dropped lines hold " + std::to_string(dc.cut_byte) + " bytes, " +
+                std::to_string(dc.overflow_lines) + " lines over the emit cap and " +
+                std::to_string(dc.truncated) + " truncated tokens, more than the index (" +
+                std::to_string(a.bytes) + ", " + std::to_string(idx_words.overflow_lines) + ", " +
+                std::to_string(idx_words.truncated) + ")");
+  // ---- the compacted index is the resident one ----
+  AppendIndex& m = store[dst].ix;
+  m.n = dc.nc;
+  m.tokens = dc.moved;
+  m.bytes = a.bytes - dc.cut_byte;
+  m.lines = a.lines - lines;
+  store_cur = dst;
+  idx_in_store = true;
+  idx_view.recs = m.recs;
+  idx_view.val = m.val;
+  idx_view.postings = m.postings;
+  idx_view.n = (u32)m.n;
+  idx_view.first_line = (u32)cut_line;
+  idx_view.text = m.text;
+  idx_view.bytes = m.bytes;
+  idx_view.nl_pos = m.nl_pos;
+  idx_view.lctr = m.lctr;
+  idx_num_lines = m.lines;
+  idx_tokens = m.tokens;
+  idx_words.num_lines = m.lines;
+  idx_words.num_tokens = m.tokens;
+  idx_words.num_unique = m.n;
+  idx_words.overflow_lines -= dc.overflow_lines;
+  idx_words.truncated -= dc.truncated;
+  if (m.bytes == 0) idx_ends_nl = true;
+  idx_resident = true;
+  out.dropped_lines = lines;
+  out.dropped_tokens = dc.dropped;
+  out.dropped_words = dc.vanished;
+  out.dropped_bytes = dc.cut_byte;
+  out.dropped_overflow_lines = dc.overflow_lines;
+  out.dropped_truncated = dc.truncated;
+  out.drop_ms = ms_between(ev_drop[0], ev_drop[1]);
+  report();
   return out;
 }
 

@@ -884,7 +884,21 @@ struct DevicePipeline {
   AppendScratch append_ws{};
   AppendCounters* h_actr = nullptr;  // pinned copy of the merge's counters
   hipEvent_t ev_append[2] = {};
-  u64 store_bytes() const { return store[0].bytes + store[1].bytes + append_bytes; }
+  // The drop (kernels/drop.hip; engine.hpp "dropping the oldest lines") reads the resident
+  // index wherever it lives -- a half, or the pass buffers -- and writes the other half (half 0
+  // from the pass buffers) whole; the halves then swap as after a merge.  Its scratch, pinned
+  // counters and events are made by the engine's first drop: an engine that never drops
+  // allocates nothing for it and runs none of its kernels.
+  char* d_drop = nullptr;
+  u64 drop_bytes = 0;
+  DropScratch drop_ws{};
+  DropCounters* h_dctr = nullptr;  // pinned copy of the drop's counters
+  hipEvent_t ev_drop[2] = {};
+  void ensure_drop_scratch(u64 recs);
+  IndexDrop drop_index(u64 lines);
+  u64 store_bytes() const {
+    return store[0].bytes + store[1].bytes + append_bytes + drop_bytes;
+  }
   void ensure_store_half(int h, u64 recs, u64 posts, u64 text_bytes, u64 lines);
   void ensure_append_scratch(u64 recs_a, u64 recs_b);
   // launch_index builds no line index for a text without tokens: the merge needs one.

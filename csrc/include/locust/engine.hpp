@@ -371,6 +371,47 @@ struct IndexAppend {
 // indexes alone, with the same checks (keys strictly ascending on either side, the counts
 // adding up to the postings).  Throws unless b.first_line == a.first_line + a.words.num_lines.
 IndexResult merge_index(const IndexResult& a, const IndexResult& b);
+
+// ---- dropping the oldest lines ----
+// The mirror image of an append, for an index that follows a log or a feed and is searched
+// over its most recent part.  The resident index holds the lines [F, F + N).  After
+// drop_index(d) with 0 <= d <= N the index in device memory is exactly the index of the
+// remaining text with first_line = F + d: the same records, val, postings (still global line
+// numbers), text bytes, line starts and num_newlines that run_index(remaining_text, F + d) would
+// have left, so index_resident() and every search_resident() answer field for field as a
+// one-pass job over the remaining lines does.  Every list is non-decreasing in the line number,
+// so what a word loses is a prefix of its list: nothing is renumbered and nothing is sorted
+// (kernels/drop.hip); words whose lists empty out leave the dictionary.
+//  * num_lines, num_tokens and num_unique are exact.  overflow_lines and truncated are exact
+//    too: the dropped lines' share is counted on the device and subtracted.  max_key_len (the
+//    statistic) is a maximum and cannot be subtracted: it stays as it was, "the longest the
+//    index has held".
+//  * d == 0 is a no-op that still reports the index's figures.  d == N leaves an empty index
+//    whose first_line is F + N; append_index goes on from there (an empty resident text counts
+//    as "ends in a newline").  A last line without its '\n' may be dropped with the rest.  Drops
+//    and appends may follow each other in any order.
+//  * Refused before anything is enqueued, the resident index intact and still searchable: no
+//    resident index or a stale one; d > N.
+//  * Any failure after the first kernel is enqueued leaves the index stale.
+// Only counters cross PCIe (the byte offset of the cut among them).
+struct IndexDrop {
+  u64 dropped_lines = 0, dropped_tokens = 0;
+  u64 dropped_words = 0;   // words whose list emptied
+  u64 dropped_bytes = 0;   // text bytes removed
+  u64 dropped_overflow_lines = 0, dropped_truncated = 0;
+  u64 first_line = 0, num_lines = 0, num_tokens = 0, num_unique = 0;  // the resident index afterwards
+  double drop_ms = 0;      // device time of the drop
+  u64 store_bytes = 0;     // device bytes of the index store (both halves and the scratches)
+};
+// The host twin of the device drop: the index of x's text without its first `lines` lines, from
+// the index alone, with merge_index's checks (keys strictly ascending, the counts adding up to
+// the postings, every list non-decreasing).  An IndexResult holds no text, so the dropped lines'
+// share of overflow_lines and truncated is the caller's to supply (a block's own run_index has
+// them); max_key_len stays.  Throws when lines > x.words.num_lines.
+//   trim_index(merge_index(a, b), a.words.num_lines, a.words.overflow_lines, a.words.truncated)
+// equals b in entries, postings, first_line and every statistic but max_key_len.
+IndexResult trim_index(const IndexResult& x, u64 lines, u64 dropped_overflow_lines = 0,
+                       u64 dropped_truncated = 0);
 // `in` cut into line-aligned blocks of at most block_bytes bytes, num_lines and first_line
 // filled in; every block but the last ends in '\n', and a text that fits is one block.  A
 // single line longer than block_bytes is an error (it names the CLI's --block-kb).
@@ -1151,6 +1192,9 @@ class GpuWordCount {
   // the block's word job and index stage, then the merge on the device into the engine's
   // index store.  in.first_line must be the resident first_line + lines.
   IndexAppend append_index(const TextInput& in);
+  // The oldest `lines` lines out of the resident index ("dropping the oldest lines" above):
+  // compacted on the device into the other half of the engine's index store.
+  IndexDrop drop_index(u64 lines);
   // The resident index downloaded (entries, postings, statistics), whatever it was built from;
   // throws as search_resident does when it is stale.
   IndexResult index_resident();

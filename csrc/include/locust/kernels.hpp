@@ -684,6 +684,72 @@ void append_scratch_carve(char* base, u64 rec_cap_a, u64 rec_cap_b, AppendScratc
 void launch_append(const AppendIndex& a, const AppendIndex& b, const AppendIndex& c,
                    AppendScratch& ws, hipStream_t s);
 
+// ---------------- drop.hip ----------------
+// Dropping the oldest lines of an index in device memory (engine.hpp "dropping the oldest
+// lines"): the mirror image of the merge.  A is the resident index over the lines
+// [F, F + N), d <= N the number of lines to drop and cut_line = F + d.  Every list is
+// non-decreasing in the line number, so what a word loses is a prefix of its list.  C, in
+// buffers of its own, is the index a single pass over A's text without its first d lines,
+// numbered from cut_line, would have left.  Nothing is renumbered and nothing is sorted.
+//
+// A sequence of kernels on `s`; data crosses between workgroups only at kernel boundaries, no
+// output array is written with atomics and every output word has exactly one writer:
+//   cut       one thread per record: k_w = the lower bound of cut_line in the word's list (the
+//             postings < cut_line; duplicates of cut_line are kept), survive_w = k_w < count_w
+//   scan      pos = exclusive scan of survive (device/tile_scan.hpp's three kernels);
+//             nC = pos[nA] stays on the device
+//   records   a survivor writes its record once, count = count_w - k_w, at pos[w], and leaves
+//             its source word there for the postings kernel; keys are checked to ascend
+//   offsets   valC = exclusive scan of C's counts (the same three kernels), valC[nC] = TC
+//   postings  tiles of kAppendTile DESTINATION elements: a tile finds the words of C its
+//             elements belong to by two binary searches in valC, stages their offsets and
+//             their shifts to the source in LDS, and every element then finds its word there.
+//             The grid is the host's bound (A's tokens); a tile past TC leaves at once
+//   lines     B = the byte behind the newline of line d - 1 (all bytes when the last,
+//             unterminated line goes too); nl_posC[k] = nl_posA[d + k] - B,
+//             num_newlines -= min(d, num_newlines)
+//   text      the suffix from B, read on the device, with 16 zero bytes behind it
+//   stats     one wave per dropped line walks it as index.hip does and counts the lines over
+//             the emit cap and, among each line's emitted tokens, those longer than max_key_len
+struct DropCounters {  // one 64-byte readback, zeroed per drop
+  u64 moved;           // postings moved
+  u64 dropped;         // postings below cut_line
+  u64 cut_byte;        // B: the text bytes removed
+  u32 records;         // records written to C
+  u32 vanished;        // words whose list emptied
+  u32 misplaced;       // a destination outside [valC[p], valC[p+1]), a position >= nC, a key
+                       // order violation, a non-ascending val
+  u32 nc;              // survivors: C's records (the scan's total)
+  u32 overflow_lines;  // dropped lines with more than emits_per_line tokens
+  u32 truncated;       // emitted tokens of the dropped lines longer than max_key_len
+  u32 pad[4];
+};
+static_assert(sizeof(DropCounters) == 64, "DropCounters: one 64-byte readback");
+constexpr int kDropStatWaves = 4;  // waves (lines in flight) per workgroup of the stats walk
+struct DropScratch {
+  DropCounters* ctr = nullptr;
+  u32* k = nullptr;         // [nA] postings of word w below cut_line
+  u64* keep = nullptr;      // [nA] 1: the word survives (the scans read u64 words)
+  u64* pos = nullptr;       // [nA + 1] exclusive scan of keep
+  u32* src_of = nullptr;    // [nA] the source word of C's record p
+  u64* tile_val = nullptr;  // [div_up(nA, kIndexTile) + 1]
+  u64 rec_cap = 0;
+};
+u64 drop_scratch_bytes(u64 rec_cap);
+void drop_scratch_carve(char* base, u64 rec_cap, DropScratch* ws);
+// The word job's token rules, for the statistics of the dropped lines.
+struct DropRules {
+  DelimMask dm{};
+  int emits_per_line = 0, max_key_len = 0;
+};
+// Enqueues the drop of a's first d lines (1 <= d <= a.lines; cut_line = a's first line + d)
+// into c, whose arrays hold a.n records, a.tokens postings, a.bytes + 16 text bytes and
+// a.lines - d line starts (c's n, tokens, bytes and lines are its capacities).  a's line index
+// must exist (a text without tokens: launch_line_index first).  ws.ctr is complete when `s`
+// has drained; C's sizes are nc, moved and a.bytes - cut_byte.
+void launch_drop(const AppendIndex& a, const AppendIndex& c, u32 cut_line, u64 d,
+                 const DropRules& rules, DropScratch& ws, hipStream_t s);
+
 // ---------------- search.hip ----------------
 // All/any/phrase/near word queries over the inverted index launch_index left on the device
 // (engine.hpp "index search"): the key-ordered records, the CSR offsets `val` and the sorted
@@ -1287,6 +1353,7 @@ void launch_string_selftest(const char* blob, const u32* off, u32 n, const char*
 // 573 MB fat binary), +1.3 GB of host memory and ~150 ms per process.
 void warm_module_append();  // (as index: the code object only, no buffers)
 void warm_module_dict();
+void warm_module_drop();  // (as append)
 void warm_module_exchange();
 void warm_module_expr();  // (as search: the code object only, no buffers)
 void warm_module_fuzzy();  // (as search: the code object only, no buffers)
@@ -1312,6 +1379,7 @@ void warm_module_topk();
 inline void warm_kernel_modules() {
   warm_module_append();
   warm_module_dict();
+  warm_module_drop();
   warm_module_exchange();
   warm_module_expr();
   warm_module_fuzzy();

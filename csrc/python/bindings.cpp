@@ -548,6 +548,11 @@ class PyGpuEngine {
     py::gil_scoped_release nogil;
     return eng_.append_index(as_input(text, first_line));
   }
+  // The oldest `lines` lines out of the resident index, compacted on the device.
+  IndexDrop drop_index(u64 lines) {
+    py::gil_scoped_release nogil;
+    return eng_.drop_index(lines);
+  }
   // The resident index downloaded, whatever it was built from.
   PyIndexResult index_resident() {
     py::gil_scoped_release nogil;
@@ -1233,6 +1238,8 @@ PYBIND11_MODULE(_locust, m) {
            "Another batch from the index the last run_index / run_search left on the device.")
       .def("append_index", &PyGpuEngine::append_index, py::arg("text"), py::arg("first_line"),
            "One more block of whole lines into the resident index, merged on the device.")
+      .def("drop_index", &PyGpuEngine::drop_index, py::arg("lines"),
+           "The oldest `lines` lines out of the resident index, compacted on the device.")
       .def("index_resident", &PyGpuEngine::index_resident,
            "The resident index downloaded (IndexResult), whatever it was built from.")
       .def("top_counts", &PyGpuEngine::top_counts, py::arg("records"), py::arg("k"),
@@ -1274,6 +1281,25 @@ PYBIND11_MODULE(_locust, m) {
         d["append_ms"] = a.append_ms;
         return d;
       });
+  py::class_<IndexDrop>(m, "IndexDrop")
+      .def_readonly("dropped_lines", &IndexDrop::dropped_lines)
+      .def_readonly("dropped_tokens", &IndexDrop::dropped_tokens)
+      .def_readonly("dropped_words", &IndexDrop::dropped_words)
+      .def_readonly("dropped_bytes", &IndexDrop::dropped_bytes)
+      .def_readonly("dropped_overflow_lines", &IndexDrop::dropped_overflow_lines)
+      .def_readonly("dropped_truncated", &IndexDrop::dropped_truncated)
+      .def_readonly("first_line", &IndexDrop::first_line)
+      .def_readonly("num_lines", &IndexDrop::num_lines)
+      .def_readonly("num_tokens", &IndexDrop::num_tokens)
+      .def_readonly("num_unique", &IndexDrop::num_unique)
+      .def_readonly("drop_ms", &IndexDrop::drop_ms)
+      .def_readonly("store_bytes", &IndexDrop::store_bytes);
+  m.def("trim_index", [](const PyIndexResult& x, u64 lines, u64 overflow_lines, u64 truncated) {
+    py::gil_scoped_release nogil;
+    return PyIndexResult{trim_index(x.x, lines, overflow_lines, truncated), x.cfg};
+  }, py::arg("x"), py::arg("lines"), py::arg("overflow_lines") = 0, py::arg("truncated") = 0,
+        "The index of x's text without its first `lines` lines (the dropped lines' statistics "
+        "are the caller's to supply).");
   m.def("merge_index", [](const PyIndexResult& a, const PyIndexResult& b) {
     py::gil_scoped_release nogil;
     return PyIndexResult{merge_index(a.x, b.x), a.cfg};

@@ -57,6 +57,7 @@ from .models.wordcount import (  # noqa: E402
     split_blocks,
     top_words_file,
     top_words_text,
+    trim_index,
     wordcount_file,
     wordcount_text,
 )
@@ -87,6 +88,7 @@ __all__ = [
     "search_file",
     "search_text",
     "merge_index",
+    "trim_index",
     "split_blocks",
     "JobConfig",
     "DistConfig",

@@ -284,6 +284,20 @@ class Engine:
         self._next_line += res.block_lines
         return res
 
+    def drop_index(self, lines: int):
+        """The oldest ``lines`` lines out of the index this engine holds on the device
+        (``IndexDrop``): afterwards the resident index is the index of the remaining lines,
+        numbered as before, so its ``first_line`` moves up by ``lines`` and every search
+        answers over the window.  The postings below the cut, the words whose lists empty out,
+        the text and the line starts go; the rest is compacted on the device.  ``lines == 0`` is
+        a no-op, all lines leave an empty index that ``append_index`` goes on from.  Refused
+        with the resident index intact: no resident index, more lines than it holds (GPU
+        engines only)."""
+        if self.cpu:
+            raise _C.LocustError("drop_index needs a GPU engine: the CPU engine keeps no "
+                                 "index (use trim_index(x, lines) on an IndexResult)")
+        return self._eng.drop_index(lines)
+
     def index_resident(self):
         """The index this engine holds on the device, downloaded (``IndexResult``), whatever it
         was built from: a ``run_index``, a ``run_search``, or those and appends."""
@@ -379,6 +393,14 @@ def merge_index(a, b):
     return _C.merge_index(a, b)
 
 
+def trim_index(x, lines: int, overflow_lines: int = 0, truncated: int = 0):
+    """The index of ``x``'s text without its first ``lines`` lines, from the ``IndexResult``
+    alone: the host twin of the device drop.  An index holds no text, so the dropped lines'
+    ``overflow_lines`` and ``truncated`` are the caller's to supply (the dropped block's own
+    index has them); ``max_key_len`` stays, the longest the index has held."""
+    return _C.trim_index(x, lines, overflow_lines, truncated)
+
+
 def split_blocks(text: bytes, block_bytes: int, first_line: int = 0):
     """``text`` cut into line-aligned blocks of at most ``block_bytes`` bytes:
     ``[(offset, bytes, lines, first_line)]``.  Every block but the last ends in a newline; a
@@ -391,57 +413,82 @@ def _blocks(text, block_bytes, first_line):
             _C.split_blocks(text, block_bytes, first_line)]
 
 
-def _index_blocks(cfg, text, first_line, block_bytes):
+def _index_blocks(cfg, text, first_line, block_bytes, keep_blocks=None):
     """(engine holding the index of ``text`` built block by block, or None on the CPU; the CPU
-    backend's merged IndexResult, or None)."""
+    backend's merged IndexResult, or None; the text the index covers).  ``keep_blocks=M``: once
+    more than M blocks are in the index, the oldest block's lines are dropped from it."""
+    if keep_blocks is not None and keep_blocks < 1:
+        raise ValueError("keep_blocks must be >= 1")
     blocks = _blocks(text, block_bytes, first_line)
+    oldest = 0  # the first block still in the index
     if cfg.backend == _C.Backend.cpu:
-        x = _C.cpu_run_index(cfg, blocks[0][0], first_line)
-        for piece, _lines, first in blocks[1:]:
-            x = _C.merge_index(x, _C.cpu_run_index(cfg, piece, first))
-        return None, x
+        parts = [_C.cpu_run_index(cfg, blocks[0][0], first_line)]
+        x = parts[0]
+        for b, (piece, _lines, first) in enumerate(blocks[1:], 1):
+            parts.append(_C.cpu_run_index(cfg, piece, first))
+            x = _C.merge_index(x, parts[b])
+            if keep_blocks is not None and b + 1 - oldest > keep_blocks:
+                x = _C.trim_index(x, blocks[oldest][1], parts[oldest].overflow_lines,
+                                  parts[oldest].truncated)
+                oldest += 1
+        return None, x, b"".join(b[0] for b in blocks[oldest:])
     eng = Engine(cfg, max(max(len(b[0]) for b in blocks), 1), max(max(b[1] for b in blocks), 1))
     eng.run_index(blocks[0][0], first_line)
-    for piece, _lines, _first in blocks[1:]:
+    for b, (piece, _lines, _first) in enumerate(blocks[1:], 1):
         eng.append_index(piece)
-    return eng, None
+        if keep_blocks is not None and b + 1 - oldest > keep_blocks:
+            eng.drop_index(blocks[oldest][1])
+            oldest += 1
+    return eng, None, b"".join(b[0] for b in blocks[oldest:])
 
 
 def index_text(text: bytes, backend: str = "gpu", cfg=None, first_line: int = 0,
-               block_bytes=None, **kw):
+               block_bytes=None, keep_blocks=None, **kw):
     """The inverted index of ``text`` (``IndexResult``); lines are numbered from
     ``first_line``.  ``block_bytes=N``: built block by block (``split_blocks``), the first
-    block indexed and the rest appended, so the engine is sized to one block."""
+    block indexed and the rest appended, so the engine is sized to one block.
+    ``keep_blocks=M`` beside it: a sliding window -- whenever more than ``M`` blocks are in the
+    index the oldest block's lines are dropped (``Engine.drop_index``; ``trim_index`` on the
+    CPU), and the result is the index of the last ``M`` blocks with their own (global) line
+    numbers and ``first_line``."""
     cfg = cfg if cfg is not None else make_config(backend, **kw)
+    if keep_blocks is not None and block_bytes is None:
+        raise ValueError("keep_blocks needs block_bytes")
     if block_bytes is not None:
-        eng, x = _index_blocks(cfg, text, first_line, block_bytes)
+        eng, x, _window = _index_blocks(cfg, text, first_line, block_bytes, keep_blocks)
         return x if eng is None else eng.index_resident()
     nlines = text.count(b"\n") + (1 if text and not text.endswith(b"\n") else 0)
     return Engine(cfg, max(len(text), 1), max(nlines, 1)).run_index(text, first_line)
 
 
 def index_file(path: str, line_start: int = -1, line_end: int = -1, backend: str = "gpu",
-               cfg=None, block_bytes=None, **kw):
+               cfg=None, block_bytes=None, keep_blocks=None, **kw):
     """The inverted index of a file or of its line window, with the file's own (global)
-    line numbers.  ``block_bytes`` as ``index_text`` takes it."""
+    line numbers.  ``block_bytes`` and ``keep_blocks`` as ``index_text`` takes them."""
     cfg = cfg if cfg is not None else make_config(backend, **kw)
     text, nlines, first, _total = _C.load_lines(path, line_start, line_end, cfg.ref_compat)
+    if keep_blocks is not None and block_bytes is None:
+        raise ValueError("keep_blocks needs block_bytes")
     if block_bytes is not None:
-        return index_text(text, cfg=cfg, first_line=first, block_bytes=block_bytes)
+        return index_text(text, cfg=cfg, first_line=first, block_bytes=block_bytes,
+                          keep_blocks=keep_blocks)
     return Engine(cfg, max(len(text), 1), max(nlines, 1)).run_index(text, first)
 
 
 def search_text(text: bytes, queries, mode="all", backend: str = "gpu", cfg=None,
                 first_line: int = 0, rank=None, wildcard=False, within=None, exclude=None,
                 glob=False, ignore_case=False, show=None, fuzzy=False, regex=False, tally=None,
-                block_bytes=None, **kw):
+                block_bytes=None, keep_blocks=None, **kw):
     """All/any/phrase/near word queries over ``text`` (``SearchResult``); see
     ``Engine.run_search``.  ``block_bytes=N``: the index is built block by block
     (``index_text``) and the batch answered from it (on the CPU: from the merged index and the
-    whole text)."""
+    text it covers).  ``keep_blocks=M`` beside it: the batch is answered over the last ``M``
+    blocks only, with their own (global) line numbers."""
     cfg = cfg if cfg is not None else make_config(backend, **kw)
+    if keep_blocks is not None and block_bytes is None:
+        raise ValueError("keep_blocks needs block_bytes")
     if block_bytes is not None:
-        eng, x = _index_blocks(cfg, text, first_line, block_bytes)
+        eng, x, text = _index_blocks(cfg, text, first_line, block_bytes, keep_blocks)
         if eng is not None:
             return eng.search_resident(queries, mode, rank, wildcard, within, exclude, glob,
                                        ignore_case, show, fuzzy, regex, tally)
@@ -458,16 +505,19 @@ def search_text(text: bytes, queries, mode="all", backend: str = "gpu", cfg=None
 def search_file(path: str, queries, mode="all", line_start: int = -1, line_end: int = -1,
                 backend: str = "gpu", cfg=None, rank=None, wildcard=False, within=None,
                 exclude=None, glob=False, ignore_case=False, show=None, fuzzy=False, regex=False,
-                tally=None, block_bytes=None, **kw):
+                tally=None, block_bytes=None, keep_blocks=None, **kw):
     """All/any/phrase/near word queries over a file or its line window, answered with the file's
-    own (global) line numbers.  ``block_bytes`` as ``search_text`` takes it."""
+    own (global) line numbers.  ``block_bytes`` and ``keep_blocks`` as ``search_text`` takes
+    them."""
     cfg = cfg if cfg is not None else make_config(backend, **kw)
     text, nlines, first, _total = _C.load_lines(path, line_start, line_end, cfg.ref_compat)
+    if keep_blocks is not None and block_bytes is None:
+        raise ValueError("keep_blocks needs block_bytes")
     if block_bytes is not None:
         return search_text(text, queries, mode, cfg=cfg, first_line=first, rank=rank,
                            wildcard=wildcard, within=within, exclude=exclude, glob=glob,
                            ignore_case=ignore_case, show=show, fuzzy=fuzzy, regex=regex,
-                           tally=tally, block_bytes=block_bytes)
+                           tally=tally, block_bytes=block_bytes, keep_blocks=keep_blocks)
     return Engine(cfg, max(len(text), 1), max(nlines, 1)).run_search(
         text, queries, mode, first, rank, wildcard, within, exclude, glob, ignore_case, show,
         fuzzy, regex, tally)

@@ -22,14 +22,15 @@ TopResult GpuWordCount::run_top_source(TextSource&, u32) { no_gpu(); }
 TopResult GpuWordCount::top_counts(const KeyCount*, u64, u32) { no_gpu(); }
 IndexResult GpuWordCount::run_index(const TextInput&) { no_gpu(); }
 SearchResult GpuWordCount::run_search(const TextInput&, const std::vector<SearchQuery>&, u64,
-                                      bool, u64, u64) {
+                                      bool, u64, u64, u32) {
   no_gpu();
 }
 SearchResult GpuWordCount::search_resident(const std::vector<SearchQuery>&, u64, bool, u64,
-                                           u64) {
+                                           u64, u32) {
   no_gpu();
 }
-IndexAppend GpuWordCount::append_index(const TextInput&) { no_gpu(); }
+IndexAppend GpuWordCount::append_index(const TextInput&, bool) { no_gpu(); }
+IndexSegments GpuWordCount::segments() const { no_gpu(); }
 IndexDrop GpuWordCount::drop_index(u64) { no_gpu(); }
 IndexResult GpuWordCount::index_resident() { no_gpu(); }
 char* GpuWordCount::input_buffer() { no_gpu(); }

@@ -106,6 +106,11 @@ struct CliArgs {
   bool index = false;  // --index: the result lines carry every word's line numbers
   // --search "w1 w2" (repeatable): the result lines are the queries' answers
   std::vector<std::string> search_args;
+  // corpus: --add FILE (repeatable) names the files behind the first; --in "PATH ..." belongs to
+  // the --search before it; --by-file / --count ask for answers by file
+  std::vector<std::string> add;
+  std::vector<std::string> in_args;
+  u32 by_file = 0;  // kByFileNone / kByFile / kByFileCount
   std::vector<std::string> not_args;  // parallel: the --not words of each --search, joined by ' '
   std::vector<SearchQuery> queries;
   std::string match;  // --match all|any|phrase|near ("": all)
@@ -248,6 +253,16 @@ void help() {
       "                             memory.  The result lines are those of the run without it.  A line\n"
       "                             longer than a block is refused.  With --backend cpu the blocks'\n"
       "                             indexes are merged on the host.  Not with --chunk-mb)\n"
+      "  --add FILE                 (--index / --search, repeatable: one more file behind the first\n"
+      "                             in the same index; lines are numbered through the corpus, every\n"
+      "                             file is cut into blocks of its own with --block-kb; not with a\n"
+      "                             line window, --chunk-mb, --gpus N, the stage split or --top)\n"
+      "  --in \"PATH ...\"            (the --search before it is answered from these files only,\n"
+      "                             named as on the command line)\n"
+      "  --by-file                  (--search: under each query's line one line per file with a hit:\n"
+      "                             its hits and their numbers inside the file; --show prints\n"
+      "                             <path>:<local>: in front of a shown line)\n"
+      "  --count                    (--by-file, and only the counts: hits per query and per file)\n"
       "  --keep-blocks M            (--block-kb: a sliding window over the text -- whenever an append\n"
       "                             leaves more than M blocks in the index, M >= 1, the oldest block's\n"
       "                             lines are dropped from it: their postings, the words that empty\n"
@@ -383,6 +398,19 @@ bool parse(int argc, char** argv, CliArgs* a) {
     } else if (s == "--search") {
       a->search_args.push_back(need("--search"));
       a->not_args.emplace_back();
+      a->in_args.emplace_back();
+    } else if (s == "--add") {
+      a->add.push_back(need("--add"));
+    } else if (s == "--by-file") {
+      a->by_file = std::max(a->by_file, kByFile);
+    } else if (s == "--count") {
+      a->by_file = kByFileCount;
+    } else if (s == "--in") {
+      const std::string v = need("--in");
+      if (a->search_args.empty())
+        throw Error("--in \"" + v + "\" names the files that the --search before it is "
+                    "answered from: give --search first");
+      a->in_args.back() += " " + v;
     } else if (s == "--not") {
       const std::string v = need("--not");
       if (a->search_args.empty())
@@ -639,8 +667,45 @@ bool parse(int argc, char** argv, CliArgs* a) {
     a->queries.push_back(make_search_query(terms, mode, a->wildcard, a->within, exclude, a->glob,
                                            a->fuzzy, a->regex));
   }
+  // corpus: what --add does not go with, and the --in paths as file ids
+  if (!a->add.empty()) {
+    if (!a->index && a->search_args.empty())
+      throw Error("--add FILE puts several files into one index: it goes with --index or "
+                  "--search");
+    if (a->window)
+      throw Error("--add does not go with a line window: every file is indexed whole, and the "
+                  "lines are numbered through the corpus");
+  }
+  if (a->by_file && a->search_args.empty())
+    throw Error("--by-file and --count print a search's hits by file: give --search");
+  for (size_t i = 0; i < a->queries.size(); ++i) {
+    std::vector<std::string> paths{a->file};
+    paths.insert(paths.end(), a->add.begin(), a->add.end());
+    std::string cur;
+    std::vector<u32> ids;
+    const auto take = [&] {
+      if (cur.empty()) return;
+      const auto it = std::find(paths.begin(), paths.end(), cur);
+      if (it == paths.end())
+        throw Error("--in \"" + cur + "\" is none of the files given on the command line (the "
+                    "input file and every --add FILE, spelt as there)");
+      ids.push_back((u32)(it - paths.begin()));
+      cur.clear();
+    };
+    for (const char c : a->in_args[i]) {
+      if (c == ' ' || c == '\t')
+        take();
+      else
+        cur.push_back(c);
+    }
+    take();
+    std::sort(ids.begin(), ids.end());
+    ids.erase(std::unique(ids.begin(), ids.end()), ids.end());
+    a->queries[i].files = ids;
+  }
   if (!a->queries.empty()) {
     check_search_queries(a->queries, a->cfg);
+    check_search_by_file(a->by_file, a->rank, a->show, a->tally);
     if (a->rank && (u64)a->cfg.emits_per_line > kRankMaxEmits)
       throw Error("--rank K takes --emits-per-line <= " + std::to_string(kRankMaxEmits) +
                   " (emits_per_line <= kRankMaxEmits: its scores fit 22 bits)");
@@ -794,6 +859,33 @@ void json_blocks(JsonOut& j, const CliArgs& a) {
   j.u("first_line", g_first_line);
 }
 
+// corpus (--add): the resident files -- path, id, first_line, base, lines -- and the files the
+// window has dropped.
+u64 g_dropped_files = 0;
+void json_files(JsonOut& j, const CliArgs& a, const std::vector<IndexSegment>& segs, u64 first,
+                u64 lines) {
+  if (a.add.empty()) return;
+  IndexSegments t;
+  t.reset(first, lines);
+  if (!segs.empty()) t.segs = segs;
+  std::string arr = "[";
+  for (size_t i = 0; i < t.segs.size(); ++i) {
+    const u32 id = t.segs[i].id;
+    std::string path = id == 0 ? a.file : id <= a.add.size() ? a.add[id - 1] : std::string();
+    std::string esc;
+    for (const char c : path) {
+      if (c == '"' || c == '\\') esc.push_back('\\');
+      esc.push_back(c);
+    }
+    arr += std::string(i ? ", " : "") + "{\"path\": \"" + esc + "\", \"id\": " +
+           std::to_string(id) + ", \"first_line\": " + std::to_string(t.segs[i].first_line) +
+           ", \"base\": " + std::to_string(t.segs[i].base) + ", \"lines\": " +
+           std::to_string(t.lines_of(i)) + "}";
+  }
+  j.kv("files", arr + "]");
+  j.u("dropped_files", g_dropped_files);
+}
+
 const IndexResult* g_index = nullptr;
 void json_index(JsonOut& j, const CliArgs& a) {
   if (!a.index) return;
@@ -803,6 +895,7 @@ void json_index(JsonOut& j, const CliArgs& a) {
     j.num("index_ms", g_index->index_ms);
     j.u("postings", g_index->postings.size());
     j.u("wire_bytes", g_index->wire_bytes);
+    json_files(j, a, g_index->segments, g_index->first_line, g_index->words.num_lines);
   }
 }
 
@@ -834,6 +927,8 @@ void json_search(JsonOut& j, const CliArgs& a) {
     j.u("wire_bytes", g_search->wire_bytes);
     j.u("merged", g_search->merged);
     j.u("walked", g_search->walked);
+    j.u("restricted", g_search->restricted);
+    json_files(j, a, g_search->segments, g_search->first_line, g_search->num_lines);
   }
 }
 
@@ -1036,6 +1131,72 @@ void format_results_or_top(const CliArgs& a, bool cpu_default, const WordCountRe
 
 // The result lines to stdout, or to --result-file (a range reducer on a worker daemon,
 // whose reply carries only the tail of stdout).
+// --by-file / --count: format_search_output's lines with, under each query's line and above its
+// shown and tally lines, one line per file of the query's CSR:
+//   "  file: <path> \t hits: <n> \t lines: <local> <local> ...\n"
+// (ranked: "top:" and <local>:<score>, in rank order; --count: the line ends behind its hits,
+// and the query's line ends behind "hits: <n>" with " \t files: <f>").  With --show a shown
+// line's prefix becomes "<path>:<local>: ".
+void format_search_by_file(const CliArgs& a, const SearchResult& r, std::string* out) {
+  std::string plain;
+  format_search_output(r, &plain, a.mark);
+  if (r.by_file == kByFileNone) {
+    out->append(plain);
+    return;
+  }
+  const auto path_of = [&](u32 id) {
+    return id == 0 ? a.file : id <= a.add.size() ? a.add[id - 1] : "file " + std::to_string(id);
+  };
+  const bool count = r.by_file == kByFileCount;
+  size_t at = 0, q = 0;
+  u64 shown = 0;  // entries of query q - 1 whose shown line is still to come
+  u64 entry = 0;
+  while (at < plain.size()) {
+    size_t nl = plain.find('\n', at);
+    if (nl == std::string::npos) nl = plain.size();
+    std::string line = plain.substr(at, nl - at);
+    at = nl + 1;
+    if (line.compare(0, 12, "print query:") == 0 && q < r.queries.size()) {
+      const u64 f0 = r.file_off[q], f1 = r.file_off[q + 1];
+      if (count) {
+        const size_t cut = line.find(" \t hits: ");
+        if (cut != std::string::npos) {
+          // (the lines stay on the device: the hits are the matches)
+          line = line.substr(0, cut) + " \t hits: " + std::to_string(r.matches[q]);
+        }
+        line += " \t files: " + std::to_string(f1 - f0);
+      }
+      out->append(line + "\n");
+      for (u64 f = f0; f < f1; ++f) {
+        out->append("  file: " + path_of(r.file_ids[f]) + " \t hits: " +
+                    std::to_string(r.file_counts[f]));
+        if (!count) {
+          out->append(r.rank_k ? " \t top:" : " \t lines:");
+          for (u64 j = r.offsets[q]; j < r.offsets[q + 1]; ++j) {
+            if (r.line_file[j] != r.file_ids[f]) continue;
+            out->append(" " + std::to_string(r.line_local[j]));
+            if (r.rank_k) out->append(":" + std::to_string(r.scores[j]));
+          }
+        }
+        out->push_back('\n');
+      }
+      entry = count ? 0 : r.offsets[q];
+      shown = r.show_bytes && !count ? r.offsets[q + 1] - r.offsets[q] : 0;
+      ++q;
+      continue;
+    }
+    if (shown && line.compare(0, 2, "  ") == 0) {  // "  <global>: <bytes>" -> "  <path>:<local>: "
+      const size_t colon = line.find(": ", 2);
+      if (colon != std::string::npos)
+        line = "  " + path_of(r.line_file[entry]) + ":" + std::to_string(r.line_local[entry]) +
+               line.substr(colon);
+      ++entry;
+      --shown;
+    }
+    out->append(line + "\n");
+  }
+}
+
 void emit_results(const CliArgs& a, const std::string& out) {
   if (a.result_file.empty()) {
     std::fflush(stdout);
@@ -1064,7 +1225,7 @@ void print_gpu_result(const CliArgs& a, const WordCountResult& r, const std::vec
                     (unsigned long long)r.truncated, a.cfg.max_key_len);
   std::string out;
   if (srch) {
-    if (!a.quiet) format_search_output(*srch, &out, a.mark);
+    if (!a.quiet) format_search_by_file(a, *srch, &out);
   } else if (idx) {
     if (!a.quiet) format_index_output(*idx, &out);
   } else if (top) {
@@ -1397,6 +1558,61 @@ int run(const CliArgs& a) {
     return 0;
   }
 
+  // ---------------- corpus: the --add files behind the first, in one buffer ----------------
+  // A file that lacks its last newline gets one when another follows (the byte makes no new
+  // line).  Every file begins a segment of the index; --block-kb cuts each file on its own.
+  std::vector<char> corpus;
+  std::vector<TextInput> corpus_files;
+  if (!a.add.empty()) {
+    std::vector<std::pair<u64, u64>> parts;  // (bytes, lines) per file
+    const auto put = [&](const TextInput& in, bool last) {
+      corpus.insert(corpus.end(), in.data, in.data + in.bytes);
+      if (!last && in.bytes && in.data[in.bytes - 1] != '\n') corpus.push_back('\n');
+      parts.emplace_back(in.bytes + (!last && in.bytes && in.data[in.bytes - 1] != '\n'),
+                         in.num_lines);
+    };
+    put(text.input, false);
+    for (size_t i = 0; i < a.add.size(); ++i)
+      put(load_lines(a.add[i], -1, -1, a.cfg.ref_compat).input, i + 1 == a.add.size());
+    u64 off = 0, line = 0;
+    for (const auto& p : parts) {
+      TextInput in;
+      in.data = corpus.data() + off;
+      in.bytes = p.first;
+      in.num_lines = p.second;
+      in.first_line = line;
+      corpus_files.push_back(in);
+      off += p.first;
+      line += p.second;
+    }
+    text.input = TextInput{};
+    text.input.data = corpus.data();
+    text.input.bytes = off;
+    text.input.num_lines = line;
+  }
+  const bool blocked = a.block_given || !a.add.empty();
+  std::vector<char> new_file;  // parallel to the blocks: the block begins a file
+  const auto make_blocks = [&] {
+    std::vector<TextInput> out;
+    new_file.clear();
+    if (corpus_files.empty()) {
+      out = split_blocks(text.input, a.block_kb << 10);
+      new_file.assign(out.size(), 0);
+      return out;
+    }
+    for (size_t f = 0; f < corpus_files.size(); ++f) {
+      const std::vector<TextInput> bs = a.block_given
+                                            ? split_blocks(corpus_files[f], a.block_kb << 10)
+                                            : std::vector<TextInput>{corpus_files[f]};
+      for (size_t j = 0; j < bs.size(); ++j) {
+        out.push_back(bs[j]);
+        new_file.push_back(f > 0 && j == 0);
+      }
+    }
+    return out;
+  };
+  g_dropped_files = 0;
+
   // ---------------- stage 0: full pipeline ----------------
   WordCountResult r;
   TopResult cpu_top;  // --top K on the CPU backend
@@ -1407,11 +1623,12 @@ int run(const CliArgs& a) {
     CpuWordCount eng(a.cfg);
     for (int i = 0; i < a.warmup; ++i) eng.run(text.input);
     for (int i = 0; i < a.iters; ++i) {
-      if (a.block_given) {
+      if (blocked) {
         // per block an index of its own, joined on the host (merge_index); a search then runs
         // over the merged index and the whole text
         const u64 t0 = now_ns();
-        const std::vector<TextInput> blocks = split_blocks(text.input, a.block_kb << 10);
+        const std::vector<TextInput> blocks = make_blocks();
+        g_dropped_files = 0;
         IndexResult x = eng.run_index(blocks[0]);
         // --keep-blocks: the dropped lines' statistics come from each block's own index
         std::vector<std::pair<u64, u64>> stats{{x.words.overflow_lines, x.words.truncated}};
@@ -1423,8 +1640,9 @@ int run(const CliArgs& a) {
           tm.process_ms += y.words.times.process_ms;
           tm.reduce_ms += y.words.times.reduce_ms;
           stats.emplace_back(y.words.overflow_lines, y.words.truncated);
-          x = merge_index(x, y);
+          x = merge_index(x, y, new_file[b] != 0);
           if (a.keep_given && b + 1 - oldest > a.keep_blocks) {
+            g_dropped_files += x.segment_table().drop(blocks[oldest].num_lines);
             x = trim_index(x, blocks[oldest].num_lines, stats[oldest].first, stats[oldest].second);
             ++oldest;
           }
@@ -1440,7 +1658,7 @@ int run(const CliArgs& a) {
         window.num_lines = text.input.first_line + text.input.num_lines - window.first_line;
         if (!a.queries.empty()) {
           cpu_search = search_index(x, window, a.queries, a.cfg, a.rank, a.ignore_case,
-                                    a.show, a.tally);
+                                    a.show, a.tally, a.by_file);
           r = search_stats(cpu_search);
           r.times = x.words.times;
         } else {
@@ -1450,7 +1668,8 @@ int run(const CliArgs& a) {
         r.times.wall_ms = (now_ns() - t0) * 1e-6;
       } else if (!a.queries.empty()) {
         cpu_search =
-            eng.run_search(text.input, a.queries, a.rank, a.ignore_case, a.show, a.tally);
+            eng.run_search(text.input, a.queries, a.rank, a.ignore_case, a.show, a.tally,
+                           a.by_file);
         r = search_stats(cpu_search);
       } else if (a.index) {
         cpu_index = eng.run_index(text.input);
@@ -1467,9 +1686,9 @@ int run(const CliArgs& a) {
     std::printf("CPU sorting %lld nanoseconds \n", ns(r.times.process_ms));
     std::printf("CPU reducing %lld nanoseconds \n", ns(r.times.reduce_ms));
   } else {
-    if (a.block_given) {
+    if (blocked) {
       // the first block indexed, the rest appended on the device; the engine holds one block
-      const std::vector<TextInput> blocks = split_blocks(text.input, a.block_kb << 10);
+      const std::vector<TextInput> blocks = make_blocks();
       u64 max_bytes = 1, max_lines = 1;
       for (const TextInput& b : blocks) {
         max_bytes = std::max(max_bytes, b.bytes);
@@ -1484,8 +1703,9 @@ int run(const CliArgs& a) {
         double index_ms = 0, append_ms = 0, drop_ms = 0;
         size_t oldest = 0;  // the first block still in the index
         u64 first_line = blocks[0].first_line;
+        g_dropped_files = 0;
         for (size_t b = 1; b < blocks.size(); ++b) {
-          const IndexAppend ap = eng.append_index(blocks[b]);
+          const IndexAppend ap = eng.append_index(blocks[b], new_file[b] != 0);
           tm.h2d_ms += ap.times.h2d_ms;
           tm.map_ms += ap.times.map_ms;
           tm.process_ms += ap.times.process_ms;
@@ -1498,10 +1718,11 @@ int run(const CliArgs& a) {
             tm.gpu_ms += dr.drop_ms;
             drop_ms += dr.drop_ms;
             first_line = dr.first_line;
+            g_dropped_files += dr.dropped_files;
           }
         }
         if (!a.queries.empty()) {
-          sr = eng.search_resident(a.queries, a.rank, a.ignore_case, a.show, a.tally);
+          sr = eng.search_resident(a.queries, a.rank, a.ignore_case, a.show, a.tally, a.by_file);
           tm.gpu_ms += sr.times.gpu_ms;
           sr.times = tm;
           sr.index_ms = index_ms;
@@ -1531,7 +1752,8 @@ int run(const CliArgs& a) {
     if (!a.queries.empty()) {  // the word job, the index stage and the search stage
       SearchResult sr;
       for (int i = 0; i < a.warmup + a.iters; ++i) {
-        sr = eng.run_search(text.input, a.queries, a.rank, a.ignore_case, a.show, a.tally);
+        sr = eng.run_search(text.input, a.queries, a.rank, a.ignore_case, a.show, a.tally,
+                            a.by_file);
         if (i >= a.warmup) walls.push_back(sr.times.wall_ms);
       }
       print_gpu_result(a, search_stats(sr), walls, nullptr, nullptr, &sr);
@@ -1568,7 +1790,7 @@ int run(const CliArgs& a) {
                     (unsigned long long)r.truncated, a.cfg.max_key_len);
   std::string out;
   if (!a.queries.empty()) {
-    if (!a.quiet) format_search_output(cpu_search, &out, a.mark);
+    if (!a.quiet) format_search_by_file(a, cpu_search, &out);
     g_search = &cpu_search;
   } else if (a.index) {
     if (!a.quiet) format_index_output(cpu_index, &out);

@@ -1,5 +1,6 @@
 // Shared host-side pieces: logging, errors, env config, tokenizer oracle, result checks.
 #include <algorithm>
+#include <map>
 #include <atomic>
 #include <chrono>
 #include <malloc.h>
@@ -330,6 +331,76 @@ void format_top_output(const TopResult& t, bool cpu_format, std::string* out) {
   }
 }
 
+// ---- corpus: the segment table (engine.hpp) ----
+void IndexSegments::reset(u64 first, u64 lines) {
+  segs.assign(1, IndexSegment{0, first, 0});
+  first_line = first;
+  num_lines = lines;
+  next_id = 1;
+}
+
+void IndexSegments::append(u64 lines, bool new_file) {
+  if (segs.empty()) reset(first_line, num_lines);
+  if (new_file) {
+    // (the host twins' refusal.  DevicePipeline::append_index makes the same check before it
+    // enqueues anything, and that one is what keeps its index intact; the id check below cannot
+    // fire there first: ids are u32 and at most kCorpusMaxFiles segments are resident.)
+    LOCUST_CHECK_ARG(segs.size() < kCorpusMaxFiles,
+                     "append_index: the index holds " + std::to_string(segs.size()) +
+                         " files, the most it takes (kCorpusMaxFiles = " +
+                         std::to_string(kCorpusMaxFiles) + "): drop the oldest first");
+    LOCUST_CHECK_ARG(next_id != 0xffffffffu, "append_index: file ids past 2^32 - 1");
+    segs.push_back(IndexSegment{next_id++, first_line + num_lines, 0});
+  }
+  num_lines += lines;
+}
+
+u64 IndexSegments::drop(u64 lines) {
+  if (segs.empty()) reset(first_line, num_lines);
+  LOCUST_CHECK_ARG(lines <= num_lines, "drop_index: " + std::to_string(lines) +
+                                           " lines to drop, the index holds " +
+                                           std::to_string(num_lines));
+  if (lines == 0) return 0;
+  const u64 cut = first_line + lines;
+  size_t k = 0;  // the last segment that begins at or before the cut: the first to stay
+  while (k + 1 < segs.size() && segs[k + 1].first_line <= cut) ++k;
+  u64 gone = 0;
+  for (size_t i = 0; i < k; ++i) gone += lines_of(i) != 0;
+  segs.erase(segs.begin(), segs.begin() + (std::ptrdiff_t)k);
+  segs[0].base += cut - segs[0].first_line;
+  segs[0].first_line = cut;
+  first_line = cut;
+  num_lines -= lines;
+  return gone;
+}
+
+size_t IndexSegments::locate(u64 line) const {
+  LOCUST_CHECK_ARG(!segs.empty() && line >= first_line && line < first_line + num_lines,
+                   "locate: line " + std::to_string(line) + " outside the resident lines [" +
+                       std::to_string(first_line) + ", " + std::to_string(first_line + num_lines) +
+                       ")");
+  // the last segment with first_line <= line
+  const auto it = std::upper_bound(segs.begin(), segs.end(), line,
+                                   [](u64 l, const IndexSegment& s) { return l < s.first_line; });
+  return (size_t)(it - segs.begin()) - 1;
+}
+
+size_t IndexSegments::find(u32 id) const {
+  const auto it = std::lower_bound(segs.begin(), segs.end(), id,
+                                   [](const IndexSegment& s, u32 i) { return s.id < i; });
+  return it != segs.end() && it->id == id ? (size_t)(it - segs.begin()) : segs.size();
+}
+
+IndexSegments IndexResult::segment_table() const {
+  IndexSegments t;
+  t.reset(first_line, words.num_lines);
+  if (!segments.empty()) {
+    t.segs = segments;
+    t.next_id = segments.back().id + 1;
+  }
+  return t;
+}
+
 // ---- inverted index (engine.hpp) ----
 void validate_index(const IndexResult& r) {
   validate_result(r.words);
@@ -337,6 +408,16 @@ void validate_index(const IndexResult& r) {
     throw Error("LOCUST_CHECK: index has " + std::to_string(r.postings.size()) +
                 " postings, num_tokens=" + std::to_string(r.words.num_tokens));
   const u64 lo = r.first_line, hi = r.first_line + r.words.num_lines;
+  for (size_t i = 0; i < r.segments.size(); ++i) {
+    const IndexSegment& sg = r.segments[i];
+    if ((i == 0 ? sg.first_line != lo : sg.first_line < r.segments[i - 1].first_line ||
+                                            sg.id <= r.segments[i - 1].id) ||
+        sg.first_line > hi || (i && sg.base))
+      throw Error("LOCUST_CHECK: segment " + std::to_string(i) + " (id " + std::to_string(sg.id) +
+                  ", first line " + std::to_string(sg.first_line) + ", base " +
+                  std::to_string(sg.base) + ") does not continue the table over [" +
+                  std::to_string(lo) + ", " + std::to_string(hi) + ")");
+  }
   u64 at = 0, j = 0;
   for (const WordCountEntry e : r.words.entries) {
     for (u64 k = 0; k < e.count; ++k) {
@@ -377,7 +458,7 @@ void format_index_output(const IndexResult& r, std::string* out) {
 }
 
 // ---- appending to the index: the host twin of kernels/append.hip (engine.hpp) ----
-IndexResult merge_index(const IndexResult& a, const IndexResult& b) {
+IndexResult merge_index(const IndexResult& a, const IndexResult& b, bool new_file) {
   LOCUST_CHECK_ARG(b.first_line == a.first_line + a.words.num_lines,
                    "merge_index: the second index starts at line " + std::to_string(b.first_line) +
                        ", the first one ends before line " +
@@ -386,6 +467,11 @@ IndexResult merge_index(const IndexResult& a, const IndexResult& b) {
                    "index: line numbers past 2^32 do not fit a u32 posting");
   IndexResult c;
   c.first_line = a.first_line;
+  {
+    IndexSegments t = a.segment_table();
+    t.append(b.words.num_lines, new_file);
+    c.segments = std::move(t.segs);
+  }
   WordCountResult& w = c.words;
   w.num_lines = a.words.num_lines + b.words.num_lines;
   w.num_tokens = a.words.num_tokens + b.words.num_tokens;
@@ -454,6 +540,11 @@ IndexResult trim_index(const IndexResult& x, u64 lines, u64 dropped_overflow_lin
   const u64 cut = x.first_line + lines;
   IndexResult c;
   c.first_line = cut;
+  {
+    IndexSegments t = x.segment_table();
+    t.drop(lines);
+    c.segments = std::move(t.segs);
+  }
   WordCountResult& w = c.words;
   w.num_lines = x.words.num_lines - lines;
   w.overflow_lines = x.words.overflow_lines - dropped_overflow_lines;
@@ -1061,6 +1152,11 @@ void check_search_queries(const std::vector<SearchQuery>& queries, const JobConf
                          std::to_string(q.excluded) + " exclusion terms of " +
                          std::to_string(q.terms.size()) + "); exclusion terms take lines away "
                          "from what at least one positive term answers");
+    for (size_t f = 1; f < q.files.size(); ++f)
+      LOCUST_CHECK_ARG(q.files[f - 1] < q.files[f],
+                       "search: the file set of query " + std::to_string(i) + " is not strictly "
+                       "ascending (" + std::to_string(q.files[f - 1]) + " stands before " +
+                       std::to_string(q.files[f]) + "): give distinct file ids in order");
     LOCUST_CHECK_ARG(q.prefix.empty() || q.prefix.size() == q.terms.size(),
                      "search: query " + std::to_string(i) + " has " +
                          std::to_string(q.prefix.size()) + " prefix flags for " +
@@ -1251,6 +1347,14 @@ void check_search_show(u64 show, u64 text_bytes) {
   LOCUST_CHECK_ARG(text_bytes < (1ull << 32),
                    "search: show takes a text window of less than 2^32 bytes (a span's start is "
                    "a u32), not " + std::to_string(text_bytes) + ": search a line window");
+}
+
+void check_search_by_file(u32 by_file, u64 rank_k, u64 show, u64 tally) {
+  LOCUST_CHECK_ARG(by_file <= kByFileCount, "search: by_file takes kByFileNone, kByFile or "
+                                            "kByFileCount, not " + std::to_string(by_file));
+  LOCUST_CHECK_ARG(by_file != kByFileCount || (rank_k == 0 && show == 0 && tally == 0),
+                   "search: count_only returns no line, so it goes with neither rank nor show nor "
+                   "tally: ask for by_file to have the lines and the counts");
 }
 
 void check_search_tally(u64 tally) {
@@ -1459,8 +1563,9 @@ void show_lines(const TextInput& text, const std::vector<u64>& line_at, const Jo
 
 SearchResult search_index_impl(const IndexResult& x, const TextInput* text,
                                const std::vector<SearchQuery>& queries, const JobConfig& cfg,
-                               u64 rank_k, bool ignore_case, u64 show, u64 tally) {
+                               u64 rank_k, bool ignore_case, u64 show, u64 tally, u32 by_file) {
   check_search_queries(queries, cfg);
+  check_search_by_file(by_file, rank_k, show, tally);
   const bool patterns = search_has_patterns(queries, ignore_case);
   check_search_rank(rank_k, cfg, patterns);
   LOCUST_CHECK_ARG(show == 0 || text,
@@ -1515,6 +1620,8 @@ SearchResult search_index_impl(const IndexResult& x, const TextInput* text,
   r.rank_k = rank_k;
   r.ignore_case = ignore_case;
   r.emits_per_line = (u64)cfg.emits_per_line;
+  const IndexSegments table = x.segment_table();
+  r.segments = table.segs;
   const size_t n = x.words.entries.size();
   const WordCountEntry* ent = x.words.entries.data();
   std::vector<u64> val(n + 1, 0);
@@ -1692,6 +1799,13 @@ SearchResult search_index_impl(const IndexResult& x, const TextInput* text,
         r.lines.erase(std::remove_if(r.lines.begin() + (std::ptrdiff_t)from, r.lines.end(), excluded),
                       r.lines.end());
     }
+    if (!q.files.empty()) {  // "file sets": the lines whose segment's id is in the set
+      const auto outside = [&](u32 line) {
+        return !std::binary_search(q.files.begin(), q.files.end(), table.segs[table.locate(line)].id);
+      };
+      r.lines.erase(std::remove_if(r.lines.begin() + (std::ptrdiff_t)from, r.lines.end(), outside),
+                    r.lines.end());
+    }
     r.matches.push_back(r.lines.size() - from);
     if (rank_k) {  // the matching lines' scores, the order and the cut
       const u64 N = x.postings.size();
@@ -1726,6 +1840,30 @@ SearchResult search_index_impl(const IndexResult& x, const TextInput* text,
   r.times.wall_ms += r.search_ms;
   if (show) show_lines(*text, line_at, cfg, patterns, (u32)show, &r);
   if (tally) tally_lines(x, tally, &r);
+  if (by_file) {  // "answers by file": every returned line's file, and the counts per query
+    r.by_file = by_file;
+    r.file_off.assign(1, 0);
+    for (size_t qi = 0; qi < queries.size(); ++qi) {
+      std::map<u32, u32> per;  // (ids ascend with the ordinals)
+      for (u64 j = r.offsets[qi]; j < r.offsets[qi + 1]; ++j) {
+        const IndexSegment& sg = table.segs[table.locate(r.lines[j])];
+        r.line_file.push_back(sg.id);
+        r.line_local.push_back((u32)(r.lines[j] - sg.first_line + sg.base));
+        ++per[sg.id];
+      }
+      for (const auto& kv : per) {
+        r.file_ids.push_back(kv.first);
+        r.file_counts.push_back(kv.second);
+      }
+      r.file_off.push_back(r.file_ids.size());
+    }
+    if (by_file == kByFileCount) {  // the lines stay where they are: only the counts are answered
+      r.lines.clear();
+      r.line_file.clear();
+      r.line_local.clear();
+      r.offsets.assign(queries.size() + 1, 0);
+    }
+  }
   if (cfg.check) validate_search(r);
   return r;
 }
@@ -1734,14 +1872,14 @@ SearchResult search_index_impl(const IndexResult& x, const TextInput* text,
 
 SearchResult search_index(const IndexResult& x, const std::vector<SearchQuery>& queries,
                           const JobConfig& cfg, u64 rank_k, bool ignore_case, u64 show,
-                          u64 tally) {
-  return search_index_impl(x, nullptr, queries, cfg, rank_k, ignore_case, show, tally);
+                          u64 tally, u32 by_file) {
+  return search_index_impl(x, nullptr, queries, cfg, rank_k, ignore_case, show, tally, by_file);
 }
 
 SearchResult search_index(const IndexResult& x, const TextInput& text,
                           const std::vector<SearchQuery>& queries, const JobConfig& cfg,
-                          u64 rank_k, bool ignore_case, u64 show, u64 tally) {
-  return search_index_impl(x, &text, queries, cfg, rank_k, ignore_case, show, tally);
+                          u64 rank_k, bool ignore_case, u64 show, u64 tally, u32 by_file) {
+  return search_index_impl(x, &text, queries, cfg, rank_k, ignore_case, show, tally, by_file);
 }
 
 namespace {
@@ -1798,6 +1936,69 @@ void validate_tally(const SearchResult& r) {
   }
 }
 
+// validate_search's part for engine.hpp "answers by file".
+void validate_by_file(const SearchResult& r, const IndexSegments& table) {
+  if (r.by_file == kByFileNone) {
+    if (!r.line_file.empty() || !r.line_local.empty() || !r.file_off.empty() ||
+        !r.file_ids.empty() || !r.file_counts.empty())
+      throw Error("LOCUST_CHECK: search result without by_file holds answers by file");
+    return;
+  }
+  const size_t Q = r.queries.size();
+  const bool count_only = r.by_file == kByFileCount;
+  if (r.file_off.size() != Q + 1 || r.file_off.front() != 0 ||
+      r.file_off.back() != r.file_ids.size() || r.file_counts.size() != r.file_ids.size() ||
+      r.line_file.size() != r.lines.size() || r.line_local.size() != r.lines.size() ||
+      (count_only && (!r.lines.empty() || r.rank_k || r.show_bytes || r.tally_k)))
+    throw Error("LOCUST_CHECK: by-file offsets do not span the " +
+                std::to_string(r.file_ids.size()) + " files of " + std::to_string(Q) +
+                " queries, or its per-line arrays the " + std::to_string(r.lines.size()) +
+                " lines");
+  for (size_t j = 0; j < r.lines.size(); ++j) {  // ids and local numbers agree with the table
+    const u64 l = r.lines[j];
+    if (l < table.first_line || l >= table.first_line + table.num_lines) continue;  // (reported)
+    const IndexSegment& sg = table.segs[table.locate(l)];
+    if (r.line_file[j] != sg.id || r.line_local[j] != l - sg.first_line + sg.base)
+      throw Error("LOCUST_CHECK: line " + std::to_string(l) + " is reported as line " +
+                  std::to_string(r.line_local[j]) + " of file " + std::to_string(r.line_file[j]) +
+                  ", the table says line " + std::to_string(l - sg.first_line + sg.base) +
+                  " of file " + std::to_string(sg.id));
+  }
+  for (size_t q = 0; q < Q; ++q) {
+    if (r.file_off[q + 1] < r.file_off[q] || r.file_off[q + 1] > r.file_ids.size())
+      throw Error("LOCUST_CHECK: by-file offsets decrease at query " + std::to_string(q));
+    u64 sum = 0;
+    for (u64 f = r.file_off[q]; f < r.file_off[q + 1]; ++f) {
+      if (r.file_counts[f] == 0 || (f > r.file_off[q] && r.file_ids[f] <= r.file_ids[f - 1]))
+        throw Error("LOCUST_CHECK: files of query " + std::to_string(q) +
+                    " not ascending, or one without a line, at position " +
+                    std::to_string(f - r.file_off[q]));
+      sum += r.file_counts[f];
+    }
+    const u64 returned = count_only ? r.matches[q] : r.offsets[q + 1] - r.offsets[q];
+    if (sum != returned)
+      throw Error("LOCUST_CHECK: the file counts of query " + std::to_string(q) + " add up to " +
+                  std::to_string(sum) + ", it returns " + std::to_string(returned) + " lines");
+    if (!count_only) {  // ... and they count the lines' own files
+      std::map<u32, u64> per;
+      for (u64 j = r.offsets[q]; j < r.offsets[q + 1]; ++j) ++per[r.line_file[j]];
+      u64 f = r.file_off[q];
+      for (const auto& kv : per) {
+        if (f >= r.file_off[q + 1] || r.file_ids[f] != kv.first || r.file_counts[f] != kv.second)
+          throw Error("LOCUST_CHECK: the file counts of query " + std::to_string(q) +
+                      " disagree with its lines' files at file " + std::to_string(kv.first));
+        ++f;
+      }
+    }
+    // (under a file set every counted file is a selected one)
+    const std::vector<u32>& fs = r.queries[q].files;
+    for (u64 f = r.file_off[q]; !fs.empty() && f < r.file_off[q + 1]; ++f)
+      if (!std::binary_search(fs.begin(), fs.end(), r.file_ids[f]))
+        throw Error("LOCUST_CHECK: query " + std::to_string(q) + " counts file " +
+                    std::to_string(r.file_ids[f]) + ", outside its file set");
+  }
+}
+
 }  // namespace
 
 void validate_search(const SearchResult& r) {
@@ -1815,11 +2016,23 @@ void validate_search(const SearchResult& r) {
   // (pattern terms' lists may overlap: one token may count for every term of a query)
   const u64 score_max = 32 * r.emits_per_line *
                         (search_has_patterns(r.queries, r.ignore_case) ? kSearchMaxTerms : 1);
+  IndexSegments table;  // "file sets": under a set, every line lies in a selected file
+  table.reset(r.first_line, r.num_lines);
+  if (!r.segments.empty()) table.segs = r.segments;
   for (size_t q = 0; q + 1 < r.offsets.size(); ++q) {
     if (r.offsets[q + 1] < r.offsets[q] || r.offsets[q + 1] > r.lines.size())
       throw Error("LOCUST_CHECK: search offsets decrease at query " + std::to_string(q));
+    const std::vector<u32>& fs = r.queries[q].files;
+    for (u64 j = r.offsets[q]; !fs.empty() && j < r.offsets[q + 1]; ++j) {
+      const u64 l = r.lines[j];
+      if (l < lo || l >= hi) continue;  // (reported below)
+      const u32 id = table.segs[table.locate(l)].id;
+      if (!std::binary_search(fs.begin(), fs.end(), id))
+        throw Error("LOCUST_CHECK: line " + std::to_string(l) + " of query " + std::to_string(q) +
+                    " lies in file " + std::to_string(id) + ", outside the query's file set");
+    }
     const u64 returned = r.offsets[q + 1] - r.offsets[q];
-    if (r.rank_k ? returned > std::min<u64>(r.rank_k, r.matches[q]) : returned != r.matches[q])
+    if (r.by_file == kByFileCount ? returned != 0 : r.rank_k ? returned > std::min<u64>(r.rank_k, r.matches[q]) : returned != r.matches[q])
       throw Error("LOCUST_CHECK: query " + std::to_string(q) + " returns " +
                   std::to_string(returned) + " lines of " + std::to_string(r.matches[q]) +
                   " matches");
@@ -1845,6 +2058,7 @@ void validate_search(const SearchResult& r) {
     }
   }
   validate_tally(r);
+  validate_by_file(r, table);
   if (r.show_bytes == 0) {
     if (!r.text.empty() || !r.text_off.empty() || !r.spans.empty() || !r.span_off.empty() ||
         r.cut_lines)

@@ -136,12 +136,13 @@ IndexResult CpuWordCount::run_index(const TextInput& in) {
 
 SearchResult CpuWordCount::run_search(const TextInput& in,
                                       const std::vector<SearchQuery>& queries, u64 rank_k,
-                                      bool ignore_case, u64 show, u64 tally) {
+                                      bool ignore_case, u64 show, u64 tally,
+                                      u32 by_file) {
   check_search_queries(queries, cfg_);  // (before the index is built)
   check_search_rank(rank_k, cfg_, search_has_patterns(queries, ignore_case));
   check_search_show(show, in.bytes);
   check_search_tally(tally);
-  return search_index(run_index(in), in, queries, cfg_, rank_k, ignore_case, show, tally);
+  return search_index(run_index(in), in, queries, cfg_, rank_k, ignore_case, show, tally, by_file);
 }
 
 std::vector<PackedKey> CpuWordCount::run_map_stage(const TextInput& in, WordCountResult* stats) {

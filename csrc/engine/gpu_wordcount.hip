@@ -51,14 +51,19 @@ TopResult GpuWordCount::top_counts(const KeyCount* recs, u64 n, u32 k) {
 IndexResult GpuWordCount::run_index(const TextInput& in) { return impl_->run_index(in); }
 SearchResult GpuWordCount::run_search(const TextInput& in,
                                       const std::vector<SearchQuery>& queries, u64 rank_k,
-                                      bool ignore_case, u64 show, u64 tally) {
-  return impl_->run_search(in, queries, rank_k, ignore_case, show, tally);
+                                      bool ignore_case, u64 show, u64 tally,
+                                      u32 by_file) {
+  return impl_->run_search(in, queries, rank_k, ignore_case, show, tally, by_file);
 }
 SearchResult GpuWordCount::search_resident(const std::vector<SearchQuery>& queries, u64 rank_k,
-                                           bool ignore_case, u64 show, u64 tally) {
-  return impl_->search_resident(queries, rank_k, ignore_case, show, tally);
+                                           bool ignore_case, u64 show, u64 tally,
+                                           u32 by_file) {
+  return impl_->search_resident(queries, rank_k, ignore_case, show, tally, by_file);
 }
-IndexAppend GpuWordCount::append_index(const TextInput& in) { return impl_->append_index(in); }
+IndexAppend GpuWordCount::append_index(const TextInput& in, bool new_file) {
+  return impl_->append_index(in, new_file);
+}
+IndexSegments GpuWordCount::segments() const { return impl_->segments(); }
 IndexDrop GpuWordCount::drop_index(u64 lines) { return impl_->drop_index(lines); }
 IndexResult GpuWordCount::index_resident() { return impl_->index_resident(); }
 GpuWordCount::Stats GpuWordCount::stats() const {
@@ -80,7 +85,7 @@ GpuWordCount::Stats GpuWordCount::stats() const {
                    (impl_->d_spat ? search_pattern_bytes() : 0) +
                    (impl_->d_sexpr ? search_expr_bytes() : 0) + impl_->show_entry_cap_bytes +
                    impl_->sshow.cap_text + impl_->sshow.cap_spans * 3 * sizeof(u32) +
-                   impl_->tally_entry_cap_bytes + impl_->tally_pair_cap_bytes;
+                   impl_->tally_entry_cap_bytes + impl_->tally_pair_cap_bytes + impl_->corpus_bytes + impl_->byfile_bytes;
   return s;
 }
 

@@ -578,6 +578,10 @@ DevicePipeline::~DevicePipeline() {
   if (d_srx) (void)hipFree(d_srx);
   pinned_free(h_srx);
   if (d_sexpr) (void)hipFree(d_sexpr);
+  if (d_corpus) (void)hipFree(d_corpus);
+  if (d_byfile) (void)hipFree(d_byfile);
+  pinned_free(h_byfile);
+  pinned_free(h_corpus);
   pinned_free(h_sexpr);
   pinned_free(h_supload);
   pinned_free(h_sres);
@@ -2060,6 +2064,8 @@ void DevicePipeline::keep_index(const TextInput& in, const WordCountResult& r, u
   idx_tokens = T;
   idx_in_store = false;  // (it lives in the pass buffers until an append moves it)
   idx_ends_nl = in.bytes == 0 || in.data[in.bytes - 1] == '\n';
+  idx_segs.reset(in.first_line, in.num_lines);  // one file: "corpus"
+  corpus_dirty = true;
   idx_resident = true;
 }
 
@@ -2103,7 +2109,8 @@ constexpr u64 kSearchQT = (u64)kSearchMaxQueries * kSearchMaxTerms;
 constexpr u64 kSearchResLen = 64;
 constexpr u64 kSearchResOff = kSearchResLen + kSearchQT * sizeof(u32);
 constexpr u64 kSearchResHits = kSearchResOff + ((u64)kSearchMaxQueries + 1) * sizeof(u64);
-constexpr u64 kSearchResBytes = kSearchResHits + (u64)kSearchMaxQueries * sizeof(u32);
+constexpr u64 kSearchResCorpus = kSearchResHits + (u64)kSearchMaxQueries * sizeof(u32);
+constexpr u64 kSearchResBytes = kSearchResCorpus + 64;  // (CorpusCounters: "file sets")
 }  // namespace
 
 void DevicePipeline::ensure_search() {
@@ -2194,6 +2201,178 @@ void DevicePipeline::ensure_search_expr() {
   LOCUST_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&d_sexpr), search_expr_bytes()));
   h_sexpr = static_cast<u32*>(pinned_alloc(search_expr_upload_bytes(kSearchMaxQueries),
                                            hipHostMallocDefault, "search expressions"));
+}
+
+void DevicePipeline::ensure_corpus(u64 segments, u64 sets) {
+  if (d_corpus && scorpus.seg_cap >= segments && scorpus.set_cap >= sets) return;
+  // first batch of this engine with a file set, or one that outgrows the arrays (engines that
+  // never see one keep their footprint)
+  sync();
+  if (d_corpus) LOCUST_HIP_CHECK(hipFree(d_corpus));
+  d_corpus = nullptr;
+  pinned_free(h_corpus);
+  h_corpus = nullptr;
+  scorpus = CorpusSets{};
+  corpus_bytes = 0;
+  const u64 seg_cap = std::min<u64>(align_up(segments + segments / 2, (u64)1024), kCorpusMaxFiles);
+  const u64 set_cap = std::min<u64>(align_up(sets, (u64)16), kSearchMaxQueries);
+  const u64 bytes = corpus_sets_bytes(seg_cap, set_cap);
+  size_t fr = 0, tot = 0;
+  LOCUST_HIP_CHECK(hipMemGetInfo(&fr, &tot));
+  if ((double)bytes > kHbmUsable * (double)fr)
+    throw Error("search: the file-set arrays (" + std::to_string(bytes) + " B for " +
+                std::to_string(seg_cap) + " segments and " + std::to_string(set_cap) +
+                " sets) do not fit the free device memory (" + std::to_string(fr) + " B free of " +
+                std::to_string(tot) + " B)");
+  LOCUST_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&d_corpus), bytes));
+  corpus_bytes = bytes;
+  corpus_sets_carve(d_corpus, seg_cap, set_cap, &scorpus);
+  h_corpus = static_cast<u32*>(pinned_alloc(
+      (2 * seg_cap + kSearchMaxQueries + set_cap * div_up(seg_cap, (u64)32)) * sizeof(u32),
+      hipHostMallocDefault, "search file sets"));
+  corpus_dirty = true;
+}
+
+void DevicePipeline::corpus_restrict(const std::vector<SearchQuery>& queries, u64 H) {
+  const u32 Q = (u32)queries.size();
+  const u64 S = idx_segs.segs.size();
+  // one bitmap per distinct set of the batch
+  std::map<std::vector<u32>, u32> set_index;
+  std::vector<u32> row_of(Q, kCorpusNoSet);
+  for (u32 q = 0; q < Q; ++q)
+    if (!queries[q].files.empty())
+      row_of[q] = set_index.emplace(queries[q].files, (u32)set_index.size()).first->second;
+  const u64 D = set_index.size();
+  ensure_corpus(S, D);
+  const u64 words = div_up(S, (u64)32);
+  u32* h_table = h_corpus;
+  u32* h_qset = h_corpus + scorpus.seg_cap;
+  u32* h_maps = h_qset + kSearchMaxQueries;
+  (void)h_table;
+  corpus_sync_table();
+  std::copy(row_of.begin(), row_of.end(), h_qset);
+  std::memset(h_maps, 0, (size_t)(D * words) * sizeof(u32));
+  for (const auto& kv : set_index)
+    for (const u32 id : kv.first) {  // (an id that is not resident has no bit)
+      const size_t o = idx_segs.find(id);
+      if (o < S) h_maps[(u64)kv.second * words + (o >> 5)] |= 1u << (o & 31);
+    }
+  LOCUST_HIP_CHECK(hipMemcpyAsync(scorpus.q_set, h_qset, (u64)Q * sizeof(u32),
+                                  hipMemcpyHostToDevice, stream));
+  LOCUST_HIP_CHECK(hipMemcpyAsync(scorpus.bitmaps, h_maps, D * words * sizeof(u32),
+                                  hipMemcpyHostToDevice, stream));
+  launch_corpus_restrict(idx_view, sbatch, scorpus, (u32)S, (u32)D, Q, H, shits, stream);
+}
+
+void DevicePipeline::corpus_sync_table() {
+  if (!corpus_dirty) return;
+  const u64 S = idx_segs.segs.size();
+  // (the ids' upload half: the words behind the bitmaps' part of the pinned buffer)
+  u32* h_table = h_corpus;
+  u32* h_ids = h_corpus + scorpus.seg_cap + kSearchMaxQueries +
+               scorpus.set_cap * div_up(scorpus.seg_cap, (u64)32);
+  for (u64 i = 0; i < S; ++i) {
+    h_table[i] = (u32)idx_segs.segs[i].first_line;
+    h_ids[i] = idx_segs.segs[i].id;
+  }
+  LOCUST_HIP_CHECK(hipMemcpyAsync(scorpus.table, h_table, S * sizeof(u32), hipMemcpyHostToDevice,
+                                  stream));
+  LOCUST_HIP_CHECK(hipMemcpyAsync(scorpus.ids, h_ids, S * sizeof(u32), hipMemcpyHostToDevice,
+                                  stream));
+  corpus_dirty = false;
+}
+
+void DevicePipeline::by_file_stage(u32 Q, const u64* offsets, u64 E, bool ranked, u32 by_file,
+                                   SearchResult* r) {
+  TraceRange tr("locust:by_file");
+  const bool count_only = by_file == kByFileCount;
+  r->by_file = by_file;
+  const u64 S = idx_segs.segs.size();
+  ensure_corpus(S, 0);
+  if (!ev_byfile[0])
+    for (auto& e : ev_byfile) LOCUST_HIP_CHECK(hipEventCreate(&e));
+  if (!d_byfile || sbyfile.cap < E) {
+    sync();
+    if (d_byfile) LOCUST_HIP_CHECK(hipFree(d_byfile));
+    d_byfile = nullptr;
+    sbyfile = CorpusByFile{};
+    byfile_bytes = 0;
+    const u64 cap = align_up(std::max<u64>(E + E / 2, 1), (u64)kCorpusTile);
+    u64 bytes = 0;
+    corpus_by_file_carve(nullptr, cap, nullptr, &bytes);
+    size_t fr = 0, tot = 0;
+    LOCUST_HIP_CHECK(hipMemGetInfo(&fr, &tot));
+    if ((double)bytes > kHbmUsable * (double)fr)
+      throw Error("by_file: the stage's arrays (" + std::to_string(bytes) + " B for " +
+                  std::to_string(E) + " returned lines) do not fit the free device memory (" +
+                  std::to_string(fr) + " B free of " + std::to_string(tot) + " B)");
+    LOCUST_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&d_byfile), bytes));
+    byfile_bytes = bytes;
+    corpus_by_file_carve(d_byfile, cap, &sbyfile);
+  }
+  constexpr u64 kHdr = 64 + ((u64)kSearchMaxQueries + 1) * sizeof(u64);
+  // (room for the worst case: a run per returned line, and the two per-line arrays)
+  const u64 need = kHdr + 4 * E * sizeof(u32);
+  if (h_byfile_cap < need) {
+    pinned_free(h_byfile);
+    h_byfile = nullptr;
+    h_byfile_cap = align_up(need, (u64)1 << 16);
+    h_byfile = static_cast<char*>(pinned_alloc(h_byfile_cap, hipHostMallocDefault, "by-file answer"));
+  }
+  CorpusCounters* h_cc = reinterpret_cast<CorpusCounters*>(h_byfile);
+  u64* h_foff = reinterpret_cast<u64*>(h_byfile + 64);
+  u32* h_arr = reinterpret_cast<u32*>(h_byfile + kHdr);
+  corpus_sync_table();
+  LOCUST_HIP_CHECK(hipEventRecord(ev_byfile[0], stream));
+  launch_corpus_by_file(scorpus, (u32)S, idx_segs.segs[0].base, offsets, Q, E, ranked, shits,
+                        sbyfile, h_plan, stream);
+  LOCUST_HIP_CHECK(hipMemcpyAsync(h_cc, sbyfile.ctr, sizeof(CorpusCounters), hipMemcpyDeviceToHost,
+                                  stream));
+  LOCUST_HIP_CHECK(hipMemcpyAsync(h_foff, sbyfile.file_off, ((u64)Q + 1) * sizeof(u64),
+                                  hipMemcpyDeviceToHost, stream));
+  sync();
+  const u64 F = h_cc->runs;
+  if (h_cc->unlocated || F > E || (E != 0) != (F != 0) || h_foff[0] != 0 || h_foff[Q] != F)
+    throw Error("by_file: " + std::to_string(F) + " (query, file) runs among " +
+                std::to_string(E) + " returned lines, " + std::to_string(h_cc->unlocated) +
+                " of them outside the table or their query; the offsets end at " +
+                std::to_string(h_foff[Q]));
+  u32* h_ids = h_arr;
+  u32* h_cnt = h_arr + F;
+  u32* h_lf = h_cnt + F;
+  u32* h_ll = h_lf + E;
+  if (F) {
+    LOCUST_HIP_CHECK(hipMemcpyAsync(h_ids, sbyfile.file_ids, F * sizeof(u32),
+                                    hipMemcpyDeviceToHost, stream));
+    LOCUST_HIP_CHECK(hipMemcpyAsync(h_cnt, sbyfile.file_counts, F * sizeof(u32),
+                                    hipMemcpyDeviceToHost, stream));
+  }
+  if (E && !count_only) {
+    LOCUST_HIP_CHECK(hipMemcpyAsync(h_lf, sbyfile.line_file, E * sizeof(u32),
+                                    hipMemcpyDeviceToHost, stream));
+    LOCUST_HIP_CHECK(hipMemcpyAsync(h_ll, sbyfile.line_local, E * sizeof(u32),
+                                    hipMemcpyDeviceToHost, stream));
+  }
+  LOCUST_HIP_CHECK(hipEventRecord(ev_byfile[1], stream));
+  sync();
+  r->file_off.assign(h_foff, h_foff + Q + 1);
+  r->file_ids.assign(h_ids, h_ids + F);
+  r->file_counts.assign(h_cnt, h_cnt + F);
+  if (!count_only) {
+    r->line_file.assign(h_lf, h_lf + E);
+    r->line_local.assign(h_ll, h_ll + E);
+  }
+  r->by_file_ms = ms_between(ev_byfile[0], ev_byfile[1]);
+  r->wire_bytes += sizeof(CorpusCounters) + ((u64)Q + 1) * sizeof(u64) + 2 * F * sizeof(u32) +
+                   (count_only ? 0 : 2 * E * sizeof(u32));
+}
+
+IndexSegments DevicePipeline::segments() const {
+  if (!idx_resident)
+    throw Error("segments: the index on the device is stale -- this engine's last job was not "
+                "a run_index, a run_search, an append_index or a drop_index; run one of them "
+                "first");
+  return idx_segs;
 }
 
 void DevicePipeline::check_search_batch(const std::vector<SearchQuery>& queries, u64 rank_k,
@@ -2490,7 +2669,8 @@ void DevicePipeline::tally_stage(u32 Q, const u64* offsets, u64 E, u32 K, Search
 }
 
 void DevicePipeline::search_stage(const std::vector<SearchQuery>& queries, u64 rank_k,
-                                  bool ignore_case, u32 show, u32 tally, SearchResult* r) {
+                                  bool ignore_case, u32 show, u32 tally, u32 by_file,
+                                  SearchResult* r) {
   TraceRange tr("locust:search");
   const u32 Q = (u32)queries.size();
   r->queries = queries;
@@ -2504,6 +2684,7 @@ void DevicePipeline::search_stage(const std::vector<SearchQuery>& queries, u64 r
   r->rank_k = rank_k;
   r->ignore_case = ignore_case;
   r->emits_per_line = (u64)cfg.emits_per_line;
+  r->segments = idx_segs.segs;
   r->offsets.assign((size_t)Q + 1, 0);
   r->matches.assign((size_t)Q, 0);
   r->term_counts.assign((size_t)Q * kSearchMaxTerms, 0);
@@ -2544,6 +2725,10 @@ void DevicePipeline::search_stage(const std::vector<SearchQuery>& queries, u64 r
     sync();
     if (show) show_stage(0, nullptr, 0, show, r);
     if (tally) tally_stage(0, nullptr, 0, tally, r);
+    if (by_file) {  // no query: an empty CSR
+      r->by_file = by_file;
+      r->file_off.assign(1, 0);
+    }
     return;
   }
   // the batch: q_meta | the terms' keys, packed exactly as the map packs them | the windows,
@@ -2681,7 +2866,8 @@ void DevicePipeline::search_stage(const std::vector<SearchQuery>& queries, u64 r
     LOCUST_HIP_CHECK(hipMemcpyAsync(h_hits, sbatch.q_hits, (u64)Q * sizeof(u32),
                                     hipMemcpyDeviceToHost, stream));
   sync();
-  const u64 H = h_sc->written, C = h_sc->cands, NC = h_sc->ncands;
+  u64 H = h_sc->written;
+  const u64 C = h_sc->cands, NC = h_sc->ncands;
   if (h_sc->merge_n != (u32)X || h_sc->unmerged)
     throw Error("search: " + std::to_string(h_sc->merge_n) + " of " + std::to_string(X) +
                 " list elements of prefix terms merged, " + std::to_string(h_sc->unmerged) +
@@ -2697,6 +2883,33 @@ void DevicePipeline::search_stage(const std::vector<SearchQuery>& queries, u64 r
     throw Error("search: " + std::to_string(NC) + " near candidates, " +
                 std::to_string(h_sc->nverified) + " of them verified, the lists hold " +
                 std::to_string(B) + " elements");
+  // "file sets": a batch in which a query names one keeps the pairs of its files only, before
+  // anything is sorted or scored; every other batch goes on as it always did
+  bool restrict = false;
+  for (const SearchQuery& sq : queries) restrict |= !sq.files.empty();
+  u64 corpus_wire = 0;
+  if (restrict) {
+    const u64 H0 = H;
+    corpus_restrict(queries, H0);
+    CorpusCounters* h_cc = reinterpret_cast<CorpusCounters*>(h_sres + kSearchResCorpus);
+    LOCUST_HIP_CHECK(hipMemcpyAsync(h_sc, sbatch.ctr, sizeof(SearchCounters),
+                                    hipMemcpyDeviceToHost, stream));
+    LOCUST_HIP_CHECK(hipMemcpyAsync(h_cc, scorpus.ctr, sizeof(CorpusCounters),
+                                    hipMemcpyDeviceToHost, stream));
+    if (rank_k)
+      LOCUST_HIP_CHECK(hipMemcpyAsync(h_hits, sbatch.q_hits, (u64)Q * sizeof(u32),
+                                      hipMemcpyDeviceToHost, stream));
+    sync();
+    H = h_sc->written;
+    if (h_cc->stray || h_cc->kept != H || H > H0 || h_sc->sort_n != H)
+      throw Error("search: the restrict stage kept " + std::to_string(h_cc->kept) + " of " +
+                  std::to_string(H0) + " hits (" + std::to_string(h_sc->sort_n) +
+                  " handed to the sort), " + std::to_string(h_cc->stray) +
+                  " of them naming no query or no segment");
+    r->restricted = H0 - H;
+    corpus_wire = sizeof(SearchCounters) + sizeof(CorpusCounters) +
+                  (rank_k ? (u64)Q * sizeof(u32) : 0);
+  }
   // ranked: R lines and R scores come back, R = the sum of min(matches, K)
   u64 R = 0, M = 0;
   if (rank_k)
@@ -2745,7 +2958,9 @@ void DevicePipeline::search_stage(const std::vector<SearchQuery>& queries, u64 r
     r->scores.assign(h_slines + R, h_slines + 2 * R);
     for (u64 i = 0; i < (u64)Q * kSearchMaxTerms; ++i) r->term_counts[i] = h_tlen[i];
     r->wire_bytes = ((u64)Q + 1) * sizeof(u64) + (u64)Q * sizeof(u32) + 2 * R * sizeof(u32) +
-                    (u64)Q * kSearchMaxTerms * sizeof(u32) + 3 * sizeof(SearchCounters);
+                    (u64)Q * kSearchMaxTerms * sizeof(u32) + 3 * sizeof(SearchCounters) +
+                    corpus_wire;
+    if (by_file) by_file_stage(Q, sbatch.out_off, R, true, by_file, r);
     if (show) show_stage(Q, sbatch.out_off, R, show, r);
     if (tally) tally_stage(Q, sbatch.out_off, R, tally, r);
     return;
@@ -2754,7 +2969,8 @@ void DevicePipeline::search_stage(const std::vector<SearchQuery>& queries, u64 r
   launch_search_order(idx_view, sbatch, Q, H, shits, h_plan, stream);
   LOCUST_HIP_CHECK(hipMemcpyAsync(h_off, sbatch.offsets, ((u64)Q + 1) * sizeof(u64),
                                   hipMemcpyDeviceToHost, stream));
-  if (H)
+  const bool count_only = by_file == kByFileCount;  // (the lines stay on the device)
+  if (H && !count_only)
     LOCUST_HIP_CHECK(hipMemcpyAsync(h_slines, shits.lines, H * sizeof(u32), hipMemcpyDeviceToHost,
                                     stream));
   LOCUST_HIP_CHECK(hipMemcpyAsync(h_sc, sbatch.ctr, sizeof(SearchCounters), hipMemcpyDeviceToHost,
@@ -2767,20 +2983,25 @@ void DevicePipeline::search_stage(const std::vector<SearchQuery>& queries, u64 r
   if (h_off[Q] != H)
     throw Error("search: the per-query hit counts add up to " + std::to_string(h_off[Q]) +
                 ", the hit kernel wrote " + std::to_string(H));
-  r->offsets.assign(h_off, h_off + Q + 1);
   for (u32 q = 0; q < Q; ++q) r->matches[q] = h_off[q + 1] - h_off[q];
-  r->lines.assign(h_slines, h_slines + H);
+  if (!count_only) {
+    r->offsets.assign(h_off, h_off + Q + 1);
+    r->lines.assign(h_slines, h_slines + H);
+  }
   for (u64 i = 0; i < (u64)Q * kSearchMaxTerms; ++i) r->term_counts[i] = h_tlen[i];
-  r->wire_bytes = ((u64)Q + 1) * sizeof(u64) + H * sizeof(u32) +
-                  (u64)Q * kSearchMaxTerms * sizeof(u32) + 3 * sizeof(SearchCounters);
+  r->wire_bytes = ((u64)Q + 1) * sizeof(u64) + (count_only ? 0 : H * sizeof(u32)) +
+                  (u64)Q * kSearchMaxTerms * sizeof(u32) + 3 * sizeof(SearchCounters) +
+                  corpus_wire;
+  if (by_file) by_file_stage(Q, sbatch.offsets, H, false, by_file, r);
   if (show) show_stage(Q, sbatch.offsets, H, show, r);
   if (tally) tally_stage(Q, sbatch.offsets, H, tally, r);
 }
 
 SearchResult DevicePipeline::run_search(const TextInput& in,
                                         const std::vector<SearchQuery>& queries, u64 rank_k,
-                                        bool ignore_case, u64 show, u64 tally) {
+                                        bool ignore_case, u64 show, u64 tally, u32 by_file) {
   TraceRange tr("locust:search_job");
+  check_search_by_file(by_file, rank_k, show, tally);
   check_search_batch(queries, rank_k, ignore_case);  // (a refused batch starts nothing)
   check_search_show(show, in.bytes);
   check_search_tally(tally);
@@ -2793,7 +3014,7 @@ SearchResult DevicePipeline::run_search(const TextInput& in,
   sync();
   check_index_counters(n, T);
   keep_index(in, w, n, T);
-  search_stage(queries, rank_k, ignore_case, (u32)show, (u32)tally, &r);
+  search_stage(queries, rank_k, ignore_case, (u32)show, (u32)tally, by_file, &r);
   r.index_ms = ms_between(ev_index[0], ev_index[1]);
   r.search_ms = ms_between(ev_search[0], ev_search[1]);
   r.wire_bytes += sizeof(IndexCounters) + sizeof(MapCounters);
@@ -2801,7 +3022,7 @@ SearchResult DevicePipeline::run_search(const TextInput& in,
   r.times.map_ms = ms_between(ev[1], ev[2]);
   r.times.process_ms = ms_between(ev[2], ev[3]);
   r.times.reduce_ms = ms_between(ev[3], ev[4]);
-  r.times.gpu_ms = ms_between(ev[0], ev_search[1]) + r.show_ms + r.tally_ms;
+  r.times.gpu_ms = ms_between(ev[0], ev_search[1]) + r.show_ms + r.tally_ms + r.by_file_ms;
   r.times.wall_ms = (now_ns() - t0) * 1e-6;
   if (cfg.check) validate_search(r);
   return r;
@@ -2809,8 +3030,9 @@ SearchResult DevicePipeline::run_search(const TextInput& in,
 
 SearchResult DevicePipeline::search_resident(const std::vector<SearchQuery>& queries,
                                              u64 rank_k, bool ignore_case, u64 show,
-                                             u64 tally) {
+                                             u64 tally, u32 by_file) {
   TraceRange tr("locust:search_resident");
+  check_search_by_file(by_file, rank_k, show, tally);
   check_search_batch(queries, rank_k, ignore_case);
   check_search_show(show, idx_view.bytes);
   check_search_tally(tally);
@@ -2820,9 +3042,9 @@ SearchResult DevicePipeline::search_resident(const std::vector<SearchQuery>& que
                 "overwrites what the index reads); run one of them first");
   SearchResult r;
   const u64 t0 = now_ns();
-  search_stage(queries, rank_k, ignore_case, (u32)show, (u32)tally, &r);
+  search_stage(queries, rank_k, ignore_case, (u32)show, (u32)tally, by_file, &r);
   r.search_ms = ms_between(ev_search[0], ev_search[1]);
-  r.times.gpu_ms = r.search_ms + r.show_ms + r.tally_ms;
+  r.times.gpu_ms = r.search_ms + r.show_ms + r.tally_ms + r.by_file_ms;
   r.times.wall_ms = (now_ns() - t0) * 1e-6;
   if (cfg.check) validate_search(r);
   return r;
@@ -2924,7 +3146,7 @@ AppendIndex DevicePipeline::resident_as_append() const {
   return a;
 }
 
-IndexAppend DevicePipeline::append_index(const TextInput& in) {
+IndexAppend DevicePipeline::append_index(const TextInput& in, bool new_file) {
   TraceRange tr("locust:index_append");
   // ---- refusals: nothing is enqueued, the resident index stays as it is ----
   if (!idx_resident)
@@ -2946,6 +3168,10 @@ IndexAppend DevicePipeline::append_index(const TextInput& in) {
                    "first line would continue its last one");
   LOCUST_CHECK_ARG(next_line + in.num_lines <= (1ull << 32),
                    "index: line numbers past 2^32 do not fit a u32 posting");
+  LOCUST_CHECK_ARG(!new_file || idx_segs.segs.size() < kCorpusMaxFiles,
+                   "append_index: the index holds " + std::to_string(idx_segs.segs.size()) +
+                       " files, the most it takes (kCorpusMaxFiles = " +
+                       std::to_string(kCorpusMaxFiles) + "): drop the oldest first");
   IndexAppend out;
   const u64 t0 = now_ns();
   if (!idx_in_store) {
@@ -3053,7 +3279,10 @@ IndexAppend DevicePipeline::append_index(const TextInput& in) {
   idx_words.truncated += w.truncated;
   idx_words.max_key_len = std::max(idx_words.max_key_len, w.max_key_len);
   if (in.bytes) idx_ends_nl = in.data[in.bytes - 1] == '\n';
+  idx_segs.append(in.num_lines, new_file);
+  corpus_dirty |= new_file;  // (the mirror holds first lines only: a longer last file changes none)
   idx_resident = true;
+  out.files = idx_segs.segs.size();
   out.block_lines = in.num_lines;
   out.block_tokens = tb;
   out.block_unique = nb;
@@ -3192,6 +3421,8 @@ IndexDrop DevicePipeline::drop_index(u64 lines) {
   idx_words.overflow_lines -= dc.overflow_lines;
   idx_words.truncated -= dc.truncated;
   if (m.bytes == 0) idx_ends_nl = true;
+  out.dropped_files = idx_segs.drop(lines);
+  corpus_dirty = true;
   idx_resident = true;
   out.dropped_lines = lines;
   out.dropped_tokens = dc.dropped;
@@ -3222,6 +3453,7 @@ IndexResult DevicePipeline::index_resident() {
                                hipMemcpyDeviceToHost));
   copy_out(x.words.entries, n);
   x.wire_bytes = T * sizeof(u32) + n * sizeof(OutRecord);
+  x.segments = idx_segs.segs;
   if (cfg.check) validate_index(x);
   return x;
 }

@@ -847,17 +847,47 @@ struct DevicePipeline {
   u32* d_sexpr = nullptr;
   u32* h_sexpr = nullptr;
   void ensure_search_expr();
+  // ---- corpus (kernels/corpus.hip; engine.hpp "corpus", "file sets") ----
+  // The segment table is host state: every job that leaves an index resets it, an append and a
+  // drop move it (the host knows every block's line count).  Its device mirror, the batch's
+  // set bitmaps and their pinned upload half are one allocation each, made by the engine's first
+  // batch with a file set and grown on demand; the mirror is uploaded only when the table has
+  // changed since the last batch that needed it.  A batch without a file set touches none of it.
+  IndexSegments idx_segs;
+  bool corpus_dirty = true;  // the device mirror is behind idx_segs
+  CorpusSets scorpus{};
+  char* d_corpus = nullptr;
+  u64 corpus_bytes = 0;
+  u32* h_corpus = nullptr;  // pinned [table (seg_cap) | q_set (kSearchMaxQueries) | bitmaps]
+  void ensure_corpus(u64 segments, u64 sets);
+  // The restrict stage over the H pairs the hit stage left: uploads what is due, launches, and
+  // returns the distinct sets (the caller reads the counters back at its next synchronisation).
+  void corpus_restrict(const std::vector<SearchQuery>& queries, u64 H);
+  IndexSegments segments() const;
+  // ---- answers by file (kernels/corpus.hip) ----
+  // The stage's arrays (40 B per returned line) and the pinned buffer its answer comes back to
+  // are allocations of their own, made by the engine's first by-file batch and grown on demand.
+  CorpusByFile sbyfile{};
+  char* d_byfile = nullptr;
+  u64 byfile_bytes = 0;
+  char* h_byfile = nullptr;  // pinned [CorpusCounters (64 B) | file_off | the arrays that cross]
+  u64 h_byfile_cap = 0;
+  hipEvent_t ev_byfile[2] = {};
+  // Uploads the table's mirror when it is behind (a batch without a file set has not).
+  void corpus_sync_table();
+  // Over the E returned lines (shits.lines) and their offsets on the device.
+  void by_file_stage(u32 Q, const u64* offsets, u64 E, bool ranked, u32 by_file, SearchResult* r);
   // The batch over idx_view on `stream`, timed by ev_search; synchronises (the bound, the
   // number of hits, the result) and fills r's lists, statistics and wire_bytes.
   // rank_k != 0: the ranked answer (engine.hpp "ranked search").
   // show != 0: show_stage behind it, over the lines and offsets it left on the device.
   // tally != 0: tally_stage behind both, over the same lines and offsets.
   void search_stage(const std::vector<SearchQuery>& queries, u64 rank_k, bool ignore_case,
-                    u32 show, u32 tally, SearchResult* r);
+                    u32 show, u32 tally, u32 by_file, SearchResult* r);
   SearchResult run_search(const TextInput& in, const std::vector<SearchQuery>& queries,
-                          u64 rank_k, bool ignore_case, u64 show, u64 tally);
+                          u64 rank_k, bool ignore_case, u64 show, u64 tally, u32 by_file);
   SearchResult search_resident(const std::vector<SearchQuery>& queries, u64 rank_k,
-                               bool ignore_case, u64 show, u64 tally);
+                               bool ignore_case, u64 show, u64 tally, u32 by_file);
   // ---- index store and append (kernels/append.hip; engine.hpp "appending to the index") ----
   // Two buffer sets ("halves") of the engine's own, apart from the pass buffers: a merge reads
   // the resident index from one half and the block's index from the pass buffers (d_out,
@@ -904,7 +934,7 @@ struct DevicePipeline {
   // launch_index builds no line index for a text without tokens: the merge needs one.
   void ensure_line_index(u64 bytes, u64 n, u64 T);
   AppendIndex resident_as_append() const;
-  IndexAppend append_index(const TextInput& in);
+  IndexAppend append_index(const TextInput& in, bool new_file);
   IndexResult index_resident();
   // ---- show (kernels/show.hip) ----
   // The stage's arrays are allocations of their own, made by the engine's first show batch and

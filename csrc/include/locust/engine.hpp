@@ -316,6 +316,53 @@ void validate_top(const TopResult& t);
 // build's (format_gpu_output / format_cpu_output, io.hpp).
 void format_top_output(const TopResult& t, bool cpu_format, std::string* out);
 
+// ---- corpus: several files in one index ----
+// A resident index is cut into S >= 1 segments: consecutive, possibly empty, line ranges that
+// cover [first_line, first_line + num_lines) in order -- the files of a corpus.  A segment has
+// an id (a u32 that numbers the files in the order they were begun: run_index / run_search begin
+// file 0, append_index(new_file) the next; a dropped file never frees its id), first_line (the
+// global number of its first resident line) and base (the file-local number of that line: 0
+// until a drop cuts into the file).  A global line l belongs to the LAST segment with
+// first_line <= l, so an empty file between two others owns no line; its local number is
+// l - first_line + base, 0-based like every line number here.
+//  * append(lines, new_file): with new_file a segment with the next id begins at the block's
+//    first line; without it the block extends the last segment.  More than kCorpusMaxFiles
+//    resident segments are refused, the table unchanged.
+//  * drop(d): segments that lie wholly inside the dropped lines leave the table (the non-empty
+//    ones are counted and returned); the segment the cut falls into keeps its id, its first_line
+//    becomes F + d and its base grows by the lines it lost; empty segments in front of the first
+//    resident line go with the dropped ones.  d == N leaves the last segment, empty, so the
+//    next block without new_file continues that file's numbering.  d == 0 changes nothing.
+//  * locate(l): the ordinal of l's segment (l inside the resident lines).
+// The table is host state of an engine; the host twins (merge_index, trim_index, search_index)
+// carry it in IndexResult::segments, where an empty table stands for the single segment
+// (0, first_line, 0).
+constexpr u64 kCorpusMaxFiles = 65536;
+struct IndexSegment {
+  u32 id = 0;
+  u64 first_line = 0;
+  u64 base = 0;
+  bool operator==(const IndexSegment& o) const {
+    return id == o.id && first_line == o.first_line && base == o.base;
+  }
+};
+struct IndexSegments {
+  std::vector<IndexSegment> segs;  // never empty behind reset()
+  u64 first_line = 0, num_lines = 0;
+  u32 next_id = 0;
+  void reset(u64 first, u64 lines);
+  void append(u64 lines, bool new_file);
+  u64 drop(u64 lines);
+  size_t locate(u64 line) const;
+  // the resident lines of segment i
+  u64 lines_of(size_t i) const {
+    return (i + 1 < segs.size() ? segs[i + 1].first_line : first_line + num_lines) -
+           segs[i].first_line;
+  }
+  // the ordinal of the resident segment with this id, or segs.size()
+  size_t find(u32 id) const;
+};
+
 // ---- inverted index: word -> the lines it occurs on ----
 // Every token the word job emits (its tokeniser, emit cap and key truncation, unchanged)
 // yields one pair (key, line); `line` is the global 0-based line number first_line + i.
@@ -332,6 +379,9 @@ struct IndexResult {
   u64 first_line = 0;          // the input window's first line (postings start there)
   double index_ms = 0;         // device time of the index stage (0: built on the host)
   u64 wire_bytes = 0;          // bytes the device wrote to host memory for the result
+  std::vector<IndexSegment> segments;  // "corpus" above; empty: the one segment (0, first_line, 0)
+  // the table as IndexSegments (an empty one made whole)
+  IndexSegments segment_table() const;
 };
 // LOCUST_CHECK invariants of an index result: the entries' counts add up to
 // postings.size() == num_tokens, every list is non-decreasing, every posting lies in
@@ -366,11 +416,14 @@ struct IndexAppend {
   double append_ms = 0;   // device time of the merge
   StageTimes times;       // the block's word job
   u64 store_bytes = 0;    // device bytes of the index store (both halves and the merge's scratch)
+  u64 files = 0;          // resident segments afterwards ("corpus")
 };
 // The host twin of the device merge: the index of a's text followed by b's, from the two
 // indexes alone, with the same checks (keys strictly ascending on either side, the counts
 // adding up to the postings).  Throws unless b.first_line == a.first_line + a.words.num_lines.
-IndexResult merge_index(const IndexResult& a, const IndexResult& b);
+// new_file: b begins a segment with a's next id ("corpus"); else it extends a's last segment.
+// b's own table is not looked at: b is one block.
+IndexResult merge_index(const IndexResult& a, const IndexResult& b, bool new_file = false);
 
 // ---- dropping the oldest lines ----
 // The mirror image of an append, for an index that follows a log or a feed and is searched
@@ -399,6 +452,7 @@ struct IndexDrop {
   u64 dropped_words = 0;   // words whose list emptied
   u64 dropped_bytes = 0;   // text bytes removed
   u64 dropped_overflow_lines = 0, dropped_truncated = 0;
+  u64 dropped_files = 0;   // non-empty segments that lay wholly inside the dropped lines ("corpus")
   u64 first_line = 0, num_lines = 0, num_tokens = 0, num_unique = 0;  // the resident index afterwards
   double drop_ms = 0;      // device time of the drop
   u64 store_bytes = 0;     // device bytes of the index store (both halves and the scratches)
@@ -817,6 +871,26 @@ struct TallyKeySplit {
 };
 // The split for n index words and `tokens` pair words; throws as described above.
 TallyKeySplit tally_key_split(u64 n, u64 tokens);
+// File sets.  SearchQuery::files is a sorted list of distinct segment ids ("corpus" above);
+// empty means every file.  The matching set of a query is what its mode answers, after
+// exclusion, intersected with the lines whose segment's id is in the set -- for all / any /
+// phrase / near / expr alike.  An id that is not resident selects nothing and is no error: it
+// may never have been begun, or it may have been dropped.  The set selects lines only: N and
+// every count of a ranked score stay those of the whole resident index, so the ranked answer
+// under a set is the unrestricted ranking filtered to the set and cut to K.  matches, the K
+// winners, show and tally all see the restricted set.  Refused: ids not strictly ascending.
+// On the device a batch with at least one non-empty set runs the restrict stage (kernels.hpp
+// "corpus.hip") between the hit / verify kernels and the sort; any other batch enqueues what it
+// always did.
+// Answers by file.  A batch may ask for by_file = kByFile: beside `lines` it returns line_file
+// and line_local, the segment id and file-local number of every returned line (ranked: in rank
+// order), and a CSR -- per query the files with at least one returned line, ids ascending, and
+// their counts, which add up to the query's returned lines (unranked: every match; ranked: the
+// min(K, matches) winners, the rule tally follows).  kByFileCount is `grep -c`: only the CSR,
+// `matches` and the counters cross PCIe; `lines` and `offsets` stay empty (offsets all 0) and
+// the lines stay on the device.  It is refused with rank, show or tally.  The device stage
+// (kernels.hpp "corpus.hip") stands behind emit / top; wire_bytes counts exactly what is copied.
+constexpr u32 kByFileNone = 0, kByFile = 1, kByFileCount = 2;
 constexpr u32 kShowMaxBytes = 65536;
 constexpr u64 kShowMaxPayload = 4ull << 30;  // bytes of one batch's show payload on the device
 constexpr u32 kSearchMaxQueries = 1024;
@@ -842,6 +916,7 @@ struct SearchQuery {
                           // (terms[t]: its source, without the slashes)
   std::string expr;       // kExpr: the expression as asked, blanks collapsed ("boolean expressions")
   std::array<u32, kExprTruthWords> truth{};  // kExpr: bit m: the value when exactly mask m holds
+  std::vector<u32> files;  // "file sets" above: segment ids, strictly ascending; empty: every file
   bool truth_at(u32 m) const { return (truth[(m >> 5) & 7u] >> (m & 31u)) & 1u; }
   bool is_prefix(size_t t) const { return t < prefix.size() && prefix[t] != 0; }
   u32 fuzzy_budget(size_t t) const { return t < fuzzy.size() ? fuzzy[t] : 0u; }
@@ -894,6 +969,19 @@ struct SearchResult {
   std::vector<u64> tally_tokens;       // [queries] the sum of all counts
   u64 tallied = 0;                     // pair words the device stage sorted (0: host evaluation)
   double tally_ms = 0;  // device time of the tally stage (host evaluation: its wall time)
+  // "file sets" (engine.hpp): the table the batch was answered under (empty: one segment
+  // (0, first_line, 0)) and the pair words the device's restrict stage removed (0: no file set
+  // in the batch, or the host evaluation)
+  std::vector<IndexSegment> segments;
+  u64 restricted = 0;
+  // "answers by file" (by_file == kByFileNone: none of these is filled)
+  u32 by_file = 0;
+  std::vector<u32> line_file;    // parallel to lines: the line's segment id (count only: empty)
+  std::vector<u32> line_local;   // parallel to lines: its file-local number (count only: empty)
+  std::vector<u64> file_off;     // [queries + 1]: query i's files, [file_off[i], file_off[i+1])
+  std::vector<u32> file_ids;     // ascending per query: the files with a returned line
+  std::vector<u32> file_counts;  // parallel to file_ids: their returned lines
+  double by_file_ms = 0;  // device time of the by-file stage (host evaluation: 0)
   u64 hits() const { return lines.size(); }
 };
 // A term's key: its first min(size, cfg.max_key_len) bytes, packed as the map packs keys.
@@ -983,6 +1071,9 @@ void check_search_rank(u64 rank_k, const JobConfig& cfg, bool patterns = false);
 void check_search_show(u64 show, u64 text_bytes);
 // Throws unless tally is 0 (no tally) or 1 <= tally <= kTopKMax ("tally" above).
 void check_search_tally(u64 tally);
+// Throws unless by_file is kByFileNone, kByFile or kByFileCount, and kByFileCount stands without
+// rank, show and tally ("answers by file" above).
+void check_search_by_file(u32 by_file, u64 rank_k, u64 show, u64 tally);
 // The host evaluation over an index result, any number of queries (cfg: the index job's
 // delimiters and max_key_len).  Throws for a phrase query and for a `near` query of two or
 // more terms: the index holds no positions, so they need the text -- the four-argument
@@ -994,7 +1085,7 @@ void check_search_tally(u64 tally);
 // tally = K: "tally" above, answered here too -- the rule needs no text.
 SearchResult search_index(const IndexResult& x, const std::vector<SearchQuery>& queries,
                           const JobConfig& cfg, u64 rank_k = 0, bool ignore_case = false,
-                          u64 show = 0, u64 tally = 0);
+                          u64 show = 0, u64 tally = 0, u32 by_file = 0);
 // The same with the text the index was built from (the same window: text.first_line ==
 // x.first_line; cfg also gives emits_per_line): a phrase's or a `near` query's candidates
 // come from the `all` evaluation and are verified by tokenising their lines with the CPU
@@ -1002,7 +1093,7 @@ SearchResult search_index(const IndexResult& x, const std::vector<SearchQuery>& 
 SearchResult search_index(const IndexResult& x, const TextInput& text,
                           const std::vector<SearchQuery>& queries, const JobConfig& cfg,
                           u64 rank_k = 0, bool ignore_case = false, u64 show = 0,
-                          u64 tally = 0);
+                          u64 tally = 0, u32 by_file = 0);
 // LOCUST_CHECK invariants of a search result: offsets monotone from 0 to lines.size(), every
 // line inside [first_line, first_line + num_lines), one `matches` per query.  Unranked: every
 // query's lines strictly ascending, matches == the hit counts, no scores.  Ranked: one score
@@ -1182,16 +1273,20 @@ class GpuWordCount {
   // tally = K: the tally stage behind both ("tally": kernels/tally.hip).
   SearchResult run_search(const TextInput& in, const std::vector<SearchQuery>& queries,
                           u64 rank_k = 0, bool ignore_case = false, u64 show = 0,
-                          u64 tally = 0);
+                          u64 tally = 0, u32 by_file = 0);
   // Another batch from the index this engine's last job left on the device.  That job must
   // have been a run_index or a run_search: any other job (a refused one that had started
   // to write included) marks the index stale, and this then throws.
   SearchResult search_resident(const std::vector<SearchQuery>& queries, u64 rank_k = 0,
-                               bool ignore_case = false, u64 show = 0, u64 tally = 0);
+                               bool ignore_case = false, u64 show = 0, u64 tally = 0,
+                               u32 by_file = 0);
   // One more block of whole lines into the resident index ("appending to the index" above):
   // the block's word job and index stage, then the merge on the device into the engine's
   // index store.  in.first_line must be the resident first_line + lines.
-  IndexAppend append_index(const TextInput& in);
+  // new_file: the block begins a segment ("corpus"); else it extends the last one.
+  IndexAppend append_index(const TextInput& in, bool new_file = false);
+  // The resident index's segment table ("corpus"); throws when the index is stale.
+  IndexSegments segments() const;
   // The oldest `lines` lines out of the resident index ("dropping the oldest lines" above):
   // compacted on the device into the other half of the engine's index store.
   IndexDrop drop_index(u64 lines);
@@ -1248,7 +1343,7 @@ class CpuWordCount {
   // of queries and every mode.
   SearchResult run_search(const TextInput& in, const std::vector<SearchQuery>& queries,
                           u64 rank_k = 0, bool ignore_case = false, u64 show = 0,
-                          u64 tally = 0);
+                          u64 tally = 0, u32 by_file = 0);
   std::vector<PackedKey> run_map_stage(const TextInput& in, WordCountResult* stats);
   WordCountResult run_reduce_stage(const PackedKey* keys, u64 n);
 

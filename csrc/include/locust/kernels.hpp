@@ -1079,6 +1079,98 @@ void launch_search_order(const SearchIndex& ix, const SearchBatch& b, u32 querie
 void launch_search_rank(const SearchIndex& ix, const SearchBatch& b, u32 queries, u64 hits,
                         u32 k, SearchHits& h, SortPlan* h_plan, hipStream_t s);
 
+// ---------------- corpus.hip ----------------
+// The restrict stage of a search batch (engine.hpp "corpus", "file sets"): of the H unsorted pair
+// words the hit and verify kernels left, those whose line lies in a segment of their query's
+// file set.  The arrays are one allocation, made by an engine's first batch with a file set and
+// grown on demand:
+//   ctr      CorpusCounters, zeroed per restricted batch
+//   table    [seg_cap] the resident segments' first lines (global, u32, ascending; [0] is the
+//            index's first_line): the device mirror of the engine's table, uploaded only when
+//            the table has changed since the last batch that needed it
+//   q_set    [kSearchMaxQueries] the query's row of `bitmaps`, or kCorpusNoSet: uploaded per batch
+//   bitmaps  [sets][ceil(S / 32)] bit o of a row: the resident segment of ordinal o is in the
+//            set (ids that are not resident have no bit): one row per distinct set of the
+//            batch, uploaded per batch
+// The stage adds no workspace per hit: the kept pairs go to SearchHits::cands, idle between the
+// verify kernels and the score kernel.
+// A deliberate choice: inside a tile the kept pairs' positions come from a workgroup scan, but a
+// tile's base is one atomic add on `kept`, not a second pass over a tile array
+// (device/tile_scan.hpp).  The pairs are "in arbitrary order" by contract -- the hit kernels
+// reserve their slots with atomics too -- and the sort behind the stage fixes the answer, so a
+// deterministic layout would buy nothing and cost two more launches.  The layout of the kept
+// pairs therefore differs from run to run; the answer does not.
+struct CorpusCounters {
+  u32 kept;   // pairs the restrict kernel kept
+  u32 stray;  // pairs that name no query of the batch, or a line in front of the table
+  // the by-file stage's (its own block, CorpusByFile::ctr)
+  u32 sort_n;     // keys handed to the sort of a ranked batch: the returned lines
+  u32 runs;       // (query, file) runs among the keys: the CSR's entries
+  u32 unlocated;  // returned lines outside the table or outside every query's range
+};
+constexpr int kCorpusBlock = 256;
+constexpr int kCorpusItems = 4;
+constexpr int kCorpusTile = kCorpusBlock * kCorpusItems;  // pairs per workgroup and step
+constexpr int kCorpusMaxBlocks = 2048;
+constexpr u32 kCorpusNoSet = 0xffffffffu;
+constexpr int kCorpusLdsSegs = 2048;  // the resolve kernel stages a table of up to this many
+                                      // segments in LDS (8 KiB); a longer one is read from
+                                      // global memory
+struct CorpusSets {
+  CorpusCounters* ctr = nullptr;
+  u32* table = nullptr;
+  u32* ids = nullptr;      // [seg_cap] the segments' ids, uploaded with the table
+  u32* q_set = nullptr;
+  u32* bitmaps = nullptr;
+  u64 seg_cap = 0, set_cap = 0;
+};
+u64 corpus_sets_bytes(u64 seg_cap, u64 set_cap);
+// Carves `base` (corpus_sets_bytes bytes, 256-B aligned); c == nullptr: only *bytes.
+void corpus_sets_carve(char* base, u64 seg_cap, u64 set_cap, CorpusSets* c, u64* bytes = nullptr);
+// restrict + seal over the `hits` pairs in h.pairs (b.ctr->written == hits): b.q_hits rebuilt,
+// b.ctr->written and sort_n the kept pairs, c.ctr complete when `s` has drained.  The kept
+// pairs are h.pairs afterwards: the launcher swaps h.pairs and h.cands.
+void launch_corpus_restrict(const SearchIndex& ix, const SearchBatch& b, const CorpusSets& c,
+                            u32 segments, u32 sets, u32 queries, u64 hits, SearchHits& h,
+                            hipStream_t s);
+// The by-file stage (engine.hpp "answers by file") behind emit / top, over the E returned lines
+// h.lines[0 .. E) and their per-query offsets [Q + 1]:
+//   resolve  one returned line per thread: its query by binary search in the offsets, its
+//            segment by the restrict stage's binary search -- in a copy of the table staged in
+//            LDS while S <= kCorpusLdsSegs, in global memory above that -- then line_file (the
+//            id), line_local (line - first_line + base; only the first segment has a base) and
+//            the key query << 32 | segment ordinal
+//   order    (ranked only: unranked keys ascend already) radix_sort() of the keys
+//   heads    a key that differs from the one before it heads a run.  Three kernels, data crossing
+//            at the kernel boundaries only: the heads of every tile of kCorpusTile keys counted,
+//            one workgroup scans the tile array (the total: `runs`), then every head takes its
+//            place from a workgroup scan inside its tile, finds its run's end by binary search
+//            (as tally.hip's run heads do) and writes one (id, count) and its key.  No atomics
+//            on any output
+//   offsets  one thread per query: file_off[q] = the lower bound of q << 32 among the run keys
+// The arrays are one allocation, grown by the batch's returned lines (40 B each).
+struct CorpusByFile {
+  CorpusCounters* ctr = nullptr;  // zeroed per by-file batch
+  u64* keys = nullptr;        // [cap]
+  u64* sorted = nullptr;      // [cap] ranked: the sorted keys
+  u64* run_keys = nullptr;    // [cap] a run's key, in CSR order
+  u64* tile_val = nullptr;    // [ceil(cap / kCorpusTile) + 1]
+  u64* file_off = nullptr;    // [kSearchMaxQueries + 1]
+  u32* line_file = nullptr;   // [cap] parallel to h.lines
+  u32* line_local = nullptr;  // [cap]
+  u32* file_ids = nullptr;    // [cap] the CSR: ids ascending per query
+  u32* file_counts = nullptr; // [cap]
+  u64 cap = 0;
+};
+void corpus_by_file_carve(char* base, u64 cap, CorpusByFile* f, u64* bytes = nullptr);
+// offsets: the returned lines' per-query offsets on the device ([queries + 1], offsets[queries]
+// == lines).  base0: the first segment's base.  f.ctr->runs, f.file_off and the outputs are
+// complete when `s` has drained; a ranked batch of more than kSmallSortMax lines synchronises
+// `s` once, as radix_sort does.
+void launch_corpus_by_file(const CorpusSets& c, u32 segments, u64 base0, const u64* offsets,
+                           u32 queries, u64 lines, bool ranked, SearchHits& h, CorpusByFile& f,
+                           SortPlan* h_plan, hipStream_t s);
+
 // ---------------- expr.hip ----------------
 // `expr` queries (engine.hpp "boolean expressions"): a batch that has one carries, in an
 // allocation of its own made by the engine's first such batch, these u32 words.  The first two
@@ -1352,6 +1444,7 @@ void launch_string_selftest(const char* blob, const u32* off, u32 n, const char*
 // HIP_ENABLE_DEFERRED_LOADING=0 would also load the RCCL library's device code (a
 // 573 MB fat binary), +1.3 GB of host memory and ~150 ms per process.
 void warm_module_append();  // (as index: the code object only, no buffers)
+void warm_module_corpus();  // (as search: the code object only, no buffers)
 void warm_module_dict();
 void warm_module_drop();  // (as append)
 void warm_module_exchange();
@@ -1378,6 +1471,7 @@ void warm_module_tokenize();
 void warm_module_topk();
 inline void warm_kernel_modules() {
   warm_module_append();
+  warm_module_corpus();
   warm_module_dict();
   warm_module_drop();
   warm_module_exchange();

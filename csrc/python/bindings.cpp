@@ -94,6 +94,14 @@ struct PyTopResult {
   }
 };
 
+// engine.hpp "corpus": a segment table as [(id, first_line, base, lines)]
+std::vector<std::tuple<u32, u64, u64, u64>> segment_rows(const IndexSegments& t) {
+  std::vector<std::tuple<u32, u64, u64, u64>> out;
+  for (size_t i = 0; i < t.segs.size(); ++i)
+    out.emplace_back(t.segs[i].id, t.segs[i].first_line, t.segs[i].base, t.lines_of(i));
+  return out;
+}
+
 // An inverted index: the word job's entries and the CSR postings behind them.
 struct PySearchResult;
 struct PyIndexResult {
@@ -104,7 +112,8 @@ struct PyIndexResult {
                         const std::vector<u64>& within,
                         const std::vector<std::vector<std::string>>& exclude, bool glob,
                         bool ignore_case, const py::object& show, bool fuzzy, bool regex,
-                        const py::object& tally) const;
+                        const py::object& tally,
+                        const std::vector<std::vector<u32>>& files, u32 by_file) const;
   py::list entries() const { return PyResult{x.words}.entries(); }
   py::list postings() const {
     py::list out;
@@ -221,6 +230,30 @@ struct PySearchResult {
         out.append(py::make_tuple(py::bytes(key_to_string(r.tally_keys[j])), r.tally_counts[j]));
     return out;
   }
+  // by file: query i's returned lines' file ids / file-local numbers (parallel to lines(i))
+  py::list files(size_t i) const {
+    check(i);
+    py::list out;
+    if (r.by_file == kByFile)
+      for (u64 j = r.offsets[i]; j < r.offsets[i + 1]; ++j) out.append(r.line_file[j]);
+    return out;
+  }
+  py::list local_lines(size_t i) const {
+    check(i);
+    py::list out;
+    if (r.by_file == kByFile)
+      for (u64 j = r.offsets[i]; j < r.offsets[i + 1]; ++j) out.append(r.line_local[j]);
+    return out;
+  }
+  // by file: [(id, count)] over the files with a returned line of query i, ids ascending
+  py::list file_hits(size_t i) const {
+    check(i);
+    py::list out;
+    if (r.by_file)
+      for (u64 f = r.file_off[i]; f < r.file_off[i + 1]; ++f)
+        out.append(py::make_tuple(r.file_ids[f], r.file_counts[f]));
+    return out;
+  }
   py::list tally_words() const {
     py::list out;
     for (const u64 w : r.tally_words) out.append(w);
@@ -268,8 +301,11 @@ std::vector<SearchQuery> to_queries(const JobConfig& cfg,
                                     const std::vector<int>& any, bool wildcard,
                                     const std::vector<u64>& within,
                                     const std::vector<std::vector<std::string>>& exclude,
-                                    bool glob, bool fuzzy = false, bool regex = false) {
+                                    bool glob, bool fuzzy = false, bool regex = false,
+                                    const std::vector<std::vector<u32>>& files = {}) {
   LOCUST_CHECK_ARG(any.size() == queries.size(), "search: one mode per query");
+  LOCUST_CHECK_ARG(files.empty() || files.size() == queries.size(),
+                   "search: one file set (files) per query, or none");
   LOCUST_CHECK_ARG(within.empty() || within.size() == queries.size(),
                    "search: one window (within) per query, or none");
   LOCUST_CHECK_ARG(exclude.empty() || exclude.size() == queries.size(),
@@ -299,6 +335,8 @@ std::vector<SearchQuery> to_queries(const JobConfig& cfg,
                                exclude.empty() ? std::vector<std::string>() : exclude[i], glob,
                                fuzzy, regex);
   }
+  // "file sets": segment ids, as given (check_search_queries refuses a set that is not ascending)
+  for (size_t i = 0; i < files.size(); ++i) out[i].files = files[i];
   return out;
 }
 
@@ -349,14 +387,15 @@ PySearchResult PyIndexResult::search(const std::vector<std::vector<std::string>>
                                      bool wildcard, const std::vector<u64>& within,
                                      const std::vector<std::vector<std::string>>& exclude, bool glob,
                         bool ignore_case, const py::object& show, bool fuzzy, bool regex,
-                        const py::object& tally) const {
+                        const py::object& tally,
+                        const std::vector<std::vector<u32>>& files, u32 by_file) const {
   const std::vector<SearchQuery> q =
-      to_queries(cfg, queries, any, wildcard, within, exclude, glob, fuzzy, regex);
+      to_queries(cfg, queries, any, wildcard, within, exclude, glob, fuzzy, regex, files);
   const u64 k = to_rank(rank);
   const u64 n = to_show(show);
   const u64 tk = to_tally(tally);
   py::gil_scoped_release nogil;
-  return PySearchResult{search_index(x, q, cfg, k, ignore_case, n, tk)};
+  return PySearchResult{search_index(x, q, cfg, k, ignore_case, n, tk, by_file)};
 }
 
 TextInput as_input(const std::string& text, u64 first_line = 0) {
@@ -504,14 +543,15 @@ class PyGpuEngine {
                             const std::vector<u64>& within,
                             const std::vector<std::vector<std::string>>& exclude, bool glob,
                         bool ignore_case, const py::object& show, bool fuzzy, bool regex,
-                        const py::object& tally) {
+                        const py::object& tally,
+                        const std::vector<std::vector<u32>>& files, u32 by_file) {
     const std::vector<SearchQuery> q =
-        to_queries(eng_.config(), queries, any, wildcard, within, exclude, glob, fuzzy, regex);
+        to_queries(eng_.config(), queries, any, wildcard, within, exclude, glob, fuzzy, regex, files);
     const u64 k = to_rank(rank);
     const u64 n = to_show(show);
     const u64 tk = to_tally(tally);
     py::gil_scoped_release nogil;
-    return PySearchResult{eng_.run_search(as_input(text, first_line), q, k, ignore_case, n, tk)};
+    return PySearchResult{eng_.run_search(as_input(text, first_line), q, k, ignore_case, n, tk, by_file)};
   }
   PySearchResult run_search_text(const HostText& t,
                                  const std::vector<std::vector<std::string>>& queries,
@@ -520,34 +560,38 @@ class PyGpuEngine {
                             const std::vector<u64>& within,
                             const std::vector<std::vector<std::string>>& exclude, bool glob,
                         bool ignore_case, const py::object& show, bool fuzzy, bool regex,
-                        const py::object& tally) {
+                        const py::object& tally,
+                        const std::vector<std::vector<u32>>& files, u32 by_file) {
     const std::vector<SearchQuery> q =
-        to_queries(eng_.config(), queries, any, wildcard, within, exclude, glob, fuzzy, regex);
+        to_queries(eng_.config(), queries, any, wildcard, within, exclude, glob, fuzzy, regex, files);
     const u64 k = to_rank(rank);
     const u64 n = to_show(show);
     const u64 tk = to_tally(tally);
     py::gil_scoped_release nogil;
-    return PySearchResult{eng_.run_search(t.input(first_line), q, k, ignore_case, n, tk)};
+    return PySearchResult{eng_.run_search(t.input(first_line), q, k, ignore_case, n, tk, by_file)};
   }
   PySearchResult search_resident(const std::vector<std::vector<std::string>>& queries,
                                  const std::vector<int>& any, const py::object& rank,
                                  bool wildcard, const std::vector<u64>& within,
                                  const std::vector<std::vector<std::string>>& exclude, bool glob,
                         bool ignore_case, const py::object& show, bool fuzzy, bool regex,
-                        const py::object& tally) {
+                        const py::object& tally,
+                        const std::vector<std::vector<u32>>& files, u32 by_file) {
     const std::vector<SearchQuery> q =
-        to_queries(eng_.config(), queries, any, wildcard, within, exclude, glob, fuzzy, regex);
+        to_queries(eng_.config(), queries, any, wildcard, within, exclude, glob, fuzzy, regex, files);
     const u64 k = to_rank(rank);
     const u64 n = to_show(show);
     const u64 tk = to_tally(tally);
     py::gil_scoped_release nogil;
-    return PySearchResult{eng_.search_resident(q, k, ignore_case, n, tk)};
+    return PySearchResult{eng_.search_resident(q, k, ignore_case, n, tk, by_file)};
   }
   // One more block of whole lines into the resident index, merged on the device.
-  IndexAppend append_index(const std::string& text, u64 first_line) {
+  IndexAppend append_index(const std::string& text, u64 first_line, bool new_file) {
     py::gil_scoped_release nogil;
-    return eng_.append_index(as_input(text, first_line));
+    return eng_.append_index(as_input(text, first_line), new_file);
   }
+  // "corpus": the resident segments, [(id, first_line, base, lines)]
+  std::vector<std::tuple<u32, u64, u64, u64>> segments() { return segment_rows(eng_.segments()); }
   // The oldest `lines` lines out of the resident index, compacted on the device.
   IndexDrop drop_index(u64 lines) {
     py::gil_scoped_release nogil;
@@ -1093,7 +1137,7 @@ PYBIND11_MODULE(_locust, m) {
       .def_property_readonly("select_ms", [](const PyTopResult& p) { return p.t.select_ms; })
       .def_property_readonly("wire_bytes", [](const PyTopResult& p) { return p.t.wire_bytes; },
                              "bytes the device wrote to host memory for the result");
-  py::class_<PyIndexResult>(m, "IndexResult")
+  py::class_<PyIndexResult>(m, "IndexResult", py::dynamic_attr())
       .def("entries", &PyIndexResult::entries)
       .def("postings", &PyIndexResult::postings)
       .def("postings_bytes", &PyIndexResult::postings_bytes)
@@ -1104,8 +1148,11 @@ PYBIND11_MODULE(_locust, m) {
            py::arg("exclude") = std::vector<std::vector<std::string>>(),
            py::arg("glob") = false, py::arg("ignore_case") = false, py::arg("show") = py::none(),
            py::arg("fuzzy") = false, py::arg("regex") = false, py::arg("tally") = py::none(),
+           py::arg("files") = std::vector<std::vector<u32>>(), py::arg("by_file") = 0,
            "The host evaluation of all/any queries (any[i]: query i's mode) over this index.")
       .def("times", &PyIndexResult::times)
+      .def("segments", [](const PyIndexResult& p) { return segment_rows(p.x.segment_table()); },
+           "The index's files: [(id, first_line, base, lines)].")
       .def("format", &PyIndexResult::format)
       .def_property_readonly("first_line", [](const PyIndexResult& p) { return p.x.first_line; })
       .def_property_readonly("num_lines", [](const PyIndexResult& p) { return p.x.words.num_lines; })
@@ -1118,7 +1165,7 @@ PYBIND11_MODULE(_locust, m) {
       .def_property_readonly("index_ms", [](const PyIndexResult& p) { return p.x.index_ms; })
       .def_property_readonly("wire_bytes", [](const PyIndexResult& p) { return p.x.wire_bytes; },
                              "bytes the device wrote to host memory for the result");
-  py::class_<PySearchResult>(m, "SearchResult")
+  py::class_<PySearchResult>(m, "SearchResult", py::dynamic_attr())
       .def("lines", &PySearchResult::lines, py::arg("i"))
       .def("hits", &PySearchResult::hits, "the number of lines of every query")
       .def("term_counts", &PySearchResult::term_counts, py::arg("i"))
@@ -1144,6 +1191,15 @@ PYBIND11_MODULE(_locust, m) {
       .def_property_readonly("show_ms", [](const PySearchResult& p) { return p.r.show_ms; })
       .def("tally", &PySearchResult::tally, py::arg("i"),
            "tally: query i's most frequent words, [(key bytes, count)]; without tally: empty")
+      .def("files", &PySearchResult::files, py::arg("i"),
+           "by_file: the file id of every line of lines(i); otherwise empty")
+      .def("local_lines", &PySearchResult::local_lines, py::arg("i"),
+           "by_file: the file-local number of every line of lines(i); otherwise empty")
+      .def("file_hits", &PySearchResult::file_hits, py::arg("i"),
+           "by_file / count_only: [(file id, lines)] of query i, ids ascending; otherwise empty")
+      .def_property_readonly("by_file", [](const PySearchResult& p) { return p.r.by_file; },
+                             "0: no answers by file; 1: by_file; 2: count_only")
+      .def_property_readonly("by_file_ms", [](const PySearchResult& p) { return p.r.by_file_ms; })
       .def("tally_words", &PySearchResult::tally_words,
            "tally: per query the words with count > 0 on its returned lines")
       .def("tally_tokens", &PySearchResult::tally_tokens,
@@ -1172,12 +1228,54 @@ PYBIND11_MODULE(_locust, m) {
       .def_property_readonly("walked", [](const PySearchResult& p) { return p.r.walked; },
                              "list elements the device's hit stage walked for the batch: the sum "
                              "of the queries' bounds (0: evaluated on the host)")
+      .def_property_readonly("restricted", [](const PySearchResult& p) { return p.r.restricted; },
+                             "hits the device's restrict stage removed under the batch's file "
+                             "sets (0: no file set, or evaluated on the host)")
+      .def("segments", [](const PySearchResult& p) {
+        IndexSegments t;
+        t.reset(p.r.first_line, p.r.num_lines);
+        if (!p.r.segments.empty()) t.segs = p.r.segments;
+        return segment_rows(t);
+      }, "The files the batch was answered under: [(id, first_line, base, lines)].")
       .def_property_readonly("merged", [](const PySearchResult& p) { return p.r.merged; },
                              "list elements the device merged for prefix terms")
       .def_property_readonly("wire_bytes", [](const PySearchResult& p) { return p.r.wire_bytes; },
                              "bytes the device wrote to host memory for the result");
   m.attr("kSearchMaxQueries") = kSearchMaxQueries;
   m.attr("kSearchMaxTerms") = kSearchMaxTerms;
+  m.attr("kCorpusMaxFiles") = kCorpusMaxFiles;
+  // engine.hpp "corpus": the table's arithmetic alone (tests): ops are ("append", lines,
+  // new_file) and ("drop", lines); returns per op the table as [(id, first_line, base, lines)]
+  // and, for a drop, the dropped files (an append: 0); all_steps = false: the last op's only
+  m.def("segment_ops", [](u64 first_line, u64 lines,
+                          const std::vector<std::tuple<std::string, u64, bool>>& ops,
+                          bool all_steps) {
+    IndexSegments t;
+    t.reset(first_line, lines);
+    std::vector<std::pair<std::vector<std::tuple<u32, u64, u64, u64>>, u64>> out;
+    if (all_steps || ops.empty()) out.emplace_back(segment_rows(t), 0);
+    for (const auto& op : ops) {
+      u64 gone = 0;
+      if (std::get<0>(op) == "append")
+        t.append(std::get<1>(op), std::get<2>(op));
+      else
+        gone = t.drop(std::get<1>(op));
+      if (all_steps || &op == &ops.back()) out.emplace_back(segment_rows(t), gone);
+    }
+    return out;
+  }, py::arg("first_line"), py::arg("lines"), py::arg("ops"), py::arg("all_steps") = true);
+  m.def("segment_locate", [](const std::vector<std::tuple<u32, u64, u64, u64>>& rows, u64 line) {
+    IndexSegments t;
+    u64 n = 0;
+    for (const auto& r : rows) {
+      t.segs.push_back(IndexSegment{std::get<0>(r), std::get<1>(r), std::get<2>(r)});
+      n += std::get<3>(r);
+    }
+    t.first_line = rows.empty() ? 0 : std::get<1>(rows[0]);
+    t.num_lines = n;
+    const size_t o = t.locate(line);
+    return py::make_tuple(t.segs[o].id, line - t.segs[o].first_line + t.segs[o].base);
+  }, py::arg("table"), py::arg("line"), "(id, local line) of a global line under a table");
   m.attr("kShowMaxBytes") = kShowMaxBytes;
   m.attr("kRankMaxEmits") = kRankMaxEmits;
   m.attr("kTopKMax") = kTopKMax;
@@ -1222,21 +1320,27 @@ PYBIND11_MODULE(_locust, m) {
            py::arg("exclude") = std::vector<std::vector<std::string>>(),
            py::arg("glob") = false, py::arg("ignore_case") = false, py::arg("show") = py::none(),
            py::arg("fuzzy") = false, py::arg("regex") = false, py::arg("tally") = py::none(),
+           py::arg("files") = std::vector<std::vector<u32>>(), py::arg("by_file") = 0,
            "WordCount of text, its index, and all/any queries answered on the device.")
       .def("run_search_text", &PyGpuEngine::run_search_text, py::arg("text"), py::arg("queries"),
            py::arg("any"), py::arg("first_line") = 0, py::arg("rank") = py::none(),
            py::arg("wildcard") = false, py::arg("within") = std::vector<u64>(),
            py::arg("exclude") = std::vector<std::vector<std::string>>(),
            py::arg("glob") = false, py::arg("ignore_case") = false, py::arg("show") = py::none(),
-           py::arg("fuzzy") = false, py::arg("regex") = false, py::arg("tally") = py::none())
+           py::arg("fuzzy") = false, py::arg("regex") = false, py::arg("tally") = py::none(),
+           py::arg("files") = std::vector<std::vector<u32>>(), py::arg("by_file") = 0)
       .def("search_resident", &PyGpuEngine::search_resident, py::arg("queries"), py::arg("any"),
            py::arg("rank") = py::none(), py::arg("wildcard") = false,
            py::arg("within") = std::vector<u64>(),
            py::arg("exclude") = std::vector<std::vector<std::string>>(),
            py::arg("glob") = false, py::arg("ignore_case") = false, py::arg("show") = py::none(),
            py::arg("fuzzy") = false, py::arg("regex") = false, py::arg("tally") = py::none(),
+           py::arg("files") = std::vector<std::vector<u32>>(), py::arg("by_file") = 0,
            "Another batch from the index the last run_index / run_search left on the device.")
+      .def("segments", &PyGpuEngine::segments,
+           "The resident index's files: [(id, first_line, base, lines)].")
       .def("append_index", &PyGpuEngine::append_index, py::arg("text"), py::arg("first_line"),
+           py::arg("new_file") = false,
            "One more block of whole lines into the resident index, merged on the device.")
       .def("drop_index", &PyGpuEngine::drop_index, py::arg("lines"),
            "The oldest `lines` lines out of the resident index, compacted on the device.")
@@ -1269,6 +1373,7 @@ PYBIND11_MODULE(_locust, m) {
       .def_readonly("index_ms", &IndexAppend::index_ms)
       .def_readonly("append_ms", &IndexAppend::append_ms)
       .def_readonly("store_bytes", &IndexAppend::store_bytes)
+      .def_readonly("files", &IndexAppend::files)
       .def("times", [](const IndexAppend& a) {
         py::dict d;
         d["h2d_ms"] = a.times.h2d_ms;
@@ -1288,6 +1393,7 @@ PYBIND11_MODULE(_locust, m) {
       .def_readonly("dropped_bytes", &IndexDrop::dropped_bytes)
       .def_readonly("dropped_overflow_lines", &IndexDrop::dropped_overflow_lines)
       .def_readonly("dropped_truncated", &IndexDrop::dropped_truncated)
+      .def_readonly("dropped_files", &IndexDrop::dropped_files)
       .def_readonly("first_line", &IndexDrop::first_line)
       .def_readonly("num_lines", &IndexDrop::num_lines)
       .def_readonly("num_tokens", &IndexDrop::num_tokens)
@@ -1300,10 +1406,10 @@ PYBIND11_MODULE(_locust, m) {
   }, py::arg("x"), py::arg("lines"), py::arg("overflow_lines") = 0, py::arg("truncated") = 0,
         "The index of x's text without its first `lines` lines (the dropped lines' statistics "
         "are the caller's to supply).");
-  m.def("merge_index", [](const PyIndexResult& a, const PyIndexResult& b) {
+  m.def("merge_index", [](const PyIndexResult& a, const PyIndexResult& b, bool new_file) {
     py::gil_scoped_release nogil;
-    return PyIndexResult{merge_index(a.x, b.x), a.cfg};
-  }, py::arg("a"), py::arg("b"),
+    return PyIndexResult{merge_index(a.x, b.x, new_file), a.cfg};
+  }, py::arg("a"), py::arg("b"), py::arg("new_file") = false,
         "The index of a's text followed by b's (b.first_line == a.first_line + a's lines).");
   // the host evaluation over an index and the text it was built from (every mode)
   m.def("search_index_text", [](const PyIndexResult& x, const std::string& text,
@@ -1312,13 +1418,14 @@ PYBIND11_MODULE(_locust, m) {
                                 const std::vector<u64>& within,
                                 const std::vector<std::vector<std::string>>& exclude, bool glob,
                                 bool ignore_case, const py::object& show, bool fuzzy, bool regex,
-                                const py::object& tally) {
+                                const py::object& tally,
+                        const std::vector<std::vector<u32>>& files, u32 by_file) {
     const std::vector<SearchQuery> q =
-        to_queries(x.cfg, queries, any, wildcard, within, exclude, glob, fuzzy, regex);
+        to_queries(x.cfg, queries, any, wildcard, within, exclude, glob, fuzzy, regex, files);
     const u64 k = to_rank(rank), n = to_show(show), tk = to_tally(tally);
     py::gil_scoped_release nogil;
     return PySearchResult{
-        search_index(x.x, as_input(text, x.x.first_line), q, x.cfg, k, ignore_case, n, tk)};
+        search_index(x.x, as_input(text, x.x.first_line), q, x.cfg, k, ignore_case, n, tk, by_file)};
   });
   m.def("split_blocks", [](const std::string& text, u64 block_bytes, u64 first_line) {
     std::vector<std::tuple<u64, u64, u64, u64>> out;
@@ -1335,18 +1442,20 @@ PYBIND11_MODULE(_locust, m) {
                              const std::vector<u64>& within,
                              const std::vector<std::vector<std::string>>& exclude, bool glob,
                         bool ignore_case, const py::object& show, bool fuzzy, bool regex,
-                        const py::object& tally) {
+                        const py::object& tally,
+                        const std::vector<std::vector<u32>>& files, u32 by_file) {
     CpuWordCount eng(cfg);
     return PySearchResult{eng.run_search(as_input(text, first_line),
-                                         to_queries(cfg, queries, any, wildcard, within, exclude, glob, fuzzy, regex),
+                                         to_queries(cfg, queries, any, wildcard, within, exclude, glob, fuzzy, regex, files),
                                          to_rank(rank), ignore_case, to_show(show),
-                                         to_tally(tally))};
+                                         to_tally(tally), by_file)};
   }, py::arg("cfg"), py::arg("text"), py::arg("queries"), py::arg("any"),
         py::arg("first_line") = 0, py::arg("rank") = py::none(), py::arg("wildcard") = false,
         py::arg("within") = std::vector<u64>(),
            py::arg("exclude") = std::vector<std::vector<std::string>>(),
            py::arg("glob") = false, py::arg("ignore_case") = false, py::arg("show") = py::none(),
-           py::arg("fuzzy") = false, py::arg("regex") = false, py::arg("tally") = py::none());
+           py::arg("fuzzy") = false, py::arg("regex") = false, py::arg("tally") = py::none(),
+           py::arg("files") = std::vector<std::vector<u32>>(), py::arg("by_file") = 0);
   m.def("make_search_expr", [](const JobConfig& cfg, const std::string& expr, bool wildcard,
                                bool glob, bool fuzzy, bool regex) {
     // engine.hpp "boolean expressions": the parsed query's parts (tests, tools)

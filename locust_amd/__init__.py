@@ -47,12 +47,14 @@ from .models.wordcount import (  # noqa: E402
     Engine,
     WordCount,
     index_file,
+    index_files,
     index_text,
     map_stage,
     merge_index,
     reduce_stage,
     run_multi,
     search_file,
+    search_files,
     search_text,
     split_blocks,
     top_words_file,
@@ -84,8 +86,10 @@ __all__ = [
     "top_words_file",
     "top_words_text",
     "index_file",
+    "index_files",
     "index_text",
     "search_file",
+    "search_files",
     "search_text",
     "merge_index",
     "trim_index",

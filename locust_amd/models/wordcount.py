@@ -35,6 +35,24 @@ def _search_exclude(exclude, n):
     return out
 
 
+def _search_files(files, n):
+    """One file set per query (``[]``: every file) from ``files``: ``None``, or a list with one
+    entry per query, each ``None`` or a list of file ids (``Engine.segments``)."""
+    if files is None:
+        return []
+    files = list(files)
+    if len(files) != n or any(isinstance(f, int) for f in files):
+        raise ValueError("search: files takes one entry per query, each None or a list of "
+                         "file ids")
+    return [[] if f is None else [int(i) for i in f] for f in files]
+
+
+def _by_file(by_file, count_only):
+    """The native entry points' by_file flag: 0 none, 1 by_file, 2 count_only (which implies
+    by_file)."""
+    return 2 if count_only else 1 if by_file else 0
+
+
 def _search_args(queries, mode, within=None, exclude=None):
     """(term lists, one mode flag per query: 0 all, 1 any, 2 phrase, 3 near, 4 expr, one window per
     query: 0 none, one list of exclusion terms per query or none at all) for the native search
@@ -83,7 +101,7 @@ def _search_args(queries, mode, within=None, exclude=None):
 
 def _index_search(self, queries, mode="all", rank=None, wildcard=False, within=None,
                   exclude=None, glob=False, ignore_case=False, show=None, fuzzy=False, regex=False,
-                  tally=None):
+                  tally=None, files=None, by_file=False, count_only=False):
     """All/any word queries over this index, evaluated on the host (``SearchResult``):
     ``queries``, ``mode``, ``rank``, ``within`` and ``exclude`` as ``Engine.run_search`` takes
     them, any number of queries.  A ``"phrase"`` query, and a ``"near"`` query of two or more
@@ -91,10 +109,12 @@ def _index_search(self, queries, mode="all", rank=None, wildcard=False, within=N
     (``Engine.run_search``, ``search_text``).  ``glob``, ``fuzzy`` and ``ignore_case`` as
     there.
     ``show=N`` is refused like a phrase: the shown lines come from the text.
-    ``tally=K`` is answered here too (``Engine.run_search``): the rule needs no text."""
+    ``tally=K`` is answered here too (``Engine.run_search``): the rule needs no text.
+    ``files`` as there, over this index's ``segments()``."""
     queries, flags, windows, exclude = _search_args(queries, mode, within, exclude)
     return self._search(queries, flags, rank, bool(wildcard), windows, exclude, bool(glob),
-                        bool(ignore_case), show, bool(fuzzy), bool(regex), tally)
+                        bool(ignore_case), show, bool(fuzzy), bool(regex), tally,
+                        _search_files(files, len(queries)), _by_file(by_file, count_only))
 
 
 _C.IndexResult.search = _index_search
@@ -141,7 +161,8 @@ class Engine:
 
     def run_search(self, text: bytes, queries, mode="all", first_line: int = 0, rank=None,
                    wildcard=False, within=None, exclude=None, glob=False, ignore_case=False,
-                   show=None, fuzzy=False, regex=False, tally=None):
+                   show=None, fuzzy=False, regex=False, tally=None, files=None, by_file=False,
+                   count_only=False):
         """WordCount of ``text``, its inverted index, and a batch of word queries answered
         from it (``SearchResult``).  ``queries`` is a list of term lists (1 to 8 byte-string
         terms each); ``mode`` is ``"all"`` (lines that hold every term), ``"any"`` (lines
@@ -241,46 +262,83 @@ class Engine:
         and the tokens of those lines.  Keys are counted as the index holds them (``To`` and
         ``to`` apart, under ``ignore_case`` too).  On the GPU the returned lines are tokenised,
         sorted and counted on the device (``tally_ms``; ``tallied`` pair words), and only the
-        winners cross PCIe."""
+        winners cross PCIe.
+
+        ``files`` gives file sets: a list with one entry per query, each ``None`` (every file)
+        or a list of distinct file ids in ascending order (``segments()``: ``run_search`` begins
+        file 0, ``append_index(text, new_file=True)`` the next).  A query then answers what it
+        answers without the set, intersected with the lines of those files
+        (``oracle.CORPUS_RULES`` states the rules): after exclusion, in every mode; a ranked
+        query's scores do not change, so its answer is the unrestricted ranking filtered to the
+        set and cut to ``K``.  An id that is not resident selects nothing.  On the GPU the hits
+        outside the sets are removed on the device before anything is sorted or scored;
+        ``restricted`` counts them.
+
+        ``by_file=True`` also answers by file: ``files(i)`` and ``local_lines(i)`` give, parallel
+        to ``lines(i)``, every returned line's file id and its number inside that file, and
+        ``file_hits(i)`` is ``[(id, count)]`` over the files with a returned line, ids ascending
+        (ranked: over the winners).  ``count_only=True`` implies it and returns the counts alone,
+        as ``grep -c`` does: ``lines(i)`` is empty, ``matches()`` and ``file_hits(i)`` are
+        filled, and on the GPU the lines never cross PCIe.  It is refused with ``rank``, ``show``
+        or ``tally``.  On the GPU the files are resolved and counted on the device behind the
+        search (``by_file_ms``)."""
         queries, flags, windows, exclude = _search_args(queries, mode, within, exclude)
+        files = _search_files(files, len(queries))
         if self.cpu:
             return _C.cpu_run_search(self.cfg, text, queries, flags, first_line, rank,
                                      bool(wildcard), windows, exclude, bool(glob),
-                                     bool(ignore_case), show, bool(fuzzy), bool(regex), tally)
+                                     bool(ignore_case), show, bool(fuzzy), bool(regex), tally,
+                                     files, _by_file(by_file, count_only))
         res = self._eng.run_search(text, queries, flags, first_line, rank, bool(wildcard),
                                    windows, exclude, bool(glob), bool(ignore_case), show,
-                                   bool(fuzzy), bool(regex), tally)
+                                   bool(fuzzy), bool(regex), tally, files,
+                                   _by_file(by_file, count_only))
         self._next_line = first_line + res.num_lines
         return res
 
     def search_resident(self, queries, mode="all", rank=None, wildcard=False, within=None,
                         exclude=None, glob=False, ignore_case=False, show=None, fuzzy=False,
-                        regex=False, tally=None):
+                        regex=False, tally=None, files=None, by_file=False, count_only=False):
         """Another batch from the index this engine's last job left on the device; that
         job must have been a ``run_index`` or a ``run_search`` (GPU engines only).  Every
         mode of ``run_search``: the job's text is resident too, so phrases and near queries
         are answered.  ``rank``, ``within``, ``exclude``, ``glob``, ``ignore_case``, ``show``,
-        ``fuzzy`` and ``tally`` as ``run_search`` takes them."""
+        ``fuzzy``, ``tally``, ``files``, ``by_file`` and ``count_only`` as ``run_search`` takes
+        them."""
         if self.cpu:
             raise _C.LocustError("search_resident needs a GPU engine: the CPU engine keeps "
                                  "no index (use run_index(text).search(...))")
         queries, flags, windows, exclude = _search_args(queries, mode, within, exclude)
         return self._eng.search_resident(queries, flags, rank, bool(wildcard), windows, exclude,
                                          bool(glob), bool(ignore_case), show, bool(fuzzy),
-                                         bool(regex), tally)
+                                         bool(regex), tally, _search_files(files, len(queries)),
+                                         _by_file(by_file, count_only))
 
-    def append_index(self, text: bytes):
+    def segments(self):
+        """The files of the index this engine holds on the device: ``[(id, first_line, base,
+        lines)]``, consecutive line ranges in order.  ``id`` numbers the files in the order they
+        were begun, ``first_line`` is the global number of the file's first resident line and
+        ``base`` that line's number inside the file (0 until a drop has cut into it): global
+        line ``l`` of the file is its line ``l - first_line + base`` (GPU engines only)."""
+        if self.cpu:
+            raise _C.LocustError("segments needs a GPU engine: the CPU engine keeps no index "
+                                 "(use IndexResult.segments())")
+        return self._eng.segments()
+
+    def append_index(self, text: bytes, new_file: bool = False):
         """One more block of whole lines into the index this engine holds on the device
         (``IndexAppend``): afterwards the resident index is the index of everything indexed and
         appended so far, one text after the other, and ``search_resident`` answers from it.
         The block's lines are numbered behind the resident ones; it is indexed in one pass of
         this engine and merged on the device.  Refused with the resident index intact: no
         resident index, a block larger than the engine's pass, a resident text that does not
-        end in a newline (GPU engines only)."""
+        end in a newline (GPU engines only).  ``new_file=True`` begins a file with the next id
+        at the block's first line (``segments()``); otherwise the block extends the last file.
+        At most 65536 files are resident at a time."""
         if self.cpu:
             raise _C.LocustError("append_index needs a GPU engine: the CPU engine keeps no "
                                  "index (use merge_index(a, b) on two IndexResults)")
-        res = self._eng.append_index(text, self._next_line)
+        res = self._eng.append_index(text, self._next_line, bool(new_file))
         self._next_line += res.block_lines
         return res
 
@@ -387,10 +445,11 @@ def top_words_file(path: str, k: int, line_start: int = -1, line_end: int = -1,
     return Engine(cfg, max(len(text), 1), max(nlines, 1)).run_top(text, k)
 
 
-def merge_index(a, b):
+def merge_index(a, b, new_file: bool = False):
     """The index of ``a``'s text followed by ``b``'s, from the two ``IndexResult`` alone: the
-    host twin of the device merge.  ``b.first_line`` must be ``a.first_line + a.num_lines``."""
-    return _C.merge_index(a, b)
+    host twin of the device merge.  ``b.first_line`` must be ``a.first_line + a.num_lines``.
+    ``new_file=True``: ``b`` begins a file of the merged index (``segments()``)."""
+    return _C.merge_index(a, b, bool(new_file))
 
 
 def trim_index(x, lines: int, overflow_lines: int = 0, truncated: int = 0):
@@ -495,7 +554,7 @@ def search_text(text: bytes, queries, mode="all", backend: str = "gpu", cfg=None
         queries, flags, windows, exclude = _search_args(queries, mode, within, exclude)
         return _C.search_index_text(x, text, queries, flags, rank, bool(wildcard), windows,
                                     exclude, bool(glob), bool(ignore_case), show, bool(fuzzy),
-                                    bool(regex), tally)
+                                    bool(regex), tally, [], 0)
     nlines = text.count(b"\n") + (1 if text and not text.endswith(b"\n") else 0)
     return Engine(cfg, max(len(text), 1), max(nlines, 1)).run_search(
         text, queries, mode, first_line, rank, wildcard, within, exclude, glob, ignore_case,
@@ -521,6 +580,102 @@ def search_file(path: str, queries, mode="all", line_start: int = -1, line_end: 
     return Engine(cfg, max(len(text), 1), max(nlines, 1)).run_search(
         text, queries, mode, first, rank, wildcard, within, exclude, glob, ignore_case, show,
         fuzzy, regex, tally)
+
+
+def _corpus_blocks(texts, block_bytes):
+    """The files' blocks in order, [(piece, lines, first_line, new_file)]: a file that lacks its
+    last newline gets one when another follows (the byte makes no new line), every file but the
+    first begins a segment, and a file is cut into line-aligned blocks when ``block_bytes`` is
+    given (an empty file is one empty block)."""
+    out, line = [], 0
+    for i, t in enumerate(texts):
+        if t and not t.endswith(b"\n") and i + 1 < len(texts):
+            t += b"\n"
+        nlines = t.count(b"\n") + (1 if t and not t.endswith(b"\n") else 0)
+        pieces = ([(t, nlines, line)] if block_bytes is None else _blocks(t, block_bytes, line))
+        for j, (piece, lines, first) in enumerate(pieces):
+            out.append((piece, lines, first, i > 0 and j == 0))
+        line += nlines
+    return out
+
+
+def _index_corpus(cfg, texts, block_bytes, keep_blocks):
+    """``_index_blocks`` over several files: (engine or None, the CPU backend's IndexResult or
+    None, the text the index covers)."""
+    if not texts:
+        raise ValueError("a corpus is one file or more")
+    if keep_blocks is not None and (block_bytes is None or keep_blocks < 1):
+        raise ValueError("keep_blocks needs block_bytes, and must be >= 1")
+    blocks = _corpus_blocks(texts, block_bytes)
+    oldest = 0
+    if cfg.backend == _C.Backend.cpu:
+        parts = [_C.cpu_run_index(cfg, blocks[0][0], 0)]
+        x = parts[0]
+        for b, (piece, _lines, first, new_file) in enumerate(blocks[1:], 1):
+            parts.append(_C.cpu_run_index(cfg, piece, first))
+            x = _C.merge_index(x, parts[b], new_file)
+            if keep_blocks is not None and b + 1 - oldest > keep_blocks:
+                x = _C.trim_index(x, blocks[oldest][1], parts[oldest].overflow_lines,
+                                  parts[oldest].truncated)
+                oldest += 1
+        return None, x, b"".join(b[0] for b in blocks[oldest:])
+    eng = Engine(cfg, max(max(len(b[0]) for b in blocks), 1), max(max(b[1] for b in blocks), 1))
+    eng.run_index(blocks[0][0], 0)
+    for b, (piece, _lines, _first, new_file) in enumerate(blocks[1:], 1):
+        eng.append_index(piece, new_file)
+        if keep_blocks is not None and b + 1 - oldest > keep_blocks:
+            eng.drop_index(blocks[oldest][1])
+            oldest += 1
+    return eng, None, b"".join(b[0] for b in blocks[oldest:])
+
+
+def _read_files(paths):
+    texts = []
+    for p in paths:
+        with open(p, "rb") as f:
+            texts.append(f.read())
+    return texts
+
+
+def index_files(paths, backend: str = "gpu", cfg=None, block_bytes=None, keep_blocks=None, **kw):
+    """One inverted index over several files (``IndexResult``): the first file is indexed and
+    the others appended, each beginning a file of the index (``segments()``), so lines are
+    numbered through the corpus.  A file that lacks its last newline gets one when another
+    follows.  ``block_bytes`` cuts every file into blocks and ``keep_blocks`` slides a window
+    over them, as ``index_text`` does.  The result carries ``paths``."""
+    cfg = cfg if cfg is not None else make_config(backend, **kw)
+    paths = list(paths)
+    eng, x, _text = _index_corpus(cfg, _read_files(paths), block_bytes, keep_blocks)
+    res = x if eng is None else eng.index_resident()
+    res.paths = paths
+    return res
+
+
+def search_files(paths, queries, mode="all", backend: str = "gpu", cfg=None, rank=None,
+                 wildcard=False, within=None, exclude=None, glob=False, ignore_case=False,
+                 show=None, fuzzy=False, regex=False, tally=None, block_bytes=None,
+                 keep_blocks=None, files=None, by_file=True, count_only=False, **kw):
+    """Word queries over several files in one index (``SearchResult``; ``index_files`` builds
+    it).  ``files`` restricts each query to some of the files, by their ids -- file ``i`` of
+    ``paths`` has id ``i`` -- as ``Engine.run_search`` takes them; the lines of the answer are
+    global, and ``segments()`` of the result gives each file's ``first_line`` and ``base``.
+    ``by_file`` (the default here) and ``count_only`` as ``Engine.run_search`` takes them.  The
+    result carries ``paths``."""
+    cfg = cfg if cfg is not None else make_config(backend, **kw)
+    paths = list(paths)
+    eng, x, text = _index_corpus(cfg, _read_files(paths), block_bytes, keep_blocks)
+    if eng is not None:
+        res = eng.search_resident(queries, mode, rank, wildcard, within, exclude, glob,
+                                  ignore_case, show, fuzzy, regex, tally, files, by_file,
+                                  count_only)
+    else:
+        queries, flags, windows, exclude = _search_args(queries, mode, within, exclude)
+        res = _C.search_index_text(x, text, queries, flags, rank, bool(wildcard), windows,
+                                   exclude, bool(glob), bool(ignore_case), show, bool(fuzzy),
+                                   bool(regex), tally, _search_files(files, len(queries)),
+                                   _by_file(by_file, count_only))
+    res.paths = paths
+    return res
 
 
 def map_stage(path: str, spill: str, line_start: int = -1, line_end: int = -1,

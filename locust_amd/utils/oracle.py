@@ -136,6 +136,140 @@ def format_index(entries, postings) -> bytes:
         for k, v, c in entries)
 
 
+CORPUS_RULES = """
+Several files in one index.  An index over the lines [F, F + N) is cut into S >= 1 segments,
+the files of a corpus: consecutive, possibly empty line ranges that cover [F, F + N) in order.
+A segment is (id, first_line, base, lines): id numbers the files in the order they were begun
+(the first text indexed is file 0; a dropped file never frees its id), first_line is the global
+number of the file's first line that is still in the index, base is that line's number inside
+the file (0 until lines of the file have been dropped), lines is how many of its lines the index
+holds.  A global line l belongs to the LAST segment with first_line <= l, so an empty file
+between two others owns no line; inside its file the line has the number l - first_line + base,
+counted from 0.
+
+Dropping the d oldest lines, 0 < d <= N, moves F to F + d.  The first segment that stays is the
+last one that begins at or before line F + d: it keeps its id, its first_line becomes F + d and
+its base grows by the lines it lost.  Every segment in front of it leaves the table, the empty
+ones too; the non-empty ones among them are the dropped files.  d == N therefore leaves the last
+file, empty, and a text appended without beginning a new file continues its numbering.  d == 0
+changes nothing.
+
+A file that lacks its last newline is given one before the next file begins; the byte makes no
+new line, so every file keeps its own numbering.
+
+File sets.  A query may name a set of file ids, distinct and ascending; no set means every file.
+Its matching set is what its mode answers -- all, any, phrase, near or expr, after the exclusion
+terms -- intersected with the lines whose segment's id is in the set.  An id that is not in the
+table selects nothing and is no error.  The set selects lines only: a ranked query's N and
+counts stay those of the whole index, so its answer is the unrestricted ranking filtered to the
+set and cut to K, and matches counts the restricted set.  A set whose ids are not strictly
+ascending is refused.
+
+Answers by file.  A batch may ask, beside each query's lines, for every returned line's file id
+and local number (``locate``), in the order of the lines (ranked: rank order), and per query for
+the files with at least one returned line, ids ascending, each with its number of returned lines
+(``by_file``); the counts of a query add up to its returned lines -- unranked every match, ranked
+the min(K, matches) winners.  Count only answers those counts and the matches alone, no line; it
+is refused together with a ranking, shown lines or a tally.
+"""
+
+CORPUS_MAX_FILES = 65536
+
+
+def segments_of(file_texts, first_line: int = 0, drop: int = 0):
+    """The table of a corpus (``CORPUS_RULES``): ``[(id, first_line, base, lines)]`` for the
+    files ``file_texts`` indexed one after the other from ``first_line``, after the ``drop``
+    oldest lines have been dropped.  Written from the files' own line counts; a file that lacks
+    its last newline counts that line."""
+    counts = [len(split_lines(t)) for t in file_texts]
+    if not counts:
+        raise ValueError("a corpus is one file or more")
+    total = sum(counts)
+    if not 0 <= drop <= total:
+        raise ValueError("drop takes 0 <= d <= %d lines" % total)
+    starts, at = [], first_line
+    for c in counts:
+        starts.append(at)
+        at += c
+    end = first_line + total
+    if drop == 0:
+        return [(i, starts[i], 0, counts[i]) for i in range(len(counts))]
+    cut = first_line + drop
+    keep = max(i for i in range(len(counts)) if starts[i] <= cut)
+    out = [(keep, cut, cut - starts[keep], starts[keep] + counts[keep] - cut)]
+    out += [(i, starts[i], 0, counts[i]) for i in range(keep + 1, len(counts))]
+    assert sum(r[3] for r in out) == end - cut
+    return out
+
+
+def append_segments(table, lines: int, new_file: bool = False):
+    """``table`` after ``lines`` more lines behind it (``CORPUS_RULES``): a new file with the
+    next id (one more than the last file's), or more lines of the last file."""
+    table = [tuple(s) for s in table]
+    if new_file:
+        if len(table) >= CORPUS_MAX_FILES:
+            raise ValueError("an index holds at most %d files" % CORPUS_MAX_FILES)
+        last = table[-1]
+        return table + [(last[0] + 1, last[1] + last[3], 0, lines)]
+    i, first, base, n = table[-1]
+    return table[:-1] + [(i, first, base, n + lines)]
+
+
+def drop_segments(table, d: int):
+    """``(table, dropped files)`` after the ``d`` oldest lines have left (``CORPUS_RULES``)."""
+    table = [tuple(s) for s in table]
+    total = sum(s[3] for s in table)
+    if not 0 <= d <= total:
+        raise ValueError("drop takes 0 <= d <= %d lines" % total)
+    if d == 0:
+        return table, 0
+    cut = table[0][1] + d
+    keep = max(j for j, s in enumerate(table) if s[1] <= cut)
+    i, first, base, n = table[keep]
+    gone = sum(1 for s in table[:keep] if s[3])
+    return [(i, cut, base + cut - first, first + n - cut)] + table[keep + 1:], gone
+
+
+def locate(table, line: int):
+    """``(id, local line)`` of global ``line`` under ``table`` (``CORPUS_RULES``): the last
+    segment that begins at or before it."""
+    at = None
+    for seg in table:
+        if seg[1] <= line:
+            at = seg
+    if at is None or line >= table[-1][1] + table[-1][3]:
+        raise ValueError("line %d outside the table's lines" % line)
+    return at[0], line - at[1] + at[2]
+
+
+def by_file(table, lines):
+    """``lines`` by file: ``(ids, locals, hits)`` -- parallel to ``lines`` the file id and local
+    number of each, and ``[(id, count)]`` ascending by id over the files with a line."""
+    where = [locate(table, l) for l in lines]
+    counts = {}
+    for i, _local in where:
+        counts[i] = counts.get(i, 0) + 1
+    return [w[0] for w in where], [w[1] for w in where], sorted(counts.items())
+
+
+def _check_files(files):
+    files = list(files)
+    if any(not isinstance(f, int) or isinstance(f, bool) or not 0 <= f < 1 << 32 for f in files) \
+            or any(a >= b for a, b in zip(files, files[1:])):
+        raise ValueError("a file set is distinct file ids in ascending order, not %r" % (files,))
+    return set(files)
+
+
+def in_files(table, lines, files):
+    """The ``lines`` whose file is in the set ``files`` (``CORPUS_RULES``; ``None``: all)."""
+    if files is None:
+        return list(lines)
+    if table is None:
+        raise ValueError("a file set needs the table (segments_of)")
+    want = _check_files(files)
+    return [l for l in lines if locate(table, l)[0] in want] if want else list(lines)
+
+
 MAX_SEARCH_TERMS = 8
 
 
@@ -687,8 +821,12 @@ def merged_elements(entries, queries, delims: bytes = DEFAULT_DELIMS, max_key: i
 
 def search(entries, postings, terms, mode: str = "all", delims: bytes = DEFAULT_DELIMS,
            max_key: int = 29, *, wildcard: bool = False, exclude=None, glob: bool = False,
-           ignore_case: bool = False, fuzzy: bool = False, regex: bool = False):
+           ignore_case: bool = False, fuzzy: bool = False, regex: bool = False, files=None,
+           table=None):
     """One all/any word query over an index: ``(lines, counts)``.
+
+    ``files`` / ``table``: the query's file set under the corpus's table (``CORPUS_RULES``):
+    the answer below, intersected with the lines of those files.
 
     ``entries`` and ``postings`` are ``index``'s output.  A query is 1 to 8 ``terms`` and a
     ``mode``.  A term is a non-empty byte string without NUL, newline or a byte of
@@ -712,6 +850,11 @@ def search(entries, postings, terms, mode: str = "all", delims: bytes = DEFAULT_
     if mode not in ("all", "any"):
         raise ValueError("mode must be 'all' or 'any'")
     terms = list(terms)
+    if files is not None:
+        lines, counts = search(entries, postings, terms, mode, delims, max_key,
+                               wildcard=wildcard, exclude=exclude, glob=glob,
+                               ignore_case=ignore_case, fuzzy=fuzzy, regex=regex)
+        return in_files(table, lines, files), counts
     if exclude is not None:
         exclude = _check_exclude(terms, exclude)
         lines, counts = search(entries, postings, terms, mode, delims, max_key,
@@ -746,8 +889,10 @@ def search(entries, postings, terms, mode: str = "all", delims: bytes = DEFAULT_
 
 def phrase(text: bytes, terms, delims: bytes = DEFAULT_DELIMS, emits: int = 20,
            max_key: int = 29, first_line: int = 0, *, wildcard: bool = False, exclude=None,
-           glob: bool = False, ignore_case: bool = False, fuzzy: bool = False, regex: bool = False):
-    """One phrase query over ``text``: ``(lines, counts)``, as ``search`` answers.
+           glob: bool = False, ignore_case: bool = False, fuzzy: bool = False, regex: bool = False,
+           files=None, table=None):
+    """One phrase query over ``text``: ``(lines, counts)``, as ``search`` answers
+    (``files`` / ``table`` too).
 
     `phrase` answers the lines on which the terms occur as consecutive tokens, in order.
     A line's token sequence is exactly what the word job emits for it, in order: the job's
@@ -774,6 +919,11 @@ def phrase(text: bytes, terms, delims: bytes = DEFAULT_DELIMS, emits: int = 20,
     above for ``terms`` alone minus the lines with an emitted token that matches an exclusion
     term, and ``counts`` lists the terms' counts first and then the exclusion terms'."""
     terms = list(terms)
+    if files is not None:
+        lines, counts = phrase(text, terms, delims, emits, max_key, first_line,
+                               wildcard=wildcard, exclude=exclude, glob=glob,
+                               ignore_case=ignore_case, fuzzy=fuzzy, regex=regex)
+        return in_files(table, lines, files), counts
     if exclude is not None:
         exclude = _check_exclude(terms, exclude)
         lines, counts = phrase(text, terms, delims, emits, max_key, first_line,
@@ -823,8 +973,10 @@ MAX_SEARCH_WITHIN = (1 << 32) - 1
 
 def near(text: bytes, terms, within: int, delims: bytes = DEFAULT_DELIMS, emits: int = 20,
          max_key: int = 29, first_line: int = 0, *, wildcard: bool = False, exclude=None,
-         glob: bool = False, ignore_case: bool = False, fuzzy: bool = False, regex: bool = False):
-    """One proximity query over ``text``: ``(lines, counts)``, as ``search`` answers.
+         glob: bool = False, ignore_case: bool = False, fuzzy: bool = False, regex: bool = False,
+         files=None, table=None):
+    """One proximity query over ``text``: ``(lines, counts)``, as ``search`` answers
+    (``files`` / ``table`` too).
 
     `near` answers the lines on which the terms occur within ``within`` = W tokens of one
     another, in any order; W is an integer with 1 <= W <= 2^32 - 1 (``ValueError``
@@ -848,6 +1000,11 @@ def near(text: bytes, terms, within: int, delims: bytes = DEFAULT_DELIMS, emits:
     above for ``terms`` alone minus the lines with an emitted token that matches an exclusion
     term, and ``counts`` lists the terms' counts first and then the exclusion terms'."""
     terms = list(terms)
+    if files is not None:
+        lines, counts = near(text, terms, within, delims, emits, max_key, first_line,
+                             wildcard=wildcard, exclude=exclude, glob=glob,
+                             ignore_case=ignore_case, fuzzy=fuzzy, regex=regex)
+        return in_files(table, lines, files), counts
     if exclude is not None:
         exclude = _check_exclude(terms, exclude)
         lines, counts = near(text, terms, within, delims, emits, max_key, first_line,
@@ -1078,15 +1235,17 @@ def _expr_lists(entries, postings, terms, delims, max_key, wildcard, glob, ignor
 
 def expr_search(entries, postings, expr: bytes, delims: bytes = DEFAULT_DELIMS,
                 max_key: int = 29, *, wildcard: bool = False, glob: bool = False,
-                ignore_case: bool = False, fuzzy: bool = False, regex: bool = False):
-    """One ``expr`` query over an index: ``(lines, counts, terms)`` (``EXPR_RULES``)."""
+                ignore_case: bool = False, fuzzy: bool = False, regex: bool = False,
+                files=None, table=None):
+    """One ``expr`` query over an index: ``(lines, counts, terms)`` (``EXPR_RULES``);
+    ``files`` / ``table``: its file set (``CORPUS_RULES``)."""
     tree, terms = expr_parse(expr, delims, max_key, wildcard=wildcard, glob=glob, fuzzy=fuzzy, regex=regex)
     lists = _expr_lists(entries, postings, terms, delims, max_key, wildcard, glob, ignore_case,
                         fuzzy, regex)
     sets = [set(l) for l in lists]
     lines = [line for line in sorted(set().union(*sets))
              if expr_holds(tree, {t for t, s in enumerate(sets) if line in s})]
-    return lines, [len(l) for l in lists], terms
+    return in_files(table, lines, files), [len(l) for l in lists], terms
 
 
 def expr_walked(entries, postings, expr: bytes, delims: bytes = DEFAULT_DELIMS,
@@ -1181,7 +1340,30 @@ def _tally_lines(tallies, n):
     return [format_tally(*t) for t in tallies]
 
 
-def format_search(queries, answers, *, exclude=None, tallies=None) -> bytes:
+def _file_lines(by_file, lines, scores=None, count=False):
+    """The CLI's ``--by-file`` lines of one query: per file of its lines, ids ascending,
+    ``  file: <path> \t hits: <n> \t lines: <local> ...`` (ranked: ``top:`` and
+    ``<local>:<score>`` in rank order; ``count``: the line ends behind its hits).  ``by_file``
+    is ``(table, paths)``, ``paths[id]`` the file's path."""
+    if by_file is None:
+        return b""
+    table, paths = by_file
+    ids, local, hits = globals()["by_file"](table, lines)
+    out = b""
+    for i, n in hits:
+        path = paths[i] if isinstance(paths[i], bytes) else paths[i].encode()
+        out += b"  file: %s \t hits: %d" % (path, n)
+        if not count:
+            out += b" \t top:" if scores is not None else b" \t lines:"
+            for j, l in enumerate(local):
+                if ids[j] == i:
+                    out += b" %d" % l + (b":%d" % scores[j] if scores is not None else b"")
+        out += b"\n"
+    return out
+
+
+def format_search(queries, answers, *, exclude=None, tallies=None, by_file=None,
+                  count=False) -> bytes:
     """The CLI's ``--search`` result lines: one per query, ``queries[i]`` its terms and
     ``answers[i]`` its lines (every line number after one space; none after "lines:" when
     the query has no hit).
@@ -1189,10 +1371,19 @@ def format_search(queries, answers, *, exclude=None, tallies=None) -> bytes:
     ``exclude``: one entry per query, ``None`` or its exclusion terms; a query with exclusion
     terms prints `` \t not: <terms joined by one space>`` between its text and ``hits:``
     (terms as they were asked: a prefix term with its star).
-    ``tallies``: one ``tally`` answer per query, printed under its line (``format_tally``)."""
+    ``tallies``: one ``tally`` answer per query, printed under its line (``format_tally``).
+    ``by_file=(table, paths)``: the CLI's ``--by-file`` lines under each query's line and above
+    its tally lines (``_file_lines``); ``count`` beside it: ``--count`` -- the query's line ends
+    behind its hits with `` \t files: <f>``, the file lines behind theirs."""
+    if count:
+        return b"".join(
+            b"print query: %s \t hits: %d \t files: %d\n"
+            % (q, len(a), len(globals()["by_file"](by_file[0], a)[2])) +
+            _file_lines(by_file, a, count=True)
+            for q, a in zip(_query_text(queries, exclude), answers))
     return b"".join(
         b"print query: %s \t hits: %d \t lines:%s\n"
-        % (q, len(a), b"".join(b" %d" % l for l in a)) + t
+        % (q, len(a), b"".join(b" %d" % l for l in a)) + _file_lines(by_file, a) + t
         for q, a, t in zip(_query_text(queries, exclude), answers,
                            _tally_lines(tallies, len(queries))))
 
@@ -1202,8 +1393,13 @@ RANK_MAX_EMITS = 65536
 
 def rank(entries, postings, lines, terms, k: int, max_key: int = 29, *,
          wildcard: bool = False, delims: bytes = DEFAULT_DELIMS, exclude=None,
-         glob: bool = False, ignore_case: bool = False, fuzzy: bool = False, regex: bool = False, emits=None):
+         glob: bool = False, ignore_case: bool = False, fuzzy: bool = False, regex: bool = False, emits=None,
+         files=None, table=None):
     """The ranked answer of one query: ``(top, matches)``.
+
+    ``files`` / ``table``: the query's file set (``CORPUS_RULES``).  The matching set is
+    ``lines`` (before or after the set was applied) intersected with the set's lines; N and the
+    counts, and so every score, stay those of the whole index.
 
     ``lines`` is the query's matching set, as ``search`` or ``phrase`` answered it; ranking
     never changes which lines match, only their order and how many are returned.  N is
@@ -1234,6 +1430,7 @@ def rank(entries, postings, lines, terms, k: int, max_key: int = 29, *,
     or an eighth of it for a query with a pattern term (``ValueError``)."""
     if k < 1:
         raise ValueError("rank takes k >= 1")
+    lines = in_files(table, lines, files)
     if emits is not None:
         pat = any(t.scattered for t in query_terms(
             list(terms) + list(exclude or []), wildcard, glob, ignore_case, delims, max_key,
@@ -1288,14 +1485,15 @@ def rank(entries, postings, lines, terms, k: int, max_key: int = 29, *,
     return [(line, score) for score, line in scored[:k]], len(lines)
 
 
-def format_ranked(queries, tops, matches, *, exclude=None, tallies=None) -> bytes:
+def format_ranked(queries, tops, matches, *, exclude=None, tallies=None, by_file=None) -> bytes:
     """The CLI's ``--search ... --rank K`` result lines: one per query, ``queries[i]`` its
     terms, ``tops[i]`` its ``(line, score)`` pairs and ``matches[i]`` its number of matching
     lines (nothing after "top:" when nothing matched).  ``exclude`` and ``tallies`` as
-    ``format_search`` takes them."""
+    ``format_search`` takes them; ``by_file=(table, paths)`` too, over the winners."""
     return b"".join(
         b"print query: %s \t hits: %d \t top:%s\n"
-        % (q, m, b"".join(b" %d:%d" % (l, s) for l, s in t)) + ta
+        % (q, m, b"".join(b" %d:%d" % (l, s) for l, s in t)) +
+        _file_lines(by_file, [l for l, _s in t], [s for _l, s in t]) + ta
         for q, t, m, ta in zip(_query_text(queries, exclude), tops, matches,
                                _tally_lines(tallies, len(queries))))
 
